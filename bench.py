@@ -23,9 +23,13 @@ shard across GPUs with no data-path collective because the open-loop stages read
 --publish each rank additionally broadcasts one reconstructed reference picture per step on a side stream).  It is the fps
 of the hot-path stages, NOT of a whole encode: mode decision / entropy coding stay on the host.
 
-The JSON line also carries `roofline` (dominant kernel), `roofline_all` (ME, transform per size, in-loop filters), HBM traffic
-measured in this run by rocprofv3 PMC passes over a child process, and `cpu_baseline` (the reference's own C and AVX2
-kernels on the host cores + the reference encoder's fps).
+A plain run sets up, warms up, times the K steps and prints the JSON line: `value`, `ms_per_step` (wall time of one timed
+step), `roofline` (dominant kernel) and `roofline_all` for the ME and transform launches, from events of the timed steps.
+--full adds everything that takes runs of its own: the in-loop-filter, temporal-filter and TPL stage entries of
+`roofline_all`, HBM traffic measured by rocprofv3 PMC passes over a child process, and `cpu_baseline` (the reference's own C
+and AVX2 kernels on the host cores + the reference encoder's fps); --no-pmc / --no-lf / --no-cpu-baseline drop parts of it.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64; a fixed, seeded sample of
+every large array; the inputs are seeded, so two builds compare output for output).
 --workload me1080 | txfm | lf keep the round-1 kernel-level measurements (configs[1], [2], [3]).
 """
 import argparse
@@ -40,6 +44,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import zlib
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -273,12 +278,14 @@ class TxfmWorkload:
         # 4 % full 10-bit range, 1 % flat +-1023 cells: the last two push the row pass past the 24-bit-multiply limits of
         # txfm_device.hpp FWD_FAST_LIMIT so that both the `Fast` and the `Exact` arithmetic paths run)
         descs = {s: [] for s in sizes}
+        self.recon_spans, self.qcoeff_spans, self.dqcoeff_spans = [], [], []     # (byte offset, bytes) in the arena, for --dump-outputs
         for f in range(F):
             base = base0 + f * pic_bytes
             po = []                                 # per plane: (residual, pred, recon) byte offsets
             o2 = base
             for p in range(3):
                 po.append((o2, o2 + plane_px[p] * 2, o2 + plane_px[p] * 4))
+                self.recon_spans.append((o2 + plane_px[p] * 4, plane_px[p] * 2))
                 o2 += plane_px[p] * 6
             for p in range(3):
                 cells = torch.rand((ph[p] + 63) // 64, (pw[p] + 63) // 64, device=dev, generator=g)
@@ -306,6 +313,8 @@ class TxfmWorkload:
                 d["pred_off"], d["recon_off"], d["pred_stride"], d["recon_stride"] = po[p][1] + pix, po[p][2] + pix, pw[p], pw[p]
                 d["coeff_off"] = abi.NO_OFFSET
                 d["qcoeff_off"], d["dqcoeff_off"] = qoff + i * (n * 4), qoff + nblk * n * 4 + i * (n * 4)
+                self.qcoeff_spans.append((qoff, nblk * n * 4))
+                self.dqcoeff_spans.append((qoff + nblk * n * 4, nblk * n * 4))
                 qoff += nblk * n * 8
                 d["iscan_off"], d["qm_off"], d["iqm_off"] = self.iscan_off[min(w, 32)], abi.NO_OFFSET, abi.NO_OFFSET
                 for k, v in QUANT.items():
@@ -703,6 +712,85 @@ def roof(kernel, alg_bytes, ms, traffic=None, **extra):
     return d
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed, as float32 (8/16-bit data) / float64 (32/64-bit data) .npy files.  An
+# output of more than DUMP_SAMPLE elements is sampled at fixed positions (seeded by its name and size), gathered on the device.
+# ---------------------------------------------------------------------------------------------------------------------
+DUMP_SAMPLE = 1 << 18
+DUMP_LIMIT = 64 << 20                    # bytes of array data in all
+TORCH_INT = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def sample_positions(name, n):
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng([zlib.crc32(name.encode()), n])
+    return np.sort(rng.choice(n, DUMP_SAMPLE, replace=False)).astype(np.int64)
+
+
+def gather_output(name, parts, dtype):
+    """`parts` = [(byte tensor on the device, byte offset, bytes)] read back to back as one array of integer `dtype`."""
+    it = np.dtype(dtype).itemsize
+    counts = np.array([nb // it for _, _, nb in parts], dtype=np.int64)
+    ends = np.cumsum(counts)
+    pos = sample_positions(name, int(ends[-1]))
+    seg = np.searchsorted(ends, pos, side="right")
+    out = []
+    for j, (t, off, nb) in enumerate(parts):
+        sel = pos[seg == j] - (ends[j] - counts[j])
+        if len(sel):
+            assert off % it == 0 and nb % it == 0 and t.numel() % it == 0
+            idx = torch.from_numpy(sel + off // it).to(t.device)
+            out.append(t.reshape(-1).view(TORCH_INT[it]).index_select(0, idx).cpu().numpy().view(dtype))
+    return np.concatenate(out)
+
+
+def gather_records(name, tensors, struct):
+    """Arrays of a ctypes structure (one device byte tensor per picture / launch) -> {field: sampled values}."""
+    rec = np.concatenate([t.cpu().numpy().view(np.dtype(struct)) for t in tensors])
+    rec = rec[sample_positions(name, len(rec))]
+    return {f: rec[f] for f, _ in struct._fields_ if not f.startswith("pad")}
+
+
+def me_workload_outputs(mw):
+    """Open-loop analysis (pyramids, variance, mean of every picture of the clip) and ME results of the F pictures."""
+    out = {}
+    for lvl in ("quarter", "sixteenth"):
+        out[f"pyramid_{lvl}"] = gather_output(f"pyramid_{lvl}", [(getattr(d, lvl).t, 0, getattr(d, lvl).h.nbytes) for d in mw.dpyr], np.uint8)
+    for key, t, dt in (("analysis_variance", mw.var_out, np.uint16), ("analysis_mean", mw.mean_out, np.uint64)):
+        row = t.shape[1]
+        out[key] = gather_output(key, [(t, i * row, row) for i in range(mw.n_clip)], dt)
+    for k, (dt, _) in frames.me_out_shapes(mw.prm_for(mw.lead)[0], mw.nb).items():
+        name = k if k.startswith("me_") else "me_" + k
+        if k == "search_results":
+            for f, v in gather_records(name, [o[k] for o in mw.outs], abi.MeSearchResult).items():
+                out[f"me_search_{f}"] = v
+        else:
+            out[name] = gather_output(name, [(o[k], 0, o[k].numel()) for o in mw.outs], dt)
+    return out
+
+
+def txfm_workload_outputs(tw):
+    """Reconstruction of every plane, quantised and dequantised coefficients, and the per-block results of each launch."""
+    out = {"txfm_recon": gather_output("txfm_recon", [(tw.arena, o, nb) for o, nb in tw.recon_spans], np.uint16),
+           "txfm_qcoeff": gather_output("txfm_qcoeff", [(tw.arena, o, nb) for o, nb in tw.qcoeff_spans], np.int32),
+           "txfm_dqcoeff": gather_output("txfm_dqcoeff", [(tw.arena, o, nb) for o, nb in tw.dqcoeff_spans], np.int32)}
+    for s, L in tw.launches.items():
+        for f, v in gather_records(f"txfm{s[0]}x{s[1]}_result", [L["d_res"]], abi.TxfmResult).items():
+            out[f"txfm{s[0]}x{s[1]}_{f}"] = v
+    return out
+
+
+def dump_outputs(path, arrays):
+    arrays = {k: v.astype(np.float32 if v.dtype.itemsize <= 2 else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes > {DUMP_LIMIT}"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    progress(f"{len(arrays)} outputs of the last timed step ({total / 2**20:.1f} MiB) written to {path}")
+
+
 def lf_stage_rooflines(lib, dev, args, sp, stream, rank):
     """In-loop filters on one synthetic 4K 10-bit 4:2:0 picture (configs[3] kernel-level): per-stage time and algorithmic GB/s."""
     from benchlib import lf_inputs as LB
@@ -925,6 +1013,9 @@ def headline(lib, dev, args, world, rank, local_rank, rehearsal, traffic, traffi
     ms = {k: float(np.mean([a.elapsed_time(b) for a, b in ev[k]])) for k in ev}
     if rank != 0:
         return
+    if args.dump_outputs:                           # before the stage measurements, which reuse the workload's pictures
+        dump_outputs(args.dump_outputs, dict(me_workload_outputs(mw), **txfm_workload_outputs(tw)))
+
     def attach(r, key, kernel):
         """measured HBM traffic and the vector-issue estimate of one roofline entry (from the PMC child passes)"""
         t = traffic.get(key) or {}
@@ -942,7 +1033,7 @@ def headline(lib, dev, args, world, rank, local_rank, rehearsal, traffic, traffi
                              f"txfm{s[0]}", f"txfm_kernel<{s[0]}, {s[1]}>"))
     tx_ms = sum(ms[s] for s in sizes)
     tx_alg = sum(tw.launches[s]["alg_bytes"] for s in sizes)
-    if not args.no_lf:
+    if args.full and not args.no_lf:
         progress("stage measurements (in-loop filters, temporal filter, TPL dispenser)")
         # the dominant kernel of a multi-kernel entry prices its instructions
         dom = {"dlf": "dlf_pass_kernel<1>", "cdef_search": "cdef_search_kernel", "cdef_apply": "cdef_apply_frame_kernel", "sgr_filter": "sgr_filter_kernel<0>",
@@ -980,7 +1071,7 @@ def headline(lib, dev, args, world, rank, local_rank, rehearsal, traffic, traffi
                          "txfm_only_frac": round(tx_alg / (tx_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
         "traffic_note": traffic_note,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         progress("CPU baselines (reference kernels on the host cores, then the reference encoder)")
         line["cpu_baseline"] = cpu_baseline_headline(mw, W, H)
     progress("done")
@@ -1025,9 +1116,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=None, help="pictures per step and rank (default 16; me1080: 16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC child passes (roofline.traffic = null)")
-    ap.add_argument("--no-lf", action="store_true", help="skip the in-loop-filter stage measurements of roofline_all")
+    ap.add_argument("--full", action="store_true",
+                    help="4k10: also the stage measurements of roofline_all (in-loop filters, temporal filter, TPL), the rocprofv3 PMC traffic "
+                         "passes and the CPU baselines (default: only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (4k10 and me1080 workloads)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the rocprofv3 PMC child passes (roofline.traffic = null)")
+    ap.add_argument("--no-lf", action="store_true", help="--full without the stage measurements of roofline_all")
     ap.add_argument("--no-publish", dest="publish", action="store_false",
                     help="N > 1: do not broadcast a reconstructed reference picture per step (default: one RCCL broadcast per step on a side stream)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
@@ -1040,6 +1136,12 @@ def main():
         args.workload = "me1080"
     if args.frames is None:
         args.frames = 16
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload not in ("4k10", "me1080"):
+        ap.error("--dump-outputs: the 4k10 and me1080 workloads only")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process becomes the launcher.  It has not touched the GPU (nothing
@@ -1054,8 +1156,8 @@ def main():
     launch_only = os.environ.get("SVTAV1_BENCH_REHEARSAL") == "launch"
 
     # HBM traffic first, while this process has not touched the GPU yet (the profiled child is a separate program)
-    traffic, traffic_note = {}, "not measured (--no-pmc, a multi-rank run, or a workload other than 4k10)"
-    if args.workload == "4k10" and world == 1 and not args.no_pmc and not args.pmc_child and not launch_only:
+    traffic, traffic_note = {}, "not measured (a run without --full, --no-pmc, a multi-rank run, or a workload other than 4k10)"
+    if args.full and args.workload == "4k10" and world == 1 and not args.no_pmc and not args.pmc_child and not launch_only:
         child = ["--steps", "2", "--warmup", "1", "--frames", str(args.frames), "--no-cpu-baseline"] + (["--no-lf"] if args.no_lf else [])
         traffic, traffic_note = measure_traffic(child, pmc_groups())
 
@@ -1132,6 +1234,8 @@ def bench_me1080(lib, dev, args, world, rank, rehearsal):
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, "cpu" if rehearsal else dev)
     me_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, me_workload_outputs(mw))
         print(json.dumps({
             "metric": METRIC, "value": round(F * world * args.steps / elapsed, 2), "unit": "fps",
             "value_scope": "fps of the open-loop analysis hot path (pyramid + variance + full per-b64 ME) at 1080p, not of a whole encode",

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-end measurement on the GPU box (from the repo root):  bash tools/final_profiles.sh <round-tag>   -> gpurun_out/final/*
-#   <tag>_bench_4k10.json             the default `python bench.py` line (headline: 4K 10-bit preset 8; live PMC traffic + issue counters
+#   <tag>_bench_4k10.json             the `python bench.py --full` line (headline: 4K 10-bit preset 8; live PMC traffic + issue counters
 #                                     for every roofline_all entry, CPU baselines, the encoder-level runs)
 #   <tag>_rocprof_kernel_stats.csv    rocprofv3 --kernel-trace --stats of the same command (without its PMC / CPU legs)
 #   <tag>_bench_1080p_me.json         configs[1] for comparison with round 1
@@ -14,7 +14,7 @@ REPO=$PWD
 TAG=${1:-r03}
 OUT=$REPO/gpurun_out/final
 mkdir -p $OUT
-python3 bench.py > $OUT/${TAG}_bench_4k10.json 2> $OUT/bench_4k10.err
+python3 bench.py --full > $OUT/${TAG}_bench_4k10.json 2> $OUT/bench_4k10.err
 echo "headline bench done"
 python3 bench.py --workload me1080 --no-cpu-baseline > $OUT/${TAG}_bench_1080p_me.json 2> $OUT/bench_me1080.err || echo "me1080 failed"
 echo "1080p bench done"
@@ -22,7 +22,7 @@ SVTAV1_BENCH_REHEARSAL=1 python3 bench.py --gpus 2 --steps 5 --warmup 2 --no-pmc
 echo "gpus2 rehearsal done"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kt_head
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_head -- python3 $REPO/bench.py --steps 20 --warmup 3 --no-pmc --no-cpu-baseline > $OUT/kt_head.log 2>&1 || echo "kernel-trace failed"
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_head -- python3 $REPO/bench.py --full --steps 20 --warmup 3 --no-pmc --no-cpu-baseline > $OUT/kt_head.log 2>&1 || echo "kernel-trace failed"
 f=$(find /tmp/kt_head -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp $f $OUT/${TAG}_rocprof_kernel_stats.csv
 echo "kernel stats done"

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 while [ $# -ge 2 ]; do
   tag=$1; export SVTAV1_HIP_LIB=$REPO/$2; shift 2
   rm -rf /tmp/kt_$tag
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$tag -- python3 $REPO/bench.py --steps 3 --warmup 1 --no-pmc --no-cpu-baseline > $REPO/gpurun_out/r2/kt_$tag.log 2>&1 || echo "failed"
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$tag -- python3 $REPO/bench.py --full --steps 3 --warmup 1 --no-pmc --no-cpu-baseline > /tmp/kt_$tag.log 2>&1 || echo "failed"
   f=$(find /tmp/kt_$tag -name "*kernel_stats.csv" | head -1)
   python3 - "$f" "$tag" <<'PY'
 import csv, sys

@@ -5,7 +5,7 @@ REPO=$PWD
 mkdir -p $REPO/gpurun_out/r2
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmcst
-rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES --kernel-include-regex "${PMC_STAGE_REGEX:-tf_|tpl_}" --kernel-trace --output-format csv -d /tmp/pmcst -- python3 $REPO/bench.py --steps 2 --warmup 1 --no-pmc --no-cpu-baseline > $REPO/gpurun_out/r2/pmcst_run.log 2>&1 || { echo "pass failed"; tail -5 /tmp/pmcst.log; }
+rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES --kernel-include-regex "${PMC_STAGE_REGEX:-tf_|tpl_}" --kernel-trace --output-format csv -d /tmp/pmcst -- python3 $REPO/bench.py --full --steps 2 --warmup 1 --no-pmc --no-cpu-baseline > /tmp/pmcst_run.log 2>&1 || { echo "pass failed"; tail -5 /tmp/pmcst_run.log; }
 python3 - "$REPO/gpurun_out/r2/pmc_stage.json" <<'PY'
 import csv, glob, json, sys
 from collections import defaultdict
