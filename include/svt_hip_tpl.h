@@ -25,8 +25,8 @@
  * XCD's L2), waiting for those stores and then setting its flags; this needs 4-byte aligned reconstruction rows (stride and sample
  * (0,0) address multiples of 4), otherwise — or with SVTAV1_HIP_TPL_FENCE set in the environment — a device-scope release fence per
  * block (an L2 write-back, about three times slower) does it.
- * Not provided: the other intra modes and the SATD source search (tpl levels 1, 2), 64x64 dispenser blocks, subsample_tx 1, the
- * rate estimate.
+ * Not provided: the other intra modes and the SATD source search (tpl levels 1, 2) — the intra part of that search is
+ * svt_hip_intra_search_frames (svt_hip_intra.h), not yet called from here —, 64x64 dispenser blocks, subsample_tx 1, the rate estimate.
  */
 #ifndef SVT_HIP_TPL_H
 #define SVT_HIP_TPL_H

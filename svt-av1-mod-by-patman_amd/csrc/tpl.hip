@@ -20,6 +20,7 @@
 
 #include "../../include/svt_hip_tpl.h"
 #include "common.hpp"
+#include "intra_device.hpp"
 #include "txfm_block.hpp"
 
 using namespace svthip;
@@ -58,48 +59,7 @@ __device__ __forceinline__ int64_t wave_sum64(int64_t v) {
     return v;
 }
 
-// svt_aom_update_neighbor_samples_array_open_loop_mb[_recon] (enc_intra_prediction.c:1127-1300) for a BS x BS block with
-// use_top_right_bottom_left = update_top_neighbor = 1; above_ref / left_ref point at the [-1] entries.  One lane.
-template <uint32_t BS>
-__device__ void neighbours(uint8_t *above_ref, uint8_t *left_ref, const uint8_t *pic0, uint32_t stride, uint32_t x, uint32_t y, uint32_t width,
-                           uint32_t height) {
-    const uint32_t bw = BS, bh = BS, n = 2 * BS;
-    const uint8_t *src = pic0 + (size_t)y * stride + x;
-    for (uint32_t i = 0; i <= n; i++) above_ref[i] = 127, left_ref[i] = 129;
-    uint8_t *a = above_ref, *l = left_ref;
-    if (x != 0 && y != 0)
-        *a = *l = (uint8_t)ld8(src - stride - 1);
-    else
-        *a = *l = 128;
-    a++, l++;
-    uint32_t count = n;
-    if (x != 0) {
-        const uint8_t *rp = src - 1;
-        if (y == 0)
-            l[-1] = (uint8_t)ld8(rp);
-        count = (y + count > height) ? count - (y + count - height) : count;
-        for (uint32_t i = 0; i < count; i++, rp += stride) *l++ = (uint8_t)ld8(rp);
-        l += n - count;
-        for (uint32_t i = 0; i < bh; i++) l[-(int)bh + (int)i] = l[-(int)bh - 1];
-    } else if (y != 0) {
-        count = (y + count > height) ? count - (y + count - height) : count;
-        const uint8_t v = (uint8_t)ld8(src - stride);
-        for (uint32_t i = 0; i <= count; i++) l[(int)i - 1] = v;
-        a[-1] = v;
-    } else
-        l += count;
-    count = n;
-    if (y != 0) {
-        count = (x + count > width) ? count - (x + count - width) : count;
-        for (uint32_t i = 0; i < count; i++) a[i] = (uint8_t)ld8(src - stride + i);
-        if (x != 0)
-            for (uint32_t i = 0; i < bw; i++) a[bw + i] = a[bw - 1];
-    } else if (x != 0) {
-        count = (x + count > width) ? count - (x + count - width) : count;
-        const uint8_t v = *(l - count);
-        for (uint32_t i = 0; i <= count; i++) a[(int)i - 1] = v;
-    }
-}
+using intra::neighbours;  // the neighbour gather of the open-loop intra search (intra_device.hpp)
 
 // DC_PRED value of the block at (x, y) of plane pic0 (svt_aom_dc_pred[x > 0][y > 0][TX_16X16 / TX_32X32]); uniform over the wave
 constexpr int NB_LEFT = 8 + 88;  // offsets of the neighbour arrays in their LDS buffer: above[-1 .. 64], left[-1 .. 64]

@@ -146,6 +146,8 @@ def load():
         for n in ("svt_compute_sub_mean_8x8_hip", "svt_compute_mean_8x8_hip",
                   "svt_compute_mean_square_values_8x8_hip"):
             getattr(_lib, n).restype = C.c_uint64
+        _lib.svt_hip_intra_search_frames.restype = C.c_int32
+        _lib.svt_hip_intra_search_frames.argtypes = [C.POINTER(IntraSearchJob), C.c_uint32, C.c_void_p]
     return _lib
 
 
@@ -351,3 +353,20 @@ class MvCostParam(C.Structure):          # SvtHipMvCostParam == struct svt_mv_co
 class TxfmParam(C.Structure):            # SvtHipTxfmParam == TxfmParam (definitions.h:1051-1063)
     _fields_ = [("tx_type", C.c_uint8), ("tx_size", C.c_uint8), ("lossless", C.c_int32), ("bd", C.c_int32), ("is_hbd", C.c_int32),
                 ("tx_set_type", C.c_uint8), ("eob", C.c_int32)]
+
+
+# include/svt_hip_intra.h: PredictionMode DC_PRED .. PAETH_PRED, EB_TRANS_COEFF_SHAPE
+INTRA_MODES = 13
+DC_PRED, V_PRED, H_PRED, D45_PRED, D135_PRED, D113_PRED, D157_PRED, D203_PRED, D67_PRED, SMOOTH_PRED, SMOOTH_V_PRED, SMOOTH_H_PRED, \
+    PAETH_PRED = range(INTRA_MODES)
+DEFAULT_SHAPE, N2_SHAPE, N4_SHAPE = 0, 1, 2
+
+
+class IntraCtrls(C.Structure):           # SvtHipIntraCtrls
+    _fields_ = [("intra_mode_end", C.c_uint8), ("use_sad", C.c_uint8), ("pf_shape", C.c_uint8), ("subsample_tx", C.c_uint8),
+                ("max_input_luma_width", C.c_uint16), ("max_input_luma_height", C.c_uint16)]
+
+
+class IntraSearchJob(C.Structure):       # SvtHipIntraSearchJob
+    _fields_ = [("src", Plane8), ("ctrls", IntraCtrls), ("best_mode", C.c_void_p), ("best_cost", C.c_void_p),
+                ("mode_cost", C.c_void_p), ("pred", C.c_void_p)]

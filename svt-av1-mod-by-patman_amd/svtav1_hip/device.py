@@ -100,6 +100,40 @@ class DeviceMeOut:
         return {k: self.bufs[k].download(dt, shape) for k, (dt, shape) in self.shapes.items()}
 
 
+class DeviceIntraOut:
+    """Device output arrays of one picture's intra search (include/svt_hip_intra.h), pre-filled with `fill`; the per-mode costs and
+    predictions only with `all_modes`."""
+
+    def __init__(self, lib, width, height, all_modes=False, fill=0xA5):
+        cells = ((width + 15) // 16, (height + 15) // 16)
+        self.shape = (cells[1], cells[0])
+        self.shapes = {"best_mode": (np.uint8, self.shape), "best_cost": (np.int64, self.shape)}
+        if all_modes:
+            self.shapes["mode_cost"] = (np.int64, self.shape + (abi.INTRA_MODES,))
+            self.shapes["pred"] = (np.uint8, self.shape + (abi.INTRA_MODES, 16, 16))
+        self.bufs = {}
+        for name, (dt, shape) in self.shapes.items():
+            b = DeviceBuffer(lib, int(np.prod(shape)) * np.dtype(dt).itemsize)
+            b.fill(fill)
+            self.bufs[name] = b
+
+    def fill_job(self, job):
+        for name in ("best_mode", "best_cost", "mode_cost", "pred"):
+            setattr(job, name, self.bufs[name].ptr if name in self.bufs else None)
+        return job
+
+    def download(self):
+        return {k: self.bufs[k].download(dt, shape) for k, (dt, shape) in self.shapes.items()}
+
+
+def intra_search_frames(lib, jobs, stream=None, sync=True):
+    """svt_hip_intra_search_frames over a list of abi.IntraSearchJob (one launch)."""
+    arr = (abi.IntraSearchJob * len(jobs))(*jobs)
+    check(lib, lib.svt_hip_intra_search_frames(arr, C.c_uint32(len(jobs)), C.c_void_p(stream)), "svt_hip_intra_search_frames")
+    if sync:
+        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+
+
 def me_frames(lib, jobs, stream=None, sync=True):
     arr = (abi.MeFrameJob * len(jobs))(*jobs)
     check(lib, lib.svt_hip_me_frames(arr, C.c_uint32(len(jobs)), C.c_void_p(stream)), "svt_hip_me_frames")
