@@ -318,6 +318,8 @@ static void tf_block_of(const SvtHipTfPictureJob *job, int ox, int oy, int q, vo
 ORC_API int32_t orc_tf_filter_picture(const SvtHipTfPictureJob *job, SvtHipTfB64State *states, uint32_t *tot) {
     if (job->n_refs > SVT_HIP_TF_MAX_REFS || (job->bit_depth != 8 && job->bit_depth != 10))
         return -1;
+    if (job->ctrls.enable_8x8_pred && !(job->me.enable_me_16x16 && job->me.enable_me_8x8)) /* the 8x8 refinement starts from the ME's 8x8 vectors */
+        return -1;
     const SvtHipPlane8 *cf = &job->centre.pyr.full;
     const uint32_t W = cf->width, H = cf->height, bw = (W + 63) / 64, bh = (H + 63) / 64, nb = bw * bh;
     const int      is16 = job->bit_depth > 8;

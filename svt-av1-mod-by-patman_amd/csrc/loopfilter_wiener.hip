@@ -336,9 +336,10 @@ __global__ __launch_bounds__(256) void wiener_convolve_kernel(const void *__rest
 [[noreturn]] void fatal(const char *what) { svthip::tier_a_throw("%s: %s", what, svt_hip_last_error()); }
 inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
-struct AuxBuf {  // per-thread grow-only device buffer for the raw first moments
-    StatsAux *dev = nullptr;
-    size_t    cap = 0;
+struct AuxBuf {  // per-thread grow-only device buffer for the raw first moments, guarded by an event against reuse from another stream
+    StatsAux  *dev = nullptr;
+    size_t     cap = 0;
+    hipEvent_t ev  = nullptr;
 };
 
 }  // namespace
@@ -365,6 +366,8 @@ extern "C" int32_t svt_hip_wiener_stats(const SvtHipWienerUnit *units, uint32_t 
         return SVT_HIP_ERR_NO_DEVICE;
     hipStream_t                st = resolve_stream(stream);
     static thread_local AuxBuf ab;
+    if (!ab.ev)
+        SVT_HIP_CHECK(hipEventCreateWithFlags(&ab.ev, hipEventDisableTiming));
     if (n_units > ab.cap) {
         if (ab.dev) {
             SVT_HIP_CHECK(hipDeviceSynchronize());
@@ -377,6 +380,8 @@ extern "C" int32_t svt_hip_wiener_stats(const SvtHipWienerUnit *units, uint32_t 
     const SvtHipWienerUnit *d_units = (const SvtHipWienerUnit *)stage_descriptors(units, sizeof(SvtHipWienerUnit) * n_units, st);
     if (!d_units)
         return SVT_HIP_ERR_RUNTIME;
+    // the previous call of this thread may sit on another stream and still read ab.dev: the zero kernel waits for its finalize kernel
+    SVT_HIP_CHECK(hipStreamWaitEvent(st, ab.ev, 0));
     // the three sum arrays start from zero: one launch instead of three memsets (a launch costs more than it moves here)
     {
         const size_t nM = (size_t)W2MAX * n_units, nH = (size_t)W2MAX * W2MAX * n_units, nA = sizeof(StatsAux) / sizeof(long long) * n_units;
@@ -385,13 +390,12 @@ extern "C" int32_t svt_hip_wiener_stats(const SvtHipWienerUnit *units, uint32_t 
     // about one workgroup per slot of the GPU (two per CU at this kernel's register count): every unit gets the same number of
     // workgroups, each with a contiguous range of the unit's (chunk, tile) items.  int32 accumulators: products of two digits are below
     // or equal to 2^12 and a wave sees a quarter of its workgroup's samples: at most 512 items (2^20 samples, 2^18 per wave) per workgroup.
-    static int slots = 0;
-    if (!slots) {
+    static const int slots = [] {
         int cus = 0, dev = 0;
-        SVT_HIP_CHECK(hipGetDevice(&dev));
-        SVT_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        slots = 2 * (cus > 0 ? cus : 256);
-    }
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            cus = 0;
+        return 2 * (cus > 0 ? cus : 256);
+    }();
     const int gx = (max_w + TW - 1) / TW, gy = (max_h + TH - 1) / TH, items = gx * gy;
     int       k  = slots / (int)n_units > 1 ? slots / (int)n_units : 1;
     k            = k > items ? items : k;
@@ -405,6 +409,7 @@ extern "C" int32_t svt_hip_wiener_stats(const SvtHipWienerUnit *units, uint32_t 
     const int divider = is_16bit ? (bit_depth == 12 ? 16 : (bit_depth == 10 ? 4 : 1)) : 1;  // restoration_pick.c:719-723
     hipLaunchKernelGGL(wiener_finalize_kernel, dim3(n_units), dim3(256), 0, st, wiener_win, divider, (long long *)d_M, (long long *)d_H,
                        (const StatsAux *)ab.dev);
+    SVT_HIP_CHECK(hipEventRecord(ab.ev, st));
     stage_commit(st);
     SVT_HIP_CHECK(hipGetLastError());
     return SVT_HIP_OK;

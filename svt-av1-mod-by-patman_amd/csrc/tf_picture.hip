@@ -863,6 +863,8 @@ extern "C" int32_t svt_hip_tf_filter_picture(const SvtHipTfPictureJob *job, void
         return bad("bit_depth must be 8 or 10");
     if (job->ctrls.enable_8x8_pred > 1 || job->ctrls.low_delay > 1)
         return bad("enable_8x8_pred / low_delay are 0 or 1");
+    if (job->ctrls.enable_8x8_pred && !(job->me.enable_me_16x16 && job->me.enable_me_8x8))  // the 8x8 refinement starts from the ME's 8x8 vectors
+        return bad("enable_8x8_pred needs ME parameters with enable_me_16x16 and enable_me_8x8 (85 stored PUs)");
     if (job->ctrls.sub_sampling_shift > 1 || job->ctrls.use_2tap > 1)
         return bad("sub_sampling_shift / use_2tap out of range");
     if (!f.buf || f.width < 64 || f.height < 64 || f.org_x < 68 || f.org_y < 68 || (f.org_x & 1) || (f.org_y & 1))

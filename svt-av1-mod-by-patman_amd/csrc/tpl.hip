@@ -469,12 +469,16 @@ __device__ __forceinline__ void tpl_block(const TplArgs &a, const uint32_t x, co
             uint32_t *q = (uint32_t *)(o + 4 * k);
             __hip_atomic_store(q, __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // vmcnt(0): the write-through stores are acknowledged
-        __syncthreads();
     }
+    // every store of this wave is acknowledged before a flag is set, or a flag can overtake the samples it publishes.  A
+    // workgroup-scope release fence does not wait: the workgroup is one wave, and the compiler lowers that fence to nothing.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
     if (lane == 0) {
-        if (!a.coherent_rows)
+        if (!a.coherent_rows) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the write-back is done before the flags (explicit: the compiler may drop it)
+        }
         for (int k = 0; k < (BS / 16) * (BS / 16); k++) {
             const uint32_t fx = cx + (k & (BS / 16 - 1)), fy = cy + k / (BS / 16);
             if (fx < a.a16 && fy < a.rows16)

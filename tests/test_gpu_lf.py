@@ -255,8 +255,9 @@ class OrcLvl:
         return lvl.reshape(-1)
 
 
-@pytest.mark.parametrize("variant", list(range(8)) + [10])
-def test_tier_b_deblock_frame(hip, orc, variant):
+def deblock_inputs(variant):
+    """Seeded inputs of one deblocking frame: (planes, w, h, flat mode info, mi_stride, mi_rows, mi_cols, header, bd, is16, level
+    table, first plane, end plane)."""
     rng = np.random.default_rng(300 + variant)
     # variant 10: the configs[3] size, 3840 x 2160 10-bit (variant % 3 == 1), all three planes
     w, h = {**dict(enumerate(((200, 136), (328, 184), (64, 64), (136, 264), (196, 134), (322, 182), (1920, 1080), (130, 258)))),
@@ -288,8 +289,14 @@ def test_tier_b_deblock_frame(hip, orc, variant):
             flat["tx_size_y"][r, c] = sq[side]
             flat["tx_size_uv"][r, c] = sq[max(4, min(bw[b] // 2, bh[b] // 2, 32))]
     planes = L.lf_planes(rng, mi_cols * 4, mi_rows * 4, bd, is16)
-    p_orc = [p.copy() for p in planes]
     ps, pe = (0, 3) if variant != 4 else (1, 3)
+    return planes, w, h, flat, mi_stride, mi_rows, mi_cols, hdr, bd, is16, lvl, ps, pe
+
+
+@pytest.mark.parametrize("variant", list(range(8)) + [10])
+def test_tier_b_deblock_frame(hip, orc, variant):
+    planes, w, h, flat, mi_stride, mi_rows, mi_cols, hdr, bd, is16, lvl, ps, pe = deblock_inputs(variant)
+    p_orc = [p.copy() for p in planes]
     f = L.lf_frame(p_orc, w, h, flat.ctypes.data, mi_stride, mi_rows, mi_cols, hdr, bd, is16, ps, pe, lvl)
     orc.orc_loop_filter_frame(C.byref(f), 64)
     got = gpu_deblock(hip, planes, w, h, flat, mi_stride, mi_rows, mi_cols, hdr, bd, is16, lvl, ps, pe)

@@ -94,6 +94,12 @@ def test_argument_checks(hip, orc):
     job.ctrls.enable_8x8_pred = 2   # a flag: 0 or 1
     assert hip.svt_hip_tf_filter_picture(C.byref(job), None) == abi.SVT_HIP_ERR_BAD_PARAMETER
     assert b"8x8" in hip.svt_hip_last_error()
+    # 8x8 prediction refines the ME's 8x8 vectors: the ME must store all 85 PUs of a b64
+    for me16, me8 in ((1, 0), (0, 1), (0, 0)):
+        job.ctrls.enable_8x8_pred, job.me.enable_me_16x16, job.me.enable_me_8x8 = 1, me16, me8
+        assert hip.svt_hip_tf_filter_picture(C.byref(job), None) == abi.SVT_HIP_ERR_BAD_PARAMETER, (me16, me8)
+        assert b"8x8" in hip.svt_hip_last_error()
+    job.me.enable_me_16x16 = job.me.enable_me_8x8 = 1
     job.ctrls.enable_8x8_pred, job.n_refs = 0, 0
     assert hip.svt_hip_tf_filter_picture(C.byref(job), None) == abi.SVT_HIP_ERR_BAD_PARAMETER
     job.n_refs, job.bit_depth = n_refs, 12
@@ -127,7 +133,8 @@ def test_filter_picture_4k(hip, orc):
 
 
 @pytest.mark.parametrize("case", [
-    ("blocks_8x8_4k", "blocks", 3840, 2160, 1, 8, "m8_4k_tl2", dict(tpc.LVL1, enable_8x8_pred=1)),
+    # the m8 4K preset stores 21 PUs per b64; 8x8 prediction needs all 85 (svt_hip_tf_filter_picture refuses it otherwise)
+    ("blocks_8x8_me8x8_4k", "blocks", 3840, 2160, 1, 8, "m8_4k_tl2", dict(tpc.LVL1, enable_8x8_pred=1, me=dict(enable_me_8x8=1))),
     ("fastpan_ld_4k_10bit", "fastpan", 3840, 2160, 2, 10, "m8_4k_tl2", dict(tpc.LVL8, low_delay=1, chroma=1)),
 ], ids=lambda c: c[0])
 def test_filter_picture_variants_4k(hip, orc, case):

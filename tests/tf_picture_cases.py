@@ -142,6 +142,8 @@ def make_job(pics, w, h, bd, key, ctl, decay=(0, 0, 0), ptrs=None):
     job = abi.TfPictureJob()
     prm = me_cases.scenario_params(key, 1, [0], [], 0, 1)
     prm.me_mctf, prm.tf_me_exit_th, prm.hme_search_method = 1, ctl["me_exit_th"], 1
+    for k, v in ctl.get("me", {}).items():   # ME parameters that differ from the preset's
+        setattr(prm, k, v)
     job.me = prm
     for k in ("half_pel_mode", "quarter_pel_mode", "eight_pel_mode", "use_2tap", "sub_sampling_shift", "use_pred_64x64_only_th",
               "subpel_early_exit_th", "use_8bit_subpel", "pred_error_32x32_th"):

@@ -87,3 +87,88 @@ def orc_quant(orc, mode, c):
         fn(P(c["coeff"]), C.c_ssize_t(n), P(t["round_fp"]), P(t["quant_fp"]), P(qc), P(dq), P(t["dequant"]), C.byref(eob),
            P(c["scan"]), qm, iqm, c["ls"])
     return qc, dq, eob.value
+
+
+class Arena:
+    """Host image of a device arena: arrays placed at 256-byte aligned offsets with 256 bytes of slack between them."""
+
+    def __init__(self):
+        self.chunks, self.size = [], 0
+
+    def add(self, arr=None, nbytes=None):
+        off = self.size
+        nbytes = arr.nbytes if arr is not None else nbytes
+        self.chunks.append((off, None if arr is None else np.ascontiguousarray(arr).view(np.uint8).reshape(-1)))
+        self.size += (nbytes + 255) // 256 * 256 + 256
+        return off
+
+    def build(self):
+        buf = np.zeros(self.size, np.uint8)
+        for off, a in self.chunks:
+            if a is not None:
+                buf[off:off + a.size] = a
+        return buf
+
+
+def fused_batch(orc, rng, w, h, n_tb):
+    """n_tb blocks of w x h for svt_hip_txfm_quant_batch (residual -> fwd -> quantise -> inverse -> recon) with every valid tx_type
+    in turn, 8- / 10-bit, both pixel widths and all four quantisers, and what the oracle pipeline makes of each.
+    -> (arena image, descriptor array, expectations); check_fused_batch compares a device result with them."""
+    from svtav1_hip import abi
+    iw, ih = min(w, 32), min(h, 32)
+    n = iw * ih
+    ls = 2 if max(w, h) == 64 and (w * h) > 1024 else (1 if w * h > 256 and max(w, h) >= 32 and min(w, h) >= 16 else 0)
+    types = [tt for tt in range(16) if orc.orc_txfm_valid(w, h, tt)]
+    scan = rng.permutation(n).astype(np.int16)
+    iscan = np.empty(n, np.int16)
+    iscan[scan] = np.arange(n)
+    ab = Arena()
+    iscan_off = ab.add(iscan)
+    descs, expect = (abi.TxfmDesc * n_tb)(), []
+    for i in range(n_tb):
+        bd = 8 if i % 3 == 0 else 10
+        pix16 = bd == 10 or i % 2 == 0
+        tt, mode = types[(i * 7) % len(types)], 1 + (i % 4)
+        tq = quant_tables(rng, bd)
+        res = (residual(rng, w, h, bd, 0, pad=5) // (1 + (i % 5))).astype(np.int16)
+        pred16 = rng.integers(0, 1 << bd, size=(h, w + 2)).astype(np.uint16)
+        d = descs[i]
+        d.residual_off, d.residual_stride = ab.add(res), w + 5
+        d.coeff_off = ab.add(nbytes=n * 4) if i % 2 else abi.NO_OFFSET
+        d.qcoeff_off, d.dqcoeff_off = ab.add(nbytes=n * 4), ab.add(nbytes=n * 4)
+        d.pred_off = ab.add(pred16 if pix16 else pred16.astype(np.uint8))
+        d.recon_off = ab.add(nbytes=h * (w + 4) * (2 if pix16 else 1))
+        d.pred_stride, d.recon_stride = w + 2, w + 4
+        d.iscan_off, d.qm_off, d.iqm_off = iscan_off, abi.NO_OFFSET, abi.NO_OFFSET
+        rnd, qnt = (tq["round"], tq["quant"]) if mode <= 2 else (tq["round_fp"], tq["quant_fp"])
+        for k in range(2):
+            d.zbin[k], d.round[k], d.quant[k] = int(tq["zbin"][k]), int(rnd[k]), int(qnt[k])
+            d.quant_shift[k], d.dequant[k] = int(tq["qshift"][k]), int(tq["dequant"][k])
+        d.tx_type, d.shape, d.bit_depth, d.quant_mode, d.log_scale = tt, 0, bd, mode, ls
+        d.flags = abi.TX_FWD | abi.TX_INV | (abi.TX_PIXEL16 if pix16 else 0)
+        co = np.zeros(w * h, np.int32)
+        orc.orc_fwd_txfm2d(P(res), P(co), C.c_uint32(w + 5), w, h, tt, bd, 0)
+        co = co[:n].copy()
+        qc, dq, eob = orc_quant(orc, mode, dict(n=n, ls=ls, coeff=co, scan=scan, iscan=iscan, qm=None, iqm=None, t=tq))
+        rec = np.zeros((h, w + 4), np.uint16)
+        orc.orc_inv_txfm2d_add(P(dq), P(pred16), w + 2, P(rec), w + 4, w, h, tt, bd)
+        expect.append((co, qc, dq, eob, rec if pix16 else rec.astype(np.uint8), pix16))
+    return ab.build(), descs, expect
+
+
+def check_fused_batch(w, h, descs, expect, out, res_raw, what=""):
+    """out: the arena after the call; res_raw: (n_tb, 16) bytes of SvtHipTxfmResult"""
+    from svtav1_hip import abi
+    n = min(w, 32) * min(h, 32)
+    for i, (co, qc, dq, eob, rec, pix16) in enumerate(expect):
+        d = descs[i]
+
+        def g(off, cnt, dt):
+            return out[off:off + cnt * np.dtype(dt).itemsize].view(dt)
+        if d.coeff_off != abi.NO_OFFSET:
+            assert np.array_equal(g(d.coeff_off, n, np.int32), co), (what, "coeff", i, d.tx_type)
+        assert np.array_equal(g(d.qcoeff_off, n, np.int32), qc), (what, "qcoeff", i, d.tx_type)
+        assert np.array_equal(g(d.dqcoeff_off, n, np.int32), dq), (what, "dqcoeff", i, d.tx_type)
+        assert int(res_raw[i, 8:10].view(np.uint16)[0]) == eob, (what, "eob", i, d.tx_type)
+        got = g(d.recon_off, h * (w + 4), np.uint16 if pix16 else np.uint8).reshape(h, w + 4)
+        assert np.array_equal(got[:, :w], rec[:, :w]), (what, "recon", i, d.tx_type)
