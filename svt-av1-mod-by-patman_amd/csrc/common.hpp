@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/svt_hip.h"
 #include "../../include/svt_hip_me.h"
@@ -16,13 +17,14 @@ void set_error(const char *fmt, ...);
 // Calling thread's private stream (created lazily) unless the caller passed its own.
 hipStream_t resolve_stream(void *stream);
 
-// Grow-only per-thread device + pinned scratch used by the Tier A (host-pointer) entry points.
+// Grow-only per-thread device + pinned scratch used by the Tier A (host-pointer) entry points.  host() keeps the first
+// `keep` bytes when it has to grow; device() keeps nothing.
 struct Scratch {
     uint8_t *dev    = nullptr;
     uint8_t *pinned = nullptr;
     size_t   dev_cap = 0, pinned_cap = 0;
     uint8_t *device(size_t bytes);
-    uint8_t *host(size_t bytes);
+    uint8_t *host(size_t bytes, size_t keep = 0);
 };
 Scratch &tls_scratch();
 
@@ -70,6 +72,7 @@ void run_module_warmups(hipStream_t st);
 // leaf on another thread — is completed by the restored CPU function with the same arguments, so the encoder carries on with
 // its own kernels and an intact bitstream.  Without an installer-saved CPU pointer (the leaf was called directly, e.g.
 // through ctypes) there is nothing to fall back on: the process stops with the error message, as before.
+// How a leaf is defined and staged: TIER_A_LEAF and TierAStage below.
 namespace svthip {
 struct TierAError {
     char what[256];
@@ -102,3 +105,64 @@ bool              tier_a_inject_now();           // test hook (svt_hip_debug_inj
         }                                                              \
         return ((TierAFn_)svthip::tier_a_cpu(#NAME))ARGS;              \
     } while (0)
+
+// A hand-written leaf is written once:
+//     TIER_A_LEAF(uint32_t, svt_nxm_sad_kernel, (const uint8_t *src, uint32_t src_stride, ...), (src, src_stride, ...)) {
+//         ...body; fails by throwing through fatal() / SVT_HIP_CHECK_FATAL...
+//     }
+// This expands to the exported `extern "C" RET NAME_hip PARAMS` (it must match the prototype in include/*.h), whose body is
+// TIER_A_CALL, and to the head of the file-local function that the braces after the macro complete.
+#define TIER_A_LEAF(RET, NAME, PARAMS, ARGS)                                        \
+    static RET NAME##_leaf PARAMS;                                                  \
+    extern "C" RET NAME##_hip PARAMS { TIER_A_CALL(NAME, NAME##_leaf ARGS, ARGS); } \
+    static RET NAME##_leaf PARAMS
+
+namespace svthip {
+
+inline size_t     up256(size_t v) { return (v + 255) / 256 * 256; }
+[[noreturn]] void fatal(const char *what);  // throws TierAError "<what>: <svt_hip_last_error()>"
+
+// rows x row_bytes between two pitched buffers (pitches in bytes)
+inline void copy_rows(void *dst, size_t dst_pitch, const void *src, size_t src_pitch, size_t rows, size_t row_bytes) {
+    for (size_t r = 0; r < rows; r++) memcpy((uint8_t *)dst + r * dst_pitch, (const uint8_t *)src + r * src_pitch, row_bytes);
+}
+
+// Staging of one Tier A leaf call in the calling thread's Scratch.  A bump allocator hands out regions: offsets, 256-byte
+// aligned, the same in the pinned and in the device buffer.  The leaf uploads what the kernel reads, launches on stream(),
+// and finish() brings the results back.  Every HIP call in here goes through SVT_HIP_CHECK_FATAL.
+//     TierAStage s("leaf name");                        // throws unless the library is initialised
+//     const size_t a = s.in(src, n), r = s.out(4);      // reserve (and fill) every region first ...
+//     s.upload();                                       // ... [0, end of the last in()) goes up in one copy
+//     hipLaunchKernelGGL(k, ..., s.stream(), s.dev(a), s.dev<uint32_t>(r));
+//     s.finish(r, 4);                                   // launch check, copy back, synchronise
+//     return *s.host<uint32_t>(r);
+// A host() pointer is valid until the next in() / out(): the pinned buffer may grow (it keeps its content).  No region can be
+// reserved after dev() / h2d() has sized the device buffer.
+class TierAStage {
+public:
+    explicit TierAStage(const char *leaf, bool ready = ensure_init());
+    // reserves bytes (+ slack that a kernel may read past the data); copies bytes from src unless src is NULL
+    size_t in(const void *src, size_t bytes, size_t slack = 0);
+    // rows x row_bytes read at src_pitch, stored packed (pitch = row_bytes)
+    size_t in_rows(const void *src, size_t src_pitch, size_t rows, size_t row_bytes);
+    size_t out(size_t bytes) { return reserve(bytes); }
+    template <class T = uint8_t> T *host(size_t off) const { return (T *)(h_ + off); }
+    template <class T = uint8_t> T *dev(size_t off) { return (T *)(device() + off); }
+    hipStream_t stream() const { return st_; }
+    void h2d(size_t off, size_t bytes);
+    void upload() { h2d(0, in_end_); }
+    void finish(size_t off, size_t bytes, size_t off2 = 0, size_t bytes2 = 0);
+    // rows x row_bytes of the packed region at off, written at dst_pitch
+    void out_rows(void *dst, size_t dst_pitch, size_t off, size_t rows, size_t row_bytes) const {
+        copy_rows(dst, dst_pitch, h_ + off, row_bytes, rows, row_bytes);
+    }
+
+private:
+    size_t      reserve(size_t bytes);
+    uint8_t    *device();
+    hipStream_t st_;
+    uint8_t    *h_ = nullptr, *d_ = nullptr;
+    size_t      used_ = 0, in_end_ = 0;
+};
+
+}  // namespace svthip

@@ -645,8 +645,6 @@ __global__ __launch_bounds__(256) void search_one_dual_kernel(const uint64_t *__
         out[0] = s_tot[0], out[1] = s_id[0];
 }
 
-[[noreturn]] void fatal(const char *what) { svthip::tier_a_throw("%s: %s", what, svt_hip_last_error()); }
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -714,67 +712,55 @@ extern "C" int32_t svt_hip_cdef_apply_frame(const SvtHipCdefPlane *planes, uint3
     return SVT_HIP_OK;
 }
 
-static void svt_aom_cdef_find_dir_dual_hip_impl(const uint16_t *img1, const uint16_t *img2, int stride, int32_t *var1, int32_t *var2, int32_t coeff_shift, uint8_t *out1, uint8_t *out2);
-extern "C" void svt_aom_cdef_find_dir_dual_hip(const uint16_t *img1, const uint16_t *img2, int stride, int32_t *var1, int32_t *var2, int32_t coeff_shift, uint8_t *out1, uint8_t *out2) { TIER_A_CALL(svt_aom_cdef_find_dir_dual, svt_aom_cdef_find_dir_dual_hip_impl(img1, img2, stride, var1, var2, coeff_shift, out1, out2), (img1, img2, stride, var1, var2, coeff_shift, out1, out2)); }
-static void svt_aom_cdef_find_dir_dual_hip_impl(const uint16_t *img1, const uint16_t *img2, int stride, int32_t *var1, int32_t *var2, int32_t coeff_shift, uint8_t *out1, uint8_t *out2) {
-    if (!ensure_init())
-        fatal("cdef_find_dir");
-    hipStream_t  st   = resolve_stream(nullptr);
-    Scratch     &sc   = tls_scratch();
-    const size_t span = ((size_t)7 * stride + 8) * 2, o2 = up256(span + 16), ores = 2 * o2;
-    uint8_t     *d = sc.device(ores + 256), *h = sc.host(ores + 256);
-    memcpy(h, img1, span);
-    if (img2)
-        memcpy(h + o2, img2, span);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, ores, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(find_dir_kernel, dim3(1), dim3(64), 0, st, (const uint16_t *)d, img2 ? (const uint16_t *)(d + o2) : nullptr, stride,
-                       coeff_shift, (int32_t *)(d + ores));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + ores, d + ores, 16, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    const int32_t *r = (const int32_t *)(h + ores);
+TIER_A_LEAF(void, svt_aom_cdef_find_dir_dual,
+            (const uint16_t *img1, const uint16_t *img2, int stride, int32_t *var1, int32_t *var2, int32_t coeff_shift, uint8_t
+             *out1, uint8_t *out2),
+            (img1, img2, stride, var1, var2, coeff_shift, out1, out2)) {
+    TierAStage   s("cdef_find_dir");
+    const size_t span = ((size_t)7 * stride + 8) * 2;
+    const size_t o1 = s.in(img1, span, 16), o2 = s.in(img2, img2 ? span : 0, 16), ores = s.out(16);
+    s.upload();
+    hipLaunchKernelGGL(find_dir_kernel, dim3(1), dim3(64), 0, s.stream(), s.dev<const uint16_t>(o1), img2 ? s.dev<const uint16_t>(o2) : nullptr,
+                       stride, coeff_shift, s.dev<int32_t>(ores));
+    s.finish(ores, 16);
+    const int32_t *r = s.host<int32_t>(ores);
     *out1 = (uint8_t)r[0], *var1 = r[1];
     if (img2)
         *out2 = (uint8_t)r[2], *var2 = r[3];
 }
-static uint8_t svt_aom_cdef_find_dir_hip_impl(const uint16_t *img, int32_t stride, int32_t *var, int32_t coeff_shift);
-extern "C" uint8_t svt_aom_cdef_find_dir_hip(const uint16_t *img, int32_t stride, int32_t *var, int32_t coeff_shift) { TIER_A_CALL(svt_aom_cdef_find_dir, svt_aom_cdef_find_dir_hip_impl(img, stride, var, coeff_shift), (img, stride, var, coeff_shift)); }
-static uint8_t svt_aom_cdef_find_dir_hip_impl(const uint16_t *img, int32_t stride, int32_t *var, int32_t coeff_shift) {
+TIER_A_LEAF(uint8_t, svt_aom_cdef_find_dir,
+            (const uint16_t *img, int32_t stride, int32_t *var, int32_t coeff_shift),
+            (img, stride, var, coeff_shift)) {
     uint8_t d = 0;
     svt_aom_cdef_find_dir_dual_hip(img, nullptr, stride, var, nullptr, coeff_shift, &d, nullptr);
     return d;
 }
 
-static void svt_cdef_filter_block_hip_impl(uint8_t *dst8, uint16_t *dst16, int32_t dstride, const uint16_t *in, int32_t pri_strength, int32_t sec_strength, int32_t dir, int32_t pri_damping, int32_t sec_damping, int32_t bsize, int32_t coeff_shift, uint8_t subsampling_factor);
-extern "C" void svt_cdef_filter_block_hip(uint8_t *dst8, uint16_t *dst16, int32_t dstride, const uint16_t *in, int32_t pri_strength, int32_t sec_strength, int32_t dir, int32_t pri_damping, int32_t sec_damping, int32_t bsize, int32_t coeff_shift, uint8_t subsampling_factor) { TIER_A_CALL(svt_cdef_filter_block, svt_cdef_filter_block_hip_impl(dst8, dst16, dstride, in, pri_strength, sec_strength, dir, pri_damping, sec_damping, bsize, coeff_shift, subsampling_factor), (dst8, dst16, dstride, in, pri_strength, sec_strength, dir, pri_damping, sec_damping, bsize, coeff_shift, subsampling_factor)); }
-static void svt_cdef_filter_block_hip_impl(uint8_t *dst8, uint16_t *dst16, int32_t dstride, const uint16_t *in, int32_t pri_strength, int32_t sec_strength, int32_t dir, int32_t pri_damping, int32_t sec_damping, int32_t bsize, int32_t coeff_shift, uint8_t subsampling_factor) {
-    if (!ensure_init())
-        fatal("cdef_filter_block");
+TIER_A_LEAF(void, svt_cdef_filter_block,
+            (uint8_t *dst8, uint16_t *dst16, int32_t dstride, const uint16_t *in, int32_t pri_strength, int32_t sec_strength,
+             int32_t dir, int32_t pri_damping, int32_t sec_damping, int32_t bsize, int32_t coeff_shift, uint8_t subsampling_factor),
+            (dst8, dst16, dstride, in, pri_strength, sec_strength, dir, pri_damping, sec_damping, bsize, coeff_shift,
+             subsampling_factor)) {
+    TierAStage   s("cdef_filter_block");
     const int    bh = 4 << (bsize == 3 || bsize == 1), bw = 4 << (bsize == 3 || bsize == 2);
     const size_t before = 2 * BS + 2, after = (size_t)(bh - 1 + 2) * BS + bw + 2;  // taps reach +-(2 rows, 2 columns)
-    const size_t in_bytes = (before + after) * 2, px = dst16 ? 2 : 1, out_bytes = ((size_t)(bh - 1) * dstride + bw) * px;
-    hipStream_t  st = resolve_stream(nullptr);
-    Scratch     &sc = tls_scratch();
-    const size_t oo = up256(in_bytes + 16);
-    uint8_t     *d = sc.device(oo + out_bytes + 256), *h = sc.host(oo + out_bytes + 256);
-    memcpy(h, in - before, in_bytes);
-    memcpy(h + oo, dst16 ? (const void *)dst16 : (const void *)dst8, out_bytes);  // rows skipped by sub-sampling keep their content
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, oo + out_bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(filter_block_kernel, dim3(1), dim3(64), 0, st, dst16 ? nullptr : d + oo, dst16 ? (uint16_t *)(d + oo) : nullptr,
-                       dstride, (const uint16_t *)d + before, pri_strength, sec_strength, dir, pri_damping, sec_damping, bsize, coeff_shift,
+    const size_t px = dst16 ? 2 : 1, out_bytes = ((size_t)(bh - 1) * dstride + bw) * px;
+    uint8_t     *dst = dst16 ? (uint8_t *)dst16 : dst8;
+    const size_t oi = s.in(in - before, (before + after) * 2, 16);
+    const size_t oo = s.in(dst, out_bytes);  // rows skipped by sub-sampling keep their content
+    s.upload();
+    hipLaunchKernelGGL(filter_block_kernel, dim3(1), dim3(64), 0, s.stream(), dst16 ? nullptr : s.dev(oo), dst16 ? s.dev<uint16_t>(oo) : nullptr,
+                       dstride, s.dev<const uint16_t>(oi) + before, pri_strength, sec_strength, dir, pri_damping, sec_damping, bsize, coeff_shift,
                        (int)subsampling_factor);
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + oo, d + oo, out_bytes, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    for (int r = 0; r < bh; r++)
-        memcpy((uint8_t *)(dst16 ? (void *)dst16 : (void *)dst8) + (size_t)r * dstride * px, h + oo + (size_t)r * dstride * px, bw * px);
+    s.finish(oo, out_bytes);
+    copy_rows(dst, dstride * px, s.host(oo), dstride * px, bh, bw * px);
 }
 
 // Pure 8-bit -> 16-bit widening of a host rectangle: no arithmetic, evaluated on the calling thread
 // (the device-resident equivalent is the tile staging of the kernels above).
-static void svt_aom_copy_rect8_8bit_to_16bit_hip_impl(uint16_t *dst, int32_t dstride, const uint8_t *src, int32_t sstride, int32_t v, int32_t hh);
-extern "C" void svt_aom_copy_rect8_8bit_to_16bit_hip(uint16_t *dst, int32_t dstride, const uint8_t *src, int32_t sstride, int32_t v, int32_t hh) { TIER_A_CALL(svt_aom_copy_rect8_8bit_to_16bit, svt_aom_copy_rect8_8bit_to_16bit_hip_impl(dst, dstride, src, sstride, v, hh), (dst, dstride, src, sstride, v, hh)); }
-static void svt_aom_copy_rect8_8bit_to_16bit_hip_impl(uint16_t *dst, int32_t dstride, const uint8_t *src, int32_t sstride, int32_t v, int32_t hh) {
+TIER_A_LEAF(void, svt_aom_copy_rect8_8bit_to_16bit,
+            (uint16_t *dst, int32_t dstride, const uint8_t *src, int32_t sstride, int32_t v, int32_t hh),
+            (dst, dstride, src, sstride, v, hh)) {
     for (int32_t i = 0; i < v; i++)
         for (int32_t j = 0; j < hh; j++) dst[i * dstride + j] = src[i * sstride + j];
 }
@@ -783,42 +769,37 @@ static uint64_t dist_tier_a(const void *dst, int32_t dstride, const void *src, c
                             int32_t coeff_shift, int32_t pli, uint8_t sub, int is16) {
     if (n <= 0)
         return 0;
-    if (!ensure_init())
-        fatal("compute_cdef_dist");
+    TierAStage   s("compute_cdef_dist");
     const int    bw = 4 << (bsize == 3 || bsize == 2), bh = 4 << (bsize == 3 || bsize == 1), px = is16 ? 2 : 1;
     int          maxy = 0, maxx = 0;
     for (int i = 0; i < n; i++) maxy = dlist[i].by > maxy ? dlist[i].by : maxy, maxx = dlist[i].bx > maxx ? dlist[i].bx : maxx;
-    const size_t dst_bytes = ((size_t)((maxy + 1) * bh - 1) * dstride + (size_t)(maxx + 1) * bw) * px;
-    const size_t src_bytes = (size_t)n * bw * bh * px, dl_bytes = (size_t)n * sizeof(SvtHipCdefList);
-    const size_t o_src = up256(dst_bytes + 16), o_dl = o_src + up256(src_bytes + 16), o_res = o_dl + up256(dl_bytes + 16);
-    hipStream_t  st = resolve_stream(nullptr);
-    Scratch     &sc = tls_scratch();
-    uint8_t     *d = sc.device(o_res + 256), *h = sc.host(o_res + 256);
-    memcpy(h, dst, dst_bytes), memcpy(h + o_src, src, src_bytes), memcpy(h + o_dl, dlist, dl_bytes);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, o_res, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(dist_kernel, dim3(1), dim3(256), 0, st, (const void *)d, dstride, (const void *)(d + o_src),
-                       (const SvtHipCdefList *)(d + o_dl), n, bsize, coeff_shift, pli, (int)sub, is16, (uint64_t *)(d + o_res));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + o_res, d + o_res, 8, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    return *(const uint64_t *)(h + o_res);
+    const size_t o_dst = s.in(dst, ((size_t)((maxy + 1) * bh - 1) * dstride + (size_t)(maxx + 1) * bw) * px, 16);
+    const size_t o_src = s.in(src, (size_t)n * bw * bh * px, 16), o_dl = s.in(dlist, (size_t)n * sizeof(SvtHipCdefList), 16);
+    const size_t o_res = s.out(8);
+    s.upload();
+    hipLaunchKernelGGL(dist_kernel, dim3(1), dim3(256), 0, s.stream(), s.dev<const void>(o_dst), dstride, s.dev<const void>(o_src),
+                       s.dev<const SvtHipCdefList>(o_dl), n, bsize, coeff_shift, pli, (int)sub, is16, s.dev<uint64_t>(o_res));
+    s.finish(o_res, 8);
+    return *s.host<uint64_t>(o_res);
 }
-static uint64_t svt_compute_cdef_dist_16bit_hip_impl(const uint16_t *dst, int32_t dstride, const uint16_t *src, const SvtHipCdefList *dlist, int32_t cdef_count, int32_t bsize, int32_t coeff_shift, int32_t pli, uint8_t sub);
-extern "C" uint64_t svt_compute_cdef_dist_16bit_hip(const uint16_t *dst, int32_t dstride, const uint16_t *src, const SvtHipCdefList *dlist, int32_t cdef_count, int32_t bsize, int32_t coeff_shift, int32_t pli, uint8_t sub) { TIER_A_CALL(svt_compute_cdef_dist_16bit, svt_compute_cdef_dist_16bit_hip_impl(dst, dstride, src, dlist, cdef_count, bsize, coeff_shift, pli, sub), (dst, dstride, src, dlist, cdef_count, bsize, coeff_shift, pli, sub)); }
-static uint64_t svt_compute_cdef_dist_16bit_hip_impl(const uint16_t *dst, int32_t dstride, const uint16_t *src, const SvtHipCdefList *dlist, int32_t cdef_count, int32_t bsize, int32_t coeff_shift, int32_t pli, uint8_t sub) {
+TIER_A_LEAF(uint64_t, svt_compute_cdef_dist_16bit,
+            (const uint16_t *dst, int32_t dstride, const uint16_t *src, const SvtHipCdefList *dlist, int32_t cdef_count, int32_t
+             bsize, int32_t coeff_shift, int32_t pli, uint8_t sub),
+            (dst, dstride, src, dlist, cdef_count, bsize, coeff_shift, pli, sub)) {
     return dist_tier_a(dst, dstride, src, dlist, cdef_count, bsize, coeff_shift, pli, sub, 1);
 }
-static uint64_t svt_compute_cdef_dist_8bit_hip_impl(const uint8_t *dst8, int32_t dstride, const uint8_t *src8, const SvtHipCdefList *dlist, int32_t cdef_count, int32_t bsize, int32_t coeff_shift, int32_t pli, uint8_t sub);
-extern "C" uint64_t svt_compute_cdef_dist_8bit_hip(const uint8_t *dst8, int32_t dstride, const uint8_t *src8, const SvtHipCdefList *dlist, int32_t cdef_count, int32_t bsize, int32_t coeff_shift, int32_t pli, uint8_t sub) { TIER_A_CALL(svt_compute_cdef_dist_8bit, svt_compute_cdef_dist_8bit_hip_impl(dst8, dstride, src8, dlist, cdef_count, bsize, coeff_shift, pli, sub), (dst8, dstride, src8, dlist, cdef_count, bsize, coeff_shift, pli, sub)); }
-static uint64_t svt_compute_cdef_dist_8bit_hip_impl(const uint8_t *dst8, int32_t dstride, const uint8_t *src8, const SvtHipCdefList *dlist, int32_t cdef_count, int32_t bsize, int32_t coeff_shift, int32_t pli, uint8_t sub) {
+TIER_A_LEAF(uint64_t, svt_compute_cdef_dist_8bit,
+            (const uint8_t *dst8, int32_t dstride, const uint8_t *src8, const SvtHipCdefList *dlist, int32_t cdef_count, int32_t
+             bsize, int32_t coeff_shift, int32_t pli, uint8_t sub),
+            (dst8, dstride, src8, dlist, cdef_count, bsize, coeff_shift, pli, sub)) {
     return dist_tier_a(dst8, dstride, src8, dlist, cdef_count, bsize, coeff_shift, pli, sub, 0);
 }
 
 // svt_search_one_dual (aom_dsp_rtcd.h:239): mse[0][i] / mse[1][i] are the luma / chroma tables of filter block i (TOTAL_STRENGTHS
 // entries each in the reference; entries below end_gi are read).  lev0 / lev1 hold nb_strengths chosen pairs and receive one more.
-static uint64_t svt_search_one_dual_hip_impl(int *lev0, int *lev1, int nb_strengths, uint64_t **mse[2], int sb_count, int start_gi, int end_gi);
-extern "C" uint64_t svt_search_one_dual_hip(int *lev0, int *lev1, int nb_strengths, uint64_t **mse[2], int sb_count, int start_gi, int end_gi) { TIER_A_CALL(svt_search_one_dual, svt_search_one_dual_hip_impl(lev0, lev1, nb_strengths, mse, sb_count, start_gi, end_gi), (lev0, lev1, nb_strengths, mse, sb_count, start_gi, end_gi)); }
-static uint64_t svt_search_one_dual_hip_impl(int *lev0, int *lev1, int nb_strengths, uint64_t **mse[2], int sb_count, int start_gi, int end_gi) {
+TIER_A_LEAF(uint64_t, svt_search_one_dual,
+            (int *lev0, int *lev1, int nb_strengths, uint64_t **mse[2], int sb_count, int start_gi, int end_gi),
+            (lev0, lev1, nb_strengths, mse, sb_count, start_gi, end_gi)) {
     if (nb_strengths < 0 || nb_strengths >= 8 || start_gi < 0 || end_gi > 64 || sb_count < 0) {
         set_error("svt_search_one_dual: nb_strengths %d / strength range %d..%d outside CDEF's limits", nb_strengths, start_gi, end_gi);
         fatal("svt_search_one_dual");
@@ -827,29 +808,23 @@ static uint64_t svt_search_one_dual_hip_impl(int *lev0, int *lev1, int nb_streng
         lev0[nb_strengths] = lev1[nb_strengths] = 0;
         return 1ull << 63;
     }
-    if (!ensure_init())
-        fatal("svt_search_one_dual");
-    const size_t n = (size_t)end_gi, tab = up256((size_t)2 * sb_count * n * 8 + 8), o_lev = tab, o_res = o_lev + 256;
-    Scratch     &sc = tls_scratch();
-    uint8_t     *h = sc.host(o_res + 256), *d = sc.device(o_res + 256);
-    uint64_t    *m = (uint64_t *)h;
-    for (int p = 0; p < 2; p++)
-        for (int i = 0; i < sb_count; i++) memcpy(m + ((size_t)p * sb_count + i) * n, mse[p][i], n * 8);
-    int32_t *lv = (int32_t *)(h + o_lev);
-    for (int g = 0; g < 8; g++) lv[g] = g < nb_strengths ? lev0[g] : 0, lv[8 + g] = g < nb_strengths ? lev1[g] : 0;
     for (int g = 0; g < nb_strengths; g++)
         if (lev0[g] < 0 || lev0[g] >= end_gi || lev1[g] < 0 || lev1[g] >= end_gi) {
             set_error("svt_search_one_dual: chosen strength outside the searched range");
             fatal("svt_search_one_dual");
         }
-    hipStream_t st = resolve_stream(nullptr);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, o_res, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(search_one_dual_kernel, dim3(1), dim3(256), 0, st, (const uint64_t *)d, (const int32_t *)(d + o_lev), nb_strengths,
-                       sb_count, end_gi, start_gi, (uint64_t *)(d + o_res));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + o_res, d + o_res, 16, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    const uint64_t *res = (const uint64_t *)(h + o_res);
+    TierAStage   s("svt_search_one_dual");
+    const size_t n = (size_t)end_gi, o_tab = s.in(nullptr, (size_t)2 * sb_count * n * 8, 8), o_lev = s.in(nullptr, 64), o_res = s.out(16);
+    uint64_t    *m = s.host<uint64_t>(o_tab);
+    for (int p = 0; p < 2; p++)
+        for (int i = 0; i < sb_count; i++) memcpy(m + ((size_t)p * sb_count + i) * n, mse[p][i], n * 8);
+    int32_t *lv = s.host<int32_t>(o_lev);
+    for (int g = 0; g < 8; g++) lv[g] = g < nb_strengths ? lev0[g] : 0, lv[8 + g] = g < nb_strengths ? lev1[g] : 0;
+    s.upload();
+    hipLaunchKernelGGL(search_one_dual_kernel, dim3(1), dim3(256), 0, s.stream(), s.dev<const uint64_t>(o_tab), s.dev<const int32_t>(o_lev),
+                       nb_strengths, sb_count, end_gi, start_gi, s.dev<uint64_t>(o_res));
+    s.finish(o_res, 16);
+    const uint64_t *res = s.host<uint64_t>(o_res);
     const int       span = end_gi - start_gi;
     const uint32_t  id   = (uint32_t)res[1];
     lev0[nb_strengths] = id == 0xffffffffu ? 0 : start_gi + (int)id / span;

@@ -205,28 +205,21 @@ __global__ void lpf_leaf_kernel(T *s, int pitch, int vertical, int len, int blim
 
 // Tier A: stage the samples the reference call touches (4 lines x 2*reach taps), run the leaf, copy them back.
 template <typename T> void lpf_tier_a(T *s, int32_t pitch, const uint8_t *blimit, const uint8_t *limit, const uint8_t *thresh, int bd, int len, int vertical) {
-    if (!ensure_init()) {
-        svthip::tier_a_throw("lpf: %s", svt_hip_last_error());
-    }
+    TierAStage      st("lpf");
     const int       reach = len == 4 ? 2 : (len == 6 ? 3 : (len == 8 ? 4 : 7));
     const ptrdiff_t first = vertical ? -reach : -(ptrdiff_t)reach * pitch;
     const ptrdiff_t last  = vertical ? 3 * (ptrdiff_t)pitch + reach : (ptrdiff_t)(reach - 1) * pitch + 4;  // one past
-    const size_t    n     = (size_t)(last - first), bytes = n * sizeof(T);
-    hipStream_t     st    = resolve_stream(nullptr);
-    Scratch        &sc    = tls_scratch();
-    uint8_t        *d = sc.device(bytes + 256), *h = sc.host(bytes + 256);
-    memcpy(h, s + first, bytes);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(lpf_leaf_kernel<T>, dim3(1), dim3(64), 0, st, (T *)d - first, (int)pitch, vertical, len, (int)*blimit, (int)*limit,
-                       (int)*thresh, bd);
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
+    const size_t    bytes = (size_t)(last - first) * sizeof(T), off = st.in(s + first, bytes);
+    st.upload();
+    hipLaunchKernelGGL(lpf_leaf_kernel<T>, dim3(1), dim3(64), 0, st.stream(), st.dev<T>(off) - first, (int)pitch, vertical, len, (int)*blimit,
+                       (int)*limit, (int)*thresh, bd);
+    st.finish(off, bytes);
+    const T *h = st.host<T>(off);
     // write back only the taps of the four lines (the span in between belongs to the caller's other samples)
     for (int i = 0; i < 4; i++)
         for (int k = -reach; k < reach; k++) {
             const ptrdiff_t o = vertical ? i * (ptrdiff_t)pitch + k : k * (ptrdiff_t)pitch + i;
-            s[o]              = ((const T *)h)[o - first];
+            s[o]              = h[o - first];
         }
 }
 

@@ -272,8 +272,6 @@ bool unit_ok(const SvtHipSgrUnit *u, bool need_src) {
 SgrGeom geom_of(const SvtHipSgrUnit *u) {
     return SgrGeom{u->dat, u->dat_stride, u->width, u->height, u->is_16bit, u->bit_depth, u->pu_w, u->pu_h};
 }
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-[[noreturn]] void fatal(const char *what) { svthip::tier_a_throw("%s: %s", what, svt_hip_last_error()); }
 template <typename T> const T *decode_ptr(const uint8_t *p, int highbd) {
     return highbd ? (const T *)((uintptr_t)p << 1) : (const T *)p;  // CONVERT_TO_SHORTPTR (definitions.h:953)
 }
@@ -357,134 +355,108 @@ extern "C" int32_t svt_hip_sgr_search_unit(const SvtHipSgrUnit *unit, int32_t st
 }
 
 // ------------------------------------------------------------------------------------------------ Tier A
-// Stage a w x h region (+border) of host samples as a packed device plane; returns the device pointer of sample (0,0).
-template <typename T> static T *stage_region(uint8_t *d, uint8_t *h, size_t &off, const T *p, int w, int hh, int stride, int border, size_t &pitch_out) {
-    const size_t pitch = (size_t)w + 2 * border, rows = (size_t)hh + 2 * border;
-    T           *hp    = (T *)(h + off);
-    for (size_t r = 0; r < rows; r++) memcpy(hp + r * pitch, p + ((ptrdiff_t)r - border) * stride - border, pitch * sizeof(T));
-    T *dp = (T *)(d + off) + (size_t)border * pitch + border;
-    off += up256(pitch * rows * sizeof(T));
-    pitch_out = pitch;
-    return dp;
+// Stage a w x h region (+border) of host samples as a packed plane; returns the offset of the plane (pitch w + 2 * border).
+static size_t stage_region(TierAStage &s, const uint8_t *p8, int highbd, int w, int hh, int stride, int border) {
+    const size_t   px = highbd ? 2 : 1, pitch = ((size_t)w + 2 * border) * px;
+    const uint8_t *p  = highbd ? (const uint8_t *)decode_ptr<uint16_t>(p8, 1) : p8;
+    return s.in_rows(p - ((ptrdiff_t)border * stride + border) * (ptrdiff_t)px, (size_t)stride * px, (size_t)hh + 2 * border, pitch);
 }
 
-static void svt_av1_selfguided_restoration_hip_impl(const uint8_t *dgd8, int32_t width, int32_t height, int32_t dgd_stride, int32_t *flt0, int32_t *flt1, int32_t flt_stride, int32_t ep, int32_t bit_depth, int32_t highbd);
-extern "C" void svt_av1_selfguided_restoration_hip(const uint8_t *dgd8, int32_t width, int32_t height, int32_t dgd_stride, int32_t *flt0, int32_t *flt1, int32_t flt_stride, int32_t ep, int32_t bit_depth, int32_t highbd) { TIER_A_CALL(svt_av1_selfguided_restoration, svt_av1_selfguided_restoration_hip_impl(dgd8, width, height, dgd_stride, flt0, flt1, flt_stride, ep, bit_depth, highbd), (dgd8, width, height, dgd_stride, flt0, flt1, flt_stride, ep, bit_depth, highbd)); }
-static void svt_av1_selfguided_restoration_hip_impl(const uint8_t *dgd8, int32_t width, int32_t height, int32_t dgd_stride, int32_t *flt0, int32_t *flt1, int32_t flt_stride, int32_t ep, int32_t bit_depth, int32_t highbd) {
-    if (!ensure_init())
-        fatal("selfguided_restoration");
+TIER_A_LEAF(void, svt_av1_selfguided_restoration,
+            (const uint8_t *dgd8, int32_t width, int32_t height, int32_t dgd_stride, int32_t *flt0, int32_t *flt1, int32_t
+             flt_stride, int32_t ep, int32_t bit_depth, int32_t highbd),
+            (dgd8, width, height, dgd_stride, flt0, flt1, flt_stride, ep, bit_depth, highbd)) {
     if (width <= 0 || height <= 0 || width > 384 || height > 384 || ep < 0 || ep > 15) {
         set_error("svt_av1_selfguided_restoration_hip: unsupported size %dx%d / ep %d", width, height, ep);
         fatal("selfguided_restoration");
     }
-    hipStream_t  st = resolve_stream(nullptr);
-    Scratch     &sc = tls_scratch();
-    const size_t px = highbd ? 2 : 1, in_bytes = up256((size_t)(width + 6) * (height + 6) * px), fl_bytes = up256((size_t)width * height * 4);
-    uint8_t     *d = sc.device(in_bytes + 2 * fl_bytes + 256), *h = sc.host(in_bytes + 2 * fl_bytes + 256);
-    size_t       off = 0, pitch = 0;
-    const void  *dp = highbd ? (const void *)stage_region<uint16_t>(d, h, off, decode_ptr<uint16_t>(dgd8, 1), width, height, dgd_stride, 3, pitch)
-                             : (const void *)stage_region<uint8_t>(d, h, off, dgd8, width, height, dgd_stride, 3, pitch);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
-    SvtHipSgrUnit u{dp, nullptr, (uint32_t)pitch, 0, (uint32_t)width, (uint32_t)height, (uint8_t)(highbd != 0), (uint8_t)bit_depth, 64, 64};
-    int32_t      *df0 = (int32_t *)(d + in_bytes), *df1 = (int32_t *)(d + in_bytes + fl_bytes);
+    TierAStage   s("selfguided_restoration");
+    const size_t px = highbd ? 2 : 1, pitch = (size_t)width + 6, fl_bytes = (size_t)width * height * 4;
+    const size_t o_in = stage_region(s, dgd8, highbd, width, height, dgd_stride, 3), o_f0 = s.out(fl_bytes), o_f1 = s.out(fl_bytes);
+    s.upload();
+    SvtHipSgrUnit u{s.dev(o_in) + (3 * pitch + 3) * px, nullptr, (uint32_t)pitch, 0, (uint32_t)width, (uint32_t)height, (uint8_t)(highbd != 0),
+                    (uint8_t)bit_depth, 64, 64};
     const dim3    grid((width + 63) / 64, (height + 63) / 64);
-    hipLaunchKernelGGL(sgr_filter_kernel<0>, grid, dim3(SGR_NT), 0, st, geom_of(&u), ep, df0, df1, (uint32_t)width, (void *)nullptr, 0u, 0, 0);
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + in_bytes, d + in_bytes, 2 * fl_bytes, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    const int32_t *hf0 = (const int32_t *)(h + in_bytes), *hf1 = (const int32_t *)(h + in_bytes + fl_bytes);
-    for (int r = 0; r < height; r++) {
-        if (SGR_PRM_H[ep][0] > 0)
-            memcpy(flt0 + (size_t)r * flt_stride, hf0 + (size_t)r * width, (size_t)width * 4);
-        if (SGR_PRM_H[ep][1] > 0)
-            memcpy(flt1 + (size_t)r * flt_stride, hf1 + (size_t)r * width, (size_t)width * 4);
-    }
+    hipLaunchKernelGGL(sgr_filter_kernel<0>, grid, dim3(SGR_NT), 0, s.stream(), geom_of(&u), ep, s.dev<int32_t>(o_f0), s.dev<int32_t>(o_f1),
+                       (uint32_t)width, (void *)nullptr, 0u, 0, 0);
+    s.finish(o_f0, o_f1 + fl_bytes - o_f0);  // adjacent: one copy brings both back
+    if (SGR_PRM_H[ep][0] > 0)
+        s.out_rows(flt0, (size_t)flt_stride * 4, o_f0, height, (size_t)width * 4);
+    if (SGR_PRM_H[ep][1] > 0)
+        s.out_rows(flt1, (size_t)flt_stride * 4, o_f1, height, (size_t)width * 4);
 }
 
-static void svt_apply_selfguided_restoration_hip_impl(const uint8_t *dat, int32_t width, int32_t height, int32_t stride, int32_t eps, const int32_t *xqd, uint8_t *dst, int32_t dst_stride, int32_t *tmpbuf, int32_t bit_depth, int32_t highbd);
-extern "C" void svt_apply_selfguided_restoration_hip(const uint8_t *dat, int32_t width, int32_t height, int32_t stride, int32_t eps, const int32_t *xqd, uint8_t *dst, int32_t dst_stride, int32_t *tmpbuf, int32_t bit_depth, int32_t highbd) { TIER_A_CALL(svt_apply_selfguided_restoration, svt_apply_selfguided_restoration_hip_impl(dat, width, height, stride, eps, xqd, dst, dst_stride, tmpbuf, bit_depth, highbd), (dat, width, height, stride, eps, xqd, dst, dst_stride, tmpbuf, bit_depth, highbd)); }
-static void svt_apply_selfguided_restoration_hip_impl(const uint8_t *dat, int32_t width, int32_t height, int32_t stride, int32_t eps, const int32_t *xqd, uint8_t *dst, int32_t dst_stride, int32_t *tmpbuf, int32_t bit_depth, int32_t highbd) {
+TIER_A_LEAF(void, svt_apply_selfguided_restoration,
+            (const uint8_t *dat, int32_t width, int32_t height, int32_t stride, int32_t eps, const int32_t *xqd, uint8_t *dst,
+             int32_t dst_stride, int32_t *tmpbuf, int32_t bit_depth, int32_t highbd),
+            (dat, width, height, stride, eps, xqd, dst, dst_stride, tmpbuf, bit_depth, highbd)) {
     (void)tmpbuf;
-    if (!ensure_init())
-        fatal("apply_selfguided_restoration");
     if (width <= 0 || height <= 0 || width > 384 || height > 384 || eps < 0 || eps > 15) {
         set_error("svt_apply_selfguided_restoration_hip: unsupported size %dx%d / eps %d", width, height, eps);
         fatal("apply_selfguided_restoration");
     }
-    hipStream_t  st = resolve_stream(nullptr);
-    Scratch     &sc = tls_scratch();
-    const size_t px = highbd ? 2 : 1, in_bytes = up256((size_t)(width + 6) * (height + 6) * px), out_bytes = up256((size_t)width * height * px);
-    uint8_t     *d = sc.device(in_bytes + out_bytes + 256), *h = sc.host(in_bytes + out_bytes + 256);
-    size_t       off = 0, pitch = 0;
-    const void  *dp = highbd ? (const void *)stage_region<uint16_t>(d, h, off, decode_ptr<uint16_t>(dat, 1), width, height, stride, 3, pitch)
-                             : (const void *)stage_region<uint8_t>(d, h, off, dat, width, height, stride, 3, pitch);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
-    SvtHipSgrUnit u{dp, nullptr, (uint32_t)pitch, 0, (uint32_t)width, (uint32_t)height, (uint8_t)(highbd != 0), (uint8_t)bit_depth, 64, 64};
-    if (svt_hip_sgr_apply_unit(&u, eps, xqd, d + in_bytes, (uint32_t)width, st) != SVT_HIP_OK)
+    TierAStage   s("apply_selfguided_restoration");
+    const size_t px = highbd ? 2 : 1, pitch = (size_t)width + 6, out_bytes = (size_t)width * height * px;
+    const size_t o_in = stage_region(s, dat, highbd, width, height, stride, 3), o_out = s.out(out_bytes);
+    s.upload();
+    SvtHipSgrUnit u{s.dev(o_in) + (3 * pitch + 3) * px, nullptr, (uint32_t)pitch, 0, (uint32_t)width, (uint32_t)height, (uint8_t)(highbd != 0),
+                    (uint8_t)bit_depth, 64, 64};
+    if (svt_hip_sgr_apply_unit(&u, eps, xqd, s.dev(o_out), (uint32_t)width, s.stream()) != SVT_HIP_OK)
         fatal("apply_selfguided_restoration");
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + in_bytes, d + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    uint8_t *dst_b = highbd ? (uint8_t *)((uintptr_t)dst << 1) : dst;
-    for (int r = 0; r < height; r++) memcpy(dst_b + (size_t)r * dst_stride * px, h + in_bytes + (size_t)r * width * px, (size_t)width * px);
+    s.finish(o_out, out_bytes);
+    s.out_rows(highbd ? (uint8_t *)((uintptr_t)dst << 1) : dst, (size_t)dst_stride * px, o_out, height, (size_t)width * px);
 }
 
 // Shared staging of (src, dat, flt0, flt1) for the two reductions
 static void proj_tier_a(const uint8_t *src8, int width, int height, int src_stride, const uint8_t *dat8, int dat_stride, int highbd,
                         const int32_t *flt0, int flt0_stride, const int32_t *flt1, int flt1_stride, const SvtHipSgrParams *params, int xq0,
                         int xq1, int want_sums, long long out[6], int32_t *xq_solved) {
-    if (!ensure_init())
-        fatal("sgr projection");
     if (width <= 0 || height <= 0 || (size_t)width * height > (size_t)1 << 20 || !params) {
         set_error("sgr projection: unsupported size %dx%d", width, height);
         fatal("sgr projection");
     }
-    hipStream_t  st = resolve_stream(nullptr);
-    Scratch     &sc = tls_scratch();
-    const size_t px = highbd ? 2 : 1, pl = up256((size_t)width * height * px), fl = up256((size_t)width * height * 4);
-    const size_t total = 2 * pl + 2 * fl + 256;
-    uint8_t     *d = sc.device(total + 256), *h = sc.host(total + 256);
+    TierAStage     s("sgr projection");
+    const size_t   px = highbd ? 2 : 1, row = (size_t)width * px, frow = (size_t)width * 4;
     const uint8_t *sb = highbd ? (const uint8_t *)((uintptr_t)src8 << 1) : src8, *db = highbd ? (const uint8_t *)((uintptr_t)dat8 << 1) : dat8;
     const int      r0 = params->r[0], r1 = params->r[1];
-    for (int r = 0; r < height; r++) {
-        memcpy(h + (size_t)r * width * px, sb + (size_t)r * src_stride * px, (size_t)width * px);
-        memcpy(h + pl + (size_t)r * width * px, db + (size_t)r * dat_stride * px, (size_t)width * px);
-        if (r0 > 0)
-            memcpy(h + 2 * pl + (size_t)r * width * 4, flt0 + (size_t)r * flt0_stride, (size_t)width * 4);
-        if (r1 > 0)
-            memcpy(h + 2 * pl + fl + (size_t)r * width * 4, flt1 + (size_t)r * flt1_stride, (size_t)width * 4);
-    }
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, 2 * pl + 2 * fl, hipMemcpyHostToDevice, st));
-    UnitData   u{d, d + pl, (const int32_t *)(d + 2 * pl), (const int32_t *)(d + 2 * pl + fl), (uint32_t)width, (uint32_t)width, (uint32_t)width,
-               (uint32_t)width, (uint32_t)width, (uint32_t)height, highbd != 0, r0, r1};
-    long long *dres = (long long *)(d + 2 * pl + 2 * fl);
-    hipLaunchKernelGGL(sgr_stats_kernel, dim3(1), dim3(1024), 0, st, u, xq0, xq1, want_sums, dres);
+    const size_t   o_src = s.in_rows(sb, (size_t)src_stride * px, height, row), o_dat = s.in_rows(db, (size_t)dat_stride * px, height, row);
+    // an unused filter plane (radius 0) is not read from the caller but keeps its place
+    const size_t   o_f0 = r0 > 0 ? s.in_rows(flt0, (size_t)flt0_stride * 4, height, frow) : s.in(nullptr, height * frow);
+    const size_t   o_f1 = r1 > 0 ? s.in_rows(flt1, (size_t)flt1_stride * 4, height, frow) : s.in(nullptr, height * frow);
+    const size_t   o_res = s.out(80);
+    s.upload();
+    UnitData   u{s.dev(o_src), s.dev(o_dat), s.dev<const int32_t>(o_f0), s.dev<const int32_t>(o_f1), (uint32_t)width, (uint32_t)width,
+               (uint32_t)width, (uint32_t)width, (uint32_t)width, (uint32_t)height, highbd != 0, r0, r1};
+    long long *dres = s.dev<long long>(o_res);
+    hipLaunchKernelGGL(sgr_stats_kernel, dim3(1), dim3(1024), 0, s.stream(), u, xq0, xq1, want_sums, dres);
     if (want_sums && xq_solved)
-        hipLaunchKernelGGL(sgr_solve_kernel, dim3(1), dim3(64), 0, st, (const long long *)dres, width * height, r0, r1, (int32_t *)(dres + 8));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + 2 * pl + 2 * fl, dres, 80, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    memcpy(out, h + 2 * pl + 2 * fl, 6 * sizeof(long long));
+        hipLaunchKernelGGL(sgr_solve_kernel, dim3(1), dim3(64), 0, s.stream(), (const long long *)dres, width * height, r0, r1, (int32_t *)(dres + 8));
+    s.finish(o_res, 80);
+    memcpy(out, s.host(o_res), 6 * sizeof(long long));
     if (xq_solved)
-        memcpy(xq_solved, h + 2 * pl + 2 * fl + 64, 8);
+        memcpy(xq_solved, s.host(o_res) + 64, 8);
 }
 
-static int64_t svt_av1_lowbd_pixel_proj_error_hip_impl(const uint8_t *src8, int32_t width, int32_t height, int32_t src_stride, const uint8_t *dat8, int32_t dat_stride, int32_t *flt0, int32_t flt0_stride, int32_t *flt1, int32_t flt1_stride, int32_t xq[2], const SvtHipSgrParams *params);
-extern "C" int64_t svt_av1_lowbd_pixel_proj_error_hip(const uint8_t *src8, int32_t width, int32_t height, int32_t src_stride, const uint8_t *dat8, int32_t dat_stride, int32_t *flt0, int32_t flt0_stride, int32_t *flt1, int32_t flt1_stride, int32_t xq[2], const SvtHipSgrParams *params) { TIER_A_CALL(svt_av1_lowbd_pixel_proj_error, svt_av1_lowbd_pixel_proj_error_hip_impl(src8, width, height, src_stride, dat8, dat_stride, flt0, flt0_stride, flt1, flt1_stride, xq, params), (src8, width, height, src_stride, dat8, dat_stride, flt0, flt0_stride, flt1, flt1_stride, xq, params)); }
-static int64_t svt_av1_lowbd_pixel_proj_error_hip_impl(const uint8_t *src8, int32_t width, int32_t height, int32_t src_stride, const uint8_t *dat8, int32_t dat_stride, int32_t *flt0, int32_t flt0_stride, int32_t *flt1, int32_t flt1_stride, int32_t xq[2], const SvtHipSgrParams *params) {
+TIER_A_LEAF(int64_t, svt_av1_lowbd_pixel_proj_error,
+            (const uint8_t *src8, int32_t width, int32_t height, int32_t src_stride, const uint8_t *dat8, int32_t dat_stride,
+             int32_t *flt0, int32_t flt0_stride, int32_t *flt1, int32_t flt1_stride, int32_t xq[2], const SvtHipSgrParams *params),
+            (src8, width, height, src_stride, dat8, dat_stride, flt0, flt0_stride, flt1, flt1_stride, xq, params)) {
     long long out[6];
     proj_tier_a(src8, width, height, src_stride, dat8, dat_stride, 0, flt0, flt0_stride, flt1, flt1_stride, params, xq[0], xq[1], 0, out, nullptr);
     return out[5];
 }
-static int64_t svt_av1_highbd_pixel_proj_error_hip_impl(const uint8_t *src8, int32_t width, int32_t height, int32_t src_stride, const uint8_t *dat8, int32_t dat_stride, int32_t *flt0, int32_t flt0_stride, int32_t *flt1, int32_t flt1_stride, int32_t xq[2], const SvtHipSgrParams *params);
-extern "C" int64_t svt_av1_highbd_pixel_proj_error_hip(const uint8_t *src8, int32_t width, int32_t height, int32_t src_stride, const uint8_t *dat8, int32_t dat_stride, int32_t *flt0, int32_t flt0_stride, int32_t *flt1, int32_t flt1_stride, int32_t xq[2], const SvtHipSgrParams *params) { TIER_A_CALL(svt_av1_highbd_pixel_proj_error, svt_av1_highbd_pixel_proj_error_hip_impl(src8, width, height, src_stride, dat8, dat_stride, flt0, flt0_stride, flt1, flt1_stride, xq, params), (src8, width, height, src_stride, dat8, dat_stride, flt0, flt0_stride, flt1, flt1_stride, xq, params)); }
-static int64_t svt_av1_highbd_pixel_proj_error_hip_impl(const uint8_t *src8, int32_t width, int32_t height, int32_t src_stride, const uint8_t *dat8, int32_t dat_stride, int32_t *flt0, int32_t flt0_stride, int32_t *flt1, int32_t flt1_stride, int32_t xq[2], const SvtHipSgrParams *params) {
+TIER_A_LEAF(int64_t, svt_av1_highbd_pixel_proj_error,
+            (const uint8_t *src8, int32_t width, int32_t height, int32_t src_stride, const uint8_t *dat8, int32_t dat_stride,
+             int32_t *flt0, int32_t flt0_stride, int32_t *flt1, int32_t flt1_stride, int32_t xq[2], const SvtHipSgrParams *params),
+            (src8, width, height, src_stride, dat8, dat_stride, flt0, flt0_stride, flt1, flt1_stride, xq, params)) {
     long long out[6];
     proj_tier_a(src8, width, height, src_stride, dat8, dat_stride, 1, flt0, flt0_stride, flt1, flt1_stride, params, xq[0], xq[1], 0, out, nullptr);
     return out[5];
 }
-static void svt_get_proj_subspace_hip_impl(const uint8_t *src8, int width, int height, int src_stride, const uint8_t *dat8, int dat_stride, int use_highbitdepth, int32_t *flt0, int flt0_stride, int32_t *flt1, int flt1_stride, int *xq, const SvtHipSgrParams *params);
-extern "C" void svt_get_proj_subspace_hip(const uint8_t *src8, int width, int height, int src_stride, const uint8_t *dat8, int dat_stride, int use_highbitdepth, int32_t *flt0, int flt0_stride, int32_t *flt1, int flt1_stride, int *xq, const SvtHipSgrParams *params) { TIER_A_CALL(svt_get_proj_subspace, svt_get_proj_subspace_hip_impl(src8, width, height, src_stride, dat8, dat_stride, use_highbitdepth, flt0, flt0_stride, flt1, flt1_stride, xq, params), (src8, width, height, src_stride, dat8, dat_stride, use_highbitdepth, flt0, flt0_stride, flt1, flt1_stride, xq, params)); }
-static void svt_get_proj_subspace_hip_impl(const uint8_t *src8, int width, int height, int src_stride, const uint8_t *dat8, int dat_stride, int use_highbitdepth, int32_t *flt0, int flt0_stride, int32_t *flt1, int flt1_stride, int *xq, const SvtHipSgrParams *params) {
+TIER_A_LEAF(void, svt_get_proj_subspace,
+            (const uint8_t *src8, int width, int height, int src_stride, const uint8_t *dat8, int dat_stride, int use_highbitdepth,
+             int32_t *flt0, int flt0_stride, int32_t *flt1, int flt1_stride, int *xq, const SvtHipSgrParams *params),
+            (src8, width, height, src_stride, dat8, dat_stride, use_highbitdepth, flt0, flt0_stride, flt1, flt1_stride, xq, params)) {
     long long out[6];
     int32_t   solved[2] = {0, 0};
     proj_tier_a(src8, width, height, src_stride, dat8, dat_stride, use_highbitdepth, flt0, flt0_stride, flt1, flt1_stride, params, 0, 0, 1, out,

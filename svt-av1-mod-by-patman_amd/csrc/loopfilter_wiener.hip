@@ -333,8 +333,6 @@ __global__ __launch_bounds__(256) void wiener_convolve_kernel(const void *__rest
     lr::wiener_tile_filter<256>(in, tmp, threadIdx.x, tw, th, x0, y0, f.x, f.y, bd, r0, r1, is16, dst, dst_stride);
 }
 
-[[noreturn]] void fatal(const char *what) { svthip::tier_a_throw("%s: %s", what, svt_hip_last_error()); }
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 struct AuxBuf {  // per-thread grow-only device buffer for the raw first moments, guarded by an event against reuse from another stream
     StatsAux  *dev = nullptr;
@@ -440,72 +438,64 @@ extern "C" int32_t svt_hip_wiener_convolve(const void *d_src, uint32_t src_strid
 // ------------------------------------------------------------------------------------------------ Tier A
 static void stats_tier_a(int32_t win, const uint8_t *dgd8, const uint8_t *src8, int32_t h_start, int32_t h_end, int32_t v_start, int32_t v_end,
                          int32_t dgd_stride, int32_t src_stride, int64_t *M, int64_t *H, int is16, int bit_depth) {
-    if (!ensure_init())
-        fatal("compute_stats");
-    const int    half = win >> 1, w = h_end - h_start, h = v_end - v_start, px = is16 ? 2 : 1;
-    const size_t dp = (size_t)w + 2 * half, dbytes = up256(dp * (h + 2 * half) * px), sbytes = up256((size_t)w * h * px);
-    const size_t obytes = sizeof(int64_t) * (W2MAX + W2MAX * W2MAX);
-    hipStream_t  st = resolve_stream(nullptr);
-    Scratch     &sc = tls_scratch();
-    uint8_t     *d = sc.device(dbytes + sbytes + obytes + 256), *hh = sc.host(dbytes + sbytes + obytes + 256);
+    TierAStage   s("compute_stats");
+    const int    half = win >> 1, w = h_end - h_start, h = v_end - v_start, px = is16 ? 2 : 1, w2 = win * win;
+    const size_t dp = (size_t)w + 2 * half, obytes = sizeof(int64_t) * (W2MAX + W2MAX * W2MAX);
     const uint8_t *db = is16 ? (const uint8_t *)((uintptr_t)dgd8 << 1) : dgd8, *sb = is16 ? (const uint8_t *)((uintptr_t)src8 << 1) : src8;
-    for (int r = 0; r < h + 2 * half; r++)
-        memcpy(hh + (size_t)r * dp * px, db + ((ptrdiff_t)(v_start + r - half) * dgd_stride + (h_start - half)) * px, dp * px);
-    for (int r = 0; r < h; r++) memcpy(hh + dbytes + (size_t)r * w * px, sb + ((ptrdiff_t)(v_start + r) * src_stride + h_start) * px, (size_t)w * px);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, hh, dbytes + sbytes, hipMemcpyHostToDevice, st));
-    SvtHipWienerUnit u{d + ((size_t)half * dp + half) * px, d + dbytes, (uint32_t)dp, (uint32_t)w, 0, w, 0, h};
-    int64_t         *dM = (int64_t *)(d + dbytes + sbytes), *dH = dM + W2MAX;
-    if (svt_hip_wiener_stats(&u, 1, win, is16, bit_depth, dM, dH, st) != SVT_HIP_OK)
+    const size_t o_dgd = s.in_rows(db + ((ptrdiff_t)(v_start - half) * dgd_stride + (h_start - half)) * px, (size_t)dgd_stride * px, h + 2 * half, dp * px);
+    const size_t o_src = s.in_rows(sb + ((ptrdiff_t)v_start * src_stride + h_start) * px, (size_t)src_stride * px, h, (size_t)w * px);
+    const size_t o_out = s.out(obytes);
+    s.upload();
+    SvtHipWienerUnit u{s.dev(o_dgd) + ((size_t)half * dp + half) * px, s.dev(o_src), (uint32_t)dp, (uint32_t)w, 0, w, 0, h};
+    int64_t         *dM = s.dev<int64_t>(o_out);
+    if (svt_hip_wiener_stats(&u, 1, win, is16, bit_depth, dM, dM + W2MAX, s.stream()) != SVT_HIP_OK)
         fatal("compute_stats");
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(hh + dbytes + sbytes, dM, obytes, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    const int w2 = win * win;
-    memcpy(M, hh + dbytes + sbytes, sizeof(int64_t) * w2);
-    memcpy(H, hh + dbytes + sbytes + sizeof(int64_t) * W2MAX, sizeof(int64_t) * w2 * w2);
+    s.finish(o_out, obytes);
+    memcpy(M, s.host(o_out), sizeof(int64_t) * w2);
+    memcpy(H, s.host(o_out) + sizeof(int64_t) * W2MAX, sizeof(int64_t) * w2 * w2);
 }
-static void svt_av1_compute_stats_hip_impl(int32_t wiener_win, const uint8_t *dgd8, const uint8_t *src8, int32_t h_start, int32_t h_end, int32_t v_start, int32_t v_end, int32_t dgd_stride, int32_t src_stride, int64_t *M, int64_t *H);
-extern "C" void svt_av1_compute_stats_hip(int32_t wiener_win, const uint8_t *dgd8, const uint8_t *src8, int32_t h_start, int32_t h_end, int32_t v_start, int32_t v_end, int32_t dgd_stride, int32_t src_stride, int64_t *M, int64_t *H) { TIER_A_CALL(svt_av1_compute_stats, svt_av1_compute_stats_hip_impl(wiener_win, dgd8, src8, h_start, h_end, v_start, v_end, dgd_stride, src_stride, M, H), (wiener_win, dgd8, src8, h_start, h_end, v_start, v_end, dgd_stride, src_stride, M, H)); }
-static void svt_av1_compute_stats_hip_impl(int32_t wiener_win, const uint8_t *dgd8, const uint8_t *src8, int32_t h_start, int32_t h_end, int32_t v_start, int32_t v_end, int32_t dgd_stride, int32_t src_stride, int64_t *M, int64_t *H) {
+TIER_A_LEAF(void, svt_av1_compute_stats,
+            (int32_t wiener_win, const uint8_t *dgd8, const uint8_t *src8, int32_t h_start, int32_t h_end, int32_t v_start, int32_t
+             v_end, int32_t dgd_stride, int32_t src_stride, int64_t *M, int64_t *H),
+            (wiener_win, dgd8, src8, h_start, h_end, v_start, v_end, dgd_stride, src_stride, M, H)) {
     stats_tier_a(wiener_win, dgd8, src8, h_start, h_end, v_start, v_end, dgd_stride, src_stride, M, H, 0, 8);
 }
-static void svt_av1_compute_stats_highbd_hip_impl(int32_t wiener_win, const uint8_t *dgd8, const uint8_t *src8, int32_t h_start, int32_t h_end, int32_t v_start, int32_t v_end, int32_t dgd_stride, int32_t src_stride, int64_t *M, int64_t *H, int32_t bit_depth);
-extern "C" void svt_av1_compute_stats_highbd_hip(int32_t wiener_win, const uint8_t *dgd8, const uint8_t *src8, int32_t h_start, int32_t h_end, int32_t v_start, int32_t v_end, int32_t dgd_stride, int32_t src_stride, int64_t *M, int64_t *H, int32_t bit_depth) { TIER_A_CALL(svt_av1_compute_stats_highbd, svt_av1_compute_stats_highbd_hip_impl(wiener_win, dgd8, src8, h_start, h_end, v_start, v_end, dgd_stride, src_stride, M, H, bit_depth), (wiener_win, dgd8, src8, h_start, h_end, v_start, v_end, dgd_stride, src_stride, M, H, bit_depth)); }
-static void svt_av1_compute_stats_highbd_hip_impl(int32_t wiener_win, const uint8_t *dgd8, const uint8_t *src8, int32_t h_start, int32_t h_end, int32_t v_start, int32_t v_end, int32_t dgd_stride, int32_t src_stride, int64_t *M, int64_t *H, int32_t bit_depth) {
+TIER_A_LEAF(void, svt_av1_compute_stats_highbd,
+            (int32_t wiener_win, const uint8_t *dgd8, const uint8_t *src8, int32_t h_start, int32_t h_end, int32_t v_start, int32_t
+             v_end, int32_t dgd_stride, int32_t src_stride, int64_t *M, int64_t *H, int32_t bit_depth),
+            (wiener_win, dgd8, src8, h_start, h_end, v_start, v_end, dgd_stride, src_stride, M, H, bit_depth)) {
     stats_tier_a(wiener_win, dgd8, src8, h_start, h_end, v_start, v_end, dgd_stride, src_stride, M, H, 1, bit_depth);
 }
 
 static void convolve_tier_a(const uint8_t *src, ptrdiff_t src_stride, uint8_t *dst, ptrdiff_t dst_stride, const int16_t *fx, const int16_t *fy,
                             int32_t w, int32_t h, int is16, int bd) {
-    if (!ensure_init())
-        fatal("wiener_convolve_add_src");
+    TierAStage   s("wiener_convolve_add_src");
     const int    px = is16 ? 2 : 1;
-    const size_t ip = (size_t)w + 8, ibytes = up256(ip * (h + 8) * px), obytes = up256((size_t)w * h * px);
-    hipStream_t  st = resolve_stream(nullptr);
-    Scratch     &sc = tls_scratch();
-    uint8_t     *d = sc.device(ibytes + obytes + 256), *hh = sc.host(ibytes + obytes + 256);
+    const size_t ip = (size_t)w + 8, o_in = s.in(nullptr, ip * (h + 8) * px), o_out = s.out((size_t)w * h * px);
     const uint8_t *sb = is16 ? (const uint8_t *)((uintptr_t)src << 1) : src;
-    uint8_t       *ob = is16 ? (uint8_t *)((uintptr_t)dst << 1) : dst;
-    for (int r = 0; r < h + 7; r++) memcpy(hh + (size_t)r * ip * px, sb + ((ptrdiff_t)(r - 3) * src_stride - 3) * px, (size_t)(w + 7) * px);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, hh, ibytes, hipMemcpyHostToDevice, st));
+    copy_rows(s.host(o_in), ip * px, sb - (3 * src_stride + 3) * px, (size_t)src_stride * px, h + 7, (size_t)(w + 7) * px);
+    s.upload();
     // the reference reads its kernels through a 256-byte aligned table base + offset (convolve.c:45-54): with step 16 that is
     // the kernel at the pointer itself; the 8th coefficient of a Wiener kernel is always zero
     int16_t kx[8], ky[8];
     memcpy(kx, fx, 16), memcpy(ky, fy, 16);
-    if (svt_hip_wiener_convolve(d + (3 * ip + 3) * px, (uint32_t)ip, d + ibytes, (uint32_t)w, (uint32_t)w, (uint32_t)h, kx, ky, is16, bd, st) != SVT_HIP_OK)
+    if (svt_hip_wiener_convolve(s.dev(o_in) + (3 * ip + 3) * px, (uint32_t)ip, s.dev(o_out), (uint32_t)w, (uint32_t)w, (uint32_t)h, kx, ky, is16, bd,
+                                s.stream()) != SVT_HIP_OK)
         fatal("wiener_convolve_add_src");
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(hh + ibytes, d + ibytes, obytes, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    for (int r = 0; r < h; r++) memcpy(ob + (size_t)r * dst_stride * px, hh + ibytes + (size_t)r * w * px, (size_t)w * px);
+    s.finish(o_out, (size_t)w * h * px);
+    s.out_rows(is16 ? (uint8_t *)((uintptr_t)dst << 1) : dst, (size_t)dst_stride * px, o_out, h, (size_t)w * px);
 }
-static void svt_av1_wiener_convolve_add_src_hip_impl(const uint8_t *src, ptrdiff_t src_stride, uint8_t *dst, ptrdiff_t dst_stride, const int16_t *filter_x, const int16_t *filter_y, int32_t w, int32_t h, const SvtHipConvolveParams *conv_params);
-extern "C" void svt_av1_wiener_convolve_add_src_hip(const uint8_t *src, ptrdiff_t src_stride, uint8_t *dst, ptrdiff_t dst_stride, const int16_t *filter_x, const int16_t *filter_y, int32_t w, int32_t h, const SvtHipConvolveParams *conv_params) { TIER_A_CALL(svt_av1_wiener_convolve_add_src, svt_av1_wiener_convolve_add_src_hip_impl(src, src_stride, dst, dst_stride, filter_x, filter_y, w, h, conv_params), (src, src_stride, dst, dst_stride, filter_x, filter_y, w, h, conv_params)); }
-static void svt_av1_wiener_convolve_add_src_hip_impl(const uint8_t *src, ptrdiff_t src_stride, uint8_t *dst, ptrdiff_t dst_stride, const int16_t *filter_x, const int16_t *filter_y, int32_t w, int32_t h, const SvtHipConvolveParams *conv_params) {
+TIER_A_LEAF(void, svt_av1_wiener_convolve_add_src,
+            (const uint8_t *src, ptrdiff_t src_stride, uint8_t *dst, ptrdiff_t dst_stride, const int16_t *filter_x, const int16_t
+             *filter_y, int32_t w, int32_t h, const SvtHipConvolveParams *conv_params),
+            (src, src_stride, dst, dst_stride, filter_x, filter_y, w, h, conv_params)) {
     (void)conv_params;  // get_conv_params_wiener(8) is the only value the reference passes (restoration.c:443)
     convolve_tier_a(src, src_stride, dst, dst_stride, filter_x, filter_y, w, h, 0, 8);
 }
-static void svt_av1_highbd_wiener_convolve_add_src_hip_impl(const uint8_t *src, ptrdiff_t src_stride, uint8_t *dst, ptrdiff_t dst_stride, const int16_t *filter_x, const int16_t *filter_y, int32_t w, int32_t h, const SvtHipConvolveParams *conv_params, int32_t bd);
-extern "C" void svt_av1_highbd_wiener_convolve_add_src_hip(const uint8_t *src, ptrdiff_t src_stride, uint8_t *dst, ptrdiff_t dst_stride, const int16_t *filter_x, const int16_t *filter_y, int32_t w, int32_t h, const SvtHipConvolveParams *conv_params, int32_t bd) { TIER_A_CALL(svt_av1_highbd_wiener_convolve_add_src, svt_av1_highbd_wiener_convolve_add_src_hip_impl(src, src_stride, dst, dst_stride, filter_x, filter_y, w, h, conv_params, bd), (src, src_stride, dst, dst_stride, filter_x, filter_y, w, h, conv_params, bd)); }
-static void svt_av1_highbd_wiener_convolve_add_src_hip_impl(const uint8_t *src, ptrdiff_t src_stride, uint8_t *dst, ptrdiff_t dst_stride, const int16_t *filter_x, const int16_t *filter_y, int32_t w, int32_t h, const SvtHipConvolveParams *conv_params, int32_t bd) {
+TIER_A_LEAF(void, svt_av1_highbd_wiener_convolve_add_src,
+            (const uint8_t *src, ptrdiff_t src_stride, uint8_t *dst, ptrdiff_t dst_stride, const int16_t *filter_x, const int16_t
+             *filter_y, int32_t w, int32_t h, const SvtHipConvolveParams *conv_params, int32_t bd),
+            (src, src_stride, dst, dst_stride, filter_x, filter_y, w, h, conv_params, bd)) {
     (void)conv_params;
     convolve_tier_a(src, src_stride, dst, dst_stride, filter_x, filter_y, w, h, 1, bd);
 }

@@ -161,41 +161,34 @@ extern "C" int32_t svt_hip_sad_loop_batch(const uint8_t *d_base, const SvtHipSad
 // ------------------------------------------------------------------------------------------------
 // Tier A — host pointers in/out, one block per call.  Each call stages the byte span it touches.
 // ------------------------------------------------------------------------------------------------
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-static void svt_sad_loop_kernel_hip_impl(uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t block_height, uint32_t block_width, uint64_t *best_sad, int16_t *x_search_center, int16_t *y_search_center, uint32_t src_stride_raw, uint8_t skip_search_line, int16_t search_area_width, int16_t search_area_height);
-extern "C" void svt_sad_loop_kernel_hip(uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t block_height, uint32_t block_width, uint64_t *best_sad, int16_t *x_search_center, int16_t *y_search_center, uint32_t src_stride_raw, uint8_t skip_search_line, int16_t search_area_width, int16_t search_area_height) { TIER_A_CALL(svt_sad_loop_kernel, svt_sad_loop_kernel_hip_impl(src, src_stride, ref, ref_stride, block_height, block_width, best_sad, x_search_center, y_search_center, src_stride_raw, skip_search_line, search_area_width, search_area_height), (src, src_stride, ref, ref_stride, block_height, block_width, best_sad, x_search_center, y_search_center, src_stride_raw, skip_search_line, search_area_width, search_area_height)); }
-static void svt_sad_loop_kernel_hip_impl(uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t block_height, uint32_t block_width, uint64_t *best_sad, int16_t *x_search_center, int16_t *y_search_center, uint32_t src_stride_raw, uint8_t skip_search_line, int16_t search_area_width, int16_t search_area_height) {
+TIER_A_LEAF(void, svt_sad_loop_kernel,
+            (uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t block_height, uint32_t block_width,
+             uint64_t *best_sad, int16_t *x_search_center, int16_t *y_search_center, uint32_t src_stride_raw, uint8_t
+             skip_search_line, int16_t search_area_width, int16_t search_area_height),
+            (src, src_stride, ref, ref_stride, block_height, block_width, best_sad, x_search_center, y_search_center,
+             src_stride_raw, skip_search_line, search_area_width, search_area_height)) {
     *best_sad = 0xffffff;
     if (search_area_width <= 0 || search_area_height <= 0 || block_width == 0 || block_height == 0)
         return;
-    if (!ensure_init()) 
-        svthip::tier_a_throw("%s", svt_hip_last_error());
-    hipStream_t  st = resolve_stream(nullptr);
-    Scratch     &sc = tls_scratch();
+    TierAStage   s("svt_sad_loop_kernel");
     const size_t src_span = (size_t)(block_height - 1) * src_stride + block_width;
     const size_t ref_span = (size_t)(search_area_height - 1) * src_stride_raw + (size_t)(block_height - 1) * ref_stride +
         (size_t)search_area_width + block_width - 1;
-    const size_t off_src = 0, off_ref = align_up(src_span + 64, 256);
-    const size_t off_desc = off_ref + align_up(ref_span + 64, 256), off_res = off_desc + 256;
-    const size_t total = off_res + 256;
-    uint8_t     *d = sc.device(total), *h = sc.host(total);
-    memcpy(h + off_src, src, src_span);
-    memcpy(h + off_ref, ref, ref_span);
-    SvtHipSadLoopDesc *dd = (SvtHipSadLoopDesc *)(h + off_desc);
+    // 64 bytes of slack behind each plane: the kernel stages whole dwords
+    const size_t off_src = s.in(src, src_span, 64), off_ref = s.in(ref, ref_span, 64);
+    const size_t off_desc = s.in(nullptr, sizeof(SvtHipSadLoopDesc)), off_res = s.out(sizeof(SvtHipSadLoopResult));
+    SvtHipSadLoopDesc *dd = s.host<SvtHipSadLoopDesc>(off_desc);
     memset(dd, 0, sizeof(*dd));
     dd->src_off = off_src, dd->ref_off = off_ref;
     dd->src_stride = src_stride, dd->ref_stride = ref_stride, dd->src_stride_raw = src_stride_raw;
     dd->block_width = (uint16_t)block_width, dd->block_height = (uint16_t)block_height;
     dd->search_area_width = search_area_width, dd->search_area_height = search_area_height;
     dd->skip_search_line = skip_search_line;
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, off_res, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(sad_loop_batch_kernel, dim3(1), dim3(WG_THREADS), 0, st, d, (const SvtHipSadLoopDesc *)(d + off_desc),
-                       (SvtHipSadLoopResult *)(d + off_res), 1u);
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + off_res, d + off_res, sizeof(SvtHipSadLoopResult), hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    const SvtHipSadLoopResult *r = (const SvtHipSadLoopResult *)(h + off_res);
+    s.upload();
+    hipLaunchKernelGGL(sad_loop_batch_kernel, dim3(1), dim3(WG_THREADS), 0, s.stream(), s.dev<const uint8_t>(0),
+                       s.dev<const SvtHipSadLoopDesc>(off_desc), s.dev<SvtHipSadLoopResult>(off_res), 1u);
+    s.finish(off_res, sizeof(SvtHipSadLoopResult));
+    const SvtHipSadLoopResult *r = s.host<SvtHipSadLoopResult>(off_res);
     *best_sad                    = r->best_sad;
     if (!(r->best_sad == 0xffffff && r->x == 0x7fff)) {
         *x_search_center = r->x;
@@ -203,54 +196,40 @@ static void svt_sad_loop_kernel_hip_impl(uint8_t *src, uint32_t src_stride, uint
     }
 }
 
-static uint32_t svt_nxm_sad_kernel_hip_impl(const uint8_t *src, uint32_t src_stride, const uint8_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width);
-extern "C" uint32_t svt_nxm_sad_kernel_hip(const uint8_t *src, uint32_t src_stride, const uint8_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width) { TIER_A_CALL(svt_nxm_sad_kernel, svt_nxm_sad_kernel_hip_impl(src, src_stride, ref, ref_stride, height, width), (src, src_stride, ref, ref_stride, height, width)); }
-static uint32_t svt_nxm_sad_kernel_hip_impl(const uint8_t *src, uint32_t src_stride, const uint8_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width) {
+TIER_A_LEAF(uint32_t, svt_nxm_sad_kernel,
+            (const uint8_t *src, uint32_t src_stride, const uint8_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width),
+            (src, src_stride, ref, ref_stride, height, width)) {
     if (height == 0 || width == 0)
         return 0;
-    if (!ensure_init()) 
-        svthip::tier_a_throw("%s", svt_hip_last_error());
-    hipStream_t  st = resolve_stream(nullptr);
-    Scratch     &sc = tls_scratch();
-    const size_t src_span = (size_t)(height - 1) * src_stride + width, ref_span = (size_t)(height - 1) * ref_stride + width;
-    const size_t off_ref = align_up(src_span, 256), off_res = off_ref + align_up(ref_span, 256);
-    uint8_t     *d = sc.device(off_res + 256), *h = sc.host(off_res + 256);
-    memcpy(h, src, src_span);
-    memcpy(h + off_ref, ref, ref_span);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, off_res, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(nxm_sad_kernel, dim3(1), dim3(WG_THREADS), 0, st, d, src_stride, d + off_ref, ref_stride, height,
-                       width, (uint32_t *)(d + off_res));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + off_res, d + off_res, 4, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    return *(uint32_t *)(h + off_res);
+    TierAStage   s("svt_nxm_sad_kernel");
+    const size_t off_src = s.in(src, (size_t)(height - 1) * src_stride + width);
+    const size_t off_ref = s.in(ref, (size_t)(height - 1) * ref_stride + width), off_res = s.out(4);
+    s.upload();
+    hipLaunchKernelGGL(nxm_sad_kernel, dim3(1), dim3(WG_THREADS), 0, s.stream(), s.dev<const uint8_t>(off_src), src_stride,
+                       s.dev<const uint8_t>(off_ref), ref_stride, height, width, s.dev<uint32_t>(off_res));
+    s.finish(off_res, 4);
+    return *s.host<uint32_t>(off_res);
 }
 
-static void svt_ext_all_sad_calculation_8x8_16x16_hip_impl(uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t mv, uint32_t *p_best_sad_8x8, uint32_t *p_best_sad_16x16, uint32_t *p_best_mv8x8, uint32_t *p_best_mv16x16, uint32_t p_eight_sad16x16[16][8], uint32_t p_eight_sad8x8[64][8], uint8_t sub_sad);
-extern "C" void svt_ext_all_sad_calculation_8x8_16x16_hip(uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t mv, uint32_t *p_best_sad_8x8, uint32_t *p_best_sad_16x16, uint32_t *p_best_mv8x8, uint32_t *p_best_mv16x16, uint32_t p_eight_sad16x16[16][8], uint32_t p_eight_sad8x8[64][8], uint8_t sub_sad) { TIER_A_CALL(svt_ext_all_sad_calculation_8x8_16x16, svt_ext_all_sad_calculation_8x8_16x16_hip_impl(src, src_stride, ref, ref_stride, mv, p_best_sad_8x8, p_best_sad_16x16, p_best_mv8x8, p_best_mv16x16, p_eight_sad16x16, p_eight_sad8x8, sub_sad), (src, src_stride, ref, ref_stride, mv, p_best_sad_8x8, p_best_sad_16x16, p_best_mv8x8, p_best_mv16x16, p_eight_sad16x16, p_eight_sad8x8, sub_sad)); }
-static void svt_ext_all_sad_calculation_8x8_16x16_hip_impl(uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t mv, uint32_t *p_best_sad_8x8, uint32_t *p_best_sad_16x16, uint32_t *p_best_mv8x8, uint32_t *p_best_mv16x16, uint32_t p_eight_sad16x16[16][8], uint32_t p_eight_sad8x8[64][8], uint8_t sub_sad) {
+TIER_A_LEAF(void, svt_ext_all_sad_calculation_8x8_16x16,
+            (uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t mv, uint32_t *p_best_sad_8x8, uint32_t
+             *p_best_sad_16x16, uint32_t *p_best_mv8x8, uint32_t *p_best_mv16x16, uint32_t p_eight_sad16x16[16][8], uint32_t
+             p_eight_sad8x8[64][8], uint8_t sub_sad),
+            (src, src_stride, ref, ref_stride, mv, p_best_sad_8x8, p_best_sad_16x16, p_best_mv8x8, p_best_mv16x16, p_eight_sad16x16,
+             p_eight_sad8x8, sub_sad)) {
     (void)p_eight_sad8x8;  // not written by the reference either (motion_estimation.c:218)
-    if (!ensure_init()) 
-        svthip::tier_a_throw("%s", svt_hip_last_error());
-    hipStream_t  st = resolve_stream(nullptr);
-    Scratch     &sc = tls_scratch();
-    const size_t src_span = (size_t)63 * src_stride + 64, ref_span = (size_t)63 * ref_stride + 64 + 7;
-    const size_t off_ref = align_up(src_span, 256), off_io = off_ref + align_up(ref_span, 256);
-    const size_t total = off_io + align_up(sizeof(ExtAllIo), 256);
-    uint8_t     *d = sc.device(total), *h = sc.host(total);
-    memcpy(h, src, src_span);
-    memcpy(h + off_ref, ref, ref_span);
-    ExtAllIo *io = (ExtAllIo *)(h + off_io);
+    TierAStage   s("svt_ext_all_sad_calculation_8x8_16x16");
+    const size_t off_src = s.in(src, (size_t)63 * src_stride + 64), off_ref = s.in(ref, (size_t)63 * ref_stride + 64 + 7);
+    const size_t off_io = s.in(nullptr, sizeof(ExtAllIo));
+    ExtAllIo    *io = s.host<ExtAllIo>(off_io);
     memcpy(io->best8, p_best_sad_8x8, sizeof(io->best8));
     memcpy(io->best16, p_best_sad_16x16, sizeof(io->best16));
     memcpy(io->mv8, p_best_mv8x8, sizeof(io->mv8));
     memcpy(io->mv16, p_best_mv16x16, sizeof(io->mv16));
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(ext_all_sad_kernel, dim3(1), dim3(WG_THREADS), 0, st, d, src_stride, d + off_ref, ref_stride, mv,
-                       (uint32_t)(sub_sad != 0), (ExtAllIo *)(d + off_io));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(io, d + off_io, sizeof(ExtAllIo), hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
+    s.upload();
+    hipLaunchKernelGGL(ext_all_sad_kernel, dim3(1), dim3(WG_THREADS), 0, s.stream(), s.dev<const uint8_t>(off_src), src_stride,
+                       s.dev<const uint8_t>(off_ref), ref_stride, mv, (uint32_t)(sub_sad != 0), s.dev<ExtAllIo>(off_io));
+    s.finish(off_io, sizeof(ExtAllIo));
     memcpy(p_best_sad_8x8, io->best8, sizeof(io->best8));
     memcpy(p_best_sad_16x16, io->best16, sizeof(io->best16));
     memcpy(p_best_mv8x8, io->mv8, sizeof(io->mv8));
@@ -266,9 +245,10 @@ static inline uint32_t mv_add_x(uint32_t mv, uint32_t p) {
     const int16_t x = (int16_t)((int16_t)(mv & 0xffff) + (int16_t)p), y = (int16_t)(mv >> 16);
     return ((uint32_t)(uint16_t)y << 16) | (uint16_t)x;
 }
-static void svt_ext_eight_sad_calculation_32x32_64x64_hip_impl(uint32_t p_sad16x16[16][8], uint32_t *p_best_sad_32x32, uint32_t *p_best_sad_64x64, uint32_t *p_best_mv32x32, uint32_t *p_best_mv64x64, uint32_t mv, uint32_t p_sad32x32[4][8]);
-extern "C" void svt_ext_eight_sad_calculation_32x32_64x64_hip(uint32_t p_sad16x16[16][8], uint32_t *p_best_sad_32x32, uint32_t *p_best_sad_64x64, uint32_t *p_best_mv32x32, uint32_t *p_best_mv64x64, uint32_t mv, uint32_t p_sad32x32[4][8]) { TIER_A_CALL(svt_ext_eight_sad_calculation_32x32_64x64, svt_ext_eight_sad_calculation_32x32_64x64_hip_impl(p_sad16x16, p_best_sad_32x32, p_best_sad_64x64, p_best_mv32x32, p_best_mv64x64, mv, p_sad32x32), (p_sad16x16, p_best_sad_32x32, p_best_sad_64x64, p_best_mv32x32, p_best_mv64x64, mv, p_sad32x32)); }
-static void svt_ext_eight_sad_calculation_32x32_64x64_hip_impl(uint32_t p_sad16x16[16][8], uint32_t *p_best_sad_32x32, uint32_t *p_best_sad_64x64, uint32_t *p_best_mv32x32, uint32_t *p_best_mv64x64, uint32_t mv, uint32_t p_sad32x32[4][8]) {
+TIER_A_LEAF(void, svt_ext_eight_sad_calculation_32x32_64x64,
+            (uint32_t p_sad16x16[16][8], uint32_t *p_best_sad_32x32, uint32_t *p_best_sad_64x64, uint32_t *p_best_mv32x32, uint32_t
+             *p_best_mv64x64, uint32_t mv, uint32_t p_sad32x32[4][8]),
+            (p_sad16x16, p_best_sad_32x32, p_best_sad_64x64, p_best_mv32x32, p_best_mv64x64, mv, p_sad32x32)) {
     for (uint32_t p = 0; p < 8; p++) {
         uint32_t t = 0;
         for (uint32_t k = 0; k < 4; k++) {
@@ -283,9 +263,10 @@ static void svt_ext_eight_sad_calculation_32x32_64x64_hip_impl(uint32_t p_sad16x
             p_best_sad_64x64[0] = t, p_best_mv64x64[0] = mv_add_x(mv, p);
     }
 }
-static void svt_ext_sad_calculation_32x32_64x64_hip_impl(uint32_t *p_sad16x16, uint32_t *p_best_sad_32x32, uint32_t *p_best_sad_64x64, uint32_t *p_best_mv32x32, uint32_t *p_best_mv64x64, uint32_t mv, uint32_t *p_sad32x32);
-extern "C" void svt_ext_sad_calculation_32x32_64x64_hip(uint32_t *p_sad16x16, uint32_t *p_best_sad_32x32, uint32_t *p_best_sad_64x64, uint32_t *p_best_mv32x32, uint32_t *p_best_mv64x64, uint32_t mv, uint32_t *p_sad32x32) { TIER_A_CALL(svt_ext_sad_calculation_32x32_64x64, svt_ext_sad_calculation_32x32_64x64_hip_impl(p_sad16x16, p_best_sad_32x32, p_best_sad_64x64, p_best_mv32x32, p_best_mv64x64, mv, p_sad32x32), (p_sad16x16, p_best_sad_32x32, p_best_sad_64x64, p_best_mv32x32, p_best_mv64x64, mv, p_sad32x32)); }
-static void svt_ext_sad_calculation_32x32_64x64_hip_impl(uint32_t *p_sad16x16, uint32_t *p_best_sad_32x32, uint32_t *p_best_sad_64x64, uint32_t *p_best_mv32x32, uint32_t *p_best_mv64x64, uint32_t mv, uint32_t *p_sad32x32) {
+TIER_A_LEAF(void, svt_ext_sad_calculation_32x32_64x64,
+            (uint32_t *p_sad16x16, uint32_t *p_best_sad_32x32, uint32_t *p_best_sad_64x64, uint32_t *p_best_mv32x32, uint32_t
+             *p_best_mv64x64, uint32_t mv, uint32_t *p_sad32x32),
+            (p_sad16x16, p_best_sad_32x32, p_best_sad_64x64, p_best_mv32x32, p_best_mv64x64, mv, p_sad32x32)) {
     uint32_t t = 0;
     for (uint32_t k = 0; k < 4; k++) {
         const uint32_t s = p_sad16x16[4 * k] + p_sad16x16[4 * k + 1] + p_sad16x16[4 * k + 2] + p_sad16x16[4 * k + 3];
@@ -298,9 +279,12 @@ static void svt_ext_sad_calculation_32x32_64x64_hip_impl(uint32_t *p_sad16x16, u
         p_best_sad_64x64[0] = t, p_best_mv64x64[0] = mv;
 }
 
-static void svt_ext_sad_calculation_8x8_16x16_hip_impl(uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t *p_best_sad_8x8, uint32_t *p_best_sad_16x16, uint32_t *p_best_mv8x8, uint32_t *p_best_mv16x16, uint32_t mv, uint32_t *p_sad16x16, uint32_t *p_sad8x8, uint8_t sub_sad);
-extern "C" void svt_ext_sad_calculation_8x8_16x16_hip(uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t *p_best_sad_8x8, uint32_t *p_best_sad_16x16, uint32_t *p_best_mv8x8, uint32_t *p_best_mv16x16, uint32_t mv, uint32_t *p_sad16x16, uint32_t *p_sad8x8, uint8_t sub_sad) { TIER_A_CALL(svt_ext_sad_calculation_8x8_16x16, svt_ext_sad_calculation_8x8_16x16_hip_impl(src, src_stride, ref, ref_stride, p_best_sad_8x8, p_best_sad_16x16, p_best_mv8x8, p_best_mv16x16, mv, p_sad16x16, p_sad8x8, sub_sad), (src, src_stride, ref, ref_stride, p_best_sad_8x8, p_best_sad_16x16, p_best_mv8x8, p_best_mv16x16, mv, p_sad16x16, p_sad8x8, sub_sad)); }
-static void svt_ext_sad_calculation_8x8_16x16_hip_impl(uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t *p_best_sad_8x8, uint32_t *p_best_sad_16x16, uint32_t *p_best_mv8x8, uint32_t *p_best_mv16x16, uint32_t mv, uint32_t *p_sad16x16, uint32_t *p_sad8x8, uint8_t sub_sad) {
+TIER_A_LEAF(void, svt_ext_sad_calculation_8x8_16x16,
+            (uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t *p_best_sad_8x8, uint32_t
+             *p_best_sad_16x16, uint32_t *p_best_mv8x8, uint32_t *p_best_mv16x16, uint32_t mv, uint32_t *p_sad16x16, uint32_t
+             *p_sad8x8, uint8_t sub_sad),
+            (src, src_stride, ref, ref_stride, p_best_sad_8x8, p_best_sad_16x16, p_best_mv8x8, p_best_mv16x16, mv, p_sad16x16,
+             p_sad8x8, sub_sad)) {
     // four 8x8 SADs of one 16x16 block at one position: four device N x M SADs
     uint32_t total = 0;
     for (uint32_t q = 0; q < 4; q++) {

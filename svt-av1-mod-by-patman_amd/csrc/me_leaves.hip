@@ -19,8 +19,6 @@ namespace {
 
 constexpr int WG = 256;
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-[[noreturn]] void fatal(const char *what) { svthip::tier_a_throw("%s: %s", what, svt_hip_last_error()); }
 
 __device__ __forceinline__ uint32_t wave_add(uint32_t v) {
 #pragma unroll
@@ -101,57 +99,48 @@ __global__ __launch_bounds__(WG) void pme_sad_kernel(PmeArgs a) {
 
 }  // namespace
 
-static uint32_t svt_nxm_sad_kernel_sub_sampled_hip_impl(const uint8_t *src, uint32_t src_stride, const uint8_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width);
-extern "C" uint32_t svt_nxm_sad_kernel_sub_sampled_hip(const uint8_t *src, uint32_t src_stride, const uint8_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width) { TIER_A_CALL(svt_nxm_sad_kernel_sub_sampled, svt_nxm_sad_kernel_sub_sampled_hip_impl(src, src_stride, ref, ref_stride, height, width), (src, src_stride, ref, ref_stride, height, width)); }
-static uint32_t svt_nxm_sad_kernel_sub_sampled_hip_impl(const uint8_t *src, uint32_t src_stride, const uint8_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width) {
+TIER_A_LEAF(uint32_t, svt_nxm_sad_kernel_sub_sampled,
+            (const uint8_t *src, uint32_t src_stride, const uint8_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width),
+            (src, src_stride, ref, ref_stride, height, width)) {
     return svt_nxm_sad_kernel_hip(src, src_stride, ref, ref_stride, height, width);
 }
 
-static uint32_t svt_aom_sad_16b_kernel_hip_impl(uint16_t *src, uint32_t src_stride, uint16_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width);
-extern "C" uint32_t svt_aom_sad_16b_kernel_hip(uint16_t *src, uint32_t src_stride, uint16_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width) { TIER_A_CALL(svt_aom_sad_16b_kernel, svt_aom_sad_16b_kernel_hip_impl(src, src_stride, ref, ref_stride, height, width), (src, src_stride, ref, ref_stride, height, width)); }
-static uint32_t svt_aom_sad_16b_kernel_hip_impl(uint16_t *src, uint32_t src_stride, uint16_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width) {
+TIER_A_LEAF(uint32_t, svt_aom_sad_16b_kernel,
+            (uint16_t *src, uint32_t src_stride, uint16_t *ref, uint32_t ref_stride, uint32_t height, uint32_t width),
+            (src, src_stride, ref, ref_stride, height, width)) {
     if (!height || !width)
         return 0;
-    if (!ensure_init())
-        fatal("sad_16b_kernel");
-    const size_t src_span = ((size_t)(height - 1) * src_stride + width) * 2, ref_span = ((size_t)(height - 1) * ref_stride + width) * 2;
-    const size_t off_ref = up256(src_span), off_res = off_ref + up256(ref_span);
-    Scratch     &sc = tls_scratch();
-    uint8_t     *d = sc.device(off_res + 256), *h = sc.host(off_res + 256);
-    memcpy(h, src, src_span);
-    memcpy(h + off_ref, ref, ref_span);
-    hipStream_t st = resolve_stream(nullptr);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, off_res, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(sad16_kernel, dim3(1), dim3(WG), 0, st, (const uint16_t *)d, src_stride, (const uint16_t *)(d + off_ref), ref_stride,
-                       height, width, (uint32_t *)(d + off_res));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + off_res, d + off_res, 4, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    return *(const uint32_t *)(h + off_res);
+    TierAStage   s("sad_16b_kernel");
+    const size_t off_src = s.in(src, ((size_t)(height - 1) * src_stride + width) * 2);
+    const size_t off_ref = s.in(ref, ((size_t)(height - 1) * ref_stride + width) * 2), off_res = s.out(4);
+    s.upload();
+    hipLaunchKernelGGL(sad16_kernel, dim3(1), dim3(WG), 0, s.stream(), s.dev<const uint16_t>(off_src), src_stride,
+                       s.dev<const uint16_t>(off_ref), ref_stride, height, width, s.dev<uint32_t>(off_res));
+    s.finish(off_res, 4);
+    return *s.host<uint32_t>(off_res);
 }
 
-static void svt_initialize_buffer_32bits_hip_impl(uint32_t *pointer, uint32_t count128, uint32_t count32, uint32_t value);
-extern "C" void svt_initialize_buffer_32bits_hip(uint32_t *pointer, uint32_t count128, uint32_t count32, uint32_t value) { TIER_A_CALL(svt_initialize_buffer_32bits, svt_initialize_buffer_32bits_hip_impl(pointer, count128, count32, value), (pointer, count128, count32, value)); }
-static void svt_initialize_buffer_32bits_hip_impl(uint32_t *pointer, uint32_t count128, uint32_t count32, uint32_t value) {
+TIER_A_LEAF(void, svt_initialize_buffer_32bits,
+            (uint32_t *pointer, uint32_t count128, uint32_t count32, uint32_t value),
+            (pointer, count128, count32, value)) {
     const uint32_t n = count128 * 4 + count32;
     if (!n)
         return;
-    if (!ensure_init())
-        fatal("svt_initialize_buffer_32bits");
-    Scratch    &sc = tls_scratch();
-    uint8_t    *d = sc.device((size_t)n * 4), *h = sc.host((size_t)n * 4);
-    hipStream_t st = resolve_stream(nullptr);
+    TierAStage     s("svt_initialize_buffer_32bits");
+    const size_t   off = s.out((size_t)n * 4);
     const uint32_t blocks = (n + WG - 1) / WG;
-    hipLaunchKernelGGL(fill32_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(WG), 0, st, (uint32_t *)d, n, value);
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h, d, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    memcpy(pointer, h, (size_t)n * 4);
+    hipLaunchKernelGGL(fill32_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(WG), 0, s.stream(), s.dev<uint32_t>(off), n, value);
+    s.finish(off, (size_t)n * 4);
+    memcpy(pointer, s.host(off), (size_t)n * 4);
 }
 
-static void svt_pme_sad_loop_kernel_hip_impl(const SvtHipMvCostParam *mv_cost_params, uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t block_height, uint32_t block_width, uint32_t *best_cost, int16_t *best_mvx, int16_t *best_mvy, int16_t search_position_start_x, int16_t search_position_start_y, int16_t search_area_width, int16_t search_area_height, int16_t search_step, int16_t mvx, int16_t mvy);
-extern "C" void svt_pme_sad_loop_kernel_hip(const SvtHipMvCostParam *mv_cost_params, uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t block_height, uint32_t block_width, uint32_t *best_cost, int16_t *best_mvx, int16_t *best_mvy, int16_t search_position_start_x, int16_t search_position_start_y, int16_t search_area_width, int16_t search_area_height, int16_t search_step, int16_t mvx, int16_t mvy) { TIER_A_CALL(svt_pme_sad_loop_kernel, svt_pme_sad_loop_kernel_hip_impl(mv_cost_params, src, src_stride, ref, ref_stride, block_height, block_width, best_cost, best_mvx, best_mvy, search_position_start_x, search_position_start_y, search_area_width, search_area_height, search_step, mvx, mvy), (mv_cost_params, src, src_stride, ref, ref_stride, block_height, block_width, best_cost, best_mvx, best_mvy, search_position_start_x, search_position_start_y, search_area_width, search_area_height, search_step, mvx, mvy)); }
-static void svt_pme_sad_loop_kernel_hip_impl(const SvtHipMvCostParam *mv_cost_params, uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t block_height, uint32_t block_width, uint32_t *best_cost, int16_t *best_mvx, int16_t *best_mvy, int16_t search_position_start_x, int16_t search_position_start_y, int16_t search_area_width, int16_t search_area_height, int16_t search_step, int16_t mvx, int16_t mvy) {
+TIER_A_LEAF(void, svt_pme_sad_loop_kernel,
+            (const SvtHipMvCostParam *mv_cost_params, uint8_t *src, uint32_t src_stride, uint8_t *ref, uint32_t ref_stride, uint32_t
+             block_height, uint32_t block_width, uint32_t *best_cost, int16_t *best_mvx, int16_t *best_mvy, int16_t
+             search_position_start_x, int16_t search_position_start_y, int16_t search_area_width, int16_t search_area_height,
+             int16_t search_step, int16_t mvx, int16_t mvy),
+            (mv_cost_params, src, src_stride, ref, ref_stride, block_height, block_width, best_cost, best_mvx, best_mvy,
+             search_position_start_x, search_position_start_y, search_area_width, search_area_height, search_step, mvx, mvy)) {
     if (search_step <= 0) {
         set_error("svt_pme_sad_loop_kernel: search_step %d would never terminate", (int)search_step);
         fatal("svt_pme_sad_loop_kernel");
@@ -174,22 +163,16 @@ static void svt_pme_sad_loop_kernel_hip_impl(const SvtHipMvCostParam *mv_cost_pa
         }
     if (pos.empty() || !block_height || !block_width)
         return;
-    if (!ensure_init())
-        fatal("svt_pme_sad_loop_kernel");
+    TierAStage   s("svt_pme_sad_loop_kernel");
     const int    type = mv_cost_params->mv_cost_type;
-    const size_t src_span = (size_t)(block_height - 1) * src_stride + block_width;
-    const size_t ref_span = (size_t)(max_y + block_height - 1) * ref_stride + max_x + block_width;
     const size_t n_pos = pos.size(), rows = (size_t)max_y + 1, cols = (size_t)max_x + 1;
-    const size_t off_ref = up256(src_span), off_pos = off_ref + up256(ref_span), off_row = off_pos + up256(n_pos * 4),
-                 off_col = off_row + up256(rows * 4), off_best = off_col + up256(cols * 4), total = off_best + 256;
-    Scratch &sc = tls_scratch();
-    uint8_t *d = sc.device(total), *h = sc.host(total);
-    memcpy(h, src, src_span);
-    memcpy(h + off_ref, ref, ref_span);
-    memcpy(h + off_pos, pos.data(), n_pos * 4);
-    PmeArgs a{};
+    const size_t off_src = s.in(src, (size_t)(block_height - 1) * src_stride + block_width);
+    const size_t off_ref = s.in(ref, (size_t)(max_y + block_height - 1) * ref_stride + max_x + block_width);
+    const size_t off_pos = s.in(pos.data(), n_pos * 4), off_row = s.in(nullptr, rows * 4), off_col = s.in(nullptr, cols * 4);
+    const size_t off_best = s.in(nullptr, 8);
+    PmeArgs      a{};
     if (type == 0) {  // gather the table entries the search can reach (svt_mv_cost, mcomp.h:136-139)
-        int32_t *rr = (int32_t *)(h + off_row), *cr = (int32_t *)(h + off_col);
+        int32_t *rr = s.host<int32_t>(off_row), *cr = s.host<int32_t>(off_col);
         for (size_t y = 0; y < rows; y++) {
             const int16_t row = (int16_t)((uint32_t)mvy + (uint32_t)(search_position_start_y + (int)y) * 8u);
             const int16_t dr  = (int16_t)(row - mv_cost_params->ref_mv->row);
@@ -202,21 +185,18 @@ static void svt_pme_sad_loop_kernel_hip_impl(const SvtHipMvCostParam *mv_cost_pa
         }
         for (int j = 0; j < 4; j++) a.joint_rate[j] = mv_cost_params->mvjcost[j];
     }
-    *(unsigned long long *)(h + off_best) = (unsigned long long)*best_cost << 32;
-    a.src = d, a.ref = d + off_ref, a.pos = (const uint32_t *)(d + off_pos);
-    a.row_rate = (const int32_t *)(d + off_row), a.col_rate = (const int32_t *)(d + off_col);
-    a.best = (unsigned long long *)(d + off_best);
+    *s.host<unsigned long long>(off_best) = (unsigned long long)*best_cost << 32;
+    a.src = s.dev(off_src), a.ref = s.dev(off_ref), a.pos = s.dev<const uint32_t>(off_pos);
+    a.row_rate = s.dev<const int32_t>(off_row), a.col_rate = s.dev<const int32_t>(off_col);
+    a.best = s.dev<unsigned long long>(off_best);
     a.src_stride = src_stride, a.ref_stride = ref_stride, a.bw = block_width, a.bh = block_height, a.n_pos = (uint32_t)n_pos;
     a.start_x = search_position_start_x, a.start_y = search_position_start_y, a.mvx = mvx, a.mvy = mvy;
     a.ref_row = mv_cost_params->ref_mv->row, a.ref_col = mv_cost_params->ref_mv->col, a.type = type;
     a.error_per_bit = mv_cost_params->error_per_bit;
-    hipStream_t st = resolve_stream(nullptr);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(pme_sad_kernel, dim3((uint32_t)((n_pos + 3) / 4)), dim3(WG), 0, st, a);
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + off_best, d + off_best, 8, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    const unsigned long long key = *(const unsigned long long *)(h + off_best);
+    s.upload();
+    hipLaunchKernelGGL(pme_sad_kernel, dim3((uint32_t)((n_pos + 3) / 4)), dim3(WG), 0, s.stream(), a);
+    s.finish(off_best, 8);
+    const unsigned long long key = *s.host<unsigned long long>(off_best);
     if ((uint32_t)key) {  // a visited position beat the incoming cost
         const uint32_t w = pos[(uint32_t)key - 1], xs = w & 0xffff, ys = w >> 16;
         *best_mvx  = (int16_t)((uint32_t)mvx + (uint32_t)(search_position_start_x + (int)xs) * 8u);

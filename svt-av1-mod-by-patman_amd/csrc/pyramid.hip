@@ -285,12 +285,6 @@ extern "C" int32_t svt_hip_analysis_frames(const SvtHipAnalysisJob *jobs, uint32
 // ------------------------------------------------------------------------------------------------
 // Tier A (host pointers): stage the touched bytes, run the same kernels, copy back.
 // ------------------------------------------------------------------------------------------------
-static void fatal_if(bool bad, const char *what) {
-    if (bad) {
-        svthip::tier_a_throw("%s: %s", what, svt_hip_last_error());
-    }
-}
-
 // Generic strided decimation used by the per-call entry point (no padding involved).
 __global__ __launch_bounds__(256) static void downsample_plain_kernel(const uint8_t *__restrict__ in, uint32_t in_stride,
                                                                        uint32_t in_w, uint32_t in_h,
@@ -305,32 +299,27 @@ __global__ __launch_bounds__(256) static void downsample_plain_kernel(const uint
     out[(size_t)oy * out_stride + ox] = (uint8_t)((s + 2) >> 2);
 }
 
-static void svt_aom_downsample_2d_hip_impl(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height, uint8_t *decim_samples, uint32_t decim_stride, uint32_t decim_step);
-extern "C" void svt_aom_downsample_2d_hip(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height, uint8_t *decim_samples, uint32_t decim_stride, uint32_t decim_step) { TIER_A_CALL(svt_aom_downsample_2d, svt_aom_downsample_2d_hip_impl(input_samples, input_stride, input_area_width, input_area_height, decim_samples, decim_stride, decim_step), (input_samples, input_stride, input_area_width, input_area_height, decim_samples, decim_stride, decim_step)); }
-static void svt_aom_downsample_2d_hip_impl(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height, uint8_t *decim_samples, uint32_t decim_stride, uint32_t decim_step) {
+TIER_A_LEAF(void, svt_aom_downsample_2d,
+            (uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height, uint8_t
+             *decim_samples, uint32_t decim_stride, uint32_t decim_step),
+            (input_samples, input_stride, input_area_width, input_area_height, decim_samples, decim_stride, decim_step)) {
     const uint32_t half = decim_step >> 1;
     if (decim_step == 0 || input_area_width <= half || input_area_height <= half)
         return;
-    fatal_if(!ensure_init(), "svt_aom_downsample_2d_hip");
+    TierAStage     s("svt_aom_downsample_2d");
     const uint32_t ow = (input_area_width - half + decim_step - 1) / decim_step;
     const uint32_t oh = (input_area_height - half + decim_step - 1) / decim_step;
     // reads start one row / one column before (half,half): rows half-1 .., columns half-1 ..
     const size_t   in_first = (size_t)(half - 1) * input_stride + (half - 1);
     const size_t   in_span  = (size_t)(input_area_height - half) * input_stride + (input_area_width - half + 1);
-    hipStream_t    st = resolve_stream(nullptr);
-    Scratch       &sc = tls_scratch();
-    const size_t   off_out = (in_span + 511) / 256 * 256, out_span = (size_t)(oh - 1) * decim_stride + ow;
-    uint8_t       *d = sc.device(off_out + out_span + 256), *h = sc.host(off_out + out_span + 256);
-    memcpy(h, input_samples + in_first, in_span);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, in_span, hipMemcpyHostToDevice, st));
-    // device pointer equivalent of `input_samples`: d - in_first (never dereferenced below in_first)
-    const uint8_t *din = d - in_first;
-    hipLaunchKernelGGL(downsample_plain_kernel, dim3((ow + 255) / 256, oh), dim3(256), 0, st, din, input_stride,
-                       input_area_width, input_area_height, d + off_out, decim_stride, decim_step);
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + off_out, d + off_out, out_span, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    for (uint32_t y = 0; y < oh; y++) memcpy(decim_samples + (size_t)y * decim_stride, h + off_out + (size_t)y * decim_stride, ow);
+    const size_t   out_span = (size_t)(oh - 1) * decim_stride + ow;
+    const size_t   off_in = s.in(input_samples + in_first, in_span, 256), off_out = s.out(out_span);
+    s.upload();
+    // device pointer equivalent of `input_samples`: never dereferenced below in_first
+    hipLaunchKernelGGL(downsample_plain_kernel, dim3((ow + 255) / 256, oh), dim3(256), 0, s.stream(), s.dev<const uint8_t>(off_in) - in_first,
+                       input_stride, input_area_width, input_area_height, s.dev(off_out), decim_stride, decim_step);
+    s.finish(off_out, out_span);
+    copy_rows(decim_samples, decim_stride, s.host(off_out), decim_stride, oh, ow);
 }
 
 // 8x8 block statistics: n8 side-by-side 8x8 blocks, (sum, sum of squares) over rows 0..7 step `rstep`.
@@ -351,23 +340,18 @@ __global__ __launch_bounds__(64) static void block8_stats_kernel(const uint8_t *
 
 static void block_stats_host(const uint8_t *in, uint32_t stride, uint32_t n8, uint32_t w, uint32_t hrows, uint32_t rstep,
                              uint32_t *res /* 2*n8 */) {
-    fatal_if(!ensure_init(), "block statistics");
-    hipStream_t  st   = resolve_stream(nullptr);
-    Scratch     &sc   = tls_scratch();
-    const size_t span = (size_t)(hrows - 1) * stride + (size_t)w * n8, off = (span + 511) / 256 * 256;
-    uint8_t     *d = sc.device(off + 256), *h = sc.host(off + 256);
-    memcpy(h, in, span);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, span, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(block8_stats_kernel, dim3(1), dim3(64), 0, st, d, stride, n8, w, hrows, rstep, (uint32_t *)(d + off));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + off, d + off, 8 * n8, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    memcpy(res, h + off, 8 * n8);
+    TierAStage   s("block statistics");
+    const size_t off_in = s.in(in, (size_t)(hrows - 1) * stride + (size_t)w * n8, 256), off_out = s.out(8 * n8);
+    s.upload();
+    hipLaunchKernelGGL(block8_stats_kernel, dim3(1), dim3(64), 0, s.stream(), s.dev<const uint8_t>(off_in), stride, n8, w, hrows, rstep,
+                       s.dev<uint32_t>(off_out));
+    s.finish(off_out, 8 * n8);
+    memcpy(res, s.host(off_out), 8 * n8);
 }
 
-static void svt_compute_interm_var_four8x8_hip_impl(uint8_t *input_samples, uint16_t input_stride, uint64_t *mean_of8x8_blocks, uint64_t *mean_of_squared8x8_blocks);
-extern "C" void svt_compute_interm_var_four8x8_hip(uint8_t *input_samples, uint16_t input_stride, uint64_t *mean_of8x8_blocks, uint64_t *mean_of_squared8x8_blocks) { TIER_A_CALL(svt_compute_interm_var_four8x8, svt_compute_interm_var_four8x8_hip_impl(input_samples, input_stride, mean_of8x8_blocks, mean_of_squared8x8_blocks), (input_samples, input_stride, mean_of8x8_blocks, mean_of_squared8x8_blocks)); }
-static void svt_compute_interm_var_four8x8_hip_impl(uint8_t *input_samples, uint16_t input_stride, uint64_t *mean_of8x8_blocks, uint64_t *mean_of_squared8x8_blocks) {
+TIER_A_LEAF(void, svt_compute_interm_var_four8x8,
+            (uint8_t *input_samples, uint16_t input_stride, uint64_t *mean_of8x8_blocks, uint64_t *mean_of_squared8x8_blocks),
+            (input_samples, input_stride, mean_of8x8_blocks, mean_of_squared8x8_blocks)) {
     uint32_t r[8];
     block_stats_host(input_samples, input_stride, 4, 8, 8, 2, r);
     for (int k = 0; k < 4; k++) {
@@ -375,23 +359,23 @@ static void svt_compute_interm_var_four8x8_hip_impl(uint8_t *input_samples, uint
         mean_of_squared8x8_blocks[k] = (uint64_t)r[2 * k + 1] << 11;
     }
 }
-static uint64_t svt_compute_sub_mean_8x8_hip_impl(uint8_t *input_samples, uint16_t input_stride);
-extern "C" uint64_t svt_compute_sub_mean_8x8_hip(uint8_t *input_samples, uint16_t input_stride) { TIER_A_CALL(svt_compute_sub_mean_8x8, svt_compute_sub_mean_8x8_hip_impl(input_samples, input_stride), (input_samples, input_stride)); }
-static uint64_t svt_compute_sub_mean_8x8_hip_impl(uint8_t *input_samples, uint16_t input_stride) {
+TIER_A_LEAF(uint64_t, svt_compute_sub_mean_8x8,
+            (uint8_t *input_samples, uint16_t input_stride),
+            (input_samples, input_stride)) {
     uint32_t r[2];
     block_stats_host(input_samples, input_stride, 1, 8, 8, 2, r);
     return (uint64_t)r[0] << 3;
 }
-static uint64_t svt_compute_mean_8x8_hip_impl(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height);
-extern "C" uint64_t svt_compute_mean_8x8_hip(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height) { TIER_A_CALL(svt_compute_mean_8x8, svt_compute_mean_8x8_hip_impl(input_samples, input_stride, input_area_width, input_area_height), (input_samples, input_stride, input_area_width, input_area_height)); }
-static uint64_t svt_compute_mean_8x8_hip_impl(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height) {
+TIER_A_LEAF(uint64_t, svt_compute_mean_8x8,
+            (uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height),
+            (input_samples, input_stride, input_area_width, input_area_height)) {
     uint32_t r[2];
     block_stats_host(input_samples, input_stride, 1, input_area_width, input_area_height, 1, r);
     return ((uint64_t)r[0] << 8) / (input_area_width * input_area_height);
 }
-static uint64_t svt_compute_mean_square_values_8x8_hip_impl(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height);
-extern "C" uint64_t svt_compute_mean_square_values_8x8_hip(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height) { TIER_A_CALL(svt_compute_mean_square_values_8x8, svt_compute_mean_square_values_8x8_hip_impl(input_samples, input_stride, input_area_width, input_area_height), (input_samples, input_stride, input_area_width, input_area_height)); }
-static uint64_t svt_compute_mean_square_values_8x8_hip_impl(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height) {
+TIER_A_LEAF(uint64_t, svt_compute_mean_square_values_8x8,
+            (uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height),
+            (input_samples, input_stride, input_area_width, input_area_height)) {
     uint32_t r[2];
     block_stats_host(input_samples, input_stride, 1, input_area_width, input_area_height, 1, r);
     return ((uint64_t)r[1] << 16) / (input_area_width * input_area_height);

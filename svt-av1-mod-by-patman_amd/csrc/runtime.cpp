@@ -227,22 +227,66 @@ uint8_t *Scratch::device(size_t bytes) {
     }
     return dev;
 }
-uint8_t *Scratch::host(size_t bytes) {
+uint8_t *Scratch::host(size_t bytes, size_t keep) {
     if (bytes > pinned_cap) {
-        if (pinned)
-            (void)hipHostFree(pinned);
-        size_t cap = bytes < (1u << 20) ? (1u << 20) : bytes * 2;
-        if (hipHostMalloc((void **)&pinned, cap + 256, hipHostMallocDefault) != hipSuccess) {
-            pinned = nullptr, pinned_cap = 0;
+        size_t   cap   = bytes < (1u << 20) ? (1u << 20) : bytes * 2;
+        uint8_t *grown = nullptr;
+        if (hipHostMalloc((void **)&grown, cap + 256, hipHostMallocDefault) != hipSuccess)
             tier_a_throw("hipHostMalloc(%zu) for the Tier A scratch buffer failed", cap);
+        if (pinned) {
+            memcpy(grown, pinned, keep);
+            (void)hipHostFree(pinned);
         }
-        pinned_cap = cap;
+        pinned = grown, pinned_cap = cap;
     }
     return pinned;
 }
 Scratch &tls_scratch() {
     static thread_local Scratch s;
     return s;
+}
+
+[[noreturn]] void fatal(const char *what) { tier_a_throw("%s: %s", what, svt_hip_last_error()); }
+
+TierAStage::TierAStage(const char *leaf, bool ready) {
+    if (!ready)
+        fatal(leaf);
+    st_ = resolve_stream(nullptr);
+}
+size_t TierAStage::reserve(size_t bytes) {
+    if (d_)
+        tier_a_throw("Tier A staging: region reserved after the device buffer was sized");
+    const size_t off = used_;
+    used_ += up256(bytes);
+    h_ = tls_scratch().host(used_ + 256, off);
+    return off;
+}
+size_t TierAStage::in(const void *src, size_t bytes, size_t slack) {
+    const size_t off = reserve(bytes + slack);
+    if (src)
+        memcpy(h_ + off, src, bytes);
+    in_end_ = off + bytes;
+    return off;
+}
+size_t TierAStage::in_rows(const void *src, size_t src_pitch, size_t rows, size_t row_bytes) {
+    const size_t off = in(nullptr, rows * row_bytes);
+    copy_rows(h_ + off, row_bytes, src, src_pitch, rows, row_bytes);
+    return off;
+}
+uint8_t *TierAStage::device() {
+    if (!d_)
+        d_ = tls_scratch().device(used_ + 256);
+    return d_;
+}
+void TierAStage::h2d(size_t off, size_t bytes) {
+    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(device() + off, h_ + off, bytes, hipMemcpyHostToDevice, st_));
+}
+void TierAStage::finish(size_t off, size_t bytes, size_t off2, size_t bytes2) {
+    SVT_HIP_CHECK_FATAL(hipGetLastError());
+    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h_ + off, device() + off, bytes, hipMemcpyDeviceToHost, st_));
+    if (bytes2)
+        SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h_ + off2, d_ + off2, bytes2, hipMemcpyDeviceToHost, st_));
+    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st_));
 }
 
 }  // namespace svthip

@@ -259,132 +259,93 @@ extern "C" int32_t svt_hip_quantize_batch(uint8_t *d_base, const SvtHipTxfmDesc 
 // ------------------------------------------------------------------------------------------------ Tier A
 namespace {
 
-[[noreturn]] void fatal(const char *what) { svthip::tier_a_throw("%s: %s", what, svt_hip_last_error()); }
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
-// One-block arena in the per-thread scratch: [desc][result][buffers...]
-struct Arena {
-    uint8_t *h, *d;
-    size_t   used;
-    Arena(size_t bytes) {
-        Scratch &sc = tls_scratch();
-        h = sc.host(bytes), d = sc.device(bytes), used = 512;
+// One block in the staging arena: [descriptor][result][buffers...]; every buffer has 16 bytes of slack for the kernel's vector accesses.
+struct OneBlock : TierAStage {
+    size_t off_desc, off_res;
+    OneBlock(const char *what) : TierAStage(what, txfm_ready() == SVT_HIP_OK), off_desc(in(nullptr, 256)), off_res(out(256)) {
+        memset(desc(), 0, sizeof(SvtHipTxfmDesc));
     }
-    size_t put(const void *src, size_t bytes) {
-        const size_t off = used;
-        if (src)
-            memcpy(h + off, src, bytes);
-        used += up256(bytes + 16);
-        return off;
+    SvtHipTxfmDesc         *desc() const { return host<SvtHipTxfmDesc>(off_desc); }
+    const SvtHipTxfmResult *result() const { return host<SvtHipTxfmResult>(off_res); }
+    void run(int w, int h) {
+        upload();
+        if (!dispatch_txfm((uint32_t)w, (uint32_t)h, dev(0), dev<const SvtHipTxfmDesc>(off_desc), dev<SvtHipTxfmResult>(off_res), 1, stream()))
+            fatal("bad transform size");
     }
 };
 
-void run_one(int w, int h, Arena &a, size_t upload_bytes, hipStream_t st) {
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(a.d, a.h, upload_bytes, hipMemcpyHostToDevice, st));
-    if (!dispatch_txfm((uint32_t)w, (uint32_t)h, a.d, (const SvtHipTxfmDesc *)a.d, (SvtHipTxfmResult *)(a.d + 256), 1, st))
-        fatal("bad transform size");
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-}
-
 void fwd_tier_a(int w, int h, int shape, int16_t *input, int32_t *output, uint32_t stride, int32_t tx_type, uint8_t bd) {
-    if (txfm_ready() != SVT_HIP_OK)
-        fatal("forward transform");
-    const size_t in_bytes = ((size_t)(h - 1) * stride + w) * 2, out_bytes = (size_t)w * h * 4;
-    Arena        a(1024 + up256(in_bytes + 16) + up256(out_bytes + 16));
-    SvtHipTxfmDesc *dsc = (SvtHipTxfmDesc *)a.h;
-    memset(dsc, 0, sizeof(*dsc));
-    dsc->residual_off = a.put(input, in_bytes);
-    dsc->coeff_off    = a.put(nullptr, out_bytes);
+    OneBlock     a("forward transform");
+    const size_t out_bytes = (size_t)w * h * 4;
+    const size_t off_in = a.in(input, ((size_t)(h - 1) * stride + w) * 2, 16), off_out = a.out(out_bytes + 16);
+    SvtHipTxfmDesc *dsc = a.desc();
+    dsc->residual_off = off_in, dsc->coeff_off = off_out;
     dsc->qcoeff_off = dsc->dqcoeff_off = dsc->qm_off = dsc->iqm_off = dsc->iscan_off = dsc->pred_off = dsc->recon_off = SVT_HIP_NO_OFFSET;
     dsc->residual_stride = stride;
     dsc->tx_type = (uint8_t)tx_type, dsc->shape = (uint8_t)shape, dsc->bit_depth = bd;
     dsc->quant_mode = SVT_HIP_QUANT_NONE, dsc->flags = SVT_HIP_TX_FWD | SVT_HIP_TX_FULLCOEFF;
-    hipStream_t st = resolve_stream(nullptr);
-    run_one(w, h, a, dsc->coeff_off, st);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(a.h + dsc->coeff_off, a.d + dsc->coeff_off, out_bytes, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    memcpy(output, a.h + dsc->coeff_off, out_bytes);
+    a.run(w, h);
+    a.finish(off_out, out_bytes);
+    memcpy(output, a.host(off_out), out_bytes);
 }
 
 template <class PIX>
 void inv_tier_a(int w, int h, const int32_t *input, const PIX *out_r, int32_t stride_r, PIX *out_w, int32_t stride_w, int32_t tx_type,
                 int32_t bd) {
-    if (txfm_ready() != SVT_HIP_OK)
-        fatal("inverse transform");
+    OneBlock     a("inverse transform");
     const int    iw = w < 32 ? w : 32, ih = h < 32 ? h : 32;
-    const size_t co_bytes = (size_t)iw * ih * 4, pr_bytes = ((size_t)(h - 1) * stride_r + w) * sizeof(PIX),
-                 rc_bytes = ((size_t)(h - 1) * stride_w + w) * sizeof(PIX);
-    Arena           a(1024 + up256(co_bytes + 16) + up256(pr_bytes + 16) + up256(rc_bytes + 16));
-    SvtHipTxfmDesc *dsc = (SvtHipTxfmDesc *)a.h;
-    memset(dsc, 0, sizeof(*dsc));
-    dsc->dqcoeff_off = a.put(input, co_bytes);
-    dsc->pred_off    = a.put(out_r, pr_bytes);
-    dsc->recon_off   = a.put(nullptr, rc_bytes);
+    const size_t rc_bytes = ((size_t)(h - 1) * stride_w + w) * sizeof(PIX);
+    const size_t off_co = a.in(input, (size_t)iw * ih * 4, 16);
+    const size_t off_pr = a.in(out_r, ((size_t)(h - 1) * stride_r + w) * sizeof(PIX), 16), off_rc = a.out(rc_bytes + 16);
+    SvtHipTxfmDesc *dsc = a.desc();
+    dsc->dqcoeff_off = off_co, dsc->pred_off = off_pr, dsc->recon_off = off_rc;
     dsc->residual_off = dsc->coeff_off = dsc->qcoeff_off = dsc->qm_off = dsc->iqm_off = dsc->iscan_off = SVT_HIP_NO_OFFSET;
     dsc->pred_stride = (uint32_t)stride_r, dsc->recon_stride = (uint32_t)stride_w;
     dsc->tx_type = (uint8_t)tx_type, dsc->bit_depth = (uint8_t)bd;
     dsc->quant_mode = SVT_HIP_QUANT_NONE, dsc->flags = SVT_HIP_TX_INV | (sizeof(PIX) == 2 ? SVT_HIP_TX_PIXEL16 : 0);
-    hipStream_t st = resolve_stream(nullptr);
-    run_one(w, h, a, dsc->recon_off, st);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(a.h + dsc->recon_off, a.d + dsc->recon_off, rc_bytes, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    const PIX *rc = (const PIX *)(a.h + dsc->recon_off);
-    for (int r = 0; r < h; r++) memcpy(out_w + (size_t)r * stride_w, rc + (size_t)r * stride_w, (size_t)w * sizeof(PIX));
+    a.run(w, h);
+    a.finish(off_rc, rc_bytes);
+    copy_rows(out_w, (size_t)stride_w * sizeof(PIX), a.host(off_rc), (size_t)stride_w * sizeof(PIX), h, (size_t)w * sizeof(PIX));
 }
 
 void quant_tier_a(int mode, const int32_t *coeff_ptr, intptr_t n, const int16_t *zbin, const int16_t *round, const int16_t *quant,
                   const int16_t *quant_shift, int32_t *qcoeff, int32_t *dqcoeff, const int16_t *dequant, uint16_t *eob,
                   const int16_t *iscan, const uint8_t *qm, const uint8_t *iqm, int log_scale) {
-    if (txfm_ready() != SVT_HIP_OK)
-        fatal("quantize");
-    const size_t    cb = (size_t)n * 4;
-    Arena           a(1024 + 3 * up256(cb + 16) + up256((size_t)n * 2 + 16) + 2 * up256((size_t)n + 16));
-    SvtHipTxfmDesc *dsc = (SvtHipTxfmDesc *)a.h;
-    memset(dsc, 0, sizeof(*dsc));
-    dsc->coeff_off = a.put(coeff_ptr, cb);
-    dsc->iscan_off = a.put(iscan, (size_t)n * 2);
-    dsc->qm_off    = qm ? a.put(qm, (size_t)n) : SVT_HIP_NO_OFFSET;
-    dsc->iqm_off   = iqm ? a.put(iqm, (size_t)n) : SVT_HIP_NO_OFFSET;
-    const size_t upload = a.used;
-    dsc->qcoeff_off     = a.put(nullptr, cb);
-    dsc->dqcoeff_off    = a.put(nullptr, cb);
+    OneBlock     a("quantize");
+    const size_t cb = (size_t)n * 4;
+    const size_t off_co = a.in(coeff_ptr, cb, 16), off_is = a.in(iscan, (size_t)n * 2, 16);
+    const size_t off_qm = qm ? a.in(qm, (size_t)n, 16) : SVT_HIP_NO_OFFSET, off_iqm = iqm ? a.in(iqm, (size_t)n, 16) : SVT_HIP_NO_OFFSET;
+    const size_t off_q = a.out(cb + 16), off_dq = a.out(cb + 16);  // adjacent: one copy brings both back
+    SvtHipTxfmDesc *dsc = a.desc();
+    dsc->coeff_off = off_co, dsc->iscan_off = off_is, dsc->qm_off = off_qm, dsc->iqm_off = off_iqm;
+    dsc->qcoeff_off = off_q, dsc->dqcoeff_off = off_dq;
     dsc->residual_off = dsc->pred_off = dsc->recon_off = SVT_HIP_NO_OFFSET;
     for (int i = 0; i < 2; i++) {
         dsc->zbin[i] = zbin ? zbin[i] : 0, dsc->round[i] = round[i], dsc->quant[i] = quant[i];
         dsc->quant_shift[i] = quant_shift ? quant_shift[i] : 0, dsc->dequant[i] = dequant[i];
     }
     dsc->quant_mode = (uint8_t)mode, dsc->log_scale = (uint8_t)log_scale;
-    hipStream_t st = resolve_stream(nullptr);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(a.d, a.h, upload, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(quantize_kernel, dim3(1), dim3(256), 0, st, a.d, (const SvtHipTxfmDesc *)a.d, (SvtHipTxfmResult *)(a.d + 256),
-                       (uint32_t)n);
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(a.h + 256, a.d + 256, sizeof(SvtHipTxfmResult), hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(a.h + dsc->qcoeff_off, a.d + dsc->qcoeff_off, a.used - dsc->qcoeff_off, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    memcpy(qcoeff, a.h + dsc->qcoeff_off, cb);
-    memcpy(dqcoeff, a.h + dsc->dqcoeff_off, cb);
-    *eob = ((const SvtHipTxfmResult *)(a.h + 256))->eob;
+    a.upload();
+    hipLaunchKernelGGL(quantize_kernel, dim3(1), dim3(256), 0, a.stream(), a.dev(0), a.dev<const SvtHipTxfmDesc>(a.off_desc),
+                       a.dev<SvtHipTxfmResult>(a.off_res), (uint32_t)n);
+    a.finish(a.off_res, sizeof(SvtHipTxfmResult), off_q, off_dq + cb - off_q);
+    memcpy(qcoeff, a.host(off_q), cb);
+    memcpy(dqcoeff, a.host(off_dq), cb);
+    *eob = a.result()->eob;
 }
 
 uint64_t handle_tier_a(int w, int h, int energy_on, int32_t *output) {
-    if (txfm_ready() != SVT_HIP_OK)
-        fatal("handle_transform");
+    TierAStage   s("handle_transform", txfm_ready() == SVT_HIP_OK);
     const size_t bytes = (size_t)w * h * 4;
-    Arena        a(1024 + up256(bytes + 16));
-    const size_t off = a.put(output, bytes);
-    hipStream_t  st  = resolve_stream(nullptr);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(a.d + off, a.h + off, bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(handle64_kernel, dim3(1), dim3(256), 0, st, (int32_t *)(a.d + off), w, h, energy_on, (uint64_t *)(a.d + 256));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    const int    iw = w < 32 ? w : 32, ih = h < 32 ? h : 32;
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(a.h + 256, a.d + 256, 8, hipMemcpyDeviceToHost, st));
-    if (w == 64)
-        SVT_HIP_CHECK_FATAL(hipMemcpyAsync(a.h + off, a.d + off, (size_t)iw * ih * 4, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
+    const size_t off_res = s.out(8), off = s.in(output, bytes, 16);
+    s.h2d(off, bytes);
+    hipLaunchKernelGGL(handle64_kernel, dim3(1), dim3(256), 0, s.stream(), s.dev<int32_t>(off), w, h, energy_on, s.dev<uint64_t>(off_res));
+    const int iw = w < 32 ? w : 32, ih = h < 32 ? h : 32;
+    s.finish(off_res, 8, off, w == 64 ? (size_t)iw * ih * 4 : 0);
     if (w == 64)  // rows 1..ih-1 were repacked; everything beyond the packed area is left as the C function leaves it
-        for (int r = 1; r < ih; r++) memmove(output + r * 32, a.h + off + (size_t)r * 32 * 4, 32 * 4);
-    return *(const uint64_t *)(a.h + 256);
+        for (int r = 1; r < ih; r++) memmove(output + r * 32, s.host(off) + (size_t)r * 32 * 4, 32 * 4);
+    return *s.host<uint64_t>(off_res);
 }
 
 }  // namespace
@@ -423,9 +384,10 @@ HANDLE_DEF(16, 64) HANDLE_DEF(32, 64) HANDLE_DEF(64, 16) HANDLE_DEF(64, 32) HAND
 // txfm_param->bd and narrows; with bd == 8 (the only value its callers pass, :3101,3163) that equals the 8-bit pixel path of
 // the kernel.  Lossless (the 4x4 Walsh-Hadamard form) is never requested by this reference version (full_loop.c:1703,1715
 // and src_ops_process.c:1157 pass 0) and is refused loudly.
-static void svt_av1_inv_txfm_add_hip_impl(const int32_t *dqcoeff, uint8_t *dst_r, int32_t stride_r, uint8_t *dst_w, int32_t stride_w, const SvtHipTxfmParam *txfm_param);
-extern "C" void svt_av1_inv_txfm_add_hip(const int32_t *dqcoeff, uint8_t *dst_r, int32_t stride_r, uint8_t *dst_w, int32_t stride_w, const SvtHipTxfmParam *txfm_param) { TIER_A_CALL(svt_av1_inv_txfm_add, svt_av1_inv_txfm_add_hip_impl(dqcoeff, dst_r, stride_r, dst_w, stride_w, txfm_param), (dqcoeff, dst_r, stride_r, dst_w, stride_w, txfm_param)); }
-static void svt_av1_inv_txfm_add_hip_impl(const int32_t *dqcoeff, uint8_t *dst_r, int32_t stride_r, uint8_t *dst_w, int32_t stride_w, const SvtHipTxfmParam *txfm_param) {
+TIER_A_LEAF(void, svt_av1_inv_txfm_add,
+            (const int32_t *dqcoeff, uint8_t *dst_r, int32_t stride_r, uint8_t *dst_w, int32_t stride_w, const SvtHipTxfmParam
+             *txfm_param),
+            (dqcoeff, dst_r, stride_r, dst_w, stride_w, txfm_param)) {
     static const uint8_t wide[19] = {4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64};
     static const uint8_t high[19] = {4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16};
     if (!txfm_param || txfm_param->tx_size >= 19 || txfm_param->lossless || txfm_param->bd != 8) {

@@ -89,7 +89,6 @@ __global__ __launch_bounds__(256) void distortion_batch_kernel(const uint8_t *__
         results[tb][0] = a, results[tb][1] = b;
 }
 
-[[noreturn]] void fatal(const char *what) { svthip::tier_a_throw("%s: %s", what, svt_hip_last_error()); }
 // sum (a - b)^2 over a w x h area of pixels (svt_spatial_full_distortion_kernel / svt_full_distortion_kernel16_bits)
 template <class PIX>
 __global__ __launch_bounds__(256) void spatial_sse_kernel(const PIX *__restrict__ a, int as, const PIX *__restrict__ b, int bs, int w, int h,
@@ -106,31 +105,21 @@ __global__ __launch_bounds__(256) void spatial_sse_kernel(const PIX *__restrict_
         atomicAdd(out, (unsigned long long)acc);
 }
 
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
 template <class PIX>
 uint64_t spatial_sse_tier_a(const PIX *a, uint32_t as, const PIX *b, uint32_t bs, uint32_t w, uint32_t h, const char *what) {
     if (!w || !h)
         return 0;
-    if (!ensure_init())
-        fatal(what);
-    const size_t pix = (size_t)w * h, pb = up256(pix * sizeof(PIX));
-    Scratch     &sc = tls_scratch();
-    uint8_t     *hh = sc.host(2 * pb + 256), *d = sc.device(2 * pb + 256);
-    for (uint32_t r = 0; r < h; r++) {
-        memcpy(hh + (size_t)r * w * sizeof(PIX), a + (size_t)r * as, (size_t)w * sizeof(PIX));
-        memcpy(hh + pb + (size_t)r * w * sizeof(PIX), b + (size_t)r * bs, (size_t)w * sizeof(PIX));
-    }
-    memset(hh + 2 * pb, 0, 8);
-    hipStream_t st = resolve_stream(nullptr);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, hh, 2 * pb + 8, hipMemcpyHostToDevice, st));
-    const int blocks = (int)((pix + 255) / 256);
-    hipLaunchKernelGGL((spatial_sse_kernel<PIX>), dim3(blocks < 256 ? blocks : 256), dim3(256), 0, st, (const PIX *)d, (int)w,
-                       (const PIX *)(d + pb), (int)w, (int)w, (int)h, (unsigned long long *)(d + 2 * pb));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(hh + 2 * pb, d + 2 * pb, 8, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    return *(const uint64_t *)(hh + 2 * pb);
+    TierAStage   s(what);
+    const size_t off_a = s.in_rows(a, as * sizeof(PIX), h, w * sizeof(PIX)), off_b = s.in_rows(b, bs * sizeof(PIX), h, w * sizeof(PIX));
+    const size_t off_sum = s.in(nullptr, 8);  // the kernel adds into it
+    memset(s.host(off_sum), 0, 8);
+    s.upload();
+    const int blocks = (int)(((size_t)w * h + 255) / 256);
+    hipLaunchKernelGGL((spatial_sse_kernel<PIX>), dim3(blocks < 256 ? blocks : 256), dim3(256), 0, s.stream(), s.dev<const PIX>(off_a), (int)w,
+                       s.dev<const PIX>(off_b), (int)w, (int)w, (int)h, s.dev<unsigned long long>(off_sum));
+    s.finish(off_sum, 8);
+    return *s.host<uint64_t>(off_sum);
 }
 
 template <class PIX>
@@ -138,51 +127,46 @@ void subtract_tier_a(int rows, int cols, int16_t *diff, ptrdiff_t diff_stride, c
                      ptrdiff_t pred_stride) {
     if (rows <= 0 || cols <= 0)
         return;
-    if (!ensure_init())
-        fatal("subtract_block");
-    // dense staging: rows x cols of each operand
-    const size_t pix = (size_t)rows * cols, pb = up256(pix * sizeof(PIX)), db = up256(pix * 2);
-    Scratch     &sc  = tls_scratch();
-    uint8_t     *h = sc.host(2 * pb + db), *d = sc.device(2 * pb + db);
-    for (int r = 0; r < rows; r++) {
-        memcpy(h + (size_t)r * cols * sizeof(PIX), src + (ptrdiff_t)r * src_stride, (size_t)cols * sizeof(PIX));
-        memcpy(h + pb + (size_t)r * cols * sizeof(PIX), pred + (ptrdiff_t)r * pred_stride, (size_t)cols * sizeof(PIX));
-    }
-    hipStream_t st = resolve_stream(nullptr);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, 2 * pb, hipMemcpyHostToDevice, st));
+    TierAStage   s("subtract_block");
+    const size_t pix = (size_t)rows * cols;  // dense staging: rows x cols of each operand
+    const size_t off_src = s.in_rows(src, src_stride * sizeof(PIX), rows, cols * sizeof(PIX));
+    const size_t off_pred = s.in_rows(pred, pred_stride * sizeof(PIX), rows, cols * sizeof(PIX)), off_diff = s.out(pix * 2);
+    s.upload();
     const int blocks = (int)((pix + 255) / 256);
-    hipLaunchKernelGGL((subtract_kernel<PIX>), dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, st, rows, cols, (int16_t *)(d + 2 * pb),
-                       cols, (const PIX *)d, cols, (const PIX *)(d + pb), cols);
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + 2 * pb, d + 2 * pb, pix * 2, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    for (int r = 0; r < rows; r++) memcpy(diff + (ptrdiff_t)r * diff_stride, h + 2 * pb + (size_t)r * cols * 2, (size_t)cols * 2);
+    hipLaunchKernelGGL((subtract_kernel<PIX>), dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, s.stream(), rows, cols,
+                       s.dev<int16_t>(off_diff), cols, s.dev<const PIX>(off_src), cols, s.dev<const PIX>(off_pred), cols);
+    s.finish(off_diff, pix * 2);
+    s.out_rows(diff, diff_stride * 2, off_diff, rows, (size_t)cols * 2);
 }
 
 }  // namespace
 
-static void svt_aom_subtract_block_hip_impl(int rows, int cols, int16_t *diff_ptr, ptrdiff_t diff_stride, const uint8_t *src_ptr, ptrdiff_t src_stride, const uint8_t *pred_ptr, ptrdiff_t pred_stride);
-extern "C" void svt_aom_subtract_block_hip(int rows, int cols, int16_t *diff_ptr, ptrdiff_t diff_stride, const uint8_t *src_ptr, ptrdiff_t src_stride, const uint8_t *pred_ptr, ptrdiff_t pred_stride) { TIER_A_CALL(svt_aom_subtract_block, svt_aom_subtract_block_hip_impl(rows, cols, diff_ptr, diff_stride, src_ptr, src_stride, pred_ptr, pred_stride), (rows, cols, diff_ptr, diff_stride, src_ptr, src_stride, pred_ptr, pred_stride)); }
-static void svt_aom_subtract_block_hip_impl(int rows, int cols, int16_t *diff_ptr, ptrdiff_t diff_stride, const uint8_t *src_ptr, ptrdiff_t src_stride, const uint8_t *pred_ptr, ptrdiff_t pred_stride) {
+TIER_A_LEAF(void, svt_aom_subtract_block,
+            (int rows, int cols, int16_t *diff_ptr, ptrdiff_t diff_stride, const uint8_t *src_ptr, ptrdiff_t src_stride, const
+             uint8_t *pred_ptr, ptrdiff_t pred_stride),
+            (rows, cols, diff_ptr, diff_stride, src_ptr, src_stride, pred_ptr, pred_stride)) {
     subtract_tier_a<uint8_t>(rows, cols, diff_ptr, diff_stride, src_ptr, src_stride, pred_ptr, pred_stride);
 }
-static void svt_aom_highbd_subtract_block_hip_impl(int rows, int cols, int16_t *diff_ptr, ptrdiff_t diff_stride, const uint8_t *src_ptr, ptrdiff_t src_stride, const uint8_t *pred_ptr, ptrdiff_t pred_stride, int bd);
-extern "C" void svt_aom_highbd_subtract_block_hip(int rows, int cols, int16_t *diff_ptr, ptrdiff_t diff_stride, const uint8_t *src_ptr, ptrdiff_t src_stride, const uint8_t *pred_ptr, ptrdiff_t pred_stride, int bd) { TIER_A_CALL(svt_aom_highbd_subtract_block, svt_aom_highbd_subtract_block_hip_impl(rows, cols, diff_ptr, diff_stride, src_ptr, src_stride, pred_ptr, pred_stride, bd), (rows, cols, diff_ptr, diff_stride, src_ptr, src_stride, pred_ptr, pred_stride, bd)); }
-static void svt_aom_highbd_subtract_block_hip_impl(int rows, int cols, int16_t *diff_ptr, ptrdiff_t diff_stride, const uint8_t *src_ptr, ptrdiff_t src_stride, const uint8_t *pred_ptr, ptrdiff_t pred_stride, int bd) {
+TIER_A_LEAF(void, svt_aom_highbd_subtract_block,
+            (int rows, int cols, int16_t *diff_ptr, ptrdiff_t diff_stride, const uint8_t *src_ptr, ptrdiff_t src_stride, const
+             uint8_t *pred_ptr, ptrdiff_t pred_stride, int bd),
+            (rows, cols, diff_ptr, diff_stride, src_ptr, src_stride, pred_ptr, pred_stride, bd)) {
     (void)bd;
     subtract_tier_a<uint16_t>(rows, cols, diff_ptr, diff_stride, (const uint16_t *)src_ptr, src_stride, (const uint16_t *)pred_ptr,
                               pred_stride);
 }
 // svt_residual_kernel8bit / 16bit (common_dsp_rtcd.h:163,174; pic_operators.c:101-143): the same difference with the
 // operands in another order
-static void svt_residual_kernel8bit_hip_impl(uint8_t *input, uint32_t input_stride, uint8_t *pred, uint32_t pred_stride, int16_t *residual, uint32_t residual_stride, uint32_t area_width, uint32_t area_height);
-extern "C" void svt_residual_kernel8bit_hip(uint8_t *input, uint32_t input_stride, uint8_t *pred, uint32_t pred_stride, int16_t *residual, uint32_t residual_stride, uint32_t area_width, uint32_t area_height) { TIER_A_CALL(svt_residual_kernel8bit, svt_residual_kernel8bit_hip_impl(input, input_stride, pred, pred_stride, residual, residual_stride, area_width, area_height), (input, input_stride, pred, pred_stride, residual, residual_stride, area_width, area_height)); }
-static void svt_residual_kernel8bit_hip_impl(uint8_t *input, uint32_t input_stride, uint8_t *pred, uint32_t pred_stride, int16_t *residual, uint32_t residual_stride, uint32_t area_width, uint32_t area_height) {
+TIER_A_LEAF(void, svt_residual_kernel8bit,
+            (uint8_t *input, uint32_t input_stride, uint8_t *pred, uint32_t pred_stride, int16_t *residual, uint32_t
+             residual_stride, uint32_t area_width, uint32_t area_height),
+            (input, input_stride, pred, pred_stride, residual, residual_stride, area_width, area_height)) {
     subtract_tier_a<uint8_t>((int)area_height, (int)area_width, residual, residual_stride, input, input_stride, pred, pred_stride);
 }
-static void svt_residual_kernel16bit_hip_impl(uint16_t *input, uint32_t input_stride, uint16_t *pred, uint32_t pred_stride, int16_t *residual, uint32_t residual_stride, uint32_t area_width, uint32_t area_height);
-extern "C" void svt_residual_kernel16bit_hip(uint16_t *input, uint32_t input_stride, uint16_t *pred, uint32_t pred_stride, int16_t *residual, uint32_t residual_stride, uint32_t area_width, uint32_t area_height) { TIER_A_CALL(svt_residual_kernel16bit, svt_residual_kernel16bit_hip_impl(input, input_stride, pred, pred_stride, residual, residual_stride, area_width, area_height), (input, input_stride, pred, pred_stride, residual, residual_stride, area_width, area_height)); }
-static void svt_residual_kernel16bit_hip_impl(uint16_t *input, uint32_t input_stride, uint16_t *pred, uint32_t pred_stride, int16_t *residual, uint32_t residual_stride, uint32_t area_width, uint32_t area_height) {
+TIER_A_LEAF(void, svt_residual_kernel16bit,
+            (uint16_t *input, uint32_t input_stride, uint16_t *pred, uint32_t pred_stride, int16_t *residual, uint32_t
+             residual_stride, uint32_t area_width, uint32_t area_height),
+            (input, input_stride, pred, pred_stride, residual, residual_stride, area_width, area_height)) {
     subtract_tier_a<uint16_t>((int)area_height, (int)area_width, residual, residual_stride, input, input_stride, pred, pred_stride);
 }
 // Tier B: the same sum over two DEVICE planes (what picture_sse_calculations, deblocking_filter.c:716-834, asks of the two leaves after
@@ -211,36 +195,31 @@ extern "C" int32_t svt_hip_plane_sse(const void *d_a, uint32_t a_stride, const v
 
 // svt_spatial_full_distortion_kernel (common_dsp_rtcd.h:171; picture_operators_c.c:62-78) and svt_full_distortion_kernel16_bits
 // (common_dsp_rtcd.h:173; pic_operators.c:174-196: byte pointers reinterpreted as 16-bit samples, offsets in samples)
-static uint64_t svt_spatial_full_distortion_kernel_hip_impl(uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *recon, int32_t recon_offset, uint32_t recon_stride, uint32_t area_width, uint32_t area_height);
-extern "C" uint64_t svt_spatial_full_distortion_kernel_hip(uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *recon, int32_t recon_offset, uint32_t recon_stride, uint32_t area_width, uint32_t area_height) { TIER_A_CALL(svt_spatial_full_distortion_kernel, svt_spatial_full_distortion_kernel_hip_impl(input, input_offset, input_stride, recon, recon_offset, recon_stride, area_width, area_height), (input, input_offset, input_stride, recon, recon_offset, recon_stride, area_width, area_height)); }
-static uint64_t svt_spatial_full_distortion_kernel_hip_impl(uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *recon, int32_t recon_offset, uint32_t recon_stride, uint32_t area_width, uint32_t area_height) {
+TIER_A_LEAF(uint64_t, svt_spatial_full_distortion_kernel,
+            (uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *recon, int32_t recon_offset, uint32_t
+             recon_stride, uint32_t area_width, uint32_t area_height),
+            (input, input_offset, input_stride, recon, recon_offset, recon_stride, area_width, area_height)) {
     return spatial_sse_tier_a<uint8_t>(input + input_offset, input_stride, recon + recon_offset, recon_stride, area_width, area_height,
                                        "svt_spatial_full_distortion_kernel");
 }
-static uint64_t svt_full_distortion_kernel16_bits_hip_impl(uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *pred, int32_t pred_offset, uint32_t pred_stride, uint32_t area_width, uint32_t area_height);
-extern "C" uint64_t svt_full_distortion_kernel16_bits_hip(uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *pred, int32_t pred_offset, uint32_t pred_stride, uint32_t area_width, uint32_t area_height) { TIER_A_CALL(svt_full_distortion_kernel16_bits, svt_full_distortion_kernel16_bits_hip_impl(input, input_offset, input_stride, pred, pred_offset, pred_stride, area_width, area_height), (input, input_offset, input_stride, pred, pred_offset, pred_stride, area_width, area_height)); }
-static uint64_t svt_full_distortion_kernel16_bits_hip_impl(uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *pred, int32_t pred_offset, uint32_t pred_stride, uint32_t area_width, uint32_t area_height) {
+TIER_A_LEAF(uint64_t, svt_full_distortion_kernel16_bits,
+            (uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *pred, int32_t pred_offset, uint32_t pred_stride,
+             uint32_t area_width, uint32_t area_height),
+            (input, input_offset, input_stride, pred, pred_offset, pred_stride, area_width, area_height)) {
     return spatial_sse_tier_a<uint16_t>((const uint16_t *)input + input_offset, input_stride, (const uint16_t *)pred + pred_offset,
                                         pred_stride, area_width, area_height, "svt_full_distortion_kernel16_bits");
 }
-static int svt_aom_satd_hip_impl(const int32_t *coeff, int length);
-extern "C" int svt_aom_satd_hip(const int32_t *coeff, int length) { TIER_A_CALL(svt_aom_satd, svt_aom_satd_hip_impl(coeff, length), (coeff, length)); }
-static int svt_aom_satd_hip_impl(const int32_t *coeff, int length) {
+TIER_A_LEAF(int, svt_aom_satd,
+            (const int32_t *coeff, int length),
+            (coeff, length)) {
     if (length <= 0)
         return 0;
-    if (!ensure_init())
-        fatal("satd");
-    const size_t cb = up256((size_t)length * 4);
-    Scratch     &sc = tls_scratch();
-    uint8_t     *h = sc.host(cb + 256), *d = sc.device(cb + 256);
-    memcpy(h, coeff, (size_t)length * 4);
-    hipStream_t st = resolve_stream(nullptr);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, h, (size_t)length * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(satd_kernel, dim3(1), dim3(256), 0, st, (const int32_t *)d, length, (int32_t *)(d + cb));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(h + cb, d + cb, 4, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    return *(const int32_t *)(h + cb);
+    TierAStage   s("satd");
+    const size_t off_in = s.in(coeff, (size_t)length * 4), off_out = s.out(4);
+    s.upload();
+    hipLaunchKernelGGL(satd_kernel, dim3(1), dim3(256), 0, s.stream(), s.dev<const int32_t>(off_in), length, s.dev<int32_t>(off_out));
+    s.finish(off_out, 4);
+    return *s.host<int32_t>(off_out);
 }
 
 namespace {
@@ -248,35 +227,26 @@ void distortion_tier_a(const int32_t *coeff, uint32_t cs, const int32_t *recon, 
     out[0] = out[1] = 0;
     if (!w || !h)
         return;
-    if (!ensure_init())
-        fatal("full_distortion");
-    const size_t n = (size_t)w * h, cb = up256(n * 4);
-    Scratch     &sc = tls_scratch();
-    uint8_t     *hh = sc.host(2 * cb + 256), *d = sc.device(2 * cb + 256);
-    for (uint32_t r = 0; r < h; r++) {
-        memcpy(hh + (size_t)r * w * 4, coeff + (size_t)r * cs, (size_t)w * 4);
-        if (recon)
-            memcpy(hh + cb + (size_t)r * w * 4, recon + (size_t)r * rs, (size_t)w * 4);
-    }
-    hipStream_t st = resolve_stream(nullptr);
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(d, hh, recon ? 2 * cb : cb, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(full_distortion_kernel, dim3(1), dim3(256), 0, st, (const int32_t *)d, (int)w, recon ? (const int32_t *)(d + cb) : nullptr,
-                       (int)w, (int)w, (int)h, (uint64_t *)(d + 2 * cb));
-    SVT_HIP_CHECK_FATAL(hipGetLastError());
-    SVT_HIP_CHECK_FATAL(hipMemcpyAsync(hh + 2 * cb, d + 2 * cb, 16, hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK_FATAL(hipStreamSynchronize(st));
-    memcpy(out, hh + 2 * cb, 16);
+    TierAStage   s("full_distortion");
+    const size_t off_co = s.in_rows(coeff, (size_t)cs * 4, h, (size_t)w * 4);
+    const size_t off_rc = recon ? s.in_rows(recon, (size_t)rs * 4, h, (size_t)w * 4) : 0, off_out = s.out(16);
+    s.upload();
+    hipLaunchKernelGGL(full_distortion_kernel, dim3(1), dim3(256), 0, s.stream(), s.dev<const int32_t>(off_co), (int)w,
+                       recon ? s.dev<const int32_t>(off_rc) : nullptr, (int)w, (int)w, (int)h, s.dev<uint64_t>(off_out));
+    s.finish(off_out, 16);
+    memcpy(out, s.host(off_out), 16);
 }
 }  // namespace
 
-static void svt_full_distortion_kernel32_bits_hip_impl(int32_t *coeff, uint32_t coeff_stride, int32_t *recon_coeff, uint32_t recon_coeff_stride, uint64_t distortion_result[2], uint32_t area_width, uint32_t area_height);
-extern "C" void svt_full_distortion_kernel32_bits_hip(int32_t *coeff, uint32_t coeff_stride, int32_t *recon_coeff, uint32_t recon_coeff_stride, uint64_t distortion_result[2], uint32_t area_width, uint32_t area_height) { TIER_A_CALL(svt_full_distortion_kernel32_bits, svt_full_distortion_kernel32_bits_hip_impl(coeff, coeff_stride, recon_coeff, recon_coeff_stride, distortion_result, area_width, area_height), (coeff, coeff_stride, recon_coeff, recon_coeff_stride, distortion_result, area_width, area_height)); }
-static void svt_full_distortion_kernel32_bits_hip_impl(int32_t *coeff, uint32_t coeff_stride, int32_t *recon_coeff, uint32_t recon_coeff_stride, uint64_t distortion_result[2], uint32_t area_width, uint32_t area_height) {
+TIER_A_LEAF(void, svt_full_distortion_kernel32_bits,
+            (int32_t *coeff, uint32_t coeff_stride, int32_t *recon_coeff, uint32_t recon_coeff_stride, uint64_t
+             distortion_result[2], uint32_t area_width, uint32_t area_height),
+            (coeff, coeff_stride, recon_coeff, recon_coeff_stride, distortion_result, area_width, area_height)) {
     distortion_tier_a(coeff, coeff_stride, recon_coeff, recon_coeff_stride, distortion_result, area_width, area_height);
 }
-static void svt_full_distortion_kernel_cbf_zero32_bits_hip_impl(int32_t *coeff, uint32_t coeff_stride, uint64_t distortion_result[2], uint32_t area_width, uint32_t area_height);
-extern "C" void svt_full_distortion_kernel_cbf_zero32_bits_hip(int32_t *coeff, uint32_t coeff_stride, uint64_t distortion_result[2], uint32_t area_width, uint32_t area_height) { TIER_A_CALL(svt_full_distortion_kernel_cbf_zero32_bits, svt_full_distortion_kernel_cbf_zero32_bits_hip_impl(coeff, coeff_stride, distortion_result, area_width, area_height), (coeff, coeff_stride, distortion_result, area_width, area_height)); }
-static void svt_full_distortion_kernel_cbf_zero32_bits_hip_impl(int32_t *coeff, uint32_t coeff_stride, uint64_t distortion_result[2], uint32_t area_width, uint32_t area_height) {
+TIER_A_LEAF(void, svt_full_distortion_kernel_cbf_zero32_bits,
+            (int32_t *coeff, uint32_t coeff_stride, uint64_t distortion_result[2], uint32_t area_width, uint32_t area_height),
+            (coeff, coeff_stride, distortion_result, area_width, area_height)) {
     distortion_tier_a(coeff, coeff_stride, nullptr, 0, distortion_result, area_width, area_height);
 }
 
