@@ -1,6 +1,6 @@
 /*
- * svt_hip_inter.h — C-ABI for inter-prediction interpolation: the single-reference and the
- * compound ("jnt") families.
+ * svt_hip_inter.h — C-ABI for inter prediction: interpolation (the single-reference and the
+ * compound ("jnt") families), the masked-compound and OBMC blends, and the compound mask search.
  *
  * Reference interfaces replaced (paths relative to /root/reference):
  *   Source/Lib/Codec/common_dsp_rtcd.h:185-221   svt_av1_convolve_{2d_sr,x_sr,y_sr,2d_copy_sr},
@@ -8,7 +8,13 @@
  *   Source/Lib/Codec/inter_prediction.c:311-668, 670-1035   their C implementations
  *   callers: svt_aom_inter_predictor / highbd_inter_predictor via svt_aom_convolve[subpel_x != 0][subpel_y != 0][is_compound]
  *            (inter_prediction.c:1036-1062)
- * Scaled references, OBMC and masked compounds are not covered.
+ *   Source/Lib/Codec/blend_a64_mask.c:34-367, inter_prediction.c:2374-2404   svt_aom_{lowbd,highbd}_blend_a64_d16_mask_c,
+ *                                                svt_aom_(highbd_)blend_a64_mask_c, the vmask / hmask blends of OBMC
+ *   Source/Lib/C_DEFAULT/inter_prediction_c.c:15-40   svt_av1_build_compound_diffwtd_mask_d16_c
+ *   Source/Lib/Codec/enc_inter_prediction.c:386-449, 501-547, 4676-4719   pick_interinter_wedge / pick_interinter_seg
+ *                                                (use_rate == 0) and the residuals of svt_aom_calc_pred_masked_compound
+ * Scaled references are not covered.  OBMC's neighbour predictions, inter-intra prediction and the rate model of the mask
+ * search (model_rd_with_curvfit) stay on the host.
  */
 #ifndef SVT_HIP_INTER_H
 #define SVT_HIP_INTER_H
@@ -86,6 +92,85 @@ typedef struct SvtHipConvolveDesc {
 SVT_HIP_API int32_t svt_hip_convolve_batch(const SvtHipConvolveDesc *d_desc, uint32_t n, void *stream);
 /* the same entry point under its first name */
 SVT_HIP_API int32_t svt_hip_convolve_sr_batch(const SvtHipConvolveDesc *d_desc, uint32_t n, void *stream);
+
+/* ---- Masked-compound and OBMC blends (Tier B) -------------------------------------------------------------------------
+ * One descriptor = one block of one plane, all pointers device memory.
+ *
+ * Masks are CALLER DATA, like the interpolation kernels of SvtHipConvolveDesc: the wedge tables
+ * (svt_aom_get_contiguous_soft_mask), the OBMC ramps (svt_av1_get_obmc_mask) and the inter-intra smooth masks are the
+ * encoder's own arrays; the caller uploads them once.  The library generates none of them.
+ *
+ * Ordering: a descriptor that reads a mask (or a ConvBufType block) which another descriptor writes must be launched in a
+ * LATER call on the same stream.  The chroma planes of a difference-weighted compound read the mask that the luma
+ * descriptor (SVT_HIP_BLEND_D16_DIFFWTD) builds: luma in one call, chroma in the next.
+ *
+ * Descriptors live in device memory, so the host cannot validate them.  The kernel SKIPS a descriptor with w == 0 or
+ * h == 0, and one whose kind, subw / subh, mask_type, sizes, rounds, bit depth or NULL pointers are out of range (see the
+ * fields); a skipped descriptor leaves dst (and mask) untouched. */
+#define SVT_HIP_BLEND_D16 0         /* svt_aom_{lowbd,highbd}_blend_a64_d16_mask_c as svt_aom_build_masked_compound_no_round calls them */
+#define SVT_HIP_BLEND_D16_DIFFWTD 1 /* svt_av1_build_compound_diffwtd_mask_d16_c, then the d16 blend with that mask (plane 0) */
+#define SVT_HIP_BLEND_MASK 2        /* svt_aom_blend_a64_mask_c / svt_aom_highbd_blend_a64_mask_c */
+#define SVT_HIP_BLEND_VMASK 3       /* svt_aom_blend_a64_vmask_c / svt_aom_highbd_blend_a64_vmask_16bit_c: mask[h], one weight per row */
+#define SVT_HIP_BLEND_HMASK 4       /* svt_aom_blend_a64_hmask_c / svt_aom_highbd_blend_a64_hmask_16bit_c: mask[w], one weight per column */
+#define SVT_HIP_BLEND_KINDS 5
+
+typedef struct SvtHipBlendDesc {
+    const void *src0, *src1; /* D16 kinds: ConvBufType (uint16) blocks as compound-1 descriptors of svt_hip_convolve_batch leave
+                              * them; the other kinds: pixels (uint8, or uint16 with is_16bit).  mask weighs src0, 64 - mask src1 */
+    void       *dst;         /* pixels (uint8, or uint16 with is_16bit).  VMASK / HMASK / MASK: may be src0 or src1 (with that
+                              * source's stride): OBMC blends in place */
+    uint8_t    *mask;        /* D16, MASK: [.][mask_stride], read; sub-sampled planes read the luma-sized mask (subw / subh).
+                              * D16_DIFFWTD: WRITTEN as [h][w] (stride w, the reference's layout; mask_stride is not used) and
+                              * used for the blend in the same pass.  VMASK: h entries.  HMASK: w entries */
+    uint32_t    src0_stride, src1_stride, dst_stride, mask_stride; /* in samples */
+    uint16_t    w, h;        /* 1 .. 128 (D16 kinds: 4 .. 128); w == 0 or h == 0: skipped */
+    uint8_t     kind;        /* SVT_HIP_BLEND_* */
+    uint8_t     subw, subh;  /* D16, MASK: 0 / 1; (1,1): rounded mean of 2 x 2 mask samples, (1,0) / (0,1): AOM_BLEND_AVG of two.
+                              * 0 for the other kinds */
+    uint8_t     mask_type;   /* D16_DIFFWTD: 0 DIFFWTD_38, 1 DIFFWTD_38_INV; 0 for the other kinds */
+    uint8_t     round_0, round_1; /* D16 kinds: ConvolveParams of the compound prediction, round_0 + round_1 <= 14 */
+    uint8_t     bit_depth;   /* 8, 10 or 12; 8 unless is_16bit */
+    uint8_t     is_16bit;    /* 0 / 1: sample type of dst (and of src0 / src1 for the pixel kinds) */
+    uint32_t    pad_;
+} SvtHipBlendDesc;
+/* SVT_HIP_ERR_BAD_PARAMETER when d_desc == NULL or n == 0, SVT_HIP_ERR_NO_DEVICE before svt_hip_init(); nothing is launched
+ * in either case.  Asynchronous on `stream` (NULL: the calling thread's stream). */
+SVT_HIP_API int32_t svt_hip_blend_batch(const SvtHipBlendDesc *d_desc, uint32_t n, void *stream);
+
+/* ---- Compound mask search (Tier B) ------------------------------------------------------------------------------------
+ * One descriptor = one luma block of one compound candidate: what svt_aom_calc_pred_masked_compound computes behind the two
+ * predictions, then pick_interinter_wedge and pick_interinter_seg with use_rate == 0 (rd = sse, strict <, first minimum). */
+#define SVT_HIP_WEDGE_TYPES 16
+#define SVT_HIP_MASK_SEARCH_OK 0
+#define SVT_HIP_MASK_SEARCH_BAD_WEDGE_SIZE 1 /* wedge_masks != NULL for a size without wedges */
+#define SVT_HIP_MASK_SEARCH_BAD_DESC 2       /* NULL block pointer, size, bit depth or sample type out of range */
+
+typedef struct SvtHipMaskSearchDesc {
+    const void    *src, *pred0, *pred1; /* pixels: uint8, or uint16 with is_16bit */
+    const uint8_t *wedge_masks;         /* [2 * SVT_HIP_WEDGE_TYPES][h * w]: mask (2 * index + sign) of this block size, i.e. the
+                                         * reference's svt_aom_get_contiguous_soft_mask(index, sign, bsize) in its own order
+                                         * (one contiguous range of wedge_mask_buf per size); NULL: no wedge search.  Sizes with
+                                         * wedges: 8x8 8x16 16x8 16x16 16x32 32x16 32x32 8x32 32x8 */
+    uint32_t       src_stride, pred0_stride, pred1_stride; /* in samples */
+    uint16_t       w, h;                /* 8, 16, 32, 64 or 128 each */
+    uint8_t        bit_depth;           /* 8, 10 or 12; 8 unless is_16bit.  Selects the difference-weighted mask's scale */
+    uint8_t        is_16bit;
+    uint8_t        pad_[6];
+} SvtHipMaskSearchDesc;
+
+typedef struct SvtHipMaskSearchResult {
+    uint64_t wedge_sse[SVT_HIP_WEDGE_TYPES];  /* svt_av1_wedge_sse_from_residuals under wedge_sign[i]; 0 without wedges */
+    uint64_t diffwtd_sse[2];                  /* ... under DIFFWTD_38 and DIFFWTD_38_INV */
+    uint32_t pred0_to_pred1_dist;             /* SAD(pred0, pred1) */
+    uint8_t  wedge_sign[SVT_HIP_WEDGE_TYPES]; /* svt_av1_wedge_sign_from_residuals */
+    int8_t   best_wedge_index;                /* -1 without wedges */
+    int8_t   best_wedge_sign;
+    uint8_t  best_diffwtd_type;
+    uint8_t  status;                          /* SVT_HIP_MASK_SEARCH_*; non-zero: every other field is 0 */
+} SvtHipMaskSearchResult;
+/* d_result[i] belongs to d_desc[i].  Errors as svt_hip_blend_batch (d_result == NULL is a bad parameter too). */
+SVT_HIP_API int32_t svt_hip_compound_mask_search_batch(const SvtHipMaskSearchDesc *d_desc, SvtHipMaskSearchResult *d_result,
+                                                       uint32_t n, void *stream);
 
 #ifdef __cplusplus
 }

@@ -148,6 +148,10 @@ def load():
             getattr(_lib, n).restype = C.c_uint64
         _lib.svt_hip_intra_search_frames.restype = C.c_int32
         _lib.svt_hip_intra_search_frames.argtypes = [C.POINTER(IntraSearchJob), C.c_uint32, C.c_void_p]
+        _lib.svt_hip_blend_batch.restype = C.c_int32
+        _lib.svt_hip_blend_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        _lib.svt_hip_compound_mask_search_batch.restype = C.c_int32
+        _lib.svt_hip_compound_mask_search_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     return _lib
 
 
@@ -271,6 +275,36 @@ class ConvolveDesc(C.Structure):         # SvtHipConvolveDesc (include/svt_hip_i
                 ("round_0", C.c_uint8), ("round_1", C.c_uint8), ("bit_depth", C.c_uint8), ("is_16bit", C.c_uint8), ("compound", C.c_uint8),
                 ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8), ("pad_", C.c_uint8 * 3), ("cbuf", C.c_void_p),
                 ("cbuf_stride", C.c_uint32), ("pad2_", C.c_uint32)]
+
+
+BLEND_D16, BLEND_D16_DIFFWTD, BLEND_MASK, BLEND_VMASK, BLEND_HMASK = range(5)   # SVT_HIP_BLEND_*
+WEDGE_TYPES = 16
+MASK_SEARCH_OK, MASK_SEARCH_BAD_WEDGE_SIZE, MASK_SEARCH_BAD_DESC = range(3)     # SVT_HIP_MASK_SEARCH_*
+
+
+class BlendDesc(C.Structure):            # SvtHipBlendDesc (include/svt_hip_inter.h)
+    _fields_ = [("src0", C.c_void_p), ("src1", C.c_void_p), ("dst", C.c_void_p), ("mask", C.c_void_p), ("src0_stride", C.c_uint32),
+                ("src1_stride", C.c_uint32), ("dst_stride", C.c_uint32), ("mask_stride", C.c_uint32), ("w", C.c_uint16), ("h", C.c_uint16),
+                ("kind", C.c_uint8), ("subw", C.c_uint8), ("subh", C.c_uint8), ("mask_type", C.c_uint8), ("round_0", C.c_uint8),
+                ("round_1", C.c_uint8), ("bit_depth", C.c_uint8), ("is_16bit", C.c_uint8), ("pad_", C.c_uint32)]
+
+
+class MaskSearchDesc(C.Structure):       # SvtHipMaskSearchDesc
+    _fields_ = [("src", C.c_void_p), ("pred0", C.c_void_p), ("pred1", C.c_void_p), ("wedge_masks", C.c_void_p),
+                ("src_stride", C.c_uint32), ("pred0_stride", C.c_uint32), ("pred1_stride", C.c_uint32), ("w", C.c_uint16),
+                ("h", C.c_uint16), ("bit_depth", C.c_uint8), ("is_16bit", C.c_uint8), ("pad_", C.c_uint8 * 6)]
+
+
+class MaskSearchResult(C.Structure):     # SvtHipMaskSearchResult
+    _fields_ = [("wedge_sse", C.c_uint64 * WEDGE_TYPES), ("diffwtd_sse", C.c_uint64 * 2), ("pred0_to_pred1_dist", C.c_uint32),
+                ("wedge_sign", C.c_uint8 * WEDGE_TYPES), ("best_wedge_index", C.c_int8), ("best_wedge_sign", C.c_int8),
+                ("best_diffwtd_type", C.c_uint8), ("status", C.c_uint8)]
+
+
+# numpy view of an array of SvtHipMaskSearchResult
+MASK_SEARCH_RESULT_DTYPE = [("wedge_sse", "<u8", (WEDGE_TYPES,)), ("diffwtd_sse", "<u8", (2,)), ("pred0_to_pred1_dist", "<u4"),
+                            ("wedge_sign", "u1", (WEDGE_TYPES,)), ("best_wedge_index", "i1"), ("best_wedge_sign", "i1"),
+                            ("best_diffwtd_type", "u1"), ("status", "u1")]
 
 
 class TfBlock(C.Structure):              # SvtHipTfBlock (include/svt_hip_tf.h)

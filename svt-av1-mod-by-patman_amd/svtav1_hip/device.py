@@ -139,3 +139,32 @@ def me_frames(lib, jobs, stream=None, sync=True):
     check(lib, lib.svt_hip_me_frames(arr, C.c_uint32(len(jobs)), C.c_void_p(stream)), "svt_hip_me_frames")
     if sync:
         check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+
+
+def upload_descriptors(lib, descs, stream=None):
+    """A list of ctypes structures of one type as a device array (the Tier B entry points of include/svt_hip_inter.h read their
+    descriptors from device memory).  Keep the returned buffer alive until the launch that reads it has finished."""
+    arr = (type(descs[0]) * len(descs))(*descs)
+    buf = DeviceBuffer(lib, C.sizeof(arr))
+    buf.upload(np.frombuffer(arr, np.uint8), stream)
+    return buf
+
+
+def blend_batch(lib, descs, stream=None, sync=True):
+    """svt_hip_blend_batch over a list of abi.BlendDesc (one launch)."""
+    d_desc = upload_descriptors(lib, descs, stream)
+    check(lib, lib.svt_hip_blend_batch(C.c_void_p(d_desc.ptr), C.c_uint32(len(descs)), C.c_void_p(stream)), "svt_hip_blend_batch")
+    if sync:
+        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+    return d_desc
+
+
+def compound_mask_search_batch(lib, descs, stream=None, fill=0xA5):
+    """svt_hip_compound_mask_search_batch over a list of abi.MaskSearchDesc (one launch); the results as a numpy record array
+    (abi.MASK_SEARCH_RESULT_DTYPE).  The result buffer is pre-filled with `fill`."""
+    d_desc = upload_descriptors(lib, descs, stream)
+    d_res = DeviceBuffer(lib, C.sizeof(abi.MaskSearchResult) * len(descs))
+    d_res.fill(fill, stream)
+    check(lib, lib.svt_hip_compound_mask_search_batch(C.c_void_p(d_desc.ptr), C.c_void_p(d_res.ptr), C.c_uint32(len(descs)),
+                                                      C.c_void_p(stream)), "svt_hip_compound_mask_search_batch")
+    return d_res.download(np.dtype(abi.MASK_SEARCH_RESULT_DTYPE), (len(descs),), stream)

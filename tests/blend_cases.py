@@ -1,0 +1,527 @@
+"""TEST INFRASTRUCTURE — masked-compound / OBMC blends and the compound mask search (include/svt_hip_inter.h): cases, input
+generators, the oracle and the golden fixture of tests/test_blend_abi.py and tests/test_gpu_blend.py.
+
+The oracle calls the reference's own exported functions (oracle/_ref/libsvtref.so through pyorc.ref()): the blend_a64 family,
+svt_av1_build_compound_diffwtd_mask_d16_c, and for the search exactly the calls of svt_aom_calc_pred_masked_compound and
+pick_wedge / pick_interinter_seg with use_rate == 0 (Source/Lib/Codec/enc_inter_prediction.c:386-449, 501-547, 4676-4719).
+tests/golden/inter_blend.npz holds the wedge masks of the nine wedge sizes and the OBMC ramps as the reference produced them, and
+the expected outputs of the cases below; inputs are regenerated from seeds.  Written by
+`PYTHONPATH=oracle:svt-av1-mod-by-patman_amd python tests/blend_cases.py`.
+"""
+import ctypes as C
+import hashlib
+import os
+
+import numpy as np
+
+import conv_cases as K
+from svtav1_hip import abi
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "inter_blend.npz")
+GUARD = 2            # guard rows above and below every block
+FILL = 0xA5          # guard rows and stride padding
+FULL_LIMIT = 4096    # expected blocks up to this many samples are kept in full, larger ones as sha256
+# BlockSize (definitions.h:773-794) of the sizes with wedges (svt_aom_get_wedge_bits_lookup == 4)
+WEDGE_BSIZE = {(8, 8): 3, (8, 16): 4, (16, 8): 5, (16, 16): 6, (16, 32): 7, (32, 16): 8, (32, 32): 9, (8, 32): 18, (32, 8): 19}
+OBMC_LENGTHS = (1, 2, 4, 8, 16, 32)
+COMPOUND_WEDGE, COMPOUND_DIFFWTD = 2, 3
+FORMATS = ((8, 0), (8, 1), (10, 1))   # (bit depth, 16-bit samples)
+
+
+def digest(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def _fn(lib, name, restype, *argtypes):
+    """A private prototype of an exported function (argtypes of the shared CDLL object stay untouched)."""
+    return C.CFUNCTYPE(restype, *argtypes)(C.cast(getattr(lib, name), C.c_void_p).value)
+
+
+class Buf:
+    """A block inside a host buffer with GUARD rows above and below, `off` samples in front of and `extra` samples behind every
+    row; everything outside the block holds FILL bytes."""
+
+    def __init__(self, block, extra=0, off=0):
+        block = np.asarray(block)
+        self.h, self.w = block.shape
+        self.off, self.stride = off, off + self.w + extra
+        self.a = np.frombuffer(bytes([FILL]) * ((self.h + 2 * GUARD) * self.stride * block.itemsize), block.dtype).copy()
+        self.a = self.a.reshape(self.h + 2 * GUARD, self.stride)
+        self.view[:] = block
+
+    @property
+    def view(self):
+        return self.a[GUARD:GUARD + self.h, self.off:self.off + self.w]
+
+    @property
+    def byte_offset(self):
+        return (GUARD * self.stride + self.off) * self.a.itemsize
+
+    @property
+    def ptr(self):
+        return self.a.ctypes.data + self.byte_offset
+
+    def outside_untouched(self):
+        keep = self.a.copy()
+        keep[GUARD:GUARD + self.h, self.off:self.off + self.w] = np.frombuffer(bytes([FILL]) * keep.itemsize, keep.dtype)[0]
+        return (keep.view(np.uint8) == FILL).all()
+
+
+# ---- the reference's tables -------------------------------------------------------------------------------------------------
+def ref_tables(ref):
+    """{wedge_WxH: [32][h * w] in the order 2 * index + sign, obmc_L: [L]} read from the reference."""
+    ref.svt_av1_init_wedge_masks()   # needs the svt_memcpy pointer: pyorc.ref() has run ref_init()
+    soft = _fn(ref, "svt_aom_get_contiguous_soft_mask", C.c_void_p, C.c_int, C.c_int, C.c_int)
+    bits = _fn(ref, "svt_aom_get_wedge_bits_lookup", C.c_int32, C.c_int)
+    obmc = _fn(ref, "svt_av1_get_obmc_mask", C.c_void_p, C.c_int)
+    out = {}
+    for (w, h), bsize in WEDGE_BSIZE.items():
+        assert bits(bsize) == 4
+        out[f"wedge_{w}x{h}"] = np.stack([np.ctypeslib.as_array(C.cast(soft(i, s, bsize), C.POINTER(C.c_uint8)), (h * w,)).copy()
+                                          for i in range(abi.WEDGE_TYPES) for s in (0, 1)])
+    for n in OBMC_LENGTHS:
+        out[f"obmc_{n}"] = np.ctypeslib.as_array(C.cast(obmc(n), C.POINTER(C.c_uint8)), (n,)).copy()
+    return out
+
+
+# ---- blend cases ------------------------------------------------------------------------------------------------------------
+# (name, kind, w, h, bit depth, is_16bit, subw, subh, mask_type, layout index, mask source, in place)
+def _blend_cases():
+    cases, k = [], 0
+    d16_sizes = [(4, 4), (8, 8), (16, 8), (8, 32), (32, 32), (64, 64), (128, 128), (64, 128), (4, 16), (16, 64), (128, 64), (32, 16)]
+    for bd, is16 in FORMATS:
+        for subw, subh in ((0, 0), (1, 0), (0, 1), (1, 1)):
+            for _ in range(3):
+                w, h = d16_sizes[k % len(d16_sizes)]
+                src = "wedge" if (w << subw, h << subh) in WEDGE_BSIZE and k % 2 == 0 else "random"
+                cases.append((f"d16_{w}x{h}_bd{bd}_{is16}_s{subw}{subh}_{k}", abi.BLEND_D16, w, h, bd, is16, subw, subh, 0, k, src, 0))
+                k += 1
+    for bd, is16 in FORMATS:
+        for mask_type in (0, 1):
+            for w, h in ((8, 8), (16, 32), (64, 64), (128, 128))[mask_type::2] + ((32, 8),):
+                cases.append((f"diffwtd_{w}x{h}_bd{bd}_{is16}_t{mask_type}", abi.BLEND_D16_DIFFWTD, w, h, bd, is16, 0, 0, mask_type, k, "built", 0))
+                k += 1
+    px_sizes = [(4, 4), (8, 16), (16, 16), (32, 32), (2, 2), (64, 32), (128, 128), (8, 8)]
+    for bd, is16 in FORMATS:
+        for subw, subh in ((0, 0), (1, 0), (0, 1), (1, 1)):
+            for _ in range(2):
+                w, h = px_sizes[k % len(px_sizes)]
+                src = "wedge" if (w << subw, h << subh) in WEDGE_BSIZE and k % 2 == 0 else "random"
+                cases.append((f"mask_{w}x{h}_bd{bd}_{is16}_s{subw}{subh}_{k}", abi.BLEND_MASK, w, h, bd, is16, subw, subh, 0, k, src, k % 3 == 0))
+                k += 1
+    # OBMC: above neighbours blend `overlap` rows with a ramp per row, left neighbours `overlap` columns with a ramp per column
+    for bd, is16 in FORMATS:
+        for w, h in ((8, 4), (16, 8), (64, 32), (4, 2), (8, 1), (128, 32), (32, 16), (4, 4)):
+            cases.append((f"vmask_{w}x{h}_bd{bd}_{is16}", abi.BLEND_VMASK, w, h, bd, is16, 0, 0, 0, k, "obmc", k % 2))
+            k += 1
+        for w, h in ((4, 8), (2, 8), (8, 16), (32, 64), (32, 128), (1, 4), (16, 32), (2, 2)):
+            cases.append((f"hmask_{w}x{h}_bd{bd}_{is16}", abi.BLEND_HMASK, w, h, bd, is16, 0, 0, 0, k, "obmc", k % 2))
+            k += 1
+    return cases
+
+
+BLEND_CASES = _blend_cases()
+LAYOUTS = [(0, 0), (3, 1), (8, 4), (5, 3), (1, 0), (6, 2)]   # (extra samples behind a row, samples in front): odd ones misalign rows
+
+
+def d16_round_offset(bd, r0, r1):
+    offset_bits = bd + 14 - r0
+    return (1 << (offset_bits - r1)) + (1 << (offset_bits - r1 - 1))
+
+
+def conv_buf_block(rng, w, h, bd, extreme):
+    """A ConvBufType block: what a compound-1 prediction leaves (pixel << round_bits plus the offset, a little over- and
+    undershoot), or any uint16 at all (`extreme`: clips at both ends)."""
+    if extreme:
+        return rng.integers(0, 65536, (h, w)).astype(np.uint16)
+    r0, r1 = K.conv_rounds_compound(bd)
+    px = rng.integers(0, 1 << bd, (h, w))
+    return np.clip(d16_round_offset(bd, r0, r1) + px * (1 << (14 - r0 - r1)) + rng.integers(-80, 81, (h, w)), 0, 65535).astype(np.uint16)
+
+
+class BlendInputs:
+    """Host buffers of one blend case (src0, src1, dst, mask as Buf) and its rounds."""
+
+    def __init__(self, case, index, tables):
+        name, kind, w, h, bd, is16, subw, subh, mask_type, lay, mask_src, inplace = case
+        rng = np.random.default_rng(9000 + index)
+        self.case, self.r0, self.r1 = case, *K.conv_rounds_compound(bd)
+        px = np.uint16 if is16 else np.uint8
+        (e0, o0), (e1, o1), (e2, o2), (e3, o3) = (LAYOUTS[(lay + j) % len(LAYOUTS)] for j in range(4))
+        if kind in (abi.BLEND_D16, abi.BLEND_D16_DIFFWTD):
+            extreme = lay % 4 == 3
+            self.src0 = Buf(conv_buf_block(rng, w, h, bd, extreme), e0, o0)
+            self.src1 = Buf(conv_buf_block(rng, w, h, bd, extreme), e1, o1)
+        else:
+            self.src0 = Buf(rng.integers(0, 1 << bd, (h, w)).astype(px), e0, o0)
+            self.src1 = Buf(rng.integers(0, 1 << bd, (h, w)).astype(px), e1, o1)
+        self.inplace = bool(inplace) and kind not in (abi.BLEND_D16, abi.BLEND_D16_DIFFWTD)
+        self.dst = self.src0 if self.inplace else Buf(np.full((h, w), FILL * 0x0101 if is16 else FILL, px), e2, o2)
+        mw, mh = w << subw, h << subh
+        if mask_src == "wedge":       # contiguous, stride = the luma block's width, as the reference passes it
+            self.mask = Buf(tables[f"wedge_{mw}x{mh}"][int(rng.integers(0, 32))].reshape(mh, mw))
+        elif mask_src == "random":
+            self.mask = Buf(rng.integers(0, 65, (mh, mw)).astype(np.uint8), e3, o3)
+        elif mask_src == "built":     # [h][w] contiguous, written by the blend; starts at any byte
+            self.mask = Buf(np.full((1, h * w), FILL, np.uint8), e3, o3)
+        else:                         # one row of h (vmask) or w (hmask) weights
+            n = h if kind == abi.BLEND_VMASK else w
+            ramp = tables[f"obmc_{n}"] if n in OBMC_LENGTHS else rng.integers(0, 65, n).astype(np.uint8)
+            self.mask = Buf(ramp.reshape(1, n), e3, o3)
+
+    def desc(self, ptrs=None):
+        """abi.BlendDesc over the host buffers, or over device copies of them ({id(Buf): device pointer})."""
+        _, kind, w, h, bd, is16, subw, subh, mask_type = self.case[:9]
+        p = (lambda b: ptrs[id(b)] + b.byte_offset) if ptrs is not None else (lambda b: b.ptr)
+        return abi.BlendDesc(p(self.src0), p(self.src1), p(self.dst), p(self.mask), self.src0.stride, self.src1.stride, self.dst.stride,
+                             self.mask.stride, w, h, kind, subw, subh, mask_type, self.r0, self.r1, bd, is16, 0)
+
+    def buffers(self):
+        return list({id(b): b for b in (self.src0, self.src1, self.dst, self.mask)}.values())
+
+
+class RefBlend:
+    """The reference's blends on host buffers."""
+
+    def __init__(self, ref):
+        V, u32, i = C.c_void_p, C.c_uint32, C.c_int
+        self.d16_lb = _fn(ref, "svt_aom_lowbd_blend_a64_d16_mask_c", None, V, u32, V, u32, V, u32, V, u32, i, i, i, i, V)
+        self.d16_hb = _fn(ref, "svt_aom_highbd_blend_a64_d16_mask_c", None, V, u32, V, u32, V, u32, V, u32, i, i, i, i, V, i)
+        self.diffwtd_d16 = _fn(ref, "svt_av1_build_compound_diffwtd_mask_d16_c", None, V, i, V, i, V, i, i, i, V, i)
+        self.mask_lb = _fn(ref, "svt_aom_blend_a64_mask_c", None, V, u32, V, u32, V, u32, V, u32, i, i, i, i)
+        self.mask_hb = _fn(ref, "svt_aom_highbd_blend_a64_mask_c", None, V, u32, V, u32, V, u32, V, u32, i, i, i, i, i)
+        self.v_lb = _fn(ref, "svt_aom_blend_a64_vmask_c", None, V, u32, V, u32, V, u32, V, i, i)
+        self.h_lb = _fn(ref, "svt_aom_blend_a64_hmask_c", None, V, u32, V, u32, V, u32, V, i, i)
+        self.v_hb = _fn(ref, "svt_aom_highbd_blend_a64_vmask_16bit_c", None, V, u32, V, u32, V, u32, V, i, i, i)
+        self.h_hb = _fn(ref, "svt_aom_highbd_blend_a64_hmask_16bit_c", None, V, u32, V, u32, V, u32, V, i, i, i)
+
+    def run(self, inp):
+        """Blends in inp's own host buffers (dst and, for the difference-weighted kind, mask are written)."""
+        _, kind, w, h, bd, is16, subw, subh, mask_type = inp.case[:9]
+        cp = abi.ConvolveParams(round_0=inp.r0, round_1=inp.r1, is_compound=1)
+        io = (inp.dst.ptr, inp.dst.stride, inp.src0.ptr, inp.src0.stride, inp.src1.ptr, inp.src1.stride, inp.mask.ptr)
+        if kind in (abi.BLEND_D16, abi.BLEND_D16_DIFFWTD):
+            ms = inp.mask.stride
+            if kind == abi.BLEND_D16_DIFFWTD:
+                self.diffwtd_d16(inp.mask.ptr, mask_type, inp.src0.ptr, inp.src0.stride, inp.src1.ptr, inp.src1.stride, h, w, C.addressof(cp), bd)
+                ms = w
+            if is16:
+                self.d16_hb(*io, ms, w, h, subw, subh, C.addressof(cp), bd)
+            else:
+                self.d16_lb(*io, ms, w, h, subw, subh, C.addressof(cp))
+        elif kind == abi.BLEND_MASK:
+            self.mask_hb(*io, inp.mask.stride, w, h, subw, subh, bd) if is16 else self.mask_lb(*io, inp.mask.stride, w, h, subw, subh)
+        elif kind == abi.BLEND_VMASK:
+            self.v_hb(*io, w, h, bd) if is16 else self.v_lb(*io, w, h)
+        else:
+            self.h_hb(*io, w, h, bd) if is16 else self.h_lb(*io, w, h)
+
+
+def blend_record(name, inp):
+    """What the fixture keeps of a blended case: dst (and the mask a difference-weighted blend built), in full or as a digest."""
+    rec = {}
+    for key, buf in (("dst", inp.dst),) + ((("mask", inp.mask),) if inp.case[1] == abi.BLEND_D16_DIFFWTD else ()):
+        v = buf.view
+        rec[f"blend_{name}_{key}" + ("" if v.size <= FULL_LIMIT else "_sha256")] = v.copy() if v.size <= FULL_LIMIT else np.array(digest(v))
+    return rec
+
+
+def check_record(gold, rec, what):
+    for k, v in rec.items():
+        if k.endswith("_sha256"):
+            assert str(gold[k]) == str(v), (what, k, "golden digest")
+        else:
+            assert gold[k].dtype == v.dtype and np.array_equal(gold[k], v), (what, k, "golden")
+
+
+# ---- search cases -----------------------------------------------------------------------------------------------------------
+RESULT_DTYPE = np.dtype(abi.MASK_SEARCH_RESULT_DTYPE)
+NO_WEDGE_SIZES = [(64, 64), (128, 128), (64, 128), (16, 64), (128, 64), (8, 64)]
+
+
+# (name, w, h, bit depth, is_16bit, input kind, wedge search, layout index)
+def _search_cases():
+    cases, sizes = [], list(WEDGE_BSIZE)
+    for k in range(60):   # pred0 close to the source on one side of a line and far off on the other, pred1 the opposite
+        w, h = sizes[k % 9]
+        bd, is16 = FORMATS[(k // 9) % 3]
+        cases.append((f"line_{w}x{h}_bd{bd}_{is16}_{k}", w, h, bd, is16, "line", 1, k))
+    for k, (w, h) in enumerate(sizes):
+        bd, is16 = FORMATS[k % 3]
+        cases.append((f"flat_{w}x{h}_bd{bd}_{is16}", w, h, bd, is16, "flat", 1, k + 1))
+        cases.append((f"noise_{w}x{h}_bd{bd}_{is16}", w, h, bd, is16, "noise", 1, k + 2))
+    for k, (w, h) in enumerate([(8, 8), (16, 32), (32, 32), (32, 8)]):   # source and predictions at opposite ends of the range
+        cases.append((f"extreme_{w}x{h}_bd10", w, h, 10, 1, "extreme", 1, k))
+        cases.append((f"extreme_{w}x{h}_bd8", w, h, 8, k & 1, "extreme", 1, k + 3))
+    for k, (w, h) in enumerate(NO_WEDGE_SIZES):    # sizes without wedges: the difference-weighted part alone
+        bd, is16 = FORMATS[k % 3]
+        cases.append((f"nowedge_{w}x{h}_bd{bd}_{is16}", w, h, bd, is16, "line" if k % 2 else "noise", 0, k))
+    cases.append(("nowedge_16x16_bd8_0", 16, 16, 8, 0, "line", 0, 1))      # a wedge size searched without wedges
+    cases.append(("extreme_128x128_bd10", 128, 128, 10, 1, "extreme", 0, 3))
+    return cases
+
+
+SEARCH_CASES = _search_cases()
+
+
+def search_blocks(rng, w, h, bd, kind):
+    """(src, pred0, pred1) sample blocks of one search case."""
+    top, scale = (1 << bd) - 1, 1 << (bd - 8)
+    yy, xx = np.mgrid[0:h, 0:w]
+    if kind == "extreme":
+        src = np.where(rng.random((h, w)) < 0.9, top - rng.integers(0, 4 * scale, (h, w)), rng.integers(0, top + 1, (h, w)))
+        side = xx * int(rng.integers(1, 4)) > yy * int(rng.integers(1, 4))
+        p0 = np.where(side, rng.integers(0, 4 * scale, (h, w)), src)
+        p1 = np.where(side, top - rng.integers(0, 9 * scale, (h, w)), rng.integers(0, 40 * scale, (h, w)))
+    else:
+        src = (top + 1) * (0.5 + 0.3 * np.sin(xx / 6.0 + rng.uniform(0, 3)) * np.cos(yy / 5.0)) + rng.integers(-6 * scale, 6 * scale + 1, (h, w))
+        if kind == "flat":         # pred0 == pred1: every mask gives the same prediction, all SSEs tie
+            p0 = p1 = src + rng.integers(-9 * scale, 9 * scale + 1, (h, w))
+        elif kind == "noise":
+            p0 = src + rng.integers(-20 * scale, 20 * scale + 1, (h, w))
+            p1 = src + rng.integers(-20 * scale, 20 * scale + 1, (h, w))
+        else:
+            ang, off = rng.uniform(0, 2 * np.pi), rng.uniform(-0.3, 0.3)
+            side = (xx - (w - 1) / 2) * np.cos(ang) / w + (yy - (h - 1) / 2) * np.sin(ang) / h > off
+            near, far = rng.integers(-3 * scale, 3 * scale + 1, (2, h, w)), rng.integers(-200 * scale, 200 * scale + 1, (2, h, w))
+            p0 = src + np.where(side, near[0], far[0])
+            p1 = src + np.where(side, far[1], near[1])
+    return tuple(np.clip(np.rint(v), 0, top).astype(np.int64) for v in (src, p0, p1))
+
+
+class SearchInputs:
+    """Host buffers of one search case: src, pred0, pred1 as Buf, each with its own stride and row offset."""
+
+    def __init__(self, case, index):
+        name, w, h, bd, is16, kind, wedge, lay = case
+        rng = np.random.default_rng(7100 + index)
+        px = np.uint16 if is16 else np.uint8
+        self.case = case
+        self.src, self.pred0, self.pred1 = (Buf(b.astype(px), *LAYOUTS[(lay + j) % len(LAYOUTS)])
+                                            for j, b in enumerate(search_blocks(rng, w, h, bd, kind)))
+
+    def desc(self, masks_ptr, ptrs=None):
+        """abi.MaskSearchDesc; masks_ptr: {(w, h): address of that size's 32 masks}."""
+        _, w, h, bd, is16, _, wedge, _ = self.case
+        p = (lambda b: ptrs[id(b)] + b.byte_offset) if ptrs is not None else (lambda b: b.ptr)
+        return abi.MaskSearchDesc(p(self.src), p(self.pred0), p(self.pred1), masks_ptr[(w, h)] if wedge else None, self.src.stride,
+                                  self.pred0.stride, self.pred1.stride, w, h, bd, is16)
+
+    def buffers(self):
+        return [self.src, self.pred0, self.pred1]
+
+
+class RefSearch:
+    """The reference's compound mask search of one block through its own functions.  `tables` are the wedge masks (the fixture's, or
+    ref_tables(ref)); the counters of what the inputs exercise are taken from the reference's intermediates."""
+
+    def __init__(self, ref, tables):
+        V, i, u32, sz = C.c_void_p, C.c_int, C.c_uint32, C.c_ssize_t
+        self.tables = tables
+        self.sad8 = _fn(ref, "svt_nxm_sad_kernel_helper_c", u32, V, u32, V, u32, u32, u32)
+        self.sad16 = _fn(ref, "svt_aom_sad_16b_kernel_c", u32, V, u32, V, u32, u32, u32)
+        self.sub8 = _fn(ref, "svt_aom_subtract_block_c", None, i, i, V, sz, V, sz, V, sz)
+        self.sub16 = _fn(ref, "svt_aom_highbd_subtract_block_c", None, i, i, V, sz, V, sz, V, sz, i)
+        self.sumsq = _fn(ref, "svt_aom_sum_squares_i16_c", C.c_uint64, V, u32)
+        self.delta = _fn(ref, "svt_av1_wedge_compute_delta_squares_c", None, V, V, V, i)
+        self.sign = _fn(ref, "svt_av1_wedge_sign_from_residuals_c", C.c_int8, V, V, i, C.c_int64)
+        self.sse = _fn(ref, "svt_av1_wedge_sse_from_residuals_c", C.c_uint64, V, V, V, i)
+        self.dw8 = _fn(ref, "svt_av1_build_compound_diffwtd_mask_c", None, V, i, V, i, V, i, i, i)
+        self.dw16 = _fn(ref, "svt_av1_build_compound_diffwtd_mask_highbd_c", None, V, i, V, i, V, i, i, i, i)
+
+    def run(self, src, src_stride, pred0, pred1, w, h, bd, is16, wedge, counters=None):
+        """src: address of the source block (stride src_stride); pred0 / pred1: contiguous [h][w] arrays, as the reference keeps
+        them.  One result record."""
+        N = w * h
+        r = np.zeros((), RESULT_DTYPE)
+        p0, p1 = np.ascontiguousarray(pred0), np.ascontiguousarray(pred1)
+        P = lambda a: a.ctypes.data
+        res0, res1, d10, ds = (np.zeros(N, np.int16) for _ in range(4))
+        if is16:
+            r["pred0_to_pred1_dist"] = self.sad16(P(p0), w, P(p1), w, h, w)
+            self.sub16(h, w, P(res1), w, src, src_stride, P(p1), w, bd)
+            self.sub16(h, w, P(d10), w, P(p1), w, P(p0), w, bd)
+            self.sub16(h, w, P(res0), w, src, src_stride, P(p0), w, bd)
+        else:
+            r["pred0_to_pred1_dist"] = self.sad8(P(p0), w, P(p1), w, h, w)
+            self.sub8(h, w, P(res1), w, src, src_stride, P(p1), w)
+            self.sub8(h, w, P(d10), w, P(p1), w, P(p0), w)
+            self.sub8(h, w, P(res0), w, src, src_stride, P(p0), w)
+        used = []
+        r["best_wedge_index"] = -1
+        if wedge:
+            masks = self.tables[f"wedge_{w}x{h}"]
+            # C: (int64 - int64) * (1 << WEDGE_WEIGHT_BITS) / 2, a multiple of 64 halved: exact
+            limit = (int(self.sumsq(P(res0), N)) - int(self.sumsq(P(res1), N))) * 64 // 2
+            self.delta(P(ds), P(res0), P(res1), N)
+            best = None
+            for i in range(abi.WEDGE_TYPES):
+                s = int(self.sign(P(ds), P(masks[2 * i]), N, limit))
+                sse = int(self.sse(P(res1), P(d10), P(masks[2 * i + s]), N))
+                r["wedge_sign"][i], r["wedge_sse"][i] = s, sse
+                used.append(masks[2 * i + s])
+                if best is None or sse < best:
+                    best, r["best_wedge_index"], r["best_wedge_sign"] = sse, i, s
+        best = None
+        seg = np.zeros(N, np.uint8)
+        for t in (0, 1):
+            self.dw16(P(seg), t, P(p0), w, P(p1), w, h, w, bd) if is16 else self.dw8(P(seg), t, P(p0), w, P(p1), w, h, w)
+            sse = int(self.sse(P(res1), P(d10), P(seg), N))
+            r["diffwtd_sse"][t] = sse
+            used.append(seg.copy())
+            if best is None or sse < best:
+                best, r["best_diffwtd_type"] = sse, t
+        if counters is not None:
+            a, b = res0.astype(np.int64), res1.astype(np.int64)
+            if wedge:
+                assert np.array_equal(ds, np.clip(a * a - b * b, -32768, 32767))
+                counters["ds_saturated"] += int((np.abs(a * a - b * b) > 32767).sum())
+            t = np.stack([64 * b + m.astype(np.int64) * d10 for m in used])
+            counters["t_clamped"] += int(((t > 32767) | (t < -32768)).sum())
+        return r
+
+    def run_inputs(self, inp, counters=None):
+        _, w, h, bd, is16, _, wedge, _ = inp.case
+        return self.run(inp.src.ptr, inp.src.stride, inp.pred0.view, inp.pred1.view, w, h, bd, is16, wedge, counters)
+
+
+# ---- the whole-picture search case ----------------------------------------------------------------------------------------------
+PICTURE = (1920, 1080)
+
+
+def picture_planes():
+    """(src, pred0, pred1) 8-bit 1080p luma planes: two predictions that are each good in some regions and bad in others."""
+    w, h = PICTURE
+    rng = np.random.default_rng(4242)
+    yy, xx = np.mgrid[0:h, 0:w]
+    src = 128 + 70 * np.sin(xx / 23.0) * np.cos(yy / 17.0) + 30 * np.sin((xx + 2 * yy) / 7.0) + rng.integers(-5, 6, (h, w))
+    bad0 = np.sin(xx / 9.0 + yy / 13.0) > 0.2
+    bad1 = np.cos(xx / 11.0 - yy / 8.0) > 0.3
+    p0 = src + np.where(bad0, rng.integers(-90, 91, (h, w)), rng.integers(-3, 4, (h, w)))
+    p1 = src + np.where(bad1, rng.integers(-90, 91, (h, w)), rng.integers(-3, 4, (h, w)))
+    return tuple(np.clip(np.rint(v), 0, 255).astype(np.uint8) for v in (src, p0, p1))
+
+
+def picture_blocks(size=16):
+    w, h = PICTURE
+    return [(x, y) for y in range(0, h - size + 1, size) for x in range(0, w - size + 1, size)]
+
+
+def picture_oracle(orc, planes, size=16):
+    src, p0, p1 = planes
+    stride = src.shape[1]
+    out = np.zeros(len(picture_blocks(size)), RESULT_DTYPE)
+    for k, (x, y) in enumerate(picture_blocks(size)):
+        out[k] = orc.run(src.ctypes.data + y * stride + x, stride, p0[y:y + size, x:x + size], p1[y:y + size, x:x + size], size, size, 8, 0, 1)
+    return out
+
+
+# ---- the pipeline: two compound-1 predictions -> masked compound ----------------------------------------------------------------
+# (name, luma w, luma h, bit depth, is_16bit, compound type, wedge index, wedge sign, mask_type)
+PIPE_CASES = [(f"{'wedge' if t == COMPOUND_WEDGE else 'diffwtd'}_{w}x{h}_bd{bd}_{k}", w, h, bd, is16, t, (5 * k + 3) % 16, k & 1, (k >> 1) & 1)
+              for k, (w, h, (bd, is16), t) in enumerate((w, h, f, t) for f in ((8, 0), (10, 1)) for (w, h) in ((16, 16), (32, 16), (8, 8), (32, 32))
+                                                        for t in (COMPOUND_WEDGE, COMPOUND_DIFFWTD))]
+PIPE_TABLES = list(K.TABLES)
+
+
+class PipeInputs:
+    """Per plane (Y, U, V; 4:2:0): two reference planes, the block's position in them, sub-pel phases and kernel tables."""
+
+    def __init__(self, case, index):
+        name, w, h, bd, is16 = case[:5]
+        rng = np.random.default_rng(8800 + index)
+        self.case, self.planes = case, []
+        for plane in range(3):
+            pw, ph = (w, h) if plane == 0 else (w // 2, h // 2)
+            refs = [K.ref_plane(rng, pw, ph, bd, is16, (0, 2)[(index + j) % 2])[0] for j in range(2)]
+            if plane == 0:   # make the two predictions differ strongly in a part of the block: the difference-weighted mask varies
+                refs[1][8:8 + ph // 2] = ((1 << bd) - 1 - refs[1][8:8 + ph // 2].astype(np.int64)).astype(refs[1].dtype)
+            phases = [(int(rng.integers(1, 16)), int(rng.integers(1, 16)), int(rng.integers(0, 3))) for _ in range(2)]
+            self.planes.append((pw, ph, refs, phases))
+
+
+class InterInterCompoundData(C.Structure):     # definitions.h:1252-1264, packed enums
+    _fields_ = [("type", C.c_uint8), ("wedge_index", C.c_uint8), ("wedge_sign", C.c_uint8), ("mask_type", C.c_uint8)]
+
+
+class RefPipe:
+    def __init__(self, ref):
+        V, i, i32 = C.c_void_p, C.c_int, C.c_int32
+        self.jnt8 = _fn(ref, "svt_av1_jnt_convolve_2d_c", None, V, i32, V, i32, i32, i32, V, V, i32, i32, V)
+        self.jnt16 = _fn(ref, "svt_av1_highbd_jnt_convolve_2d_c", None, V, i32, V, i32, i32, i32, V, V, i32, i32, V, i32)
+        self.diffwtd_d16 = _fn(ref, "svt_av1_build_compound_diffwtd_mask_d16_c", None, V, i, V, i, V, i, i, i, V, i)
+        self.masked = _fn(ref, "svt_aom_build_masked_compound_no_round", None, V, i, V, i, V, i, V, V, i, i, i, V, C.c_uint8, C.c_uint8)
+        self.tabs = {n: K.kernel_table(n) for n in K.TABLES}
+        ref.svt_av1_init_wedge_masks()
+
+    def run(self, inp):
+        """{y, u, v: the compound prediction [h][w]; mask: the luma-sized difference-weighted mask, when one is built}"""
+        name, w, h, bd, is16, ctype, widx, wsign, mask_type = inp.case
+        r0, r1 = K.conv_rounds_compound(bd)
+        out, seg = {}, np.zeros(2 * 128 * 128, np.uint8)
+        comp = InterInterCompoundData(ctype, widx, wsign, mask_type)
+        for key, (pw, ph, refs, phases) in zip("yuv", inp.planes):
+            cb = [np.zeros((ph, pw), np.uint16) for _ in range(2)]
+            for j in range(2):
+                sx, sy, ti = phases[j]
+                tab = self.tabs[PIPE_TABLES[ti]][0]
+                fp = K.InterpFilterParams(tab.ctypes.data, 8, 16, ti)
+                cp = abi.ConvolveParams(do_average=0, dst=cb[j].ctypes.data, dst_stride=pw, round_0=r0, round_1=r1, is_compound=1)
+                at = refs[j].ctypes.data + (8 * refs[j].shape[1] + 8) * refs[j].itemsize
+                args = [at, refs[j].shape[1], None, 0, pw, ph, C.addressof(fp), C.addressof(fp), sx, sy, C.addressof(cp)]
+                self.jnt16(*args, bd) if is16 else self.jnt8(*args)
+            cp = abi.ConvolveParams(round_0=r0, round_1=r1, is_compound=1)
+            if key == "y" and ctype == COMPOUND_DIFFWTD:   # enc_inter_prediction.c:135-149, plane 0
+                self.diffwtd_d16(seg.ctypes.data, mask_type, cb[0].ctypes.data, pw, cb[1].ctypes.data, pw, ph, pw, C.addressof(cp), bd)
+                out["mask"] = seg[:w * h].reshape(h, w).copy()
+            dst = np.zeros((ph, pw), np.uint16 if is16 else np.uint8)
+            self.masked(dst.ctypes.data, pw, cb[0].ctypes.data, pw, cb[1].ctypes.data, pw, C.addressof(comp), seg.ctypes.data,
+                        WEDGE_BSIZE[(w, h)], ph, pw, C.addressof(cp), bd, is16)
+            out[key] = dst
+        return out
+
+
+def pipe_record(name, res):
+    return {f"pipe_{name}_{k}": v for k, v in res.items()}
+
+
+# ---- the fixture ------------------------------------------------------------------------------------------------------------
+def golden_entries(ref, log=None):
+    """Every entry of the fixture, computed by the reference."""
+    rec = dict(ref_tables(ref))
+    blend = RefBlend(ref)
+    for i, case in enumerate(BLEND_CASES):
+        inp = BlendInputs(case, i, rec)
+        blend.run(inp)
+        rec.update(blend_record(case[0], inp))
+    orc = RefSearch(ref, rec)
+    counters = {"ds_saturated": 0, "t_clamped": 0, "t_clamped_10bit": 0}
+    results = np.zeros(len(SEARCH_CASES), RESULT_DTYPE)
+    for i, case in enumerate(SEARCH_CASES):
+        before = counters["t_clamped"]
+        results[i] = orc.run_inputs(SearchInputs(case, i), counters)
+        if case[3] == 10:
+            counters["t_clamped_10bit"] += counters["t_clamped"] - before
+    rec["search_results"] = results
+    rec["search_counters"] = np.array([counters["ds_saturated"], counters["t_clamped"], counters["t_clamped_10bit"]], np.int64)
+    pic = picture_oracle(orc, picture_planes())
+    rec["picture_sha256"] = np.array(digest(pic))
+    rec["picture_best"] = np.stack([pic["best_wedge_index"], pic["best_wedge_sign"], pic["best_diffwtd_type"].astype(np.int8)])
+    pipe = RefPipe(ref)
+    for i, case in enumerate(PIPE_CASES):
+        rec.update(pipe_record(case[0], pipe.run(PipeInputs(case, i))))
+    if log:
+        log(f"search: {len(set(results['best_wedge_index'].tolist()))} best indices, signs {sorted(set(results['best_wedge_sign'].tolist()))}, "
+            f"diffwtd winners {sorted(set(results['best_diffwtd_type'].tolist()))}, counters {counters}")
+    return rec
+
+
+def main():
+    import pyorc
+    rec = golden_entries(pyorc.ref(), print)
+    np.savez_compressed(GOLD, **rec)
+    print("wrote", GOLD, os.path.getsize(GOLD), "bytes,", len(rec), "entries")
+
+
+if __name__ == "__main__":  # PYTHONPATH=oracle:svt-av1-mod-by-patman_amd python tests/blend_cases.py
+    main()
