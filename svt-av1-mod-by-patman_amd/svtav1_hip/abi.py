@@ -1,10 +1,12 @@
-"""ctypes mirror of include/svt_hip.h and include/svt_hip_me.h (the C-ABI of libsvtav1_hip).
+"""ctypes mirror of include/*.h (the C-ABI of libsvtav1_hip): the structs here, the function prototypes in prototypes.py.
 
 This module only describes the binary interface; it contains no compute and no CPU fallback.
 `load()` raises if the HIP library has not been built (product path must fail loudly).
 """
 import ctypes as C
 import os
+
+from .prototypes import PROTOTYPES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_ROOT = os.path.dirname(_HERE)
@@ -139,19 +141,11 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(the HIP path has no CPU fallback)")
-        _lib = C.CDLL(LIB_PATH)
-        _lib.svt_hip_last_error.restype = C.c_char_p
-        _lib.svt_hip_version.restype = C.c_char_p
-        _lib.svt_nxm_sad_kernel_hip.restype = C.c_uint32
-        for n in ("svt_compute_sub_mean_8x8_hip", "svt_compute_mean_8x8_hip",
-                  "svt_compute_mean_square_values_8x8_hip"):
-            getattr(_lib, n).restype = C.c_uint64
-        _lib.svt_hip_intra_search_frames.restype = C.c_int32
-        _lib.svt_hip_intra_search_frames.argtypes = [C.POINTER(IntraSearchJob), C.c_uint32, C.c_void_p]
-        _lib.svt_hip_blend_batch.restype = C.c_int32
-        _lib.svt_hip_blend_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-        _lib.svt_hip_compound_mask_search_batch.restype = C.c_int32
-        _lib.svt_hip_compound_mask_search_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib = C.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in PROTOTYPES.items():   # every function of include/*.h; one the library lacks fails here
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype and getattr(C, restype), [getattr(C, t) for t in argtypes]
+        _lib = lib
     return _lib
 
 

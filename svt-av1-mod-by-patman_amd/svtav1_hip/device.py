@@ -168,3 +168,78 @@ def compound_mask_search_batch(lib, descs, stream=None, fill=0xA5):
     check(lib, lib.svt_hip_compound_mask_search_batch(C.c_void_p(d_desc.ptr), C.c_void_p(d_res.ptr), C.c_uint32(len(descs)),
                                                       C.c_void_p(stream)), "svt_hip_compound_mask_search_batch")
     return d_res.download(np.dtype(abi.MASK_SEARCH_RESULT_DTYPE), (len(descs),), stream)
+
+
+class DeviceMap:
+    """Uploads host arrays on first use and hands out their device addresses (keyed by the host address)."""
+
+    def __init__(self, lib):
+        self.lib, self.m = lib, {}
+
+    def __call__(self, arr):
+        key = arr.ctypes.data
+        if key not in self.m:
+            b = DeviceBuffer(self.lib, arr.nbytes)
+            b.upload(arr)
+            self.m[key] = (b, arr)
+        return self.m[key][0].ptr
+
+    def download(self, arr):
+        b, a = self.m[arr.ctypes.data]
+        return b.download(a.dtype, a.shape)
+
+
+def tpl_workspace(lib, job):
+    """A workspace of the size svt_hip_tpl_dispenser_frame needs for the picture of `job` (an abi.TplFrameJob)."""
+    return DeviceBuffer(lib, lib.svt_hip_tpl_workspace_bytes(job.src.width, job.src.height))
+
+
+def tpl_dispenser_frame(lib, job, workspace=None, stream=None, sync=True):
+    """svt_hip_tpl_dispenser_frame on one abi.TplFrameJob with the caller's workspace or a new one; returns the workspace."""
+    if workspace is None:
+        workspace = tpl_workspace(lib, job)
+    job.workspace, job.workspace_bytes = workspace.ptr, workspace.nbytes
+    check(lib, lib.svt_hip_tpl_dispenser_frame(C.byref(job), stream), "svt_hip_tpl_dispenser_frame")
+    if sync:
+        check(lib, lib.svt_hip_stream_sync(stream), "svt_hip_stream_sync")
+    return workspace
+
+
+def tpl_status(lib, job, workspace):
+    """The status word a finished svt_hip_tpl_dispenser_frame left in its workspace: 0 unless a dependency wait ran into its bound."""
+    off = lib.svt_hip_tpl_status_offset(job.src.width, job.src.height)
+    return int(workspace.download(np.uint8, (workspace.nbytes,))[off:off + 4].view(np.uint32)[0])
+
+
+def tf_workspace(lib, job):
+    """A workspace of the size svt_hip_tf_filter_picture needs for the window of `job` (an abi.TfPictureJob)."""
+    full = job.centre.pyr.full
+    return DeviceBuffer(lib, lib.svt_hip_tf_workspace_bytes(full.width, full.height, job.n_refs))
+
+
+def tf_filter_picture(lib, job, workspace=None, tot_blks=None, stream=None, sync=True):
+    """svt_hip_tf_filter_picture on one abi.TfPictureJob with the caller's workspace and counters (8 bytes, zeroed) or new ones;
+    returns (workspace, tot_blks)."""
+    if workspace is None:
+        workspace = tf_workspace(lib, job)
+    if tot_blks is None:
+        tot_blks = DeviceBuffer(lib, 8)
+        tot_blks.fill(0, stream)
+    job.workspace, job.workspace_bytes, job.tot_blks = workspace.ptr, workspace.nbytes, tot_blks.ptr
+    check(lib, lib.svt_hip_tf_filter_picture(C.byref(job), stream), "svt_hip_tf_filter_picture")
+    if sync:
+        check(lib, lib.svt_hip_stream_sync(stream), "svt_hip_stream_sync")
+    return workspace, tot_blks
+
+
+def tf_read_back(lib, job, workspace, tot_blks):
+    """What a finished svt_hip_tf_filter_picture left behind: the abi.TfB64State of every (reference, b64) as the rows of a uint8 array,
+    and the two tot_blks counters."""
+    full = job.centre.pyr.full
+    nb = frames.b64_count(full.width, full.height)
+    raw = workspace.download(np.uint8, (workspace.nbytes,))
+    states = []
+    for r in range(job.n_refs):
+        off = lib.svt_hip_tf_workspace_state_offset(full.width, full.height, job.n_refs, r)
+        states.append(raw[off:off + nb * C.sizeof(abi.TfB64State)].reshape(nb, -1))
+    return np.concatenate(states), tuple(int(x) for x in tot_blks.download(np.uint32, (2,)))

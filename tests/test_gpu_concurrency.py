@@ -28,10 +28,6 @@ import tx_cases as T
 from lf_cases import BS, HB, VB
 from svtav1_hip import abi, device, frames
 from test_gpu_lf import deblock_inputs
-from test_gpu_tf_picture import GOLD as TF_GOLD
-from test_gpu_tf_picture import DevWindow
-from test_gpu_tpl import GOLD as TPL_GOLD
-from test_gpu_tpl import DevMap
 from test_gpu_txfm import hip_inverse
 from test_leaves_oracle import orc_residual, orc_sse
 
@@ -47,17 +43,6 @@ def P(a):
 
 def enc16(addr):
     return V(addr >> 1)      # CONVERT_TO_BYTEPTR, as the reference's callers pass uint16 buffers
-
-
-@pytest.fixture(scope="module")
-def lib(hip):
-    """The shared CDLL with every return type this module relies on set once, before any thread starts."""
-    for n in ("svt_hip_tf_workspace_bytes", "svt_hip_tf_workspace_state_offset", "svt_hip_tpl_workspace_bytes", "svt_hip_tpl_status_offset",
-              "svt_spatial_full_distortion_kernel_hip", "svt_full_distortion_kernel16_bits_hip"):
-        getattr(hip, n).restype = C.c_uint64
-    hip.svt_hip_sgr_search_work_bytes.restype = C.c_size_t
-    hip.svt_hip_last_error.restype = C.c_char_p
-    return hip
 
 
 @pytest.fixture(scope="module")
@@ -213,34 +198,28 @@ class TfCase:
         self.hip, self.case = hip, case
         name, kind, w, h, n_refs, bd, key, ctl = case
         if decay is None:
-            decay = tuple(int(x) for x in np.load(TF_GOLD)[f"{name}_decay"])
+            decay = tuple(int(x) for x in np.load(tpc.GOLD)[f"{name}_decay"])
         pics = tpc.case_window(orc, case)
         ostates, self.otot = tpc.run_oracle(orc, pics, case, decay)
         self.want, self.want_states = pics[0].arrays(), tpc.states_to_array(ostates)
-        self.dev = DevWindow(hip, tpc.case_window(orc, case))
+        self.dev = tpc.DevWindow(hip, tpc.case_window(orc, case))
         self.job = tpc.make_job(self.dev.pics, w, h, bd, key, ctl, decay, self.dev.ptrs)
         need = hip.svt_hip_tf_workspace_bytes(w, h, n_refs)
-        self.ws = ws if ws is not None else device.DeviceBuffer(hip, need)
+        self.ws = ws if ws is not None else device.tf_workspace(hip, self.job)
         assert self.ws.nbytes >= need
         self.tot = device.DeviceBuffer(hip, 8)
         self.tot.fill(0)
-        self.job.workspace, self.job.workspace_bytes, self.job.tot_blks = self.ws.ptr, self.ws.nbytes, self.tot.ptr
         settle(hip)
 
     def issue(self, stream):
-        device.check(self.hip, self.hip.svt_hip_tf_filter_picture(C.byref(self.job), V(stream)), "svt_hip_tf_filter_picture")
+        device.tf_filter_picture(self.hip, self.job, self.ws, self.tot, stream, sync=False)
 
     def check(self, what=""):
-        name, kind, w, h, n_refs = self.case[:5]
-        nb = frames.b64_count(w, h)
-        raw = self.ws.download(np.uint8, (self.ws.nbytes,))
-        states = []
-        for r in range(n_refs):
-            off = self.hip.svt_hip_tf_workspace_state_offset(w, h, n_refs, r)
-            states.append(raw[off:off + nb * C.sizeof(abi.TfB64State)].reshape(nb, -1))
-        bad = np.argwhere((np.concatenate(states) != self.want_states).any(axis=1))
+        name = self.case[0]
+        states, tot = device.tf_read_back(self.hip, self.job, self.ws, self.tot)
+        bad = np.argwhere((states != self.want_states).any(axis=1))
         assert len(bad) == 0, (what, name, "refinement state of (ref, b64) entries", bad[:8].ravel().tolist())
-        assert tuple(int(x) for x in self.tot.download(np.uint32, (2,))) == self.otot, (what, name, "tot")
+        assert tot == self.otot, (what, name, "tot")
         got = self.dev.centre_arrays()
         for k, v in self.want.items():
             assert np.array_equal(got[k], v), (what, name, k, int((got[k] != v).sum()))
@@ -249,27 +228,23 @@ class TfCase:
 class TplCase:
     def __init__(self, hip, orc, case):
         self.hip, self.case = hip, case
-        TP.load_quant(np.load(TPL_GOLD))
+        TP.load_quant(np.load(TP.GOLD))
         a, b = TP.TplScene(orc, case), TP.TplScene(orc, case)
         if case[5]["src_data_ready"]:
             TP.prime_second_pass(orc, a), TP.prime_second_pass(orc, b)
         assert orc.orc_tpl_dispenser_frame(C.byref(b.job())) == 0
         self.want, self.scene = b.results(), a
-        self.dm = DevMap(hip)
+        self.dm = device.DeviceMap(hip)
         self.job = a.job(self.dm)
-        w, h = case[2], case[3]
-        self.wsb, self.status_off = hip.svt_hip_tpl_workspace_bytes(w, h), hip.svt_hip_tpl_status_offset(w, h)
-        self.ws = device.DeviceBuffer(hip, self.wsb)
+        self.ws = device.tpl_workspace(hip, self.job)
         self.ws.fill(0xCD)
-        self.job.workspace, self.job.workspace_bytes = self.ws.ptr, self.wsb
         settle(hip)
 
     def issue(self, stream):
-        device.check(self.hip, self.hip.svt_hip_tpl_dispenser_frame(C.byref(self.job), V(stream)), "svt_hip_tpl_dispenser_frame")
+        device.tpl_dispenser_frame(self.hip, self.job, self.ws, stream, sync=False)
 
     def check(self, what=""):
-        status = self.ws.download(np.uint8, (self.wsb,))[self.status_off:self.status_off + 4].view(np.uint32)[0]
-        assert status == 0, (what, self.case[0], "a dependency wait ran into its bound")
+        assert device.tpl_status(self.hip, self.job, self.ws) == 0, (what, self.case[0], "a dependency wait ran into its bound")
         got = {"recon": self.dm.download(self.scene.out.buf), "stats": self.dm.download(self.scene.stats).view(np.uint8),
                "src_stats": self.dm.download(self.scene.src_stats).view(np.uint8)}
         for k, v in self.want.items():
@@ -370,41 +345,41 @@ TWO_STREAM_FAMILIES = {
 
 
 @pytest.mark.parametrize("family", list(TWO_STREAM_FAMILIES))
-def test_two_streams_one_thread(lib, orc, gold_intra, family):
+def test_two_streams_one_thread(hip, orc, gold_intra, family):
     """A long call A on s1, right behind it a different call B on s2, no synchronisation in between; both match."""
     make_a, make_b = TWO_STREAM_FAMILIES[family]
-    a, b = make_a(lib, orc, gold_intra), make_b(lib, orc, gold_intra)
-    s1, s2 = new_stream(lib), new_stream(lib)
+    a, b = make_a(hip, orc, gold_intra), make_b(hip, orc, gold_intra)
+    s1, s2 = new_stream(hip), new_stream(hip)
     try:
         keep = [a.issue(s1), b.issue(s2)]
-        sync(lib, s1, s2)
+        sync(hip, s1, s2)
         del keep
         a.check(f"{family} A on s1")
         b.check(f"{family} B on s2")
     finally:
-        destroy(lib, s1, s2)
+        destroy(hip, s1, s2)
 
 
 # ------------------------------------------------------------------------------------------------ 1b: more calls than staging slots
-def test_more_calls_in_flight_than_staging_slots(lib, orc, gold_intra):
+def test_more_calls_in_flight_than_staging_slots(hip, orc, gold_intra):
     """6 calls each of me_frames, intra_search_frames and wiener_stats from one thread, each on its own stream, no synchronisation,
     every host descriptor array overwritten with 0xFF right after its call: 18 calls through a ring of 4 staging slots."""
     keys = ["m8_360p_tl2", "m4_360p_tl2", "m12_360p_tl2", "m8_360p_tl0", "m6_360p_tl2", "m10_360p_tl2"]
     cases = []
     for i, key in enumerate(keys):
-        cases.append(MeCase(lib, orc, ("pan", "blocks", "noise")[i % 3], 320, 200, key, 80 + i))
-        cases.append(IntraCase(lib, gold_intra, I.CASES[i]))
-        cases.append(WienerCase(lib, orc, 200 + 24 * i, 136, (8, 10)[i % 2], i % 2, (7, 5)[i % 2], 64, 90 + i))
-    streams = [new_stream(lib) for _ in cases]
+        cases.append(MeCase(hip, orc, ("pan", "blocks", "noise")[i % 3], 320, 200, key, 80 + i))
+        cases.append(IntraCase(hip, gold_intra, I.CASES[i]))
+        cases.append(WienerCase(hip, orc, 200 + 24 * i, 136, (8, 10)[i % 2], i % 2, (7, 5)[i % 2], 64, 90 + i))
+    streams = [new_stream(hip) for _ in cases]
     try:
         for c, s in zip(cases, streams):
             arr = c.issue(s)
             C.memset(arr, 0xFF, C.sizeof(arr))          # the caller's array is dead the moment the call returns
-        sync(lib, *streams)
+        sync(hip, *streams)
         for k, c in enumerate(cases):
             c.check(f"call {k}")
     finally:
-        destroy(lib, *streams)
+        destroy(hip, *streams)
 
 
 # ------------------------------------------------------------------------------------------------ 1c: many host threads, Tier A
@@ -598,10 +573,10 @@ def run_threads(n, target):
     return failures
 
 
-def test_many_threads_tier_a(lib, orc):
+def test_many_threads_tier_a(hip, orc):
     """24 host threads (the 8 pooled streams are shared) call a mix of Tier A leaves at once, each on its own seeded inputs."""
-    assert lib.svt_hip_debug_tier_a_broken(0) == 0
-    work = [tier_a_items(lib, orc, t) for t in range(N_THREADS)]
+    assert hip.svt_hip_debug_tier_a_broken(0) == 0
+    work = [tier_a_items(hip, orc, t) for t in range(N_THREADS)]
     kinds = {name.split()[0] for items in work for name, _, _ in items}
     assert kinds >= {"sad_loop", "nxm_sad", "ext_sad", "fwd_txfm", "inv_txfm", "quantize_b", "highbd_quantize_fp", "cdef_find_dir",
                      "cdef_filter_block", "lpf_vertical_8", "compute_stats", "wiener_convolve_add_src", "convolve_2d_sr", "residual", "sse"}
@@ -614,39 +589,39 @@ def test_many_threads_tier_a(lib, orc):
     failures = run_threads(N_THREADS, worker)
     bad = [f for fs in failures for f in fs]
     assert not bad, bad[:10]
-    assert lib.svt_hip_debug_tier_a_broken(0) == 0
+    assert hip.svt_hip_debug_tier_a_broken(0) == 0
 
 
 # ------------------------------------------------------------------------------------------------ 1d: many host threads, Tier B
-def test_many_threads_tier_b(lib, orc, gold_intra):
+def test_many_threads_tier_b(hip, orc, gold_intra):
     """24 host threads each run intra_search_frames, me_frames and wiener_stats on their own inputs, half of them on the shared pool
     (stream = NULL), half on a stream of their own.  One more thread makes a refused call: its message stays its own."""
     keys = ["m8_360p_tl2", "m4_360p_tl2", "m12_360p_tl2", "m6_360p_tl2"]
     work = []
     for t in range(N_THREADS):
-        work.append((IntraCase(lib, gold_intra, I.CASES[t % len(I.CASES)]),
-                     MeCase(lib, orc, ("pan", "blocks", "noise")[t % 3], 200, 136, keys[t % 4], 300 + t),
-                     WienerCase(lib, orc, 136 + 8 * t, 72, (8, 10)[t % 2], t % 2, (7, 5)[t % 2], 64, 400 + t)))
-    own = [new_stream(lib) if t % 2 else None for t in range(N_THREADS)]
+        work.append((IntraCase(hip, gold_intra, I.CASES[t % len(I.CASES)]),
+                     MeCase(hip, orc, ("pan", "blocks", "noise")[t % 3], 200, 136, keys[t % 4], 300 + t),
+                     WienerCase(hip, orc, 136 + 8 * t, 72, (8, 10)[t % 2], t % 2, (7, 5)[t % 2], 64, 400 + t)))
+    own = [new_stream(hip) if t % 2 else None for t in range(N_THREADS)]
     marker = b"ctrls out of range"
     refused, refusal = threading.Event(), []
 
     def refuse():
         job = abi.IntraSearchJob()
         job.ctrls.intra_mode_end = abi.INTRA_MODES      # one past the last mode
-        rc = lib.svt_hip_intra_search_frames((abi.IntraSearchJob * 1)(job), C.c_uint32(1), None)
-        refusal.append((rc, lib.svt_hip_last_error()))
+        rc = hip.svt_hip_intra_search_frames((abi.IntraSearchJob * 1)(job), C.c_uint32(1), None)
+        refusal.append((rc, hip.svt_hip_last_error()))
         refused.set()
 
     def worker(t, fail):
         for c in work[t]:
             c.issue(own[t])
-        sync(lib, own[t])
+        sync(hip, own[t])
         for c in work[t]:
             c.check(f"thread {t}")
         if not refused.wait(timeout=60):
             fail.append("the refusing thread did not run")
-        msg = lib.svt_hip_last_error()
+        msg = hip.svt_hip_last_error()
         if marker in msg:
             fail.append(f"thread {t} sees another thread's error: {msg!r}")
     refuser = threading.Thread(target=refuse, daemon=True)
@@ -655,32 +630,32 @@ def test_many_threads_tier_b(lib, orc, gold_intra):
         failures = run_threads(N_THREADS, worker)
         refuser.join(timeout=60)
     finally:
-        destroy(lib, *[s for s in own if s])
+        destroy(hip, *[s for s in own if s])
     assert refusal and refusal[0][0] == abi.SVT_HIP_ERR_BAD_PARAMETER and marker in refusal[0][1], refusal
     bad = [f for fs in failures for f in fs]
     assert not bad, bad[:10]
 
 
 # ------------------------------------------------------------------------------------------------ 1e: one workspace, many jobs
-def test_tf_workspace_reuse(lib, orc):
+def test_tf_workspace_reuse(hip, orc):
     """One workspace sized for the largest job: a larger picture with 4 references, then a smaller one with 2, then 8x8 prediction.
     Each job must match the oracle, whatever an earlier job left in the workspace."""
     big = ("pan_4refs_8bit", "pan", 256, 192, 4, 8, "m8_360p_tl0", tpc.LVL6)
     cases = [(big, (2247286, 6156426, 6156426)), (tf_case("pan_lvl6_8bit"), None), (tf_case("blocks_lvl1_8x8_8bit"), None),
              (tf_case("pan_lvl6_10bit"), None)]
-    ws = device.DeviceBuffer(lib, max(lib.svt_hip_tf_workspace_bytes(c[2], c[3], c[4]) for c, _ in cases))
+    ws = device.DeviceBuffer(hip, max(hip.svt_hip_tf_workspace_bytes(c[2], c[3], c[4]) for c, _ in cases))
     for case, decay in cases:
-        tc = TfCase(lib, orc, case, decay, ws=ws)
+        tc = TfCase(hip, orc, case, decay, ws=ws)
         tc.issue(None)
-        sync(lib, None)
+        sync(hip, None)
         tc.check(f"shared workspace, {case[0]}")
 
 
-def test_sgr_search_work_reuse(lib, orc):
+def test_sgr_search_work_reuse(hip, orc):
     """svt_hip_sgr_search_unit: one d_work buffer across units of different size and ep range."""
     units = [(328, 200, 8, 0, 64, (0, 16, 1, 1)), (96, 80, 10, 1, 64, (10, 16, 1, 0)), (200, 120, 8, 1, 32, (0, 8, 3, 1)),
              (56, 40, 8, 0, 32, (14, 16, 1, 1)), (256, 256, 10, 1, 64, (0, 16, 4, 1))]
-    work = device.DeviceBuffer(lib, max(lib.svt_hip_sgr_search_work_bytes(w, h, (s1 - s0 + inc - 1) // inc)
+    work = device.DeviceBuffer(hip, max(hip.svt_hip_sgr_search_work_bytes(w, h, (s1 - s0 + inc - 1) // inc)
                                         for w, h, _, _, _, (s0, s1, inc, _) in units))
     orc.orc_sgr_search_unit.restype = C.c_int64
     for k, (w, h, bd, is16, pu, (s0, s1, inc, refine)) in enumerate(units):
@@ -688,12 +663,12 @@ def test_sgr_search_work_reuse(lib, orc):
         dat, src = G.sgr_plane(rng, w, h, bd, is16, k % 3)
         want = np.zeros(3, np.int32)
         e1 = orc.orc_sgr_search_unit(V(G.at(dat)), w, h, dat.shape[1], V(G.at(src)), src.shape[1], is16, bd, pu, pu, s0, s1, inc, refine, P(want))
-        d_dat, d_src = device.DeviceBuffer(lib, dat.nbytes), device.DeviceBuffer(lib, src.nbytes)
+        d_dat, d_src = device.DeviceBuffer(hip, dat.nbytes), device.DeviceBuffer(hip, src.nbytes)
         d_dat.upload(dat), d_src.upload(src)
         off = (G.B * dat.shape[1] + G.B) * dat.itemsize
         unit = abi.SgrUnit(d_dat.ptr + off, d_src.ptr + off, dat.shape[1], src.shape[1], w, h, is16, bd, pu, pu)
         got, e2 = np.zeros(3, np.int32), C.c_int64(0)
-        device.check(lib, lib.svt_hip_sgr_search_unit(C.byref(unit), s0, s1, inc, refine, V(work.ptr), P(got), C.byref(e2), None), "sgr_search")
+        device.check(hip, hip.svt_hip_sgr_search_unit(C.byref(unit), s0, s1, inc, refine, V(work.ptr), P(got), C.byref(e2), None), "sgr_search")
         assert np.array_equal(got, want) and e2.value == e1, (k, got, want, e2.value, e1)
 
 

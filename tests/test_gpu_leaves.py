@@ -10,15 +10,13 @@ import pytest
 import leaf_cases as L
 from svtav1_hip import abi
 from test_leaves_oracle import GOLD, U32, orc_inv8, orc_residual, orc_sse
-from tx_cases import P, V
+from tx_cases import P
 
 pytestmark = pytest.mark.gpu
 
 
 def test_sad_fill_residual_distortion(hip, orc):
     gold = np.load(GOLD)
-    hip.svt_aom_sad_16b_kernel_hip.restype = U32
-    hip.svt_nxm_sad_kernel_sub_sampled_hip.restype = U32
     orc.orc_sad_16b.restype = U32
     for i, (h, w, s, r) in enumerate(L.sad16_cases()):
         got = hip.svt_aom_sad_16b_kernel_hip(P(s), U32(s.shape[1]), P(r), U32(r.shape[1]), U32(h), U32(w))
@@ -39,8 +37,6 @@ def test_sad_fill_residual_distortion(hip, orc):
                                                                                       U32(rs), U32(w), U32(h))
         assert np.array_equal(out, orc_residual(orc, h, w, rs, a, b, hbd)), (h, w, hbd)
         assert np.array_equal(out[:, :w], gold[f"res{i}"])
-    hip.svt_spatial_full_distortion_kernel_hip.restype = C.c_uint64
-    hip.svt_full_distortion_kernel16_bits_hip.restype = C.c_uint64
     for i, (h, w, o0, o1, a, b, hbd) in enumerate(L.sse_cases()):
         fn = hip.svt_full_distortion_kernel16_bits_hip if hbd else hip.svt_spatial_full_distortion_kernel_hip
         got = fn(P(a), U32(o0), U32(a.shape[1]), P(b), C.c_int32(o1), U32(b.shape[1]), U32(w), U32(h))
@@ -49,19 +45,15 @@ def test_sad_fill_residual_distortion(hip, orc):
 
 def test_pme_sad_loop(hip, orc):
     gold = np.load(GOLD)["pme"]
-    fn = hip.svt_pme_sad_loop_kernel_hip
-    fn.restype, fn.argtypes = None, list(L.PME_ARGS)
     for i, c in enumerate(L.pme_cases()):
-        got = L.run_pme(fn, c)
+        got = L.run_pme(hip.svt_pme_sad_loop_kernel_hip, c)
         assert got == L.run_pme_orc(orc, c) == tuple(int(v) for v in gold[i]), (i, c.bw, c.bh, c.saw, c.sah, c.step, c.type)
 
 
 def test_search_one_dual(hip, orc):
     gold = np.load(GOLD)["dual"]
-    fn = hip.svt_search_one_dual_hip
-    fn.restype, fn.argtypes = C.c_uint64, [V, V, C.c_int, V, C.c_int, C.c_int, C.c_int]
     for i, case in enumerate(L.dual_cases()):
-        t0, a0, a1 = L.run_dual(fn, case)
+        t0, a0, a1 = L.run_dual(hip.svt_search_one_dual_hip, case)
         t1, b0, b1 = L.run_dual_orc(orc, case)
         assert t0 == t1 == int(gold[i][0]) and np.array_equal(a0, b0) and np.array_equal(a1, b1), case[2:]
         assert np.array_equal(np.concatenate([a0, a1]).astype(np.uint64), gold[i][1:])
@@ -84,7 +76,6 @@ def test_inv_txfm_add_8bit_entry(hip, orc):
 
 
 def test_rtcd_lookup_covers_the_new_leaves(hip):
-    hip.svt_hip_rtcd_lookup.restype, hip.svt_hip_rtcd_lookup.argtypes = C.c_void_p, [C.c_char_p]
     for name in ("svt_nxm_sad_kernel_sub_sampled", "sad_16b_kernel", "svt_initialize_buffer_32bits", "svt_pme_sad_loop_kernel", "downsample_2d",
                  "svt_residual_kernel8bit", "svt_residual_kernel16bit", "svt_spatial_full_distortion_kernel", "svt_full_distortion_kernel16_bits",
                  "svt_search_one_dual", "svt_av1_inv_txfm_add"):

@@ -61,8 +61,6 @@ def test_tier_a_filter_block(hip, orc):
 def test_tier_a_dist_and_copy(hip, orc):
     rng = np.random.default_rng(3)
     orc.orc_compute_cdef_dist.restype = C.c_uint64
-    hip.svt_compute_cdef_dist_16bit_hip.restype = C.c_uint64
-    hip.svt_compute_cdef_dist_8bit_hip.restype = C.c_uint64
     for trial in range(80):
         is16 = trial % 2
         bd = 10 if is16 and trial % 4 == 1 else 8

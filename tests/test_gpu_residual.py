@@ -28,7 +28,6 @@ def test_tier_a_subtract_and_satd(hip, orc):
         assert np.array_equal(d, orc_subtract(orc, rows, cols, ds, s, p, hbd)), (rows, cols, hbd)   # incl. untouched padding
         assert np.array_equal(d[:, :cols], gold[f"sub{i}"]), i
     rng = np.random.default_rng(3)
-    hip.svt_aom_satd_hip.restype = C.c_int
     orc.orc_satd.restype = C.c_int
     for n in (16, 64, 256, 1024, 100, 1):
         for mag in (5, 32640, 1 << 20):

@@ -50,7 +50,6 @@ def test_tier_a_projection(hip, orc, bd, is16):
     rng = np.random.default_rng(40 + bd)
     orc.orc_sgr_pixel_proj_error.restype = I64
     fn = hip.svt_av1_highbd_pixel_proj_error_hip if is16 else hip.svt_av1_lowbd_pixel_proj_error_hip
-    fn.restype = I64
     for trial in range(32):
         ep = trial % 16
         w, h = ((96, 80), (64, 64), (33, 47))[trial % 3]
@@ -90,7 +89,6 @@ def test_tier_b_search_filter_apply(hip, orc, case):
     orc.orc_sgr_search_unit.restype = I64
     e1 = orc.orc_sgr_search_unit(V(G.at(dat)), w, h, dat.shape[1], V(G.at(src)), src.shape[1], is16, bd, pu, pu, start, end, inc, refine, P(o1))
     unit, keep = gpu_unit(hip, dat, src, w, h, bd, is16, pu)
-    hip.svt_hip_sgr_search_work_bytes.restype = C.c_size_t
     n_ep = (end - start + inc - 1) // inc
     work = device.DeviceBuffer(hip, hip.svt_hip_sgr_search_work_bytes(w, h, n_ep))
     o2, e2 = np.zeros(3, np.int32), I64(0)
@@ -123,7 +121,6 @@ def test_tier_b_search_filter_apply(hip, orc, case):
 
 def test_tier_b_golden(hip):
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sgr.npz"))
-    hip.svt_hip_sgr_search_work_bytes.restype = C.c_size_t
     for key, w, h, bd, is16, kind, pu, (s0, s1, inc, refine), seed in G.GOLDEN_SGR:
         dat, src, best = g[key + "_dat"].copy(), g[key + "_src"].copy(), g[key + "_best"]
         unit, keep = gpu_unit(hip, dat, src, w, h, bd, is16, pu)

@@ -196,8 +196,6 @@ def test_noise_estimate(hip, orc):
     plane) against the oracle and the values the real reference produced (golden/tf_noise.npz) — bit-exact."""
     from test_tf_oracle import GOLD_NOISE, orc_noise
     gold = np.load(GOLD_NOISE)["noise"]
-    hip.svt_estimate_noise_fp16_hip.restype = C.c_int32
-    hip.svt_estimate_noise_highbd_fp16_hip.restype = C.c_int32
     rec = np.dtype([("sum", "<u8"), ("num", "<u8"), ("noise", "<i4"), ("pad", "<i4")])
     for i, (img, w, h, stride, bd) in enumerate(F.noise_cases()):
         exp = orc_noise(orc, img, w, h, stride, bd)

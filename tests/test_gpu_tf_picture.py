@@ -2,65 +2,23 @@
 normalise, all device-resident) against the oracle's restatement of produce_temporally_filtered_pic and against the golden
 pictures the reference itself produced, bit-exact: the filtered picture, the per-block refinement state and the counters."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import tf_picture_cases as tpc
-from svtav1_hip import abi, device, frames
+from svtav1_hip import abi, device
 
 pytestmark = pytest.mark.gpu
-V = C.c_void_p
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tf_picture.npz")
-
-
-class DevWindow:
-    """Device copies of every plane of a window + the pointer sets tf_picture_cases.make_job takes."""
-
-    def __init__(self, hip, pics):
-        self.hip, self.pics, self.ptrs, self.bufs = hip, pics, [], []
-        for p in pics:
-            pyr = device.DevicePyramid(hip, p.pyr)
-            c8 = [device.DevicePlane(hip, c) for c in p.c8]
-            hbd = []
-            if p.hbd is not None:
-                for a in p.hbd:
-                    b = device.DeviceBuffer(hip, a.nbytes)
-                    b.upload(a)
-                    hbd.append(b)
-            self.bufs.append((pyr, c8, hbd))
-            self.ptrs.append({"pyr": pyr.desc(), "c8": [c.buf.ptr for c in c8], "hbd": [b.ptr for b in hbd]})
-
-    def centre_arrays(self):
-        pyr, c8, hbd = self.bufs[0]
-        out = {"y8": pyr.full.download(), "cb8": c8[0].download(), "cr8": c8[1].download()}
-        if hbd:
-            for k, b, a in zip(("y16", "cb16", "cr16"), hbd, self.pics[0].hbd):
-                out[k] = b.download(np.uint16, a.shape)
-        return out
+GOLD = tpc.GOLD
 
 
 def run_gpu(hip, pics, case, decay):
     name, kind, w, h, n_refs, bd, key, ctl = case
-    dev = DevWindow(hip, pics)
+    dev = tpc.DevWindow(hip, pics)
     job = tpc.make_job(pics, w, h, bd, key, ctl, decay, dev.ptrs)
-    hip.svt_hip_tf_workspace_bytes.restype = C.c_uint64
-    hip.svt_hip_tf_workspace_state_offset.restype = C.c_uint64
-    wsb = hip.svt_hip_tf_workspace_bytes(w, h, n_refs)
-    ws = device.DeviceBuffer(hip, wsb)
-    tot = device.DeviceBuffer(hip, 8)
-    tot.fill(0)
-    job.workspace, job.workspace_bytes, job.tot_blks = ws.ptr, wsb, tot.ptr
-    device.check(hip, hip.svt_hip_tf_filter_picture(C.byref(job), None), "svt_hip_tf_filter_picture")
-    device.check(hip, hip.svt_hip_stream_sync(None), "sync")
-    nb = frames.b64_count(w, h)
-    raw = ws.download(np.uint8, (wsb,))
-    states = []
-    for r in range(n_refs):
-        off = hip.svt_hip_tf_workspace_state_offset(w, h, n_refs, r)
-        states.append(raw[off:off + nb * C.sizeof(abi.TfB64State)].reshape(nb, -1))
-    return dev.centre_arrays(), np.concatenate(states), tuple(int(x) for x in tot.download(np.uint32, (2,)))
+    states, tot = device.tf_read_back(hip, job, *device.tf_filter_picture(hip, job))
+    return dev.centre_arrays(), states, tot
 
 
 @pytest.mark.parametrize("case", tpc.CASES, ids=lambda c: c[0])
@@ -84,13 +42,11 @@ def test_argument_checks(hip, orc):
     case = tpc.CASES[0]
     name, kind, w, h, n_refs, bd, key, ctl = case
     pics = tpc.case_window(orc, case)
-    dev = DevWindow(hip, pics)
+    dev = tpc.DevWindow(hip, pics)
     job = tpc.make_job(pics, w, h, bd, key, ctl, (1, 1, 1), dev.ptrs)
     assert hip.svt_hip_tf_filter_picture(C.byref(job), None) == abi.SVT_HIP_ERR_BAD_PARAMETER  # no workspace
-    hip.svt_hip_tf_workspace_bytes.restype = C.c_uint64
-    wsb = hip.svt_hip_tf_workspace_bytes(w, h, n_refs)
-    ws = device.DeviceBuffer(hip, wsb)
-    job.workspace, job.workspace_bytes = ws.ptr, wsb
+    ws = device.tf_workspace(hip, job)
+    job.workspace, job.workspace_bytes = ws.ptr, ws.nbytes
     job.ctrls.enable_8x8_pred = 2   # a flag: 0 or 1
     assert hip.svt_hip_tf_filter_picture(C.byref(job), None) == abi.SVT_HIP_ERR_BAD_PARAMETER
     assert b"8x8" in hip.svt_hip_last_error()

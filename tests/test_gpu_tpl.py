@@ -2,7 +2,6 @@
 oracle's restatement of tpl_mc_flow_dispenser_sb_generic and the golden results of the reference, bit-exact: the TPL
 reconstruction picture, TplStats and TplSrcStats."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -11,7 +10,7 @@ import tpl_cases as T
 from svtav1_hip import abi, device
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tpl_frame.npz")
+GOLD = T.GOLD
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -19,40 +18,13 @@ def quant():
     T.load_quant(np.load(GOLD))
 
 
-class DevMap:
-    """Uploads host arrays on first use and hands out their device addresses (keyed by the host address)."""
-
-    def __init__(self, hip):
-        self.hip, self.m = hip, {}
-
-    def __call__(self, arr):
-        key = arr.ctypes.data
-        if key not in self.m:
-            b = device.DeviceBuffer(self.hip, arr.nbytes)
-            b.upload(arr)
-            self.m[key] = (b, arr)
-        return self.m[key][0].ptr
-
-    def download(self, arr):
-        b, a = self.m[arr.ctypes.data]
-        return b.download(a.dtype, a.shape)
-
-
 def run_gpu(hip, scene):
-    name, kind, w, h, qindex, opt = scene.case
-    dm = DevMap(hip)
+    dm = device.DeviceMap(hip)
     job = scene.job(dm)
-    hip.svt_hip_tpl_workspace_bytes.restype = C.c_uint64
-    hip.svt_hip_tpl_status_offset.restype = C.c_uint64
-    wsb = hip.svt_hip_tpl_workspace_bytes(w, h)
-    ws = device.DeviceBuffer(hip, wsb)
+    ws = device.tpl_workspace(hip, job)
     ws.fill(0xCD)
-    job.workspace, job.workspace_bytes = ws.ptr, wsb
-    device.check(hip, hip.svt_hip_tpl_dispenser_frame(C.byref(job), None), "svt_hip_tpl_dispenser_frame")
-    device.check(hip, hip.svt_hip_stream_sync(None), "sync")
-    off = hip.svt_hip_tpl_status_offset(w, h)
-    status = ws.download(np.uint8, (wsb,))[off:off + 4].view(np.uint32)[0]
-    assert status == 0, "a dependency wait ran into its bound"
+    device.tpl_dispenser_frame(hip, job, ws)
+    assert device.tpl_status(hip, job, ws) == 0, "a dependency wait ran into its bound"
     return {"recon": dm.download(scene.out.buf), "stats": dm.download(scene.stats).view(np.uint8),
             "src_stats": dm.download(scene.src_stats).view(np.uint8)}
 
@@ -148,14 +120,12 @@ def test_stale_line_pattern_4k(hip, orc, level, fence):
 
 def test_argument_checks(hip, orc):
     s = T.TplScene(orc, T.CASES[0])
-    dm = DevMap(hip)
+    dm = device.DeviceMap(hip)
     job = s.job(dm)
     assert hip.svt_hip_tpl_dispenser_frame(C.byref(job), None) == abi.SVT_HIP_ERR_BAD_PARAMETER  # no workspace
     assert b"workspace" in hip.svt_hip_last_error()
     assert hip.svt_hip_tpl_dispenser_frame(None, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
-    hip.svt_hip_tpl_workspace_bytes.restype = C.c_uint64
-    wsb = hip.svt_hip_tpl_workspace_bytes(s.case[2], s.case[3])
-    ws = device.DeviceBuffer(hip, wsb)
-    job.workspace, job.workspace_bytes, job.quarter_pel, job.blk_size, job.subsample_tx = ws.ptr, wsb, 1, 32, 2
+    ws = device.tpl_workspace(hip, job)
+    job.workspace, job.workspace_bytes, job.quarter_pel, job.blk_size, job.subsample_tx = ws.ptr, ws.nbytes, 1, 32, 2
     assert hip.svt_hip_tpl_dispenser_frame(C.byref(job), None) == abi.SVT_HIP_ERR_BAD_PARAMETER  # quarter-pel comes with 16x16 blocks only
     assert b"quarter_pel" in hip.svt_hip_last_error()

@@ -48,7 +48,6 @@ def test_tier_a_fwd_inv(hip, orc, w, h):
         orc.orc_handle_transform64.restype = C.c_uint64
         for suf, en in (("", 1), ("_N2_N4", 0)):
             fn = getattr(hip, f"svt_handle_transform{w}x{h}{suf}_hip")
-            fn.restype = C.c_uint64
             co = rng.integers(-100000, 100000, size=w * h).astype(np.int32)
             c2 = co.copy()
             e1 = orc.orc_handle_transform64(P(co), w, h) * en

@@ -1,37 +1,9 @@
-"""CPU: the ctypes mirrors of include/svt_hip_intra.h have the compiler's layout, and the golden fixture of the intra search is what
-the reference computes (when oracle/_ref/libsvtref.so is built)."""
-import ctypes as C
-import os
-import subprocess
-
+"""CPU: the golden fixture of the intra search is what the reference computes (when oracle/_ref/libsvtref.so is built) and reaches
+what it is meant to reach."""
 import numpy as np
 import pytest
 
 from svtav1_hip import abi
-
-
-def _c_layout(tmp_path, structs):
-    """{struct: (sizeof, {field: offsetof})} as gcc lays out the header."""
-    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "svt_hip_intra.h"', "int main(void) {"]
-    for s, fields in structs.items():
-        lines.append(f'    printf("{s} %zu\\n", sizeof({s}));')
-        for f in fields:
-            lines.append(f'    printf("{s}.{f} %zu\\n", offsetof({s}, {f}));')
-    lines.append("    return 0;\n}")
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-I", os.path.join(abi.REPO_ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    return dict(line.rsplit(" ", 1) for line in out.splitlines())
-
-
-def test_intra_structs_match_header(tmp_path):
-    mirrors = {"SvtHipIntraCtrls": abi.IntraCtrls, "SvtHipIntraSearchJob": abi.IntraSearchJob, "SvtHipPlane8": abi.Plane8}
-    got = _c_layout(tmp_path, {s: [f for f, _ in m._fields_] for s, m in mirrors.items()})
-    for s, m in mirrors.items():
-        assert int(got[s]) == C.sizeof(m), s
-        for f, _ in m._fields_:
-            assert int(got[f"{s}.{f}"]) == getattr(m, f).offset, (s, f)
 
 
 def test_intra_golden_matches_reference(ref):

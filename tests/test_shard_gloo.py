@@ -49,7 +49,6 @@ def worker(rank, world, port, q):
         seg = (C.c_uint32 * 4)()
         lib.svt_hip_shard_segment(N, world, rank, 2, 2, seg)
         assert tuple(seg) == (first, last, c0, c1)
-        lib.svt_hip_shard_owner.restype = C.c_uint32
         assert [lib.svt_hip_shard_owner(i, 32, world) for i in range(1, 33)] == [shard.layer_aware_owner(i, world) for i in range(1, 33)]
         local = shard.analyse_segment(lambda i: analyse(i, c0, c1), N, world, rank)
         assert sorted(local) == list(range(first, last))
@@ -85,7 +84,6 @@ def test_c_abi_assignment_matches_python():
     import ctypes as C
     from svtav1_hip import abi
     lib = abi.load()
-    lib.svt_hip_shard_layer.restype = lib.svt_hip_shard_owner.restype = C.c_uint32
     for mg in (8, 16, 32):
         assert [lib.svt_hip_shard_layer(i, mg) for i in range(1, mg + 1)] == [shard.layer_of(i, mg) for i in range(1, mg + 1)]
         for world in (1, 2, 3, 4, 8):
@@ -99,8 +97,6 @@ def test_c_abi_assignment_matches_python():
             if mg % world == 0:
                 assert [own.count(g) for g in range(world)] == [mg // world] * world
         # whole sequence: base-layer pictures (multiples of the mini-GOP size) alternate over the GPUs
-        lib.svt_hip_shard_owner_gop.restype = C.c_uint32
-        lib.svt_hip_shard_owner_gop.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
         for world in (2, 4, 8):
             seq = [lib.svt_hip_shard_owner_gop(n, mg, world) for n in range(0, 8 * mg + 1)]
             assert seq == [shard.owner_in_sequence(n, world, mg) for n in range(0, 8 * mg + 1)]

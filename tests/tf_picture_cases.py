@@ -1,12 +1,14 @@
 """Shared builders for the whole-picture temporal-filter tests (test infrastructure): windows of pictures with luma pyramids,
 4:2:0 chroma and optional 10-bit planes, and the SvtHipTfPictureJob around them."""
 import ctypes as C
+import os
 
 import numpy as np
 
 import me_cases
-from svtav1_hip import abi, frames
+from svtav1_hip import abi, device, frames
 
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tf_picture.npz")
 # (name, clip kind, width, height, refs, bit depth, ME parameter key, controls)
 # controls follow the reference's tf levels (enc_handle.c:2697-3300): level 6/8-like (bilinear, 8-bit sub-pel, h/v half-pel),
 # level 1-like without 8x8 (all rounds, eighth-pel, regular filters), sub-sampled distortion + 64x64-only decision, early exits.
@@ -189,3 +191,29 @@ def run_oracle(orc, pics, case, decay):
 
 def states_to_array(states):
     return np.frombuffer(bytes(states), dtype=np.uint8).reshape(len(states), C.sizeof(abi.TfB64State)).copy()
+
+
+class DevWindow:
+    """Device copies of every plane of a window + the pointer sets make_job takes."""
+
+    def __init__(self, hip, pics):
+        self.hip, self.pics, self.ptrs, self.bufs = hip, pics, [], []
+        for p in pics:
+            pyr = device.DevicePyramid(hip, p.pyr)
+            c8 = [device.DevicePlane(hip, c) for c in p.c8]
+            hbd = []
+            if p.hbd is not None:
+                for a in p.hbd:
+                    b = device.DeviceBuffer(hip, a.nbytes)
+                    b.upload(a)
+                    hbd.append(b)
+            self.bufs.append((pyr, c8, hbd))
+            self.ptrs.append({"pyr": pyr.desc(), "c8": [c.buf.ptr for c in c8], "hbd": [b.ptr for b in hbd]})
+
+    def centre_arrays(self):
+        pyr, c8, hbd = self.bufs[0]
+        out = {"y8": pyr.full.download(), "cb8": c8[0].download(), "cr8": c8[1].download()}
+        if hbd:
+            for k, b, a in zip(("y16", "cb16", "cr16"), hbd, self.pics[0].hbd):
+                out[k] = b.download(np.uint16, a.shape)
+        return out

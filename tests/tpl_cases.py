@@ -1,12 +1,14 @@
 """Shared builders for the TPL dispenser tests (test infrastructure): a picture with its open-loop ME results, reference
 pictures with separate 'reconstructions', and the SvtHipTplFrameJob around them."""
 import ctypes as C
+import os
 
 import numpy as np
 
 import me_cases
 from svtav1_hip import abi, frames
 
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tpl_frame.npz")
 # (name, clip kind, width, height, qindex, options)
 BASE = dict(pf_shape=2, disable_intra_pred=0, is_ref=1, i_slice=0, tpl_i_slice=0, src_data_ready=0, store_src_stats=1, synth_blk_size=16)
 L5 = dict(blk_size=32, subsample_tx=2)
