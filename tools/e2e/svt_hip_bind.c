@@ -58,6 +58,9 @@ static void *open_library(void) {
 
 static void *g_lib;
 static void *lib_sym(const char *name) { return g_lib ? dlsym(g_lib, name) : NULL; }
+HD_FN(svt_hip_init);
+HD_FN(svt_hip_install_rtcd);
+HD_FN(svt_hip_last_error);
 
 /* e2e build only (tools/e2e/svt_hip_bind_simd.c): the reference's x86 intrinsics ladder as an encoder-level CPU baseline */
 int svt_hip_bind_simd_install(void) __attribute__((weak));
@@ -72,22 +75,19 @@ int svt_hip_bind_install(char *msg, unsigned msg_len) {
             return n_simd;
         }
     }
-    void *h = open_library();
-    if (!h) {
+    g_lib = open_library();
+    if (!g_lib) {
         snprintf(msg, msg_len, "cannot load libsvtav1_hip.so: %s", dlerror());
         return -1;
     }
-    int32_t (*p_init)(int32_t)                                             = (int32_t(*)(int32_t))dlsym(h, "svt_hip_init");
-    int32_t (*p_install)(const SvtHipRtcdBinding *, uint32_t, uint32_t *) =
-        (int32_t(*)(const SvtHipRtcdBinding *, uint32_t, uint32_t *))dlsym(h, "svt_hip_install_rtcd");
-    const char *(*p_err)(void) = (const char *(*)(void))dlsym(h, "svt_hip_last_error");
-    if (!p_init || !p_install || !p_err) {
+    HD_SYM(lib_sym, svt_hip_init), HD_SYM(lib_sym, svt_hip_install_rtcd), HD_SYM(lib_sym, svt_hip_last_error);
+    if (!p_svt_hip_init || !p_svt_hip_install_rtcd || !p_svt_hip_last_error) {
         snprintf(msg, msg_len, "libsvtav1_hip.so lacks svt_hip_init / svt_hip_install_rtcd");
         return -1;
     }
     const char *dev = getenv("SVTAV1_HIP_DEVICE");
-    if (p_init(dev ? atoi(dev) : 0) != SVT_HIP_OK) {
-        snprintf(msg, msg_len, "%s", p_err());
+    if (p_svt_hip_init(dev ? atoi(dev) : 0) != SVT_HIP_OK) {
+        snprintf(msg, msg_len, "%s", p_svt_hip_last_error());
         return -1;
     }
     const char       *only = getenv("SVTAV1_HIP_ONLY"), *skip = getenv("SVTAV1_HIP_SKIP");
@@ -102,11 +102,10 @@ int svt_hip_bind_install(char *msg, unsigned msg_len) {
         sel[n++] = hip_bindings[i];
     }
     uint32_t done = 0;
-    if (n && p_install(sel, n, &done) != SVT_HIP_OK) { /* n == 0: SVTAV1_HIP_ONLY matched nothing — batched entry points only */
-        snprintf(msg, msg_len, "%s", p_err());
+    if (n && p_svt_hip_install_rtcd(sel, n, &done) != SVT_HIP_OK) { /* n == 0: SVTAV1_HIP_ONLY matched nothing — batched entry points only */
+        snprintf(msg, msg_len, "%s", p_svt_hip_last_error());
         return -1;
     }
-    g_lib = h;
     svt_hip_bind_dev_setup(lib_sym); /* device API, PCIe counters, device-resident picture mirrors shared by the hooks below */
     svt_hip_bind_me_setup(lib_sym); /* Step 2b: batched open-loop ME (SVTAV1_HIP_TIERB_ME=1) */
     svt_hip_bind_tf_setup(lib_sym); /* Step 6b: whole-picture temporal filter (SVTAV1_HIP_TIERB_TF=1) */

@@ -4,6 +4,7 @@
  * "first caller computes the picture" table.
  */
 #include <pthread.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -18,7 +19,7 @@ static unsigned long long g_up_bytes, g_down_bytes, g_hits, g_misses, g_hit_byte
 static unsigned long long g_pool_bytes, g_pool_allocs, g_pool_reuses;
 static size_t             g_budget = (size_t)6144 << 20, g_resident;
 static int                g_verify;
-static int32_t (*p_host_alloc)(void **, size_t);
+HD_FN(svt_hip_host_alloc);
 
 #include <time.h>
 typedef struct HdTimer {
@@ -62,14 +63,14 @@ static void report(void) {
 }
 
 void svt_hip_bind_dev_setup(void *(*sym)(const char *)) {
-    g_hd.malloc_    = (int32_t(*)(void **, size_t))sym("svt_hip_malloc");
-    g_hd.free_      = (int32_t(*)(void *))sym("svt_hip_free");
-    g_hd.upload     = (int32_t(*)(void *, const void *, size_t, void *))sym("svt_hip_upload");
-    g_hd.download   = (int32_t(*)(void *, const void *, size_t, void *))sym("svt_hip_download");
-    g_hd.memset_    = (int32_t(*)(void *, int32_t, size_t, void *))sym("svt_hip_memset");
-    g_hd.sync       = (int32_t(*)(void *))sym("svt_hip_stream_sync");
-    g_hd.last_error = (const char *(*)(void))sym("svt_hip_last_error");
-    p_host_alloc    = (int32_t(*)(void **, size_t))sym("svt_hip_host_alloc");
+    g_hd.malloc_    = HD_LOOKUP(sym, svt_hip_malloc);
+    g_hd.free_      = HD_LOOKUP(sym, svt_hip_free);
+    g_hd.upload     = HD_LOOKUP(sym, svt_hip_upload);
+    g_hd.download   = HD_LOOKUP(sym, svt_hip_download);
+    g_hd.memset_    = HD_LOOKUP(sym, svt_hip_memset);
+    g_hd.sync       = HD_LOOKUP(sym, svt_hip_stream_sync);
+    g_hd.last_error = HD_LOOKUP(sym, svt_hip_last_error);
+    HD_SYM(sym, svt_hip_host_alloc);
     g_hd.ok         = g_hd.malloc_ && g_hd.free_ && g_hd.upload && g_hd.download && g_hd.memset_ && g_hd.sync;
     const char *mb  = getenv("SVTAV1_HIP_MIRROR_MB");
     if (mb)
@@ -96,7 +97,9 @@ int hd_upload(void *d, const void *h, size_t n) {
     if (!st)
         return g_hd.upload(d, h, n, NULL);
     memcpy(st, h, n);
-    const int rc = g_hd.upload(d, st, n, NULL) | g_hd.sync(NULL);
+    int rc = g_hd.upload(d, st, n, NULL);
+    if (rc == 0) /* (a failed upload has queued nothing that reads the block) */
+        rc = g_hd.sync(NULL);
     hd_host_free(st);
     return rc;
 }
@@ -190,7 +193,7 @@ void *hd_host_alloc(size_t n) {
     HostBlk *b = (HostBlk *)calloc(1, sizeof(*b));
     if (!b)
         return NULL;
-    if (p_host_alloc && p_host_alloc(&b->p, want) == 0)
+    if (p_svt_hip_host_alloc && p_svt_hip_host_alloc(&b->p, want) == 0)
         b->pinned = 1;
     else
         b->p = malloc(want);
@@ -318,7 +321,9 @@ uint8_t *hd_mirror_get(const void *host, size_t bytes, uint64_t tag) {
         }
         g_misses++;
         pthread_mutex_unlock(&g_mu);
-        const int rc = hd_upload(m->dev, host, bytes) | hd_sync();
+        int rc = hd_upload(m->dev, host, bytes);
+        if (rc == 0)
+            rc = hd_sync();
         pthread_mutex_lock(&g_mu);
         m->loading = 0;
         pthread_cond_broadcast(&g_cv);
@@ -393,7 +398,7 @@ struct HdOnce {
     void          *payload;
 };
 
-HdOnce *hd_once_enter(HdOnceTable *t, const void *owner, uint64_t key, uint32_t total, int *first) {
+static HdOnce *once_enter(HdOnceTable *t, const void *owner, uint64_t key, uint32_t total, int *first) {
     pthread_mutex_lock(&g_mu);
     HdOnce *e = t->head;
     while (e && !(e->owner == owner && e->key == key)) e = e->next;
@@ -414,15 +419,13 @@ HdOnce *hd_once_enter(HdOnceTable *t, const void *owner, uint64_t key, uint32_t 
     pthread_mutex_unlock(&g_mu);
     return e;
 }
-void hd_once_done(HdOnce *e, int ok, void *payload) {
+static void once_done(HdOnce *e, int ok, void *payload) {
     pthread_mutex_lock(&g_mu);
     e->payload = payload, e->state = ok ? 2 : 3;
     pthread_cond_broadcast(&g_cv);
     pthread_mutex_unlock(&g_mu);
 }
-int   hd_once_ok(const HdOnce *e) { return e->state == 2; }
-void *hd_once_payload(const HdOnce *e) { return e->payload; }
-void  hd_once_release(HdOnceTable *t, HdOnce *e, void (*free_payload)(void *)) {
+static void once_release(HdOnceTable *t, HdOnce *e, void (*free_payload)(void *)) {
     pthread_mutex_lock(&g_mu);
     if (++e->seen >= e->total) {
         for (HdOnce **pp = &t->head; *pp; pp = &(*pp)->next)
@@ -437,4 +440,139 @@ void  hd_once_release(HdOnceTable *t, HdOnce *e, void (*free_payload)(void *)) {
         return;
     }
     pthread_mutex_unlock(&g_mu);
+}
+int hd_once_run(HdOnceTable *t, const void *owner, uint64_t key, uint32_t total, int (*compute)(void *arg, void **payload),
+                void (*take)(void *arg, const void *payload), void (*free_payload)(void *), void *arg) {
+    int     first;
+    HdOnce *e = once_enter(t, owner, key, total, &first);
+    if (!e)
+        return -1;
+    if (first) {
+        void     *payload = NULL;
+        const int ok      = compute(arg, &payload);
+        once_done(e, ok, payload);
+    }
+    const int ok = e->state == 2;
+    if (ok && take)
+        take(arg, e->payload);
+    once_release(t, e, free_payload);
+    return ok ? 0 : 1;
+}
+
+/* ---- one scope per hook call ---------------------------------------------------------------------------------------------- */
+enum { BLK_DEV, BLK_PINNED, BLK_HOST };
+
+void hd_call_begin(HdCall *c, const char *timer_name) {
+    c->timer = timer_name, c->t0 = hd_now_ns();
+    c->failed = c->used = c->n_pins = c->n_blocks = 0;
+}
+int  hd_call_ok(const HdCall *c) { return !c->failed; }
+void hd_call_fail(HdCall *c) { c->failed = 1; }
+int  hd_call_check(HdCall *c, int rc) {
+    c->used = 1;
+    if (rc != 0)
+        c->failed = 1;
+    return c->failed;
+}
+/* in front of every step: 1 = the scope has failed (or has no slot left), the step is not made */
+static int call_enter(HdCall *c, int n, int cap, const char *what) {
+    c->used = 1;
+    if (!c->failed && n >= cap) {
+        fprintf(stderr, "svt_hip_bind_dev: a call scope has no %s slot left (%d)\n", what, cap);
+        c->failed = 1;
+    }
+    return c->failed;
+}
+static uint8_t *call_pin(HdCall *c, const void *host, size_t bytes, uint64_t tag, int is_new) {
+    if (call_enter(c, c->n_pins, HD_CALL_PINS, "pin"))
+        return NULL;
+    uint8_t *d = is_new ? hd_mirror_new(host, bytes, tag) : hd_mirror_get(host, bytes, tag);
+    if (!d) {
+        c->failed = 1;
+        return NULL;
+    }
+    c->pin[c->n_pins] = host, c->pin_new[c->n_pins++] = (uint8_t)is_new;
+    return d;
+}
+uint8_t *hd_call_mirror(HdCall *c, const void *host, size_t bytes, uint64_t tag) { return call_pin(c, host, bytes, tag, 0); }
+uint8_t *hd_call_mirror_new(HdCall *c, const void *host, size_t bytes, uint64_t tag) { return call_pin(c, host, bytes, tag, 1); }
+void     hd_call_unpin(HdCall *c, const void *host) {
+    for (int i = 0; i < c->n_pins; i++)
+        if (c->pin[i] == host) {
+            hd_mirror_unpin(host);
+            --c->n_pins;
+            c->pin[i] = c->pin[c->n_pins], c->pin_new[i] = c->pin_new[c->n_pins];
+            return;
+        }
+}
+static void *call_block(HdCall *c, size_t bytes, int kind) {
+    if (call_enter(c, c->n_blocks, HD_CALL_BLOCKS, "block"))
+        return NULL;
+    void *p = kind == BLK_DEV ? (void *)hd_alloc(bytes + 256) : kind == BLK_PINNED ? hd_host_alloc(bytes) : calloc(bytes ? bytes : 1, 1);
+    if (!p) {
+        c->failed = 1;
+        return NULL;
+    }
+    c->block[c->n_blocks] = p, c->block_kind[c->n_blocks++] = (uint8_t)kind;
+    return p;
+}
+uint8_t *hd_call_dev(HdCall *c, size_t bytes) { return (uint8_t *)call_block(c, bytes, BLK_DEV); }
+void    *hd_call_pinned(HdCall *c, size_t bytes) { return call_block(c, bytes, BLK_PINNED); }
+void    *hd_call_host(HdCall *c, size_t bytes) { return call_block(c, bytes, BLK_HOST); }
+uint8_t *hd_call_dev_put(HdCall *c, const void *host, size_t bytes) {
+    uint8_t *d = hd_call_dev(c, bytes);
+    return hd_call_upload(c, d, host, bytes) == 0 ? d : NULL;
+}
+int hd_call_upload(HdCall *c, void *d, const void *h, size_t n) { return HD_CALL(c, (d && h) ? hd_upload(d, h, n) : -1); }
+int hd_call_download(HdCall *c, void *h, const void *d, size_t n) { return HD_CALL(c, (d && h) ? hd_download(h, d, n) : -1); }
+int hd_call_memset(HdCall *c, void *d, int value, size_t n) { return HD_CALL(c, d ? g_hd.memset_(d, value, n, NULL) : -1); }
+int hd_call_sync(HdCall *c) {
+    if (HD_CALL(c, hd_sync()) == 0)
+        c->used = 0; /* nothing of this call is in flight any more: hd_call_end need not wait again */
+    return c->failed;
+}
+
+int hd_call_end(HdCall *c, const char *fmt, ...) {
+    /* nothing is released under work that is still in flight: the calling thread's stream is drained first, whatever happened */
+    if (c->used && hd_sync() != 0) /* (used: a step was made since the last successful hd_call_sync) */
+        c->failed = 1;
+    for (int i = 0; i < c->n_pins; i++) {
+        if (c->failed && c->pin_new[i])
+            hd_mirror_drop(c->pin[i]); /* nobody may find a buffer the call did not finish filling */
+        hd_mirror_unpin(c->pin[i]);
+    }
+    for (int i = 0; i < c->n_blocks; i++)
+        if (c->block_kind[i] == BLK_DEV)
+            hd_free(c->block[i]);
+        else if (c->block_kind[i] == BLK_PINNED)
+            hd_host_free(c->block[i]);
+        else
+            free(c->block[i]);
+    c->n_pins = c->n_blocks = 0;
+    if (c->timer)
+        hd_timer_add(c->timer, hd_now_ns() - c->t0);
+    if (c->failed && fmt) {
+        char    msg[256];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(msg, sizeof(msg), fmt, ap);
+        va_end(ap);
+        fprintf(stderr, "%s (%s)\n", msg, hd_error());
+    }
+    return c->failed ? 1 : 0;
+}
+int hd_call_decline(HdCall *c) {
+    c->failed = 1;
+    return hd_call_end(c, NULL);
+}
+
+void hd_debug_in_use(int *pins, int *dev_blocks, int *host_blocks) {
+    *pins = *dev_blocks = *host_blocks = 0;
+    pthread_mutex_lock(&g_mu);
+    for (const Mirror *m = g_mirrors; m; m = m->next) *pins += m->pins, *dev_blocks -= 1; /* a mirror's block is not scratch */
+    pthread_mutex_unlock(&g_mu);
+    pthread_mutex_lock(&g_pool_mu);
+    for (const PoolBlk *b = g_pool; b; b = b->next) *dev_blocks += b->busy;
+    for (const HostBlk *b = g_hpool; b; b = b->next) *host_blocks += b->busy;
+    pthread_mutex_unlock(&g_pool_mu);
 }

@@ -1,5 +1,5 @@
 /*
- * svt_hip_bind_dev.h — what the Tier B glue files (svt_hip_bind_{me,tf,tpl,lf,pa}.c) share: the resolved device API of
+ * svt_hip_bind_dev.h — what the Tier B glue files (svt_hip_bind_{me,tf,tpl,lf,pa,txt}.c) share: the resolved device API of
  * libsvtav1_hip.so, PCIe byte counters, and the DEVICE-RESIDENT PICTURE MIRRORS of SURVEY.md 8b "Ownership" ("the shim owns
  * device mirrors ... per-picture device planes keyed by picture number").
  *
@@ -18,14 +18,22 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "svt_hip.h"
+
+/* Entry points of libsvtav1_hip.so are looked up by name; their types come from the declarations of include/svt_hip*.h:
+ *     HD_FN(svt_hip_me_frames);  ...  HD_SYM(sym, svt_hip_me_frames);  ...  p_svt_hip_me_frames(job, 1, NULL) */
+#define HD_LOOKUP(sym, name) ((__typeof__(name) *)(sym)(#name))
+#define HD_FN(name) static __typeof__(name) *p_##name
+#define HD_SYM(sym, name) (p_##name = HD_LOOKUP(sym, name))
+
 typedef struct HipDev {
-    int32_t (*malloc_)(void **, size_t);
-    int32_t (*free_)(void *);
-    int32_t (*upload)(void *, const void *, size_t, void *);
-    int32_t (*download)(void *, const void *, size_t, void *);
-    int32_t (*memset_)(void *, int32_t, size_t, void *);
-    int32_t (*sync)(void *);
-    const char *(*last_error)(void);
+    __typeof__(svt_hip_malloc)      *malloc_;
+    __typeof__(svt_hip_free)        *free_;
+    __typeof__(svt_hip_upload)      *upload;
+    __typeof__(svt_hip_download)    *download;
+    __typeof__(svt_hip_memset)      *memset_;
+    __typeof__(svt_hip_stream_sync) *sync;
+    __typeof__(svt_hip_last_error)  *last_error;
     int ok; /* every pointer above resolved */
 } HipDev;
 extern HipDev g_hd;
@@ -75,6 +83,58 @@ void hd_mirror_drop(const void *host);
 /* Re-tag: the entry of `host` (if any, with tag `from`) now describes content `to` — the caller knows both are the same bytes. */
 void hd_mirror_retag(const void *host, uint64_t from, uint64_t to);
 
+/* ---- one scope per hook call ---------------------------------------------------------------------------------------------
+ * A hook puts an HdCall on its stack and acquires everything through it: mirror pins, device scratch, pinned staging, plain host
+ * memory.  The scope owns all of it until hd_call_end.  Its status is STICKY: once a step has failed, every later step made through
+ * the scope does nothing (no device call is issued) and returns NULL / non-zero, so a hook is straight-line code with one
+ * hd_call_sync test in front of the place where it copies its results into the encoder's buffers.  hd_call_end synchronises the
+ * calling thread's stream BEFORE it releases anything, also after a failure.  The arrays are sized for the largest user (the temporal
+ * filter: 5 planes / 3 scratch planes per window picture); one acquisition too many makes the call fail. */
+#define HD_CALL_PINS 168
+#define HD_CALL_BLOCKS 112
+typedef struct HdCall {
+    const char *timer; /* hook name of the "ms per call" lines at exit, or NULL */
+    uint64_t    t0;
+    int         failed, used, n_pins, n_blocks;
+    const void *pin[HD_CALL_PINS];
+    void       *block[HD_CALL_BLOCKS];
+    uint8_t     pin_new[HD_CALL_PINS], block_kind[HD_CALL_BLOCKS];
+} HdCall;
+void     hd_call_begin(HdCall *c, const char *timer_name);
+uint8_t *hd_call_mirror(HdCall *c, const void *host, size_t bytes, uint64_t tag);     /* hd_mirror_get, pinned until the end */
+uint8_t *hd_call_mirror_new(HdCall *c, const void *host, size_t bytes, uint64_t tag); /* hd_mirror_new; dropped if the call fails */
+void     hd_call_unpin(HdCall *c, const void *host);     /* early release of one pin (after hd_call_sync): the caller is done with it */
+uint8_t *hd_call_dev(HdCall *c, size_t bytes);           /* device scratch of >= bytes + 256, 256-aligned */
+uint8_t *hd_call_dev_put(HdCall *c, const void *host, size_t bytes); /* the same + upload */
+void    *hd_call_pinned(HdCall *c, size_t bytes);        /* page-locked staging */
+void    *hd_call_host(HdCall *c, size_t bytes);          /* zeroed */
+int      hd_call_upload(HdCall *c, void *d, const void *h, size_t n);
+int      hd_call_download(HdCall *c, void *h, const void *d, size_t n);
+int      hd_call_memset(HdCall *c, void *d, int value, size_t n);
+int      hd_call_ok(const HdCall *c);
+void     hd_call_fail(HdCall *c);
+int      hd_call_check(HdCall *c, int rc);               /* folds a return code into the status; non-zero when the scope has failed */
+/* a library call through the scope: not made once the scope has failed */
+#define HD_CALL(c, call) (hd_call_ok(c) ? hd_call_check(c, (call)) : 1)
+int      hd_call_sync(HdCall *c);                        /* 0: everything so far has succeeded and arrived: results may be committed */
+/* Syncs (unless nothing was done since a successful hd_call_sync), unpins, frees, adds the timer; after a failure prints "<fmt ...> (<hd_error()>)" once (fmt NULL:
+ * nothing).  Returns 0 = the GPU did it, 1 = the caller runs the CPU code. */
+int      hd_call_end(HdCall *c, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+int      hd_call_decline(HdCall *c);                     /* not a case for the GPU: hd_call_end without a message, returns 1 */
+/* for the tests: what is pinned / handed out right now */
+void     hd_debug_in_use(int *pins, int *dev_blocks, int *host_blocks);
+
+static inline size_t hd_al256(size_t v) { return (v + 255) & ~(size_t)255; }
+/* one pool block cut into 256-aligned regions: *cursor walks through it (NULL stays NULL) */
+static inline uint8_t *hd_carve(uint8_t **cursor, size_t n) {
+    uint8_t *r = *cursor;
+    if (r)
+        *cursor = r + hd_al256(n);
+    return r;
+}
+/* bytes of a padded luma plane; d: const EbPictureBufferDesc * (a macro: this header stays free of the reference's types) */
+#define hd_luma_bytes(d) ((size_t)(d)->stride_y * ((d)->height + 2u * (d)->org_y))
+
 /* ---- "the first caller computes the picture, the others wait" ----------------------------------------------------------
  * The reference's kernels are called per segment / block from several threads; a whole-picture entry point runs once.  An
  * entry is identified by (owner, key); `total` calls are expected per entry, after which it is recycled.  Never full: entries
@@ -83,16 +143,14 @@ typedef struct HdOnce HdOnce;
 typedef struct HdOnceTable {
     HdOnce *head;
 } HdOnceTable;
-/* Returns the entry; *first = 1 for exactly one caller, which must call hd_once_done(entry, ok, payload) when it has finished;
- * every other caller blocks until then.  hd_once_result gives ok / payload; hd_once_release counts the caller out and frees
- * the payload (with free_payload) after the last one. */
-HdOnce *hd_once_enter(HdOnceTable *t, const void *owner, uint64_t key, uint32_t total, int *first);
-void    hd_once_done(HdOnce *e, int ok, void *payload);
-int     hd_once_ok(const HdOnce *e);
-void   *hd_once_payload(const HdOnce *e);
-void    hd_once_release(HdOnceTable *t, HdOnce *e, void (*free_payload)(void *));
+/* Exactly one caller of an entry runs compute(arg, &payload) (non-zero = ok); every other caller blocks until it has finished.
+ * When it was ok, every caller gets take(arg, payload) to copy its share out; the last of the `total` callers frees the payload
+ * with free_payload.  take / free_payload may be NULL.  Returns 0 = ok, 1 = not ok, -1 = no entry (out of memory). */
+int hd_once_run(HdOnceTable *t, const void *owner, uint64_t key, uint32_t total, int (*compute)(void *arg, void **payload),
+                void (*take)(void *arg, const void *payload), void (*free_payload)(void *), void *arg);
 
-/* wall-clock spent inside each hook (summed over threads and calls; printed at exit): hd_timer_add(name, hd_now_ns() - t0) */
+/* wall-clock spent inside each hook (summed over threads and calls; printed at exit): an HdCall adds its own; a hook's sub-steps use
+ * hd_timer_add(name, hd_now_ns() - t0) */
 uint64_t hd_now_ns(void);
 void     hd_timer_add(const char *name, uint64_t ns);
 

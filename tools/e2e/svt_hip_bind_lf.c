@@ -43,20 +43,20 @@
 
 #include "svt_hip.h"
 #include "svt_hip_lf.h"
+#include "svt_hip_txfm.h" /* svt_hip_plane_sse */
 #include "svt_hip_bind.h"
 #include "svt_hip_bind_dev.h"
 
 void svt_aom_get_recon_pic(PictureControlSet *pcs, EbPictureBufferDesc **recon_ptr, Bool is_highbd);
 
-static int32_t (*p_lf_frame)(const SvtHipLfFrame *, void *);
-static int32_t (*p_cdef_search)(const SvtHipCdefPlane *, const uint8_t *, const SvtHipCdefSearchParams *, uint64_t *, uint8_t *, int32_t *, void *);
-static int32_t (*p_cdef_apply)(const SvtHipCdefPlane *, uint32_t, const uint8_t *, const uint8_t *const *, int32_t, int32_t, const uint8_t *,
-                               const int32_t *, void *);
-static int32_t (*p_wiener_stats)(const SvtHipWienerUnit *, uint32_t, int32_t, int32_t, int32_t, int64_t *, int64_t *, void *);
-static int32_t (*p_lr_frame)(const SvtHipLrPlane *, uint32_t, void *);
-static int32_t (*p_copy)(void *, const void *, size_t, void *);
-static int32_t (*p_plane_sse)(const void *, uint32_t, const void *, uint32_t, uint32_t, uint32_t, int32_t, uint64_t *, void *);
-static int32_t (*p_download_2d)(void *, size_t, const void *, size_t, size_t, size_t, void *);
+HD_FN(svt_hip_loop_filter_frame);
+HD_FN(svt_hip_cdef_search_plane);
+HD_FN(svt_hip_cdef_apply_frame);
+HD_FN(svt_hip_wiener_stats);
+HD_FN(svt_hip_restoration_filter_frame);
+HD_FN(svt_hip_copy);
+HD_FN(svt_hip_plane_sse);
+HD_FN(svt_hip_download_2d);
 static int g_dlf, g_cdef, g_lr;
 static unsigned long g_n_dlf, g_n_dlf_trials, g_n_cdef_search, g_n_cdef_apply, g_n_wiener, g_n_lr;
 
@@ -68,20 +68,13 @@ static void report(void) {
 }
 
 void svt_hip_bind_lf_setup(void *(*sym)(const char *)) {
-    p_lf_frame     = (int32_t(*)(const SvtHipLfFrame *, void *))sym("svt_hip_loop_filter_frame");
-    p_cdef_search  = (int32_t(*)(const SvtHipCdefPlane *, const uint8_t *, const SvtHipCdefSearchParams *, uint64_t *, uint8_t *, int32_t *,
-                                void *))sym("svt_hip_cdef_search_plane");
-    p_cdef_apply   = (int32_t(*)(const SvtHipCdefPlane *, uint32_t, const uint8_t *, const uint8_t *const *, int32_t, int32_t, const uint8_t *,
-                               const int32_t *, void *))sym("svt_hip_cdef_apply_frame");
-    p_wiener_stats = (int32_t(*)(const SvtHipWienerUnit *, uint32_t, int32_t, int32_t, int32_t, int64_t *, int64_t *, void *))sym("svt_hip_wiener_stats");
-    p_lr_frame     = (int32_t(*)(const SvtHipLrPlane *, uint32_t, void *))sym("svt_hip_restoration_filter_frame");
-    p_copy         = (int32_t(*)(void *, const void *, size_t, void *))sym("svt_hip_copy");
-    p_plane_sse    = (int32_t(*)(const void *, uint32_t, const void *, uint32_t, uint32_t, uint32_t, int32_t, uint64_t *, void *))sym("svt_hip_plane_sse");
-    p_download_2d  = (int32_t(*)(void *, size_t, const void *, size_t, size_t, size_t, void *))sym("svt_hip_download_2d");
-    const int base = g_hd.ok && p_copy && p_download_2d;
-    g_dlf          = base && hd_env_on("SVTAV1_HIP_TIERB_DLF") && p_lf_frame;
-    g_cdef         = base && hd_env_on("SVTAV1_HIP_TIERB_CDEF") && p_cdef_search && p_cdef_apply;
-    g_lr           = base && hd_env_on("SVTAV1_HIP_TIERB_LR") && p_wiener_stats && p_lr_frame;
+    HD_SYM(sym, svt_hip_loop_filter_frame), HD_SYM(sym, svt_hip_cdef_search_plane), HD_SYM(sym, svt_hip_cdef_apply_frame);
+    HD_SYM(sym, svt_hip_wiener_stats), HD_SYM(sym, svt_hip_restoration_filter_frame);
+    HD_SYM(sym, svt_hip_copy), HD_SYM(sym, svt_hip_plane_sse), HD_SYM(sym, svt_hip_download_2d);
+    const int base = g_hd.ok && p_svt_hip_copy && p_svt_hip_download_2d;
+    g_dlf          = base && hd_env_on("SVTAV1_HIP_TIERB_DLF") && p_svt_hip_loop_filter_frame;
+    g_cdef         = base && hd_env_on("SVTAV1_HIP_TIERB_CDEF") && p_svt_hip_cdef_search_plane && p_svt_hip_cdef_apply_frame;
+    g_lr           = base && hd_env_on("SVTAV1_HIP_TIERB_LR") && p_svt_hip_wiener_stats && p_svt_hip_restoration_filter_frame;
     if (g_dlf || g_cdef || g_lr)
         atexit(report);
 }
@@ -175,30 +168,13 @@ static const SvtHipLfMi *gather_mi(PictureControlSet *pcs, size_t *bytes) {
     return mi;
 }
 
-static int dlf_frame_impl(EbPictureBufferDesc *frame_buffer, PictureControlSet *pcs, int32_t plane_start, int32_t plane_end, int64_t *trial_sse);
-int svt_hip_bind_dlf_frame(EbPictureBufferDesc *frame_buffer, PictureControlSet *pcs, int32_t plane_start, int32_t plane_end) {
-    if (!g_dlf)
-        return 1;
-    const uint64_t t0 = hd_now_ns();
-    const int      rc = dlf_frame_impl(frame_buffer, pcs, plane_start, plane_end, NULL);
-    hd_timer_add("dlf_frame", hd_now_ns() - t0);
-    return rc;
-}
-/* One trial of the deblocking level search (try_filter_frame, deblocking_filter.c:842-882) entirely on the device: the plane is filtered in a
- * scratch copy of the mirror of the un-filtered reconstruction and compared with the source picture's mirror there (picture_sse_calculations,
- * :716-834); 8 bytes come back instead of the filtered plane, and the encoder's buffer is never touched (the reference filters it, measures
- * and restores it).  Returns 0 with *filt_err set, 1 when the caller must run the reference's sequence. */
-int svt_hip_bind_dlf_try(EbPictureBufferDesc *frame_buffer, PictureControlSet *pcs, int32_t plane, int64_t *filt_err) {
-    if (!g_dlf || !p_plane_sse || plane < 0 || plane > 2)
-        return 1;
-    const uint64_t t0 = hd_now_ns();
-    const int      rc = dlf_frame_impl(frame_buffer, pcs, plane, plane + 1, filt_err);
-    hd_timer_add("dlf_trial", hd_now_ns() - t0);
-    return rc;
-}
-static int dlf_frame_impl(EbPictureBufferDesc *frame_buffer, PictureControlSet *pcs, int32_t plane_start, int32_t plane_end, int64_t *trial_sse) {
-    if (!g_dlf || !covered(pcs) || pcs->ppcs->frm_hdr.delta_lf_params.delta_lf_present || plane_start < 0 || plane_end > 3 || plane_start >= plane_end)
-        return 1;
+/* The frame filter (trial_sse == NULL: the filtered planes go back into the encoder's buffer) or one trial of the level search (the
+ * filtered plane is only measured against the source picture, on the device). */
+static int deblock(EbPictureBufferDesc *frame_buffer, PictureControlSet *pcs, int32_t plane_start, int32_t plane_end, int64_t *trial_sse) {
+    HdCall c;
+    hd_call_begin(&c, trial_sse ? "dlf_trial" : "dlf_frame");
+    if (!covered(pcs) || pcs->ppcs->frm_hdr.delta_lf_params.delta_lf_present || plane_start < 0 || plane_end > 3 || plane_start >= plane_end)
+        return hd_call_decline(&c);
     SequenceControlSet      *scs  = pcs->scs;
     PictureParentControlSet *ppcs = pcs->ppcs;
     const Av1Common         *cm   = ppcs->av1_cm;
@@ -210,31 +186,21 @@ static int dlf_frame_impl(EbPictureBufferDesc *frame_buffer, PictureControlSet *
     size_t            mi_bytes = 0;
     const SvtHipLfMi *h_mi     = gather_mi(pcs, &mi_bytes);
     if (!h_mi)
-        return 1;
-    SvtHipLfFrame f;
-    memset(&f, 0, sizeof(f));
-    int      rc = 0, mi_pinned = 0;
-    uint8_t *d_mi = hd_mirror_get(h_mi, mi_bytes, HD_TAG(pcs->picture_number, HD_ST_MI_LF));
-    if (!d_mi)
-        rc = -1;
-    else
-        mi_pinned = 1;
+        return hd_call_decline(&c);
+    uint8_t *d_mi = hd_call_mirror(&c, h_mi, mi_bytes, HD_TAG(pcs->picture_number, HD_ST_MI_LF));
     /* the planes to filter: a scratch copy of the mirror of the picture as EncDec left it (the level search filters that same
      * picture again and again: the reference restores it after every trial, the mirror never changed) */
     uint8_t *d_work[3] = {NULL, NULL, NULL};
-    for (int p = plane_start; rc == 0 && p < plane_end; p++) {
-        uint8_t *d_src = hd_mirror_get(pl[p].host, pl[p].bytes, HD_TAG(pcs->picture_number, HD_ST_RECON));
-        if (!d_src) {
-            rc = -1;
-            break;
-        }
-        d_work[p] = hd_alloc(pl[p].bytes + 256);
-        rc        = d_work[p] ? p_copy(d_work[p], d_src, pl[p].bytes, NULL) : -1;
-        if (rc == 0)
-            rc = hd_sync(); /* the copy has read the mirror before it is unpinned */
-        hd_mirror_unpin(pl[p].host);
+    for (int p = plane_start; p < plane_end; p++) {
+        uint8_t *d_src = hd_call_mirror(&c, pl[p].host, pl[p].bytes, HD_TAG(pcs->picture_number, HD_ST_RECON));
+        d_work[p]      = hd_call_dev(&c, pl[p].bytes);
+        HD_CALL(&c, p_svt_hip_copy(d_work[p], d_src, pl[p].bytes, NULL));
+        hd_call_sync(&c); /* the copy has read the mirror before it is unpinned (the final filter below replaces that mirror) */
+        hd_call_unpin(&c, pl[p].host);
     }
-    if (rc == 0) {
+    if (hd_call_ok(&c)) {
+        SvtHipLfFrame f;
+        memset(&f, 0, sizeof(f));
         for (int p = 0; p < 3; p++) f.plane[p] = d_work[p] ? d_work[p] + pl[p].origin : NULL, f.stride[p] = pl[p].stride;
         _Static_assert(sizeof(f.lvl) == sizeof(ppcs->lf_info.lvl), "LoopFilterInfoN.lvl layout");
         f.width = frame_buffer->width, f.height = frame_buffer->height;
@@ -246,9 +212,8 @@ static int dlf_frame_impl(EbPictureBufferDesc *frame_buffer, PictureControlSet *
         f.sharpness_level = (uint8_t)lf->sharpness_level;
         f.bit_depth = (uint8_t)scs->static_config.encoder_bit_depth, f.is_16bit = (uint8_t)is16;
         f.plane_start = (uint8_t)plane_start, f.plane_end = (uint8_t)plane_end;
-        rc = p_lf_frame(&f, NULL);
+        hd_call_check(&c, p_svt_hip_loop_filter_frame(&f, NULL));
     }
-    uint8_t *h_out[3] = {NULL, NULL, NULL};
     if (trial_sse) {
         /* picture_sse_calculations: against the source picture over the aligned size (8 bit) / the picture size (16 bit) */
         const int            p     = plane_start, ss = p ? 1 : 0;
@@ -257,50 +222,49 @@ static int dlf_frame_impl(EbPictureBufferDesc *frame_buffer, PictureControlSet *
         picture_planes(input, is16, sp);
         const uint32_t w = is16 ? (uint32_t)(input->width + ss) >> ss : (uint32_t)ppcs->aligned_width >> ss;
         const uint32_t h = is16 ? (uint32_t)(input->height + ss) >> ss : (uint32_t)ppcs->aligned_height >> ss;
-        uint8_t       *d_src = rc == 0 ? hd_mirror_get(sp[p].host, sp[p].bytes, HD_TAG(pcs->picture_number, is16 ? HD_ST_SOURCE16 : HD_ST_FILTERED)) : NULL;
-        uint8_t       *d_sum = rc == 0 ? hd_alloc(256) : NULL;
+        uint8_t       *d_src = hd_call_mirror(&c, sp[p].host, sp[p].bytes, HD_TAG(pcs->picture_number, is16 ? HD_ST_SOURCE16 : HD_ST_FILTERED));
+        uint8_t       *d_sum = hd_call_dev(&c, 0);
         uint64_t       sum   = 0;
-        if (rc == 0 && (!d_src || !d_sum))
-            rc = -1;
-        if (rc == 0)
-            rc = p_plane_sse(d_src + sp[p].origin, sp[p].stride, d_work[p] + pl[p].origin, pl[p].stride, w, h, is16, (uint64_t *)d_sum, NULL);
-        if (rc == 0)
-            rc = hd_download(&sum, d_sum, 8);
-        rc |= hd_sync();
-        if (d_src)
-            hd_mirror_unpin(sp[p].host);
-        hd_free(d_sum);
-        if (rc == 0)
+        HD_CALL(&c, p_svt_hip_plane_sse(d_src + sp[p].origin, sp[p].stride, d_work[p] + pl[p].origin, pl[p].stride, w, h, is16, (uint64_t *)d_sum, NULL));
+        hd_call_download(&c, &sum, d_sum, 8);
+        if (hd_call_sync(&c) == 0)
             *trial_sse = (int64_t)sum;
     } else {
-    for (int p = plane_start; rc == 0 && p < plane_end; p++) {
-        h_out[p] = (uint8_t *)hd_host_alloc(pl[p].bytes);
-        rc       = h_out[p] ? hd_download(h_out[p], d_work[p], pl[p].bytes) : -1;
-    }
-    rc |= hd_sync();
-    if (rc == 0)
-        for (int p = plane_start; p < plane_end; p++) memcpy(pl[p].host, h_out[p], pl[p].bytes);
-    /* the picture's final deblocking (all planes; a trial filters one): the filtered planes become the mirrors of the host planes they were
-     * just downloaded into, so that the CDEF search finds its input resident instead of uploading it again */
-    if (rc == 0 && plane_start == 0 && plane_end == 3)
-        for (int p = 0; p < 3; p++) {
-            uint8_t *d_new = hd_mirror_new(pl[p].host, pl[p].bytes, HD_TAG(pcs->picture_number, HD_ST_DEBLOCKED));
-            if (!d_new)
-                continue;
-            if (p_copy(d_new, d_work[p], pl[p].bytes, NULL) != 0 || hd_sync() != 0)
-                hd_mirror_drop(pl[p].host);
-            hd_mirror_unpin(pl[p].host);
+        uint8_t *h_out[3] = {NULL, NULL, NULL};
+        for (int p = plane_start; p < plane_end; p++) {
+            h_out[p] = (uint8_t *)hd_call_pinned(&c, pl[p].bytes);
+            hd_call_download(&c, h_out[p], d_work[p], pl[p].bytes);
+        }
+        if (hd_call_sync(&c) == 0) {
+            for (int p = plane_start; p < plane_end; p++) memcpy(pl[p].host, h_out[p], pl[p].bytes);
+            /* the picture's final deblocking (all planes; a trial filters one): the filtered planes become the mirrors of the host planes they
+             * were just downloaded into, so that the CDEF search finds its input resident instead of uploading it again.  The picture is
+             * committed: a plane that cannot be adopted (a scope of its own) is simply uploaded again later */
+            for (int p = 0; plane_start == 0 && plane_end == 3 && p < 3; p++) {
+                HdCall a;
+                hd_call_begin(&a, NULL);
+                uint8_t *d_new = hd_call_mirror_new(&a, pl[p].host, pl[p].bytes, HD_TAG(pcs->picture_number, HD_ST_DEBLOCKED));
+                HD_CALL(&a, p_svt_hip_copy(d_new, d_work[p], pl[p].bytes, NULL));
+                hd_call_end(&a, NULL);
+            }
         }
     }
-    if (mi_pinned)
-        hd_mirror_unpin(h_mi);
-    for (int p = 0; p < 3; p++) hd_free(d_work[p]), hd_host_free(h_out[p]);
-    if (rc != 0) {
-        fprintf(stderr, "svt_hip_bind_lf: deblocking of picture %llu stays on the CPU (%s)\n", (unsigned long long)pcs->picture_number, hd_error());
+    if (hd_call_end(&c, "svt_hip_bind_lf: deblocking of picture %llu stays on the CPU", (unsigned long long)pcs->picture_number))
         return 1;
-    }
     __atomic_add_fetch(trial_sse ? &g_n_dlf_trials : &g_n_dlf, 1, __ATOMIC_RELAXED);
     return 0;
+}
+int svt_hip_bind_dlf_frame(EbPictureBufferDesc *frame_buffer, PictureControlSet *pcs, int32_t plane_start, int32_t plane_end) {
+    return g_dlf ? deblock(frame_buffer, pcs, plane_start, plane_end, NULL) : 1;
+}
+/* One trial of the deblocking level search (try_filter_frame, deblocking_filter.c:842-882) entirely on the device: the plane is filtered in a
+ * scratch copy of the mirror of the un-filtered reconstruction and compared with the source picture's mirror there (picture_sse_calculations,
+ * :716-834); 8 bytes come back instead of the filtered plane, and the encoder's buffer is never touched (the reference filters it, measures
+ * and restores it).  Returns 0 with *filt_err set, 1 when the caller must run the reference's sequence. */
+int svt_hip_bind_dlf_try(EbPictureBufferDesc *frame_buffer, PictureControlSet *pcs, int32_t plane, int64_t *filt_err) {
+    if (!g_dlf || !p_svt_hip_plane_sse || plane < 0 || plane > 2)
+        return 1;
+    return deblock(frame_buffer, pcs, plane, plane + 1, filt_err);
 }
 
 /* ================================================================ CDEF ==================================================== */
@@ -308,31 +272,25 @@ static HdOnceTable g_cdef_tab;
 
 /* filt8x8[r][c] != 0: the 8x8 luma block (r, c) is filtered = not all four of its 4x4 units are skipped (svt_sb_compute_cdef_list,
  * enc_cdef.c:238-276) */
-static uint8_t *skip_bitmap(const PictureControlSet *pcs, uint32_t *w8, uint32_t *h8) {
+static uint8_t *skip_bitmap(HdCall *c, const PictureControlSet *pcs, uint32_t *w8, uint32_t *h8) {
     const Av1Common *cm = pcs->ppcs->av1_cm;
     *w8 = (uint32_t)(cm->mi_cols + 1) >> 1, *h8 = (uint32_t)(cm->mi_rows + 1) >> 1;
-    uint8_t *m = (uint8_t *)calloc((size_t)*w8 * *h8, 1);
+    uint8_t *m = (uint8_t *)hd_call_host(c, (size_t)*w8 * *h8);
     if (!m)
         return NULL;
     ModeInfo **grid = pcs->mi_grid_base;
     const int  ms   = pcs->mi_stride;
     for (int32_t r = 0; r + 1 < cm->mi_rows + (cm->mi_rows & 1); r += 2)
-        for (int32_t c = 0; c + 1 < cm->mi_cols + (cm->mi_cols & 1); c += 2) {
-            const int r1 = r + 1 < cm->mi_rows ? r + 1 : r, c1 = c + 1 < cm->mi_cols ? c + 1 : c;
-            m[(size_t)(r >> 1) * *w8 + (c >> 1)] = !grid[r * ms + c]->mbmi.block_mi.skip || !grid[r * ms + c1]->mbmi.block_mi.skip ||
-                !grid[r1 * ms + c]->mbmi.block_mi.skip || !grid[r1 * ms + c1]->mbmi.block_mi.skip;
+        for (int32_t c4 = 0; c4 + 1 < cm->mi_cols + (cm->mi_cols & 1); c4 += 2) {
+            const int r1 = r + 1 < cm->mi_rows ? r + 1 : r, c1 = c4 + 1 < cm->mi_cols ? c4 + 1 : c4;
+            m[(size_t)(r >> 1) * *w8 + (c4 >> 1)] = !grid[r * ms + c4]->mbmi.block_mi.skip || !grid[r * ms + c1]->mbmi.block_mi.skip ||
+                !grid[r1 * ms + c4]->mbmi.block_mi.skip || !grid[r1 * ms + c1]->mbmi.block_mi.skip;
         }
     return m;
 }
 
-typedef struct CdefPlanes {
-    SvtHipCdefPlane pl[3];
-    const void     *pinned[6];
-    int             n_pinned;
-} CdefPlanes;
-
 /* recon (after deblocking) and the second plane of every SvtHipCdefPlane: the source picture (search) or NULL (apply: set by the caller) */
-static int cdef_planes(CdefPlanes *cp, PictureControlSet *pcs, int with_source) {
+static void cdef_planes(HdCall *c, SvtHipCdefPlane pl[3], PictureControlSet *pcs, int with_source) {
     const SequenceControlSet *scs  = pcs->scs;
     const Av1Common          *cm   = pcs->ppcs->av1_cm;
     const int                 is16 = scs->is_16bit_pipeline;
@@ -340,46 +298,39 @@ static int cdef_planes(CdefPlanes *cp, PictureControlSet *pcs, int with_source) 
     svt_aom_get_recon_pic(pcs, &recon, is16);
     PlaneRef rp[3], sp[3];
     picture_planes(recon, is16, rp), picture_planes(input, is16, sp);
-    memset(cp, 0, sizeof(*cp));
+    memset(pl, 0, 3 * sizeof(*pl));
     for (int p = 0; p < 3; p++) {
-        SvtHipCdefPlane *o = &cp->pl[p];
-        uint8_t         *d = hd_mirror_get(rp[p].host, rp[p].bytes, HD_TAG(pcs->picture_number, HD_ST_DEBLOCKED));
-        if (!d)
-            return -1;
-        cp->pinned[cp->n_pinned++] = rp[p].host;
-        o->recon = d + rp[p].origin, o->recon_stride = rp[p].stride;
+        SvtHipCdefPlane *o = &pl[p];
+        uint8_t         *d = hd_call_mirror(c, rp[p].host, rp[p].bytes, HD_TAG(pcs->picture_number, HD_ST_DEBLOCKED));
+        o->recon = d ? d + rp[p].origin : NULL, o->recon_stride = rp[p].stride;
         if (with_source) {
-            uint8_t *s = hd_mirror_get(sp[p].host, sp[p].bytes, HD_TAG(pcs->picture_number, is16 ? HD_ST_SOURCE16 : HD_ST_FILTERED));
-            if (!s)
-                return -1;
-            cp->pinned[cp->n_pinned++] = sp[p].host;
-            o->source = s + sp[p].origin, o->source_stride = sp[p].stride;
+            uint8_t *s = hd_call_mirror(c, sp[p].host, sp[p].bytes, HD_TAG(pcs->picture_number, is16 ? HD_ST_SOURCE16 : HD_ST_FILTERED));
+            o->source = s ? s + sp[p].origin : NULL, o->source_stride = sp[p].stride;
         }
         o->width = (uint32_t)(cm->mi_cols * 4) >> (p ? 1 : 0), o->height = (uint32_t)(cm->mi_rows * 4) >> (p ? 1 : 0);
         o->is_16bit = (uint8_t)is16, o->xdec = o->ydec = p ? 1 : 0, o->pli = (uint8_t)p;
     }
-    return 0;
-}
-static void cdef_planes_release(CdefPlanes *cp) {
-    for (int i = 0; i < cp->n_pinned; i++) hd_mirror_unpin(cp->pinned[i]);
-    cp->n_pinned = 0;
 }
 
 #define CDEF_DEFAULT_MSE_UV ((uint64_t)1040400 * 64) /* default_mse_uv * 64, cdef_process.c:78, :251 */
 
-static int cdef_search_picture(PictureControlSet *pcs, SequenceControlSet *scs) {
-    PictureParentControlSet *ppcs = pcs->ppcs;
-    const Av1Common         *cm   = ppcs->av1_cm;
-    const CdefControls      *cc   = &ppcs->cdef_ctrls;
-    const int                n1 = cc->first_pass_fs_num, n2 = cc->default_second_pass_fs_num, n = n1 + n2;
+/* the first segment of a picture searches all of it (hd_once_run) */
+static int cdef_search_picture(void *arg, void **payload) {
+    (void)payload;
+    PictureControlSet        *pcs  = (PictureControlSet *)arg;
+    const SequenceControlSet *scs  = pcs->scs;
+    PictureParentControlSet  *ppcs = pcs->ppcs;
+    const Av1Common          *cm   = ppcs->av1_cm;
+    const CdefControls       *cc   = &ppcs->cdef_ctrls;
+    const int                 n1 = cc->first_pass_fs_num, n2 = cc->default_second_pass_fs_num, n = n1 + n2;
+    HdCall                    c;
+    hd_call_begin(&c, "cdef_search");
     if (n < 1 || n > SVT_HIP_CDEF_MAX_STRENGTHS)
-        return 1;
+        return !hd_call_decline(&c);
     const int32_t nvfb = (cm->mi_rows + MI_SIZE_64X64 - 1) / MI_SIZE_64X64, nhfb = (cm->mi_cols + MI_SIZE_64X64 - 1) / MI_SIZE_64X64;
     const size_t  nfb  = (size_t)nvfb * nhfb;
     uint32_t      w8, h8;
-    uint8_t      *filt = skip_bitmap(pcs, &w8, &h8);
-    if (!filt)
-        return 1;
+    uint8_t      *filt = skip_bitmap(&c, pcs, &w8, &h8);
     SvtHipCdefSearchParams prm[2]; /* luma, chroma */
     memset(prm, 0, sizeof(prm));
     for (int k = 0; k < 2; k++) {
@@ -394,36 +345,30 @@ static int cdef_search_picture(PictureControlSet *pcs, SequenceControlSet *scs) 
         prm[k].coeff_shift        = AOMMAX(scs->static_config.encoder_bit_depth - 8, 0);
         prm[k].subsampling_factor = cc->subsampling_factor;
     }
-    CdefPlanes cp;
-    int        rc = cdef_planes(&cp, pcs, 1);
+    SvtHipCdefPlane pl[3];
+    cdef_planes(&c, pl, pcs, 1);
     const size_t n_mse = nfb * n * sizeof(uint64_t), n_dir = nfb * 64, n_var = nfb * 64 * sizeof(int32_t), n_filt = (size_t)w8 * h8;
-    uint8_t   *dev = rc == 0 ? hd_alloc(3 * n_mse + n_dir + n_var + n_filt + 1024) : NULL;
-    if (rc == 0 && !dev)
-        rc = -1;
-    uint8_t  *d_mse = dev, *d_dir = dev ? dev + 3 * n_mse : NULL, *d_var = dev ? d_dir + ((n_dir + 255) & ~(size_t)255) : NULL;
-    uint8_t  *d_filt = dev ? d_var + ((n_var + 255) & ~(size_t)255) : NULL;
-    uint64_t *h_mse = (uint64_t *)malloc(3 * n_mse);
-    uint8_t  *h_dir = (uint8_t *)malloc(n_dir);
-    int32_t  *h_var = (int32_t *)malloc(n_var);
-    if (!h_mse || !h_dir || !h_var)
-        rc = -1;
-    if (rc == 0)
-        rc = hd_upload(d_filt, filt, n_filt) | g_hd.memset_(d_mse, 0, 3 * n_mse, NULL);
-    for (int p = 0; rc == 0 && p < 3; p++) /* luma first: it writes the directions the chroma planes read */
-        rc = p_cdef_search(&cp.pl[p], d_filt, &prm[p ? 1 : 0], (uint64_t *)(d_mse + p * n_mse), d_dir, (int32_t *)d_var, NULL);
-    if (rc == 0)
-        rc = hd_download(h_mse, d_mse, 3 * n_mse) | hd_download(h_dir, d_dir, n_dir) | hd_download(h_var, d_var, n_var);
-    rc |= hd_sync();
-    cdef_planes_release(&cp);
-    if (rc == 0) {
+    uint8_t     *dev   = hd_call_dev(&c, hd_al256(3 * n_mse) + hd_al256(n_dir) + hd_al256(n_var) + n_filt);
+    uint8_t     *d_mse = hd_carve(&dev, 3 * n_mse), *d_dir = hd_carve(&dev, n_dir), *d_var = hd_carve(&dev, n_var), *d_filt = dev;
+    uint64_t    *h_mse = (uint64_t *)hd_call_host(&c, 3 * n_mse);
+    uint8_t     *h_dir = (uint8_t *)hd_call_host(&c, n_dir);
+    int32_t     *h_var = (int32_t *)hd_call_host(&c, n_var);
+    hd_call_upload(&c, d_filt, filt, n_filt);
+    hd_call_memset(&c, d_mse, 0, 3 * n_mse);
+    for (int p = 0; p < 3; p++) /* luma first: it writes the directions the chroma planes read */
+        HD_CALL(&c, p_svt_hip_cdef_search_plane(&pl[p], d_filt, &prm[p ? 1 : 0], (uint64_t *)(d_mse + p * n_mse), d_dir, (int32_t *)d_var, NULL));
+    hd_call_download(&c, h_mse, d_mse, 3 * n_mse);
+    hd_call_download(&c, h_dir, d_dir, n_dir);
+    hd_call_download(&c, h_var, d_var, n_var);
+    if (hd_call_sync(&c) == 0)
         for (int32_t fbr = 0; fbr < nvfb; fbr++)
             for (int32_t fbc = 0; fbc < nhfb; fbc++) {
                 const size_t fb = (size_t)fbr * nhfb + fbc;
                 /* cdef_count == 0 <=> no 8x8 of the filter block is filtered (:197-202) */
                 int any = 0;
                 for (uint32_t r = fbr * 8u; r < fbr * 8u + 8 && r < h8 && !any; r++)
-                    for (uint32_t c = fbc * 8u; c < fbc * 8u + 8 && c < w8; c++)
-                        if (filt[(size_t)r * w8 + c]) {
+                    for (uint32_t c8 = fbc * 8u; c8 < fbc * 8u + 8 && c8 < w8; c8++)
+                        if (filt[(size_t)r * w8 + c8]) {
                             any = 1;
                             break;
                         }
@@ -437,119 +382,85 @@ static int cdef_search_picture(PictureControlSet *pcs, SequenceControlSet *scs) 
                     pcs->mse_seg[1][fb][gi] = prm[1].strengths[gi] == -1 ? CDEF_DEFAULT_MSE_UV : h_mse[(nfb + fb) * n + gi] + h_mse[(2 * nfb + fb) * n + gi];
                 }
             }
-    }
-    hd_free(dev);
-    free(filt), free(h_mse), free(h_dir), free(h_var);
-    if (rc != 0) {
-        fprintf(stderr, "svt_hip_bind_lf: CDEF search of picture %llu stays on the CPU (%s)\n", (unsigned long long)pcs->picture_number, hd_error());
-        return 1;
-    }
+    if (hd_call_end(&c, "svt_hip_bind_lf: CDEF search of picture %llu stays on the CPU", (unsigned long long)pcs->picture_number))
+        return 0;
     __atomic_add_fetch(&g_n_cdef_search, 1, __ATOMIC_RELAXED);
-    return 0;
+    return 1;
 }
 
 int svt_hip_bind_cdef_seg(PictureControlSet *pcs, SequenceControlSet *scs, uint32_t segment_index) {
-    (void)segment_index;
+    (void)scs, (void)segment_index;
     if (!g_cdef || !covered(pcs))
         return 1;
-    int     first;
-    HdOnce *once = hd_once_enter(&g_cdef_tab, pcs, pcs->picture_number, pcs->cdef_segments_total_count, &first);
-    if (!once)
-        return 1;
-    if (first) {
-        const uint64_t t0 = hd_now_ns();
-        const int      ok = cdef_search_picture(pcs, scs) == 0;
-        hd_timer_add("cdef_search", hd_now_ns() - t0);
-        hd_once_done(once, ok, NULL);
-    }
-    const int ok = hd_once_ok(once);
-    hd_once_release(&g_cdef_tab, once, NULL);
-    return ok ? 0 : 1;
+    return hd_once_run(&g_cdef_tab, pcs, pcs->picture_number, pcs->cdef_segments_total_count, cdef_search_picture, NULL, NULL, pcs) != 0;
 }
 
-static int cdef_apply_impl(SequenceControlSet *scs, PictureControlSet *pcs);
 int svt_hip_bind_cdef_frame(SequenceControlSet *scs, PictureControlSet *pcs) {
     if (!g_cdef)
         return 1;
-    const uint64_t t0 = hd_now_ns();
-    const int      rc = cdef_apply_impl(scs, pcs);
-    hd_timer_add("cdef_apply", hd_now_ns() - t0);
-    return rc;
-}
-static int cdef_apply_impl(SequenceControlSet *scs, PictureControlSet *pcs) {
-    if (!g_cdef || !covered(pcs) || pcs->ppcs->cdef_ctrls.use_reference_cdef_fs)
-        return 1;
+    HdCall c;
+    hd_call_begin(&c, "cdef_apply");
+    if (!covered(pcs) || pcs->ppcs->cdef_ctrls.use_reference_cdef_fs)
+        return hd_call_decline(&c);
     PictureParentControlSet *ppcs    = pcs->ppcs;
     const Av1Common         *cm      = ppcs->av1_cm;
     const FrameHeader       *frm_hdr = &ppcs->frm_hdr;
     const int                is16    = scs->is_16bit_pipeline;
     const int32_t nvfb = (cm->mi_rows + MI_SIZE_64X64 - 1) / MI_SIZE_64X64, nhfb = (cm->mi_cols + MI_SIZE_64X64 - 1) / MI_SIZE_64X64;
     const size_t  nfb  = (size_t)nvfb * nhfb;
+    const size_t  n_dir = nfb * 64, n_var = nfb * 64 * sizeof(int32_t);
     uint32_t      w8, h8;
-    uint8_t      *filt = skip_bitmap(pcs, &w8, &h8);
-    uint8_t      *fbs  = (uint8_t *)calloc(2 * nfb, 1);
-    uint8_t      *h_dir = (uint8_t *)calloc(nfb, 64);
-    int32_t      *h_var = (int32_t *)calloc(nfb, 64 * sizeof(int32_t));
-    int           rc = (filt && fbs && h_dir && h_var) ? 0 : -1;
-    for (int32_t fbr = 0; rc == 0 && fbr < nvfb; fbr++)
+    uint8_t      *filt  = skip_bitmap(&c, pcs, &w8, &h8);
+    uint8_t      *fbs   = (uint8_t *)hd_call_host(&c, 2 * nfb);
+    uint8_t      *h_dir = (uint8_t *)hd_call_host(&c, n_dir);
+    int32_t      *h_var = (int32_t *)hd_call_host(&c, n_var);
+    for (int32_t fbr = 0; hd_call_ok(&c) && fbr < nvfb; fbr++)
         for (int32_t fbc = 0; fbc < nhfb; fbc++) {
             const size_t  fb  = (size_t)fbr * nhfb + fbc;
             const int32_t idx = pcs->mi_grid_base[MI_SIZE_64X64 * fbr * cm->mi_stride + MI_SIZE_64X64 * fbc]->mbmi.cdef_strength;
             if (idx < 0 || idx >= CDEF_MAX_STRENGTHS) {
-                rc = -1;
+                hd_call_fail(&c);
                 break;
             }
             fbs[fb] = (uint8_t)frm_hdr->cdef_params.cdef_y_strength[idx], fbs[nfb + fb] = (uint8_t)frm_hdr->cdef_params.cdef_uv_strength[idx];
             /* all four strengths zero: the reference leaves the filter block alone (:398-404) = not filtered for us */
             if (fbs[fb] == 0 && fbs[nfb + fb] == 0)
                 for (uint32_t r = fbr * 8u; r < fbr * 8u + 8 && r < h8; r++)
-                    for (uint32_t c = fbc * 8u; c < fbc * 8u + 8 && c < w8; c++) filt[(size_t)r * w8 + c] = 0;
+                    for (uint32_t c8 = fbc * 8u; c8 < fbc * 8u + 8 && c8 < w8; c8++) filt[(size_t)r * w8 + c8] = 0;
             memcpy(h_dir + fb * 64, pcs->cdef_dir_data[fb].dir, 64);
             memcpy(h_var + fb * 64, pcs->cdef_dir_data[fb].var, 64 * sizeof(int32_t));
         }
-    CdefPlanes cp;
-    memset(&cp, 0, sizeof(cp));
-    if (rc == 0)
-        rc = cdef_planes(&cp, pcs, 0);
+    SvtHipCdefPlane pl[3];
+    cdef_planes(&c, pl, pcs, 0);
     EbPictureBufferDesc *recon;
     svt_aom_get_recon_pic(pcs, &recon, is16);
     PlaneRef rp[3];
     picture_planes(recon, is16, rp);
-    const size_t n_dir = nfb * 64, n_var = nfb * 64 * sizeof(int32_t), n_filt = (size_t)w8 * h8;
-    uint8_t     *dev   = rc == 0 ? hd_alloc(n_dir + n_var + n_filt + 2 * nfb + 2048) : NULL;
-    if (rc == 0 && !dev)
-        rc = -1;
-    uint8_t *d_dir = dev, *d_var = dev ? dev + ((n_dir + 255) & ~(size_t)255) : NULL, *d_filt = dev ? d_var + ((n_var + 255) & ~(size_t)255) : NULL;
-    uint8_t *d_fbs = dev ? d_filt + ((n_filt + 255) & ~(size_t)255) : NULL;
-    uint8_t *d_out[3] = {NULL, NULL, NULL}, *h_out[3] = {NULL, NULL, NULL};
-    if (rc == 0)
-        rc = hd_upload(d_dir, h_dir, n_dir) | hd_upload(d_var, h_var, n_var) | hd_upload(d_filt, filt, n_filt) | hd_upload(d_fbs, fbs, 2 * nfb);
-    for (int p = 0; rc == 0 && p < 3; p++) {
+    const size_t n_filt = (size_t)w8 * h8;
+    uint8_t     *dev    = hd_call_dev(&c, hd_al256(n_dir) + hd_al256(n_var) + hd_al256(n_filt) + 2 * nfb);
+    uint8_t     *d_dir = hd_carve(&dev, n_dir), *d_var = hd_carve(&dev, n_var), *d_filt = hd_carve(&dev, n_filt), *d_fbs = dev;
+    uint8_t     *d_out[3] = {NULL, NULL, NULL}, *h_out[3] = {NULL, NULL, NULL};
+    hd_call_upload(&c, d_dir, h_dir, n_dir);
+    hd_call_upload(&c, d_var, h_var, n_var);
+    hd_call_upload(&c, d_filt, filt, n_filt);
+    hd_call_upload(&c, d_fbs, fbs, 2 * nfb);
+    for (int p = 0; p < 3; p++) {
         /* the output plane starts as a copy of the input: the kernel writes the picture area, the padding stays what it was */
-        d_out[p] = hd_alloc(rp[p].bytes + 256);
-        rc       = d_out[p] ? p_copy(d_out[p], (const uint8_t *)cp.pl[p].recon - rp[p].origin, rp[p].bytes, NULL) : -1;
-        cp.pl[p].source = d_out[p] ? d_out[p] + rp[p].origin : NULL, cp.pl[p].source_stride = rp[p].stride;
+        d_out[p] = hd_call_dev(&c, rp[p].bytes);
+        HD_CALL(&c, p_svt_hip_copy(d_out[p], (const uint8_t *)pl[p].recon - rp[p].origin, rp[p].bytes, NULL));
+        pl[p].source = d_out[p] ? d_out[p] + rp[p].origin : NULL, pl[p].source_stride = rp[p].stride;
     }
-    if (rc == 0) {
-        const uint8_t *strength[3] = {d_fbs, d_fbs + nfb, d_fbs + nfb};
-        rc = p_cdef_apply(cp.pl, 3, d_filt, strength, frm_hdr->cdef_params.cdef_damping, AOMMAX(scs->static_config.encoder_bit_depth - 8, 0), d_dir,
-                          (const int32_t *)d_var, NULL);
+    const uint8_t *strength[3] = {d_fbs, d_fbs + nfb, d_fbs + nfb};
+    HD_CALL(&c, p_svt_hip_cdef_apply_frame(pl, 3, d_filt, strength, frm_hdr->cdef_params.cdef_damping, AOMMAX(scs->static_config.encoder_bit_depth - 8, 0),
+                                          d_dir, (const int32_t *)d_var, NULL));
+    for (int p = 0; p < 3; p++) {
+        h_out[p] = (uint8_t *)hd_call_pinned(&c, rp[p].bytes);
+        hd_call_download(&c, h_out[p], d_out[p], rp[p].bytes);
     }
-    for (int p = 0; rc == 0 && p < 3; p++) {
-        h_out[p] = (uint8_t *)hd_host_alloc(rp[p].bytes);
-        rc       = h_out[p] ? hd_download(h_out[p], d_out[p], rp[p].bytes) : -1;
-    }
-    rc |= hd_sync();
-    cdef_planes_release(&cp);
-    if (rc == 0)
+    if (hd_call_sync(&c) == 0)
         for (int p = 0; p < 3; p++) memcpy(rp[p].host, h_out[p], rp[p].bytes);
-    for (int p = 0; p < 3; p++) hd_free(d_out[p]), hd_host_free(h_out[p]);
-    hd_free(dev);
-    free(filt), free(fbs), free(h_dir), free(h_var);
-    if (rc != 0) {
-        fprintf(stderr, "svt_hip_bind_lf: CDEF of picture %llu stays on the CPU (%s)\n", (unsigned long long)pcs->picture_number, hd_error());
+    if (hd_call_end(&c, "svt_hip_bind_lf: CDEF of picture %llu stays on the CPU", (unsigned long long)pcs->picture_number))
         return 1;
-    }
     __atomic_add_fetch(&g_n_cdef_apply, 1, __ATOMIC_RELAXED);
     return 0;
 }
@@ -610,64 +521,53 @@ static WienerPlaneStats *wiener_plane(PictureControlSet *pcs, int plane, int wie
     const Av1Common          *cm   = pcs->ppcs->av1_cm;
     const int                 is16 = scs->is_16bit_pipeline;
     const RestorationInfo    *rsi  = &pcs->rst_info[plane];
-    if (scs->use_boundaries_in_rest_search || highbd != is16)
-        return NULL;
-    EbPictureBufferDesc *recon, *input = is16 ? pcs->input_frame16bit : pcs->ppcs->enhanced_unscaled_pic;
+    EbPictureBufferDesc      *recon, *input = is16 ? pcs->input_frame16bit : pcs->ppcs->enhanced_unscaled_pic;
     svt_aom_get_recon_pic(pcs, &recon, is16);
     PlaneRef rp[3], sp[3];
     picture_planes(recon, is16, rp), picture_planes(input, is16, sp);
     const uint8_t *dgd_raw = highbd ? (const uint8_t *)CONVERT_TO_SHORTPTR(dgd) : dgd, *src_raw = highbd ? (const uint8_t *)CONVERT_TO_SHORTPTR(src) : src;
-    if (dgd_raw != rp[plane].host + rp[plane].origin || src_raw != sp[plane].host + sp[plane].origin || (uint32_t)dgd_stride != rp[plane].stride ||
-        (uint32_t)src_stride != sp[plane].stride)
-        return NULL; /* not the buffers this hook knows how to mirror (scaled source, a private copy of the reconstruction) */
-    const int ss = plane > 0, W = (cm->frm_size.superres_upscaled_width + ss) >> ss, H = (cm->frm_size.frame_height + ss) >> ss;
-    const int n  = rsi->horz_units_per_tile * rsi->vert_units_per_tile;
-    if (n < 1)
+    const int      ss = plane > 0, W = (cm->frm_size.superres_upscaled_width + ss) >> ss, H = (cm->frm_size.frame_height + ss) >> ss;
+    const int      n  = rsi->horz_units_per_tile * rsi->vert_units_per_tile;
+    HdCall         c;
+    hd_call_begin(&c, "wiener_plane");
+    /* the second line: not the buffers this hook knows how to mirror (scaled source, a private copy of the reconstruction) */
+    if (scs->use_boundaries_in_rest_search || highbd != is16 || n < 1 ||
+        dgd_raw != rp[plane].host + rp[plane].origin || src_raw != sp[plane].host + sp[plane].origin || (uint32_t)dgd_stride != rp[plane].stride ||
+        (uint32_t)src_stride != sp[plane].stride) {
+        hd_call_decline(&c);
         return NULL;
-    RestorationTileLimits *lim = (RestorationTileLimits *)calloc(n, sizeof(*lim));
-    SvtHipWienerUnit      *u   = (SvtHipWienerUnit *)calloc(n, sizeof(*u));
-    WienerPlaneStats      *st  = (WienerPlaneStats *)calloc(1, sizeof(*st));
-    int rc = (lim && u && st && unit_limits(W, H, rsi->restoration_unit_size, ss, rsi->horz_units_per_tile, rsi->vert_units_per_tile, lim) == 0) ? 0 : -1;
-    uint8_t *d_dgd = NULL, *d_src = NULL, *dev = NULL;
+    }
+    const size_t      n_m = (size_t)n * 49 * 8, n_h = (size_t)n * 49 * 49 * 8;
+    WienerPlaneStats *st  = (WienerPlaneStats *)calloc(1, sizeof(*st)); /* outlives the call: plain heap (wiener_stats_free) */
+    if (st)
+        st->lim = (RestorationTileLimits *)calloc(n, sizeof(*st->lim)), st->M = (int64_t *)malloc(n_m), st->H = (int64_t *)malloc(n_h);
+    if (!st || !st->lim || !st->M || !st->H || unit_limits(W, H, rsi->restoration_unit_size, ss, rsi->horz_units_per_tile, rsi->vert_units_per_tile, st->lim) != 0)
+        hd_call_fail(&c);
+    SvtHipWienerUnit *u = (SvtHipWienerUnit *)hd_call_host(&c, (size_t)n * sizeof(*u));
     /* the reconstruction after CDEF with the borders restoration_seg_search extended (svt_extend_frame, restoration_pick.c:1511: the
      * statistics read 3 samples beyond the picture) and the source as cdef_process.c left it */
-    if (rc == 0 && !(d_dgd = hd_mirror_get(rp[plane].host, rp[plane].bytes, HD_TAG(pcs->picture_number, HD_ST_CDEF_EXT))))
-        rc = -1;
-    if (rc == 0 && !(d_src = hd_mirror_get(sp[plane].host, sp[plane].bytes, HD_TAG(pcs->picture_number, is16 ? HD_ST_SOURCE16_LR : HD_ST_FILTERED))))
-        rc = -1;
-    const size_t n_m = (size_t)n * 49 * 8, n_h = (size_t)n * 49 * 49 * 8;
-    if (rc == 0 && !(dev = hd_alloc(n_m + n_h + 512)))
-        rc = -1;
-    if (rc == 0) {
+    uint8_t *d_dgd = hd_call_mirror(&c, rp[plane].host, rp[plane].bytes, HD_TAG(pcs->picture_number, HD_ST_CDEF_EXT));
+    uint8_t *d_src = hd_call_mirror(&c, sp[plane].host, sp[plane].bytes, HD_TAG(pcs->picture_number, is16 ? HD_ST_SOURCE16_LR : HD_ST_FILTERED));
+    uint8_t *dev   = hd_call_dev(&c, hd_al256(n_m) + n_h);
+    uint8_t *d_M = hd_carve(&dev, n_m), *d_H = dev;
+    if (hd_call_ok(&c)) {
         for (int i = 0; i < n; i++) {
+            const RestorationTileLimits *l = &st->lim[i];
             u[i].dgd = d_dgd + rp[plane].origin, u[i].src = d_src + sp[plane].origin, u[i].dgd_stride = rp[plane].stride, u[i].src_stride = sp[plane].stride;
-            u[i].h_start = lim[i].h_start, u[i].h_end = lim[i].h_end, u[i].v_start = lim[i].v_start, u[i].v_end = lim[i].v_end;
+            u[i].h_start = l->h_start, u[i].h_end = l->h_end, u[i].v_start = l->v_start, u[i].v_end = l->v_end;
         }
         st->n_units = n, st->win = wiener_win;
-        st->M = (int64_t *)malloc(n_m), st->H = (int64_t *)malloc(n_h);
-        rc = (st->M && st->H) ? p_wiener_stats(u, (uint32_t)n, wiener_win, is16, bit_depth, (int64_t *)dev, (int64_t *)(dev + ((n_m + 255) & ~(size_t)255)), NULL) : -1;
+        hd_call_check(&c, p_svt_hip_wiener_stats(u, (uint32_t)n, wiener_win, is16, bit_depth, (int64_t *)d_M, (int64_t *)d_H, NULL));
+        hd_call_download(&c, st->M, d_M, n_m);
+        hd_call_download(&c, st->H, d_H, n_h);
     }
-    if (rc == 0)
-        rc = hd_download(st->M, dev, n_m) | hd_download(st->H, dev + ((n_m + 255) & ~(size_t)255), n_h);
-    rc |= hd_sync();
-    if (d_dgd)
-        hd_mirror_unpin(rp[plane].host);
-    if (d_src)
-        hd_mirror_unpin(sp[plane].host);
-    hd_free(dev);
-    free(u);
-    if (rc == 0) {
-        st->lim = lim;
-        __atomic_add_fetch(&g_n_wiener, 1, __ATOMIC_RELAXED);
-        return st;
+    hd_call_sync(&c);
+    if (hd_call_end(&c, "svt_hip_bind_lf: Wiener statistics of picture %llu plane %d stay on the CPU", (unsigned long long)pcs->picture_number, plane)) {
+        wiener_stats_free(st);
+        return NULL;
     }
-    fprintf(stderr, "svt_hip_bind_lf: Wiener statistics of picture %llu plane %d stay on the CPU (%s)\n", (unsigned long long)pcs->picture_number, plane,
-            hd_error());
-    free(lim);
-    if (st)
-        st->lim = NULL;
-    wiener_stats_free(st);
-    return NULL;
+    __atomic_add_fetch(&g_n_wiener, 1, __ATOMIC_RELAXED);
+    return st;
 }
 
 int svt_hip_bind_wiener_stats(PictureControlSet *pcs, int plane, int rest_unit_idx, int wiener_win, const uint8_t *dgd, const uint8_t *src,
@@ -704,9 +604,7 @@ int svt_hip_bind_wiener_stats(PictureControlSet *pcs, int plane, int rest_unit_i
         wiener_stats_free(e->st);
         e->st = NULL, e->pcs = pcs, e->picture_number = pcs->picture_number, e->plane = plane, e->state = 1, e->stamp = ++g_wiener_clock;
         pthread_mutex_unlock(&g_wiener_mu);
-        const uint64_t    t0 = hd_now_ns();
         WienerPlaneStats *st = wiener_plane(pcs, plane, wiener_win, dgd, src, dgd_stride, src_stride, highbd, bit_depth);
-        hd_timer_add("wiener_plane", hd_now_ns() - t0);
         pthread_mutex_lock(&g_wiener_mu);
         e->st = st, e->state = st ? 2 : 3;
         pthread_cond_broadcast(&g_wiener_cv);
@@ -725,34 +623,24 @@ int svt_hip_bind_wiener_stats(PictureControlSet *pcs, int plane, int rest_unit_i
     return rc;
 }
 
-static int lr_frame_impl(Yv12BufferConfig *frame, Av1Common *cm, int32_t optimized_lr);
 int svt_hip_bind_lr_frame(Yv12BufferConfig *frame, Av1Common *cm, int32_t optimized_lr) {
     if (!g_lr)
         return 1;
-    const uint64_t t0 = hd_now_ns();
-    const int      rc = lr_frame_impl(frame, cm, optimized_lr);
-    hd_timer_add("lr_frame", hd_now_ns() - t0);
-    return rc;
-}
-static int lr_frame_impl(Yv12BufferConfig *frame, Av1Common *cm, int32_t optimized_lr) {
     PictureControlSet *pcs = cm->child_pcs;
-    if (!g_lr || !pcs || !covered(pcs))
-        return 1;
-    const SequenceControlSet *scs  = pcs->scs;
-    const int                 is16 = scs->is_16bit_pipeline;
-    if (cm->use_highbitdepth != is16)
-        return 1;
+    HdCall             c;
+    hd_call_begin(&c, "lr_frame");
+    if (!pcs || !covered(pcs) || cm->use_highbitdepth != pcs->scs->is_16bit_pipeline)
+        return hd_call_decline(&c);
+    const int            is16 = pcs->scs->is_16bit_pipeline;
     EbPictureBufferDesc *recon;
     svt_aom_get_recon_pic(pcs, &recon, is16);
     PlaneRef rp[3];
     picture_planes(recon, is16, rp);
     SvtHipLrPlane pl[3];
-    int           plane_of[3], n_pl = 0, rc = 0;
-    uint8_t      *d_out[3] = {NULL, NULL, NULL}, *d_units[3] = {NULL, NULL, NULL}, *d_bnd[3] = {NULL, NULL, NULL}, *h_out[3] = {NULL, NULL, NULL};
-    const void   *pinned[3];
-    int           n_pinned = 0;
+    int           plane_of[3], n_pl = 0;
+    uint8_t      *h_out[3] = {NULL, NULL, NULL};
     memset(pl, 0, sizeof(pl));
-    for (int plane = 0; rc == 0 && plane < 3; plane++) {
+    for (int plane = 0; hd_call_ok(&c) && plane < 3; plane++) {
         RestorationInfo *rsi = &pcs->rst_info[plane];
         rsi->optimized_lr    = optimized_lr; /* what the reference's loop sets for every plane (:1207) */
         if (rsi->frame_restoration_type == RESTORE_NONE)
@@ -760,25 +648,16 @@ static int lr_frame_impl(Yv12BufferConfig *frame, Av1Common *cm, int32_t optimiz
         const int      is_uv = plane > 0;
         const uint8_t *buf   = is16 ? (const uint8_t *)CONVERT_TO_SHORTPTR(frame->buffers[plane]) : frame->buffers[plane];
         if (buf != rp[plane].host + rp[plane].origin || (uint32_t)frame->strides[is_uv] != rp[plane].stride) {
-            rc = -1; /* not the picture's reconstruction buffer */
+            hd_call_fail(&c); /* not the picture's reconstruction buffer */
             break;
         }
-        SvtHipLrPlane *o = &pl[n_pl];
-        const int      n = rsi->horz_units_per_tile * rsi->vert_units_per_tile;
-        uint8_t       *d = hd_mirror_get(rp[plane].host, rp[plane].bytes, HD_TAG(pcs->picture_number, HD_ST_CDEF_EXT));
-        if (!d) {
-            rc = -1;
+        SvtHipLrPlane *o     = &pl[n_pl];
+        const int      n     = rsi->horz_units_per_tile * rsi->vert_units_per_tile;
+        uint8_t       *d     = hd_call_mirror(&c, rp[plane].host, rp[plane].bytes, HD_TAG(pcs->picture_number, HD_ST_CDEF_EXT));
+        SvtHipLrUnit  *hu    = (SvtHipLrUnit *)hd_call_host(&c, (size_t)n * sizeof(*hu));
+        uint8_t       *d_out = hd_call_dev(&c, rp[plane].bytes);
+        if (!hd_call_ok(&c))
             break;
-        }
-        pinned[n_pinned++] = rp[plane].host;
-        SvtHipLrUnit *hu   = (SvtHipLrUnit *)calloc(n, sizeof(*hu));
-        d_out[n_pl]        = hd_alloc(rp[plane].bytes + 256);
-        d_units[n_pl]      = hd_alloc((size_t)n * sizeof(*hu) + 256);
-        if (!hu || !d_out[n_pl] || !d_units[n_pl]) {
-            free(hu);
-            rc = -1;
-            break;
-        }
         for (int i = 0; i < n; i++) {
             const RestorationUnitInfo *ui = &rsi->unit_info[i];
             hu[i].restoration_type       = (uint8_t)ui->restoration_type;
@@ -786,45 +665,38 @@ static int lr_frame_impl(Yv12BufferConfig *frame, Av1Common *cm, int32_t optimiz
             memcpy(hu[i].hfilter, ui->wiener_info.hfilter, sizeof(hu[i].hfilter));
             memcpy(hu[i].vfilter, ui->wiener_info.vfilter, sizeof(hu[i].vfilter));
         }
-        rc = hd_upload(d_units[n_pl], hu, (size_t)n * sizeof(*hu));
-        free(hu);
-        if (rc == 0 && !optimized_lr) {
-            const size_t nb = (size_t)rsi->boundaries.stripe_boundary_size;
-            d_bnd[n_pl]     = hd_alloc(2 * nb + 512);
-            rc = d_bnd[n_pl] ? (hd_upload(d_bnd[n_pl], rsi->boundaries.stripe_boundary_above, nb) |
-                                hd_upload(d_bnd[n_pl] + ((nb + 255) & ~(size_t)255), rsi->boundaries.stripe_boundary_below, nb))
-                             : -1;
-            o->boundary_above = d_bnd[n_pl], o->boundary_below = d_bnd[n_pl] ? d_bnd[n_pl] + ((nb + 255) & ~(size_t)255) : NULL;
+        o->units = (const SvtHipLrUnit *)hd_call_dev_put(&c, hu, (size_t)n * sizeof(*hu));
+        if (!optimized_lr) {
+            const size_t nb    = (size_t)rsi->boundaries.stripe_boundary_size;
+            uint8_t     *d_bnd = hd_call_dev(&c, 2 * hd_al256(nb));
+            o->boundary_above = hd_carve(&d_bnd, nb), o->boundary_below = d_bnd;
+            hd_call_upload(&c, (void *)o->boundary_above, rsi->boundaries.stripe_boundary_above, nb);
+            hd_call_upload(&c, (void *)o->boundary_below, rsi->boundaries.stripe_boundary_below, nb);
             o->boundary_stride = (uint32_t)rsi->boundaries.stripe_boundary_stride;
         }
-        o->src = d + rp[plane].origin, o->dst = d_out[n_pl] + rp[plane].origin, o->src_stride = o->dst_stride = rp[plane].stride;
+        o->src = d + rp[plane].origin, o->dst = d_out + rp[plane].origin, o->src_stride = o->dst_stride = rp[plane].stride;
         o->width = (uint32_t)frame->crop_widths[is_uv], o->height = (uint32_t)frame->crop_heights[is_uv];
         o->ss_x = o->ss_y = (uint8_t)is_uv, o->is_16bit = (uint8_t)is16, o->bit_depth = (uint8_t)cm->bit_depth;
         o->unit_size = (uint32_t)rsi->restoration_unit_size, o->horz_units = (uint32_t)rsi->horz_units_per_tile, o->vert_units = (uint32_t)rsi->vert_units_per_tile;
-        o->units = (const SvtHipLrUnit *)d_units[n_pl], o->optimized_lr = (uint32_t)optimized_lr;
+        o->optimized_lr = (uint32_t)optimized_lr;
         plane_of[n_pl++] = plane;
     }
-    if (rc == 0 && n_pl)
-        rc = p_lr_frame(pl, (uint32_t)n_pl, NULL);
+    if (n_pl)
+        HD_CALL(&c, p_svt_hip_restoration_filter_frame(pl, (uint32_t)n_pl, NULL));
     /* only the picture area comes back (copy_funs[plane](dst, frame) copies the cropped plane, :1243) */
-    for (int k = 0; rc == 0 && k < n_pl; k++) {
+    for (int k = 0; k < n_pl; k++) {
         const size_t row = (size_t)pl[k].width << is16;
-        h_out[k]         = (uint8_t *)hd_host_alloc(row * pl[k].height);
-        rc = h_out[k] ? p_download_2d(h_out[k], row, pl[k].dst, (size_t)pl[k].dst_stride << is16, row, pl[k].height, NULL) : -1;
+        h_out[k]         = (uint8_t *)hd_call_pinned(&c, row * pl[k].height);
+        HD_CALL(&c, p_svt_hip_download_2d(h_out[k], row, pl[k].dst, (size_t)pl[k].dst_stride << is16, row, pl[k].height, NULL));
     }
-    rc |= hd_sync();
-    for (int i = 0; i < n_pinned; i++) hd_mirror_unpin(pinned[i]);
-    if (rc == 0)
+    if (hd_call_sync(&c) == 0)
         for (int k = 0; k < n_pl; k++) {
             const PlaneRef *r   = &rp[plane_of[k]];
             const size_t    row = (size_t)pl[k].width << is16;
             for (uint32_t y = 0; y < pl[k].height; y++) memcpy(r->host + r->origin + (((size_t)y * r->stride) << is16), h_out[k] + y * row, row);
         }
-    for (int k = 0; k < 3; k++) hd_free(d_out[k]), hd_free(d_units[k]), hd_free(d_bnd[k]), hd_host_free(h_out[k]);
-    if (rc != 0) {
-        fprintf(stderr, "svt_hip_bind_lf: restoration of picture %llu stays on the CPU (%s)\n", (unsigned long long)pcs->picture_number, hd_error());
+    if (hd_call_end(&c, "svt_hip_bind_lf: restoration of picture %llu stays on the CPU", (unsigned long long)pcs->picture_number))
         return 1;
-    }
     __atomic_add_fetch(&g_n_lr, 1, __ATOMIC_RELAXED);
     return 0;
 }

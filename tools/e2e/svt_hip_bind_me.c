@@ -28,7 +28,7 @@
 #include "svt_hip_bind.h"
 #include "svt_hip_bind_dev.h"
 
-static int32_t (*p_me_frames)(const SvtHipMeFrameJob *, uint32_t, void *);
+HD_FN(svt_hip_me_frames);
 static int           g_active;
 static unsigned long g_pictures, g_blocks; /* statistics, printed at exit */
 
@@ -37,8 +37,8 @@ static void report(void) {
 }
 
 void svt_hip_bind_me_setup(void *(*sym)(const char *)) {
-    p_me_frames = (int32_t(*)(const SvtHipMeFrameJob *, uint32_t, void *))sym("svt_hip_me_frames");
-    g_active    = hd_env_on("SVTAV1_HIP_TIERB_ME") && g_hd.ok && p_me_frames;
+    HD_SYM(sym, svt_hip_me_frames);
+    g_active = hd_env_on("SVTAV1_HIP_TIERB_ME") && g_hd.ok && p_svt_hip_me_frames;
     if (g_active)
         atexit(report);
 }
@@ -125,79 +125,95 @@ void svt_hip_bind_me_params(SvtHipMeParams *out, const PictureParentControlSet *
 }
 
 
-static size_t plane_bytes(const EbPictureBufferDesc *d) { return (size_t)d->stride_y * (d->height + 2u * d->org_y); }
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-/* the device mirror of one luma plane; `pinned` collects the host addresses to unpin after the launch */
-static int get_plane(SvtHipPlane8 *p, const EbPictureBufferDesc *d, uint64_t picture_number, const void **pinned, int *n_pinned) {
+/* the device mirror of one luma plane, pinned until the call ends */
+static void get_plane(HdCall *c, SvtHipPlane8 *p, const EbPictureBufferDesc *d, uint64_t picture_number) {
     p->stride = d->stride_y, p->org_x = d->org_x, p->org_y = d->org_y, p->width = d->width, p->height = d->height;
-    p->buf = hd_mirror_get(d->buffer_y, plane_bytes(d), HD_TAG(picture_number, HD_ST_FILTERED));
-    if (!p->buf)
-        return -1;
-    pinned[(*n_pinned)++] = d->buffer_y;
-    return 0;
+    p->buf = hd_call_mirror(c, d->buffer_y, hd_luma_bytes(d), HD_TAG(picture_number, HD_ST_FILTERED));
 }
 
-static PicResults *compute_picture(PictureParentControlSet *pcs, MeContext *me, EbPictureBufferDesc *full, EbPictureBufferDesc *quarter,
-                                   EbPictureBufferDesc *sixteenth) {
-    SvtHipMeFrameJob *job = (SvtHipMeFrameJob *)calloc(1, sizeof(*job));
-    PicResults       *e   = (PicResults *)calloc(1, sizeof(*e));
+typedef struct MeArgs {
+    PictureParentControlSet *pcs;
+    uint32_t                 b64_index;
+    MeContext               *me;
+    EbPictureBufferDesc     *full, *quarter, *sixteenth;
+} MeArgs;
+
+/* the first block of a picture that arrives searches all of it (hd_once_run); the payload is the picture's PicResults */
+static int compute_picture(void *arg, void **payload) {
+    const MeArgs            *a   = (const MeArgs *)arg;
+    PictureParentControlSet *pcs = a->pcs;
+    HdCall                   c;
+    hd_call_begin(&c, "me_picture");
+    SvtHipMeFrameJob *job = (SvtHipMeFrameJob *)hd_call_host(&c, sizeof(*job));
+    PicResults       *e   = (PicResults *)calloc(1, sizeof(*e)); /* outlives the call: plain heap (results_free) */
     if (!job || !e) {
-        free(job), free(e);
-        return NULL;
+        free(e);
+        return !hd_call_decline(&c);
     }
-    svt_hip_bind_me_params(&job->prm, pcs, me);
+    svt_hip_bind_me_params(&job->prm, pcs, a->me);
     const SvtHipMeParams *p = &job->prm;
     const uint32_t nb = pcs->b64_total_count, stored = svt_hip_me_stored_pus(p);
     e->stored = stored, e->max_refs = p->max_refs, e->max_cand = p->max_cand;
     const size_t n_mv = (size_t)nb * stored * p->max_refs * 4, n_cand = (size_t)nb * stored * p->max_cand, n_cnt = (size_t)nb * stored;
     const size_t n_best = (size_t)nb * 2 * 4 * 85 * 4, n_sr = (size_t)nb * 8 * sizeof(SvtHipMeSearchResult), n_d = (size_t)nb * 4;
-    const void  *pinned[3 + 3 * SVT_HIP_ME_MAX_LIST * SVT_HIP_ME_MAX_REF];
-    int          n_pinned = 0;
-    int          rc = get_plane(&job->src.full, full, pcs->picture_number, pinned, &n_pinned) |
-        get_plane(&job->src.quarter, quarter, pcs->picture_number, pinned, &n_pinned) |
-        get_plane(&job->src.sixteenth, sixteenth, pcs->picture_number, pinned, &n_pinned);
-    for (int l = 0; rc == 0 && l < p->num_of_list_to_search; l++)
-        for (int r = 0; rc == 0 && r < p->num_of_ref_pic_to_search[l]; r++) {
-            const EbDownScaledBufDescPtrArray *a = &me->me_ds_ref_array[l][r];
-            rc = get_plane(&job->ref[l][r].full, a->picture_ptr, a->picture_number, pinned, &n_pinned) |
-                get_plane(&job->ref[l][r].quarter, a->quarter_picture_ptr, a->picture_number, pinned, &n_pinned) |
-                get_plane(&job->ref[l][r].sixteenth, a->sixteenth_picture_ptr, a->picture_number, pinned, &n_pinned);
+    get_plane(&c, &job->src.full, a->full, pcs->picture_number);
+    get_plane(&c, &job->src.quarter, a->quarter, pcs->picture_number);
+    get_plane(&c, &job->src.sixteenth, a->sixteenth, pcs->picture_number);
+    for (int l = 0; l < p->num_of_list_to_search; l++)
+        for (int r = 0; r < p->num_of_ref_pic_to_search[l]; r++) {
+            const EbDownScaledBufDescPtrArray *ds = &a->me->me_ds_ref_array[l][r];
+            get_plane(&c, &job->ref[l][r].full, ds->picture_ptr, ds->picture_number);
+            get_plane(&c, &job->ref[l][r].quarter, ds->quarter_picture_ptr, ds->picture_number);
+            get_plane(&c, &job->ref[l][r].sixteenth, ds->sixteenth_picture_ptr, ds->picture_number);
         }
-    uint8_t *dev = rc == 0 ? hd_alloc(al256(n_mv) + al256(n_cand) + al256(n_cnt) + 2 * al256(n_best) + al256(n_sr) + 6 * al256(n_d)) : NULL;
-    if (rc == 0 && !dev)
-        rc = -1;
-    uint8_t *d_mv = dev, *d_cand = d_mv + al256(n_mv), *d_cnt = d_cand + al256(n_cand), *d_bs = d_cnt + al256(n_cnt);
-    uint8_t *d_bm = d_bs + al256(n_best), *d_sr = d_bm + al256(n_best), *d_dist = d_sr + al256(n_sr);
-    if (rc == 0) {
-        SvtHipMeFrameOut *o = &job->out;
-        o->me_mv_array = (uint32_t *)d_mv, o->me_candidate_array = d_cand, o->total_me_candidate_index = d_cnt;
-        o->best_sad = (uint32_t *)d_bs, o->best_mv = (uint32_t *)d_bm, o->search_results = (SvtHipMeSearchResult *)d_sr;
-        uint32_t **dd[6] = {&o->me_64x64_distortion, &o->me_32x32_distortion, &o->me_16x16_distortion, &o->me_8x8_distortion,
-                            &o->me_8x8_cost_variance, &o->rc_me_distortion};
-        for (int i = 0; i < 6; i++) *dd[i] = (uint32_t *)(d_dist + i * al256(n_d));
-        rc = p_me_frames(job, 1, NULL);
-    }
-    if (rc == 0) {
-        e->mv = (uint32_t *)malloc(n_mv), e->cand = (uint8_t *)malloc(n_cand), e->cnt = (uint8_t *)malloc(n_cnt);
-        for (int i = 0; i < 6; i++) e->dist[i] = (uint32_t *)malloc(n_d);
-        rc = hd_download(e->mv, d_mv, n_mv) | hd_download(e->cand, d_cand, n_cand) | hd_download(e->cnt, d_cnt, n_cnt);
-        for (int i = 0; i < 6; i++) rc |= hd_download(e->dist[i], d_dist + i * al256(n_d), n_d);
-        rc |= hd_sync();
-    } else {
-        hd_sync();
-    }
-    for (int i = 0; i < n_pinned; i++) hd_mirror_unpin(pinned[i]);
-    if (rc != 0)
-        fprintf(stderr, "svt_hip_bind_me: picture %llu falls back to the CPU search (%s)\n", (unsigned long long)pcs->picture_number, hd_error());
-    hd_free(dev);
-    free(job);
-    if (rc != 0) {
+    uint8_t *dev = hd_call_dev(&c, hd_al256(n_mv) + hd_al256(n_cand) + hd_al256(n_cnt) + 2 * hd_al256(n_best) + hd_al256(n_sr) + 6 * hd_al256(n_d));
+    uint8_t *d_mv = hd_carve(&dev, n_mv), *d_cand = hd_carve(&dev, n_cand), *d_cnt = hd_carve(&dev, n_cnt), *d_dist[6];
+    SvtHipMeFrameOut *o = &job->out;
+    o->me_mv_array = (uint32_t *)d_mv, o->me_candidate_array = d_cand, o->total_me_candidate_index = d_cnt;
+    o->best_sad = (uint32_t *)hd_carve(&dev, n_best), o->best_mv = (uint32_t *)hd_carve(&dev, n_best);
+    o->search_results = (SvtHipMeSearchResult *)hd_carve(&dev, n_sr);
+    uint32_t **dd[6] = {&o->me_64x64_distortion, &o->me_32x32_distortion, &o->me_16x16_distortion, &o->me_8x8_distortion,
+                        &o->me_8x8_cost_variance, &o->rc_me_distortion};
+    for (int i = 0; i < 6; i++) *dd[i] = (uint32_t *)(d_dist[i] = hd_carve(&dev, n_d));
+    HD_CALL(&c, p_svt_hip_me_frames(job, 1, NULL));
+    /* (a download into a block that could not be allocated makes the call fail) */
+    e->mv = (uint32_t *)malloc(n_mv), e->cand = (uint8_t *)malloc(n_cand), e->cnt = (uint8_t *)malloc(n_cnt);
+    for (int i = 0; i < 6; i++) e->dist[i] = (uint32_t *)malloc(n_d);
+    hd_call_download(&c, e->mv, d_mv, n_mv);
+    hd_call_download(&c, e->cand, d_cand, n_cand);
+    hd_call_download(&c, e->cnt, d_cnt, n_cnt);
+    for (int i = 0; i < 6; i++) hd_call_download(&c, e->dist[i], d_dist[i], n_d);
+    hd_call_sync(&c);
+    if (hd_call_end(&c, "svt_hip_bind_me: picture %llu falls back to the CPU search", (unsigned long long)pcs->picture_number)) {
         results_free(e);
-        return NULL;
+        return 0;
     }
     hd_count_picture();
-    return e;
+    __atomic_add_fetch(&g_pictures, 1, __ATOMIC_RELAXED);
+    *payload = e;
+    return 1;
+}
+
+/* every block of the picture copies its own results out of the picture's */
+static void take_block(void *arg, const void *payload) {
+    const MeArgs            *a         = (const MeArgs *)arg;
+    PictureParentControlSet *pcs       = a->pcs;
+    const uint32_t           b64_index = a->b64_index;
+    const PicResults        *e         = (const PicResults *)payload;
+    MeSbResults             *res       = pcs->pa_me_data->me_results[b64_index];
+    memcpy(res->me_mv_array, e->mv + (size_t)b64_index * e->stored * e->max_refs, (size_t)e->stored * e->max_refs * 4);
+    memcpy(res->me_candidate_array, e->cand + (size_t)b64_index * e->stored * e->max_cand, (size_t)e->stored * e->max_cand);
+    memcpy(res->total_me_candidate_index, e->cnt + (size_t)b64_index * e->stored, e->stored);
+    pcs->me_64x64_distortion[b64_index]  = e->dist[0][b64_index];
+    pcs->me_32x32_distortion[b64_index]  = e->dist[1][b64_index];
+    pcs->me_16x16_distortion[b64_index]  = e->dist[2][b64_index];
+    pcs->me_8x8_distortion[b64_index]    = e->dist[3][b64_index];
+    pcs->me_8x8_cost_variance[b64_index] = e->dist[4][b64_index];
+    pcs->rc_me_distortion[b64_index]     = e->dist[5][b64_index];
+    /* the tail of svt_aom_motion_estimation_b64 with global motion off (motion_estimation.c:3213-3215) */
+    pcs->stationary_block_present_sb[b64_index] = 0;
+    pcs->rc_me_allow_gm[b64_index]              = 0;
+    __atomic_add_fetch(&g_blocks, 1, __ATOMIC_RELAXED);
 }
 
 /* Returns 0 when block b64_index of the picture has been filled in from the GPU results, 1 when the caller must run the
@@ -206,36 +222,6 @@ int svt_hip_bind_me_b64(PictureParentControlSet *pcs, uint32_t b64_index, MeCont
                         EbPictureBufferDesc *sixteenth) {
     if (!g_active || me->me_type != ME_OPEN_LOOP || pcs->gm_ctrls.enabled || pcs->frame_superres_enabled || pcs->frame_resize_enabled)
         return 1;
-    int     first;
-    HdOnce *once = hd_once_enter(&g_tab, pcs, pcs->picture_number, pcs->b64_total_count, &first);
-    if (!once)
-        return 1;
-    if (first) {
-        const uint64_t t0 = hd_now_ns();
-        PicResults    *r  = compute_picture(pcs, me, full, quarter, sixteenth);
-        hd_timer_add("me_picture", hd_now_ns() - t0);
-        if (r)
-            __atomic_add_fetch(&g_pictures, 1, __ATOMIC_RELAXED);
-        hd_once_done(once, r != NULL, r);
-    }
-    const int ok = hd_once_ok(once);
-    if (ok) {
-        const PicResults *e   = (const PicResults *)hd_once_payload(once);
-        MeSbResults      *res = pcs->pa_me_data->me_results[b64_index];
-        memcpy(res->me_mv_array, e->mv + (size_t)b64_index * e->stored * e->max_refs, (size_t)e->stored * e->max_refs * 4);
-        memcpy(res->me_candidate_array, e->cand + (size_t)b64_index * e->stored * e->max_cand, (size_t)e->stored * e->max_cand);
-        memcpy(res->total_me_candidate_index, e->cnt + (size_t)b64_index * e->stored, e->stored);
-        pcs->me_64x64_distortion[b64_index]  = e->dist[0][b64_index];
-        pcs->me_32x32_distortion[b64_index]  = e->dist[1][b64_index];
-        pcs->me_16x16_distortion[b64_index]  = e->dist[2][b64_index];
-        pcs->me_8x8_distortion[b64_index]    = e->dist[3][b64_index];
-        pcs->me_8x8_cost_variance[b64_index] = e->dist[4][b64_index];
-        pcs->rc_me_distortion[b64_index]     = e->dist[5][b64_index];
-        /* the tail of svt_aom_motion_estimation_b64 with global motion off (motion_estimation.c:3213-3215) */
-        pcs->stationary_block_present_sb[b64_index] = 0;
-        pcs->rc_me_allow_gm[b64_index]              = 0;
-        __atomic_add_fetch(&g_blocks, 1, __ATOMIC_RELAXED);
-    }
-    hd_once_release(&g_tab, once, results_free);
-    return ok ? 0 : 1;
+    MeArgs a = {pcs, b64_index, me, full, quarter, sixteenth};
+    return hd_once_run(&g_tab, pcs, pcs->picture_number, pcs->b64_total_count, compute_picture, take_block, results_free, &a) != 0;
 }

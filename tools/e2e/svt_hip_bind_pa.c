@@ -28,8 +28,8 @@
 #include "svt_hip_bind.h"
 #include "svt_hip_bind_dev.h"
 
-static int32_t (*p_pyramid)(const SvtHipPlane8 *, const SvtHipPlane8 *, const SvtHipPlane8 *, int32_t, void *);
-static int32_t (*p_variance)(const SvtHipPlane8 *, uint16_t *, uint64_t *, int32_t, void *);
+HD_FN(svt_hip_pyramid_frame);
+HD_FN(svt_hip_variance_frame);
 static int           g_active;
 static unsigned long g_n_pyr, g_n_var;
 
@@ -38,15 +38,13 @@ static void report(void) {
 }
 
 void svt_hip_bind_pa_setup(void *(*sym)(const char *)) {
-    p_pyramid  = (int32_t(*)(const SvtHipPlane8 *, const SvtHipPlane8 *, const SvtHipPlane8 *, int32_t, void *))sym("svt_hip_pyramid_frame");
-    p_variance = (int32_t(*)(const SvtHipPlane8 *, uint16_t *, uint64_t *, int32_t, void *))sym("svt_hip_variance_frame");
-    g_active   = hd_env_on("SVTAV1_HIP_TIERB_PA") && g_hd.ok && p_pyramid && p_variance;
+    HD_SYM(sym, svt_hip_pyramid_frame), HD_SYM(sym, svt_hip_variance_frame);
+    g_active = hd_env_on("SVTAV1_HIP_TIERB_PA") && g_hd.ok && p_svt_hip_pyramid_frame && p_svt_hip_variance_frame;
     if (g_active)
         atexit(report);
 }
 
-static size_t plane_bytes(const EbPictureBufferDesc *d) { return (size_t)d->stride_y * (d->height + 2u * d->org_y); }
-static void   plane_of(SvtHipPlane8 *p, const EbPictureBufferDesc *d, uint8_t *dev) {
+static void plane_of(SvtHipPlane8 *p, const EbPictureBufferDesc *d, uint8_t *dev) {
     p->buf = dev, p->stride = d->stride_y, p->org_x = d->org_x, p->org_y = d->org_y, p->width = d->width, p->height = d->height;
 }
 /* paddings the library asks for (include/svt_hip_me.h: >= 64 / 32 / 16, the decimated planes exactly half / a quarter) */
@@ -56,110 +54,71 @@ static int geometry_ok(const EbPictureBufferDesc *f, const EbPictureBufferDesc *
         q->height == f->height >> 1 && s->width == f->width >> 2 && s->height == f->height >> 2;
 }
 
-static int pa_pyramid_impl(PictureParentControlSet *pcs, EbPictureBufferDesc *full, EbPictureBufferDesc *quarter, EbPictureBufferDesc *sixteenth);
 int svt_hip_bind_pa_pyramid(PictureParentControlSet *pcs, EbPictureBufferDesc *full, EbPictureBufferDesc *quarter, EbPictureBufferDesc *sixteenth) {
     if (!g_active)
         return 1;
-    const uint64_t t0 = hd_now_ns();
-    const int      rc = pa_pyramid_impl(pcs, full, quarter, sixteenth);
-    hd_timer_add("pa_pyramid", hd_now_ns() - t0);
-    return rc;
-}
-static int pa_pyramid_impl(PictureParentControlSet *pcs, EbPictureBufferDesc *full, EbPictureBufferDesc *quarter, EbPictureBufferDesc *sixteenth) {
-    if (!g_active || !(pcs->enable_hme_flag || pcs->tf_enable_hme_flag) || !(pcs->enable_hme_level0_flag || pcs->tf_enable_hme_level0_flag) ||
+    HdCall c;
+    hd_call_begin(&c, "pa_pyramid");
+    if (!(pcs->enable_hme_flag || pcs->tf_enable_hme_flag) || !(pcs->enable_hme_level0_flag || pcs->tf_enable_hme_level0_flag) ||
         !geometry_ok(full, quarter, sixteenth))
-        return 1;
+        return hd_call_decline(&c);
     const int      level1 = pcs->enable_hme_level1_flag || pcs->tf_enable_hme_level1_flag;
     const uint64_t tag    = HD_TAG(pcs->picture_number, HD_ST_FILTERED);
-    const size_t   nq = plane_bytes(quarter), ns = plane_bytes(sixteenth);
+    const size_t   nq = hd_luma_bytes(quarter), ns = hd_luma_bytes(sixteenth);
     const uint64_t t_a = hd_now_ns();
-    uint8_t       *d_f = hd_mirror_get(full->buffer_y, plane_bytes(full), tag);
-    if (!d_f)
-        return 1;
+    uint8_t       *d_f = hd_call_mirror(&c, full->buffer_y, hd_luma_bytes(full), tag);
     hd_timer_add("pa_pyramid.1_source_mirror", hd_now_ns() - t_a);
     const uint64_t t_b = hd_now_ns();
-    /* the decimated planes are produced on the device: their buffers become the mirrors of the host planes */
-    uint8_t *d_q = level1 ? hd_mirror_new(quarter->buffer_y, nq, tag) : hd_alloc(nq + 256);
-    uint8_t *d_s = hd_mirror_new(sixteenth->buffer_y, ns, tag);
-    uint8_t *h_q = level1 ? (uint8_t *)hd_host_alloc(nq) : NULL, *h_s = (uint8_t *)hd_host_alloc(ns);
-    int      rc  = (d_q && d_s && h_s && (h_q || !level1)) ? 0 : -1;
+    /* the decimated planes are produced on the device: their buffers become the mirrors of the host planes (a failed call drops them) */
+    uint8_t *d_q = level1 ? hd_call_mirror_new(&c, quarter->buffer_y, nq, tag) : hd_call_dev(&c, nq);
+    uint8_t *d_s = hd_call_mirror_new(&c, sixteenth->buffer_y, ns, tag);
+    uint8_t *h_q = level1 ? (uint8_t *)hd_call_pinned(&c, nq) : NULL, *h_s = (uint8_t *)hd_call_pinned(&c, ns);
     hd_timer_add("pa_pyramid.2_alloc", hd_now_ns() - t_b);
     const uint64_t t_c = hd_now_ns();
-    if (rc == 0) {
-        SvtHipPlane8 pf, pq, ps;
-        plane_of(&pf, full, d_f), plane_of(&pq, quarter, d_q), plane_of(&ps, sixteenth, d_s);
-        /* a plane keeps the bytes the kernel does not write (row tails behind the padding): start from the host's */
-        rc = (level1 ? hd_upload(d_q, quarter->buffer_y, nq) : 0) | hd_upload(d_s, sixteenth->buffer_y, ns);
-        if (rc == 0)
-            rc = p_pyramid(&pf, &pq, &ps, level1, NULL);
-        if (rc == 0)
-            rc = (level1 ? hd_download(h_q, d_q, nq) : 0) | hd_download(h_s, d_s, ns);
-    }
-    rc |= hd_sync();
+    SvtHipPlane8   pf, pq, ps;
+    plane_of(&pf, full, d_f), plane_of(&pq, quarter, d_q), plane_of(&ps, sixteenth, d_s);
+    /* a plane keeps the bytes the kernel does not write (row tails behind the padding): start from the host's */
+    if (level1)
+        hd_call_upload(&c, d_q, quarter->buffer_y, nq);
+    hd_call_upload(&c, d_s, sixteenth->buffer_y, ns);
+    HD_CALL(&c, p_svt_hip_pyramid_frame(&pf, &pq, &ps, level1, NULL));
+    if (level1)
+        hd_call_download(&c, h_q, d_q, nq);
+    hd_call_download(&c, h_s, d_s, ns);
+    const int arrived = hd_call_sync(&c) == 0;
     hd_timer_add("pa_pyramid.3_upload_kernel_download", hd_now_ns() - t_c);
     const uint64_t t_d = hd_now_ns();
-    if (rc == 0) {
+    if (arrived) {
         if (level1)
             memcpy(quarter->buffer_y, h_q, nq);
         memcpy(sixteenth->buffer_y, h_s, ns);
     }
     hd_timer_add("pa_pyramid.4_copy_out", hd_now_ns() - t_d);
-    hd_mirror_unpin(full->buffer_y);
-    if (level1 && d_q) {
-        if (rc != 0)
-            hd_mirror_drop(quarter->buffer_y);
-        hd_mirror_unpin(quarter->buffer_y);
-    } else if (!level1) {
-        hd_free(d_q);
-    }
-    if (d_s) {
-        if (rc != 0)
-            hd_mirror_drop(sixteenth->buffer_y);
-        hd_mirror_unpin(sixteenth->buffer_y);
-    }
-    hd_host_free(h_q), hd_host_free(h_s);
-    if (rc != 0) {
-        fprintf(stderr, "svt_hip_bind_pa: pyramid of picture %llu stays on the CPU (%s)\n", (unsigned long long)pcs->picture_number, hd_error());
+    if (hd_call_end(&c, "svt_hip_bind_pa: pyramid of picture %llu stays on the CPU", (unsigned long long)pcs->picture_number))
         return 1;
-    }
     __atomic_add_fetch(&g_n_pyr, 1, __ATOMIC_RELAXED);
     hd_count_picture();
     return 0;
 }
 
-static int pa_variance_impl(SequenceControlSet *scs, PictureParentControlSet *pcs, EbPictureBufferDesc *full);
 int svt_hip_bind_pa_variance(SequenceControlSet *scs, PictureParentControlSet *pcs, EbPictureBufferDesc *full) {
     if (!g_active)
         return 1;
-    const uint64_t t0 = hd_now_ns();
-    const int      rc = pa_variance_impl(scs, pcs, full);
-    hd_timer_add("pa_variance", hd_now_ns() - t0);
-    return rc;
-}
-static int pa_variance_impl(SequenceControlSet *scs, PictureParentControlSet *pcs, EbPictureBufferDesc *full) {
-    if (!g_active || full->org_x < 64 || full->org_y < 64)
-        return 1;
+    HdCall c;
+    hd_call_begin(&c, "pa_variance");
     const uint32_t nb = pcs->b64_total_count;
-    if (nb != ((uint32_t)(pcs->aligned_width + 63) / 64) * ((uint32_t)(pcs->aligned_height + 63) / 64))
-        return 1;
-    uint8_t *d_f = hd_mirror_get(full->buffer_y, plane_bytes(full), HD_TAG(pcs->picture_number, HD_ST_FILTERED));
-    if (!d_f)
-        return 1;
+    if (full->org_x < 64 || full->org_y < 64 || nb != ((uint32_t)(pcs->aligned_width + 63) / 64) * ((uint32_t)(pcs->aligned_height + 63) / 64))
+        return hd_call_decline(&c);
     const size_t n   = (size_t)nb * 85 * sizeof(uint16_t);
-    uint8_t     *dev = hd_alloc(n + 256);
-    uint16_t    *h   = (uint16_t *)malloc(n);
-    int          rc  = (dev && h) ? 0 : -1;
-    if (rc == 0) {
-        SvtHipPlane8 pf;
-        plane_of(&pf, full, d_f);
-        pf.width = pcs->aligned_width, pf.height = pcs->aligned_height; /* the b64 grid of the reference's loop (b64_geom) */
-        rc = p_variance(&pf, (uint16_t *)dev, NULL, scs->block_mean_calc_prec == BLOCK_MEAN_PREC_FULL, NULL);
-    }
-    if (rc == 0)
-        rc = hd_download(h, dev, n);
-    rc |= hd_sync();
-    hd_mirror_unpin(full->buffer_y);
-    if (rc == 0) {
+    uint8_t     *d_f = hd_call_mirror(&c, full->buffer_y, hd_luma_bytes(full), HD_TAG(pcs->picture_number, HD_ST_FILTERED));
+    uint8_t     *dev = hd_call_dev(&c, n);
+    uint16_t    *h   = (uint16_t *)hd_call_host(&c, n);
+    SvtHipPlane8 pf;
+    plane_of(&pf, full, d_f);
+    pf.width = pcs->aligned_width, pf.height = pcs->aligned_height; /* the b64 grid of the reference's loop (b64_geom) */
+    HD_CALL(&c, p_svt_hip_variance_frame(&pf, (uint16_t *)dev, NULL, scs->block_mean_calc_prec == BLOCK_MEAN_PREC_FULL, NULL));
+    hd_call_download(&c, h, dev, n);
+    if (hd_call_sync(&c) == 0) {
         /* what compute_block_mean_compute_variance stores (:1111-1380): all 85 with adaptive quantisation 1 or variance_octile, else
          * only the 64x64 entry; then the picture average (:1547-1550) */
         const int all       = scs->static_config.enable_adaptive_quantization == 1 || scs->static_config.variance_octile;
@@ -173,11 +132,8 @@ static int pa_variance_impl(SequenceControlSet *scs, PictureParentControlSet *pc
         }
         pcs->pic_avg_variance = (uint16_t)(pic_total / nb);
     }
-    hd_free(dev), free(h);
-    if (rc != 0) {
-        fprintf(stderr, "svt_hip_bind_pa: variance of picture %llu stays on the CPU (%s)\n", (unsigned long long)pcs->picture_number, hd_error());
+    if (hd_call_end(&c, "svt_hip_bind_pa: variance of picture %llu stays on the CPU", (unsigned long long)pcs->picture_number))
         return 1;
-    }
     __atomic_add_fetch(&g_n_var, 1, __ATOMIC_RELAXED);
     return 0;
 }

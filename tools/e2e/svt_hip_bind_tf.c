@@ -27,8 +27,8 @@
 #include "svt_hip_bind.h"
 #include "svt_hip_bind_dev.h"
 
-static int32_t (*p_tf_picture)(const SvtHipTfPictureJob *, void *);
-static uint64_t (*p_tf_ws_bytes)(uint32_t, uint32_t, uint32_t);
+HD_FN(svt_hip_tf_filter_picture);
+HD_FN(svt_hip_tf_workspace_bytes);
 static int           g_active;
 static unsigned long g_pictures, g_pictures_ld;
 static __thread int  t_low_delay; /* the variant the calling thread is in (svt_hip_bind_tf_picture_ld) */
@@ -40,77 +40,48 @@ static void report(void) {
 }
 
 void svt_hip_bind_tf_setup(void *(*sym)(const char *)) {
-    p_tf_picture  = (int32_t(*)(const SvtHipTfPictureJob *, void *))sym("svt_hip_tf_filter_picture");
-    p_tf_ws_bytes = (uint64_t(*)(uint32_t, uint32_t, uint32_t))sym("svt_hip_tf_workspace_bytes");
-    g_active      = hd_env_on("SVTAV1_HIP_TIERB_TF") && g_hd.ok && p_tf_picture && p_tf_ws_bytes;
+    HD_SYM(sym, svt_hip_tf_filter_picture), HD_SYM(sym, svt_hip_tf_workspace_bytes);
+    g_active = hd_env_on("SVTAV1_HIP_TIERB_TF") && g_hd.ok && p_svt_hip_tf_filter_picture && p_svt_hip_tf_workspace_bytes;
     if (g_active)
         atexit(report);
 }
 
 static HdOnceTable g_tab;
-static size_t      al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 /* device copies of one picture of the window */
 typedef struct DevPic {
     SvtHipTfPic pic;
-    uint8_t    *d_luma8, *d_c8[2], *d_hbd[3]; /* d_hbd: scratch owned by this struct; the 8-bit planes are mirrors */
+    uint8_t    *d_hbd[3]; /* scratch; the 8-bit planes are mirrors */
     size_t      n_luma8, n_c8, n_hbd_y, n_hbd_c;
-    const void *pinned[5];
-    int         n_pinned;
 } DevPic;
 
-static uint8_t *mirror(DevPic *dp, const void *host, size_t n, uint64_t picture_number) {
-    uint8_t *d = hd_mirror_get(host, n, HD_TAG(picture_number, HD_ST_FILTERED));
-    if (d)
-        dp->pinned[dp->n_pinned++] = host;
-    return d;
-}
-
 /* 8-bit luma pyramid (the picture + its pa reference object's decimations) and 8-bit chroma from the mirrors -- "FILTERED" stands
- * for "what the buffer holds until this picture's own temporal filter rewrites it" (release_picture_mirrors); the packed 16-bit
+ * for "what the buffer holds until this picture's own temporal filter rewrites it" (drop_picture_mirrors); the packed 16-bit
  * planes are per-call temporaries of the reference (altref_buffer_highbd) and go through scratch memory. */
-static int put_picture(DevPic *dp, PictureParentControlSet *pcs, EbPictureBufferDesc *pic, int is_highbd, int chroma, int scratch_8bit) {
+static void put_picture(HdCall *c, DevPic *dp, PictureParentControlSet *pcs, EbPictureBufferDesc *pic, int is_highbd, int chroma, int scratch_8bit) {
     EbPaReferenceObject *pa = (EbPaReferenceObject *)pcs->pa_ref_pic_wrapper->object_ptr;
     EbPictureBufferDesc *pl[3] = {pic, pa->quarter_downsampled_picture_ptr, pa->sixteenth_downsampled_picture_ptr};
     SvtHipPlane8        *dst[3] = {&dp->pic.pyr.full, &dp->pic.pyr.quarter, &dp->pic.pyr.sixteenth};
+    const uint64_t       tag = HD_TAG(pcs->picture_number, HD_ST_FILTERED);
     memset(dp, 0, sizeof(*dp));
     for (int k = 0; k < 3; k++) {
-        const size_t n = (size_t)pl[k]->stride_y * (pl[k]->height + 2u * pl[k]->org_y);
         dst[k]->stride = pl[k]->stride_y, dst[k]->org_x = pl[k]->org_x, dst[k]->org_y = pl[k]->org_y;
         dst[k]->width = pl[k]->width, dst[k]->height = pl[k]->height;
-        if (k == 0)
-            dp->n_luma8 = n;
         if (k == 0 && scratch_8bit) /* the centre picture of an 8-bit filter: the caller supplies a scratch copy (filtered in place) */
             continue;
-        if (!(dst[k]->buf = mirror(dp, pl[k]->buffer_y, n, pcs->picture_number)))
-            return -1;
-        if (k == 0)
-            dp->d_luma8 = dst[k]->buf;
+        dst[k]->buf = hd_call_mirror(c, pl[k]->buffer_y, hd_luma_bytes(pl[k]), tag);
     }
+    dp->n_luma8            = hd_luma_bytes(pic);
     dp->pic.chroma8_stride = pic->stride_cb;
     dp->n_c8               = (size_t)pic->stride_cb * ((pic->height + 2u * pic->org_y) >> 1);
     if (chroma && !is_highbd && !scratch_8bit)
-        for (int c = 0; c < 2; c++)
-            if (!(dp->d_c8[c] = dp->pic.chroma8[c] = mirror(dp, c ? pic->buffer_cr : pic->buffer_cb, dp->n_c8, pcs->picture_number)))
-                return -1;
+        for (int k = 0; k < 2; k++) dp->pic.chroma8[k] = hd_call_mirror(c, k ? pic->buffer_cr : pic->buffer_cb, dp->n_c8, tag);
     if (is_highbd) {
-        dp->n_hbd_y = (size_t)pic->stride_y * (pic->height + 2u * pic->org_y) * 2, dp->n_hbd_c = dp->n_c8 * 2;
-        for (int c = 0; c < (chroma ? 3 : 1); c++) {
-            const size_t n = c ? dp->n_hbd_c : dp->n_hbd_y;
-            if (!(dp->d_hbd[c] = hd_alloc(n + 256)))
-                return -1;
-            dp->pic.hbd[c] = (uint16_t *)dp->d_hbd[c];
-            if (hd_upload(dp->d_hbd[c], pcs->altref_buffer_highbd[c], n) != 0)
-                return -1;
-        }
+        dp->n_hbd_y = dp->n_luma8 * 2, dp->n_hbd_c = dp->n_c8 * 2;
+        for (int k = 0; k < (chroma ? 3 : 1); k++)
+            dp->pic.hbd[k] = (uint16_t *)(dp->d_hbd[k] = hd_call_dev_put(c, pcs->altref_buffer_highbd[k], k ? dp->n_hbd_c : dp->n_hbd_y));
     }
     dp->pic.picture_number = pcs->picture_number;
-    return 0;
-}
-static void release_picture(DevPic *dp) {
-    for (int i = 0; i < dp->n_pinned; i++) hd_mirror_unpin(dp->pinned[i]);
-    for (int c = 0; c < 3; c++) hd_free(dp->d_hbd[c]);
-    dp->n_pinned = 0;
 }
 
 /* The temporal filter is about to rewrite (or has rewritten) the centre picture: its source planes and, right behind the block
@@ -128,12 +99,11 @@ static int run_picture(PictureParentControlSet **pcs_list, EbPictureBufferDesc *
     SequenceControlSet      *scs    = centre->scs;
     EbPictureBufferDesc     *cpic   = pics[index_center];
     const TfControls        *tc     = &ctx->tf_ctrls;
+    HdCall                   c;
+    hd_call_begin(&c, "tf_picture");
     if ((tc->enable_8x8_pred && !centre->enable_me_8x8) /* tf_8x8_sub_pel_search starts from the ME's 8x8 vectors */ || scs->subsampling_x != 1 || scs->subsampling_y != 1 || cpic->width < 64 || cpic->height < 64 || cpic->org_x < 68 ||
         cpic->org_y < 68 || cpic->stride_cb * 2 != cpic->stride_y || (is_highbd && scs->static_config.encoder_bit_depth != 10))
-        return 1;
-    SvtHipTfPictureJob *job = (SvtHipTfPictureJob *)calloc(1, sizeof(*job));
-    if (!job)
-        return 1;
+        return hd_call_decline(&c);
     /* the pictures filtered against, in the reference's order, with its outlier tests (temporal_filtering.c:2990-3030) */
     int       idx[ALTREF_MAX_NFRAMES], n = 0;
     const int start[3] = {0, centre->past_altref_nframes, centre->past_altref_nframes + 1};
@@ -157,10 +127,11 @@ static int run_picture(PictureParentControlSet **pcs_list, EbPictureBufferDesc *
                 continue;
             idx[n++] = fi;
         }
-    if (n == 0 || n > SVT_HIP_TF_MAX_REFS) {
-        free(job);
-        return 1; /* nothing to filter against: the reference's loop does central + normalise, which leaves the picture as it is */
-    }
+    if (n == 0 || n > SVT_HIP_TF_MAX_REFS)
+        return hd_call_decline(&c); /* nothing to filter against: the reference's loop does central + normalise, which leaves the picture as it is */
+    SvtHipTfPictureJob *job = (SvtHipTfPictureJob *)hd_call_host(&c, sizeof(*job));
+    if (!job)
+        return hd_call_end(&c, "svt_hip_bind_tf: picture %llu stays on the CPU", (unsigned long long)centre->picture_number);
     /* ME parameters: the MeContext as svt_aom_sig_deriv_me_tf left it + what create_me_context_and_picture_control and the frame loop set */
     svt_hip_bind_me_params(&job->me, centre, ctx);
     job->me.me_mctf = 1, job->me.hme_search_method = 1, job->me.tf_me_exit_th = (uint16_t)tc->me_exit_th;
@@ -183,85 +154,84 @@ static int run_picture(PictureParentControlSet **pcs_list, EbPictureBufferDesc *
     job->mv_dist_th = ctx->tf_mv_dist_th, job->chroma = ctx->tf_chroma, job->bit_depth = is_highbd ? 10 : 8;
     job->mi_rows = (uint32_t)centre->av1_cm->mi_rows, job->mi_cols = (uint32_t)centre->av1_cm->mi_cols, job->n_refs = (uint32_t)n;
 
-    const uint64_t wsb = p_tf_ws_bytes(cpic->width, cpic->height, (uint32_t)n);
-    uint8_t       *ws  = hd_alloc(al256(wsb) + 256);
-    int            rc  = ws ? 0 : -1;
-    DevPic         dc, dr[SVT_HIP_TF_MAX_REFS];
-    int            n_dr = 0;
-    memset(&dc, 0, sizeof(dc));
-    if (rc == 0)
-        rc = put_picture(&dc, centre, cpic, is_highbd, job->chroma, !is_highbd);
+    const uint64_t wsb = p_svt_hip_tf_workspace_bytes(cpic->width, cpic->height, (uint32_t)n);
+    uint8_t       *ws  = hd_call_dev(&c, hd_al256(wsb));
+    DevPic         dc, dr;
+    put_picture(&c, &dc, centre, cpic, is_highbd, job->chroma, !is_highbd);
     job->centre = dc.pic;
-    for (int k = 0; rc == 0 && k < n; k++) {
-        rc = put_picture(&dr[k], pcs_list[idx[k]], pics[idx[k]], is_highbd, job->chroma, 0);
-        n_dr++;
-        job->ref[k] = dr[k].pic;
+    for (int k = 0; k < n; k++) {
+        put_picture(&c, &dr, pcs_list[idx[k]], pics[idx[k]], is_highbd, job->chroma, 0);
+        job->ref[k] = dr.pic;
     }
     /* the kernel filters the centre picture IN PLACE on the device: it must not do that to the cached mirror (a later window may
-     * ask for the unfiltered picture again if this call fails) -- the centre's 8-bit planes are copied into scratch first */
-    uint8_t *d_out[3] = {NULL, NULL, NULL};
-    size_t   n_out[3] = {0, 0, 0};
-    uint8_t *h_out[3] = {NULL, NULL, NULL};
-    if (rc == 0) {
-        const int np = job->chroma ? 3 : 1;
-        for (int c = 0; c < np; c++) n_out[c] = is_highbd ? (c ? dc.n_hbd_c : dc.n_hbd_y) : (c ? dc.n_c8 : dc.n_luma8);
-        if (!is_highbd) {
-            /* fresh scratch copies of the centre planes (uploaded from the host: the same bytes the mirror holds) */
-            const uint8_t *hsrc[3] = {cpic->buffer_y, cpic->buffer_cb, cpic->buffer_cr};
-            for (int c = 0; rc == 0 && c < np; c++) {
-                if (!(d_out[c] = hd_alloc(n_out[c] + 256)))
-                    rc = -1;
-                else
-                    rc = hd_upload(d_out[c], hsrc[c], n_out[c]);
-            }
-            if (rc == 0) {
-                job->centre.pyr.full.buf = d_out[0];
-                if (job->chroma)
-                    job->centre.chroma8[0] = d_out[1], job->centre.chroma8[1] = d_out[2];
-            }
-        } else {
-            for (int c = 0; c < np; c++) d_out[c] = NULL; /* the 16-bit planes already are scratch (dc.d_hbd) */
-        }
+     * ask for the unfiltered picture again if this call fails) -- the centre's 8-bit planes are fresh scratch copies (uploaded from
+     * the host: the same bytes the mirror holds); the 16-bit planes already are scratch (dc.d_hbd) */
+    const int np       = job->chroma ? 3 : 1;
+    uint8_t  *d_out[3] = {NULL, NULL, NULL}, *h_out[3] = {NULL, NULL, NULL};
+    size_t    n_out[3] = {0, 0, 0};
+    for (int k = 0; k < np; k++) {
+        const uint8_t *hsrc[3] = {cpic->buffer_y, cpic->buffer_cb, cpic->buffer_cr};
+        n_out[k] = is_highbd ? (k ? dc.n_hbd_c : dc.n_hbd_y) : (k ? dc.n_c8 : dc.n_luma8);
+        d_out[k] = is_highbd ? dc.d_hbd[k] : hd_call_dev_put(&c, hsrc[k], n_out[k]);
     }
-    uint32_t *d_tot = NULL;
-    if (rc == 0) {
-        job->workspace = ws, job->workspace_bytes = wsb;
-        d_tot = (uint32_t *)(ws + al256(wsb));
-        job->tot_blks = d_tot;
-        rc = g_hd.memset_(d_tot, 0, 8, NULL);
+    if (!is_highbd) {
+        job->centre.pyr.full.buf = d_out[0];
+        if (job->chroma)
+            job->centre.chroma8[0] = d_out[1], job->centre.chroma8[1] = d_out[2];
     }
-    if (rc == 0)
-        rc = p_tf_picture(job, NULL);
-    if (rc == 0) { /* the filtered centre picture into host staging; into the encoder's planes only when all of it has arrived */
-        const int np = job->chroma ? 3 : 1;
-        for (int c = 0; rc == 0 && c < np; c++) {
-            h_out[c] = (uint8_t *)hd_host_alloc(n_out[c]);
-            rc = h_out[c] ? hd_download(h_out[c], is_highbd ? dc.d_hbd[c] : d_out[c], n_out[c]) : -1;
-        }
-        if (rc == 0)
-            rc = hd_download(tot, d_tot, 8);
-        rc |= hd_sync();
-        if (rc == 0) {
-            uint8_t *hdst[3] = {cpic->buffer_y, cpic->buffer_cb, cpic->buffer_cr};
-            for (int c = 0; c < np; c++) memcpy(is_highbd ? (uint8_t *)centre->altref_buffer_highbd[c] : hdst[c], h_out[c], n_out[c]);
-        }
-    } else {
-        hd_sync();
+    uint32_t *d_tot = ws ? (uint32_t *)(ws + hd_al256(wsb)) : NULL;
+    job->workspace = ws, job->workspace_bytes = wsb, job->tot_blks = d_tot;
+    hd_call_memset(&c, d_tot, 0, 8);
+    HD_CALL(&c, p_svt_hip_tf_filter_picture(job, NULL));
+    /* the filtered centre picture into host staging; into the encoder's planes only when all of it has arrived */
+    for (int k = 0; k < np; k++) {
+        h_out[k] = (uint8_t *)hd_call_pinned(&c, n_out[k]);
+        hd_call_download(&c, h_out[k], d_out[k], n_out[k]);
     }
-    release_picture(&dc);
-    for (int k = 0; k < n_dr; k++) release_picture(&dr[k]);
-    for (int c = 0; c < 3; c++) hd_free(d_out[c]), hd_host_free(h_out[c]);
-    hd_free(ws);
-    if (rc != 0)
-        fprintf(stderr, "svt_hip_bind_tf: picture %llu stays on the CPU (%s)\n", (unsigned long long)centre->picture_number, hd_error());
-    else
-        hd_count_picture();
-    free(job);
-    return rc != 0;
+    hd_call_download(&c, tot, d_tot, 8);
+    if (hd_call_sync(&c) == 0) {
+        uint8_t *hdst[3] = {cpic->buffer_y, cpic->buffer_cb, cpic->buffer_cr};
+        for (int k = 0; k < np; k++) memcpy(is_highbd ? (uint8_t *)centre->altref_buffer_highbd[k] : hdst[k], h_out[k], n_out[k]);
+    }
+    if (hd_call_end(&c, "svt_hip_bind_tf: picture %llu stays on the CPU", (unsigned long long)centre->picture_number))
+        return 1;
+    hd_count_picture();
+    return 0;
 }
 
 /* Returns 0 when the picture has been filtered on the GPU (the caller skips its block loop), 1 when the caller must run it. */
-static int tf_picture(PictureParentControlSet **pcs_list, EbPictureBufferDesc **pics, int index_center, MeContext *ctx, int is_highbd);
+typedef struct TfArgs {
+    PictureParentControlSet **pcs_list;
+    EbPictureBufferDesc     **pics;
+    int                       index_center, is_highbd;
+    MeContext                *ctx;
+} TfArgs;
+/* the first temporal-filter segment of a picture that arrives filters all of it (hd_once_run) */
+static int tf_first(void *arg, void **payload) {
+    (void)payload;
+    const TfArgs            *a      = (const TfArgs *)arg;
+    PictureParentControlSet *centre = a->pcs_list[a->index_center];
+    uint32_t                 tot[2] = {0, 0};
+    const int                rc     = run_picture(a->pcs_list, a->pics, a->index_center, a->ctx, a->is_highbd, tot);
+    /* either way the centre picture changes now: here (GPU) or in the reference's loop right behind this call (CPU) */
+    drop_picture_mirrors(centre, a->pics[a->index_center]);
+    if (rc == 0) {
+        /* tf_tot_*_blks of the whole picture go to this segment's context (the caller adds every segment's into the pcs) */
+        a->ctx->tf_tot_horz_blks += tot[0], a->ctx->tf_tot_vert_blks += tot[1];
+        __atomic_add_fetch(&g_pictures, 1, __ATOMIC_RELAXED);
+        if (t_low_delay)
+            __atomic_add_fetch(&g_pictures_ld, 1, __ATOMIC_RELAXED);
+    }
+    return rc == 0;
+}
+static int tf_picture(PictureParentControlSet **pcs_list, EbPictureBufferDesc **pics, int index_center, MeContext *ctx, int is_highbd) {
+    PictureParentControlSet *centre = pcs_list[index_center];
+    TfArgs                   a      = {pcs_list, pics, index_center, is_highbd, ctx};
+    const int rc = g_active ? hd_once_run(&g_tab, centre, centre->picture_number, centre->tf_segments_total_count, tf_first, NULL, NULL, &a) : -1;
+    if (rc < 0 && g_hd.ok)
+        drop_picture_mirrors(centre, pics[index_center]); /* not through the table: other hooks may hold mirrors of the picture this loop rewrites */
+    return rc != 0;
+}
 int svt_hip_bind_tf_picture(PictureParentControlSet **pcs_list, EbPictureBufferDesc **pics, int index_center, MeContext *ctx, int is_highbd) {
     t_low_delay = 0;
     return tf_picture(pcs_list, pics, index_center, ctx, is_highbd);
@@ -277,37 +247,4 @@ int svt_hip_bind_tf_picture_ld(PictureParentControlSet **pcs_list, EbPictureBuff
     const int rc = tf_picture(pcs_list, pics, index_center, ctx, is_highbd);
     t_low_delay  = 0;
     return rc;
-}
-static int tf_picture(PictureParentControlSet **pcs_list, EbPictureBufferDesc **pics, int index_center, MeContext *ctx, int is_highbd) {
-    PictureParentControlSet *centre = pcs_list[index_center];
-    if (!g_active) {
-        if (g_hd.ok)
-            drop_picture_mirrors(centre, pics[index_center]); /* other hooks may hold mirrors of the picture this loop rewrites */
-        return 1;
-    }
-    int     first;
-    HdOnce *once = hd_once_enter(&g_tab, centre, centre->picture_number, centre->tf_segments_total_count, &first);
-    if (!once) {
-        drop_picture_mirrors(centre, pics[index_center]);
-        return 1;
-    }
-    if (first) {
-        uint32_t  tot[2] = {0, 0};
-        const uint64_t t0 = hd_now_ns();
-        const int      rc = run_picture(pcs_list, pics, index_center, ctx, is_highbd, tot);
-        hd_timer_add("tf_picture", hd_now_ns() - t0);
-        /* either way the centre picture changes now: here (GPU) or in the reference's loop right behind this call (CPU) */
-        drop_picture_mirrors(centre, pics[index_center]);
-        if (rc == 0) {
-            /* tf_tot_*_blks of the whole picture go to this segment's context (the caller adds every segment's into the pcs) */
-            ctx->tf_tot_horz_blks += tot[0], ctx->tf_tot_vert_blks += tot[1];
-            __atomic_add_fetch(&g_pictures, 1, __ATOMIC_RELAXED);
-            if (t_low_delay)
-                __atomic_add_fetch(&g_pictures_ld, 1, __ATOMIC_RELAXED);
-        }
-        hd_once_done(once, rc == 0, NULL);
-    }
-    const int on_gpu = hd_once_ok(once);
-    hd_once_release(&g_tab, once, NULL);
-    return on_gpu ? 0 : 1;
 }

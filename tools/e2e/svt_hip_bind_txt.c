@@ -25,7 +25,7 @@
 #include "svt_hip_bind.h"
 #include "svt_hip_bind_dev.h"
 
-static int32_t (*p_batch)(uint8_t *, const SvtHipTxfmDesc *, SvtHipTxfmResult *, uint32_t, uint32_t, uint32_t, void *);
+HD_FN(svt_hip_txfm_quant_batch);
 static int           g_active;
 static unsigned long g_blocks, g_transforms, g_taken;
 
@@ -35,8 +35,8 @@ static void report(void) {
 }
 
 void svt_hip_bind_txt_setup(void *(*sym)(const char *)) {
-    p_batch  = (int32_t(*)(uint8_t *, const SvtHipTxfmDesc *, SvtHipTxfmResult *, uint32_t, uint32_t, uint32_t, void *))sym("svt_hip_txfm_quant_batch");
-    g_active = hd_env_on("SVTAV1_HIP_TIERB_TXT") && g_hd.ok && p_batch;
+    HD_SYM(sym, svt_hip_txfm_quant_batch);
+    g_active = hd_env_on("SVTAV1_HIP_TIERB_TXT") && g_hd.ok && p_svt_hip_txfm_quant_batch;
     if (g_active)
         atexit(report);
 }
@@ -66,8 +66,8 @@ void *svt_hip_bind_txt_prepare(const int16_t *residual, uint32_t stride, int tx_
             c->type[c->n++] = (uint8_t)t;
     const int    n = c->n;
     const size_t n_res = (size_t)w * h * sizeof(int16_t), n_co = (size_t)w * h * sizeof(int32_t);
-    const size_t o_res = 0, o_co = (n_res + 255) & ~(size_t)255, o_desc = o_co + (((size_t)n * n_co + 255) & ~(size_t)255);
-    const size_t o_out = o_desc + (((size_t)n * sizeof(SvtHipTxfmDesc) + 255) & ~(size_t)255), total = o_out + n * sizeof(SvtHipTxfmResult) + 256;
+    const size_t o_res = 0, o_co = hd_al256(n_res), o_desc = o_co + hd_al256((size_t)n * n_co);
+    const size_t o_out = o_desc + hd_al256((size_t)n * sizeof(SvtHipTxfmDesc)), total = o_out + n * sizeof(SvtHipTxfmResult);
     if (c->coeff_cap < (size_t)n * n_co) {
         hd_host_free(c->coeff);
         c->coeff     = (int32_t *)hd_host_alloc((size_t)TXT_MAX * 32 * 32 * sizeof(int32_t));
@@ -75,9 +75,9 @@ void *svt_hip_bind_txt_prepare(const int16_t *residual, uint32_t stride, int tx_
         if (!c->coeff)
             return NULL;
     }
-    uint8_t *dev = hd_alloc(total);
-    if (!dev)
-        return NULL;
+    HdCall   call; /* (the offsets of the descriptors are relative to one base: one block) */
+    hd_call_begin(&call, NULL);
+    uint8_t *dev = hd_call_dev(&call, total);
     /* residual rows packed (stride w), descriptors, one call */
     int16_t        packed[32 * 32];
     SvtHipTxfmDesc desc[TXT_MAX];
@@ -91,15 +91,14 @@ void *svt_hip_bind_txt_prepare(const int16_t *residual, uint32_t stride, int tx_
         d->tx_type = c->type[i], d->shape = (uint8_t)pf_shape, d->bit_depth = (uint8_t)bit_depth, d->quant_mode = SVT_HIP_QUANT_NONE;
         d->flags = SVT_HIP_TX_FWD;
     }
-    int rc = hd_upload(dev + o_res, packed, n_res) | hd_upload(dev + o_desc, desc, (size_t)n * sizeof(SvtHipTxfmDesc));
-    if (rc == 0)
-        rc = p_batch(dev, (const SvtHipTxfmDesc *)(dev + o_desc), (SvtHipTxfmResult *)(dev + o_out), (uint32_t)n, (uint32_t)w, (uint32_t)h, NULL);
-    if (rc == 0)
-        rc = hd_download(c->coeff, dev + o_co, (size_t)n * n_co) | hd_download(c->res, dev + o_out, (size_t)n * sizeof(SvtHipTxfmResult));
-    rc |= hd_sync();
-    hd_free(dev);
-    if (rc != 0) {
-        fprintf(stderr, "svt_hip_bind_txt: a transform block stays on the CPU (%s)\n", hd_error());
+    hd_call_upload(&call, dev + o_res, packed, n_res);
+    hd_call_upload(&call, dev + o_desc, desc, (size_t)n * sizeof(SvtHipTxfmDesc));
+    HD_CALL(&call, p_svt_hip_txfm_quant_batch(dev, (const SvtHipTxfmDesc *)(dev + o_desc), (SvtHipTxfmResult *)(dev + o_out), (uint32_t)n, (uint32_t)w,
+                                              (uint32_t)h, NULL));
+    hd_call_download(&call, c->coeff, dev + o_co, (size_t)n * n_co);
+    hd_call_download(&call, c->res, dev + o_out, (size_t)n * sizeof(SvtHipTxfmResult));
+    hd_call_sync(&call);
+    if (hd_call_end(&call, "svt_hip_bind_txt: a transform block stays on the CPU")) {
         c->n = 0;
         return NULL;
     }
