@@ -48,7 +48,9 @@ SVT_HIP_API const char *svt_hip_version(void);
 
 /* Device memory + streams for hosts that do not bring their own (the C encoder).  A `stream`
  * argument anywhere in this API is a hipStream_t passed as void*; NULL = the calling thread's
- * private stream owned by the library. */
+ * stream, owned by the library.  It comes from a pool of 8: threads k and k + 8 share one, so
+ * svt_hip_stream_sync(NULL) may also wait for another thread's work.  What is promised is the order
+ * of the calls of one thread. */
 SVT_HIP_API int32_t svt_hip_malloc(void **dptr, size_t bytes);
 SVT_HIP_API int32_t svt_hip_free(void *dptr);
 SVT_HIP_API int32_t svt_hip_memset(void *dptr, int value, size_t bytes, void *stream);

@@ -14,7 +14,7 @@ namespace svthip {
 // Thread-local error text returned by svt_hip_last_error().
 void set_error(const char *fmt, ...);
 
-// Calling thread's private stream (created lazily) unless the caller passed its own.
+// Calling thread's pooled stream unless the caller passed its own.
 hipStream_t resolve_stream(void *stream);
 
 // Grow-only per-thread device + pinned scratch used by the Tier A (host-pointer) entry points.  host() keeps the first
@@ -26,16 +26,76 @@ struct Scratch {
     uint8_t *device(size_t bytes);
     uint8_t *host(size_t bytes, size_t keep = 0);
 };
-Scratch &tls_scratch();
 
 bool ensure_init();
+int  cu_count();                         // compute units of the device, queried once by svt_hip_init
+hipError_t ensure_event(hipEvent_t &ev); // creates ev (no timing) unless it exists: the one place events are made
 
-// Small descriptor arrays that a Tier B entry point receives in HOST memory travel to the device through a per-thread
-// ring of pinned + device staging slots.  stage_descriptors() copies and returns the device address (nullptr + error
-// set on failure); stage_commit() must be called after the kernels that read it have been launched: it records the
-// event that guards the slot against reuse.  No allocation happens on the launch path once the slots have grown.
-void *stage_descriptors(const void *host, size_t bytes, hipStream_t st);
-void  stage_commit(hipStream_t st);
+// Grow-only device buffer of one thread, with a pinned twin of the same size when the host fills it, and one event that
+// guards it against its previous user, which may sit on another stream.  acquire() makes it safe to use on st: when the
+// host is going to write the twin, or when the buffer has to grow, it waits for the buffer's OWN event on the host (never
+// for the device, never through a bare free); otherwise st waits for the event.  release() records the event behind the
+// work that uses the buffer.  After a failed growth the buffer is empty (dev == pinned == nullptr, cap == 0).
+struct GuardedBuf {
+    uint8_t   *dev = nullptr, *pinned = nullptr;
+    size_t     cap = 0;
+    hipEvent_t ev  = nullptr;
+    bool       pending = false;  // ev was recorded and the host has not waited for it since
+    bool       held    = false;  // a live TierBCall owns it
+    // grows to grow_to (>= bytes) when bytes > cap; *what names the HIP call that failed
+    hipError_t acquire(size_t bytes, size_t grow_to, bool host_writes, hipStream_t st, const char **what);
+    hipError_t release(hipStream_t st);
+};
+
+// Everything a host thread owns on the device: the library's only per-thread object (tls(), runtime.cpp).
+struct ThreadState {
+    char       err[512] = "";      // svt_hip_last_error()
+    bool       bound    = false;   // hipSetDevice done
+    int        slot     = -1;      // index into the stream pool
+    GuardedBuf ring[4];            // staging slots for descriptor arrays that arrive in host memory (TierBCall::stage)
+    int        ring_next = 0;
+    Scratch    scratch;            // Tier A staging (TierAStage)
+    GuardedBuf wiener_aux;         // raw first moments of svt_hip_wiener_stats
+    GuardedBuf txfm_perm;          // block permutation of the grouped transform launch
+    hipEvent_t produced = nullptr; // svt_hip_publish_reference: producer stream -> side stream
+};
+ThreadState &tls();
+
+// The host side of one Tier B entry point, on its stack, after the argument checks:
+//     TierBCall c("svt_hip_x", stream);                       // ensure_init + resolve_stream
+//     const Job *d_jobs = (const Job *)c.stage(jobs, bytes);   // host array -> next ring slot -> device
+//     void *aux = c.take(tls().wiener_aux, bytes, 2 * bytes);  // event-guarded per-thread device buffer
+//     if (!c.ok()) return c.status();
+//     hipLaunchKernelGGL(..., c.stream(), d_jobs, aux);
+//     return c.finish();                                       // launch check, events recorded
+// The status is sticky: after a failed step stage() and take() return nullptr and do nothing.  Whatever the scope took is
+// given back -- its event recorded on the stream -- by finish() or, on any earlier return, by the destructor, so no slot
+// can be reused while an upload from it or a kernel that reads it is still in flight.  A nested scope (tf_filter_picture
+// -> me_frames) claims the next ring slot and never touches the outer scope's.  No allocation happens on the launch path
+// once the buffers have grown.
+class TierBCall {
+public:
+    TierBCall(const char *fn, void *stream);
+    ~TierBCall() { release(); }
+    TierBCall(const TierBCall &)            = delete;
+    TierBCall &operator=(const TierBCall &) = delete;
+    bool        ok() const { return status_ == SVT_HIP_OK; }
+    int32_t     status() const { return status_; }
+    hipStream_t stream() const { return st_; }
+    void       *stage(const void *host, size_t bytes);                 // 64 KiB minimum, x2 when it grows
+    void       *take(GuardedBuf &b, size_t bytes, size_t grow_to);     // grows to grow_to when bytes > b.cap
+    int32_t     finish();
+
+private:
+    void       *fail(hipError_t e, const char *what);
+    bool        hold(GuardedBuf &b, size_t bytes, size_t grow_to, bool host_writes);
+    void        release();
+    const char *fn_;
+    hipStream_t st_     = nullptr;
+    int32_t     status_ = SVT_HIP_OK;
+    GuardedBuf *held_[6];
+    int         n_held_ = 0;
+};
 
 // The HIP runtime loads the code object of a translation unit when the first of its kernels is launched (hundreds of milliseconds for
 // the whole library, paid by whichever encoder threads come first: 23 ms per call of the first 35 calls inside the patched encoder).

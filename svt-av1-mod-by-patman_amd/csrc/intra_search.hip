@@ -163,16 +163,12 @@ extern "C" int32_t svt_hip_intra_search_frames(const SvtHipIntraSearchJob *jobs,
         const uint32_t cells = ((jb.src.width + 15u) >> 4) * ((jb.src.height + 15u) >> 4);
         max_cells            = cells > max_cells ? cells : max_cells;
     }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t                 st     = resolve_stream(stream);
-    const SvtHipIntraSearchJob *d_jobs = (const SvtHipIntraSearchJob *)stage_descriptors(jobs, sizeof(SvtHipIntraSearchJob) * n, st);
+    TierBCall                   c("svt_hip_intra_search_frames", stream);
+    const SvtHipIntraSearchJob *d_jobs = (const SvtHipIntraSearchJob *)c.stage(jobs, sizeof(SvtHipIntraSearchJob) * n);
     if (!d_jobs)
-        return SVT_HIP_ERR_RUNTIME;
-    hipLaunchKernelGGL(intra_search_kernel, dim3(max_cells, n), dim3(64), 0, st, d_jobs);
-    stage_commit(st);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+        return c.status();
+    hipLaunchKernelGGL(intra_search_kernel, dim3(max_cells, n), dim3(64), 0, c.stream(), d_jobs);
+    return c.finish();
 }
 
 SVT_HIP_MODULE_WARMUP(intra_search)

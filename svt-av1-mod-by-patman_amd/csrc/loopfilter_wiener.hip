@@ -333,13 +333,6 @@ __global__ __launch_bounds__(256) void wiener_convolve_kernel(const void *__rest
     lr::wiener_tile_filter<256>(in, tmp, threadIdx.x, tw, th, x0, y0, f.x, f.y, bd, r0, r1, is16, dst, dst_stride);
 }
 
-
-struct AuxBuf {  // per-thread grow-only device buffer for the raw first moments, guarded by an event against reuse from another stream
-    StatsAux  *dev = nullptr;
-    size_t     cap = 0;
-    hipEvent_t ev  = nullptr;
-};
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ Tier B
@@ -360,40 +353,23 @@ extern "C" int32_t svt_hip_wiener_stats(const SvtHipWienerUnit *units, uint32_t 
         max_w = u.h_end - u.h_start > max_w ? u.h_end - u.h_start : max_w;
         max_h = u.v_end - u.v_start > max_h ? u.v_end - u.v_start : max_h;
     }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t                st = resolve_stream(stream);
-    static thread_local AuxBuf ab;
-    if (!ab.ev)
-        SVT_HIP_CHECK(hipEventCreateWithFlags(&ab.ev, hipEventDisableTiming));
-    if (n_units > ab.cap) {
-        if (ab.dev) {
-            SVT_HIP_CHECK(hipDeviceSynchronize());
-            SVT_HIP_CHECK(hipFree(ab.dev));
-        }
-        ab.dev = nullptr, ab.cap = 0;
-        SVT_HIP_CHECK(hipMalloc((void **)&ab.dev, sizeof(StatsAux) * n_units * 2));
-        ab.cap = n_units * 2;
-    }
-    const SvtHipWienerUnit *d_units = (const SvtHipWienerUnit *)stage_descriptors(units, sizeof(SvtHipWienerUnit) * n_units, st);
-    if (!d_units)
-        return SVT_HIP_ERR_RUNTIME;
-    // the previous call of this thread may sit on another stream and still read ab.dev: the zero kernel waits for its finalize kernel
-    SVT_HIP_CHECK(hipStreamWaitEvent(st, ab.ev, 0));
+    TierBCall c("svt_hip_wiener_stats", stream);
+    // the raw first moments: a per-thread buffer.  The previous call of this thread may sit on another stream and still read it: the
+    // zero kernel waits for its finalize kernel (or, when the buffer has to grow, the host does)
+    StatsAux *aux = (StatsAux *)c.take(tls().wiener_aux, sizeof(StatsAux) * n_units, sizeof(StatsAux) * n_units * 2);
+    const SvtHipWienerUnit *d_units = (const SvtHipWienerUnit *)c.stage(units, sizeof(SvtHipWienerUnit) * n_units);
+    if (!c.ok())
+        return c.status();
+    hipStream_t st = c.stream();
     // the three sum arrays start from zero: one launch instead of three memsets (a launch costs more than it moves here)
     {
         const size_t nM = (size_t)W2MAX * n_units, nH = (size_t)W2MAX * W2MAX * n_units, nA = sizeof(StatsAux) / sizeof(long long) * n_units;
-        hipLaunchKernelGGL(wiener_zero_kernel, dim3((unsigned)((nH + 255) / 256)), dim3(256), 0, st, (long long *)d_M, (long long *)d_H, (long long *)ab.dev, nM, nH, nA);
+        hipLaunchKernelGGL(wiener_zero_kernel, dim3((unsigned)((nH + 255) / 256)), dim3(256), 0, st, (long long *)d_M, (long long *)d_H, (long long *)aux, nM, nH, nA);
     }
     // about one workgroup per slot of the GPU (two per CU at this kernel's register count): every unit gets the same number of
     // workgroups, each with a contiguous range of the unit's (chunk, tile) items.  int32 accumulators: products of two digits are below
     // or equal to 2^12 and a wave sees a quarter of its workgroup's samples: at most 512 items (2^20 samples, 2^18 per wave) per workgroup.
-    static const int slots = [] {
-        int cus = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            cus = 0;
-        return 2 * (cus > 0 ? cus : 256);
-    }();
+    const int slots = 2 * (cu_count() > 0 ? cu_count() : 256);
     const int gx = (max_w + TW - 1) / TW, gy = (max_h + TH - 1) / TH, items = gx * gy;
     int       k  = slots / (int)n_units > 1 ? slots / (int)n_units : 1;
     k            = k > items ? items : k;
@@ -401,16 +377,13 @@ extern "C" int32_t svt_hip_wiener_stats(const SvtHipWienerUnit *units, uint32_t 
     const int  per = (items + k - 1) / k;
     const dim3 grid((unsigned)(n_units * k));
     if (wiener_win == 7)
-        hipLaunchKernelGGL(wiener_stats_kernel<7>, grid, dim3(256), 0, st, d_units, k, per, gx, gy, is_16bit, bit_depth, (long long *)d_M, (long long *)d_H, ab.dev);
+        hipLaunchKernelGGL(wiener_stats_kernel<7>, grid, dim3(256), 0, st, d_units, k, per, gx, gy, is_16bit, bit_depth, (long long *)d_M, (long long *)d_H, aux);
     else
-        hipLaunchKernelGGL(wiener_stats_kernel<5>, grid, dim3(256), 0, st, d_units, k, per, gx, gy, is_16bit, bit_depth, (long long *)d_M, (long long *)d_H, ab.dev);
+        hipLaunchKernelGGL(wiener_stats_kernel<5>, grid, dim3(256), 0, st, d_units, k, per, gx, gy, is_16bit, bit_depth, (long long *)d_M, (long long *)d_H, aux);
     const int divider = is_16bit ? (bit_depth == 12 ? 16 : (bit_depth == 10 ? 4 : 1)) : 1;  // restoration_pick.c:719-723
     hipLaunchKernelGGL(wiener_finalize_kernel, dim3(n_units), dim3(256), 0, st, wiener_win, divider, (long long *)d_M, (long long *)d_H,
-                       (const StatsAux *)ab.dev);
-    SVT_HIP_CHECK(hipEventRecord(ab.ev, st));
-    stage_commit(st);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+                       (const StatsAux *)aux);
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_wiener_convolve(const void *d_src, uint32_t src_stride, void *d_dst, uint32_t dst_stride, uint32_t w, uint32_t h,

@@ -1660,13 +1660,11 @@ extern "C" int32_t svt_hip_me_validate_jobs(const SvtHipMeFrameJob *jobs, uint32
     return SVT_HIP_OK;
 }
 
-static int32_t launch_me(const SvtHipMeFrameJob *d_jobs, uint32_t n_jobs, uint32_t max_b64, hipStream_t st, bool mctf) {
+static void launch_me(const SvtHipMeFrameJob *d_jobs, uint32_t n_jobs, uint32_t max_b64, hipStream_t st, bool mctf) {
     if (mctf)
         hipLaunchKernelGGL(me_b64_kernel<true>, dim3((max_b64 + 7) / 8 * 8, n_jobs), dim3(WG_THREADS), 0, st, d_jobs);
     else
         hipLaunchKernelGGL(me_b64_kernel<false>, dim3((max_b64 + 7) / 8 * 8, n_jobs), dim3(WG_THREADS), 0, st, d_jobs);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
 }
 
 extern "C" int32_t svt_hip_me_frames_dev(const SvtHipMeFrameJob *d_jobs, uint32_t n_jobs, uint32_t max_b64, void *stream) {
@@ -1676,7 +1674,9 @@ extern "C" int32_t svt_hip_me_frames_dev(const SvtHipMeFrameJob *d_jobs, uint32_
     }
     if (!ensure_init())
         return SVT_HIP_ERR_NO_DEVICE;
-    return launch_me(d_jobs, n_jobs, max_b64, resolve_stream(stream), false);
+    launch_me(d_jobs, n_jobs, max_b64, resolve_stream(stream), false);
+    SVT_HIP_CHECK(hipGetLastError());
+    return SVT_HIP_OK;
 }
 
 extern "C" int32_t svt_hip_me_frames(const SvtHipMeFrameJob *jobs, uint32_t n_jobs, void *stream) {
@@ -1684,18 +1684,15 @@ extern "C" int32_t svt_hip_me_frames(const SvtHipMeFrameJob *jobs, uint32_t n_jo
     const int32_t vrc     = svt_hip_me_validate_jobs(jobs, n_jobs, &max_b64);
     if (vrc != SVT_HIP_OK)
         return vrc;
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t st = resolve_stream(stream);
+    TierBCall c("svt_hip_me_frames", stream);
     // Job descriptors travel through the per-thread staging ring (common.hpp): no allocation on the launch path.
-    const SvtHipMeFrameJob *d_jobs = (const SvtHipMeFrameJob *)stage_descriptors(jobs, sizeof(SvtHipMeFrameJob) * n_jobs, st);
+    const SvtHipMeFrameJob *d_jobs = (const SvtHipMeFrameJob *)c.stage(jobs, sizeof(SvtHipMeFrameJob) * n_jobs);
     if (!d_jobs)
-        return SVT_HIP_ERR_RUNTIME;
+        return c.status();
     bool mctf = true;  // (host copy of the descriptors: the mode of every picture is known here)
     for (uint32_t i = 0; i < n_jobs; i++) mctf = mctf && jobs[i].prm.me_mctf;
-    const int32_t rc = launch_me(d_jobs, n_jobs, max_b64, st, mctf);
-    stage_commit(st);
-    return rc;
+    launch_me(d_jobs, n_jobs, max_b64, c.stream(), mctf);
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_install_rtcd_me(void **table, uint32_t n_slots) {

@@ -264,12 +264,11 @@ extern "C" int32_t svt_hip_analysis_frames(const SvtHipAnalysisJob *jobs, uint32
         const uint32_t nb = ((y.full.width + 63u) / 64u) * ((y.full.height + 63u) / 64u);
         max_nb            = nb > max_nb ? nb : max_nb;
     }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t st = resolve_stream(stream);
-    const SvtHipAnalysisJob *d_jobs = (const SvtHipAnalysisJob *)stage_descriptors(jobs, (size_t)n_jobs * sizeof(SvtHipAnalysisJob), st);
+    TierBCall                c("svt_hip_analysis_frames", stream);
+    const SvtHipAnalysisJob *d_jobs = (const SvtHipAnalysisJob *)c.stage(jobs, (size_t)n_jobs * sizeof(SvtHipAnalysisJob));
     if (!d_jobs)
-        return SVT_HIP_ERR_RUNTIME;
+        return c.status();
+    hipStream_t st = c.stream();
     if (hme_level1_enabled) {
         hipLaunchKernelGGL(downsample_pad_batch_kernel, dim3((max_q_stride / 4 + 1 + 255) / 256, (max_q_rows + BATCH_ROWS - 1) / BATCH_ROWS, n_jobs), dim3(256), 0, st, d_jobs, 0);
         hipLaunchKernelGGL(downsample_pad_batch_kernel, dim3((max_s_stride / 4 + 1 + 255) / 256, (max_s_rows + BATCH_ROWS - 1) / BATCH_ROWS, n_jobs), dim3(256), 0, st, d_jobs, 1);
@@ -277,9 +276,7 @@ extern "C" int32_t svt_hip_analysis_frames(const SvtHipAnalysisJob *jobs, uint32
         hipLaunchKernelGGL(downsample_pad_batch_kernel, dim3((max_s_stride / 4 + 1 + 255) / 256, (max_s_rows + BATCH_ROWS - 1) / BATCH_ROWS, n_jobs), dim3(256), 0, st, d_jobs, 2);
     }
     hipLaunchKernelGGL(variance_batch_kernel, dim3((max_nb + 3) / 4, n_jobs), dim3(256), 0, st, d_jobs, (int)full_precision);
-    stage_commit(st);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 // ------------------------------------------------------------------------------------------------

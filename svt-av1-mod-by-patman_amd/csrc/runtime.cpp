@@ -10,26 +10,51 @@
 
 namespace svthip {
 
-static thread_local char tls_err[512] = "";
-static std::atomic<int>  g_device{-1};   // the device every entry point works on; -1 until svt_hip_init succeeds
-static std::atomic<int>  g_sticky{-1};   // first device ever bound: per-thread streams / scratch / once-uploaded tables live there
-static std::mutex        g_mutex;
+// Process state: one device per process, one pool of streams for the threads that pass stream == NULL.
+#ifndef SVT_HIP_STREAM_POOL
+#define SVT_HIP_STREAM_POOL 8
+#endif
+namespace {
+constexpr int STREAM_POOL = SVT_HIP_STREAM_POOL;
+struct Process {
+    std::atomic<int> device{-1};  // the device every entry point works on; -1 until svt_hip_init succeeds
+    std::atomic<int> sticky{-1};  // first device ever bound: streams / per-thread buffers / once-uploaded tables live there
+    std::atomic<int> cus{0};
+    std::mutex       mutex;       // svt_hip_init / svt_hip_shutdown
+    // The "calling thread's private stream" (stream == NULL in the API): a host such as the encoder has dozens of worker threads, and
+    // creating a HIP stream costs milliseconds (a hardware queue) -- 25 ms per first call of a thread inside the patched encoder.
+    // Threads draw from a small pool instead: thread k uses stream k mod POOL.  Two threads that share a stream only wait for each
+    // other's work in svt_hip_stream_sync; order inside one thread is kept, which is all the API promises.  Entries are created under
+    // pool_mutex (by svt_hip_init, or on demand) and published with release / read with acquire.
+    std::atomic<hipStream_t> pool[STREAM_POOL];
+    std::mutex               pool_mutex;
+    std::atomic<int>         next_thread{0};
+};
+Process g;
+}  // namespace
+
+ThreadState &tls() {
+    static thread_local ThreadState t;
+    return t;
+}
 
 void set_error(const char *fmt, ...) {
-    va_list ap;
+    ThreadState &t = tls();
+    va_list      ap;
     va_start(ap, fmt);
-    vsnprintf(tls_err, sizeof(tls_err), fmt, ap);
+    vsnprintf(t.err, sizeof(t.err), fmt, ap);
     va_end(ap);
 }
 
 bool ensure_init() {
-    if (g_device.load() >= 0) {
+    const int dev = g.device.load();
+    if (dev >= 0) {
         // each host thread must select the device once
-        static thread_local bool bound = false;
-        if (!bound) {
-            if (hipSetDevice(g_device.load()) != hipSuccess)
+        ThreadState &t = tls();
+        if (!t.bound) {
+            if (hipSetDevice(dev) != hipSuccess)
                 return false;
-            bound = true;
+            t.bound = true;
         }
         return true;
     }
@@ -38,20 +63,7 @@ bool ensure_init() {
     set_error("library not initialised: call svt_hip_init(device_ordinal) first");
     return false;
 }
-
-// The "calling thread's private stream" (stream == NULL in the API): a host such as the encoder has dozens of worker threads, and
-// creating a HIP stream costs milliseconds (a hardware queue) -- 25 ms per first call of a thread inside the patched encoder.  Threads
-// draw from a small pool instead: thread k uses stream k mod POOL.  Two threads that share a stream only wait for each other's work in
-// svt_hip_stream_sync; order inside one thread is kept, which is all the API promises.
-#ifndef SVT_HIP_STREAM_POOL
-#define SVT_HIP_STREAM_POOL 8
-#endif
-namespace {
-constexpr int     STREAM_POOL = SVT_HIP_STREAM_POOL;
-hipStream_t       g_pool_streams[STREAM_POOL];
-std::mutex        g_pool_mutex;
-std::atomic<int>  g_next_thread{0};
-}  // namespace
+int cu_count() { return g.cus.load(std::memory_order_relaxed); }
 
 namespace {
 WarmupFn g_warmups[64];
@@ -68,13 +80,13 @@ void run_module_warmups(hipStream_t st) {
 hipStream_t resolve_stream(void *stream) {
     if (stream)
         return (hipStream_t)stream;
-    static thread_local int slot = -1;
-    if (slot < 0)
-        slot = g_next_thread.fetch_add(1) % STREAM_POOL;
-    hipStream_t s = g_pool_streams[slot];
+    ThreadState &t = tls();
+    if (t.slot < 0)
+        t.slot = g.next_thread.fetch_add(1) % STREAM_POOL;
+    hipStream_t s = g.pool[t.slot].load(std::memory_order_acquire);
     if (!s) {
-        std::lock_guard<std::mutex> lk(g_pool_mutex);
-        s = g_pool_streams[slot];
+        std::lock_guard<std::mutex> lk(g.pool_mutex);
+        s = g.pool[t.slot].load(std::memory_order_relaxed);
         if (!s) {
             // streams belong to the device that is current when they are created: bind this thread first
             (void)ensure_init();
@@ -82,69 +94,107 @@ hipStream_t resolve_stream(void *stream) {
                 set_error("cannot create a stream for the calling thread");
                 return nullptr;  // the legacy default stream: callers carry on, correct but serialised
             }
-            g_pool_streams[slot] = s;
+            g.pool[t.slot].store(s, std::memory_order_release);
         }
     }
     return s;
 }
 
-namespace {
-struct StageSlot {
-    uint8_t   *dev = nullptr, *pinned = nullptr;
-    size_t     cap = 0;
-    hipEvent_t done = nullptr;
-    bool       pending = false;
-};
-struct StageRing {
-    StageSlot slot[4];
-    int       next = 0, last = -1;
-};
-thread_local StageRing g_ring;
-}  // namespace
+hipError_t ensure_event(hipEvent_t &ev) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
 
-void *stage_descriptors(const void *host, size_t bytes, hipStream_t st) {
-    StageRing &r = g_ring;
-    StageSlot &s = r.slot[r.next];
-    auto       fail = [&](hipError_t e, const char *what) {
-        set_error("stage_descriptors: %s: %s", what, hipGetErrorString(e));
-        return (void *)nullptr;
-    };
+hipError_t GuardedBuf::acquire(size_t bytes, size_t grow_to, bool host_writes, hipStream_t st, const char **what) {
     hipError_t e;
-    if (s.pending) {
-        if ((e = hipEventSynchronize(s.done)) != hipSuccess)
-            return fail(e, "hipEventSynchronize");
-        s.pending = false;
+    *what = "hipEventCreate";
+    if ((e = ensure_event(ev)) != hipSuccess)
+        return e;
+    const bool grow = bytes > cap;
+    if (pending && (host_writes || grow)) {
+        *what = "hipEventSynchronize";
+        if ((e = hipEventSynchronize(ev)) != hipSuccess)
+            return e;
+        pending = false;
+    } else if (pending) {
+        *what = "hipStreamWaitEvent";
+        if ((e = hipStreamWaitEvent(st, ev, 0)) != hipSuccess)
+            return e;
     }
-    if (!s.done && (e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming)) != hipSuccess)
-        return fail(e, "hipEventCreate");
-    if (bytes > s.cap) {
-        if (s.dev)
-            (void)hipFree(s.dev);
-        if (s.pinned)
-            (void)hipHostFree(s.pinned);
-        s.dev = s.pinned = nullptr, s.cap = 0;
-        const size_t cap = bytes < 65536 ? 65536 : bytes * 2;
-        if ((e = hipMalloc((void **)&s.dev, cap)) != hipSuccess)
-            return fail(e, "hipMalloc");
-        if ((e = hipHostMalloc((void **)&s.pinned, cap, hipHostMallocDefault)) != hipSuccess)
-            return fail(e, "hipHostMalloc");
-        s.cap = cap;
+    if (grow) {  // nothing in flight refers to it any more
+        if (dev)
+            (void)hipFree(dev);
+        if (pinned)
+            (void)hipHostFree(pinned);
+        dev = pinned = nullptr, cap = 0;
+        *what = "hipMalloc";
+        if ((e = hipMalloc((void **)&dev, grow_to)) != hipSuccess)
+            return dev = nullptr, e;
+        *what = "hipHostMalloc";
+        if (host_writes && (e = hipHostMalloc((void **)&pinned, grow_to, hipHostMallocDefault)) != hipSuccess) {
+            (void)hipFree(dev);
+            return dev = pinned = nullptr, e;
+        }
+        cap = grow_to;
     }
-    memcpy(s.pinned, host, bytes);
-    if ((e = hipMemcpyAsync(s.dev, s.pinned, bytes, hipMemcpyHostToDevice, st)) != hipSuccess)
-        return fail(e, "hipMemcpyAsync");
-    r.last = r.next;
-    r.next = (r.next + 1) % 4;
-    return s.dev;
+    return hipSuccess;
 }
-void stage_commit(hipStream_t st) {
-    StageRing &r = g_ring;
-    if (r.last < 0)
-        return;
-    StageSlot &s = r.slot[r.last];
-    if (hipEventRecord(s.done, st) == hipSuccess)
-        s.pending = true;
-    r.last = -1;
+hipError_t GuardedBuf::release(hipStream_t st) {
+    hipError_t e = hipEventRecord(ev, st);
+    if (e == hipSuccess)
+        pending = true;
+    else  // the event cannot guard the buffer: let its user finish now
+        (void)hipStreamSynchronize(st);
+    return e;
+}
+
+TierBCall::TierBCall(const char *fn, void *stream) : fn_(fn) {
+    if (!ensure_init())
+        status_ = SVT_HIP_ERR_NO_DEVICE;
+    else
+        st_ = resolve_stream(stream);
+}
+void *TierBCall::fail(hipError_t e, const char *what) {
+    if (ok())  // the first failure is the one reported
+        set_error("%s: %s: %s", fn_, what, hipGetErrorString(e));
+    status_ = SVT_HIP_ERR_RUNTIME;
+    return nullptr;
+}
+bool TierBCall::hold(GuardedBuf &b, size_t bytes, size_t grow_to, bool host_writes) {
+    if (!ok())
+        return false;
+    if (b.held)
+        return fail(hipErrorInvalidValue, "buffer still held by an enclosing call") != nullptr;
+    const char      *what;
+    const hipError_t e = b.acquire(bytes, grow_to, host_writes, st_, &what);
+    if (e != hipSuccess)
+        return fail(e, what) != nullptr;
+    b.held = true, held_[n_held_++] = &b;
+    return true;
+}
+void *TierBCall::stage(const void *host, size_t bytes) {
+    ThreadState &t = tls();
+    GuardedBuf  &s = t.ring[t.ring_next];
+    if (!hold(s, bytes, bytes < 65536 ? 65536 : bytes * 2, true))
+        return nullptr;
+    t.ring_next = (t.ring_next + 1) % 4;
+    memcpy(s.pinned, host, bytes);
+    const hipError_t e = hipMemcpyAsync(s.dev, s.pinned, bytes, hipMemcpyHostToDevice, st_);
+    return e == hipSuccess ? s.dev : fail(e, "hipMemcpyAsync");
+}
+void *TierBCall::take(GuardedBuf &b, size_t bytes, size_t grow_to) { return hold(b, bytes, grow_to, false) ? b.dev : nullptr; }
+void TierBCall::release() {
+    for (int i = 0; i < n_held_; i++) {
+        const hipError_t e = held_[i]->release(st_);
+        if (e != hipSuccess)
+            fail(e, "hipEventRecord");
+        held_[i]->held = false;
+    }
+    n_held_ = 0;
+}
+int32_t TierBCall::finish() {
+    const hipError_t e = ok() ? hipGetLastError() : hipSuccess;
+    if (e != hipSuccess)
+        fail(e, "launch");
+    release();
+    return status_;
 }
 
 // ---- Tier A failure handling (common.hpp) ----
@@ -241,11 +291,6 @@ uint8_t *Scratch::host(size_t bytes, size_t keep) {
     }
     return pinned;
 }
-Scratch &tls_scratch() {
-    static thread_local Scratch s;
-    return s;
-}
-
 [[noreturn]] void fatal(const char *what) { tier_a_throw("%s: %s", what, svt_hip_last_error()); }
 
 TierAStage::TierAStage(const char *leaf, bool ready) {
@@ -258,7 +303,7 @@ size_t TierAStage::reserve(size_t bytes) {
         tier_a_throw("Tier A staging: region reserved after the device buffer was sized");
     const size_t off = used_;
     used_ += up256(bytes);
-    h_ = tls_scratch().host(used_ + 256, off);
+    h_ = tls().scratch.host(used_ + 256, off);
     return off;
 }
 size_t TierAStage::in(const void *src, size_t bytes, size_t slack) {
@@ -275,7 +320,7 @@ size_t TierAStage::in_rows(const void *src, size_t src_pitch, size_t rows, size_
 }
 uint8_t *TierAStage::device() {
     if (!d_)
-        d_ = tls_scratch().device(used_ + 256);
+        d_ = tls().scratch.device(used_ + 256);
     return d_;
 }
 void TierAStage::h2d(size_t off, size_t bytes) {
@@ -303,7 +348,7 @@ int32_t svt_hip_device_count(void) {
 }
 
 int32_t svt_hip_init(int32_t device_ordinal) {
-    std::lock_guard<std::mutex> lk(g_mutex);
+    std::lock_guard<std::mutex> lk(g.mutex);
     int                         n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
         set_error("no HIP device visible");
@@ -313,10 +358,10 @@ int32_t svt_hip_init(int32_t device_ordinal) {
         set_error("device ordinal %d out of range (%d devices)", device_ordinal, n);
         return SVT_HIP_ERR_BAD_PARAMETER;
     }
-    if (g_sticky.load() >= 0 && g_sticky.load() != device_ordinal) {
+    if (g.sticky.load() >= 0 && g.sticky.load() != device_ordinal) {
         // per-thread streams, scratch buffers and the once-uploaded constant tables stay on the first device: one process
         // = one GPU (the multi-GPU layout is one process per GPU)
-        set_error("already bound to device %d: one process drives one GPU", g_sticky.load());
+        set_error("already bound to device %d: one process drives one GPU", g.sticky.load());
         return SVT_HIP_ERR_BAD_PARAMETER;
     }
     SVT_HIP_CHECK(hipSetDevice(device_ordinal));
@@ -327,30 +372,32 @@ int32_t svt_hip_init(int32_t device_ordinal) {
                   prop.gcnArchName);
         return SVT_HIP_ERR_NO_DEVICE;
     }
-    const bool first = g_sticky.load() < 0;
-    g_device.store(device_ordinal);
-    g_sticky.store(device_ordinal);
-    if (first) {  // load every translation unit's code object now instead of inside the first calls of the host's worker threads,
-                  // and create the stream pool here: a worker thread's first call created its slot's stream under the pool lock, and the
-                  // six picture-analysis threads of the encoder, all starting at once, paid 16 ms each for it
+    g.cus.store(prop.multiProcessorCount);
+    if (g.sticky.load() < 0) {  // load every translation unit's code object now instead of inside the first calls of the host's worker
+                                // threads, and create the stream pool here: a worker thread's first call created its slot's stream under
+                                // the pool lock, and the six picture-analysis threads of the encoder, all starting at once, paid 16 ms each
         {
-            std::lock_guard<std::mutex> pk(g_pool_mutex);
-            for (int i = 0; i < STREAM_POOL; i++)
-                if (!g_pool_streams[i] && hipStreamCreateWithFlags(&g_pool_streams[i], hipStreamNonBlocking) != hipSuccess)
-                    g_pool_streams[i] = nullptr;  // created on demand by resolve_stream
+            std::lock_guard<std::mutex> pk(g.pool_mutex);
+            for (int i = 0; i < STREAM_POOL; i++) {
+                hipStream_t s = nullptr;
+                if (!g.pool[i].load(std::memory_order_relaxed) && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess)
+                    g.pool[i].store(s, std::memory_order_release);  // a slot that stays empty is created on demand by resolve_stream
+            }
         }
         run_module_warmups(nullptr);
-        SVT_HIP_CHECK(hipDeviceSynchronize());
+        SVT_HIP_CHECK(hipDeviceSynchronize());  // a failed warm-up leaves the library uninitialised: the next svt_hip_init repeats it
     }
+    g.sticky.store(device_ordinal);
+    g.device.store(device_ordinal);
     return SVT_HIP_OK;
 }
 
 void svt_hip_shutdown(void) {
-    std::lock_guard<std::mutex> lk(g_mutex);
-    g_device.store(-1);
+    std::lock_guard<std::mutex> lk(g.mutex);
+    g.device.store(-1);
 }
 
-const char *svt_hip_last_error(void) { return tls_err; }
+const char *svt_hip_last_error(void) { return tls().err; }
 const char *svt_hip_version(void) { return "svtav1-hip 0.1 (gfx950)"; }
 
 int32_t svt_hip_malloc(void **dptr, size_t bytes) {

@@ -171,19 +171,16 @@ int32_t svt_hip_publish_reference(void *d_picture, size_t bytes, int32_t owner, 
         return SVT_HIP_ERR_RUNTIME;
     hipStream_t prod = resolve_stream(producer_stream), side = (hipStream_t)side_stream;
     // order the broadcast behind the kernels that wrote the picture: an event of the producer stream, awaited by the side stream
-    static thread_local hipEvent_t produced = nullptr;
-    if (!produced)
-        SVT_HIP_CHECK(hipEventCreateWithFlags(&produced, hipEventDisableTiming));
+    hipEvent_t &produced = tls().produced;
+    SVT_HIP_CHECK(ensure_event(produced));
     SVT_HIP_CHECK(hipEventRecord(produced, prod));
     SVT_HIP_CHECK(hipStreamWaitEvent(side, produced, 0));
     RCCL_CHECK(r, r->Broadcast(d_picture, d_picture, bytes, ncclUint8, owner, (ncclComm_t)comm, side));
     if (done) {
-        if (!*done) {
-            hipEvent_t e;
-            SVT_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            *done = (void *)e;
-        }
-        SVT_HIP_CHECK(hipEventRecord((hipEvent_t)*done, side));
+        hipEvent_t e = (hipEvent_t)*done;
+        SVT_HIP_CHECK(ensure_event(e));
+        *done = (void *)e;
+        SVT_HIP_CHECK(hipEventRecord(e, side));
     }
     return SVT_HIP_OK;
 }

@@ -896,15 +896,16 @@ extern "C" int32_t svt_hip_tf_filter_picture(const SvtHipTfPictureJob *job, void
     const Layout l = layout(f.width, f.height, job->n_refs, 2);
     if (!job->workspace || job->workspace_bytes < layout(f.width, f.height, job->n_refs, 2).total)
         return bad("workspace too small (svt_hip_tf_workspace_bytes)");
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t    st = resolve_stream(stream);
+    TierBCall c("svt_hip_tf_filter_picture", stream);
+    if (!c.ok())
+        return c.status();
+    hipStream_t    st = c.stream();
     uint8_t       *ws = (uint8_t *)job->workspace;
     const uint32_t bw = (f.width + 63) / 64, nb = bw * ((f.height + 63) / 64);
 
     // ---- ME_MCTF of the centre picture against every reference picture: one launch
-    SvtHipMeFrameJob *mj = new SvtHipMeFrameJob[job->n_refs];
-    RefineRef         refs[SVT_HIP_TF_MAX_REFS];
+    SvtHipMeFrameJob mj[SVT_HIP_TF_MAX_REFS];  // on the stack: nothing is allocated on a launch path
+    RefineRef        refs[SVT_HIP_TF_MAX_REFS];
     for (uint32_t r = 0; r < job->n_refs; r++) {
         memset(&mj[r], 0, sizeof(mj[r]));
         mj[r].prm = job->me;
@@ -927,12 +928,11 @@ extern "C" int32_t svt_hip_tf_filter_picture(const SvtHipTfPictureJob *job, void
     }
     const bool low_delay = job->ctrls.low_delay != 0;
     int32_t    rc = low_delay ? (int32_t)SVT_HIP_OK : svt_hip_me_frames(mj, job->n_refs, st);  // the low-delay variant has no motion search
-    delete[] mj;
     if (rc != SVT_HIP_OK)
         return rc;
-    RefineRef *d_refs = (RefineRef *)stage_descriptors(refs, sizeof(RefineRef) * job->n_refs, st);
+    RefineRef *d_refs = (RefineRef *)c.stage(refs, sizeof(RefineRef) * job->n_refs);
     if (!d_refs)
-        return SVT_HIP_ERR_RUNTIME;
+        return c.status();
     RefineArgs a;
     memset(&a, 0, sizeof(a));
     a.ctrls = job->ctrls, a.centre = planes_of(job->centre);
@@ -966,8 +966,8 @@ extern "C" int32_t svt_hip_tf_filter_picture(const SvtHipTfPictureJob *job, void
     }
     SVT_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(tf_blocks_kernel, dim3(nb, job->n_refs + 1), dim3(256), 0, st, a, d_refs, job->n_refs, static_blocks, outs);
-    SVT_HIP_CHECK(hipGetLastError());
-    stage_commit(st);
+    if ((rc = c.finish()) != SVT_HIP_OK)
+        return rc;
     {  // central + the accumulation over every reference + normalise: one launch, accumulators in registers
         const SvtHipTfBlock *lists[SVT_HIP_TF_MAX_REFS];
         for (uint32_t r = 0; r < job->n_refs; r++) lists[r] = refs[r].blocks;

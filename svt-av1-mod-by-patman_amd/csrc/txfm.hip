@@ -69,16 +69,6 @@ __global__ __launch_bounds__(1024) void group_by_type_kernel(const SvtHipTxfmDes
             perm[base + start[key[k]] + rank[k]] = base + k * 1024 + threadIdx.x;
 }
 
-struct GroupWs {  // grow-only per-thread index buffer, guarded by an event against reuse from another stream
-    uint32_t  *perm = nullptr;
-    size_t     cap  = 0;
-    hipEvent_t ev   = nullptr;
-};
-GroupWs &tls_group_ws() {
-    static thread_local GroupWs w;
-    return w;
-}
-
 // Stand-alone quantiser: one workgroup per block of n coefficients.
 __global__ __launch_bounds__(256) void quantize_kernel(uint8_t *__restrict__ base, const SvtHipTxfmDesc *__restrict__ descs,
                                                        SvtHipTxfmResult *__restrict__ results, uint32_t n_coeffs) {
@@ -178,29 +168,15 @@ void launch_txfm(uint8_t *base, const SvtHipTxfmDesc *descs, SvtHipTxfmResult *r
     // Measured on the 4K 10-bit workload (DCT / ADST alternating between neighbours): the grouped launch is NOT faster — the
     // mixed-type waves cost 0-3 %, the grouping pass 13-30 us per launch — so it is off unless SVTAV1_HIP_GROUP_TX is set.
     static const bool group = getenv("SVTAV1_HIP_GROUP_TX") != nullptr;
-    if (G::NT > 1 && n >= GROUP_MIN_BLOCKS && group) {
-        GroupWs &w = tls_group_ws();
-        bool     ok = true;
-        if (!w.ev)
-            ok = hipEventCreateWithFlags(&w.ev, hipEventDisableTiming) == hipSuccess;
-        if (ok && w.cap < n) {
-            if (w.perm)
-                (void)hipFree(w.perm);  // synchronises: no launch still reads it
-            w.perm = nullptr, w.cap = 0;
-            ok = hipMalloc((void **)&w.perm, (size_t)n * sizeof(uint32_t)) == hipSuccess;
-            if (ok)
-                w.cap = n;
-        } else if (ok) {
-            ok = hipStreamWaitEvent(st, w.ev, 0) == hipSuccess;  // the previous user of the buffer may sit on another stream
-        }
-        if (ok) {
-            hipLaunchKernelGGL(group_by_type_kernel, dim3((n + GROUP_CHUNK - 1) / GROUP_CHUNK), dim3(1024), 0, st, descs, n, w.perm);
-            perm = w.perm;
-        }
-        hipLaunchKernelGGL((txfm_kernel<W, H>), dim3((n + G::NT - 1) / G::NT), dim3(G::NT * G::L), 0, st, base, descs, res, n, perm);
+    if (G::NT > 1 && n >= GROUP_MIN_BLOCKS && group && st) {  // (st == NULL: no pooled stream could be made; such calls go ungrouped)
+        // the per-thread index buffer (exactly n entries when it grows); its previous user may sit on another stream.  Without it
+        // the blocks go ungrouped: the result is the same
+        TierBCall c("transform grouping", (void *)st);
+        perm = (const uint32_t *)c.take(tls().txfm_perm, (size_t)n * sizeof(uint32_t), (size_t)n * sizeof(uint32_t));
         if (perm)
-            (void)hipEventRecord(w.ev, st);
-        return;
+            hipLaunchKernelGGL(group_by_type_kernel, dim3((n + GROUP_CHUNK - 1) / GROUP_CHUNK), dim3(1024), 0, st, descs, n, (uint32_t *)perm);
+        hipLaunchKernelGGL((txfm_kernel<W, H>), dim3((n + G::NT - 1) / G::NT), dim3(G::NT * G::L), 0, st, base, descs, res, n, perm);
+        return;  // the scope records the buffer's event behind the transform kernel
     }
     hipLaunchKernelGGL((txfm_kernel<W, H>), dim3((n + G::NT - 1) / G::NT), dim3(G::NT * G::L), 0, st, base, descs, res, n, perm);
 }

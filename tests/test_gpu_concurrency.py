@@ -382,6 +382,27 @@ def test_more_calls_in_flight_than_staging_slots(hip, orc, gold_intra):
         destroy(hip, *streams)
 
 
+def test_wiener_buffer_grows_with_work_in_flight(hip, orc):
+    """A fresh thread's buffer of raw moments starts empty: 2 units on s1 size it for 4, then, with nothing synchronised, 15 units
+    on s2 make it grow while the first call may still be using it."""
+    seed = 4100
+    a, b = WienerCase(hip, orc, 128, 64, 8, 0, 7, 64, seed), WienerCase(hip, orc, 264, 136, 10, 1, 5, 64, seed + 1)
+    assert (len(a.units), len(b.units)) == (2, 15)
+    s1, s2 = new_stream(hip), new_stream(hip)
+
+    def worker(t, fail):
+        keep = [a.issue(s1), b.issue(s2)]
+        sync(hip, s1, s2)
+        del keep
+        a.check("2 units on s1")
+        b.check("15 units on s2, grown buffer")
+    try:
+        failures = run_threads(1, worker)
+    finally:
+        destroy(hip, s1, s2)
+    assert not failures[0], failures[0]
+
+
 # ------------------------------------------------------------------------------------------------ 1c: many host threads, Tier A
 def same(a, b):
     if isinstance(a, tuple):
