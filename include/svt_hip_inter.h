@@ -1,6 +1,7 @@
 /*
  * svt_hip_inter.h — C-ABI for inter prediction: interpolation (the single-reference and the
- * compound ("jnt") families), the masked-compound and OBMC blends, and the compound mask search.
+ * compound ("jnt") families), the masked-compound and OBMC blends, the compound mask search, warped prediction (local warp
+ * and global motion) and the global-motion error / refinement.
  *
  * Reference interfaces replaced (paths relative to /root/reference):
  *   Source/Lib/Codec/common_dsp_rtcd.h:185-221   svt_av1_convolve_{2d_sr,x_sr,y_sr,2d_copy_sr},
@@ -13,7 +14,14 @@
  *   Source/Lib/C_DEFAULT/inter_prediction_c.c:15-40   svt_av1_build_compound_diffwtd_mask_d16_c
  *   Source/Lib/Codec/enc_inter_prediction.c:386-449, 501-547, 4676-4719   pick_interinter_wedge / pick_interinter_seg
  *                                                (use_rate == 0) and the residuals of svt_aom_calc_pred_masked_compound
- * Scaled references are not covered.  OBMC's neighbour predictions, inter-intra prediction and the rate model of the mask
+ *   Source/Lib/Codec/warped_motion.c:570-680, 718-820   svt_av1_warp_affine_c, svt_aom_dec_svt_av1_highbd_warp_affine_c (the
+ *                                                arithmetic of svt_av1_highbd_warp_affine_c on plain uint16 samples)
+ *   Source/Lib/Codec/warped_motion.c:357-363, 1045-1068   is_affine_shear_allowed, svt_get_shear_params
+ *   Source/Lib/Codec/enc_warped_motion.c:22-98   svt_av1_warp_error
+ *   Source/Lib/Codec/global_motion.c:86-251      add_param_offset, force_wmtype, svt_av1_refine_integerized_param
+ * The warp entry points are Tier B only: the RTCD pointers svt_av1_warp_affine / svt_av1_highbd_warp_affine have no leaf.
+ * Scaled references are not covered; the corner matching / RANSAC front end of global motion and svt_find_projection stay on
+ * the host.  OBMC's neighbour predictions, inter-intra prediction and the rate model of the mask
  * search (model_rd_with_curvfit) stay on the host.
  */
 #ifndef SVT_HIP_INTER_H
@@ -171,6 +179,97 @@ typedef struct SvtHipMaskSearchResult {
 /* d_result[i] belongs to d_desc[i].  Errors as svt_hip_blend_batch (d_result == NULL is a bad parameter too). */
 SVT_HIP_API int32_t svt_hip_compound_mask_search_batch(const SvtHipMaskSearchDesc *d_desc, SvtHipMaskSearchResult *d_result,
                                                        uint32_t n, void *stream);
+
+/* ---- Warped prediction (Tier B) ---------------------------------------------------------------------------------------
+ * One descriptor = one block of one plane, all pointers device memory: svt_av1_warp_affine_c, and for uint16 samples
+ * svt_aom_dec_svt_av1_highbd_warp_affine_c.  compound / fwd_offset / bck_offset / cbuf / cbuf_stride mean exactly what they
+ * mean in SvtHipConvolveDesc, so a warped and an interpolated prediction can be averaged with each other in either order, and
+ * SVT_HIP_BLEND_D16* descriptors can read a cbuf that a warp left.
+ *
+ * The filter table (svt_aom_warped_filter) is CALLER DATA like the wedge masks: one device pointer per call, [193][8] int16,
+ * SVT_HIP_WARP_FILTER_BYTES bytes are read from it.  The library holds no copy.
+ *
+ * The kernel SKIPS a descriptor (dst and cbuf keep every byte) with p_width == 0 or p_height == 0, a NULL ref, dst (unless compound == 1,
+ * which writes cbuf only) or cbuf (compound != 0), a field out of the range given below, or a shear that is_affine_shear_allowed refuses:
+ * 4 |alpha| + 7 |beta| >= 65536 or 4 |gamma| + 4 |delta| >= 65536.  That last check is what keeps the filter index inside
+ * the table. */
+#define SVT_HIP_WARP_FILTER_ROWS 193
+#define SVT_HIP_WARP_FILTER_BYTES (SVT_HIP_WARP_FILTER_ROWS * 8 * 2)
+
+typedef struct SvtHipWarpDesc {
+    const void *ref;        /* sample (0, 0) of the reference PLANE; reads are clamped to [0, width) x [0, height) as the
+                             * reference clamps them: nothing outside the plane is read */
+    void       *dst;        /* the predicted block (uint8, or uint16 with is_16bit) */
+    uint16_t   *cbuf;       /* ConvBufType [p_height][cbuf_stride] (compound != 0) */
+    uint32_t    ref_stride, dst_stride, cbuf_stride; /* in samples */
+    uint32_t    width, height;                       /* of the reference plane, 1 .. 65536 */
+    int32_t     p_col, p_row;                        /* position of the block in the plane, 0 .. 65535 */
+    uint16_t    p_width, p_height;                   /* 4 .. 128 (4: the chroma of an 8 x 8, cropped in the vertical filter) */
+    int32_t     mat[6];                              /* wmmat[0 .. 5]; ROTZOOM: the caller has set mat[5] = mat[2], mat[4] = -mat[3] */
+    int16_t     alpha, beta, gamma, delta;           /* EbWarpedMotionParams (svt_hip_warp_shear_params) */
+    uint8_t     subsampling_x, subsampling_y;        /* 0 / 1 */
+    uint8_t     round_0, round_1;                    /* ConvolveParams of get_conv_params: round_0 1 .. 7; compound: round_0 + round_1 <= 14 */
+    uint8_t     bit_depth, is_16bit;                 /* 8, 10 or 12 (8 unless is_16bit); 0 / 1 */
+    uint8_t     compound;                            /* 0 .. 3, as SvtHipConvolveDesc.compound */
+    uint8_t     fwd_offset, bck_offset;              /* compound 3 */
+    uint8_t     pad_[7];
+} SvtHipWarpDesc;
+/* d_filter: the filter table on the device.  Errors as svt_hip_blend_batch (d_filter == NULL is a bad parameter too).
+ * Asynchronous on `stream`. */
+SVT_HIP_API int32_t svt_hip_warp_batch(const SvtHipWarpDesc *d_desc, uint32_t n, const int16_t *d_filter, void *stream);
+
+/* svt_get_shear_params: alpha, beta, gamma, delta of mat into out[0 .. 3]; returns 1, or 0 for an invalid model (mat[2] <= 0 or
+ * a shear that is not allowed; out then holds whatever the reference would have left in the model).  Host only, no device. */
+SVT_HIP_API int32_t svt_hip_warp_shear_params(const int32_t mat[6], int16_t out[4]);
+
+/* ---- Global-motion error of a whole picture (Tier B) ------------------------------------------------------------------
+ * svt_av1_warp_error for 8-bit luma over the whole current picture, N candidate models per call: 32 x 32 error blocks in
+ * raster order (the last column / row narrower), with chess_refn every other block (the start alternates per block row) and
+ * the final sum doubled, and the early exit: as soon as the running, un-doubled sum exceeds the candidate's best_error, that
+ * partial sum is the result.  Every visited block's SAD goes to the workspace; a raster-order prefix pass per candidate then
+ * returns the first prefix > best_error, else the total.  ConvolveParams are those of get_conv_params(0, 0, 0, 8). */
+#define SVT_HIP_WARP_ERROR_BLOCK 32
+#define SVT_HIP_WARP_ERROR_OK 0
+#define SVT_HIP_WARP_ERROR_BAD_SHEAR 1 /* is_affine_shear_allowed refuses alpha .. delta: error 0, blocks_summed 0 */
+
+typedef struct SvtHipWarpErrorJob {  /* host memory; the pointers in it are device memory */
+    const uint8_t *ref, *cur;        /* reference and current luma planes, sample (0, 0) */
+    const int16_t *filter;           /* svt_aom_warped_filter, SVT_HIP_WARP_FILTER_BYTES */
+    void          *workspace;        /* svt_hip_warp_error_workspace_bytes(cur_width, cur_height, n) */
+    uint64_t       workspace_bytes;
+    uint32_t       ref_stride, ref_width, ref_height;
+    uint32_t       cur_stride, cur_width, cur_height;
+    uint8_t        chess_refn;       /* 0 / 1 */
+    uint8_t        pad_[7];
+} SvtHipWarpErrorJob;
+
+typedef struct SvtHipWarpCandidate {
+    int32_t mat[6];                  /* as SvtHipWarpDesc.mat */
+    int16_t alpha, beta, gamma, delta;
+    int64_t best_error;              /* early-exit threshold */
+} SvtHipWarpCandidate;
+
+typedef struct SvtHipWarpErrorResult {
+    int64_t  error;
+    uint32_t blocks_summed;          /* 32 x 32 blocks that entered `error` */
+    uint8_t  status;                 /* SVT_HIP_WARP_ERROR_* */
+    uint8_t  pad_[3];
+} SvtHipWarpErrorResult;
+/* Layout only, needs no device: n * blocks * 4 bytes of block SADs, rounded up, plus one result slot that svt_hip_gm_refine uses.
+ * 0 when width, height or n is 0. */
+SVT_HIP_API uint64_t svt_hip_warp_error_workspace_bytes(uint32_t width, uint32_t height, uint32_t n);
+/* d_result[i] belongs to d_cand[i].  SVT_HIP_ERR_BAD_PARAMETER for a NULL pointer, n == 0 or n > 65535, an empty picture, a stride smaller
+ * than its width or a workspace that is too small.  Asynchronous on `stream`; calls on one stream may share a workspace. */
+SVT_HIP_API int32_t svt_hip_warp_error_batch(const SvtHipWarpErrorJob *job, const SvtHipWarpCandidate *d_cand,
+                                             SvtHipWarpErrorResult *d_result, uint32_t n, void *stream);
+
+/* svt_av1_refine_integerized_param on device-resident pictures: the hill climb over wmmat[0 .. n_params) with step 16 halved
+ * n_refinements times, every svt_av1_warp_error replaced by a one-candidate svt_hip_warp_error_batch and an 8-byte read-back,
+ * in the reference's order with its running best_error as the threshold.  A model that fails svt_hip_warp_shear_params
+ * evaluates to error 1, as in the reference.  wmtype in / out: TransformationType 0 IDENTITY, 1 TRANSLATION, 2 ROTZOOM,
+ * 3 AFFINE.  job->workspace serves one candidate.  Synchronous. */
+SVT_HIP_API int32_t svt_hip_gm_refine(const SvtHipWarpErrorJob *job, int32_t wmmat[8], int32_t *wmtype, int32_t n_refinements,
+                                      int64_t best_frame_error, int64_t *error, void *stream);
 
 #ifdef __cplusplus
 }

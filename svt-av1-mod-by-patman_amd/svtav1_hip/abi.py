@@ -301,6 +301,40 @@ MASK_SEARCH_RESULT_DTYPE = [("wedge_sse", "<u8", (WEDGE_TYPES,)), ("diffwtd_sse"
                             ("best_diffwtd_type", "u1"), ("status", "u1")]
 
 
+WARP_FILTER_ROWS, WARP_FILTER_BYTES = 193, 193 * 8 * 2                          # SVT_HIP_WARP_FILTER_*
+WARP_ERROR_BLOCK = 32
+WARP_ERROR_OK, WARP_ERROR_BAD_SHEAR = range(2)                                  # SVT_HIP_WARP_ERROR_*
+
+
+class WarpDesc(C.Structure):             # SvtHipWarpDesc (include/svt_hip_inter.h)
+    _fields_ = [("ref", C.c_void_p), ("dst", C.c_void_p), ("cbuf", C.c_void_p), ("ref_stride", C.c_uint32), ("dst_stride", C.c_uint32),
+                ("cbuf_stride", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("p_col", C.c_int32), ("p_row", C.c_int32),
+                ("p_width", C.c_uint16), ("p_height", C.c_uint16), ("mat", C.c_int32 * 6), ("alpha", C.c_int16), ("beta", C.c_int16),
+                ("gamma", C.c_int16), ("delta", C.c_int16), ("subsampling_x", C.c_uint8), ("subsampling_y", C.c_uint8),
+                ("round_0", C.c_uint8), ("round_1", C.c_uint8), ("bit_depth", C.c_uint8), ("is_16bit", C.c_uint8), ("compound", C.c_uint8),
+                ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8), ("pad_", C.c_uint8 * 7)]
+
+
+class WarpErrorJob(C.Structure):         # SvtHipWarpErrorJob
+    _fields_ = [("ref", C.c_void_p), ("cur", C.c_void_p), ("filter", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_uint64),
+                ("ref_stride", C.c_uint32), ("ref_width", C.c_uint32), ("ref_height", C.c_uint32), ("cur_stride", C.c_uint32),
+                ("cur_width", C.c_uint32), ("cur_height", C.c_uint32), ("chess_refn", C.c_uint8), ("pad_", C.c_uint8 * 7)]
+
+
+class WarpCandidate(C.Structure):        # SvtHipWarpCandidate
+    _fields_ = [("mat", C.c_int32 * 6), ("alpha", C.c_int16), ("beta", C.c_int16), ("gamma", C.c_int16), ("delta", C.c_int16),
+                ("best_error", C.c_int64)]
+
+
+class WarpErrorResult(C.Structure):      # SvtHipWarpErrorResult
+    _fields_ = [("error", C.c_int64), ("blocks_summed", C.c_uint32), ("status", C.c_uint8), ("pad_", C.c_uint8 * 3)]
+
+
+# numpy views of arrays of SvtHipWarpCandidate / SvtHipWarpErrorResult
+WARP_CANDIDATE_DTYPE = [("mat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2"), ("best_error", "<i8")]
+WARP_ERROR_RESULT_DTYPE = [("error", "<i8"), ("blocks_summed", "<u4"), ("status", "u1"), ("pad_", "u1", (3,))]
+
+
 class TfBlock(C.Structure):              # SvtHipTfBlock (include/svt_hip_tf.h)
     _fields_ = [("src", C.c_void_p * 3), ("pred", C.c_void_p * 3), ("accum", C.c_void_p * 3), ("count", C.c_void_p * 3),
                 ("src_stride", C.c_uint32 * 3), ("pred_stride", C.c_uint32 * 3), ("decay_factor_fp16", C.c_uint32 * 3),

@@ -170,6 +170,43 @@ def compound_mask_search_batch(lib, descs, stream=None, fill=0xA5):
     return d_res.download(np.dtype(abi.MASK_SEARCH_RESULT_DTYPE), (len(descs),), stream)
 
 
+def warp_batch(lib, descs, d_filter, stream=None, sync=True):
+    """svt_hip_warp_batch over a list of abi.WarpDesc (one launch); d_filter: device address of the [193][8] int16 filter table."""
+    d_desc = upload_descriptors(lib, descs, stream)
+    check(lib, lib.svt_hip_warp_batch(C.c_void_p(d_desc.ptr), C.c_uint32(len(descs)), C.c_void_p(d_filter), C.c_void_p(stream)),
+          "svt_hip_warp_batch")
+    if sync:
+        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+    return d_desc
+
+
+def warp_error_workspace(lib, job, n=1):
+    """Allocates job.workspace for n candidates; keep the returned buffer alive as long as the job is used."""
+    ws = DeviceBuffer(lib, lib.svt_hip_warp_error_workspace_bytes(job.cur_width, job.cur_height, n))
+    job.workspace, job.workspace_bytes = ws.ptr, ws.nbytes
+    return ws
+
+
+def warp_error_batch(lib, job, candidates, stream=None, fill=0xA5):
+    """svt_hip_warp_error_batch: candidates is a numpy record array (abi.WARP_CANDIDATE_DTYPE); the results come back as one of
+    abi.WARP_ERROR_RESULT_DTYPE.  The result buffer is pre-filled with `fill`."""
+    cand = np.ascontiguousarray(candidates, np.dtype(abi.WARP_CANDIDATE_DTYPE))
+    d_cand, d_res = DeviceBuffer(lib, cand.nbytes), DeviceBuffer(lib, C.sizeof(abi.WarpErrorResult) * len(cand))
+    d_cand.upload(cand, stream)
+    d_res.fill(fill, stream)
+    check(lib, lib.svt_hip_warp_error_batch(C.byref(job), C.c_void_p(d_cand.ptr), C.c_void_p(d_res.ptr), C.c_uint32(len(cand)),
+                                            C.c_void_p(stream)), "svt_hip_warp_error_batch")
+    return d_res.download(np.dtype(abi.WARP_ERROR_RESULT_DTYPE), (len(cand),), stream)
+
+
+def gm_refine(lib, job, wmmat, wmtype, n_refinements, best_frame_error, stream=None):
+    """svt_hip_gm_refine: (wmmat[8] as a list, wmtype, error) after the hill climb."""
+    mat, wt, err = (C.c_int32 * 8)(*wmmat), C.c_int32(wmtype), C.c_int64(0)
+    check(lib, lib.svt_hip_gm_refine(C.byref(job), mat, C.byref(wt), C.c_int32(n_refinements), C.c_int64(best_frame_error), C.byref(err),
+                                     C.c_void_p(stream)), "svt_hip_gm_refine")
+    return list(mat), wt.value, err.value
+
+
 class DeviceMap:
     """Uploads host arrays on first use and hands out their device addresses (keyed by the host address)."""
 
