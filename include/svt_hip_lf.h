@@ -8,6 +8,8 @@
  *   Source/Lib/Codec/aom_dsp_rtcd.c:207-208      svt_compute_cdef_dist_16bit, svt_compute_cdef_dist_8bit
  *   Source/Lib/Codec/cdef_process.c:106-349      cdef_seg_search            (Tier B: svt_hip_cdef_search_plane)
  *   Source/Lib/Codec/enc_cdef.c:284-610          svt_av1_cdef_frame         (Tier B: svt_hip_cdef_apply_plane)
+ *   Source/Lib/Codec/enc_cdef.c:697-727, 728-926 joint_strength_search_dual, finish_cdef_search
+ *                                                                           (Tier B: svt_hip_cdef_pick_strengths)
  */
 #ifndef SVT_HIP_LF_H
 #define SVT_HIP_LF_H
@@ -96,6 +98,51 @@ SVT_HIP_API int32_t svt_hip_cdef_apply_plane(const SvtHipCdefPlane *plane, const
 SVT_HIP_API int32_t svt_hip_cdef_apply_frame(const SvtHipCdefPlane *planes, uint32_t n_planes, const uint8_t *d_filt8x8,
                                              const uint8_t *const *fb_strength_dptrs, int32_t damping, int32_t coeff_shift,
                                              const uint8_t *d_dir, const int32_t *d_var, void *stream);
+
+/* finish_cdef_search (enc_cdef.c:728-926) between the two: the picture's strength decision taken on the device from the
+ * tables svt_hip_cdef_search_plane wrote, for use_reference_cdef_fs == 0 and 64x64 superblocks.  Not covered (the caller
+ * keeps such pictures on the host): use_reference_cdef_fs (:744-795) and 128x128 superblocks, whose odd filter blocks
+ * are left out of the search (:824-827).
+ *   takes part   a filter block with at least one non-zero 8x8 in its filt8x8 tile (!skip_cdef_seg)
+ *   costs        luma = plane 0; chroma = U + V, or 1040400 * 64 where strengths_uv[gi] == -1 (cdef_process.c:251);
+ *                zero_fs_cost_bias scales entry 0 of both (:845-851)
+ *   search       joint_strength_search_dual (:697-727) per signalling width i = 0..3, start_gi = 0, end_gi = n_strengths;
+ *                ties between (luma, chroma) pairs go to the first in luma-major order as in svt_search_one_dual
+ *   choice       RDCOST(lambda, (sb_count * i + (1 << i) * 6 * 2) << 9, joint_mse * 16), first strictly smaller wins;
+ *                every block then takes the first gi with the strictly smallest cost0[y_index[gi]] + cost1[uv_index[gi]]
+ * All arithmetic is the reference's, modulo 2^64; with no block taking part the same arithmetic gives width 0, index 0. */
+typedef struct SvtHipCdefPickParams {
+    int32_t  n_strengths;      /* first_pass_fs_num + default_second_pass_fs_num = end_gi of the reference, 1..64 */
+    uint32_t fb_cols, fb_rows; /* 64x64 filter-block grid */
+    uint32_t w8, h8;           /* dimensions of filt8x8 (row stride w8); must reach into every filter block */
+    uint16_t zero_fs_cost_bias;/* 0 = off; else cost[.][fb][0] = (bias * cost) >> 6 for both tables */
+    uint16_t pad_;
+    uint64_t lambda;           /* full_lambda of the picture (svt_aom_av1_lambda_assignment_function_table, :808-815) */
+    int8_t   strengths[SVT_HIP_CDEF_MAX_STRENGTHS];    /* luma list given to the search (pri*4+sec), 0..63: the reference's
+                                                        * filter_map (:911-919), used for BOTH planes' output */
+    int8_t   strengths_uv[SVT_HIP_CDEF_MAX_STRENGTHS]; /* chroma list given to the search; -1 = not tested */
+} SvtHipCdefPickParams;
+
+typedef struct SvtHipCdefPickResult { /* ONE record in device memory */
+    int32_t  cdef_bits, nb_strengths, sb_count, pad_;
+    int32_t  y_index[8], uv_index[8];       /* winner: indices into the searched list (before filter_map); unused slots 0 */
+    uint8_t  y_strength[8], uv_strength[8]; /* winner after filter_map = frm_hdr->cdef_params.cdef_y/uv_strength */
+    uint64_t best_cost;                     /* RDCOST of the winner */
+    uint64_t joint_mse[4], rd_cost[4];      /* per signalling width: joint_strength_search_dual's return, and its RDCOST */
+    int32_t  lev0[4][8], lev1[4][8];        /* per width: the final best_lev0 / best_lev1 (entries >= 1 << i are 0) */
+} SvtHipCdefPickResult;
+
+/* Bytes of d_workspace for a grid of n_fb filter blocks: layout arithmetic, no device; 0 for an empty grid or list. */
+SVT_HIP_API uint64_t svt_hip_cdef_pick_workspace_bytes(uint32_t n_fb, int32_t n_strengths);
+/* prm is read on the host; everything else is device memory, n_fb = fb_cols * fb_rows:
+ *   d_mse          uint64 [3][n_fb][n_strengths], the three planes as svt_hip_cdef_search_plane wrote them; not modified
+ *   d_fb_gi        uint8 [n_fb]: mbmi.cdef_strength of each filter block, 0xFF where the block takes no part
+ *   d_fb_strength  uint8 [2][n_fb]: luma, then chroma strength value per block, what svt_hip_cdef_apply_frame takes;
+ *                  0 where the block takes no part
+ * The call enqueues its launches on `stream` and returns; it neither synchronises nor reads anything back. */
+SVT_HIP_API int32_t svt_hip_cdef_pick_strengths(const SvtHipCdefPickParams *prm, const uint64_t *d_mse, const uint8_t *d_filt8x8,
+                                                SvtHipCdefPickResult *d_result, uint8_t *d_fb_gi, uint8_t *d_fb_strength,
+                                                void *d_workspace, uint64_t workspace_bytes, void *stream);
 
 /* =============================================================================================
  * Deblocking

@@ -190,6 +190,29 @@ class CdefSearchParams(C.Structure):
                 ("sec_damping", C.c_int32), ("coeff_shift", C.c_int32), ("subsampling_factor", C.c_int32)]
 
 
+CDEF_MAX_STRENGTHS = 64           # SVT_HIP_CDEF_MAX_STRENGTHS
+CDEF_PICK_WIDTHS, CDEF_PICK_MAX_LEVELS = 4, 8   # signalling widths cdef_bits 0..3; CDEF_MAX_STRENGTHS of the reference
+
+
+class CdefPickParams(C.Structure):   # SvtHipCdefPickParams
+    _fields_ = [("n_strengths", C.c_int32), ("fb_cols", C.c_uint32), ("fb_rows", C.c_uint32), ("w8", C.c_uint32), ("h8", C.c_uint32),
+                ("zero_fs_cost_bias", C.c_uint16), ("pad_", C.c_uint16), ("lambda", C.c_uint64),
+                ("strengths", C.c_int8 * CDEF_MAX_STRENGTHS), ("strengths_uv", C.c_int8 * CDEF_MAX_STRENGTHS)]
+
+
+class CdefPickResult(C.Structure):   # SvtHipCdefPickResult
+    _fields_ = [("cdef_bits", C.c_int32), ("nb_strengths", C.c_int32), ("sb_count", C.c_int32), ("pad_", C.c_int32),
+                ("y_index", C.c_int32 * 8), ("uv_index", C.c_int32 * 8), ("y_strength", C.c_uint8 * 8), ("uv_strength", C.c_uint8 * 8),
+                ("best_cost", C.c_uint64), ("joint_mse", C.c_uint64 * 4), ("rd_cost", C.c_uint64 * 4),
+                ("lev0", (C.c_int32 * 8) * 4), ("lev1", (C.c_int32 * 8) * 4)]
+
+
+# numpy view of SvtHipCdefPickResult
+CDEF_PICK_RESULT_DTYPE = [("cdef_bits", "<i4"), ("nb_strengths", "<i4"), ("sb_count", "<i4"), ("pad_", "<i4"), ("y_index", "<i4", (8,)),
+                          ("uv_index", "<i4", (8,)), ("y_strength", "u1", (8,)), ("uv_strength", "u1", (8,)), ("best_cost", "<u8"),
+                          ("joint_mse", "<u8", (4,)), ("rd_cost", "<u8", (4,)), ("lev0", "<i4", (4, 8)), ("lev1", "<i4", (4, 8))]
+
+
 class LfMi(C.Structure):          # SvtHipLfMi (include/svt_hip_lf.h)
     _fields_ = [(n, C.c_uint8) for n in ("bsize", "tx_size_y", "tx_size_uv", "skip_inter", "segment_id", "ref_frame0", "mode_lf",
                                          "reserved")]

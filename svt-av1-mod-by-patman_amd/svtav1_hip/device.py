@@ -170,6 +170,29 @@ def compound_mask_search_batch(lib, descs, stream=None, fill=0xA5):
     return d_res.download(np.dtype(abi.MASK_SEARCH_RESULT_DTYPE), (len(descs),), stream)
 
 
+class DeviceCdefPick:
+    """Result record, per-block outputs and workspace of svt_hip_cdef_pick_strengths for a grid of n_fb filter blocks, pre-filled
+    with `fill`.  run() only enqueues; download() waits for the stream."""
+
+    def __init__(self, lib, n_fb, n_strengths, fill=0xA5):
+        self.lib, self.n_fb = lib, n_fb
+        self.result = DeviceBuffer(lib, C.sizeof(abi.CdefPickResult))
+        self.fb_gi, self.fb_strength = DeviceBuffer(lib, n_fb), DeviceBuffer(lib, 2 * n_fb)
+        self.workspace = DeviceBuffer(lib, lib.svt_hip_cdef_pick_workspace_bytes(n_fb, n_strengths))
+        for b in (self.result, self.fb_gi, self.fb_strength, self.workspace):
+            b.fill(fill)
+        check(lib, lib.svt_hip_stream_sync(None), "svt_hip_stream_sync")
+
+    def run(self, prm, d_mse, d_filt8x8, stream=None):
+        return self.lib.svt_hip_cdef_pick_strengths(C.byref(prm), d_mse, d_filt8x8, self.result.ptr, self.fb_gi.ptr, self.fb_strength.ptr,
+                                                    self.workspace.ptr, self.workspace.nbytes, stream)
+
+    def download(self, stream=None):
+        return {"result": self.result.download(np.dtype(abi.CDEF_PICK_RESULT_DTYPE), (), stream),
+                "fb_gi": self.fb_gi.download(np.uint8, (self.n_fb,), stream),
+                "fb_strength": self.fb_strength.download(np.uint8, (2, self.n_fb), stream)}
+
+
 def warp_batch(lib, descs, d_filter, stream=None, sync=True):
     """svt_hip_warp_batch over a list of abi.WarpDesc (one launch); d_filter: device address of the [193][8] int16 filter table."""
     d_desc = upload_descriptors(lib, descs, stream)
