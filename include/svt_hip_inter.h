@@ -39,7 +39,10 @@ typedef struct SvtHipInterpFilterParams { /* InterpFilterParams, definitions.h:7
     int32_t        interp_filter;
 } SvtHipInterpFilterParams;
 
-/* Tier A: RTCD signatures, host pointers (the highbd functions take real uint16 pointers, as in the reference). */
+/* Tier A: RTCD signatures, host pointers (the highbd functions take real uint16 pointers, as in the reference).
+ * w, h: 1 .. 128, any value (not only the block sizes); filter_params->taps: an even number <= 8, the table [16][taps].  Anything
+ * else is refused before a kernel runs ("unsupported block"), which takes the Tier A failure path of svt_hip.h: the hot path
+ * is disabled and the host's own function completes the call. */
 #define SVT_HIP_DECL_CONV(mode)                                                                                                  \
     SVT_HIP_API void svt_av1_convolve_##mode##_hip(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride,      \
                                                    int32_t w, int32_t h, SvtHipInterpFilterParams *filter_params_x,              \
@@ -77,14 +80,21 @@ SVT_HIP_DECL_JNT(2d_copy)
 #undef SVT_HIP_DECL_JNT
 
 /* Tier B: one descriptor per predicted block, all pointers device memory.  taps_x / taps_y == 0 selects what the
- * reference dispatches to when that direction has no sub-pel offset (x_sr, y_sr, 2d_copy_sr). */
+ * reference dispatches to when that direction has no sub-pel offset (x_sr, y_sr, 2d_copy_sr).
+ * Descriptors are NOT validated (they live in device memory): the launch covers the first 2 x 2 tiles of 64 x 64 of every
+ * block, so of a block wider or taller than 128 only that part is written; taps above 8 or odd are undefined.  Exactly the
+ * w x h rectangle of dst (compound 0, 2, 3) or of cbuf (compound 1) is written and nothing else; compound 1 never touches dst,
+ * compound 2 / 3 only read cbuf. */
 typedef struct SvtHipConvolveDesc {
     const void *src;        /* sample the block's (0,0) maps to in the reference plane; taps/2-1 samples are read to the
-                             * left / above and taps/2 to the right / below */
+                             * left / above and taps/2 to the right / below, none in a direction with taps == 0; the
+                             * result depends on no other sample */
     void       *dst;
     uint32_t    src_stride, dst_stride; /* in samples */
-    uint16_t    w, h;                   /* 2 .. 128; a descriptor with w == 0 or h == 0 is skipped */
-    int16_t     filter_x[8], filter_y[8]; /* the kernels of this block's sub-pel phases (av1_get_interp_filter_subpel_kernel) */
+    uint16_t    w, h;                   /* 1 .. 128, any value (the reference's callers use 2 .. 128); a descriptor with w == 0 or
+                                         * h == 0 is skipped, its pointers may be null */
+    int16_t     filter_x[8], filter_y[8]; /* the kernels of this block's sub-pel phases (av1_get_interp_filter_subpel_kernel):
+                                           * the first taps_x / taps_y entries, the rest is ignored */
     uint8_t     taps_x, taps_y;         /* 0, or an even number <= 8 */
     uint8_t     round_0, round_1;       /* ConvolveParams of get_conv_params (convolve.h:40-68) */
     uint8_t     bit_depth, is_16bit;

@@ -42,6 +42,71 @@ def test_convolve_sr(orc, ref, bd, is16):
         ty = 8 if mode in ("2d_sr", "y_sr") else 0
         orc.orc_convolve_sr(V(at), plane.shape[1], P(o2), w + 3, w, h, V(tab[sx].ctypes.data), tx, V(tab[sy].ctypes.data), ty, r0, r1, bd, is16)
         assert np.array_equal(o1, o2), (trial, mode, w, h, sx, sy)
+    # the extended cases: every table, x table != y table, every block shape, taps 2 / 4 / 6, the adversarial planes
+    fns = [fns[m + "_sr"] for m in K.MODES]
+    rng, n = np.random.default_rng(4120 + bd), 0
+    for i, c in enumerate(K.ext_cases(bd)):
+        plane, at = K.ext_plane(rng, c)
+        o1, o2 = ext_run_fn_sr(fns, c, plane, at, ConvolveParams, K.InterpFilterParams), ext_run_orc_sr(orc, c, plane, at)
+        assert np.array_equal(o1, o2), (i, c)
+        n += 1
+    print(f"convolve_sr bd {bd}: {n} extended cases")
+
+
+def ext_filters(c):
+    """the x and y tables of a case as its InterpFilterParams' taps see them: [16][taps]"""
+    return K.narrow_table(c.tx, c.taps[0]), K.narrow_table(c.ty, c.taps[1])
+
+
+def ext_run_orc_sr(orc, c, plane, at):
+    """one extended case through the oracle; the result keeps 3 columns of padding, which must stay as they were"""
+    tabx, taby = ext_filters(c)
+    r0, r1 = K.conv_rounds(c.bd)
+    o = np.full((c.h, c.w + 3), 0xA5, plane.dtype)
+    orc.orc_convolve_sr(V(at), plane.shape[1], P(o), c.w + 3, c.w, c.h, V(tabx[c.sx].ctypes.data), c.use[0], V(taby[c.sy].ctypes.data), c.use[1],
+                        r0, r1, c.bd, c.is16)
+    return o
+
+
+def ext_run_fn_sr(fns, c, plane, at, CP, FP):
+    """the same through functions with the reference's signatures, fns[mode] (the reference's own, or the HIP Tier A leaves)"""
+    tabx, taby = ext_filters(c)
+    r0, r1 = K.conv_rounds(c.bd)
+    fx, fy = FP(tabx.ctypes.data, c.taps[0], 16, 0), FP(taby.ctypes.data, c.taps[1], 16, 0)
+    cp = CP(round_0=r0, round_1=r1)
+    o = np.full((c.h, c.w + 3), 0xA5, plane.dtype)
+    fns[c.mode](*([V(at), plane.shape[1], P(o), c.w + 3, c.w, c.h, C.byref(fx), C.byref(fy), c.sx, c.sy, C.byref(cp)] + ([c.bd] if c.is16 else [])))
+    return o
+
+
+def ext_run_orc_jnt(orc, c, p0, a0, p1, a1, avg, fwd, bck):
+    """both predictions of an extended compound case through the oracle (the same kernels for both references): returns
+    (conv buffer after the first, pixels after the second), both with padding columns"""
+    tabx, taby = ext_filters(c)
+    r0, r1 = K.conv_rounds_compound(c.bd)
+    cb, out = np.full((c.h, c.w + 5), 0xA5A5, np.uint16), np.full((c.h, c.w + 3), 0xA5, p0.dtype)
+    for at, plane, comp in ((a0, p0, 1), (a1, p1, avg)):
+        orc.orc_convolve_jnt(V(at), plane.shape[1], P(out), c.w + 3, c.w, c.h, V(tabx[c.sx].ctypes.data), c.use[0], V(taby[c.sy].ctypes.data),
+                             c.use[1], r0, r1, c.bd, c.is16, P(cb), c.w + 5, comp, fwd, bck)
+        if comp == 1:
+            first = cb.copy()
+    return first, out
+
+
+def ext_run_fn_jnt(fns, c, p0, a0, p1, a1, avg, fwd, bck, CP, FP):
+    tabx, taby = ext_filters(c)
+    r0, r1 = K.conv_rounds_compound(c.bd)
+    cb, out = np.full((c.h, c.w + 5), 0xA5A5, np.uint16), np.full((c.h, c.w + 3), 0xA5, p0.dtype)
+    fx, fy = FP(tabx.ctypes.data, c.taps[0], 16, 0), FP(taby.ctypes.data, c.taps[1], 16, 0)
+    cp = CP(do_average=0, dst=cb.ctypes.data, dst_stride=c.w + 5, round_0=r0, round_1=r1, is_compound=1)
+    tail = [c.bd] if c.is16 else []
+    fns[c.mode](*([V(a0), p0.shape[1], P(out), c.w + 3, c.w, c.h, C.byref(fx), C.byref(fy), c.sx, c.sy, C.byref(cp)] + tail))
+    first, dst_after_first = cb.copy(), out.copy()
+    cp.do_average, cp.use_jnt_comp_avg, cp.fwd_offset, cp.bck_offset = 1, int(avg == 3), fwd, bck
+    fns[c.mode](*([V(a1), p1.shape[1], P(out), c.w + 3, c.w, c.h, C.byref(fx), C.byref(fy), c.sx, c.sy, C.byref(cp)] + tail))
+    assert (dst_after_first == 0xA5).all(), "the first prediction of a compound wrote pixels"
+    assert np.array_equal(cb, first), "the second prediction of a compound wrote the conv buffer"
+    return first, out
 
 
 def test_convolve_oracle_vs_golden(orc):
@@ -101,6 +166,15 @@ def test_convolve_jnt(orc, ref, bd, is16):
         f1, o1 = run_fn_jnt(fns, c, bd, is16, ConvolveParams, K.InterpFilterParams)
         f2, o2 = run_orc_jnt(orc, c, bd, is16)
         assert np.array_equal(f1, f2) and np.array_equal(o1, o2), (i, c[:6])
+    rng, n = np.random.default_rng(4130 + bd), 0
+    for i, c in enumerate(K.ext_cases(bd)):
+        (p0, a0), (p1, a1) = K.ext_plane(rng, c), K.ext_plane(rng, c, second=True)
+        for avg, fwd, bck in K.ext_avgs(i, c):
+            f1, o1 = ext_run_fn_jnt(fns, c, p0, a0, p1, a1, avg, fwd, bck, ConvolveParams, K.InterpFilterParams)
+            f2, o2 = ext_run_orc_jnt(orc, c, p0, a0, p1, a1, avg, fwd, bck)
+            assert np.array_equal(f1, f2) and np.array_equal(o1, o2), (i, c, avg)
+            n += 1
+    print(f"jnt_convolve bd {bd}: {n} extended cases")
 
 
 def test_convolve_jnt_oracle_vs_golden(orc):
@@ -112,3 +186,16 @@ def test_convolve_jnt_oracle_vs_golden(orc):
             f, o = run_orc_jnt(orc, c, bd, is16)
             assert np.array_equal(f[:, :c[0]], g[f"first{k}"]) and np.array_equal(o[:, :c[0]], g[f"out{k}"]), k
             k += 1
+
+
+def test_convolve_ext_oracle_vs_golden(orc):
+    """the oracle against the reference's recorded results on the extended cases (holds without oracle/_ref)"""
+    n = 0
+    for c, p0, p1, fwd, bck, sr, first, avg, wtd in K.ext_golden():
+        a0, a1 = K.at_block(p0), K.at_block(p1)
+        assert np.array_equal(ext_run_orc_sr(orc, c, p0, a0)[:, :c.w], sr), c
+        for mode, want in ((2, avg), (3, wtd)):
+            f, o = ext_run_orc_jnt(orc, c, p0, a0, p1, a1, mode, fwd, bck)
+            assert np.array_equal(f[:, :c.w], first) and np.array_equal(o[:, :c.w], want), (c, mode)
+        n += 1
+    assert n == 16
