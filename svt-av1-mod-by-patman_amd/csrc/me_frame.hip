@@ -1507,6 +1507,13 @@ __global__ __launch_bounds__(WG_THREADS, SVT_HIP_ME_WGS) void me_b64_kernel(cons
                     hme_l2_round(L, c, f0, f1, part, a);
                 if (part == 0 && a.search) {
                     ME_SITE(step < 2 ? 0 : (step < 4 ? 1 : step - 2));
+#if SVT_HIP_ME_L1_DIRECT
+                    // HME level 1 searches 8 x 3 positions per quadrant: too little reuse for a staged window (uniform choice)
+                    const int direct_rows = step == 4 ? wg_direct_plan(L.sh, a.nd, a.src, a.row_dw, a.bw, a.bh) : -1;
+                    if (direct_rows >= 0)
+                        wg_direct_search(L.sh, a.nd, (uint32_t)direct_rows, a.src, a.row_dw, a.bh);
+                    else
+#endif
                     wg_multi_search(L.sh, a.nd, a.src, a.row_dw, a.bw, a.bh, L.win, a.cap);
                 }
             }

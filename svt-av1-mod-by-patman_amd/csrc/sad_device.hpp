@@ -240,6 +240,7 @@ __device__ __forceinline__ void quad_sad_fixed(const uint32_t *__restrict__ w, u
     out[0] = a0, out[1] = a1, out[2] = a2, out[3] = a3;
 }
 
+// (oct_row32 below repeats the BW = 32 sequence of this function on window dwords held in registers: keep the two in step)
 // Two horizontally adjacent quads (8 positions, window dword `w` onwards) in one walk over the block: the window dwords of a
 // row are read once for both (NF + 2 instead of 2 NF + 2), the 64-bit operand (d[j], d[j+1]) serves quad A against source
 // dword j and quad B against source dword j - 1, and the source row is read once.  out[0..3] = quad A, out[4..7] = quad B.
@@ -325,7 +326,8 @@ template <class SH>
 __device__ __forceinline__ void wg_multi_search(SH &sh, uint32_t n, const uint32_t *__restrict__ src,
                                        uint32_t src_row_dw, uint32_t bw, uint32_t bh, uint32_t *__restrict__ win,
                                        uint32_t win_cap_dw) {
-    const uint32_t tid = threadIdx.x;
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));  // opaque: or the planner's lane masks are hoisted out of the caller's loop, and spilled there
     // b128 source reads need 16-byte aligned rows (LDS addresses are 32-bit offsets: test the low bits)
     const bool src_aligned = (((uint32_t)(uintptr_t)src) & 15u) == 0 && (src_row_dw & 3u) == 0;
 #ifdef SVT_HIP_ME_PROFILE
@@ -582,6 +584,165 @@ __device__ __forceinline__ void wg_multi_search(SH &sh, uint32_t n, const uint32
         }
         if (key < KEY_NONE)
             atomicMin((unsigned long long *)&sh.best[d], (unsigned long long)key);
+    }
+    __syncthreads();
+}
+
+// ---- direct search: small windows read straight from the reference plane ----
+// A window of at most 8 x 4 positions is hardly reused (HME level 1: 363 staged dwords are read 480 times), so staging it costs
+// about as much as reading it: wg_direct_search leaves the window buffer, the plan and the passes out.
+#ifndef SVT_HIP_ME_L1_DIRECT
+#define SVT_HIP_ME_L1_DIRECT 1  // 0: diagnostic build, every search goes through wg_multi_search
+#endif
+#ifdef SVT_HIP_NO_QSAD  // the v_sad_u8 diagnostic build has no direct walk
+#undef SVT_HIP_ME_L1_DIRECT
+#define SVT_HIP_ME_L1_DIRECT 0
+#endif
+
+// One block row of 32 samples against 8 adjacent positions: the v_qsad_pk_u16_u8 sequence of oct_sad_fixed<32> (keep the two in
+// step) on window dwords 0..9 held in registers (three 16-byte loads; dwords 10 and 11 are not used).
+__device__ __forceinline__ void oct_row32(const u128v w0, const u128v w1, const u128v w2, const uint32_t *__restrict__ sr,
+                                          uint64_t &acc_a, uint64_t &acc_b) {
+    const uint32_t d[10] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y};
+#pragma unroll
+    for (uint32_t i = 0; i < 8; i += 4) {
+        const uint4 sv = *(const uint4 *)&sr[i];
+        acc_a = __builtin_amdgcn_qsad_pk_u16_u8(pair64(d[i], d[i + 1]), sv.x, acc_a);
+        acc_b = __builtin_amdgcn_qsad_pk_u16_u8(pair64(d[i + 1], d[i + 2]), sv.x, acc_b);
+        acc_a = __builtin_amdgcn_qsad_pk_u16_u8(pair64(d[i + 1], d[i + 2]), sv.y, acc_a);
+        acc_b = __builtin_amdgcn_qsad_pk_u16_u8(pair64(d[i + 2], d[i + 3]), sv.y, acc_b);
+        acc_a = __builtin_amdgcn_qsad_pk_u16_u8(pair64(d[i + 2], d[i + 3]), sv.z, acc_a);
+        acc_b = __builtin_amdgcn_qsad_pk_u16_u8(pair64(d[i + 3], d[i + 4]), sv.z, acc_b);
+        acc_a = __builtin_amdgcn_qsad_pk_u16_u8(pair64(d[i + 3], d[i + 4]), sv.w, acc_a);
+        acc_b = __builtin_amdgcn_qsad_pk_u16_u8(pair64(d[i + 4], d[i + 5]), sv.w, acc_b);
+    }
+}
+
+struct WinRow {
+    u128v a, b, c;
+};
+// 48 bytes of a window row from the window origin: the bytes stage_rows16 reads for a pitch of 11 dwords
+__device__ __forceinline__ WinRow load_win_row(const uint8_t *g, bool skip_loads) {
+    WinRow w = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+    if (!skip_loads)
+        w.a = load_u128_any(g), w.b = load_u128_any(g + 16), w.c = load_u128_any(g + 32);
+    return w;
+}
+
+// Can the n descriptors (written by threads 0..n-1, not yet behind a barrier) be searched by wg_direct_search?  The answer is
+// uniform over the workgroup: -1 = no (nothing has been done: call wg_multi_search), otherwise the largest number of searched
+// rows of a descriptor (0: nothing to search), with sh.best[] initialised and one barrier passed.  A "no" for the block shape
+// costs nothing; a "no" for a descriptor (M0's 16 x 16 level-1 area) comes after the barrier and a look at the descriptors, which
+// wg_multi_search then repeats with its own plan: a small cost on presets whose windows are large enough to be worth staging.
+// Eligible: at most 32 16-byte aligned source rows of 32 samples; every active descriptor steps its block rows by once or twice
+// the raw stride, and searches at most 8 positions in each of at most 4 consecutive rows.
+template <class SH>
+__device__ __forceinline__ int wg_direct_plan(SH &sh, uint32_t n, const uint32_t *__restrict__ src, uint32_t src_row_dw, uint32_t bw,
+                                              uint32_t bh) {
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));  // opaque: or the lane arithmetic below is hoisted out of the caller's loop and held in registers
+    if (bw != 32 || bh > 32 || n > (uint32_t)SH::MAXS || n > 64u || (((uint32_t)(uintptr_t)src) & 15u) != 0 || (src_row_dw & 3u) != 0)
+        return -1;
+    if (tid < n)
+        sh.best[tid] = KEY_NONE;
+    __syncthreads();
+    // every wave looks at all descriptors (lane = descriptor): no second barrier to spread the answer
+    const uint32_t lane = tid & 63u;
+    uint32_t       rows = 0;
+    bool           bad  = false;
+    if (lane < n) {
+        const SearchDesc &ds = sh.desc[lane];
+        if (ds.sa_w > 0 && ds.sa_h > 0) {
+            rows = (uint32_t)ds.sa_h;
+            bad  = ds.raw_stride == 0 || (ds.ref_stride != ds.raw_stride && ds.ref_stride != 2 * ds.raw_stride) || ds.sa_w > 8 ||
+                  ds.sa_h > 4 || ds.skip != 0;
+        }
+    }
+    if (__ballot(bad))
+        return -1;
+    return __ballot(rows >= 3) ? (__ballot(rows == 4) ? 4 : 3) : (__ballot(rows == 2) ? 2 : (__ballot(rows == 1) ? 1 : 0));
+}
+
+// `nrows` (at most 8: one 16-bit lane of the packed accumulator holds 8 * 32 * 255 = 65280) consecutive block rows of 32
+// samples against the 8 positions at window origin gp, added to sad[0..7].  One window row is held at a time: a variant that
+// loads the next row while this one is used needs 12 more registers, which the 64-register kernel that calls this spills
+// (scratch 48 -> 100 bytes per lane); the other workgroups of the CU cover the load latency instead.
+__device__ __forceinline__ void direct_walk32(const uint8_t *gp, uint32_t rstep, const uint32_t *__restrict__ sr, uint32_t src_row_dw,
+                                              uint32_t nrows, bool no_loads, bool no_sad, uint32_t sad[8]) {
+    uint64_t acc_a = 0, acc_b = 0;
+#pragma unroll 1
+    for (uint32_t r = 0; r < nrows; r++) {
+        const WinRow wa = load_win_row(gp, no_loads);
+        if (no_sad)
+            asm volatile("" ::"v"(wa.a), "v"(wa.b), "v"(wa.c));  // (ABLATE builds) the loads stay
+        else
+            oct_row32(wa.a, wa.b, wa.c, sr, acc_a, acc_b);
+        gp += rstep, sr += src_row_dw;
+    }
+    sad[0] += (uint32_t)(acc_a & 0xffff), sad[1] += (uint32_t)((acc_a >> 16) & 0xffff);
+    sad[2] += (uint32_t)((acc_a >> 32) & 0xffff), sad[3] += (uint32_t)(acc_a >> 48);
+    sad[4] += (uint32_t)(acc_b & 0xffff), sad[5] += (uint32_t)((acc_b >> 16) & 0xffff);
+    sad[6] += (uint32_t)((acc_b >> 32) & 0xffff), sad[7] += (uint32_t)(acc_b >> 48);
+}
+
+// Exhaustive search of n descriptors that wg_direct_plan accepted (`max_rows` = its answer), results in sh.best[] as
+// wg_multi_search leaves them.  A work item is one searched row of one descriptor (8 positions, two quads); all items form one
+// round.  The bh <= 32 block rows of an item are split over G adjacent lanes, each of which reads its window rows from global
+// memory and its source rows from LDS; the partial SADs are summed across the G lanes in 32 bits, and the first lane builds
+// the key.  G = 2 (measured against 1 and 4 on the 4K workload: 1.68 / 1.73 / 1.72 ms per launch); 1 when there are fewer than
+// two block rows per lane (b64 at the bottom edge), 4 when two lanes would get more than the 8 rows their 16-bit accumulators
+// hold (full SAD: 32 block rows).  Must be called by all WG_THREADS threads; ends with a barrier.
+template <class SH>
+__device__ __forceinline__ void wg_direct_search(SH &sh, uint32_t n, uint32_t max_rows, const uint32_t *__restrict__ src,
+                                                 uint32_t src_row_dw, uint32_t bh) {
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));  // (opaque, as in wg_direct_plan)
+    const uint32_t lg = bh < 4 ? 0u : (bh > 16 ? 2u : 1u);  // log2 G
+    const uint32_t rpl = (bh + (1u << lg) - 1u) >> lg, g = tid & ((1u << lg) - 1u);  // block rows per lane, lane within the item
+    const uint32_t rb = g * rpl, nrows = bh > rb ? (bh - rb < rpl ? bh - rb : rpl) : 0u;  // this lane's rows: [rb, rb + nrows)
+    const uint32_t inv = max_rows <= 1 ? 0u : (max_rows == 2 ? 0x80000000u : (max_rows == 3 ? 0x55555556u : 0x40000000u));
+#ifdef SVT_HIP_ME_ABLATE
+    const int      ms_skip = g_ms_skip;
+    const bool     no_loads = ms_skip & 1, no_sad = ms_skip & 2;
+    const uint32_t nslots = (ms_skip & 4) ? 0u : n * max_rows;
+#else
+    constexpr bool no_loads = false, no_sad = false;
+    const uint32_t nslots = n * max_rows;
+#endif
+    for (uint32_t slot = tid >> lg; slot < nslots; slot += (uint32_t)WG_THREADS >> lg) {
+        const uint32_t    d = fast_div(slot, inv), j = slot - d * max_rows;
+        const SearchDesc &ds = sh.desc[d];
+        const int32_t     saw = ds.sa_w;
+        if (saw <= 0 || (int32_t)j >= ds.sa_h)  // (the G lanes of an item leave together)
+            continue;
+        const uint32_t  rstep = ds.ref_stride;
+        const uint8_t  *gp = ds.ref + (size_t)(sad_mul_u24(j, ds.raw_stride) + sad_mul_u24(rb, rstep));
+        const uint32_t *sr = src + rb * src_row_dw;
+        uint32_t        sad[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        direct_walk32(gp, rstep, sr, src_row_dw, nrows, no_loads, no_sad, sad);
+        // sum over the G lanes of the item: quad_perm [1,0,3,2], then [2,3,0,1] (an item never straddles a group of four lanes)
+        if (lg >= 1) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) sad[i] += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sad[i], 0xB1, 0xf, 0xf, true);
+        }
+        if (lg >= 2) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) sad[i] += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sad[i], 0x4E, 0xf, 0xf, true);
+        }
+        if (no_sad) {  // (ABLATE builds)
+#pragma unroll
+            for (int i = 0; i < 8; i++) sad[i] = slot + i;
+        }
+        if (g == 0) {
+            // as in wg_multi_search: positions in raster order, (sad << 3 | position) keeps the first minimum
+            uint32_t kmin = ~0u;
+#pragma unroll
+            for (uint32_t p = 0; p < 8; p++) {
+                const uint32_t k = (int32_t)p < saw ? ((sad[p] << 3) | p) : ~0u;
+                kmin             = k < kmin ? k : kmin;
+            }
+            atomicMin((unsigned long long *)&sh.best[d], ((unsigned long long)(kmin >> 3) << 32) | ((j << 16) | (kmin & 7u)));
+        }
     }
     __syncthreads();
 }
