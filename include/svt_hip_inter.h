@@ -21,8 +21,9 @@
  *   Source/Lib/Codec/global_motion.c:86-251      add_param_offset, force_wmtype, svt_av1_refine_integerized_param
  * The warp entry points are Tier B only: the RTCD pointers svt_av1_warp_affine / svt_av1_highbd_warp_affine have no leaf.
  * Scaled references are not covered; the corner matching / RANSAC front end of global motion and svt_find_projection stay on
- * the host.  OBMC's neighbour predictions, inter-intra prediction and the rate model of the mask
- * search (model_rd_with_curvfit) stay on the host.
+ * the host.  OBMC's neighbour predictions and the rate model of the mask search (model_rd_with_curvfit) stay on the host.
+ * Inter-intra prediction is in svt_hip_intra.h: the smooth form is an epilogue of svt_hip_intra_predict_batch, the wedge form is
+ * that prediction followed by a SVT_HIP_BLEND_MASK descriptor here.
  */
 #ifndef SVT_HIP_INTER_H
 #define SVT_HIP_INTER_H

@@ -1,7 +1,9 @@
 /*
- * svt_hip_intra.h — C-ABI for the open-loop intra search of TPL level 1 (presets M0 - M4): the source-based intra search of every
- * 16x16 block of one or more pictures over the intra modes DC_PRED .. intra_mode_end, with SAD or SATD cost.
+ * svt_hip_intra.h — C-ABI for intra prediction: (1) the open-loop intra search of TPL level 1 (presets M0 - M4), (2) the AV1 intra
+ * predictor of any transform-block size as mode decision and EncDec call it, with the smooth inter-intra combination, and (3) CfL.
  *
+ * (1) svt_hip_intra_search_frames: the source-based intra search of every 16x16 block of one or more pictures over the intra modes
+ * DC_PRED .. intra_mode_end, with SAD or SATD cost.
  * Reference interface replaced (paths relative to the reference's Source/Lib):
  *   Codec/src_ops_process.c:519-760   the intra part of the source-based path of tpl_mc_flow_dispenser_sb_generic at
  *                                     dispenser_search_level 0 (16x16 blocks, TX_16X16) with in_loop_ois = 1, when the fast
@@ -13,8 +15,31 @@
  *   svt_aom_subtract_block -> svt_av1_wht_fwd_txfm (DCT_DCT 16x16, pf_shape) -> svt_aom_satd; the first strict minimum wins.
  * A searched block may reach 8 samples past the right / bottom edge of the picture: its cost then reads the source padding.
  * All pictures of one call are searched in one launch (one wavefront per block).
- * Not provided: the rest of TPL level 1 (SATD in the inter source search, the quarter-pel tree without diagonal refinement, the rate
- * estimate), subsample_tx != 0, 10-bit input, 32x32 / 64x64 blocks, angle deltas, CfL, filter-intra.
+ * Not provided by the search: the rest of TPL level 1 (SATD in the inter source search, the quarter-pel tree without diagonal
+ * refinement, the rate estimate), subsample_tx != 0, 10-bit input, other block sizes, angle deltas.
+ *
+ * (2) svt_hip_intra_predict_batch: one descriptor = one transform block of one plane, device-resident (Tier B).
+ * Reference interface replaced:
+ *   Codec/enc_intra_prediction.c:60-435   build_intra_predictors / build_intra_predictors_high, behind svt_av1_predict_intra_block
+ *                                     and svt_av1_predict_intra_block_16bit: the need_* rules, the early-return fill, copy /
+ *                                     replication / fall-backs of the edges, filter_intra_edge_corner[_high],
+ *                                     svt_aom_intra_edge_filter_strength, svt_av1_filter_intra_edge[_high]_c,
+ *                                     svt_aom_use_intra_edge_upsample, svt_av1_upsample_intra_edge[_high]_c, svt_aom_dr_predictor /
+ *                                     svt_aom_highbd_dr_predictor (z1 / z2 / z3, both upsampling flags), the DC family, V, H, the
+ *                                     SMOOTH modes, PAETH, svt_av1_filter_intra_predictor_c / svt_aom_highbd_filter_intra_predictor
+ *   Codec/inter_prediction.c:2128-2214, 2341-2372   svt_aom_combine_interintra[_highbd] with use_wedge_interintra == 0 as an optional
+ *                                     epilogue: the smooth mask and the unblended intra prediction never reach memory.  The
+ *                                     wedge form needs no code of its own: predict into a buffer with this call, then blend it
+ *                                     with the inter prediction by a SVT_HIP_BLEND_MASK descriptor (src0 = the intra prediction,
+ *                                     mask = the wedge mask) of svt_hip_blend_batch in a later call on the same stream.
+ * (3) svt_hip_cfl_predict_batch: one descriptor = one chroma block of one plane for one alpha (4:2:0).
+ *   Codec/intra_prediction.c:420-465, C_DEFAULT/cfl_c.c   svt_cfl_luma_subsampling_420_{lbd,hbd}_c, svt_subtract_average_c,
+ *                                     svt_cfl_predict_{lbd,hbd}_c as compute_cfl_ac_components (product_coding_loop.c:3615-3650)
+ *                                     and the alpha search call them.
+ * Neither is an RTCD leaf: a leaf would put a round trip over the bus behind every intra call of the encoder.
+ * Not provided: palette prediction, intra block copy, the 4:4:4 and 4:2:2 CfL sub-sampling, the derivation of the availability
+ * counts (svt_aom_intra_has_top_right / _bottom_left, tile and frame edges: control logic of the caller), and the caller that keeps
+ * mode decision's candidates on the device.
  */
 #ifndef SVT_HIP_INTRA_H
 #define SVT_HIP_INTRA_H
@@ -52,6 +77,67 @@ typedef struct SvtHipIntraSearchJob {
  * SVT_HIP_ERR_BAD_PARAMETER (with svt_hip_last_error set) for ctrls out of range, subsample_tx != 0, a NULL source or required
  * output, an empty picture or a stride that cannot hold org_x + ceil16(width). */
 SVT_HIP_API int32_t svt_hip_intra_search_frames(const SvtHipIntraSearchJob *jobs, uint32_t n, void *stream);
+
+/* ---- Intra prediction of one transform block (Tier B) ------------------------------------------------------------------
+ * The arguments of build_intra_predictors[_high], flat.  Every pointer is device memory; samples are uint8, or uint16 with
+ * is_16bit.  Descriptors live in device memory, so the host cannot validate them: the kernel SKIPS a descriptor (dst keeps every
+ * byte) whose fields are out of the ranges given here, or whose uint16 pointers are odd.  Exactly the w x h rectangle of dst is
+ * written.  No descriptor of a call may read (above, left, inter) what another descriptor of the same call writes; `inter` may be
+ * `dst` itself (with its stride). */
+#define SVT_HIP_FILTER_INTRA_NONE 5 /* FILTER_INTRA_MODES: no filter-intra */
+
+typedef struct SvtHipIntraPredDesc {
+    const void *above;       /* sample [0] of the row above the block; [-1] is the top-left sample, read only when n_top_px > 0 and
+                              * n_left_px > 0.  n_top_px (+ n_topright_px for modes that look right) samples are read.  May be
+                              * NULL when n_top_px == 0 */
+    const void *left;        /* the sample left of row 0; row i is at left[i * left_stride].  n_left_px (+ n_bottomleft_px)
+                              * samples are read.  May be NULL when n_left_px == 0 */
+    void       *dst;         /* the predicted block */
+    const void *inter;       /* NULL: plain intra prediction.  Otherwise the inter prediction of the block: dst gets
+                              * AOM_BLEND_A64(smooth mask of ii_mode, intra, inter) */
+    uint32_t    left_stride; /* in samples: 1 for a neighbour array, the plane's stride for a reconstructed picture */
+    uint32_t    dst_stride, inter_stride; /* in samples */
+    uint8_t     w, h;        /* tx_size_wide / tx_size_high: one of the 19 transform shapes, 4 .. 64 each, 1:1, 1:2, 1:4 */
+    uint8_t     mode;        /* PredictionMode 0 DC_PRED .. 12 PAETH_PRED */
+    int8_t      angle_delta; /* -3 .. 3 for V_PRED .. D67_PRED, 0 for the others */
+    uint8_t     filter_intra_mode;   /* 0 .. 4, or SVT_HIP_FILTER_INTRA_NONE; a filter mode needs mode == DC_PRED, w <= 32, h <= 32 */
+    uint8_t     disable_edge_filter; /* 0 / 1 */
+    uint8_t     filt_type;   /* 0 / 1: get_filt_type, i.e. whether the above or the left block is smooth (the caller knows them) */
+    uint8_t     ii_mode;     /* with inter: InterIntraMode 0 II_DC_PRED, 1 II_V_PRED, 2 II_H_PRED, 3 II_SMOOTH_PRED */
+    uint8_t     n_top_px, n_topright_px;   /* n_top_px <= w; n_topright_px <= w, and n_top_px == w unless it is 0 */
+    uint8_t     n_left_px, n_bottomleft_px; /* n_left_px <= h; n_bottomleft_px <= h, and n_left_px == h unless it is 0 */
+    uint8_t     is_16bit;    /* 0 / 1 */
+    uint8_t     bit_depth;   /* 8, 10 or 12; 8 unless is_16bit */
+    uint8_t     pad_[6];
+} SvtHipIntraPredDesc;
+/* SVT_HIP_ERR_BAD_PARAMETER when d_desc == NULL or n == 0, SVT_HIP_ERR_NO_DEVICE before svt_hip_init(); nothing is launched in
+ * either case.  Asynchronous on `stream` (NULL: the calling thread's stream); n is not limited by the grid (2^20 and more). */
+SVT_HIP_API int32_t svt_hip_intra_predict_batch(const SvtHipIntraPredDesc *d_desc, uint32_t n, void *stream);
+/* The same with the number of descriptors that share a workgroup chosen by the caller (1, 2 or 4 wavefronts, one descriptor each;
+ * svt_hip_intra_predict_batch uses 4): a tuning aid, the results do not depend on it.  Any other value is a bad parameter. */
+SVT_HIP_API int32_t svt_hip_intra_predict_batch_packed(const SvtHipIntraPredDesc *d_desc, uint32_t n, uint32_t waves_per_workgroup,
+                                                       void *stream);
+
+/* ---- CfL of one chroma block (Tier B, 4:2:0) -----------------------------------------------------------------------------
+ * Luma sub-sampling, average removal and the prediction for one alpha.  A descriptor derives the AC block from luma itself, so an
+ * alpha search is N descriptors over the same luma block and no descriptor reads what another writes.  Skipped (dst and ac_out
+ * keep every byte): NULL luma / pred / dst, w or h not 4, 8, 16 or 32, |alpha_q3| > 16, bit depth fields out of range, odd
+ * uint16 pointers. */
+#define SVT_HIP_CFL_BUF_LINE 32
+
+typedef struct SvtHipCflDesc {
+    const void *luma;        /* the reconstructed luma block, 2 w x 2 h samples */
+    const void *pred;        /* the chroma DC prediction, w x h samples; may be dst */
+    void       *dst;         /* clip(pred + ROUND_POWER_OF_TWO_SIGNED(alpha_q3 * ac, 6)) */
+    int16_t    *ac_out;      /* optional (NULL): the AC block in Q3, [h][SVT_HIP_CFL_BUF_LINE], w entries of a row written */
+    uint32_t    luma_stride, pred_stride, dst_stride; /* in samples */
+    int8_t      alpha_q3;    /* -16 .. 16 */
+    uint8_t     w, h;        /* 4, 8, 16 or 32 each */
+    uint8_t     is_16bit, bit_depth; /* as SvtHipIntraPredDesc */
+    uint8_t     pad_[7];
+} SvtHipCflDesc;
+/* Errors as svt_hip_intra_predict_batch. */
+SVT_HIP_API int32_t svt_hip_cfl_predict_batch(const SvtHipCflDesc *d_desc, uint32_t n, void *stream);
 
 #ifdef __cplusplus
 }

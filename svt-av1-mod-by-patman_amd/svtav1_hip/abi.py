@@ -455,3 +455,32 @@ class IntraCtrls(C.Structure):           # SvtHipIntraCtrls
 class IntraSearchJob(C.Structure):       # SvtHipIntraSearchJob
     _fields_ = [("src", Plane8), ("ctrls", IntraCtrls), ("best_mode", C.c_void_p), ("best_cost", C.c_void_p),
                 ("mode_cost", C.c_void_p), ("pred", C.c_void_p)]
+
+
+FILTER_INTRA_NONE = 5                    # SVT_HIP_FILTER_INTRA_NONE (FILTER_INTRA_MODES)
+II_DC_PRED, II_V_PRED, II_H_PRED, II_SMOOTH_PRED = range(4)   # InterIntraMode
+CFL_BUF_LINE = 32                        # SVT_HIP_CFL_BUF_LINE
+
+
+class IntraPredDesc(C.Structure):        # SvtHipIntraPredDesc
+    _fields_ = [("above", C.c_void_p), ("left", C.c_void_p), ("dst", C.c_void_p), ("inter", C.c_void_p), ("left_stride", C.c_uint32),
+                ("dst_stride", C.c_uint32), ("inter_stride", C.c_uint32), ("w", C.c_uint8), ("h", C.c_uint8), ("mode", C.c_uint8),
+                ("angle_delta", C.c_int8), ("filter_intra_mode", C.c_uint8), ("disable_edge_filter", C.c_uint8), ("filt_type", C.c_uint8),
+                ("ii_mode", C.c_uint8), ("n_top_px", C.c_uint8), ("n_topright_px", C.c_uint8), ("n_left_px", C.c_uint8),
+                ("n_bottomleft_px", C.c_uint8), ("is_16bit", C.c_uint8), ("bit_depth", C.c_uint8), ("pad_", C.c_uint8 * 6)]
+
+
+class CflDesc(C.Structure):              # SvtHipCflDesc
+    _fields_ = [("luma", C.c_void_p), ("pred", C.c_void_p), ("dst", C.c_void_p), ("ac_out", C.c_void_p), ("luma_stride", C.c_uint32),
+                ("pred_stride", C.c_uint32), ("dst_stride", C.c_uint32), ("alpha_q3", C.c_int8), ("w", C.c_uint8), ("h", C.c_uint8),
+                ("is_16bit", C.c_uint8), ("bit_depth", C.c_uint8), ("pad_", C.c_uint8 * 7)]
+
+
+# numpy views of arrays of SvtHipIntraPredDesc / SvtHipCflDesc (pointers as addresses)
+INTRA_PRED_DESC_DTYPE = [("above", "<u8"), ("left", "<u8"), ("dst", "<u8"), ("inter", "<u8"), ("left_stride", "<u4"), ("dst_stride", "<u4"),
+                         ("inter_stride", "<u4"), ("w", "u1"), ("h", "u1"), ("mode", "u1"), ("angle_delta", "i1"), ("filter_intra_mode", "u1"),
+                         ("disable_edge_filter", "u1"), ("filt_type", "u1"), ("ii_mode", "u1"), ("n_top_px", "u1"), ("n_topright_px", "u1"),
+                         ("n_left_px", "u1"), ("n_bottomleft_px", "u1"), ("is_16bit", "u1"), ("bit_depth", "u1"), ("pad_", "u1", (6,))]
+CFL_DESC_DTYPE = [("luma", "<u8"), ("pred", "<u8"), ("dst", "<u8"), ("ac_out", "<u8"), ("luma_stride", "<u4"), ("pred_stride", "<u4"),
+                  ("dst_stride", "<u4"), ("alpha_q3", "i1"), ("w", "u1"), ("h", "u1"), ("is_16bit", "u1"), ("bit_depth", "u1"), ("pad_", "u1", (7,))]
+assert np.dtype(INTRA_PRED_DESC_DTYPE).itemsize == C.sizeof(IntraPredDesc) == 64 and np.dtype(CFL_DESC_DTYPE).itemsize == C.sizeof(CflDesc) == 56

@@ -134,6 +134,30 @@ def intra_search_frames(lib, jobs, stream=None, sync=True):
         check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
 
 
+def intra_predict_batch(lib, descs, stream=None, sync=True, waves_per_workgroup=None):
+    """svt_hip_intra_predict_batch over a list of abi.IntraPredDesc or a record array of abi.INTRA_PRED_DESC_DTYPE (one launch); with waves_per_workgroup (1, 2 or 4) the
+    same through svt_hip_intra_predict_batch_packed.  Returns the device copy of the descriptors: keep it until the stream has been synchronised."""
+    d_desc = upload_descriptors(lib, descs, stream)
+    if waves_per_workgroup is None:
+        rc = lib.svt_hip_intra_predict_batch(C.c_void_p(d_desc.ptr), C.c_uint32(len(descs)), C.c_void_p(stream))
+    else:
+        rc = lib.svt_hip_intra_predict_batch_packed(C.c_void_p(d_desc.ptr), C.c_uint32(len(descs)), C.c_uint32(waves_per_workgroup),
+                                                    C.c_void_p(stream))
+    check(lib, rc, "svt_hip_intra_predict_batch")
+    if sync:
+        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+    return d_desc
+
+
+def cfl_predict_batch(lib, descs, stream=None, sync=True):
+    """svt_hip_cfl_predict_batch over a list of abi.CflDesc or a record array of abi.CFL_DESC_DTYPE (one launch)."""
+    d_desc = upload_descriptors(lib, descs, stream)
+    check(lib, lib.svt_hip_cfl_predict_batch(C.c_void_p(d_desc.ptr), C.c_uint32(len(descs)), C.c_void_p(stream)), "svt_hip_cfl_predict_batch")
+    if sync:
+        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+    return d_desc
+
+
 def me_frames(lib, jobs, stream=None, sync=True):
     arr = (abi.MeFrameJob * len(jobs))(*jobs)
     check(lib, lib.svt_hip_me_frames(arr, C.c_uint32(len(jobs)), C.c_void_p(stream)), "svt_hip_me_frames")
@@ -142,11 +166,15 @@ def me_frames(lib, jobs, stream=None, sync=True):
 
 
 def upload_descriptors(lib, descs, stream=None):
-    """A list of ctypes structures of one type as a device array (the Tier B entry points of include/svt_hip_inter.h read their
-    descriptors from device memory).  Keep the returned buffer alive until the launch that reads it has finished."""
-    arr = (type(descs[0]) * len(descs))(*descs)
-    buf = DeviceBuffer(lib, C.sizeof(arr))
-    buf.upload(np.frombuffer(arr, np.uint8), stream)
+    """A list of ctypes structures of one type, or a numpy record array, as a device array (the Tier B entry points of
+    include/svt_hip_inter.h and svt_hip_intra.h read their descriptors from device memory).  Keep the returned buffer alive until the
+    launch that reads it has finished."""
+    if isinstance(descs, np.ndarray):
+        raw = np.ascontiguousarray(descs).view(np.uint8).reshape(-1)
+    else:
+        raw = np.frombuffer((type(descs[0]) * len(descs))(*descs), np.uint8)
+    buf = DeviceBuffer(lib, raw.nbytes)
+    buf.upload(raw, stream)
     return buf
 
 
