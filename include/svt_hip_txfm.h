@@ -205,6 +205,100 @@ SVT_HIP_API int32_t svt_hip_txfm_distortion_batch(const uint8_t *d_base, const S
 SVT_HIP_API int32_t svt_hip_quantize_batch(uint8_t *d_base, const SvtHipTxfmDesc *d_desc, SvtHipTxfmResult *d_result,
                                            uint32_t n_blocks, uint32_t n_coeffs, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Tier B — coefficient rate of transform blocks: svt_av1_cost_coeffs_txb (rd_cost.c:434-559) as mode decision reaches it
+ * through svt_aom_txb_estimate_coeff_bits (rd_cost.c:1405-1450) with allow_update_cdf = 0, and the cost tx_type_search forms
+ * from it (product_coding_loop.c:4737-4786).  Run after svt_hip_txfm_quant_batch and svt_hip_txfm_distortion_batch on the
+ * same stream, it completes cost = RDCOST(lambda, bits, dist) of every candidate on the device.  No Tier A leaf: one PCIe
+ * round trip per transform block would cost more than the table look-ups it replaces.
+ * ------------------------------------------------------------------------------------------- */
+/* LvMapCoeffCost (md_rate_estimation.h:41-49), field for field: txb_skip_cost, base_eob_cost, base_cost, eob_extra_cost,
+ * dc_sign_cost, lps_cost.  eob_extra holds the first 9 rows of eob_extra_cost (the reference declares EOB_COEF_CONTEXTS = 22
+ * rows, get_eob_cost reaches rows eob_pt - 3 = 0 .. 8); every other array has the reference's dimensions. */
+typedef struct SvtHipCoeffCost {
+    int32_t txb_skip[13][2];
+    int32_t base_eob[4][3];
+    int32_t base[42][8];
+    int32_t eob_extra[9][2];
+    int32_t dc_sign[3][2];
+    int32_t lps[21][26];
+} SvtHipCoeffCost;
+
+/* One set of rate tables (one picture, or one CDF state); the caller copies four fields of MdRateEstimationContext
+ * (md_rate_estimation.h:127-133), each array with the reference's own dimensions:
+ *   coeff[txs_ctx][plane]             = coeff_fac_bits[txs_ctx][plane], array by array
+ *   eob[size][plane][ctx][pt]         = eob_frac_bits[size][plane].eob_cost[ctx][pt]
+ *   intra_tx_type[set][sq][dir][type] = intra_tx_type_fac_bits
+ *   inter_tx_type[set][sq][type]      = inter_tx_type_fac_bits */
+typedef struct SvtHipRateTables {
+    SvtHipCoeffCost coeff[5][2];
+    int32_t         eob[7][2][2][11];
+    int32_t         intra_tx_type[3][4][13][17];
+    int32_t         inter_tx_type[4][4][17];
+} SvtHipRateTables;
+
+enum { /* SvtHipTxbCostDesc::est_mode: which of the three rates of product_coding_loop.c:4757-4782 a block gets */
+    SVT_HIP_TXB_COST_EXACT = 0,    /* coeff_rate_est_lvl 1: always svt_av1_cost_coeffs_txb */
+    SVT_HIP_TXB_COST_SHORT_SMALL,  /* coeff_rate_est_lvl >= 2: bits = 6000 + 1000 * eob when eob < (w * h) >> 6, else exact */
+    SVT_HIP_TXB_COST_SHORT_ALL     /* coeff_rate_est_lvl 0: the same, and bits = 3000 + 100 * eob for every other eob */
+};
+enum { /* SvtHipTxbCostDesc::flags */
+    SVT_HIP_TXB_COST_NO_SHIFT = 1  /* bits of a non-zero eob are not shifted by subres_step (c_start still depends on it): what
+                                    * svt_aom_txb_estimate_coeff_bits does for the two chroma blocks (rd_cost.c:1455-1500) */
+};
+
+typedef struct SvtHipTxbCostDesc {
+    uint64_t qcoeff_off;           /* int32 qcoeff[n], n = min(w,32) * min(h,32): the quantiser's output in the arena */
+    uint64_t iscan_off;            /* int16 iscan[n], the table the quantiser descriptor carries; iscan[0] is 0 in every AV1 scan */
+    uint32_t table;                /* index into d_tables (clamped to n_tables - 1) */
+    uint32_t lambda;               /* full_lambda of the block; enters rd_cost only */
+    uint16_t eob;                  /* ignored when d_txfm_result is given */
+    uint8_t  tx_type;              /* TxType, 0 .. 15 */
+    uint8_t  plane_type;           /* 0 luma (pays the transform-type rate), 1 chroma */
+    uint8_t  txb_skip_ctx;         /* 0 .. 12 */
+    uint8_t  dc_sign_ctx;          /* 0 .. 2 */
+    uint8_t  pred_mode;            /* PredictionMode of the candidate: 0 .. 12 intra, 13 .. 24 inter (is_inter_mode) */
+    uint8_t  filter_intra_mode;    /* 0 .. 4, or 5 (FILTER_INTRA_MODES) for none */
+    uint8_t  reduced_tx_set;       /* frm_hdr->reduced_tx_set */
+    uint8_t  fast_coeff_est_level; /* ctx->mds_fast_coeff_est_level */
+    uint8_t  subres_step;          /* ctx->mds_subres_step */
+    uint8_t  est_mode;             /* SVT_HIP_TXB_COST_EXACT ... */
+    uint8_t  flags;
+    uint8_t  pad_[3];
+} SvtHipTxbCostDesc;
+
+typedef struct SvtHipTxbCost {
+    uint64_t bits;
+    uint64_t rd_cost;
+} SvtHipTxbCost;
+
+/* d_out[i] for n_blocks transform blocks of ONE size w x h (any of the 19 transform sizes).
+ *   eob == 0:  bits = txb_skip[txb_skip_ctx][1], not shifted (av1_cost_skip_txb, rd_cost.c:1447).
+ *   eob  > 0:  bits = svt_av1_cost_coeffs_txb(...) << subres_step (rd_cost.c:1433-1445): txb_skip[ctx][0] + the transform-type rate (luma only)
+ *              + the eob cost + the coefficient loop, the latter over scan positions eob-1, 0 and c_start .. 1 with
+ *              c_start = MIN(eob - 2, eob / MAX(1, fast_coeff_est_level - subres_step)) (rd_cost.c:408).
+ *   est_mode 1, 2 replace either by the closed forms above (which are not shifted).
+ * The levels that the contexts are formed from (svt_av1_txb_init_levels, get_nz_mag, get_br_ctx) come from the WHOLE
+ * retained array min(w,32) x min(h,32), also from positions at or beyond eob in scan order, because that is what the
+ * reference reads.  An eob above min(w,32) * min(h,32) is clamped to it; field values beyond the ranges given with the
+ * descriptor are clamped into the tables, so that nothing is read out of bounds.  A zero coefficient at scan position
+ * eob - 1 (the reference asserts against it and reads one entry before the row) costs base_eob[ctx][0].
+ *   d_txfm_result (or NULL): eob = d_txfm_result[i].eob as svt_hip_txfm_quant_batch left it, three_quad_energy likewise.
+ *   d_distortion (or NULL, then rd_cost = 0): d_distortion[i][0] is DIST_CALC_RESIDUAL of svt_hip_txfm_distortion_batch,
+ *       dist    = RIGHT_SIGNED_SHIFT(d_distortion[i][0] + three_quad_energy, (MAX_TX_SCALE - tx_scale(w, h)) * 2) << subres_step
+ *       rd_cost = RDCOST(lambda, bits, dist)                                                        (rd_cost.h:37)
+ * Returns SVT_HIP_ERR_BAD_PARAMETER, before any device is touched, for a w x h that is no transform size, for n_tables == 0
+ * and for a NULL d_desc, d_tables or d_out with n_blocks > 0; n_blocks == 0 succeeds. */
+SVT_HIP_API int32_t svt_hip_txb_cost_batch(const uint8_t *d_base, const SvtHipTxbCostDesc *d_desc, const SvtHipRateTables *d_tables,
+                                           uint32_t n_tables, const SvtHipTxfmResult *d_txfm_result, const uint64_t (*d_distortion)[2],
+                                           SvtHipTxbCost *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, void *stream);
+/* The same with the placement of the two SvtHipCoeffCost tables of the launch chosen by the caller (a measuring aid):
+ * 0 read through the cache, 1 staged into LDS once per workgroup.  svt_hip_txb_cost_batch uses the faster one. */
+SVT_HIP_API int32_t svt_hip_txb_cost_batch_placed(const uint8_t *d_base, const SvtHipTxbCostDesc *d_desc, const SvtHipRateTables *d_tables,
+                                                  uint32_t n_tables, const SvtHipTxfmResult *d_txfm_result,
+                                                  const uint64_t (*d_distortion)[2], SvtHipTxbCost *d_out, uint32_t n_blocks, uint32_t w,
+                                                  uint32_t h, uint32_t tables_in_lds, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,348 @@
+// txfm_rate.hip — the coefficient rate of transform blocks on device-resident quantiser output (Tier B only):
+//   svt_av1_cost_coeffs_txb with allow_update_cdf = 0   (reference: rd_cost.c:434-559, reached through
+//   svt_aom_txb_estimate_coeff_bits :1405-1450) and the cost tx_type_search forms from it (product_coding_loop.c:4737-4786).
+// The reference walks the scan backwards; every term of its sum depends only on one position, its scan index and the levels
+// of up to five neighbours, so the sum is taken BY POSITION here: the lane that owns raster position pos reads c = iscan[pos]
+// and adds the eob-1 form, the DC form, the loop form or nothing.  Integer table look-ups only; sums are int32 as there.
+//
+// Work split: a block of n = min(w,32) * min(h,32) retained coefficients belongs to a group of min(n, 64) lanes, so 16-, 32-
+// and 64-coefficient blocks sit 4, 2 and 1 to a wavefront and larger blocks take n / 64 (up to 16) positions per lane.  A
+// workgroup of 256 lanes walks the batch in steps of its 256 / group blocks.  The levels (|qcoeff| clamped to 127, as
+// svt_av1_txb_init_levels_c) of each block lie in LDS with the reference's row pitch of w + 4 and four zero rows below, so
+// get_nz_mag and get_br_ctx read neighbours without bounds tests; the two rows the reference keeps above are never read by
+// either and are left out.  Blocks with eob <= 1 or a closed-form rate read no level, as in the reference.
+// Rate tables: one launch has one size context, so each workgroup stages the two planes' SvtHipCoeffCost (7552 B) of its first block's
+// table set into LDS once and keeps them for all its steps (the grid is capped, a workgroup takes many steps); a block of another
+// table set reads its own through the cache.  Reading all of them through the cache is the LDS_TABLES = false instance, kept for
+// svt_hip_txb_cost_batch_placed: 13 - 15 % slower at every size (profiles/txb_cost_4k.json).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/svt_hip_txfm.h"
+#include "common.hpp"
+
+using namespace svthip;
+
+namespace {
+
+// what the host derives from w x h once per launch
+struct TxbCostLaunch {
+    int32_t  orient;      // sign of w - h: which family of eb_av1_nz_map_ctx_offset the size uses
+    int32_t  txs_ctx;     // (txsize_sqr_map + txsize_sqr_up_map + 1) >> 1
+    int32_t  sqr, sqr_up; // TX_4X4 .. TX_64X64 of min(w, h) and max(w, h)
+    int32_t  dist_shift;  // (MAX_TX_SCALE - av1_get_tx_scale_tab) * 2: 2, 0 or -2
+    uint32_t area_th;     // (w * h) >> 6
+    uint32_t n_tables;
+    uint32_t n_blocks;
+};
+
+constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
+
+// tx_type_to_class (cabac_context_model.h:459-476): 0 two-dimensional, 1 horizontal, 2 vertical
+__device__ __forceinline__ int tx_class_of(int tx_type) { return tx_type < 10 ? 0 : (tx_type & 1) ? 1 : 2; }
+
+// get_golomb_cost (rd_cost.c:90-97)
+__device__ __forceinline__ int golomb_cost(int level) {
+    if (level < 15)
+        return 0;
+    const int length = 32 - __clz(level - 14);
+    return (2 * length - 1) * 512;
+}
+
+// get_eob_cost (rd_cost.c:281-298) with get_eob_pos_token, eb_k_eob_group_start and eb_k_eob_offset_bits in closed form
+__device__ __forceinline__ int eob_cost(int eob, const int32_t (*eob_bits)[11], const int32_t (*eob_extra)[2], int cls) {
+    const int pt = eob < 2 ? eob : 33 - __clz(eob - 1);
+    int       cost = eob_bits[cls != 0][pt - 1];
+    const int offset_bits = pt - 2;
+    if (offset_bits > 0) {
+        const int extra = eob - ((1 << offset_bits) + 1);
+        cost += eob_extra[pt - 3][(extra >> (offset_bits - 1)) & 1] + (offset_bits - 1) * 512;
+    }
+    return cost;
+}
+
+// av1_transform_type_rate_estimation (rd_cost.c:113-158) with get_ext_tx_set_type / ext_tx_set_index (definitions.h:1795-1836)
+__device__ int tx_type_rate(const SvtHipRateTables &t, const SvtHipTxbCostDesc &d, const TxbCostLaunch &p) {
+    const int is_inter = d.pred_mode >= 13 && d.pred_mode < 25;
+    int       set_type;  // TxSetType
+    if (p.sqr_up > 3)
+        set_type = 0;
+    else if (p.sqr_up == 3)
+        set_type = is_inter ? 1 : 0;
+    else if (d.reduced_tx_set)
+        set_type = is_inter ? 1 : 2;
+    else if (is_inter)
+        set_type = p.sqr == 2 ? 4 : 5;
+    else
+        set_type = p.sqr == 2 ? 2 : 3;
+    if (set_type == 0)  // one type in the set
+        return 0;
+    const int tx_type = d.tx_type & 15, sq = p.sqr < 3 ? p.sqr : 3;
+    if (is_inter) {
+        const int set = set_type == 1 ? 3 : set_type == 4 ? 2 : 1;
+        return t.inter_tx_type[set][sq][tx_type];
+    }
+    const int set = set_type == 3 ? 1 : 2;
+    int       dir = d.pred_mode;
+    if (d.filter_intra_mode < 5)  // fimode_to_intradir
+        dir = d.filter_intra_mode == 1 ? 1 : d.filter_intra_mode == 2 ? 2 : d.filter_intra_mode == 3 ? 6 : 0;
+    return t.intra_tx_type[set][sq][dir < 12 ? dir : 12][tx_type];
+}
+
+__device__ __forceinline__ int min3(int v) { return v < 3 ? v : 3; }
+
+// lps_cost[ctx][..] + Golomb tail of a level above NUM_BASE_LEVELS
+__device__ __forceinline__ int range_cost(const SvtHipCoeffCost &cc, int br_ctx, int level) {
+    const int base_range = level - 3;
+    return cc.lps[br_ctx][base_range < 12 ? base_range : 12] + golomb_cost(level);
+}
+
+// the eob == 1 form (av1_cost_coeffs_txb_loop_cost_one_eob, rd_cost.c:310-337): no level is read
+__device__ __forceinline__ int one_eob_cost(const SvtHipCoeffCost &cc, int32_t v, int dc_sign_ctx) {
+    const int level = v < 0 ? -v : v;
+    int       cost = cc.base_eob[0][level ? min3(level) - 1 : 0];
+    if (v != 0) {
+        cost += cc.dc_sign[dc_sign_ctx][v < 0];
+        if (level > 2)
+            cost += range_cost(cc, 0, level);
+    }
+    return cost;
+}
+
+// One position's term of av1_cost_coeffs_txb_loop_cost_eob (rd_cost.c:339-431) for eob > 1 and c == eob - 1, c == 0 or
+// 1 <= c <= c_start.  levels: the block's padded level array.
+template <int IW, int IH>
+__device__ __forceinline__ int position_cost(const SvtHipCoeffCost &cc, const uint8_t *levels, const int32_t *qc, int pos, int c, int eob,
+                                             int cls, int orient, int dc_sign_ctx) {
+    constexpr int  BWL = ilog2(IW), STRIDE = IW + 4, N = IW * IH;
+    const int      row = pos >> BWL, col = pos & (IW - 1);
+    const uint8_t *L = levels + row * STRIDE + col;
+    int            level = L[0];
+    int32_t        v = level;  // its sign matters to the DC term only
+    if (level >= 15 || c == 0) {  // beyond the base range the Golomb tail needs the value itself
+        v     = qc[pos];
+        level = v < 0 ? -v : v;
+    }
+    // get_br_ctx (common_utils.h:104-141)
+    int br_ctx = 0;
+    if (level > 2) {
+        int mag = L[1] + L[STRIDE];
+        mag += cls == 0 ? L[STRIDE + 1] : cls == 1 ? L[2] : L[2 * STRIDE];
+        mag    = (mag + 1) >> 1;
+        br_ctx = mag < 6 ? mag : 6;
+        if (pos != 0)
+            br_ctx += (cls == 0 ? (row < 2 && col < 2) : cls == 1 ? col == 0 : row == 0) ? 7 : 14;
+    }
+    int cost;
+    if (c == eob - 1) {  // get_nz_map_ctx with is_eob (encode_txb_ref_c.c:17-27); c >= 1 here
+        const int ctx = c <= N / 8 ? 1 : c <= N / 4 ? 2 : 3;
+        cost = cc.base_eob[ctx][level ? min3(level) - 1 : 0] + (level ? 512 : 0);
+    } else {  // get_nz_mag + get_nz_map_ctx_from_stats (coefficients.h:2884-2943)
+        int ctx = 0;
+        if (cls != 0 || pos != 0) {
+            int mag = min3(L[1]) + min3(L[STRIDE]);
+            if (cls == 0)
+                mag += min3(L[STRIDE + 1]) + min3(L[2]) + min3(L[2 * STRIDE]);
+            else if (cls == 2)
+                mag += min3(L[2 * STRIDE]) + min3(L[3 * STRIDE]) + min3(L[4 * STRIDE]);
+            else
+                mag += min3(L[2]) + min3(L[3]) + min3(L[4]);
+            ctx = (mag + 1) >> 1;
+            ctx = ctx < 4 ? ctx : 4;
+            if (cls == 0) {  // the rule eb_av1_nz_map_ctx_offset was generated by
+                if (orient < 0 && row < 2)
+                    ctx += 11;
+                else if (orient > 0 && col < 2)
+                    ctx += 16;
+                else
+                    ctx += row + col < 2 ? 1 : row + col < 4 ? 6 : 21;
+            } else {  // nz_map_ctx_offset_1d
+                const int k = cls == 1 ? col : row;
+                ctx += k == 0 ? 26 : k == 1 ? 31 : 36;
+            }
+        }
+        cost = cc.base[ctx][min3(level)];
+        if (level)
+            cost += c == 0 ? cc.dc_sign[dc_sign_ctx][v < 0] : 512;
+    }
+    if (level > 2)
+        cost += range_cost(cc, br_ctx, level);
+    return cost;
+}
+
+// everything of one block that is summed over positions; G lanes call it together
+template <int IW, int IH, int G>
+__device__ __forceinline__ int coefficient_cost(const SvtHipCoeffCost &cc, const uint8_t *levels, const int32_t *qc, const int16_t *iscan,
+                                                int li, int eob, int c_start, int cls, int orient, int dc_sign_ctx) {
+    constexpr int N = IW * IH;
+    int           cost = 0;
+    if (eob == 1) {
+        if (li == 0)
+            cost = one_eob_cost(cc, qc[0], dc_sign_ctx);
+        return cost;
+    }
+#pragma unroll
+    for (int k = 0; k < N / G; k++) {
+        const int pos = li + k * G, c = iscan[pos];
+        if (c == eob - 1 || (c >= 0 && c <= c_start))
+            cost += position_cost<IW, IH>(cc, levels, qc, pos, c, eob, cls, orient, dc_sign_ctx);
+    }
+    return cost;
+}
+
+template <int IW, int IH, bool LDS_TABLES>
+__global__ __launch_bounds__(256) void txb_cost_kernel(const uint8_t *__restrict__ base, const SvtHipTxbCostDesc *__restrict__ descs,
+                                                       const SvtHipRateTables *__restrict__ tables, const SvtHipTxfmResult *__restrict__ results,
+                                                       const uint64_t (*__restrict__ dist)[2], SvtHipTxbCost *__restrict__ out, TxbCostLaunch prm) {
+    constexpr int N = IW * IH, G = N < 64 ? N : 64, BLOCKS = 256 / G;
+    constexpr int STRIDE = IW + 4, ROW_WORDS = STRIDE / 4, LEVEL_WORDS = ROW_WORDS * (IH + 4);
+    __shared__ uint32_t        lv[BLOCKS][LEVEL_WORDS];
+    constexpr int TABLE_WORDS = 2 * sizeof(SvtHipCoeffCost) / 4;
+    __shared__ int32_t staged_words[LDS_TABLES ? TABLE_WORDS : 1];  // both planes of the table set of the workgroup's first block
+    const SvtHipCoeffCost *staged = (const SvtHipCoeffCost *)staged_words;
+    const int      gi = threadIdx.x / G, li = threadIdx.x % G;
+    uint32_t       first_table = 0;
+    if (LDS_TABLES) {
+        first_table = descs[blockIdx.x * BLOCKS].table;  // the grid never exceeds the batch
+        first_table = first_table < prm.n_tables ? first_table : prm.n_tables - 1;
+        const int32_t *src = (const int32_t *)&tables[first_table].coeff[prm.txs_ctx][0];
+        for (int i = threadIdx.x; i < TABLE_WORDS; i += 256) staged_words[i] = src[i];
+    }
+    for (uint32_t b0 = blockIdx.x * BLOCKS; b0 < prm.n_blocks; b0 += gridDim.x * BLOCKS) {
+        const uint32_t tb = b0 + gi;
+        const bool     active = tb < prm.n_blocks;
+        SvtHipTxbCostDesc d = descs[active ? tb : prm.n_blocks - 1];
+        int            eob = results ? results[active ? tb : 0].eob : d.eob;
+        eob = eob < N ? eob : N;
+        const bool short_form = (d.est_mode >= SVT_HIP_TXB_COST_SHORT_SMALL && (uint32_t)eob < prm.area_th) || d.est_mode >= SVT_HIP_TXB_COST_SHORT_ALL;
+        const bool exact = active && eob > 0 && !short_form;
+        const int32_t *qc = (const int32_t *)(base + d.qcoeff_off);
+        __syncthreads();  // the levels of the previous step have been read (and, first time round, the staged tables written)
+        if (exact && eob > 1) {  // svt_av1_txb_init_levels_c, four levels to a word; the pad columns and rows are zero
+            const bool vec = (((uintptr_t)qc) & 15) == 0;
+            for (int wd = li; wd < LEVEL_WORDS; wd += G) {
+                const int r = wd / ROW_WORDS, c4 = wd - r * ROW_WORDS;
+                uint32_t  word = 0;
+                if (r < IH && c4 < IW / 4) {
+                    const int32_t *q = qc + r * IW + c4 * 4;
+                    int32_t        v[4];
+                    if (vec) {
+                        const int4 q4 = *(const int4 *)q;
+                        v[0] = q4.x, v[1] = q4.y, v[2] = q4.z, v[3] = q4.w;
+                    } else {
+                        v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const uint32_t a = v[j] < 0 ? 0u - (uint32_t)v[j] : (uint32_t)v[j];
+                        word |= (a < 127 ? a : 127) << (8 * j);
+                    }
+                }
+                lv[gi][wd] = word;
+            }
+        }
+        __syncthreads();
+        int cost = 0;
+        const uint32_t ti = d.table < prm.n_tables ? d.table : prm.n_tables - 1;
+        const SvtHipRateTables &t = tables[ti];
+        const int plane = d.plane_type != 0, cls = tx_class_of(d.tx_type & 15);
+        const int skip_ctx = d.txb_skip_ctx < 12 ? d.txb_skip_ctx : 12, sign_ctx = d.dc_sign_ctx < 2 ? d.dc_sign_ctx : 2;
+        const SvtHipCoeffCost &cc_global = t.coeff[prm.txs_ctx][plane];
+        if (exact) {
+            const int div = (int)d.fast_coeff_est_level - (int)d.subres_step;
+            const int by = eob / (div > 1 ? div : 1), c_start = eob - 2 < by ? eob - 2 : by;
+            const int16_t *iscan = (const int16_t *)(base + d.iscan_off);
+            const uint8_t *levels = (const uint8_t *)lv[gi];
+            if (LDS_TABLES && ti == first_table)
+                cost = coefficient_cost<IW, IH, G>(staged[plane], levels, qc, iscan, li, eob, c_start, cls, prm.orient, sign_ctx);
+            else
+                cost = coefficient_cost<IW, IH, G>(cc_global, levels, qc, iscan, li, eob, c_start, cls, prm.orient, sign_ctx);
+            if (li == 0) {
+                cost += cc_global.txb_skip[skip_ctx][0] + eob_cost(eob, t.eob[ilog2(N) - 4][plane], cc_global.eob_extra, cls);
+                if (!plane)
+                    cost += tx_type_rate(t, d, prm);
+            }
+        }
+#pragma unroll
+        for (int off = G / 2; off > 0; off >>= 1) cost += __shfl_xor(cost, off, 64);
+        if (active && li == 0) {
+            uint64_t bits;
+            if (short_form)
+                bits = d.est_mode >= SVT_HIP_TXB_COST_SHORT_SMALL && (uint32_t)eob < prm.area_th ? 6000 + 1000 * (uint64_t)eob : 3000 + 100 * (uint64_t)eob;
+            else if (eob == 0)
+                bits = (uint64_t)(int64_t)cc_global.txb_skip[skip_ctx][1];
+            else
+                bits = (uint64_t)(int64_t)cost << ((d.flags & SVT_HIP_TXB_COST_NO_SHIFT) ? 0 : d.subres_step);
+            uint64_t rd = 0;
+            if (dist) {  // product_coding_loop.c:4737-4749 and RDCOST (rd_cost.h:37)
+                uint64_t dd = dist[tb][0] + (results ? results[tb].three_quad_energy : 0);
+                dd = (prm.dist_shift < 0 ? dd << -prm.dist_shift : dd >> prm.dist_shift) << d.subres_step;
+                rd = (uint64_t)((((int64_t)bits * (int64_t)d.lambda + 256) >> 9) + (int64_t)dd * 128);
+            }
+            SvtHipTxbCost r;
+            r.bits = bits, r.rd_cost = rd;
+            out[tb] = r;
+        }
+    }
+}
+
+template <int IW, int IH>
+void launch(bool lds, dim3 grid, hipStream_t st, const uint8_t *base, const SvtHipTxbCostDesc *descs, const SvtHipRateTables *tables,
+            const SvtHipTxfmResult *results, const uint64_t (*dist)[2], SvtHipTxbCost *out, const TxbCostLaunch &prm) {
+    if (lds)
+        hipLaunchKernelGGL((txb_cost_kernel<IW, IH, true>), grid, dim3(256), 0, st, base, descs, tables, results, dist, out, prm);
+    else
+        hipLaunchKernelGGL((txb_cost_kernel<IW, IH, false>), grid, dim3(256), 0, st, base, descs, tables, results, dist, out, prm);
+}
+
+constexpr bool kTablesInLds = true;  // svt_hip_txb_cost_batch: the faster placement at every size of profiles/txb_cost_4k.json
+
+int size_index(uint32_t v) { return v == 4 ? 0 : v == 8 ? 1 : v == 16 ? 2 : v == 32 ? 3 : v == 64 ? 4 : -1; }
+
+}  // namespace
+
+extern "C" int32_t svt_hip_txb_cost_batch_placed(const uint8_t *d_base, const SvtHipTxbCostDesc *d_desc, const SvtHipRateTables *d_tables,
+                                                 uint32_t n_tables, const SvtHipTxfmResult *d_txfm_result, const uint64_t (*d_distortion)[2],
+                                                 SvtHipTxbCost *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, uint32_t tables_in_lds,
+                                                 void *stream) {
+    const int  sw = size_index(w), sh = size_index(h);
+    const bool is_tx_size = sw >= 0 && sh >= 0 && (sw > sh ? sw - sh : sh - sw) <= 2;  // 1:1, 1:2 and 1:4: the 19 transform sizes
+    if (!is_tx_size || n_tables == 0 || (n_blocks > 0 && (!d_base || !d_desc || !d_tables || !d_out))) {
+        set_error("svt_hip_txb_cost_batch: bad argument (%u x %u, %u table sets, %u blocks)", w, h, n_tables, n_blocks);
+        return SVT_HIP_ERR_BAD_PARAMETER;
+    }
+    if (n_blocks == 0)
+        return SVT_HIP_OK;
+    if (!ensure_init())
+        return SVT_HIP_ERR_NO_DEVICE;
+    TxbCostLaunch prm;
+    prm.orient = sw < sh ? -1 : sw > sh;
+    prm.sqr = sw < sh ? sw : sh, prm.sqr_up = sw > sh ? sw : sh;
+    prm.txs_ctx = (prm.sqr + prm.sqr_up + 1) >> 1;
+    const uint32_t pixels = w * h;
+    prm.dist_shift = (1 - (pixels > 1024 ? 2 : pixels > 256 ? 1 : 0)) * 2;  // av1_get_tx_scale_tab (full_loop.h:52)
+    prm.area_th = pixels >> 6, prm.n_tables = n_tables, prm.n_blocks = n_blocks;
+    const uint32_t iw = w < 32 ? w : 32, ih = h < 32 ? h : 32, n = iw * ih, per_wg = 256 / (n < 64 ? n : 64);
+    const uint32_t wanted = (n_blocks + per_wg - 1) / per_wg, cap = (uint32_t)cu_count() * 8;  // 8 workgroups fill a CU's wave slots
+    const dim3     grid(wanted < cap ? wanted : cap);
+    const bool     lds = tables_in_lds != 0;
+    hipStream_t    st = resolve_stream(stream);
+#define TXB_COST_CASE(W, H)                                                                       \
+    if (iw == W && ih == H)                                                                       \
+        launch<W, H>(lds, grid, st, d_base, d_desc, d_tables, d_txfm_result, d_distortion, d_out, prm);
+    TXB_COST_CASE(4, 4) TXB_COST_CASE(8, 8) TXB_COST_CASE(16, 16) TXB_COST_CASE(32, 32) TXB_COST_CASE(4, 8) TXB_COST_CASE(8, 4)
+    TXB_COST_CASE(8, 16) TXB_COST_CASE(16, 8) TXB_COST_CASE(16, 32) TXB_COST_CASE(32, 16) TXB_COST_CASE(4, 16) TXB_COST_CASE(16, 4)
+    TXB_COST_CASE(8, 32) TXB_COST_CASE(32, 8)
+#undef TXB_COST_CASE
+    SVT_HIP_CHECK(hipGetLastError());
+    return SVT_HIP_OK;
+}
+
+extern "C" int32_t svt_hip_txb_cost_batch(const uint8_t *d_base, const SvtHipTxbCostDesc *d_desc, const SvtHipRateTables *d_tables,
+                                          uint32_t n_tables, const SvtHipTxfmResult *d_txfm_result, const uint64_t (*d_distortion)[2],
+                                          SvtHipTxbCost *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, void *stream) {
+    return svt_hip_txb_cost_batch_placed(d_base, d_desc, d_tables, n_tables, d_txfm_result, d_distortion, d_out, n_blocks, w, h, kTablesInLds,
+                                         stream);
+}
+
+SVT_HIP_MODULE_WARMUP(txfm_rate)

@@ -175,6 +175,44 @@ class TxfmResult(C.Structure):
     _fields_ = [("three_quad_energy", C.c_uint64), ("eob", C.c_uint16), ("pad_", C.c_uint16), ("satd", C.c_uint32)]
 
 
+class CoeffCost(C.Structure):          # SvtHipCoeffCost == LvMapCoeffCost (md_rate_estimation.h:41-49)
+    _fields_ = [("txb_skip", (C.c_int32 * 2) * 13), ("base_eob", (C.c_int32 * 3) * 4), ("base", (C.c_int32 * 8) * 42),
+                ("eob_extra", (C.c_int32 * 2) * 9), ("dc_sign", (C.c_int32 * 2) * 3), ("lps", (C.c_int32 * 26) * 21)]
+
+
+class RateTables(C.Structure):         # SvtHipRateTables: one set of rate tables
+    _fields_ = [("coeff", (CoeffCost * 2) * 5), ("eob", (((C.c_int32 * 11) * 2) * 2) * 7),
+                ("intra_tx_type", (((C.c_int32 * 17) * 13) * 4) * 3), ("inter_tx_type", ((C.c_int32 * 17) * 4) * 4)]
+
+
+TXB_COST_EXACT, TXB_COST_SHORT_SMALL, TXB_COST_SHORT_ALL = range(3)   # SvtHipTxbCostDesc::est_mode
+TXB_COST_NO_SHIFT = 1                                                  # SvtHipTxbCostDesc::flags
+
+
+class TxbCostDesc(C.Structure):        # SvtHipTxbCostDesc
+    _fields_ = [("qcoeff_off", C.c_uint64), ("iscan_off", C.c_uint64), ("table", C.c_uint32), ("lambda", C.c_uint32), ("eob", C.c_uint16),
+                ("tx_type", C.c_uint8), ("plane_type", C.c_uint8), ("txb_skip_ctx", C.c_uint8), ("dc_sign_ctx", C.c_uint8),
+                ("pred_mode", C.c_uint8), ("filter_intra_mode", C.c_uint8), ("reduced_tx_set", C.c_uint8),
+                ("fast_coeff_est_level", C.c_uint8), ("subres_step", C.c_uint8), ("est_mode", C.c_uint8), ("flags", C.c_uint8),
+                ("pad_", C.c_uint8 * 3)]
+
+
+class TxbCost(C.Structure):            # SvtHipTxbCost
+    _fields_ = [("bits", C.c_uint64), ("rd_cost", C.c_uint64)]
+
+
+# numpy views of SvtHipRateTables and of arrays of SvtHipTxbCostDesc / SvtHipTxbCost
+COEFF_COST_DTYPE = [("txb_skip", "<i4", (13, 2)), ("base_eob", "<i4", (4, 3)), ("base", "<i4", (42, 8)), ("eob_extra", "<i4", (9, 2)),
+                    ("dc_sign", "<i4", (3, 2)), ("lps", "<i4", (21, 26))]
+RATE_TABLES_DTYPE = [("coeff", COEFF_COST_DTYPE, (5, 2)), ("eob", "<i4", (7, 2, 2, 11)), ("intra_tx_type", "<i4", (3, 4, 13, 17)),
+                     ("inter_tx_type", "<i4", (4, 4, 17))]
+TXB_COST_DESC_DTYPE = [("qcoeff_off", "<u8"), ("iscan_off", "<u8"), ("table", "<u4"), ("lambda", "<u4"), ("eob", "<u2"), ("tx_type", "u1"),
+                       ("plane_type", "u1"), ("txb_skip_ctx", "u1"), ("dc_sign_ctx", "u1"), ("pred_mode", "u1"), ("filter_intra_mode", "u1"),
+                       ("reduced_tx_set", "u1"), ("fast_coeff_est_level", "u1"), ("subres_step", "u1"), ("est_mode", "u1"), ("flags", "u1"),
+                       ("pad_", "u1", (3,))]
+TXB_COST_DTYPE = [("bits", "<u8"), ("rd_cost", "<u8")]
+
+
 class CdefList(C.Structure):
     _fields_ = [("by", C.c_uint8), ("bx", C.c_uint8)]
 

@@ -198,6 +198,29 @@ def compound_mask_search_batch(lib, descs, stream=None, fill=0xA5):
     return d_res.download(np.dtype(abi.MASK_SEARCH_RESULT_DTYPE), (len(descs),), stream)
 
 
+def txb_cost_batch(lib, d_base, descs, tables, w, h, d_txfm_result=None, d_distortion=None, stream=None, tables_in_lds=None, guard=64, fill=0xA5):
+    """svt_hip_txb_cost_batch for blocks of one size w x h (one launch).  d_base: device address of the arena the descriptors' offsets
+    refer to; descs: a record array of abi.TXB_COST_DESC_DTYPE (or a list of abi.TxbCostDesc); tables: a record array of
+    abi.RATE_TABLES_DTYPE, one record per table set; d_txfm_result / d_distortion: device addresses of what the transform batch and
+    svt_hip_txfm_distortion_batch wrote, or None.  With tables_in_lds (0 or 1) the same through svt_hip_txb_cost_batch_placed.
+    Returns (results as a record array of abi.TXB_COST_DTYPE, the `guard` bytes before and after them: still `fill` if untouched)."""
+    n = len(descs)
+    tables = np.ascontiguousarray(tables, np.dtype(abi.RATE_TABLES_DTYPE)).reshape(-1)
+    d_desc, d_tab = upload_descriptors(lib, descs, stream), DeviceBuffer(lib, tables.nbytes)
+    d_tab.upload(tables, stream)
+    d_out = DeviceBuffer(lib, 2 * guard + C.sizeof(abi.TxbCost) * n)
+    d_out.fill(fill, stream)
+    args = (C.c_void_p(d_base), C.c_void_p(d_desc.ptr), C.c_void_p(d_tab.ptr), C.c_uint32(len(tables)), C.c_void_p(d_txfm_result),
+            C.c_void_p(d_distortion), C.c_void_p(d_out.ptr + guard), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h))
+    if tables_in_lds is None:
+        rc = lib.svt_hip_txb_cost_batch(*args, C.c_void_p(stream))
+    else:
+        rc = lib.svt_hip_txb_cost_batch_placed(*args, C.c_uint32(tables_in_lds), C.c_void_p(stream))
+    check(lib, rc, "svt_hip_txb_cost_batch")
+    raw = d_out.download(np.uint8, (d_out.nbytes,), stream)
+    return raw[guard:d_out.nbytes - guard].view(np.dtype(abi.TXB_COST_DTYPE)).copy(), np.concatenate([raw[:guard], raw[d_out.nbytes - guard:]])
+
+
 class DeviceCdefPick:
     """Result record, per-block outputs and workspace of svt_hip_cdef_pick_strengths for a grid of n_fb filter blocks, pre-filled
     with `fill`.  run() only enqueues; download() waits for the stream."""
