@@ -29,7 +29,7 @@ def test_tier_a_fwd_inv(hip, orc, w, h):
     for tt in range(16):
         if not orc.orc_txfm_valid(w, h, tt):
             continue
-        for bd in (8, 10):
+        for bd in (8, 10, 12):
             trial = (tt + bd) % 3
             res = T.residual(rng, w, h, bd, trial)
             for shape, suf in ((0, ""), (1, "_N2"), (2, "_N4")):

@@ -43,7 +43,7 @@ def test_fwd_inv_vs_reference(orc, ref, w, h):
     for tt in range(16):
         if not orc.orc_txfm_valid(w, h, tt):
             continue
-        for bd in (8, 10):
+        for bd in (8, 10, 12):
             for trial in range(3):
                 res = T.residual(rng, w, h, bd, trial)
                 for shape, suf in ((0, ""), (1, "_N2"), (2, "_N4")):
@@ -112,6 +112,35 @@ def test_quantizers_vs_reference(orc, ref):
                       (run_ref(hfp, t["round_fp"], t["quant_fp"], ls), T.orc_quant(orc, 4, c))]
         for k, (a, b) in enumerate(pairs):
             assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2], (trial, k)
+
+
+def test_quantizers_single_matrix_vs_reference(orc, ref):
+    """The oracle's quantisers with qm only and with iqm only (the other pointer NULL: flat 32), and with both at 12-bit
+    magnitudes and over the whole range of a QmVal, against the reference's functions."""
+    rng = np.random.default_rng(12)
+    SIG = (V, C.c_ssize_t, V, V, V, V, V, V, V, V, V, V)
+    fns = [(rtcd(ref, "svt_aom_quantize_b", None, *SIG, V, V, C.c_int32), "round", "quant"),
+           (rtcd(ref, "svt_aom_highbd_quantize_b", None, *SIG, V, V, C.c_int32), "round", "quant"),
+           (rtcd(ref, "svt_av1_quantize_fp_qm", None, *SIG, V, V, C.c_int16), "round_fp", "quant_fp"),
+           (rtcd(ref, "svt_av1_highbd_quantize_fp_qm", None, *SIG, V, V, C.c_int16), "round_fp", "quant_fp")]
+    A = lambda a: a.ctypes.data if a is not None else None
+    for trial in range(240):
+        c = T.quant_case(rng, 1)                      # a permuted scan, both matrices
+        n, t = c["n"], c["t"]
+        if trial % 4 == 3:
+            c["qm"], c["iqm"] = rng.integers(1, 256, size=n).astype(np.uint8), rng.integers(1, 256, size=n).astype(np.uint8)
+        if trial % 5 == 4:
+            c["coeff"] = rng.integers(-(1 << 19), (1 << 19) + 1, size=n).astype(np.int32)   # 1 << (bd + 7) at 12 bits
+        if trial % 3 == 0:
+            c["iqm"] = None
+        elif trial % 3 == 1:
+            c["qm"] = None
+        for mode, (fn, rnd, qnt) in enumerate(fns, 1):
+            qc, dq, eob = np.full(n, 7, np.int32), np.full(n, 7, np.int32), C.c_uint16(9999)
+            fn(A(c["coeff"]), n, A(t["zbin"]), A(t[rnd]), A(t[qnt]), A(t["qshift"]), A(qc), A(dq), A(t["dequant"]), C.addressof(eob),
+               A(c["scan"]), A(c["iscan"]), A(c["qm"]), A(c["iqm"]), c["ls"])
+            o = T.orc_quant(orc, mode, c)
+            assert np.array_equal(qc, o[0]) and np.array_equal(dq, o[1]) and eob.value == o[2], (trial, mode)
 
 
 def golden_cases():
