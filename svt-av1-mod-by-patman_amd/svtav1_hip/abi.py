@@ -6,12 +6,32 @@ This module only describes the binary interface; it contains no compute and no C
 import ctypes as C
 import os
 
+import numpy as np
+
 from .prototypes import PROTOTYPES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_ROOT = os.path.dirname(_HERE)
 REPO_ROOT = os.path.dirname(PKG_ROOT)
 LIB_PATH = os.path.join(PKG_ROOT, "csrc", "libsvtav1_hip.so")
+
+
+def record_dtype(mirror):
+    """The numpy record of a ctypes.Structure, from the mirror's own fields, offsets and size: arrays keep their whole shape,
+    nested structures are records, pointers are addresses (<u8).  The *_DTYPE views below are this, so tests/test_abi.py, which
+    compares every mirror with the compiler's layout of its header struct, covers them."""
+    def fmt(t):
+        shape = ()
+        while issubclass(t, C.Array):
+            shape, t = shape + (t._length_,), t._type_
+        if issubclass(t, C.Structure):
+            base = record_dtype(t)
+        else:
+            base = np.dtype("<u8" if issubclass(t, (C.c_void_p, C._Pointer)) else t)
+        return np.dtype((base, shape)) if shape else base
+    names = [n for n, _ in mirror._fields_]
+    return np.dtype({"names": names, "formats": [fmt(t) for _, t in mirror._fields_],
+                     "offsets": [getattr(mirror, n).offset for n in names], "itemsize": C.sizeof(mirror)})
 
 ME_MAX_LIST, ME_MAX_REF, ME_SQUARE_PUS = 2, 4, 85
 
@@ -202,15 +222,8 @@ class TxbCost(C.Structure):            # SvtHipTxbCost
 
 
 # numpy views of SvtHipRateTables and of arrays of SvtHipTxbCostDesc / SvtHipTxbCost
-COEFF_COST_DTYPE = [("txb_skip", "<i4", (13, 2)), ("base_eob", "<i4", (4, 3)), ("base", "<i4", (42, 8)), ("eob_extra", "<i4", (9, 2)),
-                    ("dc_sign", "<i4", (3, 2)), ("lps", "<i4", (21, 26))]
-RATE_TABLES_DTYPE = [("coeff", COEFF_COST_DTYPE, (5, 2)), ("eob", "<i4", (7, 2, 2, 11)), ("intra_tx_type", "<i4", (3, 4, 13, 17)),
-                     ("inter_tx_type", "<i4", (4, 4, 17))]
-TXB_COST_DESC_DTYPE = [("qcoeff_off", "<u8"), ("iscan_off", "<u8"), ("table", "<u4"), ("lambda", "<u4"), ("eob", "<u2"), ("tx_type", "u1"),
-                       ("plane_type", "u1"), ("txb_skip_ctx", "u1"), ("dc_sign_ctx", "u1"), ("pred_mode", "u1"), ("filter_intra_mode", "u1"),
-                       ("reduced_tx_set", "u1"), ("fast_coeff_est_level", "u1"), ("subres_step", "u1"), ("est_mode", "u1"), ("flags", "u1"),
-                       ("pad_", "u1", (3,))]
-TXB_COST_DTYPE = [("bits", "<u8"), ("rd_cost", "<u8")]
+COEFF_COST_DTYPE, RATE_TABLES_DTYPE = record_dtype(CoeffCost), record_dtype(RateTables)
+TXB_COST_DESC_DTYPE, TXB_COST_DTYPE = record_dtype(TxbCostDesc), record_dtype(TxbCost)
 
 
 class CdefList(C.Structure):
@@ -246,9 +259,7 @@ class CdefPickResult(C.Structure):   # SvtHipCdefPickResult
 
 
 # numpy view of SvtHipCdefPickResult
-CDEF_PICK_RESULT_DTYPE = [("cdef_bits", "<i4"), ("nb_strengths", "<i4"), ("sb_count", "<i4"), ("pad_", "<i4"), ("y_index", "<i4", (8,)),
-                          ("uv_index", "<i4", (8,)), ("y_strength", "u1", (8,)), ("uv_strength", "u1", (8,)), ("best_cost", "<u8"),
-                          ("joint_mse", "<u8", (4,)), ("rd_cost", "<u8", (4,)), ("lev0", "<i4", (4, 8)), ("lev1", "<i4", (4, 8))]
+CDEF_PICK_RESULT_DTYPE = record_dtype(CdefPickResult)
 
 
 class LfMi(C.Structure):          # SvtHipLfMi (include/svt_hip_lf.h)
@@ -264,7 +275,7 @@ class LfFrame(C.Structure):       # SvtHipLfFrame
                 ("plane_start", C.c_uint8), ("plane_end", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
 
-LF_MI_DTYPE = [(n, "u1") for n in ("bsize", "tx_size_y", "tx_size_uv", "skip_inter", "segment_id", "ref_frame0", "mode_lf", "reserved")]
+LF_MI_DTYPE = record_dtype(LfMi)   # numpy view of the mode-info grid
 
 
 class SgrParams(C.Structure):     # SvtHipSgrParams == SgrParamsType
@@ -299,11 +310,7 @@ class LrUnit(C.Structure):          # SvtHipLrUnit
                 ("hfilter", C.c_int16 * 8), ("vfilter", C.c_int16 * 8)]
 
 
-import numpy as np  # noqa: E402
-
-LR_UNIT_DTYPE = np.dtype([("restoration_type", np.uint8), ("ep", np.uint8), ("pad_", np.int16), ("xqd", np.int32, 2),
-                          ("hfilter", np.int16, 8), ("vfilter", np.int16, 8)])
-assert LR_UNIT_DTYPE.itemsize == C.sizeof(LrUnit) == 44
+LR_UNIT_DTYPE = record_dtype(LrUnit)
 
 
 class LrPlane(C.Structure):         # SvtHipLrPlane
@@ -357,9 +364,7 @@ class MaskSearchResult(C.Structure):     # SvtHipMaskSearchResult
 
 
 # numpy view of an array of SvtHipMaskSearchResult
-MASK_SEARCH_RESULT_DTYPE = [("wedge_sse", "<u8", (WEDGE_TYPES,)), ("diffwtd_sse", "<u8", (2,)), ("pred0_to_pred1_dist", "<u4"),
-                            ("wedge_sign", "u1", (WEDGE_TYPES,)), ("best_wedge_index", "i1"), ("best_wedge_sign", "i1"),
-                            ("best_diffwtd_type", "u1"), ("status", "u1")]
+MASK_SEARCH_RESULT_DTYPE = record_dtype(MaskSearchResult)
 
 
 WARP_FILTER_ROWS, WARP_FILTER_BYTES = 193, 193 * 8 * 2                          # SVT_HIP_WARP_FILTER_*
@@ -392,8 +397,7 @@ class WarpErrorResult(C.Structure):      # SvtHipWarpErrorResult
 
 
 # numpy views of arrays of SvtHipWarpCandidate / SvtHipWarpErrorResult
-WARP_CANDIDATE_DTYPE = [("mat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2"), ("best_error", "<i8")]
-WARP_ERROR_RESULT_DTYPE = [("error", "<i8"), ("blocks_summed", "<u4"), ("status", "u1"), ("pad_", "u1", (3,))]
+WARP_CANDIDATE_DTYPE, WARP_ERROR_RESULT_DTYPE = record_dtype(WarpCandidate), record_dtype(WarpErrorResult)
 
 
 class TfBlock(C.Structure):              # SvtHipTfBlock (include/svt_hip_tf.h)
@@ -515,10 +519,4 @@ class CflDesc(C.Structure):              # SvtHipCflDesc
 
 
 # numpy views of arrays of SvtHipIntraPredDesc / SvtHipCflDesc (pointers as addresses)
-INTRA_PRED_DESC_DTYPE = [("above", "<u8"), ("left", "<u8"), ("dst", "<u8"), ("inter", "<u8"), ("left_stride", "<u4"), ("dst_stride", "<u4"),
-                         ("inter_stride", "<u4"), ("w", "u1"), ("h", "u1"), ("mode", "u1"), ("angle_delta", "i1"), ("filter_intra_mode", "u1"),
-                         ("disable_edge_filter", "u1"), ("filt_type", "u1"), ("ii_mode", "u1"), ("n_top_px", "u1"), ("n_topright_px", "u1"),
-                         ("n_left_px", "u1"), ("n_bottomleft_px", "u1"), ("is_16bit", "u1"), ("bit_depth", "u1"), ("pad_", "u1", (6,))]
-CFL_DESC_DTYPE = [("luma", "<u8"), ("pred", "<u8"), ("dst", "<u8"), ("ac_out", "<u8"), ("luma_stride", "<u4"), ("pred_stride", "<u4"),
-                  ("dst_stride", "<u4"), ("alpha_q3", "i1"), ("w", "u1"), ("h", "u1"), ("is_16bit", "u1"), ("bit_depth", "u1"), ("pad_", "u1", (7,))]
-assert np.dtype(INTRA_PRED_DESC_DTYPE).itemsize == C.sizeof(IntraPredDesc) == 64 and np.dtype(CFL_DESC_DTYPE).itemsize == C.sizeof(CflDesc) == 56
+INTRA_PRED_DESC_DTYPE, CFL_DESC_DTYPE = record_dtype(IntraPredDesc), record_dtype(CflDesc)

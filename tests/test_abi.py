@@ -1,15 +1,18 @@
 """CPU: the C-ABI shared library loads and exports every symbol the headers declare, every function carries the header's
 prototype and every struct mirror the header's layout (no compute calls)."""
 import ctypes as C
+import functools
 import glob
 import importlib
 import os
+import re
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from support import fresh_process, header_values
 from svtav1_hip import abi
 from svtav1_hip.prototypes import PROTOTYPES
 
@@ -66,39 +69,87 @@ def test_64_bit_return_arrives_whole(monkeypatch):
     assert abi.load().svt_hip_tf_workspace_bytes(7680, 4320, abi.TF_MAX_REFS) > 2 ** 32
 
 
-def _c_layout(tmp_path, struct, fields):
-    """{struct: sizeof, field: offsetof} as gcc lays out `struct` of include/*.h."""
-    headers = sorted(os.path.basename(h) for h in glob.glob(os.path.join(abi.REPO_ROOT, "include", "*.h")))
-    lines = ["#include <stddef.h>", "#include <stdio.h>"] + [f'#include "{h}"' for h in headers] + ["int main(void) {"]
-    lines.append(f'    printf("{struct} %zu\\n", sizeof({struct}));')
-    lines += [f'    printf("{f} %zu\\n", offsetof({struct}, {f}));' for f in fields]
-    lines.append("    return 0;\n}")
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-I", os.path.join(abi.REPO_ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
-    return {k: int(v) for k, v in (line.split() for line in out.splitlines())}
-
-
 MIRRORS = [c for c in vars(abi).values() if isinstance(c, type) and issubclass(c, C.Structure) and c.__module__ == abi.__name__]
-RECORD_VIEWS = {abi.LfMi: abi.LF_MI_DTYPE, abi.LrUnit: abi.LR_UNIT_DTYPE, abi.MaskSearchResult: abi.MASK_SEARCH_RESULT_DTYPE}
+
+
+@functools.lru_cache(maxsize=None)
+def c_layouts():
+    """sizeof of SvtHip<mirror>, and offsetof and sizeof of each of its members, for every mirror, as the compiler has them."""
+    exprs = []
+    for m in MIRRORS:
+        s = "SvtHip" + m.__name__
+        exprs.append(f"sizeof({s})")
+        for f, _ in m._fields_:
+            exprs += [f"offsetof({s}, {f})", f"sizeof((({s} *)0)->{f})"]
+    return header_values(exprs)
 
 
 @pytest.mark.parametrize("mirror", MIRRORS, ids=lambda m: m.__name__)
-def test_mirror_has_the_layout_of_its_header_struct(tmp_path, mirror):
-    """Every ctypes.Structure of abi.py is SvtHip<its name> of include/*.h: size and every field's offset as the compiler has
-    them; a numpy record view of the struct is the same record."""
+def test_mirror_has_the_layout_of_its_header_struct(mirror):
+    """Every ctypes.Structure of abi.py is SvtHip<its name> of include/*.h: size and every field's offset and size as the compiler
+    has them, and abi.record_dtype(mirror), the numpy view of an array of them, is the same record."""
     fields = [f for f, _ in mirror._fields_]
-    struct = "SvtHip" + mirror.__name__
-    want = _c_layout(tmp_path, struct, fields)
-    assert C.sizeof(mirror) == want[struct]
+    s, want, dt = "SvtHip" + mirror.__name__, c_layouts(), abi.record_dtype(mirror)
+    assert C.sizeof(mirror) == dt.itemsize == want[f"sizeof({s})"] and list(dt.names) == fields
     for f in fields:
-        assert getattr(mirror, f).offset == want[f], f
-    if mirror in RECORD_VIEWS:
-        dt = np.dtype(RECORD_VIEWS[mirror])
-        assert dt.itemsize == want[struct] and list(dt.names) == fields
-        for f in fields:
-            assert dt.fields[f][1] == want[f], f
+        offset, size = want[f"offsetof({s}, {f})"], want[f"sizeof((({s} *)0)->{f})"]
+        assert (getattr(mirror, f).offset, getattr(mirror, f).size) == (offset, size), f
+        assert (dt.fields[f][1], dt.fields[f][0].itemsize) == (offset, size), f
+
+
+@pytest.mark.parametrize("mirror", [abi.WarpDesc, abi.CdefPickParams, abi.CdefPickResult], ids=lambda m: m.__name__)
+def test_mirror_has_no_implicit_padding(mirror):
+    end = 0
+    for f, _ in mirror._fields_:
+        assert getattr(mirror, f).offset == end, f"implicit padding before {mirror.__name__}.{f}"
+        end += getattr(mirror, f).size
+    assert end == C.sizeof(mirror)
+
+
+def test_record_views_are_derived_from_their_mirrors():
+    """The literal sizes pin the headers themselves, not only the agreement; the shapes are what the CDEF pick tests index."""
+    assert [C.sizeof(m) for m in (abi.IntraPredDesc, abi.CflDesc, abi.LrUnit, abi.WarpDesc)] == [64, 56, 44, 104]
+    assert abi.INTRA_PRED_DESC_DTYPE.itemsize == 64 and abi.CFL_DESC_DTYPE.itemsize == 56 and abi.LR_UNIT_DTYPE.itemsize == 44
+    dt = abi.CDEF_PICK_RESULT_DTYPE
+    assert abi.CDEF_MAX_STRENGTHS == 64
+    assert (abi.CDEF_PICK_WIDTHS, abi.CDEF_PICK_MAX_LEVELS) == dt["lev0"].shape == dt["lev1"].shape == (4, 8)
+    assert abi.RATE_TABLES_DTYPE["coeff"].shape == (5, 2) and abi.RATE_TABLES_DTYPE["coeff"].base == abi.COEFF_COST_DTYPE
+    assert abi.COEFF_COST_DTYPE["lps"].shape == (21, 26) and abi.record_dtype(abi.MvCostParam)["ref_mv"] == np.dtype("<u8")
+
+
+# what the per-feature constant tests of blend, warp and CDEF pick compared one by one before this test took them over
+REQUIRED_CONSTANTS = {"SVT_HIP_BLEND_D16", "SVT_HIP_BLEND_D16_DIFFWTD", "SVT_HIP_BLEND_MASK", "SVT_HIP_BLEND_VMASK", "SVT_HIP_BLEND_HMASK",
+                      "SVT_HIP_WEDGE_TYPES", "SVT_HIP_MASK_SEARCH_OK", "SVT_HIP_MASK_SEARCH_BAD_WEDGE_SIZE", "SVT_HIP_MASK_SEARCH_BAD_DESC",
+                      "SVT_HIP_WARP_FILTER_ROWS", "SVT_HIP_WARP_FILTER_BYTES", "SVT_HIP_WARP_ERROR_BLOCK", "SVT_HIP_WARP_ERROR_OK",
+                      "SVT_HIP_WARP_ERROR_BAD_SHEAR", "SVT_HIP_CDEF_MAX_STRENGTHS"}
+CONSTANTS_FLOOR = 43   # how many of the headers' 59 constants abi.py states today; a count of what exists, it only grows
+
+
+def header_constants():
+    """Every object-like integer macro and every enumerator named SVT_HIP_* of include/*.h."""
+    names = []
+    for h in sorted(glob.glob(os.path.join(abi.REPO_ROOT, "include", "*.h"))):
+        with open(h) as f:
+            text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+        names += re.findall(r"^[ \t]*#[ \t]*define[ \t]+(SVT_HIP_\w+)[ \t]+[-+~()\w \t*<|]+$", text, re.M)   # a value, no strings, no continuation
+        for body in re.findall(r"\benum\b[^{;]*\{([^}]*)\}", text):
+            names += re.findall(r"\bSVT_HIP_\w+(?=\s*(?:=|,|$))", body)
+    return names
+
+
+def test_constants_are_those_of_the_headers():
+    """Every SVT_HIP_X of the headers that abi.py states (as X or as SVT_HIP_X) has the header's value there: the status codes as
+    the signed 32-bit values a ctypes call returns, everything else as 64-bit."""
+    names = header_constants()
+    assert len(set(names)) == len(names)
+    matched = set()
+    for name, value in header_values(names).items():
+        mine = getattr(abi, name, getattr(abi, name[len("SVT_HIP_"):], None))
+        if type(mine) is int:
+            assert (mine - value) % (1 << (32 if name.startswith("SVT_HIP_ERR_") else 64)) == 0, (name, mine, value)
+            matched.add(name)
+    assert matched >= REQUIRED_CONSTANTS, REQUIRED_CONSTANTS - matched
+    assert len(matched) >= CONSTANTS_FLOOR, sorted(matched)
 
 
 def test_every_mirror_is_covered():
@@ -168,8 +219,5 @@ def test_no_stream_ordered_allocator_on_the_launch_paths():
 def test_uninitialised_library_refuses_to_pick_a_device():
     """No silent fall-back to GPU 0 for a process that forgot svt_hip_init: without a successful init every entry
     point that needs the device reports SVT_HIP_ERR_NO_DEVICE."""
-    code = ("import sys; sys.path.insert(0, %r); from svtav1_hip import abi; import ctypes as C; lib = abi.load(); p = C.c_void_p();"
-            "rc = lib.svt_hip_malloc(C.byref(p), C.c_size_t(64)); print(rc, lib.svt_hip_last_error().decode())") % os.path.join(abi.REPO_ROOT, "svt-av1-mod-by-patman_amd")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True)
-    rc, msg = r.stdout.strip().split(" ", 1)
-    assert int(rc) == abi.SVT_HIP_ERR_NO_DEVICE and "not initialised" in msg
+    rc, said_so = fresh_process('lib.svt_hip_malloc(C.byref(p), 64), "not initialised" in lib.svt_hip_last_error().decode()')
+    assert rc == abi.SVT_HIP_ERR_NO_DEVICE and said_so

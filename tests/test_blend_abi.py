@@ -1,34 +1,18 @@
-"""CPU: the blend / mask-search constants of abi.py are those of include/svt_hip_inter.h, the golden
+"""CPU: the golden
 fixture of tests/blend_cases.py is what the reference computes (when oracle/_ref/libsvtref.so is built), and its cases reach what
 they are meant to reach."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import blend_cases as B
+from support import assert_not_rtcd_leaf
 from svtav1_hip import abi
-
-
-def test_blend_constants_match_header(tmp_path):
-    names = {"SVT_HIP_BLEND_D16": abi.BLEND_D16, "SVT_HIP_BLEND_D16_DIFFWTD": abi.BLEND_D16_DIFFWTD, "SVT_HIP_BLEND_MASK": abi.BLEND_MASK,
-             "SVT_HIP_BLEND_VMASK": abi.BLEND_VMASK, "SVT_HIP_BLEND_HMASK": abi.BLEND_HMASK, "SVT_HIP_WEDGE_TYPES": abi.WEDGE_TYPES,
-             "SVT_HIP_MASK_SEARCH_OK": abi.MASK_SEARCH_OK, "SVT_HIP_MASK_SEARCH_BAD_WEDGE_SIZE": abi.MASK_SEARCH_BAD_WEDGE_SIZE,
-             "SVT_HIP_MASK_SEARCH_BAD_DESC": abi.MASK_SEARCH_BAD_DESC}
-    src, exe = tmp_path / "consts.c", tmp_path / "consts"
-    src.write_text('#include <stdio.h>\n#include "svt_hip_inter.h"\nint main(void) {\n' +
-                   "".join(f'    printf("{n} %d\\n", (int)({n}));\n' for n in names) + "    return 0;\n}\n")
-    subprocess.run(["gcc", "-I", os.path.join(abi.REPO_ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert {n: int(v) for n, v in got.items()} == names
 
 
 @pytest.mark.parametrize("name", ["svt_hip_blend_batch", "svt_hip_compound_mask_search_batch"])
 def test_blend_exports_are_not_rtcd_leaves(name):
     """tools/e2e/gen_bind_table.py takes every exported name ending in _hip for an RTCD leaf."""
-    lib = abi.load()
-    assert hasattr(lib, name) and not name.endswith("_hip")
+    assert_not_rtcd_leaf(name)
 
 
 def test_blend_golden_matches_reference(ref):

@@ -2,12 +2,12 @@
 call reaches a device here: the workspace helper is layout arithmetic and every refusal comes before the library looks for one."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cdef_pick_cases as K
+from support import assert_not_rtcd_leaf
 from svtav1_hip import abi
 from svtav1_hip.prototypes import PROTOTYPES
 
@@ -30,34 +30,6 @@ def test_fixture_is_no_larger_than_the_leaves_fixture():
     assert os.path.getsize(os.path.join(gold, "cdef_pick.npz")) <= os.path.getsize(os.path.join(gold, "leaves.npz"))
 
 
-def test_mirrors_and_constants_match_the_header(tmp_path):
-    """Size of both structs, the offset of every field, no implicit padding, and the constants, as the compiler has them."""
-    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "svt_hip_lf.h"', "int main(void) {",
-             '    printf("MAX %d\\n", SVT_HIP_CDEF_MAX_STRENGTHS);']
-    for m in (abi.CdefPickParams, abi.CdefPickResult):
-        s = "SvtHip" + m.__name__
-        lines.append(f'    printf("{s} %zu\\n", sizeof({s}));')
-        lines += [f'    printf("{s}.{f} %zu %zu\\n", offsetof({s}, {f}), sizeof((({s} *)0)->{f}));' for f, _ in m._fields_]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines + ["    return 0;", "}"]))
-    subprocess.run(["gcc", "-I", os.path.join(abi.REPO_ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = {ln.split()[0]: [int(v) for v in ln.split()[1:]] for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()}
-    assert got["MAX"] == [abi.CDEF_MAX_STRENGTHS] == [64]
-    for m in (abi.CdefPickParams, abi.CdefPickResult):
-        s, end = "SvtHip" + m.__name__, 0
-        assert got[s] == [C.sizeof(m)]
-        for f, _ in m._fields_:
-            off, size = got[f"{s}.{f}"]
-            assert (off, size) == (getattr(m, f).offset, getattr(m, f).size), f
-            assert off == end, f"implicit padding before {s}.{f}"
-            end = off + size
-        assert end == C.sizeof(m)
-    dt = np.dtype(abi.CDEF_PICK_RESULT_DTYPE)
-    assert dt.itemsize == C.sizeof(abi.CdefPickResult) and list(dt.names) == [f for f, _ in abi.CdefPickResult._fields_]
-    assert all(dt.fields[f][1] == getattr(abi.CdefPickResult, f).offset for f in dt.names)
-    assert (abi.CDEF_PICK_WIDTHS, abi.CDEF_PICK_MAX_LEVELS) == dt["lev0"].shape == dt["lev1"].shape == (4, 8)
-
-
 def test_workspace_helper_is_layout_arithmetic():
     """Monotone in both arguments, 0 for empty input, needs no device (the library is not initialised here)."""
     f = abi.load().svt_hip_cdef_pick_workspace_bytes
@@ -76,8 +48,8 @@ def test_workspace_helper_is_layout_arithmetic():
 def test_new_names_are_exported_and_are_not_rtcd_leaves():
     lib = abi.load()
     for n in NAMES:
-        assert n in PROTOTYPES and hasattr(lib, n) and not n.endswith("_hip")
-        assert lib.svt_hip_rtcd_lookup(n.encode()) is None and lib.svt_hip_rtcd_lookup(n[len("svt_hip_"):].encode()) is None
+        assert_not_rtcd_leaf(n)
+        assert n in PROTOTYPES and lib.svt_hip_rtcd_lookup(n[len("svt_hip_"):].encode()) is None
     assert PROTOTYPES["svt_hip_cdef_pick_workspace_bytes"] == ("c_uint64", ("c_uint32", "c_int32"))
     assert PROTOTYPES["svt_hip_cdef_pick_strengths"] == ("c_int32", ("c_void_p",) * 7 + ("c_uint64", "c_void_p"))
 

@@ -3,6 +3,7 @@ what it is meant to reach."""
 import numpy as np
 import pytest
 
+from support import assert_not_rtcd_leaf
 from svtav1_hip import abi
 
 
@@ -30,5 +31,4 @@ def test_intra_golden_covers_every_mode_and_cost_form():
 @pytest.mark.parametrize("name", ["svt_hip_intra_search_frames"])
 def test_intra_export_is_not_an_rtcd_leaf(name):
     """tools/e2e/gen_bind_table.py takes every exported name ending in _hip for an RTCD leaf."""
-    lib = abi.load()
-    assert hasattr(lib, name) and not name.endswith("_hip")
+    assert_not_rtcd_leaf(name)

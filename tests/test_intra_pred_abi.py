@@ -4,14 +4,12 @@ reach."""
 import ast
 import ctypes as C
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import intra_pred_cases as P
+from support import assert_not_rtcd_leaf, build_pin, fresh_process, have_reference_tree
 from svtav1_hip import abi
 
 
@@ -30,27 +28,12 @@ def test_intra_pred_golden_matches_reference(ref, gold):
     assert keys.tolist() == gold["counter_keys"].tolist() and values.tolist() == gold["counter_values"].tolist()
 
 
-def _reference_tree():
-    """Where oracle/Makefile takes the reference from, with its include paths and defines."""
-    with open(os.path.join(abi.REPO_ROOT, "oracle", "Makefile")) as f:
-        mk = f.read()
-    root = os.environ.get("REF") or re.search(r"^REF\s*\?=\s*(\S+)", mk, re.M).group(1)
-    defs = re.search(r"^REF_DEFS\s*:=\s*(.*)$", mk, re.M).group(1).split()
-    incs = [f"-I{root}/{d}" for d in ("Source/API", "Source/Lib/Globals", "Source/Lib/Codec", "Source/Lib/C_DEFAULT", "third_party/fastfeat")]
-    return root, defs + incs
-
-
 def test_restatement_is_what_the_static_functions_do(ref, tmp_path):
     """build_intra_predictors / build_intra_predictors_high themselves (tests/intra_pred_pin_driver.c includes their file), with the
     reference's asserts on, against RefIntraPred.intra on every case."""
-    import pyorc
-    root, flags = _reference_tree()
-    if not os.path.isdir(os.path.join(root, "Source", "Lib", "Codec")):
+    if not have_reference_tree():
         pytest.skip("the reference tree is not present")
-    so = tmp_path / "intra_pred_pin.so"
-    subprocess.run(["gcc", "-O1", "-fPIC", "-shared", "-w", *flags, os.path.join(P.HERE, "intra_pred_pin_driver.c"), "-o", str(so), pyorc.REF_SO],
-                   check=True)
-    pin = C.CDLL(str(so))
+    pin = build_pin(tmp_path, os.path.join(P.HERE, "intra_pred_pin_driver.c"))
     V, i = C.c_void_p, C.c_int32
     pin.pin_build_intra_predictors.argtypes = [V, V, V] + [i] * 11
     pin.pin_build_intra_predictors_high.argtypes = [V, V, V] + [i] * 12
@@ -103,27 +86,13 @@ def test_case_list_has_every_group_size_and_format():
 @pytest.mark.parametrize("name", ["svt_hip_intra_predict_batch", "svt_hip_intra_predict_batch_packed", "svt_hip_cfl_predict_batch"])
 def test_intra_pred_export_is_not_an_rtcd_leaf(name):
     """tools/e2e/gen_bind_table.py takes every exported name ending in _hip for an RTCD leaf."""
-    lib = abi.load()
-    assert hasattr(lib, name) and not name.endswith("_hip")
-
-
-@pytest.mark.parametrize("mirror, view", [(abi.IntraPredDesc, abi.INTRA_PRED_DESC_DTYPE), (abi.CflDesc, abi.CFL_DESC_DTYPE)], ids=lambda m: getattr(m, "__name__", ""))
-def test_record_view_is_the_mirror(mirror, view):
-    """The numpy record the tests fill is the ctypes mirror that tests/test_abi.py compares with the header."""
-    dt = np.dtype(view)
-    assert dt.itemsize == C.sizeof(mirror) and list(dt.names) == [f for f, _ in mirror._fields_]
-    for f, _ in mirror._fields_:
-        assert dt.fields[f][1] == getattr(mirror, f).offset, f
+    assert_not_rtcd_leaf(name)
 
 
 def test_refusals_need_no_device():
     """A process that never called svt_hip_init: NULL / n == 0 are bad parameters, anything else SVT_HIP_ERR_NO_DEVICE; nothing is
     launched either way."""
-    code = ("import sys; sys.path.insert(0, %r); from svtav1_hip import abi; import ctypes as C; lib = abi.load(); b = C.create_string_buffer(256);"
-            "p = C.cast(b, C.c_void_p); print(lib.svt_hip_intra_predict_batch(None, 1, None), lib.svt_hip_intra_predict_batch(p, 0, None),"
-            "lib.svt_hip_intra_predict_batch_packed(p, 1, 3, None), lib.svt_hip_cfl_predict_batch(None, 1, None), lib.svt_hip_cfl_predict_batch(p, 0, None),"
-            "lib.svt_hip_intra_predict_batch(p, 1, None), lib.svt_hip_intra_predict_batch_packed(p, 1, 1, None), lib.svt_hip_cfl_predict_batch(p, 1, None))"
-            ) % os.path.join(abi.REPO_ROOT, "svt-av1-mod-by-patman_amd")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True)
-    got = [int(v) for v in r.stdout.split()]
+    got = fresh_process("lib.svt_hip_intra_predict_batch(None, 1, None), lib.svt_hip_intra_predict_batch(p, 0, None),"
+                        "lib.svt_hip_intra_predict_batch_packed(p, 1, 3, None), lib.svt_hip_cfl_predict_batch(None, 1, None), lib.svt_hip_cfl_predict_batch(p, 0, None),"
+                        "lib.svt_hip_intra_predict_batch(p, 1, None), lib.svt_hip_intra_predict_batch_packed(p, 1, 1, None), lib.svt_hip_cfl_predict_batch(p, 1, None)")
     assert got == [abi.SVT_HIP_ERR_BAD_PARAMETER] * 5 + [abi.SVT_HIP_ERR_NO_DEVICE] * 3

@@ -1,15 +1,11 @@
 """CPU: the golden fixture of the coefficient rate (tests/txb_cost_cases.py) is what the reference's svt_av1_cost_coeffs_txb returns, the
 numpy restatement equals it on every case, the cases reach what they are meant to reach, and the entry point refuses bad arguments
 without a device."""
-import ctypes as C
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import txb_cost_cases as T
+from support import assert_not_rtcd_leaf, fresh_process, have_reference_tree
 from svtav1_hip import abi
 
 
@@ -30,7 +26,7 @@ def blocks(gold):
 
 @pytest.fixture(scope="module")
 def pin(ref, tmp_path_factory):
-    if not os.path.isdir(os.path.join(T.reference_tree()[0], "Source", "Lib", "Codec")):
+    if not have_reference_tree():
         pytest.skip("the reference tree is not present")
     return T.Pin(ref, tmp_path_factory.mktemp("txb_cost_pin"))
 
@@ -140,33 +136,16 @@ def test_cases_reach_every_branch(blocks):
 @pytest.mark.parametrize("name", ["svt_hip_txb_cost_batch", "svt_hip_txb_cost_batch_placed"])
 def test_txb_cost_export_is_not_an_rtcd_leaf(name):
     """tools/e2e/gen_bind_table.py takes every exported name ending in _hip for an RTCD leaf."""
-    lib = abi.load()
-    assert hasattr(lib, name) and not name.endswith("_hip")
-    assert lib.svt_hip_rtcd_lookup(name.encode()) is None
-
-
-@pytest.mark.parametrize("mirror, view", [(abi.RateTables, abi.RATE_TABLES_DTYPE), (abi.TxbCostDesc, abi.TXB_COST_DESC_DTYPE),
-                                          (abi.TxbCost, abi.TXB_COST_DTYPE), (abi.CoeffCost, abi.COEFF_COST_DTYPE)], ids=lambda m: getattr(m, "__name__", ""))
-def test_record_view_is_the_mirror(mirror, view):
-    """The numpy record the tests fill is the ctypes mirror that tests/test_abi.py compares with the header."""
-    dt = np.dtype(view)
-    assert dt.itemsize == C.sizeof(mirror) and list(dt.names) == [f for f, _ in mirror._fields_]
-    for f, _ in mirror._fields_:
-        assert dt.fields[f][1] == getattr(mirror, f).offset, f
-        assert dt.fields[f][0].itemsize == getattr(mirror, f).size, f
+    assert_not_rtcd_leaf(name)
 
 
 def test_refusals_need_no_device():
     """A process that never called svt_hip_init: a size that is no transform size, no table set, and NULL arrays with blocks to do are
     bad parameters; an empty batch succeeds; anything else is SVT_HIP_ERR_NO_DEVICE.  Nothing is launched either way."""
-    code = ("import sys; sys.path.insert(0, %r); from svtav1_hip import abi; import ctypes as C; lib = abi.load(); b = C.create_string_buffer(256);"
-            "p = C.cast(b, C.c_void_p); f = lib.svt_hip_txb_cost_batch;"
-            "print(f(p, p, p, 1, None, None, p, 1, 4, 32, None), f(p, p, p, 1, None, None, p, 1, 12, 8, None), f(p, p, p, 1, None, None, p, 0, 64, 8, None),"
-            "f(p, p, p, 0, None, None, p, 1, 8, 8, None), f(p, p, p, 0, None, None, p, 0, 8, 8, None), f(p, None, p, 1, None, None, p, 1, 8, 8, None),"
-            "f(p, p, None, 1, None, None, p, 1, 8, 8, None), f(p, p, p, 1, None, None, None, 1, 8, 8, None),"
-            "lib.svt_hip_txb_cost_batch_placed(p, p, p, 1, None, None, None, 1, 8, 8, 1, None),"
-            "f(None, None, None, 1, None, None, None, 0, 16, 64, None), f(p, p, p, 1, None, None, p, 1, 16, 64, None))"
-            ) % os.path.join(abi.REPO_ROOT, "svt-av1-mod-by-patman_amd")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True)
-    got = [int(v) for v in r.stdout.split()]
+    got = fresh_process("(lambda f: ("
+                        "f(p, p, p, 1, None, None, p, 1, 4, 32, None), f(p, p, p, 1, None, None, p, 1, 12, 8, None), f(p, p, p, 1, None, None, p, 0, 64, 8, None),"
+                        "f(p, p, p, 0, None, None, p, 1, 8, 8, None), f(p, p, p, 0, None, None, p, 0, 8, 8, None), f(p, None, p, 1, None, None, p, 1, 8, 8, None),"
+                        "f(p, p, None, 1, None, None, p, 1, 8, 8, None), f(p, p, p, 1, None, None, None, 1, 8, 8, None),"
+                        "lib.svt_hip_txb_cost_batch_placed(p, p, p, 1, None, None, None, 1, 8, 8, 1, None),"
+                        "f(None, None, None, 1, None, None, None, 0, 16, 64, None), f(p, p, p, 1, None, None, p, 1, 16, 64, None)))(lib.svt_hip_txb_cost_batch)")
     assert got == [abi.SVT_HIP_ERR_BAD_PARAMETER] * 9 + [abi.SVT_HIP_OK, abi.SVT_HIP_ERR_NO_DEVICE]

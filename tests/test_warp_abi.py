@@ -1,44 +1,25 @@
-"""CPU: the warp constants of abi.py are those of include/svt_hip_inter.h, svt_hip_warp_shear_params is svt_get_shear_params,
+"""CPU: svt_hip_warp_shear_params is svt_get_shear_params,
 the golden fixture of tests/warp_cases.py is what the reference computes (when oracle/_ref/libsvtref.so is built), and its cases
 reach what they are meant to reach."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import blend_cases as B
 import warp_cases as W
+from support import assert_not_rtcd_leaf
 from svtav1_hip import abi
 
 ONE = W.ONE
-
-
-def test_warp_constants_match_header(tmp_path):
-    names = {"SVT_HIP_WARP_FILTER_ROWS": abi.WARP_FILTER_ROWS, "SVT_HIP_WARP_FILTER_BYTES": abi.WARP_FILTER_BYTES,
-             "SVT_HIP_WARP_ERROR_BLOCK": abi.WARP_ERROR_BLOCK, "SVT_HIP_WARP_ERROR_OK": abi.WARP_ERROR_OK,
-             "SVT_HIP_WARP_ERROR_BAD_SHEAR": abi.WARP_ERROR_BAD_SHEAR}
-    src, exe = tmp_path / "consts.c", tmp_path / "consts"
-    src.write_text('#include <stdio.h>\n#include "svt_hip_inter.h"\nint main(void) {\n' +
-                   "".join(f'    printf("{n} %d\\n", (int)({n}));\n' for n in names) + "    return 0;\n}\n")
-    subprocess.run(["gcc", "-I", os.path.join(abi.REPO_ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert {n: int(v) for n, v in got.items()} == names
-    for dtype, struct in ((abi.WARP_CANDIDATE_DTYPE, abi.WarpCandidate), (abi.WARP_ERROR_RESULT_DTYPE, abi.WarpErrorResult)):
-        dt = np.dtype(dtype)
-        assert dt.itemsize == C.sizeof(struct)
-        assert {n: dt.fields[n][1] for n in dt.names} == {n: getattr(struct, n).offset for n, _ in struct._fields_}
-    # no implicit padding in the descriptor
-    assert C.sizeof(abi.WarpDesc) == sum(C.sizeof(t) for _, t in abi.WarpDesc._fields_) == 104
 
 
 @pytest.mark.parametrize("name", ["svt_hip_warp_batch", "svt_hip_warp_error_batch", "svt_hip_gm_refine", "svt_hip_warp_shear_params",
                                   "svt_hip_warp_error_workspace_bytes"])
 def test_warp_exports_are_not_rtcd_leaves(name):
     """tools/e2e/gen_bind_table.py takes every exported name ending in _hip for an RTCD leaf."""
-    lib = abi.load()
-    assert hasattr(lib, name) and not name.endswith("_hip")
+    assert_not_rtcd_leaf(name)
 
 
 def shear_models():
@@ -171,7 +152,7 @@ def test_error_cases_cover_the_walk():
     for k, (w, h) in enumerate(W.ERROR_PICTURES):
         for chess in (0, 1):
             best, res = gold[f"error_{k}_{chess}_best"], gold[f"error_{k}_{chess}_results"]
-            assert len(best) == len(res) >= 40 and res.dtype == np.dtype(abi.WARP_ERROR_RESULT_DTYPE)
+            assert len(best) == len(res) >= 40 and res.dtype == abi.WARP_ERROR_RESULT_DTYPE
             assert (res["status"][n_valid:] == abi.WARP_ERROR_BAD_SHEAR).all() and len(res) - n_valid == 2 and (res["error"][n_valid:] == 0).all()
             assert (res["status"][:n_valid] == 0).all()
             full = np.repeat(res["error"][:n_valid:len(W.THRESHOLDS)], len(W.THRESHOLDS))   # the "max" threshold of each model

@@ -7,8 +7,6 @@ svt_av1_cost_coeffs_txb through tests/txb_cost_pin_driver.c wherever oracle/_ref
 import collections
 import ctypes as C
 import os
-import re
-import subprocess
 
 import numpy as np
 
@@ -327,26 +325,13 @@ def expected_rd(i, bits):
 
 
 # ------------------------------------------------------------------------------------------------ the reference, where it was built
-def reference_tree():
-    """Where oracle/Makefile takes the reference from, with its include paths and defines."""
-    with open(os.path.join(abi.REPO_ROOT, "oracle", "Makefile")) as f:
-        mk = f.read()
-    root = os.environ.get("REF") or re.search(r"^REF\s*\?=\s*(\S+)", mk, re.M).group(1)
-    defs = re.search(r"^REF_DEFS\s*:=\s*(.*)$", mk, re.M).group(1).split()
-    incs = [f"-I{root}/{d}" for d in ("Source/API", "Source/Lib/Globals", "Source/Lib/Codec", "Source/Lib/C_DEFAULT", "third_party/fastfeat")]
-    return root, defs + incs + ["-I" + os.path.join(abi.REPO_ROOT, "include")]
-
-
 class Pin:
     """tests/txb_cost_pin_driver.c built into `directory` against oracle/_ref/libsvtref.so (ref: the loaded pyorc.ref(), whose
     ref_init has set the RTCD pointers the rate estimation goes through)."""
 
     def __init__(self, ref, directory):
-        import pyorc
-        root, flags = reference_tree()
-        so = os.path.join(str(directory), "txb_cost_pin.so")
-        subprocess.run(["gcc", "-O1", "-fPIC", "-shared", "-w", *flags, os.path.join(HERE, "txb_cost_pin_driver.c"), "-o", so, pyorc.REF_SO], check=True)
-        self.ref, self.lib = ref, C.CDLL(so)
+        from support import build_pin
+        self.ref, self.lib = ref, build_pin(directory, os.path.join(HERE, "txb_cost_pin_driver.c"))
         self.lib.pin_tables_new.restype, self.lib.pin_tables_new.argtypes = C.c_void_p, [C.c_int32]
         self.lib.pin_tables_export.restype, self.lib.pin_tables_export.argtypes = C.c_size_t, [C.c_void_p, C.c_void_p]
         self.lib.pin_iscan.argtypes = [C.c_int32, C.c_int32, C.c_void_p]

@@ -7,7 +7,6 @@ Beside each median: its algorithmic bytes / time, and the reference's C function
 processes (the per-call cost of ctypes is measured and reported apart).  Writes profiles/r05_inter_blend_4k.json.  Needs the GPU.
     python tools/blend_time.py [repeats]"""
 import ctypes as C
-import json
 import multiprocessing as mp
 import os
 import statistics
@@ -23,6 +22,7 @@ for p in (os.path.join(ROOT, "svt-av1-mod-by-patman_amd"), os.path.join(ROOT, "t
 import blend_cases as B  # noqa: E402
 import conv_cases as K  # noqa: E402
 import pyorc  # noqa: E402
+from benchlib import timing  # noqa: E402
 from svtav1_hip import abi, device  # noqa: E402
 
 W, H, WORKERS = 3840, 2160, 16
@@ -126,28 +126,13 @@ def cpu_legs():
 
 
 # ---- the GPU ------------------------------------------------------------------------------------------------------------------
-def timed(torch, stream, repeats, launch):
-    for _ in range(3):
-        launch()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(repeats)]
-    for a, b in evs:
-        a.record(stream)
-        launch()
-        b.record(stream)
-    torch.cuda.synchronize()
-    ms = [a.elapsed_time(b) for a, b in evs]
-    return statistics.median(ms), min(ms), max(ms)
-
-
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 30
     assert repeats >= 20
     cpu = cpu_legs()   # before anything touches the GPU: the workers are forked
+    lib = timing.open_library()
+    assert lib is not None, abi.load().svt_hip_last_error().decode()
     import torch
-    lib = abi.load()
-    rc = lib.svt_hip_init(0)
-    assert rc == 0, lib.svt_hip_last_error().decode()
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
     gold = np.load(B.GOLD)
@@ -159,9 +144,8 @@ def main():
         return d
 
     def leg(name, ms, n, nbytes, extra=None):
-        med, lo, hi = ms
-        res["legs"][name] = {"descriptors": n, "median_ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4),
-                             "algorithmic_bytes": nbytes, "TBps": round(nbytes / (med * 1e-3) / 1e12, 3), **(extra or {})}
+        res["legs"][name] = {"descriptors": n, **timing.summary(ms), "algorithmic_bytes": nbytes,
+                             "TBps": round(nbytes / (statistics.median(ms) * 1e-3) / 1e12, 3), **(extra or {})}
 
     # (a) blend
     planes, wedge = blend_inputs()
@@ -180,7 +164,7 @@ def main():
                                            abi.BLEND_D16, sub, sub, 0, r0, r1, 10, 1, 0))
     d_desc = device.upload_descriptors(lib, descs)
     n_luma, n_chroma = W * H, 2 * (W // 2) * (H // 2)
-    leg("blend_4k10", timed(torch, stream, repeats, lambda: device.check(lib, lib.svt_hip_blend_batch(d_desc.ptr, len(descs), sp), "blend")),
+    leg("blend_4k10", timing.events(torch, stream, repeats, lambda: device.check(lib, lib.svt_hip_blend_batch(d_desc.ptr, len(descs), sp), "blend")),
         len(descs), n_luma * (4 + 1 + 2) + n_chroma * (4 + 4 + 2),
         {"bytes_note": "luma 4 N in + N mask + 2 N out, chroma 4 n in + 4 n mask + 2 n out; the masks come from an 8 KiB table"})
     got = d_dst[0].download(np.uint16, planes[0][0].shape)
@@ -197,15 +181,11 @@ def main():
         d_res = device.DeviceBuffer(lib, C.sizeof(abi.MaskSearchResult) * len(descs))
         n = len(descs) * size * size
         leg(f"search_{size}x{size}_4k8",
-            timed(torch, stream, repeats, lambda: device.check(lib, lib.svt_hip_compound_mask_search_batch(d_desc.ptr, d_res.ptr, len(descs), sp), "search")),
+            timing.events(torch, stream, repeats, lambda: device.check(lib, lib.svt_hip_compound_mask_search_batch(d_desc.ptr, d_res.ptr, len(descs), sp), "search")),
             len(descs), 3 * n + C.sizeof(abi.MaskSearchResult) * len(descs),
             {"bytes_note": "3 N samples in + one 168-byte record out per block; the 32 N mask bytes per block come from one table per size "
                            f"({32 * size * size} bytes, cache-resident)", "mask_bytes_read": 32 * n})
-    print(json.dumps(res))
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "r05_inter_blend_4k.json"), "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    timing.write_profile("r05_inter_blend_4k.json", res)
     assert got.any()
 
 

@@ -11,7 +11,6 @@ without a device the device half is null, without oracle/_ref the host half.
     python tools/cdef_pick_time.py [--repeats 20] [--out FILE]"""
 import argparse
 import ctypes as C
-import json
 import os
 import statistics
 import sys
@@ -26,7 +25,8 @@ for p in (os.path.join(ROOT, "svt-av1-mod-by-patman_amd"), os.path.join(ROOT, "t
 import pyorc  # noqa: E402
 import cdef_pick_cases as K  # noqa: E402
 import leaf_cases  # noqa: E402
-from svtav1_hip import abi, device  # noqa: E402
+from benchlib import timing  # noqa: E402
+from svtav1_hip import device  # noqa: E402
 
 COLS, ROWS = 60, 34
 STEPS = 5 << 3                      # the widest signalling width: 8 greedy + 32 refinement steps; the others run beside it
@@ -70,10 +70,9 @@ def main():
     assert args.repeats >= 20
     res = {"filter_blocks": COLS * ROWS, "repeats": args.repeats, "launches_per_pick": LAUNCHES, "serial_steps": STEPS}
     ref = pyorc.ref() if pyorc.have_ref() else None
-    import torch                    # before the library, as bench.py has it: both then share one HIP runtime
-    lib = abi.load()
-    have_gpu = lib.svt_hip_init(0) == 0
-    if have_gpu:
+    lib = timing.open_library()
+    if lib is not None:
+        import torch
         stream = torch.cuda.Stream()
         sp = C.c_void_p(stream.cuda_stream)
     for n in (16, 64):
@@ -83,7 +82,7 @@ def main():
         want = None
         if ref:
             r["host"], want = host_leg(ref, x, 3)
-        if not have_gpu:
+        if lib is None:
             continue
         d_mse, d_filt = device.DeviceBuffer(lib, x.mse.nbytes), device.DeviceBuffer(lib, x.filt.nbytes)
         d_mse.upload(x.mse), d_filt.upload(x.filt)
@@ -104,8 +103,7 @@ def main():
             b.record(stream)
             torch.cuda.synchronize()
         ms = [a.elapsed_time(b) for a, b in evs]
-        r["device"] = {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4),
-                       "per_launch_us": round(statistics.median(ms) * 1e3 / LAUNCHES, 2), "host_enqueue_median_ms": round(statistics.median(enqueue), 4),
+        r["device"] = {**timing.summary(ms), "per_launch_us": round(statistics.median(ms) * 1e3 / LAUNCHES, 2), "host_enqueue_median_ms": round(statistics.median(enqueue), 4),
                        "workspace_bytes": pick.workspace.nbytes}
         host = np.empty_like(x.mse)
         down = []
@@ -115,11 +113,7 @@ def main():
             device.check(lib, lib.svt_hip_stream_sync(sp), "sync")
             down.append((time.perf_counter() - t0) * 1e3)
         r["tables_download_ms"] = round(statistics.median(down), 4)
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    timing.write_profile(os.path.abspath(args.out), res)
 
 
 if __name__ == "__main__":

@@ -10,9 +10,7 @@ Algorithmic bytes = samples written (d * w * h) + edge samples read; the 64-byte
 profiles/intra_predict_4k.json; without a device the GPU half is recorded as null.
     python tools/intra_pred_time.py [repeats]"""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -22,6 +20,7 @@ for p in (os.path.join(ROOT, "svt-av1-mod-by-patman_amd"), os.path.join(ROOT, "t
     sys.path.insert(0, p)
 
 import intra_pred_cases as P  # noqa: E402
+from benchlib import timing  # noqa: E402
 from svtav1_hip import abi, device  # noqa: E402
 
 WIDTH, HEIGHT = 3840, 2160
@@ -52,29 +51,15 @@ def descriptors(size, variants, bd, is16, plane_ptr, stride, dst_ptr):
     return d, int(x.size * size * size * px + edges.sum() * px)
 
 
-def gpu_events(torch, stream, repeats, launch):
-    for _ in range(3):
-        launch()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(repeats)]
-    for a, b in evs:
-        a.record(stream)
-        launch()
-        b.record(stream)
-    torch.cuda.synchronize()
-    ms = [a.elapsed_time(b) for a, b in evs]
-    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
-
-
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 30
     res = {"width": WIDTH, "height": HEIGHT, "repeats": repeats, "roof_TBps": list(ROOF_TBPS),
            "packing": "waves_per_workgroup descriptors share one workgroup, one wavefront each; 4 is svt_hip_intra_predict_batch, 1 is wave-per-descriptor"}
-    import torch
-    lib = abi.load()
-    if lib.svt_hip_init(0) != 0:
+    lib = timing.open_library()
+    if lib is None:
         res["gpu"] = None
-        return write(res)
+        return timing.write_profile("intra_predict_4k.json", res)
+    import torch
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
     stride = WIDTH + 64
@@ -92,21 +77,13 @@ def main():
         entry = {"descriptors": n, "algorithmic_bytes": algo_bytes, "descriptor_bytes": int(descs.nbytes)}
         for waves in (4, 2, 1):
             launch = lambda: device.check(lib, lib.svt_hip_intra_predict_batch_packed(C.c_void_p(d_desc.ptr), n, waves, sp), "intra_predict")  # noqa: E731
-            t = gpu_events(torch, stream, repeats, launch)
+            t = timing.summary(timing.events(torch, stream, repeats, launch))
             t["fraction_of_roof"] = [round(algo_bytes / (t["median_ms"] * 1e-3) / (r * 1e12), 4) for r in ROOF_TBPS]
             t["descriptors_per_us"] = round(n / (t["median_ms"] * 1e3), 1)
             entry[f"waves_per_workgroup_{waves}"] = t
         res["gpu"][name] = entry
         del d_desc, d_dst, d_plane
-    write(res)
-
-
-def write(res):
-    print(json.dumps(res))
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "intra_predict_4k.json"), "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    timing.write_profile("intra_predict_4k.json", res)
 
 
 if __name__ == "__main__":

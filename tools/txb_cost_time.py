@@ -10,7 +10,6 @@ the wave-launch bound that profiles/intra_predict_4k.json measured; without a de
 import ctypes as C
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -20,6 +19,7 @@ for p in (os.path.join(ROOT, "svt-av1-mod-by-patman_amd"), os.path.join(ROOT, "t
     sys.path.insert(0, p)
 
 import txb_cost_cases as T  # noqa: E402
+from benchlib import timing  # noqa: E402
 from svtav1_hip import abi, device  # noqa: E402
 
 WIDTH, HEIGHT, CANDIDATES = 3840, 2160, 16
@@ -54,20 +54,6 @@ def workload(gold, size, rng):
     return arena, d
 
 
-def gpu_events(torch, stream, repeats, launch):
-    for _ in range(3):
-        launch()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(repeats)]
-    for a, b in evs:
-        a.record(stream)
-        launch()
-        b.record(stream)
-    torch.cuda.synchronize()
-    ms = [a.elapsed_time(b) for a, b in evs]
-    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
-
-
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 30
     res = {"width": WIDTH, "height": HEIGHT, "candidates_per_block": CANDIDATES, "repeats": repeats,
@@ -78,11 +64,11 @@ def main():
         res["intra_predict_descriptors_per_us"] = {k: v["waves_per_workgroup_4"]["descriptors_per_us"] for k, v in intra.items()}
     except (OSError, KeyError, TypeError):
         res["intra_predict_descriptors_per_us"] = None
-    import torch
-    lib = abi.load()
-    if lib.svt_hip_init(0) != 0:
+    lib = timing.open_library()
+    if lib is None:
         res["gpu"] = None
-        return write(res)
+        return timing.write_profile("txb_cost_4k.json", res)
+    import torch
     gold = T.Golden()
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
@@ -102,20 +88,12 @@ def main():
             launch = lambda: device.check(lib, lib.svt_hip_txb_cost_batch_placed(C.c_void_p(d_arena.ptr), C.c_void_p(d_desc.ptr), C.c_void_p(d_tab.ptr),  # noqa: E731
                                                                                  len(gold.tables), None, C.c_void_p(d_dist.ptr), C.c_void_p(d_out.ptr), nd, size, size,
                                                                                  lds, sp), "svt_hip_txb_cost_batch_placed")
-            t = gpu_events(torch, stream, repeats, launch)
+            t = timing.summary(timing.events(torch, stream, repeats, launch))
             t["descriptors_per_us"] = round(nd / (t["median_ms"] * 1e3), 1)
             entry[f"tables_in_lds_{lds}"] = t
         res["gpu"][f"{size}x{size}_16types"] = entry
         del d_desc, d_dist, d_out, d_arena, arena, descs
-    write(res)
-
-
-def write(res):
-    print(json.dumps(res))
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "txb_cost_4k.json"), "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    timing.write_profile("txb_cost_4k.json", res)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,6 @@ The GPU error of every timed candidate is checked against the reference's.  Writ
 device the GPU half is recorded as null.
     python tools/warp_time.py [repeats]"""
 import ctypes as C
-import json
 import os
 import statistics
 import sys
@@ -22,6 +21,7 @@ for p in (os.path.join(ROOT, "svt-av1-mod-by-patman_amd"), os.path.join(ROOT, "t
 
 import pyorc  # noqa: E402
 import warp_cases as W  # noqa: E402
+from benchlib import timing  # noqa: E402
 from svtav1_hip import abi, device  # noqa: E402
 
 WIDTH, HEIGHT = 1920, 1080
@@ -48,20 +48,6 @@ def cpu_leg(ref, pair, repeats=5):
     return out
 
 
-def gpu_events(torch, stream, repeats, launch):
-    for _ in range(3):
-        launch()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(repeats)]
-    for a, b in evs:
-        a.record(stream)
-        launch()
-        b.record(stream)
-    torch.cuda.synchronize()
-    ms = [a.elapsed_time(b) for a, b in evs]
-    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
-
-
 def host_clock(repeats, step):
     for _ in range(3):
         step()
@@ -80,11 +66,11 @@ def main():
     res = {"width": WIDTH, "height": HEIGHT, "repeats": repeats, "error_blocks": -(-WIDTH // 32) * -(-HEIGHT // 32)}
     ref = pyorc.ref() if pyorc.have_ref() else None
     res["cpu_reference_one_core"] = cpu_leg(ref, pair) if ref else None   # before anything touches the GPU
-    import torch
-    lib = abi.load()
-    if lib.svt_hip_init(0) != 0:   # no device: the CPU half alone is still a record
+    lib = timing.open_library()
+    if lib is None:   # no device: the CPU half alone is still a record
         res["gpu"] = None
-        return write(res)
+        return timing.write_profile("r06_warp_error_1080p.json", res)
+    import torch
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
     bufs, ptrs = [], {}
@@ -111,7 +97,7 @@ def main():
             d_cand, d_res = device.DeviceBuffer(lib, cand.nbytes), device.DeviceBuffer(lib, 16 * n)
             d_cand.upload(cand)
             launch = lambda: device.check(lib, lib.svt_hip_warp_error_batch(C.byref(job), d_cand.ptr, d_res.ptr, n, sp), "warp_error")  # noqa: E731
-            res["gpu"][f"warp_error_batch_n{n}_chess{chess}"] = {**gpu_events(torch, stream, repeats, launch), "errors": got["error"].tolist()}
+            res["gpu"][f"warp_error_batch_n{n}_chess{chess}"] = {**timing.summary(timing.events(torch, stream, repeats, launch)), "errors": got["error"].tolist()}
             if n == 1 and chess == 0:
                 host8 = np.zeros(1, np.int64)
 
@@ -127,15 +113,7 @@ def main():
                 mat, wt, err = device.gm_refine(lib, job, start, W.AFFINE, 5, W.INT64_MAX, stream.cuda_stream)
                 res["gpu"]["gm_refine_affine_5_refinements"] = {"wall_ms": round((time.perf_counter() - t0) * 1e3, 2), "error": err, "wmmat": mat[:6]}
             del ws
-    write(res)
-
-
-def write(res):
-    print(json.dumps(res))
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "r06_warp_error_1080p.json"), "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    timing.write_profile("r06_warp_error_1080p.json", res)
 
 
 if __name__ == "__main__":
