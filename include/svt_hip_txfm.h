@@ -299,6 +299,91 @@ SVT_HIP_API int32_t svt_hip_txb_cost_batch_placed(const uint8_t *d_base, const S
                                                   const uint64_t (*d_distortion)[2], SvtHipTxbCost *d_out, uint32_t n_blocks, uint32_t w,
                                                   uint32_t h, uint32_t tables_in_lds, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Tier B — the RDOQ stage of the quantiser: svt_aom_quantize_inv_quantize (full_loop.c:1562-1685) from the point after its first
+ * quantiser, that is the SATD gate, the eob_th / eob_fast_th decisions, svt_fast_optimize_b, svt_av1_optimize_b (:1124-1331, the
+ * trellis) and svt_av1_compute_cul_level_c, with allow_update_cdf = 0.  Run after svt_hip_txfm_quant_batch on the same stream with
+ * the same d_txfm_desc: that call has written coeff, qcoeff, dqcoeff (quant_mode QUANT_FP[_HBD], or the B family where the encoder
+ * has fp_q_y / fp_q_uv off), eob and, with SVT_HIP_TX_SATD, satd.  No Tier A leaf, for the reason the rate has none.
+ *
+ * The five launches of one transform-type search, all on one stream:
+ *   svt_hip_txfm_quant_batch (FWD + QUANT_FP[_HBD] + SATD, result array A) -> svt_hip_rdoq_batch (A) ->
+ *   svt_hip_txfm_quant_batch (quant_mode NONE, flags TX_INV: reads dqcoeff_off; result array B) ->
+ *   svt_hip_txfm_distortion_batch -> svt_hip_txb_cost_batch (A).
+ * The INV-only pass writes eob = 0 into the result array it is given, so it gets a second array B; A keeps the trellis's eob
+ * for the rate.
+ * ------------------------------------------------------------------------------------------- */
+enum { /* SvtHipRdoqDesc::flags */
+    SVT_HIP_RDOQ_PERFORM   = 1, /* the host-known part of perform_rdoq: (!mds_skip_rdoq || is_encode_pass) && rdoq_level, and for
+                                 * mode decision !(dct_dct_only && tx_type != DCT_DCT) && !(skip_uv && chroma) */
+    SVT_HIP_RDOQ_FAST_MODE = 2, /* fast_mode of svt_av1_optimize_b: the eob_fast_{y,uv}_{inter,intra} control of the block */
+    SVT_HIP_RDOQ_SHARPNESS = 4  /* use_sharpness && delta_q_present && luma && sb qindex below the picture's: rweight 0, sharpness 1 */
+};
+enum { /* SvtHipRdoqResult::path: the low three bits say which way the block went, the others what happened on the way */
+    SVT_HIP_RDOQ_PATH_NOT_FLAGGED = 0, /* no SVT_HIP_RDOQ_PERFORM: arrays and eob untouched */
+    SVT_HIP_RDOQ_PATH_EOB_ZERO,        /* eob 0 on entry, or after svt_fast_optimize_b (then with SVT_HIP_RDOQ_PATH_FAST_TRIM) */
+    SVT_HIP_RDOQ_PATH_REQUANT_SATD,    /* the SATD gate refused the trellis: quantised with the quantize_b family */
+    SVT_HIP_RDOQ_PATH_REQUANT_EOB,     /* eob_perc >= eob_th: quantised with the quantize_b family */
+    SVT_HIP_RDOQ_PATH_EARLY_EXIT,      /* the early exit of svt_av1_optimize_b */
+    SVT_HIP_RDOQ_PATH_TRELLIS,         /* svt_av1_optimize_b ran */
+    SVT_HIP_RDOQ_PATH_MASK      = 7,
+    SVT_HIP_RDOQ_PATH_FAST_TRIM = 8,   /* update_coeff_eob_fast ran (eob_fast_th, fast_mode or both) */
+    SVT_HIP_RDOQ_PATH_SKIP      = 16,  /* update_skip chose the all-zero block */
+    SVT_HIP_RDOQ_PATH_BAD_EOB   = 32   /* qcoeff[scan[eob - 1]] was zero where the trellis would start: see below */
+};
+
+typedef struct SvtHipRdoqDesc {
+    uint32_t table;                 /* index into d_tables (clamped to n_tables - 1) */
+    uint32_t lambda;                /* the lambda svt_aom_quantize_inv_quantize is given */
+    int16_t  zbin[2], round[2], quant[2], quant_shift[2]; /* [0] DC, [1] AC of the quantize_b family (zbin_qtx, round_qtx,
+                                                           * quant_qtx, quant_shift_qtx), read only where a block is re-quantised */
+    uint32_t early_exit_limit;      /* sq_size_idx * rdoq_ctrls.early_exit_th, sq_size_idx = 7 - log2(blk_geom->sq_size) */
+    uint8_t  plane_type;            /* 0 luma, 1 chroma */
+    uint8_t  txb_skip_ctx;          /* 0 .. 12 */
+    uint8_t  dc_sign_ctx;           /* 0 .. 2 */
+    uint8_t  is_inter;              /* pred_mode >= NEARESTMV */
+    uint8_t  eob_th, eob_fast_th;   /* rdoq_ctrls, percent of w * h; 255 = never */
+    uint8_t  satd_factor;           /* rdoq_ctrls.satd_factor; 255 = no SATD gate */
+    uint8_t  dequant_shift;         /* hbd_md ? bit depth of the picture - 5 : 3 */
+    uint8_t  flags;                 /* SVT_HIP_RDOQ_* */
+    uint8_t  pic_bit_depth;         /* bit depth of the picture (enhanced_pic->bit_depth), which the SATD gate scales by whatever depth
+                                     * the block is quantised at; 0 = the transform descriptor's bit_depth */
+    uint8_t  pad_[2];
+} SvtHipRdoqDesc;
+
+typedef struct SvtHipRdoqResult {
+    uint16_t eob;       /* the final eob, also written to d_txfm_result[i].eob */
+    uint8_t  cul_level; /* svt_av1_compute_cul_level_c of the final arrays (a caller with update_skip_ctx_dc_sign_ctx off ignores it) */
+    uint8_t  path;      /* SVT_HIP_RDOQ_PATH_* */
+} SvtHipRdoqResult;
+
+/* n_blocks transform blocks of ONE size w x h (any of the 19 transform sizes).  Of d_txfm_desc[i] the call reads coeff_off (input),
+ * qcoeff_off / dqcoeff_off (updated in place), iscan_off, qm_off, iqm_off, dequant, tx_type, bit_depth, quant_mode and log_scale;
+ * of d_txfm_result[i] eob (in and out) and satd (in; it is svt_aom_satd over the retained coefficients).  three_quad_energy and satd are never written.  Per block:
+ *   not SVT_HIP_RDOQ_PERFORM:  nothing but cul_level.
+ *   satd_factor != 255 and (satd >> ..) > satd_factor * (dequant[1] >> dequant_shift) * sqrt_tx_pixels_2d (full_loop.c:1574-1584),
+ *   or eob * 100 / (w * h) >= eob_th (:1630-1658):  coeff is quantised again with svt_aom_quantize_b / svt_aom_highbd_quantize_b
+ *       (qm / iqm included; the high-bit-depth form behind QUANT_FP_HBD) from this descriptor's zbin / round / quant / quant_shift;
+ *       a block whose quant_mode is already of the B family is left as it is.
+ *   eob * 100 / (w * h) >= eob_fast_th:  svt_fast_optimize_b.
+ *   then svt_av1_optimize_b, all of it.
+ * An eob above min(w,32) * min(h,32) is clamped to it; descriptor fields beyond their ranges are clamped into the tables.  The
+ * reference asserts qcoeff[scan[eob - 1]] != 0 where the trellis starts and the project's quantisers guarantee it; a block that
+ * breaks it keeps its arrays and eob, gets cul_level and path = PATH_TRELLIS | PATH_BAD_EOB, and nothing is read or written
+ * out of bounds.  iscan must hold values below min(w,32) * min(h,32); larger ones are reduced modulo that count.
+ * Returns SVT_HIP_ERR_BAD_PARAMETER, before any device is touched, for a w x h that is no transform size, for n_tables == 0 and for
+ * a NULL d_base, d_txfm_desc, d_desc, d_tables, d_txfm_result or d_out with n_blocks > 0; n_blocks == 0 succeeds. */
+SVT_HIP_API int32_t svt_hip_rdoq_batch(uint8_t *d_base, const SvtHipTxfmDesc *d_txfm_desc, const SvtHipRdoqDesc *d_desc,
+                                       const SvtHipRateTables *d_tables, uint32_t n_tables, SvtHipTxfmResult *d_txfm_result /* eob in/out, satd in */,
+                                       SvtHipRdoqResult *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, void *stream);
+/* The same with the work split chosen by the caller (a measuring aid): 0 a lane group per block, the block's walking lane goes on
+ * through update_coeff_simple in scan order; 1 a lane group per block, its lanes take one anti-diagonal per round; 2 one lane per
+ * block, which exists up to 128 retained coefficients (SVT_HIP_ERR_BAD_PARAMETER above, and for any other value).  All leave the same
+ * arrays; svt_hip_rdoq_batch uses the fastest one of each size. */
+SVT_HIP_API int32_t svt_hip_rdoq_batch_mapped(uint8_t *d_base, const SvtHipTxfmDesc *d_txfm_desc, const SvtHipRdoqDesc *d_desc,
+                                              const SvtHipRateTables *d_tables, uint32_t n_tables, SvtHipTxfmResult *d_txfm_result,
+                                              SvtHipRdoqResult *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, uint32_t mapping, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,8 +20,10 @@
 
 #include "../../include/svt_hip_txfm.h"
 #include "common.hpp"
+#include "txfm_rate_device.hpp"
 
 using namespace svthip;
+using namespace svthip::rate;
 
 namespace {
 
@@ -35,31 +37,6 @@ struct TxbCostLaunch {
     uint32_t n_tables;
     uint32_t n_blocks;
 };
-
-constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
-
-// tx_type_to_class (cabac_context_model.h:459-476): 0 two-dimensional, 1 horizontal, 2 vertical
-__device__ __forceinline__ int tx_class_of(int tx_type) { return tx_type < 10 ? 0 : (tx_type & 1) ? 1 : 2; }
-
-// get_golomb_cost (rd_cost.c:90-97)
-__device__ __forceinline__ int golomb_cost(int level) {
-    if (level < 15)
-        return 0;
-    const int length = 32 - __clz(level - 14);
-    return (2 * length - 1) * 512;
-}
-
-// get_eob_cost (rd_cost.c:281-298) with get_eob_pos_token, eb_k_eob_group_start and eb_k_eob_offset_bits in closed form
-__device__ __forceinline__ int eob_cost(int eob, const int32_t (*eob_bits)[11], const int32_t (*eob_extra)[2], int cls) {
-    const int pt = eob < 2 ? eob : 33 - __clz(eob - 1);
-    int       cost = eob_bits[cls != 0][pt - 1];
-    const int offset_bits = pt - 2;
-    if (offset_bits > 0) {
-        const int extra = eob - ((1 << offset_bits) + 1);
-        cost += eob_extra[pt - 3][(extra >> (offset_bits - 1)) & 1] + (offset_bits - 1) * 512;
-    }
-    return cost;
-}
 
 // av1_transform_type_rate_estimation (rd_cost.c:113-158) with get_ext_tx_set_type / ext_tx_set_index (definitions.h:1795-1836)
 __device__ int tx_type_rate(const SvtHipRateTables &t, const SvtHipTxbCostDesc &d, const TxbCostLaunch &p) {
@@ -88,8 +65,6 @@ __device__ int tx_type_rate(const SvtHipRateTables &t, const SvtHipTxbCostDesc &
         dir = d.filter_intra_mode == 1 ? 1 : d.filter_intra_mode == 2 ? 2 : d.filter_intra_mode == 3 ? 6 : 0;
     return t.intra_tx_type[set][sq][dir < 12 ? dir : 12][tx_type];
 }
-
-__device__ __forceinline__ int min3(int v) { return v < 3 ? v : 3; }
 
 // lps_cost[ctx][..] + Golomb tail of a level above NUM_BASE_LEVELS
 __device__ __forceinline__ int range_cost(const SvtHipCoeffCost &cc, int br_ctx, int level) {
@@ -123,44 +98,13 @@ __device__ __forceinline__ int position_cost(const SvtHipCoeffCost &cc, const ui
         v     = qc[pos];
         level = v < 0 ? -v : v;
     }
-    // get_br_ctx (common_utils.h:104-141)
-    int br_ctx = 0;
-    if (level > 2) {
-        int mag = L[1] + L[STRIDE];
-        mag += cls == 0 ? L[STRIDE + 1] : cls == 1 ? L[2] : L[2 * STRIDE];
-        mag    = (mag + 1) >> 1;
-        br_ctx = mag < 6 ? mag : 6;
-        if (pos != 0)
-            br_ctx += (cls == 0 ? (row < 2 && col < 2) : cls == 1 ? col == 0 : row == 0) ? 7 : 14;
-    }
+    const int br_ctx = level > 2 ? br_ctx_of<IW>(L, pos, row, col, cls) : 0;
     int cost;
     if (c == eob - 1) {  // get_nz_map_ctx with is_eob (encode_txb_ref_c.c:17-27); c >= 1 here
         const int ctx = c <= N / 8 ? 1 : c <= N / 4 ? 2 : 3;
         cost = cc.base_eob[ctx][level ? min3(level) - 1 : 0] + (level ? 512 : 0);
-    } else {  // get_nz_mag + get_nz_map_ctx_from_stats (coefficients.h:2884-2943)
-        int ctx = 0;
-        if (cls != 0 || pos != 0) {
-            int mag = min3(L[1]) + min3(L[STRIDE]);
-            if (cls == 0)
-                mag += min3(L[STRIDE + 1]) + min3(L[2]) + min3(L[2 * STRIDE]);
-            else if (cls == 2)
-                mag += min3(L[2 * STRIDE]) + min3(L[3 * STRIDE]) + min3(L[4 * STRIDE]);
-            else
-                mag += min3(L[2]) + min3(L[3]) + min3(L[4]);
-            ctx = (mag + 1) >> 1;
-            ctx = ctx < 4 ? ctx : 4;
-            if (cls == 0) {  // the rule eb_av1_nz_map_ctx_offset was generated by
-                if (orient < 0 && row < 2)
-                    ctx += 11;
-                else if (orient > 0 && col < 2)
-                    ctx += 16;
-                else
-                    ctx += row + col < 2 ? 1 : row + col < 4 ? 6 : 21;
-            } else {  // nz_map_ctx_offset_1d
-                const int k = cls == 1 ? col : row;
-                ctx += k == 0 ? 26 : k == 1 ? 31 : 36;
-            }
-        }
+    } else {
+        const int ctx = nz_ctx_of<IW>(L, pos, row, col, cls, orient);
         cost = cc.base[ctx][min3(level)];
         if (level)
             cost += c == 0 ? cc.dc_sign[dc_sign_ctx][v < 0] : 512;

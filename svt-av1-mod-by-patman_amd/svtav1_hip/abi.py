@@ -225,6 +225,27 @@ class TxbCost(C.Structure):            # SvtHipTxbCost
 COEFF_COST_DTYPE, RATE_TABLES_DTYPE = record_dtype(CoeffCost), record_dtype(RateTables)
 TXB_COST_DESC_DTYPE, TXB_COST_DTYPE = record_dtype(TxbCostDesc), record_dtype(TxbCost)
 
+RDOQ_PERFORM, RDOQ_FAST_MODE, RDOQ_SHARPNESS = 1, 2, 4                # SvtHipRdoqDesc::flags
+# SvtHipRdoqResult::path: the way a block went (path & RDOQ_PATH_MASK) and what happened on the way
+(RDOQ_PATH_NOT_FLAGGED, RDOQ_PATH_EOB_ZERO, RDOQ_PATH_REQUANT_SATD, RDOQ_PATH_REQUANT_EOB, RDOQ_PATH_EARLY_EXIT,
+ RDOQ_PATH_TRELLIS) = range(6)
+RDOQ_PATH_MASK, RDOQ_PATH_FAST_TRIM, RDOQ_PATH_SKIP, RDOQ_PATH_BAD_EOB = 7, 8, 16, 32
+
+
+class RdoqDesc(C.Structure):           # SvtHipRdoqDesc
+    _fields_ = [("table", C.c_uint32), ("lambda", C.c_uint32), ("zbin", C.c_int16 * 2), ("round", C.c_int16 * 2), ("quant", C.c_int16 * 2),
+                ("quant_shift", C.c_int16 * 2), ("early_exit_limit", C.c_uint32), ("plane_type", C.c_uint8), ("txb_skip_ctx", C.c_uint8),
+                ("dc_sign_ctx", C.c_uint8), ("is_inter", C.c_uint8), ("eob_th", C.c_uint8), ("eob_fast_th", C.c_uint8),
+                ("satd_factor", C.c_uint8), ("dequant_shift", C.c_uint8), ("flags", C.c_uint8), ("pic_bit_depth", C.c_uint8), ("pad_", C.c_uint8 * 2)]
+
+
+class RdoqResult(C.Structure):         # SvtHipRdoqResult
+    _fields_ = [("eob", C.c_uint16), ("cul_level", C.c_uint8), ("path", C.c_uint8)]
+
+
+TXFM_DESC_DTYPE, TXFM_RESULT_DTYPE = record_dtype(TxfmDesc), record_dtype(TxfmResult)
+RDOQ_DESC_DTYPE, RDOQ_RESULT_DTYPE = record_dtype(RdoqDesc), record_dtype(RdoqResult)
+
 
 class CdefList(C.Structure):
     _fields_ = [("by", C.c_uint8), ("bx", C.c_uint8)]

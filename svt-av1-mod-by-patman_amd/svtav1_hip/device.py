@@ -221,6 +221,29 @@ def txb_cost_batch(lib, d_base, descs, tables, w, h, d_txfm_result=None, d_disto
     return raw[guard:d_out.nbytes - guard].view(np.dtype(abi.TXB_COST_DTYPE)).copy(), np.concatenate([raw[:guard], raw[d_out.nbytes - guard:]])
 
 
+def rdoq_batch(lib, d_base, d_txfm_desc, descs, tables, d_txfm_result, w, h, stream=None, mapping=None, guard=64, fill=0xA5):
+    """svt_hip_rdoq_batch for blocks of one size w x h (one launch), behind svt_hip_txfm_quant_batch.  d_base: device address of the
+    arena; d_txfm_desc / d_txfm_result: device addresses of the transform batch's descriptors and results (eob is updated in place);
+    descs: a record array of abi.RDOQ_DESC_DTYPE (or a list of abi.RdoqDesc); tables: a record array of abi.RATE_TABLES_DTYPE.
+    With mapping (0, 1 or 2) the same through svt_hip_rdoq_batch_mapped.
+    Returns (results as a record array of abi.RDOQ_RESULT_DTYPE, the `guard` bytes before and after them: still `fill` if untouched)."""
+    n = len(descs)
+    tables = np.ascontiguousarray(tables, np.dtype(abi.RATE_TABLES_DTYPE)).reshape(-1)
+    d_desc, d_tab = upload_descriptors(lib, descs, stream), DeviceBuffer(lib, tables.nbytes)
+    d_tab.upload(tables, stream)
+    d_out = DeviceBuffer(lib, 2 * guard + C.sizeof(abi.RdoqResult) * n)
+    d_out.fill(fill, stream)
+    args = (C.c_void_p(d_base), C.c_void_p(d_txfm_desc), C.c_void_p(d_desc.ptr), C.c_void_p(d_tab.ptr), C.c_uint32(len(tables)),
+            C.c_void_p(d_txfm_result), C.c_void_p(d_out.ptr + guard), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h))
+    if mapping is None:
+        rc = lib.svt_hip_rdoq_batch(*args, C.c_void_p(stream))
+    else:
+        rc = lib.svt_hip_rdoq_batch_mapped(*args, C.c_uint32(mapping), C.c_void_p(stream))
+    check(lib, rc, "svt_hip_rdoq_batch")
+    raw = d_out.download(np.uint8, (d_out.nbytes,), stream)
+    return raw[guard:d_out.nbytes - guard].view(np.dtype(abi.RDOQ_RESULT_DTYPE)).copy(), np.concatenate([raw[:guard], raw[d_out.nbytes - guard:]])
+
+
 class DeviceCdefPick:
     """Result record, per-block outputs and workspace of svt_hip_cdef_pick_strengths for a grid of n_fb filter blocks, pre-filled
     with `fill`.  run() only enqueues; download() waits for the stream."""
