@@ -20,6 +20,7 @@
 
 #include "../../include/svt_hip_txfm.h"
 #include "common.hpp"
+#include "txb_geometry.hpp"
 #include "txfm_rate_device.hpp"
 
 using namespace svthip;
@@ -27,15 +28,12 @@ using namespace svthip::rate;
 
 namespace {
 
-// what the host derives from w x h once per launch
+// what the kernel reads of the launch; the first four are TxbGeometry's
 struct TxbCostLaunch {
-    int32_t  orient;      // sign of w - h: which family of eb_av1_nz_map_ctx_offset the size uses
-    int32_t  txs_ctx;     // (txsize_sqr_map + txsize_sqr_up_map + 1) >> 1
-    int32_t  sqr, sqr_up; // TX_4X4 .. TX_64X64 of min(w, h) and max(w, h)
-    int32_t  dist_shift;  // (MAX_TX_SCALE - av1_get_tx_scale_tab) * 2: 2, 0 or -2
+    int32_t  orient, txs_ctx, sqr, sqr_up;
+    int32_t  dist_shift;  // (MAX_TX_SCALE - tx_scale) * 2: 2, 0 or -2
     uint32_t area_th;     // (w * h) >> 6
-    uint32_t n_tables;
-    uint32_t n_blocks;
+    uint32_t n_tables, n_blocks;
 };
 
 // av1_transform_type_rate_estimation (rd_cost.c:113-158) with get_ext_tx_set_type / ext_tx_set_index (definitions.h:1795-1836)
@@ -66,12 +64,6 @@ __device__ int tx_type_rate(const SvtHipRateTables &t, const SvtHipTxbCostDesc &
     return t.intra_tx_type[set][sq][dir < 12 ? dir : 12][tx_type];
 }
 
-// lps_cost[ctx][..] + Golomb tail of a level above NUM_BASE_LEVELS
-__device__ __forceinline__ int range_cost(const SvtHipCoeffCost &cc, int br_ctx, int level) {
-    const int base_range = level - 3;
-    return cc.lps[br_ctx][base_range < 12 ? base_range : 12] + golomb_cost(level);
-}
-
 // the eob == 1 form (av1_cost_coeffs_txb_loop_cost_one_eob, rd_cost.c:310-337): no level is read
 __device__ __forceinline__ int one_eob_cost(const SvtHipCoeffCost &cc, int32_t v, int dc_sign_ctx) {
     const int level = v < 0 ? -v : v;
@@ -100,9 +92,8 @@ __device__ __forceinline__ int position_cost(const SvtHipCoeffCost &cc, const ui
     }
     const int br_ctx = level > 2 ? br_ctx_of<IW>(L, pos, row, col, cls) : 0;
     int cost;
-    if (c == eob - 1) {  // get_nz_map_ctx with is_eob (encode_txb_ref_c.c:17-27); c >= 1 here
-        const int ctx = c <= N / 8 ? 1 : c <= N / 4 ? 2 : 3;
-        cost = cc.base_eob[ctx][level ? min3(level) - 1 : 0] + (level ? 512 : 0);
+    if (c == eob - 1) {  // c >= 1 here
+        cost = cc.base_eob[eob_ctx_of<N>(c)][level ? min3(level) - 1 : 0] + (level ? 512 : 0);
     } else {
         const int ctx = nz_ctx_of<IW>(L, pos, row, col, cls, orient);
         cost = cc.base[ctx][min3(level)];
@@ -138,10 +129,9 @@ template <int IW, int IH, bool LDS_TABLES>
 __global__ __launch_bounds__(256) void txb_cost_kernel(const uint8_t *__restrict__ base, const SvtHipTxbCostDesc *__restrict__ descs,
                                                        const SvtHipRateTables *__restrict__ tables, const SvtHipTxfmResult *__restrict__ results,
                                                        const uint64_t (*__restrict__ dist)[2], SvtHipTxbCost *__restrict__ out, TxbCostLaunch prm) {
-    constexpr int N = IW * IH, G = N < 64 ? N : 64, BLOCKS = 256 / G;
-    constexpr int STRIDE = IW + 4, ROW_WORDS = STRIDE / 4, LEVEL_WORDS = ROW_WORDS * (IH + 4);
+    constexpr int N = IW * IH, G = group_lanes(N), BLOCKS = 256 / G;
+    constexpr int ROW_WORDS = Levels<IW, IH>::ROW_WORDS, LEVEL_WORDS = Levels<IW, IH>::WORDS;
     __shared__ uint32_t        lv[BLOCKS][LEVEL_WORDS];
-    constexpr int TABLE_WORDS = 2 * sizeof(SvtHipCoeffCost) / 4;
     __shared__ int32_t staged_words[LDS_TABLES ? TABLE_WORDS : 1];  // both planes of the table set of the workgroup's first block
     const SvtHipCoeffCost *staged = (const SvtHipCoeffCost *)staged_words;
     const int      gi = threadIdx.x / G, li = threadIdx.x % G;
@@ -230,18 +220,7 @@ __global__ __launch_bounds__(256) void txb_cost_kernel(const uint8_t *__restrict
     }
 }
 
-template <int IW, int IH>
-void launch(bool lds, dim3 grid, hipStream_t st, const uint8_t *base, const SvtHipTxbCostDesc *descs, const SvtHipRateTables *tables,
-            const SvtHipTxfmResult *results, const uint64_t (*dist)[2], SvtHipTxbCost *out, const TxbCostLaunch &prm) {
-    if (lds)
-        hipLaunchKernelGGL((txb_cost_kernel<IW, IH, true>), grid, dim3(256), 0, st, base, descs, tables, results, dist, out, prm);
-    else
-        hipLaunchKernelGGL((txb_cost_kernel<IW, IH, false>), grid, dim3(256), 0, st, base, descs, tables, results, dist, out, prm);
-}
-
 constexpr bool kTablesInLds = true;  // svt_hip_txb_cost_batch: the faster placement at every size of profiles/txb_cost_4k.json
-
-int size_index(uint32_t v) { return v == 4 ? 0 : v == 8 ? 1 : v == 16 ? 2 : v == 32 ? 3 : v == 64 ? 4 : -1; }
 
 }  // namespace
 
@@ -249,9 +228,8 @@ extern "C" int32_t svt_hip_txb_cost_batch_placed(const uint8_t *d_base, const Sv
                                                  uint32_t n_tables, const SvtHipTxfmResult *d_txfm_result, const uint64_t (*d_distortion)[2],
                                                  SvtHipTxbCost *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, uint32_t tables_in_lds,
                                                  void *stream) {
-    const int  sw = size_index(w), sh = size_index(h);
-    const bool is_tx_size = sw >= 0 && sh >= 0 && (sw > sh ? sw - sh : sh - sw) <= 2;  // 1:1, 1:2 and 1:4: the 19 transform sizes
-    if (!is_tx_size || n_tables == 0 || (n_blocks > 0 && (!d_base || !d_desc || !d_tables || !d_out))) {
+    const TxbGeometry g(w, h);
+    if (!g.valid || n_tables == 0 || (n_blocks > 0 && (!d_base || !d_desc || !d_tables || !d_out))) {
         set_error("svt_hip_txb_cost_batch: bad argument (%u x %u, %u table sets, %u blocks)", w, h, n_tables, n_blocks);
         return SVT_HIP_ERR_BAD_PARAMETER;
     }
@@ -259,25 +237,17 @@ extern "C" int32_t svt_hip_txb_cost_batch_placed(const uint8_t *d_base, const Sv
         return SVT_HIP_OK;
     if (!ensure_init())
         return SVT_HIP_ERR_NO_DEVICE;
-    TxbCostLaunch prm;
-    prm.orient = sw < sh ? -1 : sw > sh;
-    prm.sqr = sw < sh ? sw : sh, prm.sqr_up = sw > sh ? sw : sh;
-    prm.txs_ctx = (prm.sqr + prm.sqr_up + 1) >> 1;
-    const uint32_t pixels = w * h;
-    prm.dist_shift = (1 - (pixels > 1024 ? 2 : pixels > 256 ? 1 : 0)) * 2;  // av1_get_tx_scale_tab (full_loop.h:52)
-    prm.area_th = pixels >> 6, prm.n_tables = n_tables, prm.n_blocks = n_blocks;
-    const uint32_t iw = w < 32 ? w : 32, ih = h < 32 ? h : 32, n = iw * ih, per_wg = 256 / (n < 64 ? n : 64);
-    const uint32_t wanted = (n_blocks + per_wg - 1) / per_wg, cap = (uint32_t)cu_count() * 8;  // 8 workgroups fill a CU's wave slots
-    const dim3     grid(wanted < cap ? wanted : cap);
-    const bool     lds = tables_in_lds != 0;
-    hipStream_t    st = resolve_stream(stream);
-#define TXB_COST_CASE(W, H)                                                                       \
-    if (iw == W && ih == H)                                                                       \
-        launch<W, H>(lds, grid, st, d_base, d_desc, d_tables, d_txfm_result, d_distortion, d_out, prm);
-    TXB_COST_CASE(4, 4) TXB_COST_CASE(8, 8) TXB_COST_CASE(16, 16) TXB_COST_CASE(32, 32) TXB_COST_CASE(4, 8) TXB_COST_CASE(8, 4)
-    TXB_COST_CASE(8, 16) TXB_COST_CASE(16, 8) TXB_COST_CASE(16, 32) TXB_COST_CASE(32, 16) TXB_COST_CASE(4, 16) TXB_COST_CASE(16, 4)
-    TXB_COST_CASE(8, 32) TXB_COST_CASE(32, 8)
-#undef TXB_COST_CASE
+    const TxbCostLaunch prm{g.orient, g.txs_ctx, g.sqr, g.sqr_up, (1 - g.tx_scale) * 2, g.pixels >> 6, n_tables, n_blocks};
+    const dim3  grid(grid_blocks(n_blocks, 256 / group_lanes(g.retained), (uint32_t)cu_count() * 8));  // 8 workgroups fill a CU's wave slots
+    const bool  launched = for_retained_shape(g.iw, g.ih, [&](auto W, auto H) {
+        constexpr int IW = decltype(W)::value, IH = decltype(H)::value;
+        const auto    kernel = tables_in_lds ? txb_cost_kernel<IW, IH, true> : txb_cost_kernel<IW, IH, false>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, resolve_stream(stream), d_base, d_desc, d_tables, d_txfm_result, d_distortion, d_out, prm);
+    });
+    if (!launched) {
+        set_error("svt_hip_txb_cost_batch: no kernel for the retained shape %u x %u", g.iw, g.ih);
+        return SVT_HIP_ERR_RUNTIME;
+    }
     SVT_HIP_CHECK(hipGetLastError());
     return SVT_HIP_OK;
 }

@@ -24,6 +24,7 @@
 
 #include "../../include/svt_hip_txfm.h"
 #include "common.hpp"
+#include "txb_geometry.hpp"
 #include "txfm_block.hpp"
 #include "txfm_rate_device.hpp"
 
@@ -32,21 +33,17 @@ using namespace svthip::rate;
 
 namespace {
 
-// what the host derives from w x h once per launch
+// what the kernel reads of the launch; all but the counts are TxbGeometry's
 struct RdoqLaunch {
-    int32_t  orient;    // sign of w - h
-    int32_t  txs_ctx;   // (txsize_sqr_map + txsize_sqr_up_map + 1) >> 1
-    int32_t  tx_scale;  // av1_get_tx_scale_tab
-    int32_t  sqrt_px;   // sqrt_tx_pixels_2d
-    uint32_t pixels;    // w * h
-    uint32_t n_tables;
-    uint32_t n_blocks;
+    int32_t  orient, txs_ctx, tx_scale;
+    int32_t  sqrt_px;  // sqrt_retained
+    uint32_t pixels, n_tables, n_blocks;
 };
 
 // the walk of svt_av1_optimize_b over one block, by one lane
 template <int IW, int IH>
 struct Trellis {
-    static constexpr int BWL = ilog2(IW), STRIDE = IW + 4, N = IW * IH;
+    static constexpr int BWL = ilog2(IW), STRIDE = Levels<IW, IH>::STRIDE, N = IW * IH;
     const SvtHipCoeffCost *cc;
     const int32_t (*eob_bits)[11];
     uint8_t       *levels;  // LDS, padded
@@ -71,8 +68,7 @@ struct Trellis {
     __device__ __forceinline__ uint8_t *lv(int ci) const { return levels + (ci >> BWL) * STRIDE + (ci & (IW - 1)); }
     __device__ __forceinline__ int      lower_ctx(int ci) const { return nz_ctx_of<IW>(lv(ci), ci, ci >> BWL, ci & (IW - 1), cls, orient); }
     __device__ __forceinline__ int      br_ctx(int ci) const { return br_ctx_of<IW>(lv(ci), ci, ci >> BWL, ci & (IW - 1), cls); }
-    // get_lower_levels_ctx_eob
-    __device__ __forceinline__ int eob_ctx(int si) const { return si == 0 ? 0 : si <= N / 8 ? 1 : si <= N / 4 ? 2 : 3; }
+    __device__ __forceinline__ int      eob_ctx(int si) const { return si == 0 ? 0 : eob_ctx_of<N>(si); }
     // get_br_ctx_eob
     __device__ __forceinline__ int br_ctx_eob(int ci) const {
         if (ci == 0)
@@ -80,18 +76,13 @@ struct Trellis {
         const int row = ci >> BWL, col = ci & (IW - 1);
         return (cls == 0 ? (row < 2 && col < 2) : cls == 1 ? col == 0 : row == 0) ? 7 : 14;
     }
-    // get_br_cost
-    __device__ __forceinline__ int br_cost(int level, int ctx) const {
-        const int base_range = level - 3;
-        return cc->lps[ctx][base_range < 12 ? base_range : 12] + golomb_cost(level);
-    }
     // get_coeff_cost_general; abs_qc >= 1 where is_last
     __device__ __forceinline__ int cost_general(bool is_last, int ci, int abs_qc, int sign, int ctx) const {
         int cost = is_last ? cc->base_eob[ctx][min3(abs_qc) - 1] : cc->base[ctx][min3(abs_qc)];
         if (abs_qc != 0) {
             cost += ci == 0 ? cc->dc_sign[sign_ctx][sign] : 512;
             if (abs_qc > 2)
-                cost += br_cost(abs_qc, is_last ? br_ctx_eob(ci) : br_ctx(ci));
+                cost += range_cost(*cc, is_last ? br_ctx_eob(ci) : br_ctx(ci), abs_qc);
         }
         return cost;
     }
@@ -99,7 +90,7 @@ struct Trellis {
     __device__ __forceinline__ int cost_eob(int ci, int abs_qc, int sign, int ctx) const {
         int cost = cc->base_eob[ctx][min3(abs_qc) - 1] + (ci == 0 ? cc->dc_sign[sign_ctx][sign] : 512);
         if (abs_qc > 2)
-            cost += br_cost(abs_qc, br_ctx_eob(ci));
+            cost += range_cost(*cc, br_ctx_eob(ci), abs_qc);
         return cost;
     }
     // get_two_coeff_cost_simple with get_br_cost_with_diff; abs_qc >= 1
@@ -290,9 +281,8 @@ template <int IW, int IH, bool ROUNDS, bool LANE>
 __global__ __launch_bounds__(64) void rdoq_kernel(uint8_t *base, const SvtHipTxfmDesc *__restrict__ tdescs, const SvtHipRdoqDesc *__restrict__ descs,
                                                   const SvtHipRateTables *__restrict__ tables, SvtHipTxfmResult *results, SvtHipRdoqResult *out,
                                                   RdoqLaunch prm) {
-    constexpr int N = IW * IH, G = LANE ? 1 : N < 64 ? N : 64, BLOCKS = 64 / G, PER = N / G;
-    constexpr int STRIDE = IW + 4, ROW_WORDS = STRIDE / 4, LEVEL_WORDS = ROW_WORDS * (IH + 4);
-    constexpr int TABLE_WORDS = 2 * sizeof(SvtHipCoeffCost) / 4;
+    constexpr int N = IW * IH, G = LANE ? 1 : group_lanes(N), BLOCKS = 64 / G, PER = N / G;
+    constexpr int ROW_WORDS = Levels<IW, IH>::ROW_WORDS, LEVEL_WORDS = Levels<IW, IH>::WORDS;
     __shared__ uint32_t lv[BLOCKS][LEVEL_WORDS];
     __shared__ int16_t  scan_lds[BLOCKS][N];
     __shared__ int16_t  nz_lds[BLOCKS][8];
@@ -457,7 +447,7 @@ __global__ __launch_bounds__(64) void rdoq_kernel(uint8_t *base, const SvtHipTxf
             const uint8_t *levels = (const uint8_t *)lv[gi];
             const int      last = scan_lds[gi][eob - 1];
             int            new_eob = eob, bits = 0, si = -1;
-            if (levels[(last / IW) * STRIDE + last % IW] == 0) {
+            if (levels[(last / IW) * Levels<IW, IH>::STRIDE + last % IW] == 0) {
                 bits = SVT_HIP_RDOQ_PATH_BAD_EOB;
             } else {
                 bool skipped = false;
@@ -524,8 +514,6 @@ __global__ __launch_bounds__(64) void rdoq_kernel(uint8_t *base, const SvtHipTxf
     }
 }
 
-int size_index(uint32_t v) { return v == 4 ? 0 : v == 8 ? 1 : v == 16 ? 2 : v == 32 ? 3 : v == 64 ? 4 : -1; }
-
 }  // namespace
 
 constexpr uint32_t kLaneMax = 128;  // retained coefficients up to which the lane-per-block kernels exist (LDS, see the head of the file)
@@ -538,10 +526,9 @@ constexpr uint32_t mapping_for(uint32_t retained) { return retained <= kLaneMax 
 extern "C" int32_t svt_hip_rdoq_batch_mapped(uint8_t *d_base, const SvtHipTxfmDesc *d_txfm_desc, const SvtHipRdoqDesc *d_desc,
                                       const SvtHipRateTables *d_tables, uint32_t n_tables, SvtHipTxfmResult *d_txfm_result,
                                              SvtHipRdoqResult *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, uint32_t mapping, void *stream) {
-    const int  sw = size_index(w), sh = size_index(h);
-    const bool is_tx_size = sw >= 0 && sh >= 0 && (sw > sh ? sw - sh : sh - sw) <= 2;  // 1:1, 1:2 and 1:4: the 19 transform sizes
-    const bool is_mapping = mapping <= 1 || (mapping == 2 && (w < 32 ? w : 32) * (h < 32 ? h : 32) <= kLaneMax);
-    if (!is_tx_size || !is_mapping || n_tables == 0 || (n_blocks > 0 && (!d_base || !d_txfm_desc || !d_desc || !d_tables || !d_txfm_result || !d_out))) {
+    const TxbGeometry g(w, h);
+    const bool        is_mapping = mapping <= 1 || (mapping == 2 && g.retained <= kLaneMax);
+    if (!g.valid || !is_mapping || n_tables == 0 || (n_blocks > 0 && (!d_base || !d_txfm_desc || !d_desc || !d_tables || !d_txfm_result || !d_out))) {
         set_error("svt_hip_rdoq_batch: bad argument (%u x %u, %u table sets, %u blocks)", w, h, n_tables, n_blocks);
         return SVT_HIP_ERR_BAD_PARAMETER;
     }
@@ -549,38 +536,19 @@ extern "C" int32_t svt_hip_rdoq_batch_mapped(uint8_t *d_base, const SvtHipTxfmDe
         return SVT_HIP_OK;
     if (!ensure_init())
         return SVT_HIP_ERR_NO_DEVICE;
-    RdoqLaunch prm;
-    prm.orient = sw < sh ? -1 : sw > sh;
-    prm.txs_ctx = ((sw < sh ? sw : sh) + (sw > sh ? sw : sh) + 1) >> 1;
-    prm.pixels = w * h;
-    prm.tx_scale = prm.pixels > 1024 ? 2 : prm.pixels > 256 ? 1 : 0;  // av1_get_tx_scale_tab (full_loop.h:52)
-    prm.n_tables = n_tables, prm.n_blocks = n_blocks;
-    const uint32_t iw = w < 32 ? w : 32, ih = h < 32 ? h : 32, n = iw * ih, per_wg = mapping == 2 ? 64 : 64 / (n < 64 ? n : 64);
-    // sqrt_tx_pixels_2d (full_loop.c:1112): the root of the retained coefficient count, rounded up
-    uint32_t root = 1;
-    while (root * root < n) root++;
-    prm.sqrt_px = root;
-    const uint32_t wanted = (n_blocks + per_wg - 1) / per_wg, cap = (uint32_t)cu_count() * 16;
-    const dim3     grid(wanted < cap ? wanted : cap);
-    hipStream_t    st = resolve_stream(stream);
-#define RDOQ_LAUNCH(W, H, ROUNDS, LANE) \
-    hipLaunchKernelGGL((rdoq_kernel<W, H, ROUNDS, LANE>), grid, dim3(64), 0, st, d_base, d_txfm_desc, d_desc, d_tables, d_txfm_result, d_out, prm)
-#define RDOQ_CASE(W, H)                      \
-    if (iw == W && ih == H) {                \
-        if (mapping == 1)                    \
-            RDOQ_LAUNCH(W, H, true, false);  \
-        else if (mapping == 0)               \
-            RDOQ_LAUNCH(W, H, false, false); \
+    const RdoqLaunch prm{g.orient, g.txs_ctx, g.tx_scale, (int32_t)g.sqrt_retained, g.pixels, n_tables, n_blocks};
+    const dim3  grid(grid_blocks(n_blocks, mapping == 2 ? 64 : 64 / group_lanes(g.retained), (uint32_t)cu_count() * 16));
+    const bool  launched = for_retained_shape(g.iw, g.ih, [&](auto W, auto H) {
+        constexpr int IW = decltype(W)::value, IH = decltype(H)::value;
+        auto          kernel = mapping == 1 ? rdoq_kernel<IW, IH, true, false> : rdoq_kernel<IW, IH, false, false>;
+        if constexpr ((uint32_t)(IW * IH) <= kLaneMax)  // where the lane-per-block instance exists; is_mapping refused it elsewhere
+            kernel = mapping == 2 ? rdoq_kernel<IW, IH, false, true> : kernel;
+        hipLaunchKernelGGL(kernel, grid, dim3(64), 0, resolve_stream(stream), d_base, d_txfm_desc, d_desc, d_tables, d_txfm_result, d_out, prm);
+    });
+    if (!launched) {
+        set_error("svt_hip_rdoq_batch: no kernel for the retained shape %u x %u", g.iw, g.ih);
+        return SVT_HIP_ERR_RUNTIME;
     }
-#define RDOQ_CASE_LANE(W, H)                 \
-    RDOQ_CASE(W, H)                          \
-    if (iw == W && ih == H && mapping == 2)  \
-        RDOQ_LAUNCH(W, H, false, true);
-    RDOQ_CASE_LANE(4, 4) RDOQ_CASE_LANE(8, 8) RDOQ_CASE(16, 16) RDOQ_CASE(32, 32) RDOQ_CASE_LANE(4, 8) RDOQ_CASE_LANE(8, 4) RDOQ_CASE_LANE(8, 16)
-    RDOQ_CASE_LANE(16, 8) RDOQ_CASE(16, 32) RDOQ_CASE(32, 16) RDOQ_CASE_LANE(4, 16) RDOQ_CASE_LANE(16, 4) RDOQ_CASE(8, 32) RDOQ_CASE(32, 8)
-#undef RDOQ_CASE_LANE
-#undef RDOQ_CASE
-#undef RDOQ_LAUNCH
     SVT_HIP_CHECK(hipGetLastError());
     return SVT_HIP_OK;
 }
@@ -589,7 +557,7 @@ extern "C" int32_t svt_hip_rdoq_batch(uint8_t *d_base, const SvtHipTxfmDesc *d_t
                                       const SvtHipRateTables *d_tables, uint32_t n_tables, SvtHipTxfmResult *d_txfm_result,
                                       SvtHipRdoqResult *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, void *stream) {
     return svt_hip_rdoq_batch_mapped(d_base, d_txfm_desc, d_desc, d_tables, n_tables, d_txfm_result, d_out, n_blocks, w, h,
-                                     mapping_for((w < 32 ? w : 32) * (h < 32 ? h : 32)), stream);
+                                     mapping_for(TxbGeometry(w, h).retained), stream);
 }
 
 SVT_HIP_MODULE_WARMUP(txfm_rdoq)

@@ -32,10 +32,6 @@ Case = collections.namedtuple("Case", "group w h tx_type plane is_inter bd table
                                       "satd_factor early_exit_th sq_size fp_q eob dc recipe pic_bd")
 
 
-def tx_scale(w, h):
-    return T.tx_scale(w, h)
-
-
 def _cases():
     out = []
 
@@ -172,7 +168,7 @@ def coefficients(i, c, iscan, qt, qm):
     step = qt["dequant"][(pos != 0).astype(int)].astype(np.float64)
     if qm is not None:
         step = step * 32.0 / qm[pos]
-    mag = np.floor(np.maximum(level + u, 0) * step / (1 << tx_scale(c.w, c.h))).astype(np.int64)
+    mag = np.floor(np.maximum(level + u, 0) * step / (1 << T.tx_scale(c.w, c.h))).astype(np.int64)
     co[pos] = sign * mag
     assert np.abs(co).max() < 1 << 28
     return co.astype(np.int32)
@@ -188,7 +184,7 @@ def first_quant(orc, c, coeff, iscan, qt, qm, iqm):
 
 def quant(orc, mode, c, coeff, iscan, qt, qm, iqm):
     which = {abi.QUANT_B: 1, abi.QUANT_B_HBD: 2, abi.QUANT_FP: 3, abi.QUANT_FP_HBD: 4}[mode]
-    return tx_cases.orc_quant(orc, which, dict(n=len(iscan), ls=tx_scale(c.w, c.h), coeff=np.ascontiguousarray(coeff, np.int32),
+    return tx_cases.orc_quant(orc, which, dict(n=len(iscan), ls=T.tx_scale(c.w, c.h), coeff=np.ascontiguousarray(coeff, np.int32),
                                                 scan=T.scan_of(iscan).astype(np.int16), iscan=iscan, qm=qm, iqm=iqm, t=qt))
 
 
@@ -234,7 +230,7 @@ class Trellis:
         self.tc, self.q, self.dq = coeff, q, dq
         self.scan = T.scan_of(iscan).tolist()
         self.dequant, self.iqm = dqt, None if iqm is None else [int(v) for v in iqm]
-        self.shift, self.c, self.hit = tx_scale(c.w, c.h), c, hit
+        self.shift, self.c, self.hit = T.tx_scale(c.w, c.h), c, hit
         self.sharp = c.sharp
         self.rdmult = ((c.lam * PLANE_RD_MULT[c.is_inter][c.plane] * (0 if c.sharp else 100)) // 100 + 2) >> 2
         self.nz_off, self.br_off = neighbours(self.cls)
@@ -489,7 +485,7 @@ def mul32(a, b):
 
 def fast_trim(c, eob, coeff, q, dq, scan, dequant):
     """update_coeff_eob_fast (full_loop.c:1089-1108) -> new eob"""
-    shift = tx_scale(c.w, c.h)
+    shift = T.tx_scale(c.w, c.h)
     zbin = [int(d) + ((int(d) * 70 + 64) >> 7) for d in dequant]
     for i in range(eob - 1, -1, -1):
         rc = scan[i]
@@ -518,7 +514,7 @@ def restate(c, t, coeff, mode, q, dq, eob, satd, iscan, qt, qm, iqm, quant_b, hi
     path, perform, requant = abi.RDOQ_PATH_NOT_FLAGGED, bool(c.perform), False
     if perform and c.satd_factor != 255:
         s = satd
-        shift = 1 - tx_scale(c.w, c.h)
+        shift = 1 - T.tx_scale(c.w, c.h)
         s = s << -shift if shift < 0 else s >> shift
         limit = c.satd_factor * (dequant[1] >> dequant_shift(c)) * SQRT_TX_PIXELS[(c.w, c.h)]
         if s >> (c.pic_bd - 8) > limit:
@@ -634,7 +630,7 @@ def batch(blocks, w, h, order=None, repeat=1):
         fp = b.mode in (abi.QUANT_FP, abi.QUANT_FP_HBD)
         d["zbin"], d["round"], d["quant"] = b.qt["zbin"][:2], b.qt["round_fp" if fp else "round"][:2], b.qt["quant_fp" if fp else "quant"][:2]
         d["quant_shift"], d["dequant"] = b.qt["qshift"][:2], b.qt["dequant"][:2]
-        d["tx_type"], d["bit_depth"], d["quant_mode"], d["log_scale"] = c.tx_type, c.bd, b.mode, tx_scale(w, h)
+        d["tx_type"], d["bit_depth"], d["quant_mode"], d["log_scale"] = c.tx_type, c.bd, b.mode, T.tx_scale(w, h)
         r["table"], r["lambda"], r["early_exit_limit"] = c.table, c.lam, early_exit_limit(c)
         r["zbin"], r["round"], r["quant"], r["quant_shift"] = b.qt["zbin"][:2], b.qt["round"][:2], b.qt["quant"][:2], b.qt["qshift"][:2]
         r["plane_type"], r["txb_skip_ctx"], r["dc_sign_ctx"], r["is_inter"] = c.plane, c.skip_ctx, c.dc_sign_ctx, c.is_inter

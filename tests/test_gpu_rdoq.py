@@ -186,7 +186,7 @@ def test_chain_of_five_launches(hip, orc, gold, w, h):
     quantiser fed through the restatement, then the oracle's inverse, the distortion on the host, restate_bits and rd_cost."""
     rng = np.random.default_rng(w * 1000 + h)
     iw, ih = T.retained(w, h)
-    n, n_tb, ls = iw * ih, 9, R.tx_scale(w, h)
+    n, n_tb, ls = iw * ih, 9, T.tx_scale(w, h)
     types = T.size_types(w, h)
     ab = tx_cases.Arena()
     iscan_off = {t: ab.add(gold.iscan(w, h, t)) for t in types}

@@ -2,6 +2,8 @@
 restatement equals it on every case, the cases reach every branch they are meant to reach, the scans have the dependency order the
 walk rests on, and the entry point refuses bad arguments without a device."""
 import collections
+import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -150,6 +152,57 @@ def test_neighbours_follow_in_scan_order(gold):
         for dr, dc in set(nz) | set(br):
             assert (grid[row + dr, col + dc] > iscan).all(), (w, h, tx_type, dr, dc)
             assert dr >= 0 and dc >= 0 and dr + dc > 0   # a later anti-diagonal in every class: one diagonal's positions are independent
+
+
+GEOMETRY_FIELDS = "valid sw sh orient sqr sqr_up txs_ctx pixels tx_scale iw ih retained sqrt_retained".split()
+GEOMETRY_PROGRAM = """
+#include "txb_geometry.hpp"
+#include <cstdio>
+#include <cstdlib>
+using namespace svthip;
+static_assert(TxbGeometry(64, 16).retained == 512 && grid_blocks(9, 4, 100) == 3 && grid_blocks(8, 4, 100) == 2 && grid_blocks(9, 4, 2) == 2, "");
+int main(int argc, char **argv) {
+    for (int i = 1; i + 1 < argc; i += 2) {
+        const uint32_t w = (uint32_t)atoi(argv[i]), h = (uint32_t)atoi(argv[i + 1]);
+        const TxbGeometry g(w, h);
+        int got_w = -1, got_h = -1;
+        const bool listed = for_retained_shape(w, h, [&](auto W, auto H) { got_w = decltype(W)::value, got_h = decltype(H)::value; });
+        printf("%d %d %d %d %d %d %d %u %d %u %u %u %u %d %d %d\\n", (int)g.valid, g.sw, g.sh, g.orient, g.sqr, g.sqr_up, g.txs_ctx, g.pixels, g.tx_scale, g.iw,
+               g.ih, g.retained, g.sqrt_retained, (int)listed, got_w, got_h);
+    }
+    printf("%u %u %u %u\\n", group_lanes(16), group_lanes(32), group_lanes(64), group_lanes(1024));
+    return 0;
+}
+"""
+
+
+def test_geometry_header(tmp_path):
+    """csrc/txb_geometry.hpp by a host compiler alone, against the Python restatements: which (w, h) are transform sizes, every field
+    of the 19 that are, and that the list of retained shapes holds exactly the 14 of them (each handed on as itself)."""
+    src, exe = tmp_path / "geometry.cpp", tmp_path / "geometry"
+    src.write_text(GEOMETRY_PROGRAM)
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(abi.PKG_ROOT, "csrc"), str(src), "-o", str(exe)], check=True)
+    sides = (4, 8, 16, 32, 64)
+    sizes = [(w, h) for w in sides for h in sides] + [(3, 4), (12, 8), (128, 128), (0, 0)]
+    shapes = sorted({T.retained(w, h) for w, h in T.SIZES}) + [(64, 64), (4, 32), (2, 2)]
+    out = subprocess.run([str(exe)] + [str(v) for s in sizes + shapes for v in s], check=True, capture_output=True, text=True).stdout
+    rows = [list(map(int, line.split())) for line in out.splitlines()]
+    assert rows.pop() == [16, 32, 64, 64]   # group_lanes: 4, 2 and 1 blocks to a wavefront, then one block to 64 lanes
+    assert len(rows) == len(sizes) + len(shapes)
+    for (w, h), row in zip(sizes, rows):
+        g = dict(zip(GEOMETRY_FIELDS, row))
+        assert g["valid"] == ((w, h) in T.SIZES), (w, h)
+        if g["valid"]:
+            sw, sh = T.size_index(w), T.size_index(h)
+            want = dict(valid=1, sw=sw, sh=sh, orient=(w > h) - (w < h), sqr=min(sw, sh), sqr_up=max(sw, sh),
+                        txs_ctx=(T.size_index(min(w, h)) + T.size_index(max(w, h)) + 1) >> 1, pixels=w * h, tx_scale=T.tx_scale(w, h),
+                        iw=T.retained(w, h)[0], ih=T.retained(w, h)[1], retained=T.retained(w, h)[0] * T.retained(w, h)[1],
+                        sqrt_retained=R.SQRT_TX_PIXELS[(w, h)])
+            assert g == want, (w, h)
+    assert len(shapes) == 14 + 3
+    for (iw, ih), row in zip(shapes, rows[len(sizes):]):
+        listed = (iw, ih) in shapes[:14]
+        assert row[13:] == ([1, iw, ih] if listed else [0, -1, -1]), (iw, ih)
 
 
 @pytest.mark.parametrize("name", ["svt_hip_rdoq_batch", "svt_hip_rdoq_batch_mapped"])

@@ -77,7 +77,7 @@ def workload(gold, w, h, rng):
     fwd["residual_stride"] = fwd["pred_stride"] = fwd["recon_stride"] = w
     for f, src in (("zbin", "zbin"), ("round", "round_fp"), ("quant", "quant_fp"), ("quant_shift", "qshift"), ("dequant", "dequant")):
         fwd[f] = qt[src][:2]
-    fwd["tx_type"], fwd["bit_depth"], fwd["quant_mode"], fwd["log_scale"] = np.array(types)[which], 8, abi.QUANT_FP, R.tx_scale(w, h)
+    fwd["tx_type"], fwd["bit_depth"], fwd["quant_mode"], fwd["log_scale"] = np.array(types)[which], 8, abi.QUANT_FP, T.tx_scale(w, h)
     fwd["flags"] = abi.TX_FWD | abi.TX_SATD
     inv = fwd.copy()
     inv["quant_mode"], inv["flags"] = abi.QUANT_NONE, abi.TX_INV
