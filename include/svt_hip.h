@@ -43,6 +43,7 @@ typedef enum SvtHipStatus {
 SVT_HIP_API int32_t     svt_hip_init(int32_t device_ordinal);
 SVT_HIP_API void        svt_hip_shutdown(void);
 SVT_HIP_API int32_t     svt_hip_device_count(void);
+SVT_HIP_API int32_t     svt_hip_compute_units(void); /* of the device svt_hip_init chose (what the capped grids are sized by); 0 before it */
 SVT_HIP_API const char *svt_hip_last_error(void);   /* thread-local message of the last failure */
 SVT_HIP_API const char *svt_hip_version(void);
 

@@ -312,6 +312,7 @@ SVT_HIP_API int32_t svt_hip_txb_cost_batch_placed(const uint8_t *d_base, const S
  *   svt_hip_txfm_distortion_batch -> svt_hip_txb_cost_batch (A).
  * The INV-only pass writes eob = 0 into the result array it is given, so it gets a second array B; A keeps the trellis's eob
  * for the rate.
+ * svt_hip_txt_search_batch (the transform-type search, below) enqueues this chain and the decision behind it in one call.
  * ------------------------------------------------------------------------------------------- */
 enum { /* SvtHipRdoqDesc::flags */
     SVT_HIP_RDOQ_PERFORM   = 1, /* the host-known part of perform_rdoq: (!mds_skip_rdoq || is_encode_pass) && rdoq_level, and for
@@ -383,6 +384,141 @@ SVT_HIP_API int32_t svt_hip_rdoq_batch(uint8_t *d_base, const SvtHipTxfmDesc *d_
 SVT_HIP_API int32_t svt_hip_rdoq_batch_mapped(uint8_t *d_base, const SvtHipTxfmDesc *d_txfm_desc, const SvtHipRdoqDesc *d_desc,
                                               const SvtHipRateTables *d_tables, uint32_t n_tables, SvtHipTxfmResult *d_txfm_result,
                                               SvtHipRdoqResult *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, uint32_t mapping, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Tier B — the transform-type search of a transform block: tx_type_search (product_coding_loop.c:4458-4940), all of it on the
+ * device.  The five launches above leave one set of records per CANDIDATE (one transform type of one transform block); the calls
+ * below add the spatial distortion of :4697-4718, replay the loop's decision (:4581-4812) per block, gather the winner's arrays and
+ * leave ONE record per transform block.  No Tier A leaf, for the reason the rate has none.
+ *
+ * Out of scope (the caller keeps such blocks on the host): mds_subres_step != 0 (the inverse then runs at another size than the
+ * forward transform), tx_search_skip_flag, tune_ssim_level > 0 (the SSIM pass of :4815-4911), chroma, and the encoder-side hook.
+ * ------------------------------------------------------------------------------------------- */
+/* Where the source pixels of one candidate lie (svt_hip_txfm_spatial_distortion_batch) */
+typedef struct SvtHipSpatialSrc {
+    uint64_t src_off;        /* source pixels: uint8, or uint16 where the candidate's descriptor has SVT_HIP_TX_PIXEL16 */
+    uint32_t src_stride;     /* in pixels */
+    uint8_t  crop_w, crop_h; /* cropped_tx_width / cropped_tx_height, 1 .. w and 1 .. h; 0 or more than the side = the whole side */
+    uint8_t  pad_[2];
+} SvtHipSpatialSrc;
+
+/* d_distortion[i] = {DIST_CALC_RESIDUAL = sum (src - recon)^2, DIST_CALC_PREDICTION = sum (src - pred)^2} << 4 over the top-left
+ * crop_w x crop_h pixels of candidate i: svt_spatial_full_distortion_kernel, or svt_full_distortion_kernel16_bits with
+ * SVT_HIP_TX_PIXEL16, as product_coding_loop.c:4697-4718 calls them.  pred_off / recon_off, their strides and the flag come from
+ * d_desc[i]; run it behind the pass that wrote recon_off.  A candidate without pred_off or recon_off gets {0, 0}.  Any stride and
+ * any offset that is a multiple of the pixel size will do.
+ * Returns SVT_HIP_ERR_BAD_PARAMETER, before any device is touched, for a w x h that is no transform size and for a NULL pointer with
+ * n_blocks > 0; n_blocks == 0 succeeds. */
+SVT_HIP_API int32_t svt_hip_txfm_spatial_distortion_batch(const uint8_t *d_base, const SvtHipTxfmDesc *d_desc, const SvtHipSpatialSrc *d_src,
+                                                          uint64_t (*d_distortion)[2], uint32_t n_blocks, uint32_t w, uint32_t h, void *stream);
+
+#define SVT_HIP_TXT_MAX_CAND 16 /* TX_TYPES */
+enum { /* SvtHipTxtDesc::flags */
+    SVT_HIP_TXT_EARLY_EXIT  = 1, /* ssim_level <= SSIM_LVL_1 && !only_dct_dct: the coefficient-count / cost exit of :4798-4811 */
+    SVT_HIP_TXT_SPATIAL_SSE = 2  /* mds_spatial_sse || (!is_inter && tx_depth): the distortion is the spatial one */
+};
+enum { /* flags of svt_hip_txt_search_batch */
+    SVT_HIP_TXT_SEARCH_INVERSE = 1 /* some block has SVT_HIP_TXT_SPATIAL_SSE or a recon destination: run the inverse-only pass and the
+                                    * spatial distortion.  The block descriptors live on the device, so the call cannot derive this: the
+                                    * caller, who filled them, MUST set it whenever any block has SVT_HIP_TXT_SPATIAL_SSE.  Without it the
+                                    * call has neither spatial sums nor reconstructions: every block is decided as if SVT_HIP_TXT_SPATIAL_SSE
+                                    * were clear, on the transform-domain distortion, and dst_recon_off is skipped. */
+};
+
+/* What the host knows of one transform block before the loop.  Its candidates are the n_cand consecutive entries from first_cand of
+ * the per-candidate arrays, in the reference's loop order: after tx_type_group[_sc], only_dct_dct and av1_ext_tx_used have been
+ * applied.  A candidate's transform type is the tx_type of its SvtHipTxbCostDesc. */
+typedef struct SvtHipTxtDesc {
+    uint64_t src_off;             /* source pixels of the block (SVT_HIP_TXT_SPATIAL_SSE) */
+    uint64_t dst_qcoeff_off, dst_dqcoeff_off; /* int32 [n] each: where the winner's arrays go; SVT_HIP_NO_OFFSET skips one */
+    uint64_t dst_recon_off;       /* the winner's w x h reconstruction, pixel type of the winner's descriptor; SVT_HIP_NO_OFFSET skips it */
+    uint32_t first_cand;
+    uint32_t src_stride, dst_recon_stride; /* in pixels */
+    uint32_t full_lambda;
+    uint32_t early_exit_coeff_th, early_exit_dist_th; /* txt_ctrls */
+    uint32_t tx_pixels;           /* blk_geom->tx_width[tx_depth] * blk_geom->tx_height[tx_depth] */
+    uint16_t satd_early_exit_th;  /* already q-weighted as at :4533-4541; 0 = no SATD test */
+    uint16_t txt_rate_cost_th;    /* txt_ctrls.txt_rate_cost_th; 0 = none */
+    uint16_t group_start;         /* bit k: candidate k is the first of a transform-type group (best_tx_non_coeff = 64 * 64) */
+    uint8_t  n_cand;              /* 1 .. SVT_HIP_TXT_MAX_CAND; more are clamped */
+    uint8_t  flags;               /* SVT_HIP_TXT_* */
+    uint8_t  crop_w, crop_h;      /* as SvtHipSpatialSrc */
+    uint8_t  pad_[2];
+} SvtHipTxtDesc;
+
+typedef struct SvtHipTxtResult {
+    uint64_t bits;          /* y_txb_coeff_bits_txt[best_tx_type] */
+    uint64_t distortion[2]; /* txb_full_distortion_txt[DIST_SSD][best_tx_type][DIST_CALC_RESIDUAL, DIST_CALC_PREDICTION] */
+    uint64_t cost;          /* best_cost_tx_search (~0 where no candidate reached the comparison) */
+    uint16_t eob;
+    uint16_t quant_mask;    /* bit k: the reference would have run the quantiser of candidate k (it passed the rate-cost and SATD tests) */
+    uint16_t cost_mask;     /* bit k: candidate k reached the cost comparison */
+    uint8_t  tx_type;       /* best_tx_type */
+    uint8_t  cand;          /* the winner's index within the block, 0xFF if no candidate reached the comparison */
+    uint8_t  cul_level;     /* the winner's SvtHipRdoqResult::cul_level (0 without RDOQ results) */
+    uint8_t  pad_[7];
+} SvtHipTxtResult;
+
+/* The decision for n_blocks transform blocks of ONE size w x h over the records of n_cand candidates: d_txfm_result (array A of the
+ * chain: eob, satd, three_quad_energy), d_rdoq_result (or NULL), d_distortion and d_cost (its bits).  Per block, candidates in order,
+ * from best_cost = dct_cost = ~0, best_satd = INT_MAX, best_tx_type = DCT_DCT (tx_type, txt_rate = the transform-type rate
+ * svt_hip_txb_cost_batch charges the candidate: av1_txt_rate_est, 0 where the set has one type):
+ *     if the group starts here: best_non_coeff = 64 * 64
+ *     if tx_type != DCT_DCT && txt_rate_cost_th && (uint64_t)RDCOST(lambda, txt_rate, 0) * 1000 > dct_cost * txt_rate_cost_th: continue
+ *     if satd_early_exit_th: satd < best_satd ? best_satd = satd : if (satd - best_satd) * 100 > best_satd * satd_early_exit_th: continue
+ *     (quant_mask)  if eob == 0 && tx_type != DCT_DCT: continue
+ *     if (uint64_t)RDCOST(lambda, 0, dist[RESIDUAL]) > best_cost: continue
+ *     (cost_mask)  cost = RDCOST(lambda, bits, dist[RESIDUAL]); if cost < best_cost: this is the best; DCT_DCT also sets dct_cost
+ *     with SVT_HIP_TXT_EARLY_EXIT: if best_non_coeff < early_exit_coeff_th || best_cost < (early_exit_dist_th ?
+ *                                     RDCOST(lambda, 1, tx_pixels * early_exit_dist_th) : 0): the search ends
+ * in the reference's integer types (the uint64_t products wrap as in C, the SATD test is int).  Ties keep the earlier candidate.
+ * dist is d_distortion[i] itself with SVT_HIP_TXT_SPATIAL_SSE, else RIGHT_SIGNED_SHIFT(d_distortion[i] + three_quad_energy,
+ * (MAX_TX_SCALE - tx_scale) * 2) << min(subres_step, 2) for both entries, the residual figure svt_hip_txb_cost_batch forms.
+ * Where no candidate reaches the comparison the record is the reference's zero-initialised locals with DCT_DCT, and nothing is copied.
+ * Then the winner's qcoeff, dqcoeff (n = min(w,32) * min(h,32) int32 each) and w x h reconstruction (recon_off / recon_stride of its
+ * SvtHipTxfmDesc) are copied to the block's destinations; nothing is copied where a destination is the winner's own array (the
+ * reference's DCT_DCT case).  first_cand + n_cand beyond n_cand_total is cut at it; table and context fields are clamped as in
+ * svt_hip_txb_cost_batch.  Arena offsets are the caller's, as everywhere in this header.
+ * Returns SVT_HIP_ERR_BAD_PARAMETER, before any device is touched, for a w x h that is no transform size, for n_tables == 0 and for
+ * a NULL pointer other than d_rdoq_result with n_blocks > 0; n_blocks == 0 succeeds. */
+SVT_HIP_API int32_t svt_hip_txt_select_batch(uint8_t *d_base, const SvtHipTxtDesc *d_desc, const SvtHipTxfmDesc *d_txfm_desc,
+                                             const SvtHipTxbCostDesc *d_cost_desc, const SvtHipRateTables *d_tables, uint32_t n_tables,
+                                             const SvtHipTxfmResult *d_txfm_result, const SvtHipRdoqResult *d_rdoq_result,
+                                             const uint64_t (*d_distortion)[2], const SvtHipTxbCost *d_cost, SvtHipTxtResult *d_out,
+                                             uint32_t n_cand_total, uint32_t n_blocks, uint32_t w, uint32_t h, void *stream);
+/* The same with the work split chosen by the caller (a measuring aid): 0 one lane per block replays the loop, then the wavefront copies
+ * the winners of its 64 blocks one after the other; 1 the replay in one kernel and the copies in a second one, a wavefront per block.
+ * Both leave the same bytes; svt_hip_txt_select_batch uses the faster one.  Any other value is SVT_HIP_ERR_BAD_PARAMETER. */
+SVT_HIP_API int32_t svt_hip_txt_select_batch_mapped(uint8_t *d_base, const SvtHipTxtDesc *d_desc, const SvtHipTxfmDesc *d_txfm_desc,
+                                                    const SvtHipTxbCostDesc *d_cost_desc, const SvtHipRateTables *d_tables, uint32_t n_tables,
+                                                    const SvtHipTxfmResult *d_txfm_result, const SvtHipRdoqResult *d_rdoq_result,
+                                                    const uint64_t (*d_distortion)[2], const SvtHipTxbCost *d_cost, SvtHipTxtResult *d_out,
+                                                    uint32_t n_cand_total, uint32_t n_blocks, uint32_t w, uint32_t h, uint32_t mapping,
+                                                    void *stream);
+
+/* Bytes of scratch svt_hip_txt_search_batch needs for n_cand candidates of n_blocks blocks (host arithmetic only) */
+SVT_HIP_API size_t svt_hip_txt_search_scratch_bytes(uint32_t n_cand, uint32_t n_blocks);
+
+/* The whole search of n_blocks transform blocks of ONE size w x h with n_cand candidates in all, enqueued on one stream:
+ *   1. svt_hip_txfm_quant_batch over d_txfm_desc (the caller sets FWD, a quantiser and SATD)
+ *   2. svt_hip_rdoq_batch where d_rdoq_desc is given
+ *   3. with SVT_HIP_TXT_SEARCH_INVERSE the inverse-only pass over the SAME descriptors: it reads dqcoeff_off and writes recon_off of
+ *      every candidate that has dqcoeff_off, pred_off and recon_off, as quant_mode NONE / flags TX_INV would; its results go to an
+ *      array of its own in the scratch
+ *   4. svt_hip_txfm_distortion_batch, and with SVT_HIP_TXT_SEARCH_INVERSE (only then) the spatial distortion for the candidates of
+ *      blocks with SVT_HIP_TXT_SPATIAL_SSE
+ *   5. svt_hip_txb_cost_batch
+ *   6. svt_hip_txt_select_batch into d_out[n_blocks]; without SVT_HIP_TXT_SEARCH_INVERSE it takes SVT_HIP_TXT_SPATIAL_SSE as clear and
+ *      dst_recon_off as SVT_HIP_NO_OFFSET in every block
+ * The per-candidate records live in d_scratch (caller-owned, svt_hip_txt_search_scratch_bytes; 16-byte aligned) and may be reused by
+ * the next call on the same stream.  d_out is all a caller has to download.
+ * Returns SVT_HIP_ERR_BAD_PARAMETER, before any device is touched, for a w x h that is no transform size, for n_tables == 0, for a
+ * scratch smaller than svt_hip_txt_search_scratch_bytes(n_cand, n_blocks) and for a NULL pointer other than d_rdoq_desc with
+ * n_blocks > 0; n_blocks == 0 succeeds. */
+SVT_HIP_API int32_t svt_hip_txt_search_batch(uint8_t *d_base, const SvtHipTxfmDesc *d_txfm_desc, const SvtHipRdoqDesc *d_rdoq_desc,
+                                             const SvtHipTxbCostDesc *d_cost_desc, const SvtHipRateTables *d_tables, uint32_t n_tables,
+                                             const SvtHipTxtDesc *d_desc, void *d_scratch, size_t scratch_bytes, SvtHipTxtResult *d_out,
+                                             uint32_t n_cand, uint32_t n_blocks, uint32_t w, uint32_t h, uint32_t flags, void *stream);
 
 #ifdef __cplusplus
 }

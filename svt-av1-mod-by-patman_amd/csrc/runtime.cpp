@@ -340,6 +340,8 @@ using namespace svthip;
 
 extern "C" {
 
+int32_t svt_hip_compute_units(void) { return cu_count(); }
+
 int32_t svt_hip_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess)

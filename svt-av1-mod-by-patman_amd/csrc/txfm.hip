@@ -154,12 +154,17 @@ void           upload_tables() {
                 g_tables_rc = SVT_HIP_ERR_RUNTIME;
             }
 }
-int32_t txfm_ready() {
+}  // namespace
+
+// also called by txfm_txt.hip, whose inverse-only pass instantiates txfm_block too
+int32_t svthip::txfm_ready() {
     if (!ensure_init())
         return SVT_HIP_ERR_NO_DEVICE;
     std::call_once(g_tables_once, upload_tables);
     return g_tables_rc;
 }
+
+namespace {
 
 template <int W, int H>
 void launch_txfm(uint8_t *base, const SvtHipTxfmDesc *descs, SvtHipTxfmResult *res, uint32_t n, hipStream_t st) {

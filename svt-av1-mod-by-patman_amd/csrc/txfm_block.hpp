@@ -10,6 +10,7 @@
 #include "txfm_device.hpp"
 
 namespace svthip {
+int32_t txfm_ready();  // txfm.hip: the library is initialised and the transform constants passed their self-check
 namespace txb {
 using namespace svthip::txd;
 

@@ -36,34 +36,6 @@ struct TxbCostLaunch {
     uint32_t n_tables, n_blocks;
 };
 
-// av1_transform_type_rate_estimation (rd_cost.c:113-158) with get_ext_tx_set_type / ext_tx_set_index (definitions.h:1795-1836)
-__device__ int tx_type_rate(const SvtHipRateTables &t, const SvtHipTxbCostDesc &d, const TxbCostLaunch &p) {
-    const int is_inter = d.pred_mode >= 13 && d.pred_mode < 25;
-    int       set_type;  // TxSetType
-    if (p.sqr_up > 3)
-        set_type = 0;
-    else if (p.sqr_up == 3)
-        set_type = is_inter ? 1 : 0;
-    else if (d.reduced_tx_set)
-        set_type = is_inter ? 1 : 2;
-    else if (is_inter)
-        set_type = p.sqr == 2 ? 4 : 5;
-    else
-        set_type = p.sqr == 2 ? 2 : 3;
-    if (set_type == 0)  // one type in the set
-        return 0;
-    const int tx_type = d.tx_type & 15, sq = p.sqr < 3 ? p.sqr : 3;
-    if (is_inter) {
-        const int set = set_type == 1 ? 3 : set_type == 4 ? 2 : 1;
-        return t.inter_tx_type[set][sq][tx_type];
-    }
-    const int set = set_type == 3 ? 1 : 2;
-    int       dir = d.pred_mode;
-    if (d.filter_intra_mode < 5)  // fimode_to_intradir
-        dir = d.filter_intra_mode == 1 ? 1 : d.filter_intra_mode == 2 ? 2 : d.filter_intra_mode == 3 ? 6 : 0;
-    return t.intra_tx_type[set][sq][dir < 12 ? dir : 12][tx_type];
-}
-
 // the eob == 1 form (av1_cost_coeffs_txb_loop_cost_one_eob, rd_cost.c:310-337): no level is read
 __device__ __forceinline__ int one_eob_cost(const SvtHipCoeffCost &cc, int32_t v, int dc_sign_ctx) {
     const int level = v < 0 ? -v : v;
@@ -194,7 +166,7 @@ __global__ __launch_bounds__(256) void txb_cost_kernel(const uint8_t *__restrict
             if (li == 0) {
                 cost += cc_global.txb_skip[skip_ctx][0] + eob_cost(eob, t.eob[ilog2(N) - 4][plane], cc_global.eob_extra, cls);
                 if (!plane)
-                    cost += tx_type_rate(t, d, prm);
+                    cost += tx_type_rate(t, d, prm.sqr, prm.sqr_up);
             }
         }
 #pragma unroll

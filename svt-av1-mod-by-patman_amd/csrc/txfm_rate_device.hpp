@@ -53,6 +53,35 @@ __device__ __forceinline__ int range_cost(const SvtHipCoeffCost &cc, int br_ctx,
 
 __device__ __forceinline__ int min3(int v) { return v < 3 ? v : 3; }
 
+// av1_transform_type_rate_estimation (rd_cost.c:113-158) with get_ext_tx_set_type / ext_tx_set_index (definitions.h:1795-1836), which
+// is also av1_txt_rate_est (product_coding_loop.c:4432-4454); sqr, sqr_up: TxbGeometry's
+__device__ inline int tx_type_rate(const SvtHipRateTables &t, const SvtHipTxbCostDesc &d, int sqr, int sqr_up) {
+    const int is_inter = d.pred_mode >= 13 && d.pred_mode < 25;
+    int       set_type;  // TxSetType
+    if (sqr_up > 3)
+        set_type = 0;
+    else if (sqr_up == 3)
+        set_type = is_inter ? 1 : 0;
+    else if (d.reduced_tx_set)
+        set_type = is_inter ? 1 : 2;
+    else if (is_inter)
+        set_type = sqr == 2 ? 4 : 5;
+    else
+        set_type = sqr == 2 ? 2 : 3;
+    if (set_type == 0)  // one type in the set
+        return 0;
+    const int tx_type = d.tx_type & 15, sq = sqr < 3 ? sqr : 3;
+    if (is_inter) {
+        const int set = set_type == 1 ? 3 : set_type == 4 ? 2 : 1;
+        return t.inter_tx_type[set][sq][tx_type];
+    }
+    const int set = set_type == 3 ? 1 : 2;
+    int       dir = d.pred_mode;
+    if (d.filter_intra_mode < 5)  // fimode_to_intradir
+        dir = d.filter_intra_mode == 1 ? 1 : d.filter_intra_mode == 2 ? 2 : d.filter_intra_mode == 3 ? 6 : 0;
+    return t.intra_tx_type[set][sq][dir < 12 ? dir : 12][tx_type];
+}
+
 // get_nz_map_ctx with is_eob (encode_txb_ref_c.c:17-27), get_lower_levels_ctx_eob: of scan index c >= 1 (scan index 0 has context 0)
 template <int N>
 __device__ __forceinline__ int eob_ctx_of(int c) { return c <= N / 8 ? 1 : c <= N / 4 ? 2 : 3; }

@@ -246,6 +246,31 @@ class RdoqResult(C.Structure):         # SvtHipRdoqResult
 TXFM_DESC_DTYPE, TXFM_RESULT_DTYPE = record_dtype(TxfmDesc), record_dtype(TxfmResult)
 RDOQ_DESC_DTYPE, RDOQ_RESULT_DTYPE = record_dtype(RdoqDesc), record_dtype(RdoqResult)
 
+TXT_MAX_CAND = 16                                                     # SVT_HIP_TXT_MAX_CAND
+TXT_EARLY_EXIT, TXT_SPATIAL_SSE = 1, 2                                # SvtHipTxtDesc::flags
+TXT_SEARCH_INVERSE = 1                                                # flags of svt_hip_txt_search_batch
+TXT_NO_CAND = 0xFF                                                    # SvtHipTxtResult::cand where no candidate reached the comparison
+
+
+class SpatialSrc(C.Structure):         # SvtHipSpatialSrc
+    _fields_ = [("src_off", C.c_uint64), ("src_stride", C.c_uint32), ("crop_w", C.c_uint8), ("crop_h", C.c_uint8), ("pad_", C.c_uint8 * 2)]
+
+
+class TxtDesc(C.Structure):            # SvtHipTxtDesc
+    _fields_ = [("src_off", C.c_uint64), ("dst_qcoeff_off", C.c_uint64), ("dst_dqcoeff_off", C.c_uint64), ("dst_recon_off", C.c_uint64),
+                ("first_cand", C.c_uint32), ("src_stride", C.c_uint32), ("dst_recon_stride", C.c_uint32), ("full_lambda", C.c_uint32),
+                ("early_exit_coeff_th", C.c_uint32), ("early_exit_dist_th", C.c_uint32), ("tx_pixels", C.c_uint32),
+                ("satd_early_exit_th", C.c_uint16), ("txt_rate_cost_th", C.c_uint16), ("group_start", C.c_uint16), ("n_cand", C.c_uint8),
+                ("flags", C.c_uint8), ("crop_w", C.c_uint8), ("crop_h", C.c_uint8), ("pad_", C.c_uint8 * 2)]
+
+
+class TxtResult(C.Structure):          # SvtHipTxtResult
+    _fields_ = [("bits", C.c_uint64), ("distortion", C.c_uint64 * 2), ("cost", C.c_uint64), ("eob", C.c_uint16), ("quant_mask", C.c_uint16),
+                ("cost_mask", C.c_uint16), ("tx_type", C.c_uint8), ("cand", C.c_uint8), ("cul_level", C.c_uint8), ("pad_", C.c_uint8 * 7)]
+
+
+SPATIAL_SRC_DTYPE, TXT_DESC_DTYPE, TXT_RESULT_DTYPE = record_dtype(SpatialSrc), record_dtype(TxtDesc), record_dtype(TxtResult)
+
 
 class CdefList(C.Structure):
     _fields_ = [("by", C.c_uint8), ("bx", C.c_uint8)]

@@ -244,6 +244,80 @@ def rdoq_batch(lib, d_base, d_txfm_desc, descs, tables, d_txfm_result, w, h, str
     return raw[guard:d_out.nbytes - guard].view(np.dtype(abi.RDOQ_RESULT_DTYPE)).copy(), np.concatenate([raw[:guard], raw[d_out.nbytes - guard:]])
 
 
+def _guarded(lib, nbytes, guard, fill, stream):
+    """A device buffer of nbytes between two runs of `guard` bytes, all of it `fill`"""
+    buf = DeviceBuffer(lib, 2 * guard + nbytes)
+    buf.fill(fill, stream)
+    return buf
+
+
+def _unguard(buf, dtype, guard, stream):
+    """(the records between the guards, the guard bytes before and after them: still the fill if untouched)"""
+    raw = buf.download(np.uint8, (buf.nbytes,), stream)
+    return raw[guard:buf.nbytes - guard].view(np.dtype(dtype)).copy(), np.concatenate([raw[:guard], raw[buf.nbytes - guard:]])
+
+
+def spatial_distortion_batch(lib, d_base, d_txfm_desc, srcs, w, h, stream=None, guard=64, fill=0xA5):
+    """svt_hip_txfm_spatial_distortion_batch for candidates of one size w x h (one launch).  d_txfm_desc: device address of the
+    candidates' transform descriptors (pred_off, recon_off, strides, TX_PIXEL16); srcs: a record array of abi.SPATIAL_SRC_DTYPE.
+    Returns (uint64 [n][2] = {residual, prediction}, the guard bytes around them)."""
+    n = len(srcs)
+    d_src = upload_descriptors(lib, srcs, stream)
+    d_out = _guarded(lib, 16 * n, guard, fill, stream)
+    check(lib, lib.svt_hip_txfm_spatial_distortion_batch(C.c_void_p(d_base), C.c_void_p(d_txfm_desc), C.c_void_p(d_src.ptr), C.c_void_p(d_out.ptr + guard),
+                                                         C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), C.c_void_p(stream)),
+          "svt_hip_txfm_spatial_distortion_batch")
+    out, guards = _unguard(d_out, np.uint64, guard, stream)
+    return out.reshape(n, 2), guards
+
+
+def txt_select_batch(lib, d_base, descs, d_txfm_desc, cost_descs, tables, d_txfm_result, d_rdoq_result, d_distortion, d_cost, n_cand, w, h,
+                     stream=None, mapping=None, guard=64, fill=0xA5):
+    """svt_hip_txt_select_batch for blocks of one size w x h over the records of n_cand candidates.  descs: a record array of
+    abi.TXT_DESC_DTYPE; cost_descs: one of abi.TXB_COST_DESC_DTYPE; tables: one of abi.RATE_TABLES_DTYPE; the d_* are device addresses
+    (d_rdoq_result may be None).  With mapping (0 or 1) the same through svt_hip_txt_select_batch_mapped.
+    Returns (results as a record array of abi.TXT_RESULT_DTYPE, the guard bytes around them)."""
+    n = len(descs)
+    tables = np.ascontiguousarray(tables, np.dtype(abi.RATE_TABLES_DTYPE)).reshape(-1)
+    d_desc, d_cdesc, d_tab = upload_descriptors(lib, descs, stream), upload_descriptors(lib, cost_descs, stream), DeviceBuffer(lib, tables.nbytes)
+    d_tab.upload(tables, stream)
+    d_out = _guarded(lib, C.sizeof(abi.TxtResult) * n, guard, fill, stream)
+    args = (C.c_void_p(d_base), C.c_void_p(d_desc.ptr), C.c_void_p(d_txfm_desc), C.c_void_p(d_cdesc.ptr), C.c_void_p(d_tab.ptr), C.c_uint32(len(tables)),
+            C.c_void_p(d_txfm_result), C.c_void_p(d_rdoq_result), C.c_void_p(d_distortion), C.c_void_p(d_cost), C.c_void_p(d_out.ptr + guard),
+            C.c_uint32(n_cand), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h))
+    if mapping is None:
+        rc = lib.svt_hip_txt_select_batch(*args, C.c_void_p(stream))
+    else:
+        rc = lib.svt_hip_txt_select_batch_mapped(*args, C.c_uint32(mapping), C.c_void_p(stream))
+    check(lib, rc, "svt_hip_txt_select_batch")
+    return _unguard(d_out, abi.TXT_RESULT_DTYPE, guard, stream)
+
+
+def txt_search_batch(lib, d_base, txfm_descs, rdoq_descs, cost_descs, tables, descs, w, h, inverse=False, stream=None, guard=64, fill=0xA5):
+    """svt_hip_txt_search_batch: the whole transform-type search of the blocks `descs` (abi.TXT_DESC_DTYPE) of one size w x h over their
+    candidates (txfm_descs: abi.TXFM_DESC_DTYPE, rdoq_descs: abi.RDOQ_DESC_DTYPE or None, cost_descs: abi.TXB_COST_DESC_DTYPE, one record per
+    candidate each), with a scratch of exactly svt_hip_txt_search_scratch_bytes between guards.  inverse: SVT_HIP_TXT_SEARCH_INVERSE; without
+    it no block measures spatial SSE or gets a reconstruction, whatever its descriptor says.
+    Returns (results as a record array of abi.TXT_RESULT_DTYPE, the guard bytes around results and scratch)."""
+    n, n_cand = len(descs), len(txfm_descs)
+    tables = np.ascontiguousarray(tables, np.dtype(abi.RATE_TABLES_DTYPE)).reshape(-1)
+    d_tdesc, d_cdesc, d_desc = upload_descriptors(lib, txfm_descs, stream), upload_descriptors(lib, cost_descs, stream), upload_descriptors(lib, descs, stream)
+    d_rdesc = upload_descriptors(lib, rdoq_descs, stream) if rdoq_descs is not None else None
+    d_tab = DeviceBuffer(lib, tables.nbytes)
+    d_tab.upload(tables, stream)
+    need = lib.svt_hip_txt_search_scratch_bytes(n_cand, n)
+    sguard = 256
+    d_scratch = _guarded(lib, need, sguard, fill, stream)
+    d_out = _guarded(lib, C.sizeof(abi.TxtResult) * n, guard, fill, stream)
+    rc = lib.svt_hip_txt_search_batch(C.c_void_p(d_base), C.c_void_p(d_tdesc.ptr), C.c_void_p(d_rdesc.ptr if d_rdesc else None), C.c_void_p(d_cdesc.ptr),
+                                      C.c_void_p(d_tab.ptr), C.c_uint32(len(tables)), C.c_void_p(d_desc.ptr), C.c_void_p(d_scratch.ptr + sguard),
+                                      C.c_size_t(need), C.c_void_p(d_out.ptr + guard), C.c_uint32(n_cand), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h),
+                                      C.c_uint32(abi.TXT_SEARCH_INVERSE if inverse else 0), C.c_void_p(stream))
+    check(lib, rc, "svt_hip_txt_search_batch")
+    out, guards = _unguard(d_out, abi.TXT_RESULT_DTYPE, guard, stream)
+    return out, np.concatenate([guards, _unguard(d_scratch, np.uint8, sguard, stream)[1]])
+
+
 class DeviceCdefPick:
     """Result record, per-block outputs and workspace of svt_hip_cdef_pick_strengths for a grid of n_fb filter blocks, pre-filled
     with `fill`.  run() only enqueues; download() waits for the stream."""
