@@ -192,6 +192,12 @@ typedef struct SvtHipTxfmResult {
 
 SVT_HIP_API int32_t svt_hip_txfm_quant_batch(uint8_t *d_base, const SvtHipTxfmDesc *d_desc, SvtHipTxfmResult *d_result,
                                              uint32_t n_blocks, uint32_t w, uint32_t h, void *stream);
+/* Test aid.  svt_hip_txfm_quant_batch runs a kernel that holds the common class of blocks only (8/10-bit, forward + inverse,
+ * quantize_b without matrices, amplitudes within the 24-bit arithmetic) and hands the blocks of every wave that meets anything
+ * else to the general kernel, launched behind it.  *out = how many blocks the calling thread's last svt_hip_txfm_quant_batch
+ * handed over (0 when that call used the general kernel alone, or when the thread's scratch has been taken for something else
+ * since); waits for the stream that call ran on, which must still exist. */
+SVT_HIP_API int32_t svt_hip_debug_txfm_fallback_blocks(uint32_t *out);
 
 /* Transform-domain distortion of the same blocks, what svt_aom_full_loop_core reads right after the quantiser
  * (svt_aom_picture_full_distortion32_bits_single, pic_operators.c:150-234): d_distortion[i] = {DIST_CALC_RESIDUAL =

@@ -56,7 +56,9 @@ struct ThreadState {
     int        ring_next = 0;
     Scratch    scratch;            // Tier A staging (TierAStage)
     GuardedBuf wiener_aux;         // raw first moments of svt_hip_wiener_stats
-    GuardedBuf txfm_perm;          // block permutation of the grouped transform launch
+    GuardedBuf txfm_perm;          // transform batch: fallback counters and list, block permutation of the grouped launch (txfm.hip)
+    hipStream_t     txfm_fast_stream = nullptr;  // stream and counters of the last transform batch if it ran lean + fallback
+    const uint32_t *txfm_fast_hdr    = nullptr;  // (svt_hip_debug_txfm_fallback_blocks)
     hipEvent_t produced = nullptr; // svt_hip_publish_reference: producer stream -> side stream
 };
 ThreadState &tls();

@@ -179,7 +179,12 @@ void *TierBCall::stage(const void *host, size_t bytes) {
     const hipError_t e = hipMemcpyAsync(s.dev, s.pinned, bytes, hipMemcpyHostToDevice, st_);
     return e == hipSuccess ? s.dev : fail(e, "hipMemcpyAsync");
 }
-void *TierBCall::take(GuardedBuf &b, size_t bytes, size_t grow_to) { return hold(b, bytes, grow_to, false) ? b.dev : nullptr; }
+void *TierBCall::take(GuardedBuf &b, size_t bytes, size_t grow_to) {
+    ThreadState &t = tls();
+    if (&b == &t.txfm_perm)  // whoever takes it may grow or overwrite it: the last transform batch's counters are gone
+        t.txfm_fast_stream = nullptr, t.txfm_fast_hdr = nullptr;
+    return hold(b, bytes, grow_to, false) ? b.dev : nullptr;
+}
 void TierBCall::release() {
     for (int i = 0; i < n_held_; i++) {
         const hipError_t e = held_[i]->release(st_);

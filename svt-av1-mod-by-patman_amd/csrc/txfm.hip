@@ -23,18 +23,66 @@ using namespace svthip::txb;
 
 namespace {
 
+// A batch of a size with Geo::LEAN runs as two launches on the caller's stream.  txfm_kernel holds the lean form of txfm_block: one
+// class of blocks (8/10-bit, forward + inverse, quantize_b with plain tables: txfm_block.hpp lean_class) in the 24-bit arithmetic,
+// and nothing else, so it needs fewer registers and instructions than the general form.  A wave that meets a block outside the
+// class, or data beyond the limits of that arithmetic, writes nothing and appends the indices of its blocks to a list in the calling
+// thread's scratch (ThreadState::txfm_perm), one atomic per wave.  txfm_general_kernel, the kernel for every path, follows with the
+// list as its index table and the count read from device memory -- no host synchronisation; its workgroups beyond the count leave
+// at once.  Words of the scratch: [FB_COUNT ...][FB_LIST: n indices][n more for the grouping pass].  The count is cleared by a
+// 4-byte memset ahead of the lean kernel.  At a size without Geo::LEAN, txfm_kernel IS the kernel for every path (one launch, as
+// before the split), so that the kernel doing a size's work is always called txfm_kernel<W, H>, the name the profiling tools select by.
+enum : uint32_t { FB_COUNT = 0, FB_LIST = 16 };
+
 template <int W, int H>
-__global__ __launch_bounds__((Geo<W, H>::NT * Geo<W, H>::L), (Geo<W, H>::MINW)) void txfm_kernel(uint8_t *__restrict__ base,
+__global__ __launch_bounds__((Geo<W, H>::NT * Geo<W, H>::L), (Geo<W, H>::LEANW)) void txfm_kernel(uint8_t *__restrict__ base,
                                                                             const SvtHipTxfmDesc *__restrict__ descs,
                                                                             SvtHipTxfmResult *__restrict__ results,
-                                                                            uint32_t n, const uint32_t *__restrict__ perm) {
+                                                                            uint32_t n, const uint32_t *__restrict__ perm,
+                                                                            uint32_t *__restrict__ fb) {
     using G = Geo<W, H>;
     constexpr int L = G::L, PW = G::PW, NT = G::NT;
+    static_assert(NT * L == 64, "one wave per workgroup: a bail-out is uniform over the workgroup");
     __shared__ int32_t buf[NT][H * PW];
     const int          t = threadIdx.x % L, slot = threadIdx.x / L;
     const uint32_t     i    = blockIdx.x * NT + slot;
     const bool         live = i < n;
     const uint32_t     tb   = live ? (perm ? perm[i] : i) : 0;  // perm: blocks grouped by transform type (group_by_type_kernel)
+    if constexpr (!G::LEAN) {
+        txfm_block<W, H>(base, descs[tb], results + tb, live, t, buf[slot]);  // (fb is NULL)
+    } else {
+        if (txfm_block<W, H, false, true>(base, descs[tb], results + tb, live, t, buf[slot]))
+            return;
+        const uint32_t left = n - blockIdx.x * NT, n_live = left < (uint32_t)NT ? left : (uint32_t)NT;  // the live slots are the first ones
+        uint32_t       at   = 0;
+        if (threadIdx.x == 0)
+            at = atomicAdd(&fb[FB_COUNT], n_live);
+        at = (uint32_t)__shfl((int)at, 0, 64);
+        if (live && t == 0)
+            fb[FB_LIST + at + slot] = tb;  // at + slot < n: the counts of all waves sum to at most n
+    }
+}
+
+// The kernel for every path at the sizes with a lean form: block i of n, through perm if given, one workgroup per NT blocks.  With `count` the number of blocks
+// is read from device memory (what the lean kernel listed in perm) and the workgroups beyond it leave at once.
+template <int W, int H>
+__global__ __launch_bounds__((Geo<W, H>::NT * Geo<W, H>::L), (Geo<W, H>::MINW)) void txfm_general_kernel(uint8_t *__restrict__ base,
+                                                                            const SvtHipTxfmDesc *__restrict__ descs,
+                                                                            SvtHipTxfmResult *__restrict__ results,
+                                                                            uint32_t n, const uint32_t *__restrict__ perm,
+                                                                            const uint32_t *__restrict__ count) {
+    using G = Geo<W, H>;
+    constexpr int L = G::L, PW = G::PW, NT = G::NT;
+    __shared__ int32_t buf[NT][H * PW];
+    if (count) {
+        n = *count;
+        if (blockIdx.x * NT >= n)
+            return;
+    }
+    const int          t = threadIdx.x % L, slot = threadIdx.x / L;
+    const uint32_t     i    = blockIdx.x * NT + slot;
+    const bool         live = i < n;
+    const uint32_t     tb   = live ? (perm ? perm[i] : i) : 0;  // perm: blocks grouped by transform type (group_by_type_kernel), or the lean kernel's list
     txfm_block<W, H>(base, descs[tb], results + tb, live, t, buf[slot]);
 }
 
@@ -167,30 +215,54 @@ int32_t svthip::txfm_ready() {
 namespace {
 
 template <int W, int H>
-void launch_txfm(uint8_t *base, const SvtHipTxfmDesc *descs, SvtHipTxfmResult *res, uint32_t n, hipStream_t st) {
+void launch_txfm(uint8_t *base, const SvtHipTxfmDesc *descs, SvtHipTxfmResult *res, uint32_t n, hipStream_t st, bool batch) {
     using G = Geo<W, H>;
     const uint32_t *perm = nullptr;
+    const dim3      grid((n + G::NT - 1) / G::NT), wg(G::NT * G::L);
+    ThreadState    &ts = tls();
+    auto            launch_general = [&](const uint32_t *pm) {  // every path, one launch
+        if constexpr (G::LEAN)
+            hipLaunchKernelGGL((txfm_general_kernel<W, H>), grid, wg, 0, st, base, descs, res, n, pm, (const uint32_t *)nullptr);
+        else
+            hipLaunchKernelGGL((txfm_kernel<W, H>), grid, wg, 0, st, base, descs, res, n, pm, (uint32_t *)nullptr);
+    };
+    ts.txfm_fast_stream = nullptr;  // svt_hip_debug_txfm_fallback_blocks: this call has no fallback list (yet)
     // Measured on the 4K 10-bit workload (DCT / ADST alternating between neighbours): the grouped launch is NOT faster — the
     // mixed-type waves cost 0-3 %, the grouping pass 13-30 us per launch — so it is off unless SVTAV1_HIP_GROUP_TX is set.
     static const bool group = getenv("SVTAV1_HIP_GROUP_TX") != nullptr;
-    if (G::NT > 1 && n >= GROUP_MIN_BLOCKS && group && st) {  // (st == NULL: no pooled stream could be made; such calls go ungrouped)
-        // the per-thread index buffer (exactly n entries when it grows); its previous user may sit on another stream.  Without it
-        // the blocks go ungrouped: the result is the same
-        TierBCall c("transform grouping", (void *)st);
-        perm = (const uint32_t *)c.take(tls().txfm_perm, (size_t)n * sizeof(uint32_t), (size_t)n * sizeof(uint32_t));
-        if (perm)
+    // SVTAV1_HIP_TXFM_FAST=0: every block through the general kernel alone, for A/B runs
+    static const bool fast_on = !(getenv("SVTAV1_HIP_TXFM_FAST") && atoi(getenv("SVTAV1_HIP_TXFM_FAST")) == 0);
+    const bool fast = G::LEAN && fast_on && batch, grouped = G::NT > 1 && n >= GROUP_MIN_BLOCKS && group;
+    if ((fast || grouped) && st) {  // (st == NULL: no pooled stream could be made; such calls go ungrouped through the general kernel)
+        // the per-thread index buffer (exactly what this call needs when it grows); its previous user may sit on another stream.
+        // Without it the blocks go ungrouped through the general kernel: the result is the same
+        TierBCall    c("transform scratch", (void *)st);
+        const size_t bytes = ((size_t)FB_LIST + (size_t)n * (grouped ? 2 : 1)) * sizeof(uint32_t);
+        uint32_t    *fb    = (uint32_t *)c.take(ts.txfm_perm, bytes, bytes);
+        if (fb && grouped) {
+            perm = fb + FB_LIST + n;
             hipLaunchKernelGGL(group_by_type_kernel, dim3((n + GROUP_CHUNK - 1) / GROUP_CHUNK), dim3(1024), 0, st, descs, n, (uint32_t *)perm);
-        hipLaunchKernelGGL((txfm_kernel<W, H>), dim3((n + G::NT - 1) / G::NT), dim3(G::NT * G::L), 0, st, base, descs, res, n, perm);
-        return;  // the scope records the buffer's event behind the transform kernel
+        }
+        if constexpr (G::LEAN) {
+            if (fb && fast && hipMemsetAsync(fb + FB_COUNT, 0, sizeof(uint32_t), st) == hipSuccess) {
+                hipLaunchKernelGGL((txfm_kernel<W, H>), grid, wg, 0, st, base, descs, res, n, perm, fb);
+                hipLaunchKernelGGL((txfm_general_kernel<W, H>), grid, wg, 0, st, base, descs, res, n, fb + FB_LIST, fb + FB_COUNT);
+                ts.txfm_fast_stream = st, ts.txfm_fast_hdr = fb;  // (TierBCall::take forgets them when the buffer is taken again)
+                return;  // the scope records the buffer's event behind the last kernel
+            }
+        }
+        launch_general(perm);
+        return;
     }
-    hipLaunchKernelGGL((txfm_kernel<W, H>), dim3((n + G::NT - 1) / G::NT), dim3(G::NT * G::L), 0, st, base, descs, res, n, perm);
+    launch_general(perm);
 }
 
+// batch: svt_hip_txfm_quant_batch; the Tier A leaves run one block outside the lean class and go to the general kernel directly
 bool dispatch_txfm(uint32_t w, uint32_t h, uint8_t *base, const SvtHipTxfmDesc *descs, SvtHipTxfmResult *res, uint32_t n,
-                   hipStream_t st) {
+                   hipStream_t st, bool batch) {
 #define CASE(W, H)                                \
     if (w == W && h == H) {                       \
-        launch_txfm<W, H>(base, descs, res, n, st); \
+        launch_txfm<W, H>(base, descs, res, n, st, batch); \
         return true;                              \
     }
     CASE(4, 4) CASE(8, 8) CASE(16, 16) CASE(32, 32) CASE(64, 64) CASE(4, 8) CASE(8, 4) CASE(8, 16) CASE(16, 8) CASE(16, 32)
@@ -213,11 +285,25 @@ extern "C" int32_t svt_hip_txfm_quant_batch(uint8_t *d_base, const SvtHipTxfmDes
         return rc;
     if (n_blocks == 0)
         return SVT_HIP_OK;
-    if (!dispatch_txfm(w, h, d_base, d_desc, d_result, n_blocks, resolve_stream(stream))) {
+    if (!dispatch_txfm(w, h, d_base, d_desc, d_result, n_blocks, resolve_stream(stream), true)) {
         set_error("svt_hip_txfm_quant_batch: %ux%u is not an AV1 transform size", w, h);
         return SVT_HIP_ERR_BAD_PARAMETER;
     }
     SVT_HIP_CHECK(hipGetLastError());
+    return SVT_HIP_OK;
+}
+
+extern "C" int32_t svt_hip_debug_txfm_fallback_blocks(uint32_t *out) {
+    if (!out) {
+        set_error("svt_hip_debug_txfm_fallback_blocks: NULL pointer");
+        return SVT_HIP_ERR_BAD_PARAMETER;
+    }
+    *out = 0;
+    ThreadState &ts = tls();
+    if (!ts.txfm_fast_stream)  // the last batch went to the general kernel alone
+        return SVT_HIP_OK;
+    SVT_HIP_CHECK(hipStreamSynchronize(ts.txfm_fast_stream));
+    SVT_HIP_CHECK(hipMemcpy(out, ts.txfm_fast_hdr + FB_COUNT, sizeof(uint32_t), hipMemcpyDeviceToHost));
     return SVT_HIP_OK;
 }
 
@@ -251,7 +337,7 @@ struct OneBlock : TierAStage {
     const SvtHipTxfmResult *result() const { return host<SvtHipTxfmResult>(off_res); }
     void run(int w, int h) {
         upload();
-        if (!dispatch_txfm((uint32_t)w, (uint32_t)h, dev(0), dev<const SvtHipTxfmDesc>(off_desc), dev<SvtHipTxfmResult>(off_res), 1, stream()))
+        if (!dispatch_txfm((uint32_t)w, (uint32_t)h, dev(0), dev<const SvtHipTxfmDesc>(off_desc), dev<SvtHipTxfmResult>(off_res), 1, stream(), false))
             fatal("bad transform size");
     }
 };

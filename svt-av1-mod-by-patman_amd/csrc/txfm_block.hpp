@@ -43,6 +43,11 @@ struct Geo {
     static constexpr int NT = cmax(1, 64 / L);  // one wave per workgroup: its barriers cost nothing and waves never wait for each other
     static constexpr int IW = cmin(W, 32), IH = cmin(H, 32);
     static constexpr int MINW = L == 32 ? 3 : (L == 8 ? 8 : (L == 64 ? SVT_HIP_TX64_WAVES : 1));  // waves per SIMD the register allocation aims for: 3 for the 32-wide kernels (150 VGPRs, no scratch: 2.86 TB/s; at 4 waves / 128 VGPRs they spill 104 B per lane: 2.31 TB/s); 8 for the 8-wide ones (64 VGPRs, 12 B of scratch: +4 %); the 16-wide take what they need (96 VGPRs, 5 waves: capped at 80 they spill 64 B and lose 15 %)
+    // the batch call runs the lean kernel ahead of the general one (txfm.hip) at 16 and 32 lanes per block; measured on the 4K 10-bit
+    // workload the pair is 12 - 15 % faster there and 6 - 12 % slower than the general kernel alone at 8x8 and 64x64, where what
+    // the lean kernel saves is less than the second launch costs
+    static constexpr bool LEAN  = L == 16 || L == 32;
+    static constexpr int  LEANW = LEAN ? 1 : MINW;  // waves per SIMD txfm_kernel is compiled for; the lean form takes what it needs (61 VGPRs = 8 waves at 16x16, 89 = 5 at 32x32, where LDS allows 19 workgroups per CU)
     static constexpr int WI = clog2(W) - 2, HI = clog2(H) - 2;
     static constexpr bool RECT = (W == 2 * H) || (H == 2 * W);
 };
@@ -242,8 +247,24 @@ __device__ __forceinline__ void coop_store_tile(const int32_t *__restrict__ lds,
 // BLKERR (the TPL dispenser's get_quantize_error, src_ops_process.c:225-249; sizes without a 64-point side): result->three_quad_energy
 // = svt_av1_block_error = sum of (coeff - dqcoeff)^2 over the block, taken in the quantiser loop where both values are in registers, so
 // that neither array has to be stored and read back (coeff_off / dqcoeff_off may be SVT_HIP_NO_OFFSET).
-template <int W, int H, bool BLKERR = false>
-__device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const SvtHipTxfmDesc &d, SvtHipTxfmResult *__restrict__ result,
+// LEAN (txfm_kernel, txfm.hip): the function holds the code of ONE class of blocks only -- lean_class() below, with the `Fast`
+// arithmetic and the short quantiser -- and returns false, having written nothing to global memory, when the wave (every lane of
+// it must be in the call: one wave per workgroup) holds a block outside that class or data that fail one of the three tests the
+// general form uses to pick its arithmetic: column and row magnitudes against FWD_FAST_LIMIT, coefficients against 32767.  All of
+// them come before the first global store.  The caller hands such a wave's blocks to the general form, which returns true always.
+template <int W, int H>
+__device__ __forceinline__ bool lean_class(const SvtHipTxfmDesc &d, const uint8_t *base) {
+    using G = Geo<W, H>;
+    const int vk = VTX_D[d.tx_type & 15], hk = HTX_D[d.tx_type & 15];
+    const int bdi = d.bit_depth == 8 ? 0 : (d.bit_depth == 10 ? 1 : -1);  // 12-bit rows need the 64-bit arithmetic at most sizes: none here
+    QP q;  // load_qp reads descriptor fields only (no table is fetched); the quantiser section loads them again, from the cache
+    load_qp(q, d, base);
+    return (d.flags & ~(uint32_t)SVT_HIP_TX_PIXEL16) == (SVT_HIP_TX_FWD | SVT_HIP_TX_INV) && d.shape == 0 && d.coeff_off == SVT_HIP_NO_OFFSET &&
+        (q.mode == SVT_HIP_QUANT_B || q.mode == SVT_HIP_QUANT_B_HBD) && q.simple && bdi >= 0 &&
+        INV_FAST_OK[bdi < 0 ? 0 : bdi][0][G::WI][kind_index(hk)] != 0 && INV_FAST_OK[bdi < 0 ? 0 : bdi][1][G::HI][kind_index(vk)] != 0;
+}
+template <int W, int H, bool BLKERR = false, bool LEAN = false>
+__device__ __forceinline__ bool txfm_block(uint8_t *__restrict__ base, const SvtHipTxfmDesc &d, SvtHipTxfmResult *__restrict__ result,
                                            const bool live, const int t, int32_t *__restrict__ lds) {
     static_assert(!BLKERR || (W != 64 && H != 64), "three_quad_energy is the 64-point energy for those sizes");
     using G = Geo<W, H>;
@@ -252,7 +273,12 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
     const bool ud = vk == 2, lr = hk == 2;
     const int  bd = d.bit_depth;
     const int  bdi = bd == 8 ? 0 : (bd == 10 ? 1 : (bd == 12 ? 2 : -1));  // row of INV_FAST_OK
-    const bool do_fwd = d.flags & SVT_HIP_TX_FWD, do_inv = d.flags & SVT_HIP_TX_INV;
+    const bool do_fwd = LEAN || (d.flags & SVT_HIP_TX_FWD), do_inv = LEAN || (d.flags & SVT_HIP_TX_INV);
+    if constexpr (LEAN) {
+        if (!__all(!live || lean_class<W, H>(d, base)))
+            return false;
+    }
+    bool fast_ok = true;  // LEAN: cleared by a lane whose data need the exact arithmetic
     constexpr int sh0 = FWD_SHIFT[G::WI][G::HI][0], sh1 = FWD_SHIFT[G::WI][G::HI][1], sh2 = FWD_SHIFT[G::WI][G::HI][2];
     int32_t  row[W];
 #pragma unroll
@@ -265,7 +291,7 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
             {   // FLIPADST columns read the rows bottom-up: walk the pointers, the register index stays constant
                 const ptrdiff_t step = ud ? -(ptrdiff_t)d.residual_stride : (ptrdiff_t)d.residual_stride;
                 const ptrdiff_t row0 = (ud ? (ptrdiff_t)(H - 1) * d.residual_stride : 0) + t;
-                if (!(d.flags & SVT_HIP_TX_SRC_PRED)) {
+                if (LEAN || !(d.flags & SVT_HIP_TX_SRC_PRED)) {
                     const int16_t *rp = (const int16_t *)(base + d.residual_off) + row0;
 #pragma unroll
                     for (int r = 0; r < H; r++, rp += step) v[r] = (int32_t)((uint32_t)(int32_t)__builtin_nontemporal_load(rp) << sh0);  // read once
@@ -293,6 +319,8 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
 #pragma unroll
                     for (int r = 0; r < H; r++) v[r] = Fast::rs(v[r], -sh1);
                 }
+            } else if constexpr (LEAN) {
+                fast_ok = false;
             } else {
                 fwd1d<Exact, H>(v, vk, FWD_COS_COL[G::WI][G::HI]);
                 if constexpr (sh1 < 0) {
@@ -303,6 +331,10 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
             const int cc = lr ? W - 1 - t : t;
 #pragma unroll
             for (int r = 0; r < H; r++) lds[r * PW + cc] = v[r];
+        }
+        if constexpr (LEAN) {
+            if (!__all(fast_ok))
+                return false;
         }
         __syncthreads();
         // -------------------------------------------------------------- forward: rows
@@ -315,6 +347,8 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
 #pragma unroll
                     for (int c = 0; c < W; c++) row[c] = Fast::rs(row[c], -sh2);
                 }
+            } else if constexpr (LEAN) {
+                fast_ok = false;
             } else {
                 fwd1d<Exact, W>(row, hk, FWD_COS_ROW[G::WI][G::HI]);
                 if constexpr (sh2 < 0) {
@@ -322,7 +356,7 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
                     for (int c = 0; c < W; c++) row[c] = rshift64(row[c], -sh2);
                 }
             }
-            const int kw = W >> d.shape, kh = H >> d.shape;
+            const int kw = LEAN ? W : W >> d.shape, kh = LEAN ? H : H >> d.shape;
 #pragma unroll
             for (int c = 0; c < W; c++) {
                 int32_t x = row[c];
@@ -331,6 +365,10 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
                 row[c] = (t < kh && c < kw) ? x : 0;
             }
         }
+    }
+    if constexpr (LEAN) {  // row magnitudes, and every coefficient the quantiser takes within the short form's 32767
+        if (!__all(fast_ok && (!live || t >= IH || max_abs<IW>(row) <= 32767u)))
+            return false;
     }
     // ---------------------------------------------------------------------- 64-point energy (svt_handle_transformWxH)
     uint64_t energy = 0;
@@ -345,7 +383,7 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
     }
     // ---------------------------------------------------------------------- transform-domain cost (svt_aom_satd)
     uint32_t satd = 0;
-    if (do_fwd && (d.flags & SVT_HIP_TX_SATD)) {
+    if (!LEAN && do_fwd && (d.flags & SVT_HIP_TX_SATD)) {
         if (live && t < IH) {
 #pragma unroll
             for (int c = 0; c < IW; c++) satd += (uint32_t)(row[c] < 0 ? -row[c] : row[c]);
@@ -357,23 +395,23 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
     // this lane's scan positions are requested before the coefficient stores below (same arena: see the prediction loads)
     uint32_t iscv[(IW + 1) / 2];
     {
-        const bool      qon = live && t < IH && d.quant_mode != SVT_HIP_QUANT_NONE;
+        const bool      qon = live && t < IH && (LEAN || d.quant_mode != SVT_HIP_QUANT_NONE);
         const uint16_t *isp = (const uint16_t *)(base + (qon ? d.iscan_off : 0)) + (qon ? t * IW : 0);
 #pragma unroll
         for (int c = 0; c < IW; c += 2) iscv[c / 2] = qon ? ((uint32_t)isp[c] | ((uint32_t)isp[c + 1] << 16)) : 0u;
     }
-    if (live && do_fwd && d.coeff_off != SVT_HIP_NO_OFFSET && (d.flags & SVT_HIP_TX_FULLCOEFF) && t < H) {
+    if (!LEAN && live && do_fwd && d.coeff_off != SVT_HIP_NO_OFFSET && (d.flags & SVT_HIP_TX_FULLCOEFF) && t < H) {
         int32_t *co = (int32_t *)(base + d.coeff_off) + t * W;
 #pragma unroll
         for (int c = 0; c < W; c++) co[c] = row[c];
     }
     if (live && t < IH) {
-        if (do_fwd && d.coeff_off != SVT_HIP_NO_OFFSET && !(d.flags & SVT_HIP_TX_FULLCOEFF)) {
+        if (!LEAN && do_fwd && d.coeff_off != SVT_HIP_NO_OFFSET && !(d.flags & SVT_HIP_TX_FULLCOEFF)) {
             int32_t *co = (int32_t *)(base + d.coeff_off) + t * IW;
 #pragma unroll
             for (int c = 0; c < IW; c++) co[c] = row[c];
         }
-        if (d.quant_mode != SVT_HIP_QUANT_NONE) {
+        if (LEAN || d.quant_mode != SVT_HIP_QUANT_NONE) {
             QP q;
             load_qp(q, d, base);
             if (!do_fwd) {  // quantise coefficients that already live in memory
@@ -383,8 +421,8 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
             }
             // one decision per wave: every coefficient small and plain tables -> the branch-free short form
             const bool btype = q.mode == SVT_HIP_QUANT_B || q.mode == SVT_HIP_QUANT_B_HBD;
-            const int  path  = (q.simple && max_abs<IW>(row) <= 32767u) ? (btype ? 1 : 2) : 0;
-            const bool all1 = __all(path == 1), all2 = __all(path == 2);
+            const int  path  = LEAN ? 1 : ((q.simple && max_abs<IW>(row) <= 32767u) ? (btype ? 1 : 2) : 0);
+            const bool all1 = LEAN || __all(path == 1), all2 = !LEAN && __all(path == 2);
 #pragma unroll
             for (int c = 0; c < IW; c++) {
                 const uint32_t rc = (uint32_t)(t * IW + c);
@@ -415,7 +453,7 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
     if constexpr (BLKERR)
         energy = group_sum64<L>(energy);
     {   // qcoeff / dqcoeff leave through LDS so that the stores are line-coalesced (all L lanes of the block take part)
-        const bool quant = live && d.quant_mode != SVT_HIP_QUANT_NONE;
+        const bool quant = live && (LEAN || d.quant_mode != SVT_HIP_QUANT_NONE);
         __syncthreads();
         if (quant && d.qcoeff_off != SVT_HIP_NO_OFFSET)
             coop_store_tile<IW, IH, L, PW>(lds, (int32_t *)(base + d.qcoeff_off), t);
@@ -451,7 +489,7 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
         }
         if (any) {  // an all-zero row stays all-zero through every 1-D kernel
             constexpr int ish0 = INV_SHIFT0[G::WI][G::HI];
-            if (__all(bdi >= 0 && INV_FAST_OK[bdi < 0 ? 0 : bdi][0][G::WI][kind_index(hk)] != 0)) {
+            if (LEAN || __all(bdi >= 0 && INV_FAST_OK[bdi < 0 ? 0 : bdi][0][G::WI][kind_index(hk)] != 0)) {
                 inv1d<Fast, W>(row, hk, range_row);
                 if constexpr (ish0 < 0) {
 #pragma unroll
@@ -476,7 +514,7 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
         const int cc = lr ? W - 1 - t : t;
 #pragma unroll
         for (int r = 0; r < H; r++) v[r] = r < IH ? clampv<true>(lds[r * PW + cc], col_clamp) : 0;  // rows >= IH of a 64-point column are zero: the network below folds
-        if (__all(bdi >= 0 && INV_FAST_OK[bdi < 0 ? 0 : bdi][1][G::HI][kind_index(vk)] != 0)) {
+        if (LEAN || __all(bdi >= 0 && INV_FAST_OK[bdi < 0 ? 0 : bdi][1][G::HI][kind_index(vk)] != 0)) {
             inv1d<Fast, H>(v, vk, range_col);
 #pragma unroll
             for (int r = 0; r < H; r++) v[r] = Fast::rs(v[r], 4);
@@ -514,6 +552,7 @@ __device__ __forceinline__ void txfm_block(uint8_t *__restrict__ base, const Svt
             for (int r = 0; r < H; r++, rc += rs) *rc = (uint8_t)clip.add((uint16_t)(predv[r / 2] >> (16 * (r & 1))), v[r]);
         }
     }
+    return true;
 }
 
 }  // namespace txb
