@@ -1,7 +1,7 @@
 /*
  * svt_hip_inter.h — C-ABI for inter prediction: interpolation (the single-reference and the
  * compound ("jnt") families), the masked-compound and OBMC blends, the compound mask search, warped prediction (local warp
- * and global motion) and the global-motion error / refinement.
+ * and global motion), the global-motion error / refinement and the sub-pel motion search of mode decision.
  *
  * Reference interfaces replaced (paths relative to /root/reference):
  *   Source/Lib/Codec/common_dsp_rtcd.h:185-221   svt_av1_convolve_{2d_sr,x_sr,y_sr,2d_copy_sr},
@@ -19,6 +19,7 @@
  *   Source/Lib/Codec/warped_motion.c:357-363, 1045-1068   is_affine_shear_allowed, svt_get_shear_params
  *   Source/Lib/Codec/enc_warped_motion.c:22-98   svt_av1_warp_error
  *   Source/Lib/Codec/global_motion.c:86-251      add_param_offset, force_wmtype, svt_av1_refine_integerized_param
+ *   Source/Lib/Codec/mcomp.c:609-775             svt_av1_find_best_sub_pixel_tree(_pruned) as md_subpel_search calls them
  * The warp entry points are Tier B only: the RTCD pointers svt_av1_warp_affine / svt_av1_highbd_warp_affine have no leaf.
  * Scaled references are not covered; the corner matching / RANSAC front end of global motion and svt_find_projection stay on
  * the host.  OBMC's neighbour predictions and the rate model of the mask search (model_rd_with_curvfit) stay on the host.
@@ -29,6 +30,7 @@
 #define SVT_HIP_INTER_H
 
 #include "svt_hip_lf.h" /* SvtHipConvolveParams */
+#include "svt_hip_me.h" /* SvtHipMv */
 
 #ifdef __cplusplus
 extern "C" {
@@ -281,6 +283,92 @@ SVT_HIP_API int32_t svt_hip_warp_error_batch(const SvtHipWarpErrorJob *job, cons
  * 3 AFFINE.  job->workspace serves one candidate.  Synchronous. */
 SVT_HIP_API int32_t svt_hip_gm_refine(const SvtHipWarpErrorJob *job, int32_t wmmat[8], int32_t *wmtype, int32_t n_refinements,
                                       int64_t best_frame_error, int64_t *error, void *stream);
+
+/* ---- Sub-pel motion search of mode decision (Tier B) ---------------------------------------------------------------------
+ * One descriptor = one luma block of one (list, reference): md_subpel_search (product_coding_loop.c:2502-2614) behind its
+ * set-up, i.e. svt_av1_find_best_sub_pixel_tree or svt_av1_find_best_sub_pixel_tree_pruned (mcomp.c:609-775) with everything
+ * they call: svt_upsampled_setup_center_error, the exits, svt_first_level_check / svt_second_level_check_v2 over
+ * svt_aom_upsampled_pred_c (variance.c:204-254) + vf, two_level_checks_fast over the bilinear svf (variance.c:28-68, 308-318),
+ * svt_mv_err_cost_ with all six MV_COST_TYPEs, and the reference's integer types (unsigned cost * weight wraps mod 2^32).
+ * 8-bit only, as the reference (hbd_md = 0 there).  Not covered: the compound / masked / OBMC variants the reference leaves
+ * commented out, scaled references, and the encoder hook.
+ *
+ * What is read: of src the w x h block; of ref the (w + 8) x (h + 8) window that starts 4 samples above and 4 to the left of the
+ * sample start_mv points at, whatever the filter and the controls (with two iterations per step a candidate lies up to 14/8 pel
+ * from start_mv, and the filter tables reach 2 samples before and 3 after): the caller's picture border must cover it. */
+#define SVT_HIP_SUBPEL_TREE 0        /* SUBPEL_SEARCH_METHODS, definitions.h:743-748 */
+#define SVT_HIP_SUBPEL_TREE_PRUNED 1
+#define SVT_HIP_SUBPEL_USE_2_TAPS 1  /* SUBPEL_SEARCH_TYPE, definitions.h:736-741 */
+#define SVT_HIP_SUBPEL_USE_4_TAPS 2
+#define SVT_HIP_SUBPEL_USE_8_TAPS 3
+/* SvtHipSubpelResult.exit: where the function returned */
+#define SVT_HIP_SUBPEL_EXIT_NONE 0      /* bad descriptor */
+#define SVT_HIP_SUBPEL_EXIT_EARLY 1     /* the early_exit flag */
+#define SVT_HIP_SUBPEL_EXIT_VARIANCE 2  /* variance of the full-pel prediction below pred_variance_th */
+#define SVT_HIP_SUBPEL_EXIT_ABS_TH 3    /* centre error below th_normalizer */
+#define SVT_HIP_SUBPEL_EXIT_NO_ROUND 4  /* round == 0 */
+#define SVT_HIP_SUBPEL_EXIT_ROUND_DEV 5 /* _pruned: deviation >= round_dev_th after a round */
+#define SVT_HIP_SUBPEL_EXIT_END 6       /* every round ran */
+/* SvtHipSubpelResult.status */
+#define SVT_HIP_SUBPEL_OK 0
+#define SVT_HIP_SUBPEL_BAD_SIZE 1     /* w x h is none of the 22 block sizes */
+#define SVT_HIP_SUBPEL_BAD_POINTER 2  /* src or ref NULL */
+#define SVT_HIP_SUBPEL_BAD_START_MV 3 /* start_mv not full-pel, or not inside MV_LOW .. MV_UPP */
+#define SVT_HIP_SUBPEL_BAD_METHOD 4
+#define SVT_HIP_SUBPEL_BAD_FILTER 5   /* subpel_search_type (checked under both methods) */
+#define SVT_HIP_SUBPEL_BAD_COST 6     /* mv_cost_type out of range, or MV_COST_ENTROPY without the job's tables */
+
+typedef struct SvtHipSubpelJob { /* host memory; the pointers in it are device memory.  What a picture's blocks share */
+    int32_t        mvjcost[4];
+    const int32_t *mvcost[2];    /* centres of the row / column tables, index MV_LOW .. MV_UPP (-(1 << 14) .. 1 << 14), as
+                                  * SvtHipMvCostParam.mvcost; NULL: no descriptor uses MV_COST_ENTROPY */
+} SvtHipSubpelJob;
+
+typedef struct SvtHipSubpelDesc {
+    const uint8_t *src, *ref;    /* the block's co-located first sample in the source and in the reference picture
+                                  * (ms_buffers->src->buf / ref->buf); no alignment is required */
+    uint32_t src_stride, ref_stride;
+    uint16_t w, h;               /* one of the 22 sizes of init_fn_ptr (av1me.c:31-170) */
+    SvtHipMv start_mv;           /* full-pel, in 1/8 units */
+    SvtHipMv ref_mv;             /* the vector the cost is taken against */
+    SvtHipMv best_mvp;           /* mvp_array[list][ref][best_fp_mvp_idx] (mvp_th rule) */
+    int32_t  col_min, col_max, row_min, row_max; /* SubpelMvLimits (svt_hip_subpel_mv_limits) */
+    int32_t  iters_per_step;
+    int32_t  pred_variance_th, round_dev_th;
+    int32_t  error_per_bit, early_exit_th;
+    int32_t  hp_mv_th;
+    uint32_t best_mvp_dist;      /* best_fp_mvp_dist[list][ref] */
+    uint8_t  method;             /* SVT_HIP_SUBPEL_TREE / _PRUNED */
+    uint8_t  subpel_search_type; /* SVT_HIP_SUBPEL_USE_*; _PRUNED always filters bilinearly */
+    uint8_t  forced_stop;        /* SUBPEL_FORCE_STOP: 0 EIGHTH_PEL .. 3 FULL_PEL */
+    uint8_t  allow_hp, bias_fp;
+    uint8_t  skip_diag_refinement; /* 0 .. 4 */
+    uint8_t  abs_th_mult, qp;
+    uint8_t  mv_cost_type;       /* MV_COST_TYPE, see SvtHipMvCostParam */
+    uint8_t  early_exit;         /* the flag of product_coding_loop.c:2595-2597 */
+    uint8_t  mvp_th;             /* _TREE with SPEL_ME in PD_PASS_1: md_subpel_me_ctrls.mvp_th; 0: the rule is off */
+    uint8_t  pad_;
+} SvtHipSubpelDesc;
+
+typedef struct SvtHipSubpelResult {
+    SvtHipMv best_mv;
+    int32_t  besterr;     /* the function's return value */
+    int32_t  distortion;
+    uint32_t sse;         /* *sse1; 0 when no candidate won (the centre does not write it) */
+    uint32_t fullpel_err; /* the centre's error, what the reference stores in ctx->fp_me_dist */
+    uint8_t  exit;        /* SVT_HIP_SUBPEL_EXIT_* */
+    uint8_t  status;      /* SVT_HIP_SUBPEL_*; non-zero: every other field is 0 */
+    uint8_t  pad_[2];
+} SvtHipSubpelResult;
+/* d_result[i] belongs to d_desc[i].  SVT_HIP_ERR_BAD_PARAMETER for a NULL job, d_desc or d_result; n == 0 is SVT_HIP_OK and launches
+ * nothing.  Asynchronous on `stream`. */
+SVT_HIP_API int32_t svt_hip_subpel_search_batch(const SvtHipSubpelJob *job, const SvtHipSubpelDesc *d_desc, SvtHipSubpelResult *d_result,
+                                                uint32_t n, void *stream);
+/* product_coding_loop.c:2527-2537: the MvLimits of a block at (mi_row, mi_col) of mi_width x mi_height mode-info units in a picture
+ * of mi_rows x mi_cols, then svt_av1_set_mv_search_range and svt_av1_set_subpel_mv_search_range around ref_mv.
+ * limits: col_min, col_max, row_min, row_max.  Host only, no device.  SVT_HIP_ERR_BAD_PARAMETER for a NULL pointer. */
+SVT_HIP_API int32_t svt_hip_subpel_mv_limits(int32_t mi_row, int32_t mi_col, int32_t mi_width, int32_t mi_height, int32_t mi_rows,
+                                             int32_t mi_cols, const SvtHipMv *ref_mv, int32_t limits[4]);
 
 #ifdef __cplusplus
 }

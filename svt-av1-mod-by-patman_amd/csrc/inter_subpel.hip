@@ -1,0 +1,385 @@
+// inter_subpel.hip — the sub-pel motion search of mode decision on gfx950: svt_av1_find_best_sub_pixel_tree and
+// svt_av1_find_best_sub_pixel_tree_pruned (mcomp.c:609-775) as md_subpel_search (product_coding_loop.c:2502-2614) calls them,
+// bit-exact, one descriptor per luma block of one (list, reference).
+//
+// One workgroup per descriptor.  Two instantiations of one kernel share a call: a single wave takes the blocks of up to 256
+// samples (and every bad descriptor), four waves take the larger ones; each walks all descriptors and skips the other's.  With
+// two iterations per step a round of step s moves the centre by up to 2 s per component, so a candidate lies up to
+// 2 (4 + 2 + 1) = 14 eighths from start_mv: full-pel offsets -2 .. +1, and with the taps 1 .. 6 that the filter tables use the
+// (w + 8) x (h + 8) reference window from 4 above and 4 left of start_mv holds every sample any candidate reads.  It is staged in
+// LDS once.  A candidate is two separable passes over it with a uint8 intermediate in LDS, clipped between the passes as
+// svt_aom_convolve8_horiz_c / svt_aom_convolve8_vert_c leave it; a direction without a sub-pel offset filters with the identity kernel, which is exact, so
+// the four cases of svt_aom_upsampled_pred_c are one path.  The bilinear svf of the pruned search is the same path with the
+// bilinear table (its uint16 intermediate never exceeds 255, so the clip changes nothing).  The variance sums cross the lanes
+// by shuffles and the waves through LDS; the search itself is replayed by every lane on those uniform values.
+#include "../../include/svt_hip_inter.h"
+#include "blend_device.hpp"
+#include "common.hpp"
+
+#include <algorithm>
+
+using namespace svthip;
+using svthip::blend::wave_sum;
+
+namespace {
+
+constexpr int SUBPEL_MV_LOW = -(1 << 14), SUBPEL_MV_UPP = 1 << 14;  // MV_LOW, MV_UPP (cabac_context_model.h:523-525)
+constexpr int SUBPEL_MAX_FULL_PEL_VAL = (1 << 10) - 1;             // av1me.h:24-27
+constexpr int SUBPEL_SMALL_AREA = 256;                             // the single-wave kernel takes blocks up to this many samples
+
+// av1_bilinear_filters, av1_sub_pel_filters_4 and av1_sub_pel_filters_8 (variance.c:73-140): av1_get_filter(USE_2_TAPS ..
+// USE_8_TAPS), row = subpel_q3 << 1.  Only the even rows are ever addressed.
+__constant__ int16_t SUBPEL_FILTERS[3][8][8] = {
+    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 0, 0, 112, 16, 0, 0, 0}, {0, 0, 0, 96, 32, 0, 0, 0}, {0, 0, 0, 80, 48, 0, 0, 0},
+     {0, 0, 0, 64, 64, 0, 0, 0}, {0, 0, 0, 48, 80, 0, 0, 0}, {0, 0, 0, 32, 96, 0, 0, 0}, {0, 0, 0, 16, 112, 0, 0, 0}},
+    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 0, -8, 122, 18, -4, 0, 0}, {0, 0, -12, 110, 38, -8, 0, 0}, {0, 0, -14, 94, 58, -10, 0, 0},
+     {0, 0, -12, 76, 76, -12, 0, 0}, {0, 0, -10, 58, 94, -14, 0, 0}, {0, 0, -8, 38, 110, -12, 0, 0}, {0, 0, -4, 18, 122, -8, 0, 0}},
+    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 2, -10, 122, 18, -4, 0, 0}, {0, 2, -14, 110, 38, -10, 2, 0}, {0, 2, -16, 94, 58, -12, 2, 0},
+     {0, 2, -14, 76, 76, -14, 2, 0}, {0, 2, -12, 58, 94, -16, 2, 0}, {0, 2, -10, 38, 110, -14, 2, 0}, {0, 0, -4, 18, 122, -10, 2, 0}}};
+// first tap that is not zero and one past the last, per table, for a direction with a sub-pel offset
+__constant__ int8_t SUBPEL_TAP_RANGE[3][2] = {{3, 5}, {2, 6}, {1, 7}};
+
+__device__ __forceinline__ int clip_pixel(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+
+__device__ __forceinline__ int log2_pow2(int v) { return 31 - __clz(v); }
+
+__device__ int subpel_status(const SvtHipSubpelDesc &d, const SvtHipSubpelJob &job) {
+    const int  w = d.w, h = d.h;
+    const bool pow2 = w >= 4 && w <= 128 && h >= 4 && h <= 128 && !(w & (w - 1)) && !(h & (h - 1));
+    if (!pow2 || w > 4 * h || h > 4 * w)  // the 22 sizes: both sides a power of two in 4 .. 128, aspect at most 4 : 1
+        return SVT_HIP_SUBPEL_BAD_SIZE;
+    if (!d.src || !d.ref)
+        return SVT_HIP_SUBPEL_BAD_POINTER;
+    if ((d.start_mv.row & 7) || (d.start_mv.col & 7) || abs((int)d.start_mv.row) >= SUBPEL_MV_UPP || abs((int)d.start_mv.col) >= SUBPEL_MV_UPP)
+        return SVT_HIP_SUBPEL_BAD_START_MV;  // (inside MV_LOW .. MV_UPP no candidate leaves int16, so none leaves the window)
+    if (d.method > SVT_HIP_SUBPEL_TREE_PRUNED)
+        return SVT_HIP_SUBPEL_BAD_METHOD;
+    if (d.subpel_search_type < SVT_HIP_SUBPEL_USE_2_TAPS || d.subpel_search_type > SVT_HIP_SUBPEL_USE_8_TAPS)
+        return SVT_HIP_SUBPEL_BAD_FILTER;
+    if (d.mv_cost_type > 5 || (d.mv_cost_type == 0 && (!job.mvcost[0] || !job.mvcost[1])))
+        return SVT_HIP_SUBPEL_BAD_COST;
+    return SVT_HIP_SUBPEL_OK;
+}
+
+// svt_mv_err_cost (mcomp.c:44-68)
+__device__ int mv_err_cost(SvtHipMv mv, const SvtHipSubpelDesc &d, const SvtHipSubpelJob &job) {
+    const int16_t dr = (int16_t)(mv.row - d.ref_mv.row), dc = (int16_t)(mv.col - d.ref_mv.col);  // MV fields: int16
+    const int     l1 = (int16_t)abs((int)dr) + (int16_t)abs((int)dc);
+    switch (d.mv_cost_type) {
+    case 0: {  // MV_COST_ENTROPY: svt_mv_cost (mcomp.h:136-139)
+        const int joint = dr == 0 ? (dc == 0 ? 0 : 1) : (dc == 0 ? 2 : 3);
+        const int rate = job.mvjcost[joint] + job.mvcost[0][min(max((int)dr, SUBPEL_MV_LOW), SUBPEL_MV_UPP)] +
+            job.mvcost[1][min(max((int)dc, SUBPEL_MV_LOW), SUBPEL_MV_UPP)];
+        return (int)(((int64_t)rate * d.error_per_bit + (1 << 13)) >> 14);  // RDDIV_BITS + AV1_PROB_COST_SHIFT - RD_EPB_SHIFT + 4
+    }
+    case 1: return (2 * l1) >> 3;  // SSE_LAMBDA_LOWRES
+    case 2: return 0;              // SSE_LAMBDA_MIDRES is 0
+    case 3: return l1 >> 3;        // SSE_LAMBDA_HDRES
+    case 4: return (int)(((int64_t)(l1 << 8) * d.error_per_bit + (1 << 13)) >> 14);  // MV_COST_OPT
+    default: return 0;             // MV_COST_NONE
+    }
+}
+
+struct Block {          // what a candidate's error is computed from
+    const uint8_t *win; // LDS: the reference window, row 0 / column 0 = 4 above / left of the sample start_mv points at
+    uint8_t       *tmp; // LDS: the intermediate of the first pass, rows 1 .. h + 5 of [h + 7][w]
+    int32_t       *red; // LDS: per-wave partial sums
+    const uint8_t *src; // global
+    int            src_stride, w, h, lw, win_stride, log2_area;
+    int            base_row, base_col;  // start_mv >> 3
+    int            table;               // row of SUBPEL_FILTERS
+};
+
+struct Error {
+    uint32_t var, sse;
+};
+
+// vf(prediction at mv, src): the variance and the sum of squares.  against_128: vf(.., svt_aom_eb_av1_var_offs, 0, ..) instead.  Inlined
+// at each of the search's twenty-odd calls: as a function it costs a call frame in scratch and thirty more VGPRs.
+template <int NT> __device__ __forceinline__ Error candidate_error(const Block b, SvtHipMv mv, bool against_128) {
+    const int tid = threadIdx.x, w = b.w, h = b.h, lw = b.lw, ws = b.win_stride;
+    const int oy = (mv.row >> 3) - b.base_row + 1, ox = (mv.col >> 3) - b.base_col + 1;  // window row / column of tap 0 of sample (0, 0), less 3
+    const int sy = mv.row & 7, sx = mv.col & 7;
+    const int16_t *fx = SUBPEL_FILTERS[b.table][sx], *fy = SUBPEL_FILTERS[b.table][sy];
+    const int kx0 = sx ? SUBPEL_TAP_RANGE[b.table][0] : 3, kx1 = sx ? SUBPEL_TAP_RANGE[b.table][1] : 4;
+    const int ky0 = sy ? SUBPEL_TAP_RANGE[b.table][0] : 3, ky1 = sy ? SUBPEL_TAP_RANGE[b.table][1] : 4;
+    __syncthreads();  // the previous candidate's second pass has read tmp, its sums have been read from red
+    // horizontal pass over the rows the vertical taps reach: tmp row t is reference row t - 3 of the block
+    const int t0 = ky0, rows = h - 1 + ky1 - ky0;
+    for (int i = tid; i < (rows << lw); i += NT) {
+        const int      t = t0 + (i >> lw), c = i & (w - 1);
+        const uint8_t *p = b.win + (t + oy) * ws + c + ox;
+        int            s = 64;
+        for (int k = kx0; k < kx1; k++) s += fx[k] * p[k];
+        b.tmp[(t << lw) + c] = (uint8_t)clip_pixel(s >> 7);
+    }
+    __syncthreads();
+    int      sum = 0;
+    uint32_t sse = 0;
+    for (int i = tid; i < (h << lw); i += NT) {
+        const int      r = i >> lw, c = i & (w - 1);
+        const uint8_t *p = b.tmp + (r << lw) + c;
+        int            s = 64;
+        for (int k = ky0; k < ky1; k++) s += fy[k] * p[k << lw];
+        const int diff = clip_pixel(s >> 7) - (against_128 ? 128 : (int)b.src[r * b.src_stride + c]);
+        sum += diff, sse += (uint32_t)(diff * diff);
+    }
+    sum = (int)wave_sum((uint32_t)sum), sse = wave_sum(sse);
+    if (NT > 64) {
+        if ((tid & 63) == 0)
+            b.red[2 * (tid >> 6)] = sum, b.red[2 * (tid >> 6) + 1] = (int32_t)sse;
+        __syncthreads();
+        sum = 0, sse = 0;
+#pragma unroll
+        for (int v = 0; v < NT / 64; v++) sum += b.red[2 * v], sse += (uint32_t)b.red[2 * v + 1];
+    }
+    return {sse - (uint32_t)(((int64_t)sum * sum) >> b.log2_area), sse};
+}
+
+struct Search {  // the running best of one search and what the checks need
+    const SvtHipSubpelDesc &d;
+    const SvtHipSubpelJob  &job;
+    const Block            &b;
+    SvtHipMv                best_mv;
+    uint32_t                besterr, sse1;
+    int                     distortion;
+
+    __device__ bool in_range(SvtHipMv mv) const {
+        return mv.col >= d.col_min && mv.col <= d.col_max && mv.row >= d.row_min && mv.row <= d.row_max;
+    }
+    __device__ static SvtHipMv mv_of(int row, int col) {
+        SvtHipMv mv;
+        mv.row = (int16_t)row, mv.col = (int16_t)col;
+        return mv;
+    }
+    // the comparison both checks end in; returns whether mv won
+    __device__ bool take_if_better(SvtHipMv mv, uint32_t cost, int thismse, uint32_t sse) {
+        const uint32_t weight = d.bias_fp && best_mv.col % 8 == 0 && best_mv.row % 8 == 0 ? 110 : 100;  // BIAS_FP_WEIGHT
+        if ((cost * weight) / 100 >= besterr)                                                              // wraps mod 2^32
+            return false;
+        besterr = cost, best_mv = mv, distortion = thismse, sse1 = sse;
+        return true;
+    }
+    // svt_check_better (mcomp.c:226-253)
+    template <int NT> __device__ uint32_t check(SvtHipMv mv, bool *better = nullptr) {
+        if (!in_range(mv))
+            return 0x7FFFFFFFu;
+        const Error    e = candidate_error<NT>(b, mv, false);
+        const int      thismse = (int)e.var;
+        const uint32_t cost = (uint32_t)mv_err_cost(mv, d, job) + (uint32_t)thismse;
+        if (take_if_better(mv, cost, thismse, e.sse) && better)
+            *better = true;
+        return cost;
+    }
+    // svt_check_better_fast (mcomp.c:184-222)
+    template <int NT> __device__ uint32_t check_fast(SvtHipMv mv) {
+        if (!in_range(mv))
+            return 0x7FFFFFFFu;
+        uint32_t cost = (uint32_t)mv_err_cost(mv, d, job);
+        if (d.mv_cost_type == 4) {  // MV_COST_OPT
+            const int64_t bestcost = (int64_t)((uint32_t)distortion + cost);
+            if (bestcost > ((int64_t)besterr * (int64_t)d.early_exit_th) / 1000)
+                return (uint32_t)bestcost;
+        }
+        const Error e = candidate_error<NT>(b, mv, false);
+        const int   thismse = (int)e.var;
+        cost += (uint32_t)thismse;
+        take_if_better(mv, cost, thismse, e.sse);
+        return cost;
+    }
+};
+
+// svt_av1_find_best_sub_pixel_tree behind the centre and the exits (mcomp.c:749-772)
+template <int NT> __device__ void tree_rounds(Search &s, int round, int iters_per_step) {
+    int hstep = 4;
+    for (int iter = 0; iter < round; iter++, hstep >>= 1) {
+        const SvtHipMv c = s.best_mv;
+        // svt_first_level_check
+        const uint32_t left = s.check<NT>(Search::mv_of(c.row, c.col - hstep)), right = s.check<NT>(Search::mv_of(c.row, c.col + hstep));
+        const uint32_t up = s.check<NT>(Search::mv_of(c.row - hstep, c.col)), down = s.check<NT>(Search::mv_of(c.row + hstep, c.col));
+        int            step_row = up <= down ? -hstep : hstep, step_col = left <= right ? -hstep : hstep;
+        s.check<NT>(Search::mv_of(c.row + step_row, c.col + step_col));
+        if ((c.row == s.best_mv.row && c.col == s.best_mv.col) || iters_per_step <= 1)
+            continue;
+        // svt_second_level_check_v2
+        if (c.row == s.best_mv.row)
+            step_row = -step_row;
+        else if (c.col == s.best_mv.col)
+            step_col = -step_col;
+        const SvtHipMv m = s.best_mv;
+        bool           better = false;
+        s.check<NT>(Search::mv_of(m.row + step_row, m.col), &better);
+        s.check<NT>(Search::mv_of(m.row, m.col + step_col), &better);
+        if (better)
+            s.check<NT>(Search::mv_of(m.row + step_row, m.col + step_col));
+    }
+}
+
+// two_level_checks_fast (mcomp.c:378-607)
+template <int NT> __device__ void two_level_checks_fast(Search &s, SvtHipMv t, int hstep, uint32_t orgerr, int iters) {
+    const uint32_t left = s.check_fast<NT>(Search::mv_of(t.row, t.col - hstep)), right = s.check_fast<NT>(Search::mv_of(t.row, t.col + hstep));
+    const uint32_t up = s.check_fast<NT>(Search::mv_of(t.row - hstep, t.col)), down = s.check_fast<NT>(Search::mv_of(t.row + hstep, t.col));
+    const int      step_row = up <= down ? -hstep : hstep, step_col = left <= right ? -hstep : hstep;
+    if (s.besterr >= orgerr)
+        return;
+    s.check_fast<NT>(Search::mv_of(t.row + step_row, t.col + step_col));
+    if (s.besterr >= orgerr || iters <= 1)
+        return;
+    // second_level_check_fast
+    const int br = s.best_mv.row, bc = s.best_mv.col;
+    if (t.row != br && t.col != bc) {
+        s.check_fast<NT>(Search::mv_of(br, bc + step_col));
+        s.check_fast<NT>(Search::mv_of(br + step_row, bc));
+    } else if (t.row == br && t.col != bc) {
+        s.check_fast<NT>(Search::mv_of(br + hstep, bc + step_col));
+        s.check_fast<NT>(Search::mv_of(br - hstep, bc + step_col));
+        s.check_fast<NT>(Search::mv_of(br - step_row, bc));
+    } else if (t.row != br && t.col == bc) {
+        s.check_fast<NT>(Search::mv_of(br + step_row, bc + hstep));
+        s.check_fast<NT>(Search::mv_of(br + step_row, bc - hstep));
+        s.check_fast<NT>(Search::mv_of(br, bc - step_col));
+    }
+}
+
+template <int NT> __device__ int search_block(Search &s) {
+    const SvtHipSubpelDesc &d = s.d;
+    const Block            &b = s.b;
+    const bool              pruned = d.method == SVT_HIP_SUBPEL_TREE_PRUNED;
+    int                     round = min(3 - (int)d.forced_stop, 3 - !d.allow_hp);
+    if (!pruned && d.mvp_th > 0) {  // mcomp.c:715-729; int arithmetic that wraps where the reference's would overflow
+        const int mvp_err = (int)(d.best_mvp_dist + 1u), me_err = (int)(s.besterr + 1u);
+        const int deviation = me_err ? (int)((uint32_t)(me_err - mvp_err) * 100u) / me_err : 0;
+        if (deviation >= d.mvp_th)
+            round = 1;
+        else if (abs(s.best_mv.col - d.best_mvp.col) > d.hp_mv_th || abs(s.best_mv.row - d.best_mvp.row) > d.hp_mv_th)
+            round = min(round, 2);
+    }
+    if (d.early_exit)
+        return SVT_HIP_SUBPEL_EXIT_EARLY;
+    const uint64_t th_normalizer = (uint64_t)(int64_t)(((b.w * b.h) >> (pruned ? 3 : 2)) * (int)d.abs_th_mult * (d.qp >> 1));
+    if (pruned) {
+        if (s.besterr < th_normalizer)
+            return SVT_HIP_SUBPEL_EXIT_ABS_TH;
+        if (!round)
+            return SVT_HIP_SUBPEL_EXIT_NO_ROUND;
+    }
+    const uint32_t var = candidate_error<NT>(b, s.best_mv, true).var;
+    const int      block_var = (int)((var + ((1u << b.log2_area) >> 1)) >> b.log2_area);
+    if (block_var < d.pred_variance_th)
+        return SVT_HIP_SUBPEL_EXIT_VARIANCE;
+    if (!pruned) {
+        if (s.besterr < th_normalizer)
+            return SVT_HIP_SUBPEL_EXIT_ABS_TH;
+        if (!round)
+            return SVT_HIP_SUBPEL_EXIT_NO_ROUND;
+        tree_rounds<NT>(s, round, d.iters_per_step);
+        return SVT_HIP_SUBPEL_EXIT_END;
+    }
+    uint32_t org_error = 0;
+    if (d.skip_diag_refinement < 4) {
+        const uint32_t demo = d.skip_diag_refinement >= 2 && (b.w >= 64 || b.h >= 64) ? 2 : 1;
+        org_error = d.skip_diag_refinement ? s.besterr / demo : 0x7FFFFFFFu;
+    }
+    SvtHipMv start = s.best_mv;
+    int      hstep = 4;
+    for (int iter = 0; iter < round; iter++) {
+        const uint32_t prev = s.besterr;
+        two_level_checks_fast<NT>(s, start, hstep, org_error, d.iters_per_step);
+        hstep >>= 1, start = s.best_mv;
+        if (d.skip_diag_refinement && iter < 1)  // QUARTER_PEL
+            org_error = min(org_error, s.besterr);
+        const int64_t p = max(prev, 1u);
+        if ((int32_t)((((int64_t)max(s.besterr, 1u) - p) * 100) / p) >= d.round_dev_th)
+            return SVT_HIP_SUBPEL_EXIT_ROUND_DEV;
+    }
+    return SVT_HIP_SUBPEL_EXIT_END;
+}
+
+template <int NT, int WIN_BYTES, int TMP_BYTES, bool LARGE>
+__global__ __launch_bounds__(NT) void subpel_kernel(const SvtHipSubpelJob job, const SvtHipSubpelDesc *__restrict__ d_desc,
+                                                    SvtHipSubpelResult *__restrict__ d_result, uint32_t n) {
+    __shared__ uint8_t win[WIN_BYTES];
+    __shared__ uint8_t tmp[TMP_BYTES];
+    __shared__ int32_t red[2 * (NT / 64)];
+    const int          tid = threadIdx.x;
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const SvtHipSubpelDesc d = d_desc[i];
+        const int              status = subpel_status(d, job);
+        const bool             large = status != SVT_HIP_SUBPEL_BAD_SIZE && (int)d.w * d.h > SUBPEL_SMALL_AREA;
+        if (large != LARGE)
+            continue;
+        SvtHipSubpelResult r = {};
+        r.status = (uint8_t)status;
+        if (status != SVT_HIP_SUBPEL_OK) {
+            if (tid == 0)
+                d_result[i] = r;
+            continue;
+        }
+        Block b;
+        b.win = win, b.tmp = tmp, b.red = red, b.src = d.src, b.src_stride = (int)d.src_stride, b.w = d.w, b.h = d.h;
+        b.lw = log2_pow2(d.w), b.win_stride = d.w + 8, b.log2_area = b.lw + log2_pow2(d.h);
+        b.base_row = d.start_mv.row >> 3, b.base_col = d.start_mv.col >> 3;
+        b.table = d.method == SVT_HIP_SUBPEL_TREE_PRUNED ? 0 : d.subpel_search_type - SVT_HIP_SUBPEL_USE_2_TAPS;
+        __syncthreads();  // the previous block's last candidate has read win
+        const uint8_t *ref = d.ref + ((int64_t)b.base_row - 4) * (int64_t)d.ref_stride + (b.base_col - 4);
+        for (int k = tid; k < (d.w + 8) * (d.h + 8); k += NT) {
+            const int y = k / b.win_stride, x = k - y * b.win_stride;
+            win[k] = ref[(int64_t)y * d.ref_stride + x];
+        }
+        Search s = {d, job, b, d.start_mv, 0, 0, 0};
+        // svt_upsampled_setup_center_error: the variance lands in *distortion, *sse1 is not written
+        s.distortion = (int)candidate_error<NT>(b, d.start_mv, false).var;
+        s.besterr = (uint32_t)s.distortion + (uint32_t)mv_err_cost(d.start_mv, d, job);
+        r.fullpel_err = s.besterr;
+        r.exit = (uint8_t)search_block<NT>(s);
+        r.best_mv = s.best_mv, r.besterr = (int32_t)s.besterr, r.distortion = s.distortion, r.sse = s.sse1;
+        if (tid == 0)
+            d_result[i] = r;
+    }
+}
+
+}  // namespace
+
+extern "C" int32_t svt_hip_subpel_search_batch(const SvtHipSubpelJob *job, const SvtHipSubpelDesc *d_desc, SvtHipSubpelResult *d_result,
+                                               uint32_t n, void *stream) {
+    if (!job || !d_desc || !d_result) {
+        set_error("svt_hip_subpel_search_batch: bad argument");
+        return SVT_HIP_ERR_BAD_PARAMETER;
+    }
+    if (n == 0)
+        return SVT_HIP_OK;
+    TierBCall c("svt_hip_subpel_search_batch", stream);
+    if (!c.ok())
+        return c.status();
+    // a workgroup strides over the descriptors when there are more than the grid holds
+    const uint32_t small_grid = std::min(n, (uint32_t)cu_count() * 32u), large_grid = std::min(n, (uint32_t)cu_count() * 8u);
+    hipLaunchKernelGGL((subpel_kernel<64, 640, 480, false>), dim3(small_grid), dim3(64), 0, c.stream(), *job, d_desc, d_result, n);
+    hipLaunchKernelGGL((subpel_kernel<256, 136 * 136, 135 * 128, true>), dim3(large_grid), dim3(256), 0, c.stream(), *job, d_desc, d_result, n);
+    return c.finish();
+}
+
+extern "C" int32_t svt_hip_subpel_mv_limits(int32_t mi_row, int32_t mi_col, int32_t mi_width, int32_t mi_height, int32_t mi_rows,
+                                            int32_t mi_cols, const SvtHipMv *ref_mv, int32_t limits[4]) {
+    if (!ref_mv || !limits) {
+        set_error("svt_hip_subpel_mv_limits: bad argument");
+        return SVT_HIP_ERR_BAD_PARAMETER;
+    }
+    // product_coding_loop.c:2532-2535 (MI_SIZE 4, AOM_INTERP_EXTEND 4)
+    int col_min = -(((mi_col + mi_width) * 4) + 4), col_max = (mi_cols - mi_col) * 4 + 4;
+    int row_min = -(((mi_row + mi_height) * 4) + 4), row_max = (mi_rows - mi_row) * 4 + 4;
+    // svt_av1_set_mv_search_range (av1me.c:205-226)
+    const int mv_low = SUBPEL_MV_LOW, mv_upp = SUBPEL_MV_UPP, max_fp = SUBPEL_MAX_FULL_PEL_VAL;
+    col_min = std::max(col_min, std::max((ref_mv->col >> 3) - max_fp + !!(ref_mv->col & 7), (mv_low >> 3) + 1));
+    row_min = std::max(row_min, std::max((ref_mv->row >> 3) - max_fp + !!(ref_mv->row & 7), (mv_low >> 3) + 1));
+    col_max = std::min(col_max, std::min((ref_mv->col >> 3) + max_fp, (mv_upp >> 3) - 1));
+    row_max = std::min(row_max, std::min((ref_mv->row >> 3) + max_fp, (mv_upp >> 3) - 1));
+    // svt_av1_set_subpel_mv_search_range (mcomp.h:113-125)
+    const int max_mv = max_fp * 8;
+    limits[0] = std::max(mv_low + 1, std::max(col_min * 8, ref_mv->col - max_mv));
+    limits[1] = std::min(mv_upp - 1, std::min(col_max * 8, ref_mv->col + max_mv));
+    limits[2] = std::max(mv_low + 1, std::max(row_min * 8, ref_mv->row - max_mv));
+    limits[3] = std::min(mv_upp - 1, std::min(row_max * 8, ref_mv->row + max_mv));
+    return SVT_HIP_OK;
+}
+
+SVT_HIP_MODULE_WARMUP(inter_subpel)

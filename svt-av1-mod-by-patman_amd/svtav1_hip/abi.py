@@ -523,6 +523,37 @@ class MvCostParam(C.Structure):          # SvtHipMvCostParam == struct svt_mv_co
                 ("mvcost", C.c_void_p * 2), ("error_per_bit", C.c_int), ("early_exit_th", C.c_int), ("sad_per_bit", C.c_int)]
 
 
+SUBPEL_TREE, SUBPEL_TREE_PRUNED = range(2)                                       # SVT_HIP_SUBPEL_* (include/svt_hip_inter.h)
+SUBPEL_USE_2_TAPS, SUBPEL_USE_4_TAPS, SUBPEL_USE_8_TAPS = 1, 2, 3
+(SUBPEL_EXIT_NONE, SUBPEL_EXIT_EARLY, SUBPEL_EXIT_VARIANCE, SUBPEL_EXIT_ABS_TH, SUBPEL_EXIT_NO_ROUND, SUBPEL_EXIT_ROUND_DEV,
+ SUBPEL_EXIT_END) = range(7)
+(SUBPEL_OK, SUBPEL_BAD_SIZE, SUBPEL_BAD_POINTER, SUBPEL_BAD_START_MV, SUBPEL_BAD_METHOD, SUBPEL_BAD_FILTER,
+ SUBPEL_BAD_COST) = range(7)
+
+
+class SubpelJob(C.Structure):            # SvtHipSubpelJob (include/svt_hip_inter.h)
+    _fields_ = [("mvjcost", C.c_int32 * 4), ("mvcost", C.c_void_p * 2)]
+
+
+class SubpelDesc(C.Structure):           # SvtHipSubpelDesc
+    _fields_ = [("src", C.c_void_p), ("ref", C.c_void_p), ("src_stride", C.c_uint32), ("ref_stride", C.c_uint32), ("w", C.c_uint16),
+                ("h", C.c_uint16), ("start_mv", Mv), ("ref_mv", Mv), ("best_mvp", Mv), ("col_min", C.c_int32), ("col_max", C.c_int32),
+                ("row_min", C.c_int32), ("row_max", C.c_int32), ("iters_per_step", C.c_int32), ("pred_variance_th", C.c_int32),
+                ("round_dev_th", C.c_int32), ("error_per_bit", C.c_int32), ("early_exit_th", C.c_int32), ("hp_mv_th", C.c_int32),
+                ("best_mvp_dist", C.c_uint32), ("method", C.c_uint8), ("subpel_search_type", C.c_uint8), ("forced_stop", C.c_uint8),
+                ("allow_hp", C.c_uint8), ("bias_fp", C.c_uint8), ("skip_diag_refinement", C.c_uint8), ("abs_th_mult", C.c_uint8),
+                ("qp", C.c_uint8), ("mv_cost_type", C.c_uint8), ("early_exit", C.c_uint8), ("mvp_th", C.c_uint8), ("pad_", C.c_uint8)]
+
+
+class SubpelResult(C.Structure):         # SvtHipSubpelResult
+    _fields_ = [("best_mv", Mv), ("besterr", C.c_int32), ("distortion", C.c_int32), ("sse", C.c_uint32), ("fullpel_err", C.c_uint32),
+                ("exit", C.c_uint8), ("status", C.c_uint8), ("pad_", C.c_uint8 * 2)]
+
+
+SUBPEL_DESC_DTYPE = record_dtype(SubpelDesc)       # numpy views of arrays of them
+SUBPEL_RESULT_DTYPE = record_dtype(SubpelResult)
+
+
 class TxfmParam(C.Structure):            # SvtHipTxfmParam == TxfmParam (definitions.h:1051-1063)
     _fields_ = [("tx_type", C.c_uint8), ("tx_size", C.c_uint8), ("lossless", C.c_int32), ("bd", C.c_int32), ("is_hbd", C.c_int32),
                 ("tx_set_type", C.c_uint8), ("eob", C.c_int32)]

@@ -198,6 +198,18 @@ def compound_mask_search_batch(lib, descs, stream=None, fill=0xA5):
     return d_res.download(np.dtype(abi.MASK_SEARCH_RESULT_DTYPE), (len(descs),), stream)
 
 
+def subpel_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
+    """svt_hip_subpel_search_batch over a record array of abi.SUBPEL_DESC_DTYPE (or a list of abi.SubpelDesc) under the abi.SubpelJob `job`
+    (one call).  Returns (results as a record array of abi.SUBPEL_RESULT_DTYPE, the `guard` bytes before and after them: still `fill` if
+    untouched)."""
+    n = len(descs)
+    d_desc = upload_descriptors(lib, descs, stream)
+    d_out = _guarded(lib, C.sizeof(abi.SubpelResult) * n, guard, fill, stream)
+    check(lib, lib.svt_hip_subpel_search_batch(C.byref(job), C.c_void_p(d_desc.ptr), C.c_void_p(d_out.ptr + guard), C.c_uint32(n), C.c_void_p(stream)),
+          "svt_hip_subpel_search_batch")
+    return _unguard(d_out, abi.SUBPEL_RESULT_DTYPE, guard, stream)
+
+
 def txb_cost_batch(lib, d_base, descs, tables, w, h, d_txfm_result=None, d_distortion=None, stream=None, tables_in_lds=None, guard=64, fill=0xA5):
     """svt_hip_txb_cost_batch for blocks of one size w x h (one launch).  d_base: device address of the arena the descriptors' offsets
     refer to; descs: a record array of abi.TXB_COST_DESC_DTYPE (or a list of abi.TxbCostDesc); tables: a record array of
