@@ -243,8 +243,12 @@ typedef struct SvtHipPyramid8 {
     SvtHipPlane8 full, quarter, sixteenth; /* input_padded_pic, quarter_/sixteenth_downsampled_picture_ptr */
 } SvtHipPyramid8;
 
-/* Batched picture analysis: svt_hip_pyramid_frame + svt_hip_variance_frame for n pictures in three launches
- * (the picture-analysis kernel's per-picture work, pic_analysis_process.c:2126,2137, for a whole mini-GOP at once).
+/* Batched picture analysis: svt_hip_pyramid_frame + svt_hip_variance_frame for n pictures in one launch that reads every
+ * full-resolution sample once (the picture-analysis kernel's per-picture work, pic_analysis_process.c:2126,2137, for a
+ * whole mini-GOP at once).  The one launch needs decimated planes of the reference's sizes, (width >> 1, height >> 1) and
+ * (width >> 2, height >> 2) of the full plane; a batch with any other descriptor, and every batch under
+ * SVTAV1_HIP_ANALYSIS_FUSED=0 (read once per process), runs as three launches with the same results.  The quarter
+ * plane is neither read nor written when hme_level1_enabled is 0.
  * `jobs` is a HOST array; the planes and output arrays it names are device memory. */
 typedef struct SvtHipAnalysisJob {
     SvtHipPyramid8 pyr;

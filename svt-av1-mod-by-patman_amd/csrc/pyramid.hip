@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "sad_device.hpp"
 
 using namespace svthip;
 
@@ -170,6 +171,189 @@ __global__ __launch_bounds__(256) void variance_batch_kernel(const SvtHipAnalysi
     variance_body(f.buf + f.org_x + (size_t)f.org_y * f.stride, f.stride, bw, bw * bh, j.variance, j.mean, full_precision);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Fused picture analysis: one read of the full plane gives both decimated planes, their padding and the block statistics.
+// One wave64 per 128x64 tile of the full plane (two 64x64 blocks side by side), no barrier and no LDS.  Lane (px, py) =
+// (lane & 7, lane >> 3) owns the 16x8 patch at (16 px, 8 py) of the tile and loads it as eight 16-byte rows, so one load
+// instruction of the wave reads 8 rows of 128 contiguous bytes.  A patch is two whole 8x8 blocks, 8x4 quarter samples and
+// 4x2 sixteenth samples: only the reduction tree of the statistics crosses lanes (shuffles), nothing crosses waves.
+// The bytes loaded are exactly those variance_body reads (every row of every 64x64 block that exists; with sub-sampled
+// statistics the odd rows below the picture are left out), so no load needs a clamped form.
+// ------------------------------------------------------------------------------------------------
+typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
+__device__ __forceinline__ void store_any(uint8_t *g, uint8_t v) { *(__attribute__((address_space(1))) uint8_t *)g = v; }
+__device__ __forceinline__ void store_any(uint8_t *g, uint32_t v) { *(__attribute__((address_space(1))) dev::u32_unaligned *)g = v; }
+__device__ __forceinline__ void store_any(uint8_t *g, uint64_t v) { *(__attribute__((address_space(1))) u64_unaligned *)g = v; }
+__device__ __forceinline__ void store_any(uint8_t *g, dev::u128v v) { *(__attribute__((address_space(1))) dev::u128_unaligned *)g = v; }
+
+// n copies of the byte v from p on, any alignment
+__device__ __forceinline__ void fill_bytes(uint8_t *p, uint32_t n, uint32_t v) {
+    const uint32_t   w  = v * 0x01010101u;
+    const dev::u128v w4 = {w, w, w, w};
+    uint32_t         i  = 0;
+    for (; i + 16 <= n; i += 16) store_any(p + i, w4);
+    for (; i < n; i++) store_any(p + i, (uint8_t)v);
+}
+
+// bytes (a0 a1 a2 a3), (b0 b1 b2 b3) -> (a0 + a1 + b0 + b1 + 2) >> 2 in bits 0-7 and (a2 + a3 + b2 + b3 + 2) >> 2 in bits 16-23
+__device__ __forceinline__ uint32_t avg2x2_pairs(uint32_t a, uint32_t b) {
+    const uint32_t s = (a & 0x00ff00ffu) + ((a >> 8) & 0x00ff00ffu) + (b & 0x00ff00ffu) + ((b >> 8) & 0x00ff00ffu) + 0x00020002u;
+    return (s >> 2) & 0x00ff00ffu;
+}
+// the two means of `lo` and the two of `hi` as four adjacent bytes
+__device__ __forceinline__ uint32_t pack_pairs(uint32_t lo, uint32_t hi) {
+    return ((lo | (lo >> 8)) & 0xffffu) | ((hi | (hi >> 8)) << 16);
+}
+
+// The CL x RL samples one lane holds of a decimated plane, at column cx0 / row cy0 of its picture area (r0 .. r3: CL bytes
+// each, first column lowest), go to the plane together with the replicated padding they define: the lanes holding column 0 /
+// the last column write the left / right padding of their rows (right: up to the stride), the lanes holding row 0 / the
+// last row repeat that over the top / bottom padding rows, corners included.  Every byte of stride * (height + 2 * pad)
+// is written by exactly one lane, as downsample_pad_body leaves it.
+template <int CL, int RL>
+__device__ __forceinline__ void store_decimated(const SvtHipPlane8 &o, uint32_t cx0, uint32_t cy0, uint64_t r0, uint64_t r1, uint64_t r2 = 0,
+                                                uint64_t r3 = 0) {
+    const uint32_t dw = o.width, dh = o.height, pad = o.org_x, stride = o.stride;
+    if (cx0 >= dw || cy0 >= dh)
+        return;
+    const uint32_t nc = dw - cx0 < (uint32_t)CL ? dw - cx0 : (uint32_t)CL, nr = dh - cy0 < (uint32_t)RL ? dh - cy0 : (uint32_t)RL;
+    const bool     left = cx0 == 0, right = cx0 + nc == dw;
+    // rows of the padded plane this lane writes: its own, preceded by the top padding / followed by the bottom padding
+    const uint32_t y_own = pad + cy0, y_beg = cy0 == 0 ? 0 : y_own, y_end = cy0 + nr == dh ? dh + 2 * pad : y_own + nr;
+    for (uint32_t Y = y_beg; Y < y_end; Y++) {
+        const uint32_t r = Y < y_own ? 0 : (Y - y_own < nr ? Y - y_own : nr - 1);
+        uint64_t       v = r == 1 ? r1 : r0;  // scalars, not an array: a row picked by a run-time index stays in registers
+        if (RL == 4)
+            v = r == 2 ? r2 : (r == 3 ? r3 : v);
+        uint8_t *row = o.buf + (size_t)Y * stride, *p = row + pad + cx0;
+        if (nc == (uint32_t)CL) {
+            if (CL == 8)
+                store_any(p, v);
+            else
+                store_any(p, (uint32_t)v);
+        } else {
+            for (uint32_t k = 0; k < nc; k++) store_any(p + k, (uint8_t)(v >> (8 * k)));
+        }
+        if (left)
+            fill_bytes(row, pad, (uint32_t)v & 0xffu);
+        if (right)
+            fill_bytes(row + pad + dw, stride - pad - dw, (uint32_t)(v >> (8 * (nc - 1))) & 0xffu);
+    }
+}
+
+__device__ __forceinline__ uint64_t xor_add(uint64_t v, int mask) { return v + __shfl_xor((unsigned long long)v, mask, 64); }
+
+template <bool L1, bool FP>
+__device__ __forceinline__ void analysis_fused_body(const SvtHipAnalysisJob &j) {
+    const SvtHipPlane8 &f  = j.pyr.full;
+    const uint32_t      W = f.width, H = f.height;
+    const uint32_t      bw = (W + 63u) / 64u, bh = (H + 63u) / 64u, tw = (bw + 1u) / 2u;  // 64x64 blocks, tiles per row
+    const uint32_t      t = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (t >= tw * bh)  // the grid is sized by the largest job; uniform over the wave
+        return;
+    const uint32_t ty = t / tw, tx = t - ty * tw;
+    const uint32_t lane = threadIdx.x & 63u, px = lane & 7u, py = lane >> 3;
+    const uint32_t bx = 2u * tx + (px >> 2);
+    const bool     on = bx < bw;  // the right half of the last tile of a row may have no block
+    const uint32_t X0 = 128u * tx + 16u * px, Y0 = 64u * ty + 8u * py;
+    // Eight loads with no branch between them, so all are in flight at once.  A lane without a block loads what the lane
+    // 64 columns to its left loads, and an odd row below the picture that sub-sampled statistics do not read is replaced by
+    // the even row above it: neither value is ever used (see below), and no byte is read that variance_body does not read.
+    const uint8_t *p = f.buf + f.org_x + (on ? X0 : X0 - 64u) + (size_t)(f.org_y + Y0) * f.stride;
+    dev::u128v     d[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const uint32_t rl = FP || !(r & 1) || Y0 + r < H ? r : r - 1;
+        d[r]              = dev::load_u128_any(p + (size_t)rl * f.stride);
+    }
+
+    // decimated planes.  A lane of a block that does not exist lies right of every decimated sample and writes nothing;
+    // a row pair with a replaced row lies below them.
+    uint64_t s16[2];
+    if (L1) {
+        uint64_t q[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const dev::u128v a = d[2 * k], b = d[2 * k + 1];
+            q[k] = dev::pair64(pack_pairs(avg2x2_pairs(a.x, b.x), avg2x2_pairs(a.y, b.y)),
+                               pack_pairs(avg2x2_pairs(a.z, b.z), avg2x2_pairs(a.w, b.w)));
+        }
+        store_decimated<8, 4>(j.pyr.quarter, X0 >> 1, Y0 >> 1, q[0], q[1], q[2], q[3]);
+#pragma unroll
+        for (int k = 0; k < 2; k++)  // from the rounded quarter samples, as the second downsample does
+            s16[k] = pack_pairs(avg2x2_pairs((uint32_t)q[2 * k], (uint32_t)q[2 * k + 1]),
+                                avg2x2_pairs((uint32_t)(q[2 * k] >> 32), (uint32_t)(q[2 * k + 1] >> 32)));
+    } else {
+#pragma unroll
+        for (int k = 0; k < 2; k++) {  // STEP 4: columns 4i + 1, 4i + 2 of rows 4j + 1, 4j + 2
+            const dev::u128v a = d[4 * k + 1], b = d[4 * k + 2];
+            auto mid = [](uint32_t ta, uint32_t tb) -> uint32_t {
+                return (((ta >> 8) & 0xffu) + ((ta >> 16) & 0xffu) + ((tb >> 8) & 0xffu) + ((tb >> 16) & 0xffu) + 2u) >> 2;
+            };
+            s16[k] = mid(a.x, b.x) | (mid(a.y, b.y) << 8) | (mid(a.z, b.z) << 16) | (mid(a.w, b.w) << 24);
+        }
+    }
+    store_decimated<4, 2>(j.pyr.sixteenth, X0 >> 2, Y0 >> 2, s16[0], s16[1]);
+
+    // statistics of the two 8x8 blocks of the patch, then the tree of variance_body: the 16x16 block is both 8x8 of this
+    // lane and of lane ^ 8, the 32x32 block joins lanes ^ 1 and ^ 16, the 64x64 block lanes ^ 2 and ^ 32.  The two blocks
+    // of a tile differ in bit 2 of the lane and never mix, so what a lane without a block carries does not matter.
+    uint32_t sa = 0, sb = 0, qa = 0, qb = 0;
+#pragma unroll
+    for (int r = 0; r < 8; r += FP ? 1 : 2) {
+        sa = __builtin_amdgcn_sad_u8(d[r].y, 0u, __builtin_amdgcn_sad_u8(d[r].x, 0u, sa));
+        sb = __builtin_amdgcn_sad_u8(d[r].w, 0u, __builtin_amdgcn_sad_u8(d[r].z, 0u, sb));
+        qa = __builtin_amdgcn_udot4(d[r].y, d[r].y, __builtin_amdgcn_udot4(d[r].x, d[r].x, qa, false), false);
+        qb = __builtin_amdgcn_udot4(d[r].w, d[r].w, __builtin_amdgcn_udot4(d[r].z, d[r].z, qb, false), false);
+    }
+    // sub-sampled: sum << 3, sumsq << 11; full: (sum << 8) / 64, (sumsq << 16) / 64
+    const uint64_t m8a = (uint64_t)sa << (FP ? 2 : 3), m8b = (uint64_t)sb << (FP ? 2 : 3);
+    const uint64_t q8a = (uint64_t)qa << (FP ? 10 : 11), q8b = (uint64_t)qb << (FP ? 10 : 11);
+    const uint64_t m16 = xor_add(m8a + m8b, 8) >> 2, q16 = xor_add(q8a + q8b, 8) >> 2;
+    const uint64_t m32 = xor_add(xor_add(m16, 1), 16) >> 2, q32 = xor_add(xor_add(q16, 1), 16) >> 2;
+    const uint64_t m64 = xor_add(xor_add(m32, 2), 32) >> 2, q64 = xor_add(xor_add(q32, 2), 32) >> 2;
+    if (!on)
+        return;
+    const uint32_t b  = ty * bw + bx, cx = px & 3u;
+    uint16_t      *vo = j.variance + (size_t)85 * b;
+    uint64_t      *mo = j.mean ? j.mean + (size_t)85 * b : nullptr;
+    auto put = [&](uint32_t i, uint64_t m, uint64_t q) {  // global stores, not the flat ones a generic pointer gets
+        *(__attribute__((address_space(1))) uint16_t *)(vo + i) = (uint16_t)((q - m * m) >> 16);
+        if (mo)
+            *(__attribute__((address_space(1))) uint64_t *)(mo + i) = m;
+    };
+    put(21u + 8u * py + 2u * cx, m8a, q8a);
+    put(22u + 8u * py + 2u * cx, m8b, q8b);
+    if (!(py & 1u))
+        put(5u + 4u * (py >> 1) + cx, m16, q16);
+    if (!(py & 3u) && !(cx & 1u))
+        put(1u + 2u * (py >> 2) + (cx >> 1), m32, q32);
+    if (py == 0 && cx == 0)
+        put(0, m64, q64);
+}
+
+// blockIdx.y = picture, four tiles (waves) per workgroup
+template <bool L1, bool FP>
+__global__ __launch_bounds__(256) void analysis_fused_kernel(const SvtHipAnalysisJob *__restrict__ jobs) {
+    // A copy made in 8-byte words: the whole descriptor comes through scalar loads up front (its 16-bit fields would each
+    // take a vector load and a wait where they are first used) and stays in scalar registers across the stores.
+    SvtHipAnalysisJob j;
+    static_assert(sizeof(j) % 8 == 0 && alignof(SvtHipAnalysisJob) == 8, "copied as 64-bit words");
+    uint64_t w[sizeof(j) / 8];
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(j) / 8; i++) w[i] = ((const uint64_t *)(jobs + blockIdx.y))[i];
+    memcpy(&j, w, sizeof(j));
+    analysis_fused_body<L1, FP>(j);
+}
+
+// The fused kernel takes decimated planes of the sizes the reference allocates (max_width >> 1 and >> 2, and the same of
+// the height: reference_object.c:227-241); with those every decimated sample depends on samples of its own tile only.
+bool fused_sizes(const SvtHipPyramid8 &y, int32_t hme_level1_enabled) {
+    const uint32_t w = y.full.width, h = y.full.height;
+    return y.sixteenth.width == (w >> 2) && y.sixteenth.height == (h >> 2) &&
+           (!hme_level1_enabled || (y.quarter.width == (w >> 1) && y.quarter.height == (h >> 1)));
+}
+
 bool plane_ok(const SvtHipPlane8 *p) {
     return p && p->buf && p->width && p->height && p->stride >= (uint32_t)p->width + 2u * p->org_x;
 }
@@ -242,14 +426,18 @@ extern "C" int32_t svt_hip_variance_frame(const SvtHipPlane8 *full, uint16_t *d_
     return SVT_HIP_OK;
 }
 
-// Batched picture analysis: pyramids + variances of n pictures in three launches (blockIdx.z / .y = picture).
+// Batched picture analysis: pyramids + variances of n pictures in one fused launch (blockIdx.y = picture), or in the three
+// launches of the single-picture kernels' batch forms (blockIdx.z / .y = picture) when a descriptor has other sizes.
 extern "C" int32_t svt_hip_analysis_frames(const SvtHipAnalysisJob *jobs, uint32_t n_jobs, int32_t hme_level1_enabled,
                                            int32_t full_precision, void *stream) {
     if (!jobs || n_jobs == 0 || n_jobs > 65535) {
         set_error("svt_hip_analysis_frames: bad job count");
         return SVT_HIP_ERR_BAD_PARAMETER;
     }
-    uint32_t max_q_stride = 0, max_q_rows = 0, max_s_stride = 0, max_s_rows = 0, max_nb = 0;
+    // SVTAV1_HIP_ANALYSIS_FUSED=0: every batch through the three launches, for A/B runs
+    static const bool fused_on = !(getenv("SVTAV1_HIP_ANALYSIS_FUSED") && atoi(getenv("SVTAV1_HIP_ANALYSIS_FUSED")) == 0);
+    bool              fused    = fused_on;
+    uint32_t max_q_stride = 0, max_q_rows = 0, max_s_stride = 0, max_s_rows = 0, max_nb = 0, max_tiles = 0;
     for (uint32_t i = 0; i < n_jobs; i++) {
         const SvtHipPyramid8 &y = jobs[i].pyr;
         if (!plane_ok(&y.full) || !plane_ok(&y.sixteenth) || (hme_level1_enabled && !plane_ok(&y.quarter)) || !jobs[i].variance ||
@@ -263,12 +451,27 @@ extern "C" int32_t svt_hip_analysis_frames(const SvtHipAnalysisJob *jobs, uint32
         max_s_rows   = y.sixteenth.height + 2u * y.sixteenth.org_y > max_s_rows ? y.sixteenth.height + 2u * y.sixteenth.org_y : max_s_rows;
         const uint32_t nb = ((y.full.width + 63u) / 64u) * ((y.full.height + 63u) / 64u);
         max_nb            = nb > max_nb ? nb : max_nb;
+        const uint32_t nt = (((y.full.width + 63u) / 64u + 1u) / 2u) * ((y.full.height + 63u) / 64u);
+        max_tiles         = nt > max_tiles ? nt : max_tiles;
+        fused             = fused && fused_sizes(y, hme_level1_enabled);
     }
     TierBCall                c("svt_hip_analysis_frames", stream);
     const SvtHipAnalysisJob *d_jobs = (const SvtHipAnalysisJob *)c.stage(jobs, (size_t)n_jobs * sizeof(SvtHipAnalysisJob));
     if (!d_jobs)
         return c.status();
     hipStream_t st = c.stream();
+    if (fused) {
+        const dim3 grid((max_tiles + 3) / 4, n_jobs);
+        if (hme_level1_enabled && full_precision)
+            hipLaunchKernelGGL((analysis_fused_kernel<true, true>), grid, dim3(256), 0, st, d_jobs);
+        else if (hme_level1_enabled)
+            hipLaunchKernelGGL((analysis_fused_kernel<true, false>), grid, dim3(256), 0, st, d_jobs);
+        else if (full_precision)
+            hipLaunchKernelGGL((analysis_fused_kernel<false, true>), grid, dim3(256), 0, st, d_jobs);
+        else
+            hipLaunchKernelGGL((analysis_fused_kernel<false, false>), grid, dim3(256), 0, st, d_jobs);
+        return c.finish();
+    }
     if (hme_level1_enabled) {
         hipLaunchKernelGGL(downsample_pad_batch_kernel, dim3((max_q_stride / 4 + 1 + 255) / 256, (max_q_rows + BATCH_ROWS - 1) / BATCH_ROWS, n_jobs), dim3(256), 0, st, d_jobs, 0);
         hipLaunchKernelGGL(downsample_pad_batch_kernel, dim3((max_s_stride / 4 + 1 + 255) / 256, (max_s_rows + BATCH_ROWS - 1) / BATCH_ROWS, n_jobs), dim3(256), 0, st, d_jobs, 1);
