@@ -117,7 +117,6 @@ __device__ __forceinline__ uint16_t pic_dist(const SvtHipMeParams &p, int li, in
 __device__ __forceinline__ const uint8_t *plane_at(const SvtHipPlane8 &pl, int x, int y) {
     return pl.buf + (ptrdiff_t)((int)pl.org_y + y) * (ptrdiff_t)pl.stride + (int)pl.org_x + x;
 }
-__device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *g) { return load_u32_any(g); }
 
 // This lane's share of the SAD between the staged 64x64 source (LDS rows of 16 dwords, every `row_step`-th row) and a block
 // in global memory at any byte address: 16 bytes per load, `ndw` = block width in dwords (b64_w / 4, a multiple of 2).

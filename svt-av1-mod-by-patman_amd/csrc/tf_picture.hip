@@ -76,7 +76,6 @@ struct RefineRef {  // per reference picture
 };
 
 __device__ __forceinline__ int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int32_t rnd(int32_t v, int n) { return (v + ((1 << n) >> 1)) >> n; }
 
 // compute_subpel_params + clamp_mv_to_umv_border_sb (enc_inter_prediction.c:28-48, 3166-3177) for a bw x bh block of a plane
 // with sub-sampling ss that belongs to the luma block (lx, ly, lsize): 1/16-sample column / row

@@ -53,11 +53,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
-__device__ __forceinline__ int64_t wave_sum64(int64_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 using intra::neighbours;  // the neighbour gather of the open-loop intra search (intra_device.hpp)
 

@@ -19,35 +19,38 @@ def check(lib, rc, what):
         raise HipError(f"{what} failed (0x{rc & 0xffffffff:08x}): {lib.svt_hip_last_error().decode()}")
 
 
+def _call(lib, name, *args, stream=None, sync=False):
+    """The export `name` with `stream` as its last argument (abi.load declared the argument types: plain ints, None and byref(..) do),
+    its return code checked under its own name, then svt_hip_stream_sync if asked for."""
+    check(lib, getattr(lib, name)(*args, stream), name)
+    if sync:
+        check(lib, lib.svt_hip_stream_sync(stream), "svt_hip_stream_sync")
+
+
 class DeviceBuffer:
     def __init__(self, lib, nbytes):
         self.lib, self.nbytes = lib, int(nbytes)
         p = C.c_void_p()
-        check(lib, lib.svt_hip_malloc(C.byref(p), C.c_size_t(self.nbytes)), "svt_hip_malloc")
+        check(lib, lib.svt_hip_malloc(C.byref(p), self.nbytes), "svt_hip_malloc")
         self.ptr = p.value
 
     def upload(self, arr, stream=None):
         arr = np.ascontiguousarray(arr)
         assert arr.nbytes <= self.nbytes
-        check(self.lib, self.lib.svt_hip_upload(C.c_void_p(self.ptr), arr.ctypes.data_as(C.c_void_p),
-                                                C.c_size_t(arr.nbytes), C.c_void_p(stream)), "svt_hip_upload")
-        check(self.lib, self.lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+        _call(self.lib, "svt_hip_upload", self.ptr, arr.ctypes.data, arr.nbytes, stream=stream, sync=True)
 
     def download(self, dtype, shape, stream=None):
         out = np.empty(shape, dtype=dtype)
         assert out.nbytes <= self.nbytes
-        check(self.lib, self.lib.svt_hip_download(out.ctypes.data_as(C.c_void_p), C.c_void_p(self.ptr),
-                                                  C.c_size_t(out.nbytes), C.c_void_p(stream)), "svt_hip_download")
-        check(self.lib, self.lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+        _call(self.lib, "svt_hip_download", out.ctypes.data, self.ptr, out.nbytes, stream=stream, sync=True)
         return out
 
     def fill(self, value, stream=None):
-        check(self.lib, self.lib.svt_hip_memset(C.c_void_p(self.ptr), int(value), C.c_size_t(self.nbytes),
-                                                C.c_void_p(stream)), "svt_hip_memset")
+        _call(self.lib, "svt_hip_memset", self.ptr, int(value), self.nbytes, stream=stream)
 
     def free(self):
         if self.ptr:
-            self.lib.svt_hip_free(C.c_void_p(self.ptr))
+            self.lib.svt_hip_free(self.ptr)
             self.ptr = None
 
     def __del__(self):
@@ -55,6 +58,20 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class Guarded:
+    """A device buffer of nbytes between two runs of `guard` bytes, all of it `fill`; ptr is the payload's address."""
+
+    def __init__(self, lib, nbytes, guard, fill, stream=None):
+        self.buf, self.guard, self.stream = DeviceBuffer(lib, 2 * guard + nbytes), guard, stream
+        self.buf.fill(fill, stream)
+        self.ptr = self.buf.ptr + guard
+
+    def read(self, dtype):
+        """(the records between the guards, the guard bytes before and after them: still the fill if untouched)"""
+        raw, end = self.buf.download(np.uint8, (self.buf.nbytes,), self.stream), self.buf.nbytes - self.guard
+        return raw[self.guard:end].view(np.dtype(dtype)).copy(), np.concatenate([raw[:self.guard], raw[end:]])
 
 
 class DevicePlane:
@@ -126,12 +143,17 @@ class DeviceIntraOut:
         return {k: self.bufs[k].download(dt, shape) for k, (dt, shape) in self.shapes.items()}
 
 
+def _tables(lib, tables, stream):
+    """Rate tables as one contiguous record array, and its device copy"""
+    tables = np.ascontiguousarray(tables, np.dtype(abi.RATE_TABLES_DTYPE)).reshape(-1)
+    d_tab = DeviceBuffer(lib, tables.nbytes)
+    d_tab.upload(tables, stream)
+    return tables, d_tab
+
+
 def intra_search_frames(lib, jobs, stream=None, sync=True):
     """svt_hip_intra_search_frames over a list of abi.IntraSearchJob (one launch)."""
-    arr = (abi.IntraSearchJob * len(jobs))(*jobs)
-    check(lib, lib.svt_hip_intra_search_frames(arr, C.c_uint32(len(jobs)), C.c_void_p(stream)), "svt_hip_intra_search_frames")
-    if sync:
-        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+    _call(lib, "svt_hip_intra_search_frames", (abi.IntraSearchJob * len(jobs))(*jobs), len(jobs), stream=stream, sync=sync)
 
 
 def intra_predict_batch(lib, descs, stream=None, sync=True, waves_per_workgroup=None):
@@ -139,30 +161,21 @@ def intra_predict_batch(lib, descs, stream=None, sync=True, waves_per_workgroup=
     same through svt_hip_intra_predict_batch_packed.  Returns the device copy of the descriptors: keep it until the stream has been synchronised."""
     d_desc = upload_descriptors(lib, descs, stream)
     if waves_per_workgroup is None:
-        rc = lib.svt_hip_intra_predict_batch(C.c_void_p(d_desc.ptr), C.c_uint32(len(descs)), C.c_void_p(stream))
+        _call(lib, "svt_hip_intra_predict_batch", d_desc.ptr, len(descs), stream=stream, sync=sync)
     else:
-        rc = lib.svt_hip_intra_predict_batch_packed(C.c_void_p(d_desc.ptr), C.c_uint32(len(descs)), C.c_uint32(waves_per_workgroup),
-                                                    C.c_void_p(stream))
-    check(lib, rc, "svt_hip_intra_predict_batch")
-    if sync:
-        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+        _call(lib, "svt_hip_intra_predict_batch_packed", d_desc.ptr, len(descs), waves_per_workgroup, stream=stream, sync=sync)
     return d_desc
 
 
 def cfl_predict_batch(lib, descs, stream=None, sync=True):
     """svt_hip_cfl_predict_batch over a list of abi.CflDesc or a record array of abi.CFL_DESC_DTYPE (one launch)."""
     d_desc = upload_descriptors(lib, descs, stream)
-    check(lib, lib.svt_hip_cfl_predict_batch(C.c_void_p(d_desc.ptr), C.c_uint32(len(descs)), C.c_void_p(stream)), "svt_hip_cfl_predict_batch")
-    if sync:
-        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+    _call(lib, "svt_hip_cfl_predict_batch", d_desc.ptr, len(descs), stream=stream, sync=sync)
     return d_desc
 
 
 def me_frames(lib, jobs, stream=None, sync=True):
-    arr = (abi.MeFrameJob * len(jobs))(*jobs)
-    check(lib, lib.svt_hip_me_frames(arr, C.c_uint32(len(jobs)), C.c_void_p(stream)), "svt_hip_me_frames")
-    if sync:
-        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+    _call(lib, "svt_hip_me_frames", (abi.MeFrameJob * len(jobs))(*jobs), len(jobs), stream=stream, sync=sync)
 
 
 def upload_descriptors(lib, descs, stream=None):
@@ -181,9 +194,7 @@ def upload_descriptors(lib, descs, stream=None):
 def blend_batch(lib, descs, stream=None, sync=True):
     """svt_hip_blend_batch over a list of abi.BlendDesc (one launch)."""
     d_desc = upload_descriptors(lib, descs, stream)
-    check(lib, lib.svt_hip_blend_batch(C.c_void_p(d_desc.ptr), C.c_uint32(len(descs)), C.c_void_p(stream)), "svt_hip_blend_batch")
-    if sync:
-        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+    _call(lib, "svt_hip_blend_batch", d_desc.ptr, len(descs), stream=stream, sync=sync)
     return d_desc
 
 
@@ -193,8 +204,7 @@ def compound_mask_search_batch(lib, descs, stream=None, fill=0xA5):
     d_desc = upload_descriptors(lib, descs, stream)
     d_res = DeviceBuffer(lib, C.sizeof(abi.MaskSearchResult) * len(descs))
     d_res.fill(fill, stream)
-    check(lib, lib.svt_hip_compound_mask_search_batch(C.c_void_p(d_desc.ptr), C.c_void_p(d_res.ptr), C.c_uint32(len(descs)),
-                                                      C.c_void_p(stream)), "svt_hip_compound_mask_search_batch")
+    _call(lib, "svt_hip_compound_mask_search_batch", d_desc.ptr, d_res.ptr, len(descs), stream=stream)
     return d_res.download(np.dtype(abi.MASK_SEARCH_RESULT_DTYPE), (len(descs),), stream)
 
 
@@ -204,10 +214,9 @@ def subpel_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
     untouched)."""
     n = len(descs)
     d_desc = upload_descriptors(lib, descs, stream)
-    d_out = _guarded(lib, C.sizeof(abi.SubpelResult) * n, guard, fill, stream)
-    check(lib, lib.svt_hip_subpel_search_batch(C.byref(job), C.c_void_p(d_desc.ptr), C.c_void_p(d_out.ptr + guard), C.c_uint32(n), C.c_void_p(stream)),
-          "svt_hip_subpel_search_batch")
-    return _unguard(d_out, abi.SUBPEL_RESULT_DTYPE, guard, stream)
+    d_out = Guarded(lib, C.sizeof(abi.SubpelResult) * n, guard, fill, stream)
+    _call(lib, "svt_hip_subpel_search_batch", C.byref(job), d_desc.ptr, d_out.ptr, n, stream=stream)
+    return d_out.read(abi.SUBPEL_RESULT_DTYPE)
 
 
 def txb_cost_batch(lib, d_base, descs, tables, w, h, d_txfm_result=None, d_distortion=None, stream=None, tables_in_lds=None, guard=64, fill=0xA5):
@@ -217,20 +226,14 @@ def txb_cost_batch(lib, d_base, descs, tables, w, h, d_txfm_result=None, d_disto
     svt_hip_txfm_distortion_batch wrote, or None.  With tables_in_lds (0 or 1) the same through svt_hip_txb_cost_batch_placed.
     Returns (results as a record array of abi.TXB_COST_DTYPE, the `guard` bytes before and after them: still `fill` if untouched)."""
     n = len(descs)
-    tables = np.ascontiguousarray(tables, np.dtype(abi.RATE_TABLES_DTYPE)).reshape(-1)
-    d_desc, d_tab = upload_descriptors(lib, descs, stream), DeviceBuffer(lib, tables.nbytes)
-    d_tab.upload(tables, stream)
-    d_out = DeviceBuffer(lib, 2 * guard + C.sizeof(abi.TxbCost) * n)
-    d_out.fill(fill, stream)
-    args = (C.c_void_p(d_base), C.c_void_p(d_desc.ptr), C.c_void_p(d_tab.ptr), C.c_uint32(len(tables)), C.c_void_p(d_txfm_result),
-            C.c_void_p(d_distortion), C.c_void_p(d_out.ptr + guard), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h))
+    d_desc, (tables, d_tab) = upload_descriptors(lib, descs, stream), _tables(lib, tables, stream)
+    d_out = Guarded(lib, C.sizeof(abi.TxbCost) * n, guard, fill, stream)
+    args = (d_base, d_desc.ptr, d_tab.ptr, len(tables), d_txfm_result, d_distortion, d_out.ptr, n, w, h)
     if tables_in_lds is None:
-        rc = lib.svt_hip_txb_cost_batch(*args, C.c_void_p(stream))
+        _call(lib, "svt_hip_txb_cost_batch", *args, stream=stream)
     else:
-        rc = lib.svt_hip_txb_cost_batch_placed(*args, C.c_uint32(tables_in_lds), C.c_void_p(stream))
-    check(lib, rc, "svt_hip_txb_cost_batch")
-    raw = d_out.download(np.uint8, (d_out.nbytes,), stream)
-    return raw[guard:d_out.nbytes - guard].view(np.dtype(abi.TXB_COST_DTYPE)).copy(), np.concatenate([raw[:guard], raw[d_out.nbytes - guard:]])
+        _call(lib, "svt_hip_txb_cost_batch_placed", *args, tables_in_lds, stream=stream)
+    return d_out.read(abi.TXB_COST_DTYPE)
 
 
 def rdoq_batch(lib, d_base, d_txfm_desc, descs, tables, d_txfm_result, w, h, stream=None, mapping=None, guard=64, fill=0xA5):
@@ -240,33 +243,14 @@ def rdoq_batch(lib, d_base, d_txfm_desc, descs, tables, d_txfm_result, w, h, str
     With mapping (0, 1 or 2) the same through svt_hip_rdoq_batch_mapped.
     Returns (results as a record array of abi.RDOQ_RESULT_DTYPE, the `guard` bytes before and after them: still `fill` if untouched)."""
     n = len(descs)
-    tables = np.ascontiguousarray(tables, np.dtype(abi.RATE_TABLES_DTYPE)).reshape(-1)
-    d_desc, d_tab = upload_descriptors(lib, descs, stream), DeviceBuffer(lib, tables.nbytes)
-    d_tab.upload(tables, stream)
-    d_out = DeviceBuffer(lib, 2 * guard + C.sizeof(abi.RdoqResult) * n)
-    d_out.fill(fill, stream)
-    args = (C.c_void_p(d_base), C.c_void_p(d_txfm_desc), C.c_void_p(d_desc.ptr), C.c_void_p(d_tab.ptr), C.c_uint32(len(tables)),
-            C.c_void_p(d_txfm_result), C.c_void_p(d_out.ptr + guard), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h))
+    d_desc, (tables, d_tab) = upload_descriptors(lib, descs, stream), _tables(lib, tables, stream)
+    d_out = Guarded(lib, C.sizeof(abi.RdoqResult) * n, guard, fill, stream)
+    args = (d_base, d_txfm_desc, d_desc.ptr, d_tab.ptr, len(tables), d_txfm_result, d_out.ptr, n, w, h)
     if mapping is None:
-        rc = lib.svt_hip_rdoq_batch(*args, C.c_void_p(stream))
+        _call(lib, "svt_hip_rdoq_batch", *args, stream=stream)
     else:
-        rc = lib.svt_hip_rdoq_batch_mapped(*args, C.c_uint32(mapping), C.c_void_p(stream))
-    check(lib, rc, "svt_hip_rdoq_batch")
-    raw = d_out.download(np.uint8, (d_out.nbytes,), stream)
-    return raw[guard:d_out.nbytes - guard].view(np.dtype(abi.RDOQ_RESULT_DTYPE)).copy(), np.concatenate([raw[:guard], raw[d_out.nbytes - guard:]])
-
-
-def _guarded(lib, nbytes, guard, fill, stream):
-    """A device buffer of nbytes between two runs of `guard` bytes, all of it `fill`"""
-    buf = DeviceBuffer(lib, 2 * guard + nbytes)
-    buf.fill(fill, stream)
-    return buf
-
-
-def _unguard(buf, dtype, guard, stream):
-    """(the records between the guards, the guard bytes before and after them: still the fill if untouched)"""
-    raw = buf.download(np.uint8, (buf.nbytes,), stream)
-    return raw[guard:buf.nbytes - guard].view(np.dtype(dtype)).copy(), np.concatenate([raw[:guard], raw[buf.nbytes - guard:]])
+        _call(lib, "svt_hip_rdoq_batch_mapped", *args, mapping, stream=stream)
+    return d_out.read(abi.RDOQ_RESULT_DTYPE)
 
 
 def spatial_distortion_batch(lib, d_base, d_txfm_desc, srcs, w, h, stream=None, guard=64, fill=0xA5):
@@ -275,11 +259,9 @@ def spatial_distortion_batch(lib, d_base, d_txfm_desc, srcs, w, h, stream=None, 
     Returns (uint64 [n][2] = {residual, prediction}, the guard bytes around them)."""
     n = len(srcs)
     d_src = upload_descriptors(lib, srcs, stream)
-    d_out = _guarded(lib, 16 * n, guard, fill, stream)
-    check(lib, lib.svt_hip_txfm_spatial_distortion_batch(C.c_void_p(d_base), C.c_void_p(d_txfm_desc), C.c_void_p(d_src.ptr), C.c_void_p(d_out.ptr + guard),
-                                                         C.c_uint32(n), C.c_uint32(w), C.c_uint32(h), C.c_void_p(stream)),
-          "svt_hip_txfm_spatial_distortion_batch")
-    out, guards = _unguard(d_out, np.uint64, guard, stream)
+    d_out = Guarded(lib, 16 * n, guard, fill, stream)
+    _call(lib, "svt_hip_txfm_spatial_distortion_batch", d_base, d_txfm_desc, d_src.ptr, d_out.ptr, n, w, h, stream=stream)
+    out, guards = d_out.read(np.uint64)
     return out.reshape(n, 2), guards
 
 
@@ -290,19 +272,15 @@ def txt_select_batch(lib, d_base, descs, d_txfm_desc, cost_descs, tables, d_txfm
     (d_rdoq_result may be None).  With mapping (0 or 1) the same through svt_hip_txt_select_batch_mapped.
     Returns (results as a record array of abi.TXT_RESULT_DTYPE, the guard bytes around them)."""
     n = len(descs)
-    tables = np.ascontiguousarray(tables, np.dtype(abi.RATE_TABLES_DTYPE)).reshape(-1)
-    d_desc, d_cdesc, d_tab = upload_descriptors(lib, descs, stream), upload_descriptors(lib, cost_descs, stream), DeviceBuffer(lib, tables.nbytes)
-    d_tab.upload(tables, stream)
-    d_out = _guarded(lib, C.sizeof(abi.TxtResult) * n, guard, fill, stream)
-    args = (C.c_void_p(d_base), C.c_void_p(d_desc.ptr), C.c_void_p(d_txfm_desc), C.c_void_p(d_cdesc.ptr), C.c_void_p(d_tab.ptr), C.c_uint32(len(tables)),
-            C.c_void_p(d_txfm_result), C.c_void_p(d_rdoq_result), C.c_void_p(d_distortion), C.c_void_p(d_cost), C.c_void_p(d_out.ptr + guard),
-            C.c_uint32(n_cand), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h))
+    d_desc, d_cdesc, (tables, d_tab) = upload_descriptors(lib, descs, stream), upload_descriptors(lib, cost_descs, stream), _tables(lib, tables, stream)
+    d_out = Guarded(lib, C.sizeof(abi.TxtResult) * n, guard, fill, stream)
+    args = (d_base, d_desc.ptr, d_txfm_desc, d_cdesc.ptr, d_tab.ptr, len(tables), d_txfm_result, d_rdoq_result, d_distortion, d_cost, d_out.ptr,
+            n_cand, n, w, h)
     if mapping is None:
-        rc = lib.svt_hip_txt_select_batch(*args, C.c_void_p(stream))
+        _call(lib, "svt_hip_txt_select_batch", *args, stream=stream)
     else:
-        rc = lib.svt_hip_txt_select_batch_mapped(*args, C.c_uint32(mapping), C.c_void_p(stream))
-    check(lib, rc, "svt_hip_txt_select_batch")
-    return _unguard(d_out, abi.TXT_RESULT_DTYPE, guard, stream)
+        _call(lib, "svt_hip_txt_select_batch_mapped", *args, mapping, stream=stream)
+    return d_out.read(abi.TXT_RESULT_DTYPE)
 
 
 def txt_search_batch(lib, d_base, txfm_descs, rdoq_descs, cost_descs, tables, descs, w, h, inverse=False, stream=None, guard=64, fill=0xA5):
@@ -312,22 +290,16 @@ def txt_search_batch(lib, d_base, txfm_descs, rdoq_descs, cost_descs, tables, de
     it no block measures spatial SSE or gets a reconstruction, whatever its descriptor says.
     Returns (results as a record array of abi.TXT_RESULT_DTYPE, the guard bytes around results and scratch)."""
     n, n_cand = len(descs), len(txfm_descs)
-    tables = np.ascontiguousarray(tables, np.dtype(abi.RATE_TABLES_DTYPE)).reshape(-1)
     d_tdesc, d_cdesc, d_desc = upload_descriptors(lib, txfm_descs, stream), upload_descriptors(lib, cost_descs, stream), upload_descriptors(lib, descs, stream)
     d_rdesc = upload_descriptors(lib, rdoq_descs, stream) if rdoq_descs is not None else None
-    d_tab = DeviceBuffer(lib, tables.nbytes)
-    d_tab.upload(tables, stream)
+    tables, d_tab = _tables(lib, tables, stream)
     need = lib.svt_hip_txt_search_scratch_bytes(n_cand, n)
-    sguard = 256
-    d_scratch = _guarded(lib, need, sguard, fill, stream)
-    d_out = _guarded(lib, C.sizeof(abi.TxtResult) * n, guard, fill, stream)
-    rc = lib.svt_hip_txt_search_batch(C.c_void_p(d_base), C.c_void_p(d_tdesc.ptr), C.c_void_p(d_rdesc.ptr if d_rdesc else None), C.c_void_p(d_cdesc.ptr),
-                                      C.c_void_p(d_tab.ptr), C.c_uint32(len(tables)), C.c_void_p(d_desc.ptr), C.c_void_p(d_scratch.ptr + sguard),
-                                      C.c_size_t(need), C.c_void_p(d_out.ptr + guard), C.c_uint32(n_cand), C.c_uint32(n), C.c_uint32(w), C.c_uint32(h),
-                                      C.c_uint32(abi.TXT_SEARCH_INVERSE if inverse else 0), C.c_void_p(stream))
-    check(lib, rc, "svt_hip_txt_search_batch")
-    out, guards = _unguard(d_out, abi.TXT_RESULT_DTYPE, guard, stream)
-    return out, np.concatenate([guards, _unguard(d_scratch, np.uint8, sguard, stream)[1]])
+    d_scratch = Guarded(lib, need, 256, fill, stream)
+    d_out = Guarded(lib, C.sizeof(abi.TxtResult) * n, guard, fill, stream)
+    _call(lib, "svt_hip_txt_search_batch", d_base, d_tdesc.ptr, d_rdesc.ptr if d_rdesc else None, d_cdesc.ptr, d_tab.ptr, len(tables), d_desc.ptr,
+          d_scratch.ptr, need, d_out.ptr, n_cand, n, w, h, abi.TXT_SEARCH_INVERSE if inverse else 0, stream=stream)
+    out, guards = d_out.read(abi.TXT_RESULT_DTYPE)
+    return out, np.concatenate([guards, d_scratch.read(np.uint8)[1]])
 
 
 class DeviceCdefPick:
@@ -341,7 +313,7 @@ class DeviceCdefPick:
         self.workspace = DeviceBuffer(lib, lib.svt_hip_cdef_pick_workspace_bytes(n_fb, n_strengths))
         for b in (self.result, self.fb_gi, self.fb_strength, self.workspace):
             b.fill(fill)
-        check(lib, lib.svt_hip_stream_sync(None), "svt_hip_stream_sync")
+        _call(lib, "svt_hip_stream_sync")
 
     def run(self, prm, d_mse, d_filt8x8, stream=None):
         return self.lib.svt_hip_cdef_pick_strengths(C.byref(prm), d_mse, d_filt8x8, self.result.ptr, self.fb_gi.ptr, self.fb_strength.ptr,
@@ -356,10 +328,7 @@ class DeviceCdefPick:
 def warp_batch(lib, descs, d_filter, stream=None, sync=True):
     """svt_hip_warp_batch over a list of abi.WarpDesc (one launch); d_filter: device address of the [193][8] int16 filter table."""
     d_desc = upload_descriptors(lib, descs, stream)
-    check(lib, lib.svt_hip_warp_batch(C.c_void_p(d_desc.ptr), C.c_uint32(len(descs)), C.c_void_p(d_filter), C.c_void_p(stream)),
-          "svt_hip_warp_batch")
-    if sync:
-        check(lib, lib.svt_hip_stream_sync(C.c_void_p(stream)), "svt_hip_stream_sync")
+    _call(lib, "svt_hip_warp_batch", d_desc.ptr, len(descs), d_filter, stream=stream, sync=sync)
     return d_desc
 
 
@@ -377,16 +346,14 @@ def warp_error_batch(lib, job, candidates, stream=None, fill=0xA5):
     d_cand, d_res = DeviceBuffer(lib, cand.nbytes), DeviceBuffer(lib, C.sizeof(abi.WarpErrorResult) * len(cand))
     d_cand.upload(cand, stream)
     d_res.fill(fill, stream)
-    check(lib, lib.svt_hip_warp_error_batch(C.byref(job), C.c_void_p(d_cand.ptr), C.c_void_p(d_res.ptr), C.c_uint32(len(cand)),
-                                            C.c_void_p(stream)), "svt_hip_warp_error_batch")
+    _call(lib, "svt_hip_warp_error_batch", C.byref(job), d_cand.ptr, d_res.ptr, len(cand), stream=stream)
     return d_res.download(np.dtype(abi.WARP_ERROR_RESULT_DTYPE), (len(cand),), stream)
 
 
 def gm_refine(lib, job, wmmat, wmtype, n_refinements, best_frame_error, stream=None):
     """svt_hip_gm_refine: (wmmat[8] as a list, wmtype, error) after the hill climb."""
     mat, wt, err = (C.c_int32 * 8)(*wmmat), C.c_int32(wmtype), C.c_int64(0)
-    check(lib, lib.svt_hip_gm_refine(C.byref(job), mat, C.byref(wt), C.c_int32(n_refinements), C.c_int64(best_frame_error), C.byref(err),
-                                     C.c_void_p(stream)), "svt_hip_gm_refine")
+    _call(lib, "svt_hip_gm_refine", C.byref(job), mat, C.byref(wt), n_refinements, best_frame_error, C.byref(err), stream=stream)
     return list(mat), wt.value, err.value
 
 
@@ -419,9 +386,7 @@ def tpl_dispenser_frame(lib, job, workspace=None, stream=None, sync=True):
     if workspace is None:
         workspace = tpl_workspace(lib, job)
     job.workspace, job.workspace_bytes = workspace.ptr, workspace.nbytes
-    check(lib, lib.svt_hip_tpl_dispenser_frame(C.byref(job), stream), "svt_hip_tpl_dispenser_frame")
-    if sync:
-        check(lib, lib.svt_hip_stream_sync(stream), "svt_hip_stream_sync")
+    _call(lib, "svt_hip_tpl_dispenser_frame", C.byref(job), stream=stream, sync=sync)
     return workspace
 
 
@@ -446,9 +411,7 @@ def tf_filter_picture(lib, job, workspace=None, tot_blks=None, stream=None, sync
         tot_blks = DeviceBuffer(lib, 8)
         tot_blks.fill(0, stream)
     job.workspace, job.workspace_bytes, job.tot_blks = workspace.ptr, workspace.nbytes, tot_blks.ptr
-    check(lib, lib.svt_hip_tf_filter_picture(C.byref(job), stream), "svt_hip_tf_filter_picture")
-    if sync:
-        check(lib, lib.svt_hip_stream_sync(stream), "svt_hip_stream_sync")
+    _call(lib, "svt_hip_tf_filter_picture", C.byref(job), stream=stream, sync=sync)
     return workspace, tot_blks
 
 

@@ -17,9 +17,9 @@ for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "svt-av1-mod-by-patma
 
 import me_cases  # noqa: E402
 import pyorc  # noqa: E402
+from arena import GUARD as FILL  # noqa: E402  (a byte nobody writes keeps it on both sides; zeros would hide it)
 from svtav1_hip import abi, device, frames  # noqa: E402
 
-FILL = 0xA5     # a byte nobody writes keeps it on both sides; zeros would hide it
 SWITCH_BATCH = [("noise", 64, 64, 41), ("pan", 206, 142, 42), ("noise", 648, 360, 43)]
 
 

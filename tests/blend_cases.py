@@ -14,12 +14,13 @@ import os
 
 import numpy as np
 
+import arena
 import conv_cases as K
 from svtav1_hip import abi
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "inter_blend.npz")
 GUARD = 2            # guard rows above and below every block
-FILL = 0xA5          # guard rows and stride padding
+FILL = arena.GUARD   # guard rows and stride padding
 FULL_LIMIT = 4096    # expected blocks up to this many samples are kept in full, larger ones as sha256
 # BlockSize (definitions.h:773-794) of the sizes with wedges (svt_aom_get_wedge_bits_lookup == 4)
 WEDGE_BSIZE = {(8, 8): 3, (8, 16): 4, (16, 8): 5, (16, 16): 6, (16, 32): 7, (32, 16): 8, (32, 32): 9, (8, 32): 18, (32, 8): 19}

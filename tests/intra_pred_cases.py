@@ -21,11 +21,11 @@ import os
 
 import numpy as np
 
+from arena import GUARD, Arena, check_containment, rows
 from svtav1_hip import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "intra_pred.npz")
-FILL = 0xA5
 ORG = 16          # above[ORG + i] is above_ref[i] of an input array, left[ORG + i] is left_ref[i]
 EDGE_LEN = ORG + 144
 # TxSize order (definitions.h): tx_size_wide[] / tx_size_high[]
@@ -316,7 +316,7 @@ class RefIntraPred:
         return out
 
     def cfl(self, c, luma, pred):
-        """(dst [h][w], ac [h][CFL_BUF_LINE] int16 with FILL bytes outside the block) of a CfL case."""
+        """(dst [h][w], ac [h][CFL_BUF_LINE] int16 with GUARD bytes outside the block) of a CfL case."""
         luma, pred = np.ascontiguousarray(luma), np.ascontiguousarray(pred)
         buf = np.zeros((32, abi.CFL_BUF_LINE), np.int16)
         (self.sub16 if c.is16 else self.sub8)(luma.ctypes.data, 2 * c.w, buf.ctypes.data, 2 * c.w, 2 * c.h)
@@ -324,7 +324,7 @@ class RefIntraPred:
         self.sub_avg(buf.ctypes.data, c.w, c.h, (c.w * c.h) >> 1, log2[c.w] + log2[c.h])
         dst = np.zeros_like(pred)
         (self.cfl16 if c.is16 else self.cfl8)(buf.ctypes.data, pred.ctypes.data, c.w, dst.ctypes.data, c.w, c.alpha, c.bd, c.w, c.h)
-        ac = np.frombuffer(bytes([FILL]) * (c.h * abi.CFL_BUF_LINE * 2), np.int16).copy().reshape(c.h, abi.CFL_BUF_LINE)
+        ac = np.frombuffer(bytes([GUARD]) * (c.h * abi.CFL_BUF_LINE * 2), np.int16).copy().reshape(c.h, abi.CFL_BUF_LINE)
         ac[:, :c.w] = buf[:c.h, :c.w]
         return dst, ac
 
@@ -382,29 +382,16 @@ def check_against_golden(gold, blocks, cfl=None):
 
 
 # ---- device batches -----------------------------------------------------------------------------------------------------------
-class Arena:
-    """A host byte buffer that arrays are appended to at aligned offsets; it becomes one device buffer."""
+PACKED = dict(align=16, gap=0)        # how the neighbour arrays of a batch lie in their arena: 16-byte aligned, nothing between them
 
-    def __init__(self):
-        self.parts, self.size = [], 0
 
-    def add(self, arr, align=16, lead=0):
-        """Offset of arr's first byte; `lead` FILL bytes in front of it break the alignment on purpose."""
-        self.size = -(-self.size // align) * align + lead
-        off = self.size
-        self.parts.append((off, np.ascontiguousarray(arr).view(np.uint8).reshape(-1)))
-        self.size += self.parts[-1][1].size
-        return off
-
-    def bytes(self):
-        out = np.full(self.size + 64, FILL, np.uint8)
-        for off, a in self.parts:
-            out[off:off + a.size] = a
-        return out
+def input_arena():
+    """The arena of a batch's input arrays (add them with **PACKED): GUARD between and 64 bytes behind them"""
+    return Arena(fill=GUARD, tail=64)
 
 
 class OutLayout:
-    """Where the blocks of a batch go in one output buffer pre-filled with FILL: (offset, stride in samples) per block, with `extra`
+    """Where the blocks of a batch go in one output buffer pre-filled with GUARD: (offset, stride in samples) per block, with `extra`
     samples behind every row and `lead` bytes in front of the block."""
 
     def __init__(self):
@@ -427,14 +414,11 @@ class OutLayout:
         return np.ascontiguousarray(rows).view(dt).reshape(h, w)
 
     def untouched_outside(self, raw):
-        """Every byte that belongs to no block still holds FILL."""
-        mask = np.zeros(raw.size, bool)
-        for off, stride, w, h, itemsize in self.blocks:
-            idx = off + (np.arange(h)[:, None] * stride * itemsize + np.arange(w * itemsize)[None, :])
-            mask[idx.reshape(-1)] = True
-        return bool((raw[~mask] == FILL).all())
-
-
+        """Every byte that belongs to no block's rows still holds GUARD (check_containment raises where one does not)."""
+        regions = [(off, ((h - 1) * stride + w) * itemsize, f"block {k}") for k, (off, stride, w, h, itemsize) in enumerate(self.blocks)]
+        declared = [r for off, stride, w, h, itemsize in self.blocks for r in rows(off, stride * itemsize, w * itemsize, h)]
+        check_containment(np.full(raw.size, GUARD, np.uint8), raw, regions, declared, "the output buffer")
+        return True
 
 
 def pred_desc(c, above, left, dst, dst_stride, left_stride=1, inter=0, inter_stride=0):
@@ -453,14 +437,14 @@ class PredBatch:
     """Inputs, output layout and descriptors of a list of cases fed from neighbour arrays.  layout(k) -> (extra, lead) of block k."""
 
     def __init__(self, cases, layout=lambda k: ((0, 3, 8, 5)[k % 4], 0)):
-        self.cases, self.arena, self.out = cases, Arena(), OutLayout()
+        self.cases, self.arena, self.out = cases, input_arena(), OutLayout()
         self.rel = []
         for k, c in enumerate(cases):
             above, left, inter = case_inputs(c)
             size = 2 if c.is16 else 1
-            a = self.arena.add(above) + ORG * size
-            l = self.arena.add(left) + ORG * size
-            i = self.arena.add(inter) if inter is not None else None
+            a = self.arena.add(f"above {k}", above, **PACKED) + ORG * size
+            l = self.arena.add(f"left {k}", left, **PACKED) + ORG * size
+            i = self.arena.add(f"inter {k}", inter, **PACKED) if inter is not None else None
             extra, lead = layout(k)
             o, stride = self.out.add(c.w, c.h, size, extra, lead * size)
             self.rel.append((a, l, i, o, stride))

@@ -15,6 +15,7 @@ import numpy as np
 
 import tx_cases
 import txb_cost_cases as T
+from arena import PATTERN, Arena
 from svtav1_hip import abi
 from tx_cases import SIZES
 
@@ -604,17 +605,17 @@ class Block:
 # ------------------------------------------------------------------------------------------------ device input
 def batch(blocks, w, h, order=None, repeat=1):
     """The blocks of size w x h as one launch: (indices into blocks, arena image, transform descriptors, RDOQ descriptors, transform
-    results), the three as record arrays."""
+    results, the arena's named regions), the three as record arrays.  Every byte of the arena that is no input holds the pattern."""
     idx = [i for i, b in enumerate(blocks) if (b.c.w, b.c.h) == (w, h)]
     if order is not None:
         idx = [idx[k] for k in order(len(idx))]
     idx = idx * repeat
-    ab = tx_cases.Arena()
+    ab = Arena(fill=PATTERN)
     shared = {}
 
     def once(key, arr):
         if key not in shared:
-            shared[key] = ab.add(arr)
+            shared[key] = ab.add(f"{key[0]} {key[1]}", arr)
         return shared[key]
     tdescs = np.zeros(len(idx), abi.TXFM_DESC_DTYPE)
     descs = np.zeros(len(idx), abi.RDOQ_DESC_DTYPE)
@@ -622,7 +623,7 @@ def batch(blocks, w, h, order=None, repeat=1):
     for k, i in enumerate(idx):
         b, c = blocks[i], blocks[i].c
         d, r = tdescs[k], descs[k]
-        d["coeff_off"], d["qcoeff_off"], d["dqcoeff_off"] = ab.add(b.coeff), ab.add(b.q0), ab.add(b.dq0)
+        d["coeff_off"], d["qcoeff_off"], d["dqcoeff_off"] = ab.add(f"coeff of block {k}", b.coeff), ab.add(f"qcoeff of block {k}", b.q0), ab.add(f"dqcoeff of block {k}", b.dq0)
         d["residual_off"] = d["pred_off"] = d["recon_off"] = abi.NO_OFFSET
         d["iscan_off"] = once(("iscan", c.tx_type), b.iscan)
         d["qm_off"] = once(("qm", c.plane), b.qm) if c.qm else abi.NO_OFFSET
@@ -638,7 +639,7 @@ def batch(blocks, w, h, order=None, repeat=1):
         r["pic_bit_depth"] = c.pic_bd if c.pic_bd != c.bd or k % 2 else 0     # 0: the transform descriptor's
         r["flags"] = abi.RDOQ_PERFORM * c.perform | abi.RDOQ_FAST_MODE * c.fast | abi.RDOQ_SHARPNESS * c.sharp
         results[k]["three_quad_energy"], results[k]["eob"], results[k]["pad_"], results[k]["satd"] = 0x1234567800000000 + i, b.eob0, 0xBEEF, b.satd
-    return idx, ab.build(), tdescs, descs, results
+    return idx, ab.build(), tdescs, descs, results, ab.regions
 
 
 # ------------------------------------------------------------------------------------------------ the reference, where it was built

@@ -12,6 +12,7 @@ import os
 
 import numpy as np
 
+import arena
 from svtav1_hip import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -479,29 +480,20 @@ class Arena:
     behind them.  layout(i) -> (offset shift in bytes, extra stride) lets a test ask for unaligned pointers and odd strides."""
 
     def __init__(self, cases, layout=lambda i: (0, 0)):
-        self.cases, self.planes, chunks, at = cases, [], [], 0
+        self.cases, self.planes, ab = cases, [], arena.Arena(tail=64)
         for i, c in enumerate(cases):
             shift, extra = layout(i)
             entry = []
-            for plane in pictures(c):
+            for name, plane in zip(("src", "ref"), pictures(c)):
                 stride = plane.shape[1] + extra
                 buf = np.full((plane.shape[0], stride), 0x5A, np.uint8)
                 buf[:, :plane.shape[1]] = plane
-                at = ((at + 63) & ~63) + shift
+                at = ab.add(f"{name} of case {i}", buf, align=64, gap=0, skew=shift)
                 entry.append((at + BORDER * stride + BORDER, stride))
-                chunks.append((at, buf.reshape(-1)))
-                at += buf.size
             self.planes.append(entry)
         self.mvj, row, col = mv_cost_tables()
-        self.table_at = []
-        for t in (row, col):
-            at = (at + 63) & ~63
-            self.table_at.append(at - 4 * MV_LOW)     # the centre
-            chunks.append((at, t.view(np.uint8)))
-            at += t.nbytes
-        self.host = np.zeros(at + 64, np.uint8)
-        for o, b in chunks:
-            self.host[o:o + b.size] = b
+        self.table_at = [ab.add(name, t, align=64, gap=0) - 4 * MV_LOW for name, t in (("mvcost row", row), ("mvcost col", col))]     # the centres
+        self.host = ab.build()
 
     def job(self, base):
         j = abi.SubpelJob()

@@ -9,6 +9,7 @@ import pytest
 import blend_cases as B
 import conv_cases as K
 import pyorc
+from arena import GUARD, OnDevice
 from svtav1_hip import abi, device
 
 pytestmark = pytest.mark.gpu
@@ -35,20 +36,9 @@ def wedge_dev(hip, gold):
     return {k: b.ptr for k, b in bufs.items()}, bufs
 
 
-class OnDevice:
-    """Device copies of the host buffers (blend_cases.Buf) of a list of inputs."""
-
-    def __init__(self, hip, inputs):
-        self.bufs, self.ptrs = {}, {}
-        for inp in inputs:
-            for b in inp.buffers():
-                d = device.DeviceBuffer(hip, b.a.nbytes)
-                d.upload(b.a)
-                self.bufs[id(b)], self.ptrs[id(b)] = d, d.ptr
-
-    def fetch(self, buf):
-        """Overwrite the host buffer with its device copy."""
-        buf.a[:] = self.bufs[id(buf)].download(buf.a.dtype, buf.a.shape)
+def on_device(hip, inputs):
+    """Device copies of the host buffers of a list of inputs"""
+    return OnDevice(hip, [b for inp in inputs for b in inp.buffers()])
 
 
 # ---- 1. blends --------------------------------------------------------------------------------------------------------------
@@ -73,7 +63,7 @@ def check_blend(gold, ref, index, inp, dev):
 @pytest.mark.parametrize("index", range(len(B.BLEND_CASES)), ids=lambda i: B.BLEND_CASES[i][0])
 def test_blend_case(hip, gold, ref, index):
     inp = B.BlendInputs(B.BLEND_CASES[index], index, gold)
-    dev = OnDevice(hip, [inp])
+    dev = on_device(hip, [inp])
     device.blend_batch(hip, [inp.desc(dev.ptrs)])
     check_blend(gold, ref, index, inp, dev)
 
@@ -81,7 +71,7 @@ def test_blend_case(hip, gold, ref, index):
 def test_blend_all_cases_in_one_call(hip, gold, ref):
     """Mixed kinds, sizes and formats in one launch, with empty descriptors (w == 0 / h == 0) in between."""
     inputs = [B.BlendInputs(c, i, gold) for i, c in enumerate(B.BLEND_CASES)]
-    dev = OnDevice(hip, inputs)
+    dev = on_device(hip, inputs)
     descs = []
     for i, inp in enumerate(inputs):
         descs.append(inp.desc(dev.ptrs))
@@ -111,14 +101,14 @@ def check_search(gold, ref, indices, got):
 @pytest.mark.parametrize("index", range(len(B.SEARCH_CASES)), ids=lambda i: B.SEARCH_CASES[i][0])
 def test_search_case(hip, gold, ref, wedge_dev, index):
     inp = B.SearchInputs(B.SEARCH_CASES[index], index)
-    dev = OnDevice(hip, [inp])
+    dev = on_device(hip, [inp])
     got = device.compound_mask_search_batch(hip, [inp.desc(wedge_dev[0], dev.ptrs)])
     check_search(gold, ref, [index], got)
 
 
 def test_search_all_cases_in_one_call(hip, gold, ref, wedge_dev):
     inputs = [B.SearchInputs(c, i) for i, c in enumerate(B.SEARCH_CASES)]
-    dev = OnDevice(hip, inputs)
+    dev = on_device(hip, inputs)
     got = device.compound_mask_search_batch(hip, [inp.desc(wedge_dev[0], dev.ptrs) for inp in inputs])
     check_search(gold, ref, list(range(len(inputs))), got)
 
@@ -140,7 +130,7 @@ def test_convolve_then_masked_compound(hip, gold, ref, wedge_dev, index):
         for j in range(2):
             d_ref, d_cb = device.DeviceBuffer(hip, refs[j].nbytes), device.DeviceBuffer(hip, pw * ph * 2)
             d_ref.upload(refs[j])
-            d_cb.fill(0xA5)
+            d_cb.fill(GUARD)
             sx, sy, ti = phases[j]
             t = np.array(K.TABLES[B.PIPE_TABLES[ti]], np.int16)
             conv.append(abi.ConvolveDesc(d_ref.ptr + (8 * refs[j].shape[1] + 8) * px, scrap.ptr, refs[j].shape[1], pw, pw, ph,
@@ -149,12 +139,12 @@ def test_convolve_then_masked_compound(hip, gold, ref, wedge_dev, index):
             keep += [d_ref, d_cb]
             cbs.append(d_cb)
         d_dst = device.DeviceBuffer(hip, pw * ph * px)
-        d_dst.fill(0xA5)
+        d_dst.fill(GUARD)
         planes.append((pw, ph, cbs, d_dst))
     d_conv = device.upload_descriptors(hip, conv)
     device.check(hip, hip.svt_hip_convolve_batch(V(d_conv.ptr), len(conv), None), "svt_hip_convolve_batch")
     d_mask = device.DeviceBuffer(hip, w * h)
-    d_mask.fill(0xA5)
+    d_mask.fill(GUARD)
     if ctype == B.COMPOUND_WEDGE:
         mask_ptr, kind = wedge_dev[0][(w, h)] + (2 * widx + wsign) * w * h, abi.BLEND_D16
     else:
@@ -171,7 +161,7 @@ def test_convolve_then_masked_compound(hip, gold, ref, wedge_dev, index):
     if ctype == B.COMPOUND_DIFFWTD:
         got["mask"] = d_mask.download(np.uint8, (h, w))
     else:
-        assert (d_mask.download(np.uint8, (h, w)) == 0xA5).all()
+        assert (d_mask.download(np.uint8, (h, w)) == GUARD).all()
     wants = [{k: gold[f"pipe_{name}_{k}"] for k in got}] + ([B.RefPipe(ref).run(inp)] if ref is not None else [])
     for want in wants:
         assert set(want) == set(got)
@@ -213,7 +203,7 @@ def test_blend_skips_out_of_range_descriptors(hip, gold, ref):
     good_idx = sorted({i for _, i, _ in bad})
     good = [B.BlendInputs(B.BLEND_CASES[i], i, gold) for i in good_idx]
     victims = [B.BlendInputs(B.BLEND_CASES[i], i, gold) for _, i, _ in bad]
-    dev = OnDevice(hip, good + victims)
+    dev = on_device(hip, good + victims)
     descs = []
     for k, ((what, _, mutate), inp) in enumerate(zip(bad, victims)):
         d = inp.desc(dev.ptrs)
@@ -240,7 +230,7 @@ def test_search_skips_out_of_range_descriptors(hip, gold, ref, wedge_dev):
     inputs = [B.SearchInputs(B.SEARCH_CASES[i], i) for i in idx]
     big = next(i for i, c in enumerate(B.SEARCH_CASES) if (c[1], c[2]) == (64, 64))
     inputs.append(B.SearchInputs(B.SEARCH_CASES[big], big))
-    dev = OnDevice(hip, inputs)
+    dev = on_device(hip, inputs)
     descs = [inp.desc(wedge_dev[0], dev.ptrs) for inp in inputs]
     bad = []
     for what, k, name, value, status in (("w", 0, "w", 12, 2), ("h", 1, "h", 256, 2), ("src", 2, "src", None, 2), ("pred1", 3, "pred1", None, 2),

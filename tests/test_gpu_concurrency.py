@@ -25,6 +25,7 @@ import test_lf_oracle as TL
 import tf_picture_cases as tpc
 import tpl_cases as TP
 import tx_cases as T
+from arena import GUARD
 from lf_cases import BS, HB, VB
 from svtav1_hip import abi, device, frames
 from test_gpu_lf import deblock_inputs
@@ -183,7 +184,7 @@ class IntraCase:
         got = self.out.download()
         if "pred" in got:   # predictions of unsearched modes and blocks stay at the 0xA5 fill; the oracle leaves them at 0
             end, searched = self.case[4], got["best_mode"] != I.NOT_SEARCHED
-            assert (got["pred"][searched][:, end + 1:] == 0xA5).all() and (got["pred"][~searched] == 0xA5).all(), (what, self.case[0])
+            assert (got["pred"][searched][:, end + 1:] == GUARD).all() and (got["pred"][~searched] == GUARD).all(), (what, self.case[0])
             got["pred"][~searched] = 0
             got["pred"][:, :, end + 1:] = 0
         I.check_against_golden(self.gold, self.case[0], got)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import conv_cases as K
+from arena import GUARD
 from lf_cases import P, V
 from svtav1_hip import abi, device
 
@@ -170,7 +171,6 @@ def test_tier_b_compound_batch(hip, orc, bd, is16):
 
 
 # ---- extended net: every table / shape / phase / kernel length, adversarial planes, the Tier B contract ------------------------
-CANARY = 0xA5
 BDS = [(8, 0), (10, 1), (12, 1)]
 
 
@@ -278,7 +278,7 @@ class Batch:
 
 
 def _canary(shape, dtype):
-    return np.full(shape, CANARY * (0x101 if np.dtype(dtype).itemsize == 2 else 1), dtype)
+    return np.full(shape, GUARD * (0x101 if np.dtype(dtype).itemsize == 2 else 1), dtype)
 
 
 def _three_launches(hip, orc, cases, src, src_at, slot, strides):
@@ -413,7 +413,7 @@ def test_tier_b_containment(hip, orc, bd, is16):
             b.run()
             got, got_cb = dst.pull(), cb.pull()
             assert (got[~inside] == dst.host[0, 0]).all(), (mode, comp, "dst outside the blocks")
-            assert (got_cb[:, :dstride][~inside] == 0xA5A5).all() and (got_cb[:, dstride:] == 0xA5A5).all(), (mode, comp, "cbuf outside the blocks")
+            assert (got_cb[:, :dstride][~inside] == GUARD * 0x101).all() and (got_cb[:, dstride:] == GUARD * 0x101).all(), (mode, comp, "cbuf outside the blocks")
             assert np.array_equal(got, dst.host) and np.array_equal(got_cb, cb.host), (mode, comp)
             if comp == 1:
                 assert (got == got[0, 0]).all(), (mode, "compound 1 wrote dst")

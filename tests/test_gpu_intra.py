@@ -8,6 +8,7 @@ import pytest
 
 import intra_cases as I
 import pyorc
+from arena import GUARD
 from svtav1_hip import abi, device
 
 pytestmark = pytest.mark.gpu
@@ -60,8 +61,8 @@ def test_intra_search_case(hip, gold, oracle, case):
     end = case[4]
     searched = got["best_mode"] != I.NOT_SEARCHED
     assert (got["mode_cost"][:, :, end + 1:] == I.INT64_MAX).all()
-    assert (got["pred"][searched][:, end + 1:] == 0xA5).all()
-    assert (got["pred"][~searched] == 0xA5).all()
+    assert (got["pred"][searched][:, end + 1:] == GUARD).all()
+    assert (got["pred"][~searched] == GUARD).all()
     got["pred"][~searched] = 0  # the oracle leaves the predictions of blocks it does not search at 0
     got["pred"][:, :, end + 1:] = 0
     check(gold, oracle, case, plane, got)
@@ -117,7 +118,7 @@ def test_intra_search_bad_parameter(hip, what, mutate):
     device.check(hip, hip.svt_hip_stream_sync(None), "sync")
     for _, _, _, out in keep:
         for k, v in out.download().items():
-            assert (v.view(np.uint8) == 0xA5).all(), (what, k)
+            assert (v.view(np.uint8) == GUARD).all(), (what, k)
 
 
 def test_intra_search_bad_job_array(hip):

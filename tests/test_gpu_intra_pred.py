@@ -9,6 +9,7 @@ import pytest
 import blend_cases as B
 import intra_pred_cases as P
 import pyorc
+from arena import GUARD
 from svtav1_hip import abi, device
 
 pytestmark = pytest.mark.gpu
@@ -33,13 +34,13 @@ def on_device(hip, host):
 
 def filled(hip, nbytes):
     d = device.DeviceBuffer(hip, nbytes)
-    d.fill(P.FILL)
+    d.fill(GUARD)
     return d
 
 
 def run_batch(hip, batch, order=None, waves=None):
     """The output buffer of a PredBatch after one call over its descriptors (in `order`)."""
-    d_in, d_out = on_device(hip, batch.arena.bytes()), filled(hip, batch.out.nbytes())
+    d_in, d_out = on_device(hip, batch.arena.build()), filled(hip, batch.out.nbytes())
     descs = batch.descs(d_in.ptr, d_out.ptr)
     device.intra_predict_batch(hip, descs if order is None else descs[order], waves_per_workgroup=waves)
     return d_out.download(np.uint8, (batch.out.nbytes(),))
@@ -112,7 +113,7 @@ def test_edges_read_straight_from_a_plane(hip, orc):
     rng = np.random.default_rng(77)
     planes = {is16: rng.integers(0, 1024 if is16 else 256, (rows, stride)).astype(P.sample_type(is16)) for is16 in (0, 1)}
     d_planes = {k: on_device(hip, p) for k, p in planes.items()}
-    arena, out_a, out_b = P.Arena(), P.OutLayout(), P.OutLayout()
+    arena, out_a, out_b = P.input_arena(), P.OutLayout(), P.OutLayout()
     rel, inputs = [], []
     for k, c in enumerate(cases):
         x, y, size, p = 5 + 3 * (k % 7), 3 + 2 * (k % 11), 2 if c.is16 else 1, planes[c.is16]
@@ -120,9 +121,10 @@ def test_edges_read_straight_from_a_plane(hip, orc):
         above[P.ORG - 1:P.ORG + 2 * c.w] = p[y - 1, x - 1:x + 2 * c.w]
         left[P.ORG:P.ORG + 2 * c.h] = p[y:y + 2 * c.h, x - 1]
         inputs.append((above, left))
-        rel.append((((y - 1) * stride + x) * size, (y * stride + x - 1) * size, arena.add(above) + P.ORG * size, arena.add(left) + P.ORG * size,
+        rel.append((((y - 1) * stride + x) * size, (y * stride + x - 1) * size,
+                    arena.add(f"above {k}", above, **P.PACKED) + P.ORG * size, arena.add(f"left {k}", left, **P.PACKED) + P.ORG * size,
                     out_a.add(c.w, c.h, size, 3)[0], out_b.add(c.w, c.h, size, 3)[0]))
-    d_in, d_a, d_b = on_device(hip, arena.bytes()), filled(hip, out_a.nbytes()), filled(hip, out_b.nbytes())
+    d_in, d_a, d_b = on_device(hip, arena.build()), filled(hip, out_a.nbytes()), filled(hip, out_b.nbytes())
     descs = np.zeros(2 * len(cases), P.DESC_DTYPE)
     for k, (c, (pa, pl, aa, al, oa, ob)) in enumerate(zip(cases, rel)):
         descs[2 * k] = P.pred_desc(c, d_planes[c.is16].ptr + pa, d_planes[c.is16].ptr + pl, d_a.ptr + oa, c.w + 3, stride)
@@ -162,7 +164,7 @@ def test_large_batch(hip, whole):
     picked = [next(i for i, c in want if (c.w, c.h) == s and c.mode == m) for s, m in (((4, 4), 0), ((8, 8), 3), ((4, 4), 12), ((8, 8), 5), ((4, 4), 9))]
     n, slot = 300001, 128
     batch = P.PredBatch([P.CASES[i] for i in picked])
-    d_in, d_out = on_device(hip, batch.arena.bytes()), filled(hip, n * slot)
+    d_in, d_out = on_device(hip, batch.arena.build()), filled(hip, n * slot)
     base = batch.descs(d_in.ptr, 0)
     descs = base[np.arange(n) % len(picked)]
     descs["dst"] = d_out.ptr + np.arange(n, dtype=np.uint64) * slot
@@ -170,7 +172,7 @@ def test_large_batch(hip, whole):
     device.intra_predict_batch(hip, descs)
     raw = d_out.download(np.uint8, (n, slot))
     for j, i in enumerate(picked):
-        expect = np.full(slot, P.FILL, np.uint8)
+        expect = np.full(slot, GUARD, np.uint8)
         expect[:blocks[i].nbytes] = blocks[i].view(np.uint8).reshape(-1)
         assert (raw[j::len(picked)] == expect).all(), (j, P.CASES[i])
 
@@ -186,7 +188,7 @@ def test_host_argument_checks(hip):
     assert b"svt_hip_cfl_predict_batch" in hip.svt_hip_last_error()
     assert hip.svt_hip_cfl_predict_batch(V(d.ptr), 0, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
     device.check(hip, hip.svt_hip_stream_sync(None), "sync")
-    assert (d.download(np.uint8, (4096,)) == P.FILL).all()   # nothing was launched over the "descriptors"
+    assert (d.download(np.uint8, (4096,)) == GUARD).all()   # nothing was launched over the "descriptors"
 
 
 INVALID = [("shape 12 x 8", "dr", {"w": 12}), ("shape 64 x 8", "dr", {"w": 64}), ("shape 8 x 2", "dr", {"h": 2}), ("mode 13", "dr", {"mode": 13}),
@@ -209,7 +211,7 @@ def test_invalid_descriptors_are_skipped(hip, whole):
     for _, which, _ in INVALID:
         idx += [base["dr"], base[which], base["dc"]]
     batch = P.PredBatch([P.CASES[i] for i in idx], layout=lambda k: (0, 0))
-    d_in, d_out = on_device(hip, batch.arena.bytes()), filled(hip, batch.out.nbytes())
+    d_in, d_out = on_device(hip, batch.arena.build()), filled(hip, batch.out.nbytes())
     descs = batch.descs(d_in.ptr, d_out.ptr)
     for k, (what, _, change) in enumerate(INVALID):
         for name, value in change.items():
@@ -218,7 +220,7 @@ def test_invalid_descriptors_are_skipped(hip, whole):
     got = batch.blocks(d_out.download(np.uint8, (batch.out.nbytes(),)))
     for k, (what, which, change) in enumerate(INVALID):
         assert np.array_equal(got[3 * k], blocks[base["dr"]]) and np.array_equal(got[3 * k + 2], blocks[base["dc"]]), (what, "a neighbour")
-        assert (got[3 * k + 1] == P.FILL).all(), (what, "was not skipped")
+        assert (got[3 * k + 1] == GUARD).all(), (what, "was not skipped")
 
 
 # ---- 6. inter-intra ---------------------------------------------------------------------------------------------------------------
@@ -241,7 +243,7 @@ def test_wedge_interintra_through_the_blend(hip, orc, w, h, bd, is16):
     above, left, inter = P.case_inputs(c)
     plain = c._replace(ii_mode=-1)
     batch = P.PredBatch([plain], layout=lambda k: (0, 0))
-    d_in, d_intra = on_device(hip, batch.arena.bytes()), filled(hip, batch.out.nbytes())
+    d_in, d_intra = on_device(hip, batch.arena.build()), filled(hip, batch.out.nbytes())
     keep = device.intra_predict_batch(hip, batch.descs(d_in.ptr, d_intra.ptr), sync=False)
     wedge_index, wedge_sign = 5, 1
     mask = np.load(B.GOLD)[f"wedge_{w}x{h}"][2 * wedge_index + wedge_sign]
@@ -267,16 +269,16 @@ def test_wedge_interintra_through_the_blend(hip, orc, w, h, bd, is16):
 # ---- 7. CfL ---------------------------------------------------------------------------------------------------------------------
 def test_cfl_cases(hip, gold, orc):
     """Prediction and ac_out of every CfL case in one call (test_cfl_alpha_search runs without ac_out)."""
-    arena, out = P.Arena(), P.OutLayout()
+    arena, out = P.input_arena(), P.OutLayout()
     rel = []
     for k, c in enumerate(P.CFL_CASES):
         luma, pred = P.cfl_inputs(c)
         size, extra = 2 if c.is16 else 1, (0, 2, 8, 5)[k % 4]
         lp = np.full((2 * c.h, 2 * c.w + extra), 0, luma.dtype)
         lp[:, :2 * c.w] = luma
-        rel.append((arena.add(lp), 2 * c.w + extra, arena.add(pred), out.add(c.w, c.h, size, extra)[0], c.w + extra,
+        rel.append((arena.add(f"luma {k}", lp, **P.PACKED), 2 * c.w + extra, arena.add(f"pred {k}", pred, **P.PACKED), out.add(c.w, c.h, size, extra)[0], c.w + extra,
                     out.add(abi.CFL_BUF_LINE, c.h, 2)[0]))
-    d_in, d_out = on_device(hip, arena.bytes()), filled(hip, out.nbytes())
+    d_in, d_out = on_device(hip, arena.build()), filled(hip, out.nbytes())
     descs = np.zeros(len(rel), P.CFL_DESC_DTYPE)
     for k, (c, (lu, ls, pr, ds, dstride, ac)) in enumerate(zip(P.CFL_CASES, rel)):
         descs[k] = P.cfl_desc(c, d_in.ptr + lu, d_in.ptr + pr, d_out.ptr + ds, d_out.ptr + ac, ls, c.w, dstride)
@@ -323,6 +325,6 @@ def test_cfl_invalid_descriptors_are_skipped(hip, gold):
     got = d_out.download(pred.dtype, (len(descs), c.h, c.w))
     for k in range(len(descs)):
         if k % 2:
-            assert (got[k].view(np.uint8) == P.FILL).all(), bad[k // 2]
+            assert (got[k].view(np.uint8) == GUARD).all(), bad[k // 2]
         else:
             assert np.array_equal(got[k], gold["cfl_alpha_search"][16 + 5])

@@ -9,6 +9,7 @@ import pytest
 import rdoq_cases as R
 import tx_cases
 import txb_cost_cases as T
+from arena import GUARD, PATTERN, Arena, check_containment, rows
 from svtav1_hip import abi, device
 
 pytestmark = pytest.mark.gpu
@@ -38,7 +39,7 @@ def launch(hip, gold, arena, tdescs, descs, results, w, h, mapping=None):
     d_res = device.upload_descriptors(hip, results)
     d_arena.upload(arena)
     out, guard = device.rdoq_batch(hip, d_arena.ptr, d_tdesc.ptr, descs, gold.tables, d_res.ptr, w, h, mapping=mapping)
-    assert (guard == 0xA5).all(), "bytes around d_out were written"
+    assert (guard == GUARD).all(), "bytes around d_out were written"
     return d_arena.download(np.uint8, (arena.nbytes,)), out, d_res.download(np.dtype(abi.TXFM_RESULT_DTYPE), (len(results),))
 
 
@@ -46,8 +47,8 @@ def i32(buf, off, n):
     return buf[int(off):int(off) + 4 * n].view(np.int32)
 
 
-def check(gold, blocks, idx, arena, tdescs, results, got_arena, out, got_results):
-    want_arena = arena.copy()
+def check(gold, blocks, idx, arena, regions, tdescs, results, got_arena, out, got_results):
+    declared = []
     for k, i in enumerate(idx):
         b, d, n = blocks[i], tdescs[k], len(blocks[i].q)
         q, dq = i32(got_arena, d["qcoeff_off"], n), i32(got_arena, d["dqcoeff_off"], n)
@@ -56,9 +57,8 @@ def check(gold, blocks, idx, arena, tdescs, results, got_arena, out, got_results
         assert (R.digest(q), R.digest(dq)) == (gold.q_digest[i], gold.dq_digest[i]), ("digest", i, b.c)
         assert (int(out["eob"][k]), int(out["cul_level"][k]), int(out["path"][k])) == (b.eob, b.cul, b.path), ("result", i, b.c, out[k])
         assert (b.eob, b.cul, b.path) == (gold.eob[i], gold.cul_level[i], gold.path[i])
-        i32(want_arena, d["qcoeff_off"], n)[:] = b.q
-        i32(want_arena, d["dqcoeff_off"], n)[:] = b.dq
-    assert np.array_equal(got_arena, want_arena), "the arena was written outside qcoeff / dqcoeff"
+        declared += [(int(d["qcoeff_off"]), 4 * n), (int(d["dqcoeff_off"]), 4 * n)]
+    check_containment(arena, got_arena, regions, declared, "svt_hip_rdoq_batch")
     want_results = results.copy()
     want_results["eob"] = [blocks[i].eob for i in idx]     # an unflagged block keeps the eob it came with: the restatement's too
     assert got_results.tobytes() == want_results.tobytes(), "d_txfm_result: only eob may change"
@@ -68,18 +68,18 @@ def check(gold, blocks, idx, arena, tdescs, results, got_arena, out, got_results
 def test_rdoq_matches_reference(hip, gold, blocks, w, h):
     """Every case of the size in one launch, with every work split the size has: both arrays, eob, cul_level and path as the
     restatement (pinned to the reference) has them, the digests of the fixture, eob handed on in d_txfm_result, nothing else written."""
-    idx, arena, tdescs, descs, results = R.batch(blocks, w, h)
+    idx, arena, tdescs, descs, results, regions = R.batch(blocks, w, h)
     assert len(idx) >= 40
     for mapping in mappings(w, h):
-        check(gold, blocks, idx, arena, tdescs, results, *launch(hip, gold, arena, tdescs, descs, results, w, h, mapping))
+        check(gold, blocks, idx, arena, regions, tdescs, results, *launch(hip, gold, arena, tdescs, descs, results, w, h, mapping))
 
 
 @pytest.mark.parametrize("w, h", [(4, 4), (8, 4), (8, 8), (16, 16), (32, 32), (64, 16)], ids=lambda v: str(v))
 def test_reversed_order(hip, gold, blocks, w, h):
     """The same descriptors in reversed order give the same results: no block depends on its place in the wave or the batch."""
-    idx, arena, tdescs, descs, results = R.batch(blocks, w, h, order=lambda n: range(n - 1, -1, -1))
+    idx, arena, tdescs, descs, results, regions = R.batch(blocks, w, h, order=lambda n: range(n - 1, -1, -1))
     for mapping in mappings(w, h)[1:]:
-        check(gold, blocks, idx, arena, tdescs, results, *launch(hip, gold, arena, tdescs, descs, results, w, h, mapping))
+        check(gold, blocks, idx, arena, regions, tdescs, results, *launch(hip, gold, arena, tdescs, descs, results, w, h, mapping))
 
 
 @pytest.mark.parametrize("w, h, mapping", [(4, 4, 0), (4, 4, 1), (4, 4, 2), (8, 8, 0), (8, 8, 1)], ids=lambda v: str(v))
@@ -90,7 +90,7 @@ def test_more_blocks_than_one_pass_of_the_grid(hip, gold, blocks, w, h, mapping)
     the arena of the first."""
     n, compute_units = w * h, 320                            # an MI355X has 256; the margin keeps the test meaningful on a larger part
     per_pass = compute_units * 16 * (64 if mapping == 2 else 64 // min(n, 64))
-    idx, arena, tdescs, descs, results = R.batch(blocks, w, h)
+    idx, arena, tdescs, descs, results, regions = R.batch(blocks, w, h)
     repeat = per_pass // len(idx) + 2
     nb = len(idx) * repeat
     packed = np.tile(np.stack([np.stack([blocks[i].coeff, blocks[i].q0, blocks[i].dq0]) for i in idx]), (repeat, 1, 1))   # [nb][3][n]
@@ -100,7 +100,7 @@ def test_more_blocks_than_one_pass_of_the_grid(hip, gold, blocks, w, h, mapping)
     tdescs["coeff_off"], tdescs["qcoeff_off"], tdescs["dqcoeff_off"] = at, at + np.uint64(4 * n), at + np.uint64(8 * n)
     got, out, got_results = launch(hip, gold, big, tdescs, descs, results, w, h, mapping)
     want = np.tile(np.stack([np.stack([blocks[i].coeff, blocks[i].q, blocks[i].dq]) for i in idx]), (repeat, 1, 1))
-    assert np.array_equal(got[:arena.nbytes], arena)
+    check_containment(arena, got[:arena.nbytes], regions, [], "svt_hip_rdoq_batch_mapped")
     bad = np.nonzero((got[arena.nbytes:].view(np.int32).reshape(nb, 3, n) != want).any(axis=(1, 2)))[0]
     assert bad.size == 0, (bad[:8], [blocks[idx[k % len(idx)]].c for k in bad[:2]])
     for field, attr in (("eob", "eob"), ("cul_level", "cul"), ("path", "path")):
@@ -114,7 +114,7 @@ def test_out_of_range_fields_are_clamped(hip, gold, blocks, w, h):
     """include/svt_hip_txfm.h: a table index beyond n_tables, contexts beyond their tables and an eob above the retained count are
     clamped, iscan values are reduced modulo the retained count.  Each is given where the clamped value is the case's own, so the
     results are the restatement's."""
-    idx, arena, tdescs, descs, results = R.batch(blocks, w, h)
+    idx, arena, tdescs, descs, results, regions = R.batch(blocks, w, h)
     n = min(w, 32) * min(h, 32)
     cs = [blocks[i].c for i in idx]
     hit = dict(table=0, skip=0, sign=0, eob=0)
@@ -131,19 +131,20 @@ def test_out_of_range_fields_are_clamped(hip, gold, blocks, w, h):
     for off in {int(d["iscan_off"]) for d in tdescs}:      # iscan + a multiple of n that keeps it a positive int16
         arena[off:off + 2 * n].view(np.int16)[:] += np.int16((16384 // n) * n)
     for mapping in mappings(w, h):
-        check(gold, blocks, idx, arena, tdescs, results, *launch(hip, gold, arena, tdescs, descs, results, w, h, mapping))
+        check(gold, blocks, idx, arena, regions, tdescs, results, *launch(hip, gold, arena, tdescs, descs, results, w, h, mapping))
 
 
 @pytest.mark.parametrize("w, h", [(4, 8), (16, 16), (32, 64)], ids=lambda v: str(v))
 def test_unflagged_blocks_are_left_alone(hip, gold, blocks, w, h):
     """Without SVT_HIP_RDOQ_PERFORM a block keeps its arrays and its eob in d_txfm_result whatever else its descriptor says; it gets
     cul_level, and an eob above the retained count is clamped in d_out only."""
-    idx, arena, tdescs, descs, results = R.batch(blocks, w, h)
+    idx, arena, tdescs, descs, results, regions = R.batch(blocks, w, h)
     descs["flags"] &= ~np.uint8(abi.RDOQ_PERFORM)
     n = min(w, 32) * min(h, 32)
     results["eob"][::5] = n + 7
     got_arena, out, got_results = launch(hip, gold, arena, tdescs, descs, results, w, h)
-    assert np.array_equal(got_arena, arena) and got_results.tobytes() == results.tobytes()
+    check_containment(arena, got_arena, regions, [], "svt_hip_rdoq_batch")
+    assert got_results.tobytes() == results.tobytes()
     for k, i in enumerate(idx):
         b = blocks[i]
         eob = min(int(results["eob"][k]), n)
@@ -155,7 +156,7 @@ def test_unflagged_blocks_are_left_alone(hip, gold, blocks, w, h):
 def test_zero_at_the_last_position_is_refused(hip, gold, blocks, w, h):
     """The reference asserts qcoeff[scan[eob - 1]] != 0 at the start of the trellis.  A block that breaks it keeps arrays and eob,
     gets cul_level and PATH_TRELLIS | PATH_BAD_EOB (include/svt_hip_txfm.h); its neighbours in the launch are not disturbed."""
-    idx, arena, tdescs, descs, results = R.batch(blocks, w, h)
+    idx, arena, tdescs, descs, results, regions = R.batch(blocks, w, h)
     broken = []
     for k, i in enumerate(idx):
         b = blocks[i]
@@ -177,6 +178,8 @@ def test_zero_at_the_last_position_is_refused(hip, gold, blocks, w, h):
         else:
             assert np.array_equal(i32(got_arena, d["qcoeff_off"], n), b.q) and np.array_equal(i32(got_arena, d["dqcoeff_off"], n), b.dq), (i, b.c)
             assert (int(out["eob"][k]), int(out["cul_level"][k]), int(out["path"][k])) == (b.eob, b.cul, b.path), (i, b.c)
+    check_containment(arena, got_arena, regions, [(int(d[f]), 4 * len(blocks[i].q)) for d, i in zip(tdescs, idx) for f in ("qcoeff_off", "dqcoeff_off")],
+                      "svt_hip_rdoq_batch_mapped")
 
 
 @pytest.mark.parametrize("w, h", [(4, 4), (16, 8), (16, 64), (64, 64)], ids=lambda v: str(v))
@@ -188,8 +191,8 @@ def test_chain_of_five_launches(hip, orc, gold, w, h):
     iw, ih = T.retained(w, h)
     n, n_tb, ls = iw * ih, 9, T.tx_scale(w, h)
     types = T.size_types(w, h)
-    ab = tx_cases.Arena()
-    iscan_off = {t: ab.add(gold.iscan(w, h, t)) for t in types}
+    ab = Arena(fill=PATTERN)
+    iscan_off = {t: ab.add(f"iscan {t}", gold.iscan(w, h, t)) for t in types}
     fwd, inv = np.zeros(n_tb, abi.TXFM_DESC_DTYPE), np.zeros(n_tb, abi.TXFM_DESC_DTYPE)
     rdescs, cdescs = np.zeros(n_tb, abi.RDOQ_DESC_DTYPE), np.zeros(n_tb, abi.TXB_COST_DESC_DTYPE)
     want = []
@@ -206,9 +209,10 @@ def test_chain_of_five_launches(hip, orc, gold, w, h):
             res[:] = 0                                  # eob 0
         pred16 = rng.integers(0, 1 << bd, size=(h, w + 2)).astype(np.uint16)
         d = fwd[i]
-        d["residual_off"], d["residual_stride"] = ab.add(res), w + 5
-        d["coeff_off"], d["qcoeff_off"], d["dqcoeff_off"] = ab.add(nbytes=n * 4), ab.add(nbytes=n * 4), ab.add(nbytes=n * 4)
-        d["pred_off"], d["recon_off"] = ab.add(pred16 if pix16 else pred16.astype(np.uint8)), ab.add(nbytes=h * (w + 4) * (2 if pix16 else 1))
+        d["residual_off"], d["residual_stride"] = ab.add(f"residual {i}", res), w + 5
+        d["coeff_off"], d["qcoeff_off"], d["dqcoeff_off"] = ab.add(f"coeff {i}", nbytes=n * 4), ab.add(f"qcoeff {i}", nbytes=n * 4), ab.add(f"dqcoeff {i}", nbytes=n * 4)
+        d["pred_off"] = ab.add(f"pred {i}", pred16 if pix16 else pred16.astype(np.uint8))
+        d["recon_off"] = ab.add(f"recon {i}", nbytes=h * (w + 4) * (2 if pix16 else 1))
         d["pred_stride"], d["recon_stride"] = w + 2, w + 4
         d["iscan_off"], d["qm_off"], d["iqm_off"] = iscan_off[tt], abi.NO_OFFSET, abi.NO_OFFSET
         d["zbin"], d["round"], d["quant"], d["quant_shift"], d["dequant"] = qt["zbin"][:2], qt["round_fp"][:2], qt["quant_fp"][:2], qt["qshift"][:2], qt["dequant"][:2]
@@ -256,11 +260,11 @@ def test_chain_of_five_launches(hip, orc, gold, w, h):
                                 device.DeviceBuffer(hip, 16 * n_tb))
     device.check(hip, hip.svt_hip_txfm_quant_batch(V(d_arena.ptr), V(d_fwd.ptr), V(d_res.ptr), n_tb, w, h, None), "svt_hip_txfm_quant_batch")
     out, guard = device.rdoq_batch(hip, d_arena.ptr, d_fwd.ptr, rdescs, gold.tables, d_res.ptr, w, h)
-    assert (guard == 0xA5).all()
+    assert (guard == GUARD).all()
     device.check(hip, hip.svt_hip_txfm_quant_batch(V(d_arena.ptr), V(d_inv.ptr), V(d_res_inv.ptr), n_tb, w, h, None), "svt_hip_txfm_quant_batch (INV)")
     device.check(hip, hip.svt_hip_txfm_distortion_batch(V(d_arena.ptr), V(d_fwd.ptr), V(d_dist.ptr), n_tb, w, h, None), "svt_hip_txfm_distortion_batch")
     cost, guard = device.txb_cost_batch(hip, d_arena.ptr, cdescs, gold.tables, w, h, d_txfm_result=d_res.ptr, d_distortion=d_dist.ptr)
-    assert (guard == 0xA5).all()
+    assert (guard == GUARD).all()
     got = d_arena.download(np.uint8, (arena.nbytes,))
     res = d_res.download(np.dtype(abi.TXFM_RESULT_DTYPE), (n_tb,))
     for i, x in enumerate(want):
@@ -272,3 +276,8 @@ def test_chain_of_five_launches(hip, orc, gold, w, h):
         rec = got[int(d["recon_off"]):int(d["recon_off"]) + h * (w + 4) * np.dtype(pix).itemsize].view(pix).reshape(h, w + 4)
         assert np.array_equal(rec[:, :w], x["rec"][:, :w]), ("recon", i)
     assert [(int(b), int(r)) for b, r in zip(cost["bits"], cost["rd_cost"])] == [(x["bits"], x["rd"]) for x in want]
+    declared = [(int(d[f]), 4 * n) for d in fwd for f in ("coeff_off", "qcoeff_off", "dqcoeff_off")]
+    for d in fwd:
+        px = 2 if d["flags"] & abi.TX_PIXEL16 else 1
+        declared += rows(int(d["recon_off"]), (w + 4) * px, w * px, h)
+    check_containment(arena, got, ab.regions, declared, "the chain of five launches")

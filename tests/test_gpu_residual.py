@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 import tx_cases as T
+from arena import Arena
 from svtav1_hip import abi, device
-from test_gpu_txfm import ArenaBuilder
 from test_residual_oracle import GOLD, PD, distortion_cases, orc_subtract, orc_tpl_cost, subtract_cases, tpl_cases
 from tx_cases import P, V
 
@@ -73,11 +73,11 @@ def test_tier_b_tpl_block_cost(hip, orc, size, ss):
     transform size as w x h and the strides pre-shifted as the reference's call does."""
     cases = [(k, c) for k, c in enumerate(tpl_cases()) if c[0] == size and c[1] == ss] * 9   # 81 blocks
     gold = np.load(GOLD)["tpl_cost"]
-    ab, descs = ArenaBuilder(), []
-    for _, (_, _, pf, src, pred) in cases:
+    ab, descs = Arena(), []
+    for i, (_, (_, _, pf, src, pred)) in enumerate(cases):
         d = blank_desc()
-        d.residual_off, d.residual_stride = ab.add(src), src.shape[1] << ss
-        d.pred_off, d.pred_stride = ab.add(pred), pred.shape[1] << ss
+        d.residual_off, d.residual_stride = ab.add(f"source {i}", src), src.shape[1] << ss
+        d.pred_off, d.pred_stride = ab.add(f"pred {i}", pred), pred.shape[1] << ss
         d.tx_type, d.shape, d.bit_depth, d.quant_mode = 0, pf, 8, abi.QUANT_NONE
         d.flags = abi.TX_FWD | abi.TX_SRC_PRED | abi.TX_SATD
         descs.append(d)
@@ -96,8 +96,8 @@ def test_tier_b_source_minus_prediction_to_recon(hip, orc, bd):
     w = h = 16
     n = w * h
     iscan = np.arange(n, dtype=np.int16)
-    ab, descs, expect = ArenaBuilder(), [], []
-    iscan_off = ab.add(iscan)
+    ab, descs, expect = Arena(), [], []
+    iscan_off = ab.add("iscan", iscan)
     pix16 = bd == 10
     dt = np.uint16 if pix16 else np.uint8
     for i in range(120):
@@ -109,10 +109,10 @@ def test_tier_b_source_minus_prediction_to_recon(hip, orc, bd):
         pp[:, :w] = pred
         tt = (0, 1, 4, 9)[i % 4]
         d = blank_desc()
-        d.residual_off, d.residual_stride = ab.add(src), w + 9
-        d.pred_off, d.pred_stride = ab.add(pp), w + 2
-        d.qcoeff_off, d.dqcoeff_off = ab.add(nbytes=n * 4), ab.add(nbytes=n * 4)
-        d.recon_off, d.recon_stride = ab.add(nbytes=h * (w + 4) * (2 if pix16 else 1)), w + 4
+        d.residual_off, d.residual_stride = ab.add(f"source {i}", src), w + 9
+        d.pred_off, d.pred_stride = ab.add(f"pred {i}", pp), w + 2
+        d.qcoeff_off, d.dqcoeff_off = ab.add(f"qcoeff {i}", nbytes=n * 4), ab.add(f"dqcoeff {i}", nbytes=n * 4)
+        d.recon_off, d.recon_stride = ab.add(f"recon {i}", nbytes=h * (w + 4) * (2 if pix16 else 1)), w + 4
         d.iscan_off = iscan_off
         mode = abi.QUANT_B_HBD if pix16 else abi.QUANT_B
         for k in range(2):

@@ -6,10 +6,10 @@ import numpy as np
 import pytest
 
 import subpel_cases as S
+from arena import GUARD
 from svtav1_hip import abi, device
 
 pytestmark = pytest.mark.gpu
-FILL = 0xA5
 
 
 class Loaded:
@@ -23,8 +23,8 @@ class Loaded:
 
     def run(self, descs):
         """(records, whether the guard bytes around them kept their fill)"""
-        out, guards = device.subpel_search_batch(self.lib, self.job, descs, fill=FILL)
-        return out, bool((guards == FILL).all())
+        out, guards = device.subpel_search_batch(self.lib, self.job, descs, fill=GUARD)
+        return out, bool((guards == GUARD).all())
 
 
 @pytest.fixture(scope="module")
@@ -121,7 +121,7 @@ def test_bad_descriptors_among_good_ones(loaded, one_by_one):
     # MV_COST_ENTROPY without the job's tables
     job = abi.SubpelJob()
     entropy = [i for i, c in enumerate(S.CASES) if c.cost_type == S.ENTROPY][:2] + [i for i, c in enumerate(S.CASES) if c.cost_type == S.NONE][:1]
-    out, _ = device.subpel_search_batch(loaded.lib, job, loaded.descs[entropy], fill=FILL)
+    out, _ = device.subpel_search_batch(loaded.lib, job, loaded.descs[entropy], fill=GUARD)
     assert [int(r["status"]) for r in out] == [abi.SUBPEL_BAD_COST, abi.SUBPEL_BAD_COST, abi.SUBPEL_OK]
     assert out[2].tobytes() == one_by_one[entropy[2]].tobytes()
 
@@ -129,7 +129,7 @@ def test_bad_descriptors_among_good_ones(loaded, one_by_one):
 def test_call_level_errors(hip, loaded):
     """NULL job, descriptors or results: SVT_HIP_ERR_BAD_PARAMETER; an empty batch is fine and writes nothing"""
     res = device.DeviceBuffer(hip, 256)
-    res.fill(FILL)
+    res.fill(GUARD)
     d_desc = device.upload_descriptors(hip, loaded.descs[:1])
     f, job, p, r = hip.svt_hip_subpel_search_batch, C.byref(loaded.job), C.c_void_p(d_desc.ptr), C.c_void_p(res.ptr)
     assert f(None, p, r, 1, None) == abi.SVT_HIP_ERR_BAD_PARAMETER and b"svt_hip_subpel_search_batch" in hip.svt_hip_last_error()
@@ -138,4 +138,4 @@ def test_call_level_errors(hip, loaded):
     assert f(None, None, None, 0, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
     assert f(job, p, r, 0, None) == abi.SVT_HIP_OK
     device.check(hip, hip.svt_hip_stream_sync(None), "svt_hip_stream_sync")
-    assert (res.download(np.uint8, (256,)) == FILL).all()
+    assert (res.download(np.uint8, (256,)) == GUARD).all()

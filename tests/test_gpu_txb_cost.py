@@ -7,6 +7,7 @@ import pytest
 
 import tx_cases
 import txb_cost_cases as T
+from arena import GUARD, PATTERN, Arena, check_containment
 from svtav1_hip import abi, device
 
 pytestmark = pytest.mark.gpu
@@ -19,14 +20,14 @@ def gold():
 
 
 def run(hip, gold, w, h, order=None, with_distortion=True, tables_in_lds=None):
-    idx, arena, descs, dist = T.batch(gold, w, h, order)
+    idx, arena, descs, dist, regions = T.batch(gold, w, h, order)
     d_arena, d_dist = device.DeviceBuffer(hip, arena.nbytes), device.DeviceBuffer(hip, dist.nbytes)
     d_arena.upload(arena)
     d_dist.upload(dist)
     out, guard = device.txb_cost_batch(hip, d_arena.ptr, descs, gold.tables, w, h, d_distortion=d_dist.ptr if with_distortion else None,
                                        tables_in_lds=tables_in_lds)
-    assert (guard == 0xA5).all(), "bytes around d_out were written"
-    assert np.array_equal(d_arena.download(np.uint8, (arena.nbytes,)), arena), "the arena was written"
+    assert (guard == GUARD).all(), "bytes around d_out were written"
+    check_containment(arena, d_arena.download(np.uint8, (arena.nbytes,)), regions, [], "svt_hip_txb_cost_batch")
     return idx, out
 
 
@@ -61,8 +62,8 @@ def test_chain_behind_the_transform_batch(hip, orc, gold, w, h):
     n, n_tb = iw * ih, 7
     ls = 2 if max(w, h) == 64 and (w * h) > 1024 else (1 if w * h > 256 and max(w, h) >= 32 and min(w, h) >= 16 else 0)
     types = T.size_types(w, h)
-    ab = tx_cases.Arena()
-    iscan_off = {t: ab.add(gold.iscan(w, h, t)) for t in types}
+    ab = Arena(fill=PATTERN)
+    iscan_off = {t: ab.add(f"iscan {t}", gold.iscan(w, h, t)) for t in types}
     descs, cost_descs, want = (abi.TxfmDesc * n_tb)(), np.zeros(n_tb, np.dtype(abi.TXB_COST_DESC_DTYPE)), []
     for i in range(n_tb):
         bd, tt, mode = (8, 10)[i % 2], types[i % len(types)], (abi.QUANT_B, abi.QUANT_FP, abi.QUANT_B_HBD)[i % 3]
@@ -72,8 +73,8 @@ def test_chain_behind_the_transform_batch(hip, orc, gold, w, h):
             res[:] = 0                                  # eob 0
         iscan = gold.iscan(w, h, tt)
         d = descs[i]
-        d.residual_off, d.residual_stride = ab.add(res), w + 5
-        d.coeff_off, d.qcoeff_off, d.dqcoeff_off = ab.add(nbytes=n * 4), ab.add(nbytes=n * 4), ab.add(nbytes=n * 4)
+        d.residual_off, d.residual_stride = ab.add(f"residual {i}", res), w + 5
+        d.coeff_off, d.qcoeff_off, d.dqcoeff_off = ab.add(f"coeff {i}", nbytes=n * 4), ab.add(f"qcoeff {i}", nbytes=n * 4), ab.add(f"dqcoeff {i}", nbytes=n * 4)
         d.pred_off = d.recon_off = d.qm_off = d.iqm_off = abi.NO_OFFSET
         d.iscan_off = iscan_off[tt]
         rnd, qnt = (tq["round"], tq["quant"]) if mode != abi.QUANT_FP else (tq["round_fp"], tq["quant_fp"])
@@ -107,6 +108,8 @@ def test_chain_behind_the_transform_batch(hip, orc, gold, w, h):
     d_res, d_dist = device.DeviceBuffer(hip, abi.TXFM_RESULT_BYTES * n_tb), device.DeviceBuffer(hip, 16 * n_tb)
     device.check(hip, hip.svt_hip_txfm_quant_batch(V(d_arena.ptr), V(d_desc.ptr), V(d_res.ptr), n_tb, w, h, None), "svt_hip_txfm_quant_batch")
     device.check(hip, hip.svt_hip_txfm_distortion_batch(V(d_arena.ptr), V(d_desc.ptr), V(d_dist.ptr), n_tb, w, h, None), "svt_hip_txfm_distortion_batch")
+    before = d_arena.download(np.uint8, (arena.nbytes,))
     out, guard = device.txb_cost_batch(hip, d_arena.ptr, cost_descs, gold.tables, w, h, d_txfm_result=d_res.ptr, d_distortion=d_dist.ptr)
-    assert (guard == 0xA5).all()
+    assert (guard == GUARD).all()
     assert [(int(b), int(r)) for b, r in zip(out["bits"], out["rd_cost"])] == [(b, r) for _, b, r in want], want
+    check_containment(before, d_arena.download(np.uint8, (arena.nbytes,)), ab.regions, [], "svt_hip_txb_cost_batch behind the transform")

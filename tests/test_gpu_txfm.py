@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import tx_cases as T
+from arena import Arena
 from svtav1_hip import abi, device
 from tx_cases import P, V
 
@@ -123,25 +124,6 @@ def test_tier_a_quantizers(hip, orc):
             assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2], (trial, k)
 
 
-class ArenaBuilder:
-    def __init__(self):
-        self.chunks, self.size = [], 0
-
-    def add(self, arr=None, nbytes=None):
-        off = self.size
-        nbytes = arr.nbytes if arr is not None else nbytes
-        self.chunks.append((off, None if arr is None else np.ascontiguousarray(arr).view(np.uint8).reshape(-1)))
-        self.size += (nbytes + 255) // 256 * 256 + 256
-        return off
-
-    def build(self):
-        buf = np.zeros(self.size, np.uint8)
-        for off, a in self.chunks:
-            if a is not None:
-                buf[off:off + a.size] = a
-        return buf
-
-
 @pytest.mark.parametrize("w,h", T.SIZES)
 def test_tier_b_fused_batch(hip, orc, w, h):
     """residual -> fwd -> [energy/repack] -> quantise -> inverse -> recon for hundreds of blocks in one launch,
@@ -155,8 +137,8 @@ def test_tier_b_fused_batch(hip, orc, w, h):
     scan = rng.permutation(n).astype(np.int16)
     iscan = np.empty(n, np.int16)
     iscan[scan] = np.arange(n)
-    ab = ArenaBuilder()
-    iscan_off = ab.add(iscan)
+    ab = Arena()
+    iscan_off = ab.add("iscan", iscan)
     descs, expect = [], []
     for i in range(n_tb):
         bd = 8 if i % 3 == 0 else 10
@@ -169,11 +151,11 @@ def test_tier_b_fused_batch(hip, orc, w, h):
         res = res.astype(np.int16)
         pred16 = rng.integers(0, 1 << bd, size=(h, w + 2)).astype(np.uint16)
         d = abi.TxfmDesc()
-        d.residual_off, d.residual_stride = ab.add(res), w + 5
-        d.coeff_off = ab.add(nbytes=n * 4) if i % 2 else abi.NO_OFFSET
-        d.qcoeff_off, d.dqcoeff_off = ab.add(nbytes=n * 4), ab.add(nbytes=n * 4)
-        d.pred_off = ab.add(pred16 if pix16 else pred16.astype(np.uint8))
-        d.recon_off = ab.add(nbytes=h * (w + 4) * (2 if pix16 else 1))
+        d.residual_off, d.residual_stride = ab.add(f"residual {i}", res), w + 5
+        d.coeff_off = ab.add(f"coeff {i}", nbytes=n * 4) if i % 2 else abi.NO_OFFSET
+        d.qcoeff_off, d.dqcoeff_off = ab.add(f"qcoeff {i}", nbytes=n * 4), ab.add(f"dqcoeff {i}", nbytes=n * 4)
+        d.pred_off = ab.add(f"pred {i}", pred16 if pix16 else pred16.astype(np.uint8))
+        d.recon_off = ab.add(f"recon {i}", nbytes=h * (w + 4) * (2 if pix16 else 1))
         d.pred_stride, d.recon_stride = w + 2, w + 4
         d.iscan_off, d.qm_off, d.iqm_off = iscan_off, abi.NO_OFFSET, abi.NO_OFFSET
         rnd, qnt = (tq["round"], tq["quant"]) if mode <= 2 else (tq["round_fp"], tq["quant_fp"])
@@ -231,7 +213,7 @@ def test_tier_b_fused_batch(hip, orc, w, h):
 def test_quantize_batch(hip, orc):
     rng = np.random.default_rng(77)
     n, n_tb = 1024, 40
-    ab = ArenaBuilder()
+    ab = Arena()
     descs, expect = [], []
     for i in range(n_tb):
         c = T.quant_case(rng, i)
@@ -244,8 +226,8 @@ def test_quantize_batch(hip, orc):
         mode = 1 + i % 4
         t = c["t"]
         d = abi.TxfmDesc()
-        d.coeff_off, d.iscan_off = ab.add(c["coeff"]), ab.add(c["iscan"])
-        d.qcoeff_off, d.dqcoeff_off = ab.add(nbytes=n * 4), ab.add(nbytes=n * 4)
+        d.coeff_off, d.iscan_off = ab.add(f"coeff {i}", c["coeff"]), ab.add(f"iscan {i}", c["iscan"])
+        d.qcoeff_off, d.dqcoeff_off = ab.add(f"qcoeff {i}", nbytes=n * 4), ab.add(f"dqcoeff {i}", nbytes=n * 4)
         d.qm_off = d.iqm_off = abi.NO_OFFSET
         rnd, qnt = (t["round"], t["quant"]) if mode <= 2 else (t["round_fp"], t["quant_fp"])
         for k in range(2):

@@ -29,6 +29,7 @@ import numpy as np
 import pytest
 
 import tx_cases as T
+from arena import GUARD, PATTERN, Arena, check_containment
 from svtav1_hip import abi, device
 from tx_cases import V
 
@@ -111,7 +112,7 @@ def build(orc, rng, w, h, kinds):
     scan = rng.permutation(n).astype(np.int16)
     iscan = np.empty(n, np.int16)
     iscan[scan] = np.arange(n)
-    ab = T.SentinelArena()
+    ab = Arena(fill=PATTERN)
     iscan_off = ab.add("iscan", iscan)
     descs, blocks, why, patch = (abi.TxfmDesc * len(kinds))(), [], [], []
     F, I = abi.TX_FWD, abi.TX_INV
@@ -205,7 +206,7 @@ class Launch:
         self.ddesc = device.DeviceBuffer(hip, C.sizeof(darr))
         self.ddesc.upload(np.frombuffer(darr, dtype=np.uint8))
         self.dres = device.DeviceBuffer(hip, abi.TXFM_RESULT_BYTES * self.n)
-        self.dres.fill(0xA5)
+        self.dres.fill(GUARD)
         device.check(hip, hip.svt_hip_stream_sync(None), "svt_hip_stream_sync")
 
     def issue(self, stream=None):
@@ -219,7 +220,7 @@ class Launch:
         res_raw = self.dres.download(np.uint8, (self.n, abi.TXFM_RESULT_BYTES))
         T.check_fused_blocks(orc, self.w, self.h, b["descs"], b["blocks"], out, res_raw, what=(self.w, self.h))
         if contain:
-            T.check_containment(b["arena"], out, b["regions"], [o for d in b["descs"] for o in T.declared_outputs(d, self.w, self.h)],
+            check_containment(b["arena"], out, b["regions"], [o for d in b["descs"] for o in T.declared_outputs(d, self.w, self.h)],
                                 what=(self.w, self.h))
 
 

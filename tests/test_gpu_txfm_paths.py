@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import tx_cases as T
+from arena import GUARD, check_containment
 from svtav1_hip import abi, device
 from tx_cases import V
 
@@ -34,7 +35,7 @@ def run_fused(hip, w, h, batch, distortion=False):
     ddesc = device.DeviceBuffer(hip, C.sizeof(darr))
     ddesc.upload(np.frombuffer(darr, dtype=np.uint8))
     dres = device.DeviceBuffer(hip, abi.TXFM_RESULT_BYTES * n_tb)
-    dres.fill(0xA5)
+    dres.fill(GUARD)
     device.check(hip, hip.svt_hip_stream_sync(None), "svt_hip_stream_sync")
     device.check(hip, hip.svt_hip_txfm_quant_batch(V(darena.ptr), V(ddesc.ptr), V(dres.ptr), C.c_uint32(n_tb), C.c_uint32(w),
                                                    C.c_uint32(h), None), "svt_hip_txfm_quant_batch")
@@ -75,7 +76,7 @@ def test_path_matrix_containment(hip, orc, w, h):
     """The same launch wrote nothing but its declared outputs: the inputs, the slack between arrays (a third of the coefficient
     arrays sit 4 / 8 / 12 bytes past a 16-byte boundary) and the columns right of each reconstruction row are untouched."""
     batch, out, _, _ = path_run(hip, orc, w, h)
-    T.check_containment(batch["arena"], out, batch["regions"], declared(batch, w, h), what=(w, h))
+    check_containment(batch["arena"], out, batch["regions"], declared(batch, w, h), what=(w, h))
 
 
 @pytest.mark.parametrize("w,h", T.SIZES)
@@ -87,7 +88,7 @@ def test_flag_combinations(hip, orc, w, h):
     assert {b["kind"] for b in batch["blocks"]} == set(T.FLAG_COMBOS)
     out, res_raw, _ = run_fused(hip, w, h, batch)
     T.check_fused_blocks(orc, w, h, batch["descs"], batch["blocks"], out, res_raw, what=(w, h))
-    T.check_containment(batch["arena"], out, batch["regions"], declared(batch, w, h), what=(w, h))
+    check_containment(batch["arena"], out, batch["regions"], declared(batch, w, h), what=(w, h))
 
 
 @pytest.mark.parametrize("n", [16, 64, 256, 1024])
@@ -102,7 +103,7 @@ def test_quantize_batch_paths(hip, orc, n):
     ddesc = device.DeviceBuffer(hip, C.sizeof(darr))
     ddesc.upload(np.frombuffer(darr, dtype=np.uint8))
     dres = device.DeviceBuffer(hip, abi.TXFM_RESULT_BYTES * n_tb)
-    dres.fill(0xA5)
+    dres.fill(GUARD)
     device.check(hip, hip.svt_hip_stream_sync(None), "svt_hip_stream_sync")
     device.check(hip, hip.svt_hip_quantize_batch(V(darena.ptr), V(ddesc.ptr), V(dres.ptr), C.c_uint32(n_tb), C.c_uint32(n), None),
                  "svt_hip_quantize_batch")
@@ -114,4 +115,4 @@ def test_quantize_batch_paths(hip, orc, n):
         assert np.array_equal(out[d.dqcoeff_off:d.dqcoeff_off + 4 * n].view(np.int32), dq), ("dqcoeff", n, i, d.quant_mode)
         r = abi.TxfmResult.from_buffer_copy(res_raw[i].tobytes())
         assert (r.eob, r.three_quad_energy, r.satd) == (eob, 0, 0), ("result", n, i, d.quant_mode)
-    T.check_containment(arena, out, batch["regions"], [(off, 4 * n) for d in darr for off in (d.qcoeff_off, d.dqcoeff_off)], what=n)
+    check_containment(arena, out, batch["regions"], [(off, 4 * n) for d in darr for off in (d.qcoeff_off, d.dqcoeff_off)], what=n)

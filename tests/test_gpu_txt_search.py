@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import rdoq_cases as R
-import tx_cases
 import txt_search_cases as X
+from arena import GUARD, PATTERN, Arena, check_containment
 from svtav1_hip import abi, device
 
 pytestmark = pytest.mark.gpu
@@ -60,7 +60,7 @@ def select(hip, gold, s, descs, mapping, d_base=None, d_tdesc=None):
     keep = [device.DeviceBuffer(hip, 256), device.upload_descriptors(hip, np.zeros(len(s.cdescs), abi.TXFM_DESC_DTYPE))]
     out, guard = device.txt_select_batch(hip, d_base or keep[0].ptr, descs, d_tdesc or keep[1].ptr, s.cdescs, gold.tables, up[0].ptr, up[1].ptr, up[2].ptr,
                                          up[3].ptr, len(s.cdescs), s.w, s.h, mapping=mapping)
-    assert (guard == 0xA5).all(), "bytes around d_out were written"
+    assert (guard == GUARD).all(), "bytes around d_out were written"
     return out
 
 
@@ -87,7 +87,7 @@ def test_select_without_rdoq_results_and_beyond_the_arrays(hip, gold, sets):
     keep = [device.DeviceBuffer(hip, 256), device.upload_descriptors(hip, np.zeros(len(s.cdescs), abi.TXFM_DESC_DTYPE))]
     got, guard = device.txt_select_batch(hip, keep[0].ptr, descs, keep[1].ptr, s.cdescs, gold.tables, up[0].ptr, None, up[1].ptr, up[2].ptr, len(s.cdescs),
                                          s.w, s.h)
-    assert (guard == 0xA5).all()
+    assert (guard == GUARD).all()
     assert all(X.same_record(g, w) for g, w in zip(got, want))
     assert want[3]["cand"] == abi.TXT_NO_CAND and want[3]["cost"] == X.M64 and not any(w["cul_level"] for w in want)
 
@@ -103,6 +103,12 @@ def test_select_longer_than_one_pass_of_the_grid(hip, gold, sets, mapping):
     assert got.tobytes() == np.tile(records(want), repeat).tobytes()
 
 
+def coefficient_arrays(S, descs):
+    """(offset, bytes) of what a search without the inverse pass may write: the candidates' coefficient arrays and the blocks' destinations"""
+    return [(int(d[f]), 4 * S.n) for d in S.tdescs for f in ("coeff_off", "qcoeff_off", "dqcoeff_off")] + \
+           [(int(b[f]), 4 * S.n) for b in descs for f in ("dst_qcoeff_off", "dst_dqcoeff_off")]
+
+
 def pixels(buf, off, rows, stride, w, pix):
     n = np.dtype(pix).itemsize
     return buf[int(off):int(off) + rows * stride * n].view(pix).reshape(rows, stride)[:, :w]
@@ -114,18 +120,14 @@ def test_spatial_distortion_matches_numpy(hip, w, h):
     samples; odd strides and offsets that are no multiple of 4."""
     rng = np.random.default_rng(w * 100 + h)
     crops = [(cw, ch) for cw in range(1, 5) for ch in range(1, 5)] if (w, h) == (4, 4) else [(w, h), (w - 1, h), (w, h - 1), (w - 1, h - 1), (1, h), (w, 1), (0, 0)]
-    ab = tx_cases.Arena()
-    tdescs, srcs, want, planes = np.zeros(2 * len(crops), abi.TXFM_DESC_DTYPE), np.zeros(2 * len(crops), abi.SPATIAL_SRC_DTYPE), [], {}
+    ab = Arena(fill=PATTERN)
+    tdescs, srcs, want = np.zeros(2 * len(crops), abi.TXFM_DESC_DTYPE), np.zeros(2 * len(crops), abi.SPATIAL_SRC_DTYPE), []
     for i in range(len(tdescs)):
         pix16 = i % 2
         pix, (cw, ch) = (np.uint16 if pix16 else np.uint8), crops[i // 2]
         strides = (w + 1 + 2 * (i % 3), w + 3, w + 5)
         arrays = [rng.integers(0, 1024 if pix16 else 256, size=(h, st)).astype(pix) for st in strides]
-        offs = []
-        for a in arrays:
-            skew = np.dtype(pix).itemsize * (1 + i % 5)
-            offs.append(ab.add(nbytes=a.nbytes + skew) + skew)
-            planes[offs[-1]] = a
+        offs = [ab.add(f"{name} of candidate {i}", a, skew=np.dtype(pix).itemsize * (1 + i % 5)) for name, a in zip(("pred", "recon", "src"), arrays)]
         d, s = tdescs[i], srcs[i]
         d["pred_off"], d["recon_off"], d["pred_stride"], d["recon_stride"], d["flags"] = offs[0], offs[1], strides[0], strides[1], abi.TX_PIXEL16 * pix16
         s["src_off"], s["src_stride"], s["crop_w"], s["crop_h"] = offs[2], strides[2], cw, ch
@@ -135,14 +137,12 @@ def test_spatial_distortion_matches_numpy(hip, w, h):
     tdescs["pred_off"][-1] = abi.NO_OFFSET               # a candidate without a prediction gets {0, 0}
     want[-1] = (0, 0)
     arena = ab.build()
-    for off, a in planes.items():
-        arena[off:off + a.nbytes] = a.view(np.uint8).reshape(-1)
     d_arena, d_tdesc = device.DeviceBuffer(hip, arena.nbytes), device.upload_descriptors(hip, tdescs)
     d_arena.upload(arena)
     got, guard = device.spatial_distortion_batch(hip, d_arena.ptr, d_tdesc.ptr, srcs, w, h)
-    assert (guard == 0xA5).all()
+    assert (guard == GUARD).all()
     assert [tuple(int(v) for v in g) for g in got] == want
-    assert np.array_equal(d_arena.download(np.uint8, (arena.nbytes,)), arena)
+    check_containment(arena, d_arena.download(np.uint8, (arena.nbytes,)), ab.regions, [], "svt_hip_txfm_spatial_distortion_batch")
 
 
 def check_search(S, fixture, got_arena, out):
@@ -158,10 +158,7 @@ def check_search(S, fixture, got_arena, out):
         q, dq = (got_arena[int(b[f]):int(b[f]) + 4 * n].view(np.int32) for f in ("dst_qcoeff_off", "dst_dqcoeff_off"))
         assert np.array_equal(q, win["q"]) and np.array_equal(dq, win["dq"]), (bi, S.cases[bi])
         assert np.array_equal(pixels(got_arena, b["dst_recon_off"], h, int(b["dst_recon_stride"]), w, pix), win["rec"]), (bi, S.cases[bi])
-    free = np.ones(S.arena.size, bool)
-    for off, nb in S.written:
-        free[off:off + nb] = False
-    assert np.array_equal(got_arena[free], S.arena[free]), "the arena was written outside the candidates' own arrays and the destinations"
+    check_containment(S.arena, got_arena, S.regions, S.written, "svt_hip_txt_search_batch")
     for i, c in enumerate(S.cand):             # the candidates' own arrays are what the chain leaves, except where a winner was copied over them
         d = S.tdescs[i]
         if not any(int(b["dst_qcoeff_off"]) == int(d["qcoeff_off"]) and S.winner(bi) is not None for bi, b in enumerate(S.descs)):
@@ -172,7 +169,7 @@ def run_search(hip, gold, S):
     d_arena = device.DeviceBuffer(hip, S.arena.nbytes + 256)
     d_arena.upload(S.arena)
     out, guard = device.txt_search_batch(hip, d_arena.ptr, S.tdescs, S.rdescs, S.cdescs, gold.tables, S.descs, S.w, S.h, inverse=True)
-    assert (guard == 0xA5).all(), "bytes around d_out or the scratch were written"
+    assert (guard == GUARD).all(), "bytes around d_out or the scratch were written"
     return d_arena.download(np.uint8, (S.arena.nbytes,)), out
 
 
@@ -202,7 +199,7 @@ def test_search_without_the_inverse_pass(hip, gold, searches, w, h):
     d_arena = device.DeviceBuffer(hip, S.arena.nbytes + 256)
     d_arena.upload(S.arena)
     out, guard = device.txt_search_batch(hip, d_arena.ptr, S.tdescs, S.rdescs, S.cdescs, gold.tables, descs, w, h, inverse=False)
-    assert (guard == 0xA5).all()
+    assert (guard == GUARD).all()
     got = d_arena.download(np.uint8, (S.arena.nbytes,))
     assert 2 <= len(keep) < len(S.cases)
     for k, bi in enumerate(keep):
@@ -210,14 +207,7 @@ def test_search_without_the_inverse_pass(hip, gold, searches, w, h):
         win, b = S.winner(bi), descs[k]
         q, dq = (got[int(b[f]):int(b[f]) + 4 * S.n].view(np.int32) for f in ("dst_qcoeff_off", "dst_dqcoeff_off"))
         assert np.array_equal(q, win["q"]) and np.array_equal(dq, win["dq"]), (bi, S.cases[bi])
-    free = np.ones(S.arena.size, bool)
-    for d in S.tdescs:
-        for f in ("coeff_off", "qcoeff_off", "dqcoeff_off"):
-            free[int(d[f]):int(d[f]) + 4 * S.n] = False
-    for b in descs:
-        for f in ("dst_qcoeff_off", "dst_dqcoeff_off"):
-            free[int(b[f]):int(b[f]) + 4 * S.n] = False
-    assert np.array_equal(got[free], S.arena[free]), "something but the coefficient arrays was written"
+    check_containment(S.arena, got, S.regions, coefficient_arrays(S, descs), "svt_hip_txt_search_batch without the inverse pass")
 
 
 @pytest.mark.parametrize("w, h", [(4, 4), (16, 16)], ids=lambda v: str(v))
@@ -243,7 +233,7 @@ def test_search_without_the_inverse_pass_ignores_spatial_sse(hip, gold, searches
     assert all(want[bi] == S.want[bi] for bi, c in enumerate(S.cases) if not c.spatial)
     d_arena.upload(S.arena)
     out, guard = device.txt_search_batch(hip, d_arena.ptr, S.tdescs, S.rdescs, S.cdescs, gold.tables, S.descs, w, h, inverse=False)
-    assert (guard == 0xA5).all()
+    assert (guard == GUARD).all()
     got = d_arena.download(np.uint8, (S.arena.nbytes,))
     for bi, b in enumerate(S.descs):
         assert X.same_record(out[bi], want[bi]), (bi, S.cases[bi], out[bi], want[bi])
@@ -251,14 +241,7 @@ def test_search_without_the_inverse_pass_ignores_spatial_sse(hip, gold, searches
             win = S.cand[int(b["first_cand"]) + want[bi]["cand"]]
             q, dq = (got[int(b[f]):int(b[f]) + 4 * S.n].view(np.int32) for f in ("dst_qcoeff_off", "dst_dqcoeff_off"))
             assert np.array_equal(q, win["q"]) and np.array_equal(dq, win["dq"]), (bi, S.cases[bi])
-    free = np.ones(S.arena.size, bool)
-    for d in S.tdescs:
-        for f in ("coeff_off", "qcoeff_off", "dqcoeff_off"):
-            free[int(d[f]):int(d[f]) + 4 * S.n] = False
-    for b in S.descs:
-        for f in ("dst_qcoeff_off", "dst_dqcoeff_off"):
-            free[int(b[f]):int(b[f]) + 4 * S.n] = False
-    assert np.array_equal(got[free], S.arena[free]), "something but the coefficient arrays was written"
+    check_containment(S.arena, got, S.regions, coefficient_arrays(S, S.descs), "svt_hip_txt_search_batch without the inverse pass")
 
 
 @pytest.mark.parametrize("mapping", [0, 1])
@@ -288,7 +271,7 @@ def test_copies_in_a_launch_longer_than_one_pass_of_the_grid(hip, gold, searches
     out = select(hip, gold, s, descs, mapping, d_arena.ptr, d_tdesc.ptr)
     got = d_arena.download(np.uint8, (big.nbytes,))
     assert out.tobytes() == np.tile(records(S.want), repeat).tobytes()
-    assert np.array_equal(got[:arena.nbytes], arena)
+    check_containment(arena, got[:arena.nbytes], S.regions, [], "svt_hip_txt_select_batch")
     one = np.full((nb0, per), 0x3C, np.uint8)
     for bi in range(nb0):
         win = S.winner(bi)

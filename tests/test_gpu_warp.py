@@ -11,6 +11,7 @@ import blend_cases as B
 import conv_cases as K
 import pyorc
 import warp_cases as W
+from arena import GUARD, OnDevice
 from svtav1_hip import abi, device
 
 pytestmark = pytest.mark.gpu
@@ -33,21 +34,6 @@ def filt(hip, gold):
     d = device.DeviceBuffer(hip, abi.WARP_FILTER_BYTES)
     d.upload(gold["warped_filter"])
     return d
-
-
-class OnDevice:
-    """Device copies of host buffers (blend_cases.Buf)."""
-
-    def __init__(self, hip, bufs):
-        self.bufs, self.ptrs = {}, {}
-        for b in bufs:
-            d = device.DeviceBuffer(hip, b.a.nbytes)
-            d.upload(b.a)
-            self.bufs[id(b)], self.ptrs[id(b)] = d, d.ptr
-
-    def fetch(self, buf):
-        """Overwrite the host buffer with its device copy."""
-        buf.a[:] = self.bufs[id(buf)].download(buf.a.dtype, buf.a.shape)
 
 
 # ---- 1. prediction ----------------------------------------------------------------------------------------------------------
@@ -145,7 +131,7 @@ def test_warp_with_convolve_and_blend(hip, gold, ref, filt, index):
     dev = OnDevice(hip, inp.planes)
     d_dst, d_cb = device.DeviceBuffer(hip, w * h * px), [device.DeviceBuffer(hip, w * h * 2) for _ in range(2)]
     for d in [d_dst] + d_cb:
-        d.fill(0xA5)
+        d.fill(GUARD)
 
     def warp(j, cb, compound):
         p = inp.planes[j]
@@ -168,7 +154,7 @@ def test_warp_with_convolve_and_blend(hip, gold, ref, filt, index):
         conv(0, d_cb[0], 1), warp(1, d_cb[0], 2)
     else:
         warp(0, d_cb[0], 1), warp(1, d_cb[1], 1)
-        assert (d_dst.download(np.uint8, (w * h * px,)) == 0xA5).all()   # compound 1 leaves dst alone
+        assert (d_dst.download(np.uint8, (w * h * px,)) == GUARD).all()   # compound 1 leaves dst alone
         d_mask = device.DeviceBuffer(hip, w * h)
         d_mask.upload(np.load(B.GOLD)["wedge_16x16"][W.INTER_WEDGE])
         device.blend_batch(hip, [abi.BlendDesc(d_cb[0].ptr, d_cb[1].ptr, d_dst.ptr, d_mask.ptr, w, w, w, w, w, h, abi.BLEND_D16, 0, 0, 0,

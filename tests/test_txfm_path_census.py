@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import tx_cases as T
+from arena import check_containment
 
 
 @pytest.mark.parametrize("w,h", T.SIZES)
@@ -16,9 +17,9 @@ def test_path_cases_census(orc, w, h):
     # what no descriptor declares as an output covers all inputs and all slack: the containment check has something to guard
     declared = sum(nb for d in batch["descs"] for _, nb in T.declared_outputs(d, w, h))
     assert 0 < declared < batch["arena"].size
-    T.check_containment(batch["arena"], batch["arena"].copy(), batch["regions"], [])
+    check_containment(batch["arena"], batch["arena"].copy(), batch["regions"], [])
     spoilt = batch["arena"].copy()
     d = batch["descs"][1]
     spoilt[d.recon_off + w * (2 if d.bit_depth != 8 else 1)] ^= 1            # first byte right of row 0 of a reconstruction
     with pytest.raises(AssertionError, match="recon of block 1"):
-        T.check_containment(batch["arena"], spoilt, batch["regions"], [o for x in batch["descs"] for o in T.declared_outputs(x, w, h)])
+        check_containment(batch["arena"], spoilt, batch["regions"], [o for x in batch["descs"] for o in T.declared_outputs(x, w, h)])

@@ -3,6 +3,8 @@ import ctypes as C
 
 import numpy as np
 
+from arena import PATTERN, Arena
+
 SIZES = [(4, 4), (8, 8), (16, 16), (32, 32), (64, 64), (4, 8), (8, 4), (8, 16), (16, 8), (16, 32), (32, 16), (32, 64),
          (64, 32), (4, 16), (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]
 V = C.c_void_p
@@ -89,27 +91,6 @@ def orc_quant(orc, mode, c):
     return qc, dq, eob.value
 
 
-class Arena:
-    """Host image of a device arena: arrays placed at 256-byte aligned offsets with 256 bytes of slack between them."""
-
-    def __init__(self):
-        self.chunks, self.size = [], 0
-
-    def add(self, arr=None, nbytes=None):
-        off = self.size
-        nbytes = arr.nbytes if arr is not None else nbytes
-        self.chunks.append((off, None if arr is None else np.ascontiguousarray(arr).view(np.uint8).reshape(-1)))
-        self.size += (nbytes + 255) // 256 * 256 + 256
-        return off
-
-    def build(self):
-        buf = np.zeros(self.size, np.uint8)
-        for off, a in self.chunks:
-            if a is not None:
-                buf[off:off + a.size] = a
-        return buf
-
-
 def fused_batch(orc, rng, w, h, n_tb):
     """n_tb blocks of w x h for svt_hip_txfm_quant_batch (residual -> fwd -> quantise -> inverse -> recon) with every valid tx_type
     in turn, 8- / 10-bit, both pixel widths and all four quantisers, and what the oracle pipeline makes of each.
@@ -123,7 +104,7 @@ def fused_batch(orc, rng, w, h, n_tb):
     iscan = np.empty(n, np.int16)
     iscan[scan] = np.arange(n)
     ab = Arena()
-    iscan_off = ab.add(iscan)
+    iscan_off = ab.add("iscan", iscan)
     descs, expect = (abi.TxfmDesc * n_tb)(), []
     for i in range(n_tb):
         bd = 8 if i % 3 == 0 else 10
@@ -133,11 +114,11 @@ def fused_batch(orc, rng, w, h, n_tb):
         res = (residual(rng, w, h, bd, 0, pad=5) // (1 + (i % 5))).astype(np.int16)
         pred16 = rng.integers(0, 1 << bd, size=(h, w + 2)).astype(np.uint16)
         d = descs[i]
-        d.residual_off, d.residual_stride = ab.add(res), w + 5
-        d.coeff_off = ab.add(nbytes=n * 4) if i % 2 else abi.NO_OFFSET
-        d.qcoeff_off, d.dqcoeff_off = ab.add(nbytes=n * 4), ab.add(nbytes=n * 4)
-        d.pred_off = ab.add(pred16 if pix16 else pred16.astype(np.uint8))
-        d.recon_off = ab.add(nbytes=h * (w + 4) * (2 if pix16 else 1))
+        d.residual_off, d.residual_stride = ab.add(f"residual {i}", res), w + 5
+        d.coeff_off = ab.add(f"coeff {i}", nbytes=n * 4) if i % 2 else abi.NO_OFFSET
+        d.qcoeff_off, d.dqcoeff_off = ab.add(f"qcoeff {i}", nbytes=n * 4), ab.add(f"dqcoeff {i}", nbytes=n * 4)
+        d.pred_off = ab.add(f"pred {i}", pred16 if pix16 else pred16.astype(np.uint8))
+        d.recon_off = ab.add(f"recon {i}", nbytes=h * (w + 4) * (2 if pix16 else 1))
         d.pred_stride, d.recon_stride = w + 2, w + 4
         d.iscan_off, d.qm_off, d.iqm_off = iscan_off, abi.NO_OFFSET, abi.NO_OFFSET
         rnd, qnt = (tq["round"], tq["quant"]) if mode <= 2 else (tq["round_fp"], tq["quant_fp"])
@@ -184,30 +165,6 @@ def own_log_scale(w, h):
     return 2 if max(w, h) == 64 and (w * h) > 1024 else (1 if w * h > 256 and max(w, h) >= 32 and min(w, h) >= 16 else 0)
 
 
-class SentinelArena:
-    """Host image of a device arena like Arena, but every byte starts as a pattern that depends on its position, outputs
-    included, and every array is recorded by name: check_containment tells from it what a kernel wrote outside its outputs.
-    skew moves an array that many bytes past its 256-byte boundary."""
-
-    def __init__(self):
-        self.chunks, self.regions, self.size = [], [], 0
-
-    def add(self, name, arr=None, nbytes=None, skew=0):
-        off = self.size + skew
-        nbytes = arr.nbytes if arr is not None else nbytes
-        self.regions.append((off, nbytes, name))
-        if arr is not None:
-            self.chunks.append((off, np.ascontiguousarray(arr).view(np.uint8).reshape(-1)))
-        self.size += (skew + nbytes + 255) // 256 * 256 + 256
-        return off
-
-    def build(self):
-        buf = ((np.arange(self.size, dtype=np.uint32) * 37 + 11) & 0xFF).astype(np.uint8)
-        for off, a in self.chunks:
-            buf[off:off + a.size] = a
-        return buf
-
-
 def declared_outputs(d, w, h):
     """(offset, bytes) of everything descriptor d allows the fused kernel to write."""
     from svtav1_hip import abi
@@ -220,20 +177,6 @@ def declared_outputs(d, w, h):
     if d.flags & abi.TX_INV:
         out += [(d.recon_off + r * d.recon_stride * px, w * px) for r in range(h)]
     return out
-
-
-def check_containment(arena, out, regions, declared, what=""):
-    """Every byte of the arena that no (offset, bytes) of `declared` covers is what it was before the call."""
-    free = np.ones(arena.size, bool)
-    for off, nb in declared:
-        free[off:off + nb] = False
-    bad = np.flatnonzero((out != arena) & free)
-    if bad.size:
-        o, where = int(bad[0]), "before the first array"
-        for off, nb, name in regions:
-            if off <= o:
-                where = name if o < off + nb else "slack after " + name
-        raise AssertionError(f"{what}: byte {o} ({where}) changed from {arena[o]} to {out[o]}; {bad.size} bytes in all")
 
 
 def _fused_block(ab, orc, rng, w, h, d, i, scan, iscan, iscan_off, res, bd, pix16, tt, shape, mode, ls, flags, qm=None, iqm=None,
@@ -372,7 +315,7 @@ def path_cases(orc, rng, w, h):
     kinds = [km for _ in range(1 if L <= 8 else (2 if L == 16 else 3)) for wave in path_plan(nt) for km in wave]
     if nt > 1:
         kinds.append(("small", 2))
-    ab = SentinelArena()
+    ab = Arena(fill=PATTERN)
     iscan_off = ab.add("iscan", iscan)
     descs, blocks = (abi.TxfmDesc * len(kinds))(), []
 
@@ -534,7 +477,7 @@ def flag_cases(orc, rng, w, h):
     iscan = np.empty(n, np.int16)
     iscan[scan] = np.arange(n)
     n_tb = max(24, 4 * nt) + (nt > 1)
-    ab = SentinelArena()
+    ab = Arena(fill=PATTERN)
     iscan_off = ab.add("iscan", iscan)
     descs, blocks = (abi.TxfmDesc * n_tb)(), []
     F, I, S = abi.TX_FWD, abi.TX_INV, abi.TX_SATD
@@ -569,7 +512,7 @@ def quantize_batch_cases(orc, rng, n, n_tb=64):
     (1 << 20 among them), log_scale 0..2, a permuted scan, matrices on a third of the blocks.
     -> dict(arena, regions, descs, expect): expect[i] = (qcoeff, dqcoeff, eob) of the oracle."""
     from svtav1_hip import abi
-    ab = SentinelArena()
+    ab = Arena(fill=PATTERN)
     descs, expect = (abi.TxfmDesc * n_tb)(), []
     for i in range(n_tb):
         bd, mode = int(rng.choice([8, 10])), 1 + i % 4

@@ -10,8 +10,9 @@ import os
 
 import numpy as np
 
+from arena import PATTERN, Arena
 from svtav1_hip import abi
-from tx_cases import SIZES, Arena
+from tx_cases import SIZES
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "txb_cost.npz")
@@ -297,11 +298,12 @@ class Golden:
 
 
 def batch(gold, w, h, order=None):
-    """The cases of size w x h as one launch: (case indices, arena image, descriptor record array, distortions [n][2])."""
+    """The cases of size w x h as one launch: (case indices, arena image, descriptor record array, distortions [n][2], the arena's
+    named regions).  Every byte of the arena that is no input holds the pattern."""
     idx = [i for i, c in enumerate(CASES) if (c.w, c.h) == (w, h)]
     if order is not None:
         idx = [idx[k] for k in order(len(idx))]
-    ab = Arena()
+    ab = Arena(fill=PATTERN)
     iscan_off = {}
     descs = np.zeros(len(idx), np.dtype(abi.TXB_COST_DESC_DTYPE))
     dist = np.zeros((len(idx), 2), np.uint64)
@@ -309,14 +311,14 @@ def batch(gold, w, h, order=None):
         c = CASES[i]
         iscan = gold.iscan(w, h, c.tx_type)
         if c.tx_type not in iscan_off:
-            iscan_off[c.tx_type] = ab.add(iscan)
+            iscan_off[c.tx_type] = ab.add(f"iscan {c.tx_type}", iscan)
         d = descs[k]
-        d["qcoeff_off"], d["iscan_off"] = ab.add(coefficients(i, c, iscan)), iscan_off[c.tx_type]
+        d["qcoeff_off"], d["iscan_off"] = ab.add(f"qcoeff of block {k}", coefficients(i, c, iscan)), iscan_off[c.tx_type]
         d["table"], d["lambda"], d["eob"], d["tx_type"], d["plane_type"] = c.table, c.lam, c.eob, c.tx_type, c.plane
         d["txb_skip_ctx"], d["dc_sign_ctx"], d["pred_mode"], d["filter_intra_mode"] = c.skip_ctx, c.dc_sign_ctx, c.pred_mode, c.fim
         d["reduced_tx_set"], d["fast_coeff_est_level"], d["subres_step"], d["est_mode"], d["flags"] = c.reduced, c.fast, c.step, c.est_mode, c.flags
         dist[k] = (c.dist, 0xDEAD)
-    return idx, ab.build(), descs, dist
+    return idx, ab.build(), descs, dist, ab.regions
 
 
 def expected_rd(i, bits):

@@ -15,6 +15,7 @@ import numpy as np
 import rdoq_cases as R
 import tx_cases
 import txb_cost_cases as T
+from arena import PATTERN, Arena, rows
 from svtav1_hip import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -243,7 +244,7 @@ class Search:
         self.n = n
         plan = [candidate_order(w, h, c.is_inter, 0, c.sc, c.n_groups) for c in cases]
         n_cand = sum(len(p[0]) for p in plan)
-        ab = tx_cases.Arena()
+        ab = Arena(fill=PATTERN)
         shared = {}
         self.tdescs, self.rdescs = np.zeros(n_cand, abi.TXFM_DESC_DTYPE), np.zeros(n_cand, abi.RDOQ_DESC_DTYPE)
         self.cdescs, self.descs = np.zeros(n_cand, abi.TXB_COST_DESC_DTYPE), np.zeros(len(cases), abi.TXT_DESC_DTYPE)
@@ -262,10 +263,9 @@ class Search:
             res = np.zeros((h, res_stride), np.int16)
             res[:, :w] = src[:, :w] - pred[:, :w]
             skew = pix().itemsize * (1 + ci % 3)                          # pixel planes off their 256-byte boundaries
-            pred_off = ab.add(nbytes=pred.size * pix().itemsize + skew) + skew
-            src_off = ab.add(nbytes=src.size * pix().itemsize + skew) + skew
-            shared[pred_off], shared[src_off] = pred.astype(pix), src.astype(pix)
-            res_off = ab.add(res)
+            pred_off = ab.add(f"pred of block {bi}", pred.astype(pix), skew=skew)
+            src_off = ab.add(f"src of block {bi}", src.astype(pix), skew=skew)
+            res_off = ab.add(f"residual of block {bi}", res)
             pred_mode = T.NEARESTMV if c.is_inter else (0, 1, 9)[ci % 3]
             cw, ch = (max(1, w - 1 - ci % 3), max(1, h - 2)) if c.crop else (w, h)
             self.inputs.append(dict(res=res, pred=pred.astype(pix), src=src.astype(pix), strides=(res_stride, ps, ss, rs), crop=(cw, ch), pred_mode=pred_mode))
@@ -286,18 +286,18 @@ class Search:
                 iscan = iscan_of(gold, w, h, tt)
                 key = ("iscan", T.tx_class(tt))
                 if key not in shared:
-                    shared[key] = ab.add(iscan)
+                    shared[key] = ab.add(f"iscan of class {key[1]}", iscan)
                 d = self.tdescs[i]
                 d["residual_off"], d["residual_stride"] = res_off, res_stride
-                d["coeff_off"], d["qcoeff_off"], d["dqcoeff_off"] = ab.add(nbytes=n * 4), ab.add(nbytes=n * 4), ab.add(nbytes=n * 4)
-                d["pred_off"], d["pred_stride"], d["recon_off"], d["recon_stride"] = pred_off, ps, ab.add(nbytes=h * rs * pix().itemsize), rs
+                d["coeff_off"], d["qcoeff_off"], d["dqcoeff_off"] = (ab.add(f"{f} of candidate {i}", nbytes=n * 4) for f in ("coeff", "qcoeff", "dqcoeff"))
+                d["pred_off"], d["pred_stride"], d["recon_off"], d["recon_stride"] = pred_off, ps, ab.add(f"recon of candidate {i}", nbytes=h * rs * pix().itemsize), rs
                 d["iscan_off"], d["qm_off"], d["iqm_off"] = shared[key], abi.NO_OFFSET, abi.NO_OFFSET
                 d["zbin"], d["round"], d["quant"] = qt["zbin"][:2], qt["round_fp" if fp else "round"][:2], qt["quant_fp" if fp else "quant"][:2]
                 d["quant_shift"], d["dequant"] = qt["qshift"][:2], qt["dequant"][:2]
                 d["tx_type"], d["bit_depth"], d["quant_mode"], d["log_scale"] = tt, c.bd, mode, ls
                 d["flags"] = abi.TX_FWD | abi.TX_SATD | (abi.TX_PIXEL16 if pix16 else 0)
                 self.written += [(int(d["coeff_off"]), n * 4), (int(d["qcoeff_off"]), n * 4), (int(d["dqcoeff_off"]), n * 4)]
-                self.written += [(int(d["recon_off"]) + r * rs * pix().itemsize, w * pix().itemsize) for r in range(h)]
+                self.written += rows(int(d["recon_off"]), rs * pix().itemsize, w * pix().itemsize, h)
                 r = self.rdescs[i]
                 cc = rc._replace(tx_type=tt)
                 r["table"], r["lambda"], r["early_exit_limit"] = c.table, c.lam, R.early_exit_limit(cc)
@@ -336,18 +336,15 @@ class Search:
             # the winner's destinations: the DCT_DCT candidate's own arrays (the reference's cand_bf), or arrays of their own
             dct = at + types.index(DCT_DCT)
             if c.own_dst:
-                b["dst_qcoeff_off"], b["dst_dqcoeff_off"] = ab.add(nbytes=n * 4), ab.add(nbytes=n * 4)
-                b["dst_recon_off"], b["dst_recon_stride"] = ab.add(nbytes=h * (w + 9) * pix().itemsize), w + 9
+                b["dst_qcoeff_off"], b["dst_dqcoeff_off"] = ab.add(f"dst qcoeff of block {bi}", nbytes=n * 4), ab.add(f"dst dqcoeff of block {bi}", nbytes=n * 4)
+                b["dst_recon_off"], b["dst_recon_stride"] = ab.add(f"dst recon of block {bi}", nbytes=h * (w + 9) * pix().itemsize), w + 9
             else:
                 b["dst_qcoeff_off"], b["dst_dqcoeff_off"] = self.tdescs[dct]["qcoeff_off"], self.tdescs[dct]["dqcoeff_off"]
                 b["dst_recon_off"], b["dst_recon_stride"] = self.tdescs[dct]["recon_off"], rs
             self.written += [(int(b["dst_qcoeff_off"]), n * 4), (int(b["dst_dqcoeff_off"]), n * 4)]
-            self.written += [(int(b["dst_recon_off"]) + r * int(b["dst_recon_stride"]) * pix().itemsize, w * pix().itemsize) for r in range(h)]
+            self.written += rows(int(b["dst_recon_off"]), int(b["dst_recon_stride"]) * pix().itemsize, w * pix().itemsize, h)
             at += len(types)
-        self.arena = ab.build()
-        for off, a in shared.items():
-            if isinstance(off, int):
-                self.arena[off:off + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        self.arena, self.regions = ab.build(), ab.regions
         self.records = (results, rdoq, dist, cost)
         self.want = [decide(gold.tables, w, h, b, self.cdescs, results, rdoq, dist, cost) for b in self.descs]
 
