@@ -1,7 +1,8 @@
 /*
  * svt_hip_inter.h — C-ABI for inter prediction: interpolation (the single-reference and the
  * compound ("jnt") families), the masked-compound and OBMC blends, the compound mask search, warped prediction (local warp
- * and global motion), the global-motion error / refinement and the sub-pel motion search of mode decision.
+ * and global motion), the global-motion error / refinement, the sub-pel motion search of mode decision and OBMC's weighted
+ * target and motion refinement.
  *
  * Reference interfaces replaced (paths relative to /root/reference):
  *   Source/Lib/Codec/common_dsp_rtcd.h:185-221   svt_av1_convolve_{2d_sr,x_sr,y_sr,2d_copy_sr},
@@ -20,9 +21,15 @@
  *   Source/Lib/Codec/enc_warped_motion.c:22-98   svt_av1_warp_error
  *   Source/Lib/Codec/global_motion.c:86-251      add_param_offset, force_wmtype, svt_av1_refine_integerized_param
  *   Source/Lib/Codec/mcomp.c:609-775             svt_av1_find_best_sub_pixel_tree(_pruned) as md_subpel_search calls them
+ *   Source/Lib/Codec/enc_inter_prediction.c:1592-1649, 1767-1827   calc_target_weighted_pred and its two visitors
+ *   Source/Lib/Codec/mode_decision.c:2425-2533, av1me.c:709-1132   single_motion_search (OBMC_CAUSAL): svt_av1_obmc_full_pixel_search,
+ *                                                svt_av1_find_best_obmc_sub_pixel_tree_up, svt_aom_obmc_sad* / svt_aom_obmc_variance*
  * The warp entry points are Tier B only: the RTCD pointers svt_av1_warp_affine / svt_av1_highbd_warp_affine have no leaf.
  * Scaled references are not covered; the corner matching / RANSAC front end of global motion and svt_find_projection stay on
- * the host.  OBMC's neighbour predictions and the rate model of the mask search (model_rd_with_curvfit) stay on the host.
+ * the host.  The rate model of the mask search (model_rd_with_curvfit) stays on the host.  An OBMC candidate needs no host
+ * arithmetic: its neighbour predictions are SvtHipConvolveDesc descriptors, then svt_hip_obmc_target_batch,
+ * svt_hip_obmc_search_batch, the prediction at the vector found and the SVT_HIP_BLEND_VMASK / _HMASK blends; which neighbours
+ * overlap, and svt_aom_choose_best_av1_mv_pred behind the search, stay the caller's control logic.
  * Inter-intra prediction is in svt_hip_intra.h: the smooth form is an epilogue of svt_hip_intra_predict_batch, the wedge form is
  * that prediction followed by a SVT_HIP_BLEND_MASK descriptor here.
  */
@@ -369,6 +376,111 @@ SVT_HIP_API int32_t svt_hip_subpel_search_batch(const SvtHipSubpelJob *job, cons
  * limits: col_min, col_max, row_min, row_max.  Host only, no device.  SVT_HIP_ERR_BAD_PARAMETER for a NULL pointer. */
 SVT_HIP_API int32_t svt_hip_subpel_mv_limits(int32_t mi_row, int32_t mi_col, int32_t mi_width, int32_t mi_height, int32_t mi_rows,
                                              int32_t mi_cols, const SvtHipMv *ref_mv, int32_t limits[4]);
+
+/* ---- OBMC motion refinement (Tier B) ------------------------------------------------------------------------------------------
+ * What svt_aom_precompute_obmc_data and svt_aom_obmc_motion_refinement compute between the neighbour predictions
+ * (SvtHipConvolveDesc) and the final blends (SVT_HIP_BLEND_VMASK / _HMASK): the weighted target, then single_motion_search
+ * (mode_decision.c:2425-2533) for OBMC_CAUSAL.  8-bit only, as the reference (calc_target_weighted_pred sets is16bit = 0,
+ * single_motion_search "supports 8bit path only").  Not covered: the bilinear osvf path (use_accurate_subpel_search == 0, which the
+ * encoder never takes), scaled references, svt_aom_choose_best_av1_mv_pred and the validity check behind the search, and an
+ * encoder hook.  wsrc and mask are int32_t arrays and must be 4-byte aligned; every other pointer may have any alignment. */
+#define SVT_HIP_OBMC_MAX_NEIGHBOURS 4 /* max_neighbor_obmc[] never exceeds it */
+/* status of both entry points */
+#define SVT_HIP_OBMC_OK 0
+#define SVT_HIP_OBMC_BAD_SIZE 1     /* w x h is none of the 22 block sizes */
+#define SVT_HIP_OBMC_BAD_POINTER 2  /* a NULL pointer that would be read or written, or wsrc / mask not 4-byte aligned */
+#define SVT_HIP_OBMC_BAD_SEGMENT 3  /* target: more than 4 neighbours on a side, an empty one, one that runs past the block, or two that
+                                     * are not in ascending order without overlap */
+#define SVT_HIP_OBMC_BAD_RANGE 4    /* search: fpel_search_range above 16 */
+#define SVT_HIP_OBMC_BAD_START_MV 5 /* search: start_mv not inside MV_LOW .. MV_UPP */
+#define SVT_HIP_OBMC_BAD_LIMITS 6   /* search: a minimum above its maximum, or full-pel limits outside -2048 .. 2048 */
+#define SVT_HIP_OBMC_BAD_FILTER 7   /* search: subpel_search_type */
+#define SVT_HIP_OBMC_BAD_COST 8     /* search: approx_inter_rate == 0 without the job's tables */
+
+typedef struct SvtHipObmcNeighbour { /* one call of the visitor of foreach_overlappable_nb_above / _left (enc_inter_prediction.c:684-752) */
+    uint8_t rel_mi;                  /* rel_mi_col / rel_mi_row: where the neighbour starts along the block's edge, in units of 4 samples */
+    uint8_t mi_len;                  /* nb_mi_width / nb_mi_height: AOMMIN(xd->n4_w, mi_step), in the same units */
+} SvtHipObmcNeighbour;
+
+/* calc_target_weighted_pred (enc_inter_prediction.c:1767-1827) with svt_av1_calc_target_weighted_pred_above_c / _left_c: wsrc = 0,
+ * mask = 64; the above neighbours write (64 - m) * above and m over min(h, 64) / 2 rows; both times 64; the left neighbours blend
+ * min(w, 64) / 2 columns; wsrc = src * 4096 - wsrc.  The ramps m are svt_av1_get_obmc_mask(overlap), held by the kernel.
+ * WHICH neighbours overlap is the caller's: the walk over the mode info, the pairs of 4-wide blocks, nb_max and the clip at
+ * mi_cols / mi_rows give the (rel_mi, mi_len) lists.
+ * What is read: of src the w x h block; of above the rows 0 .. min(h, 64) / 2 and of left the columns 0 .. min(w, 64) / 2 of the
+ * listed neighbours' samples, both laid out block-sized from the block's (0, 0) as svt_aom_precompute_obmc_data lays them out.
+ * What is written: wsrc[h][w] and mask[h][w] (stride w) and the status.  A descriptor with a non-zero status leaves wsrc and mask
+ * zero (untouched where the size or the two pointers themselves are what is wrong). */
+typedef struct SvtHipObmcTargetDesc {
+    const uint8_t      *src, *above, *left; /* above / left may be NULL when that side is unavailable or lists no neighbour */
+    int32_t            *wsrc, *mask;
+    uint32_t            src_stride, above_stride, left_stride;
+    uint16_t            w, h;               /* one of the 22 sizes of init_fn_ptr (av1me.c:31-170) */
+    uint8_t             up_available, left_available;
+    uint8_t             n_above, n_left;    /* 0 .. SVT_HIP_OBMC_MAX_NEIGHBOURS; ignored on a side that is not available */
+    SvtHipObmcNeighbour above_nb[SVT_HIP_OBMC_MAX_NEIGHBOURS], left_nb[SVT_HIP_OBMC_MAX_NEIGHBOURS];
+    uint32_t            pad_;
+} SvtHipObmcTargetDesc;
+/* d_status[i] (SVT_HIP_OBMC_*) belongs to d_desc[i].  SVT_HIP_ERR_BAD_PARAMETER for a NULL d_desc or d_status; n == 0 is SVT_HIP_OK and
+ * launches nothing.  Asynchronous on `stream`. */
+SVT_HIP_API int32_t svt_hip_obmc_target_batch(const SvtHipObmcTargetDesc *d_desc, uint32_t *d_status, uint32_t n, void *stream);
+
+/* single_motion_search for one block of one reference.
+ * Full-pel stage (do_full_refine): svt_av1_obmc_full_pixel_search (av1me.c:721-776): start_mv >> 3 clamped into fp_limits, then
+ * obmc_refining_search_sad over 4 or 8 neighbours for up to fpel_search_range rounds, error svt_aom_obmc_sad*, vector cost
+ * mvsad_err_cost in both forms.  Without it the vector is start_mv >> 3.
+ * Sub-pel stage (do_frac_refine): svt_av1_find_best_obmc_sub_pixel_tree_up (av1me.c:963-1132) on the accurate path
+ * (svt_aom_upsampled_pred_c + svt_aom_obmc_variance*), limits from raw_limits as set_subpel_mv_search_range (av1me.c:778-790) derives
+ * them, vector cost svt_aom_mv_err_cost / svt_aom_mv_err_cost_light.  Without it the vector is the full-pel one << 3.
+ * rate_mv: svt_av1_mv_bit_cost(.., MV_COST_WEIGHT) or svt_av1_mv_bit_cost_light, as mode_decision.c:2529-2532.
+ *
+ * What is read: wsrc[h][w] and mask[h][w]; of ref, with R = fpel_search_range (0 without do_full_refine), the
+ * (w + 2 R + 8) x (h + 2 R + 8) window that starts R + 4 samples above and R + 4 to the left of the sample the clamped start points at
+ * (the full-pel stage moves at most R samples from there; the tree adds what the sub-pel section above states): the caller's
+ * picture border must cover it. */
+typedef struct SvtHipObmcSearchDesc {
+    const int32_t *wsrc, *mask;  /* as svt_hip_obmc_target_batch leaves them */
+    const uint8_t *ref;          /* the block's co-located first sample in the reference picture; no alignment is required */
+    uint32_t ref_stride;
+    uint16_t w, h;               /* one of the 22 sizes */
+    SvtHipMv start_mv;           /* cand->mv, 1/8 units */
+    SvtHipMv ref_mv;             /* cand->pred_mv */
+    int32_t  raw_limits[4];      /* col_min, col_max, row_min, row_max in full-pel: x->mv_limits of mode_decision.c:2459-2462 */
+    int32_t  fp_limits[4];       /* the same after svt_av1_set_mv_search_range (svt_hip_obmc_mv_limits gives both) */
+    int32_t  sad_per_bit;        /* x->sadperbit16 */
+    int32_t  error_per_bit;      /* x->errorperbit */
+    int32_t  iters_per_step;     /* the encoder passes 2 */
+    uint8_t  do_full_refine, do_frac_refine; /* the switch over refine_level at mode_decision.c:2430-2443 */
+    uint8_t  fpel_search_range;  /* obmc_ctrls.fpel_search_range: 0 .. 16 */
+    uint8_t  fpel_search_diag;   /* obmc_ctrls.fpel_search_diag: 0: 4 neighbours, otherwise 8 */
+    uint8_t  approx_inter_rate;  /* ctx->approx_inter_rate: the light vector costs */
+    uint8_t  allow_hp;
+    uint8_t  subpel_search_type; /* SVT_HIP_SUBPEL_USE_2_TAPS .. _8_TAPS; the encoder passes 8 taps */
+    uint8_t  forced_stop;        /* 0 .. 3; the encoder passes 0 */
+    uint32_t pad_;
+} SvtHipObmcSearchDesc;
+
+typedef struct SvtHipObmcSearchResult {
+    SvtHipMv best_mv;        /* x->best_mv, 1/8 units */
+    SvtHipMv fullpel_mv;     /* the vector after the full-pel stage, in full-pel units */
+    int32_t  besterr;        /* what the tree returns; 0 without do_frac_refine */
+    int32_t  distortion;     /* dis; 0 without do_frac_refine */
+    uint32_t sse;            /* sse1; 0 without do_frac_refine */
+    int32_t  rate_mv;
+    uint8_t  fullpel_rounds; /* rounds of the full-pel stage that moved the vector */
+    uint8_t  status;         /* SVT_HIP_OBMC_*; non-zero: every other field is 0 */
+    uint8_t  pad_[2];
+} SvtHipObmcSearchResult;
+/* d_result[i] belongs to d_desc[i]; job: mvjcost and the two centred mvcost tables (x->nmv_vec_cost, x->mv_cost_stack), read unless
+ * approx_inter_rate.  SVT_HIP_ERR_BAD_PARAMETER for a NULL job, d_desc or d_result; n == 0 is SVT_HIP_OK and launches nothing.
+ * Asynchronous on `stream`. */
+SVT_HIP_API int32_t svt_hip_obmc_search_batch(const SvtHipSubpelJob *job, const SvtHipObmcSearchDesc *d_desc, SvtHipObmcSearchResult *d_result,
+                                              uint32_t n, void *stream);
+/* mode_decision.c:2459-2462: the full-pel MvLimits of a block at (mi_row, mi_col) of mi_width x mi_height mode-info units in a picture of
+ * mi_rows x mi_cols into raw_limits, and the same after svt_av1_set_mv_search_range around ref_mv into fp_limits (col_min, col_max,
+ * row_min, row_max each).  Host only, no device.  SVT_HIP_ERR_BAD_PARAMETER for a NULL pointer. */
+SVT_HIP_API int32_t svt_hip_obmc_mv_limits(int32_t mi_row, int32_t mi_col, int32_t mi_width, int32_t mi_height, int32_t mi_rows,
+                                           int32_t mi_cols, const SvtHipMv *ref_mv, int32_t raw_limits[4], int32_t fp_limits[4]);
 
 #ifdef __cplusplus
 }

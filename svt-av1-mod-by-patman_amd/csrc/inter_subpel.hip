@@ -7,50 +7,27 @@
 // two iterations per step a round of step s moves the centre by up to 2 s per component, so a candidate lies up to
 // 2 (4 + 2 + 1) = 14 eighths from start_mv: full-pel offsets -2 .. +1, and with the taps 1 .. 6 that the filter tables use the
 // (w + 8) x (h + 8) reference window from 4 above and 4 left of start_mv holds every sample any candidate reads.  It is staged in
-// LDS once.  A candidate is two separable passes over it with a uint8 intermediate in LDS, clipped between the passes as
+// LDS once.  A candidate is two separable passes over it (subpel_device.hpp, shared with inter_obmc.hip) with a uint8 intermediate in LDS, clipped between the passes as
 // svt_aom_convolve8_horiz_c / svt_aom_convolve8_vert_c leave it; a direction without a sub-pel offset filters with the identity kernel, which is exact, so
 // the four cases of svt_aom_upsampled_pred_c are one path.  The bilinear svf of the pruned search is the same path with the
 // bilinear table (its uint16 intermediate never exceeds 255, so the clip changes nothing).  The variance sums cross the lanes
 // by shuffles and the waves through LDS; the search itself is replayed by every lane on those uniform values.
-#include "../../include/svt_hip_inter.h"
-#include "blend_device.hpp"
 #include "common.hpp"
+#include "subpel_device.hpp"
 
 #include <algorithm>
 
 using namespace svthip;
-using svthip::blend::wave_sum;
+using namespace svthip::subpel;
 
 namespace {
 
-constexpr int SUBPEL_MV_LOW = -(1 << 14), SUBPEL_MV_UPP = 1 << 14;  // MV_LOW, MV_UPP (cabac_context_model.h:523-525)
-constexpr int SUBPEL_MAX_FULL_PEL_VAL = (1 << 10) - 1;             // av1me.h:24-27
-constexpr int SUBPEL_SMALL_AREA = 256;                             // the single-wave kernel takes blocks up to this many samples
-
-// av1_bilinear_filters, av1_sub_pel_filters_4 and av1_sub_pel_filters_8 (variance.c:73-140): av1_get_filter(USE_2_TAPS ..
-// USE_8_TAPS), row = subpel_q3 << 1.  Only the even rows are ever addressed.
-__constant__ int16_t SUBPEL_FILTERS[3][8][8] = {
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 0, 0, 112, 16, 0, 0, 0}, {0, 0, 0, 96, 32, 0, 0, 0}, {0, 0, 0, 80, 48, 0, 0, 0},
-     {0, 0, 0, 64, 64, 0, 0, 0}, {0, 0, 0, 48, 80, 0, 0, 0}, {0, 0, 0, 32, 96, 0, 0, 0}, {0, 0, 0, 16, 112, 0, 0, 0}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 0, -8, 122, 18, -4, 0, 0}, {0, 0, -12, 110, 38, -8, 0, 0}, {0, 0, -14, 94, 58, -10, 0, 0},
-     {0, 0, -12, 76, 76, -12, 0, 0}, {0, 0, -10, 58, 94, -14, 0, 0}, {0, 0, -8, 38, 110, -12, 0, 0}, {0, 0, -4, 18, 122, -8, 0, 0}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 2, -10, 122, 18, -4, 0, 0}, {0, 2, -14, 110, 38, -10, 2, 0}, {0, 2, -16, 94, 58, -12, 2, 0},
-     {0, 2, -14, 76, 76, -14, 2, 0}, {0, 2, -12, 58, 94, -16, 2, 0}, {0, 2, -10, 38, 110, -14, 2, 0}, {0, 0, -4, 18, 122, -10, 2, 0}}};
-// first tap that is not zero and one past the last, per table, for a direction with a sub-pel offset
-__constant__ int8_t SUBPEL_TAP_RANGE[3][2] = {{3, 5}, {2, 6}, {1, 7}};
-
-__device__ __forceinline__ int clip_pixel(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
-
-__device__ __forceinline__ int log2_pow2(int v) { return 31 - __clz(v); }
-
 __device__ int subpel_status(const SvtHipSubpelDesc &d, const SvtHipSubpelJob &job) {
-    const int  w = d.w, h = d.h;
-    const bool pow2 = w >= 4 && w <= 128 && h >= 4 && h <= 128 && !(w & (w - 1)) && !(h & (h - 1));
-    if (!pow2 || w > 4 * h || h > 4 * w)  // the 22 sizes: both sides a power of two in 4 .. 128, aspect at most 4 : 1
+    if (!is_block_size(d.w, d.h))
         return SVT_HIP_SUBPEL_BAD_SIZE;
     if (!d.src || !d.ref)
         return SVT_HIP_SUBPEL_BAD_POINTER;
-    if ((d.start_mv.row & 7) || (d.start_mv.col & 7) || abs((int)d.start_mv.row) >= SUBPEL_MV_UPP || abs((int)d.start_mv.col) >= SUBPEL_MV_UPP)
+    if ((d.start_mv.row & 7) || (d.start_mv.col & 7) || abs((int)d.start_mv.row) >= MV_UPP || abs((int)d.start_mv.col) >= MV_UPP)
         return SVT_HIP_SUBPEL_BAD_START_MV;  // (inside MV_LOW .. MV_UPP no candidate leaves int16, so none leaves the window)
     if (d.method > SVT_HIP_SUBPEL_TREE_PRUNED)
         return SVT_HIP_SUBPEL_BAD_METHOD;
@@ -68,8 +45,8 @@ __device__ int mv_err_cost(SvtHipMv mv, const SvtHipSubpelDesc &d, const SvtHipS
     switch (d.mv_cost_type) {
     case 0: {  // MV_COST_ENTROPY: svt_mv_cost (mcomp.h:136-139)
         const int joint = dr == 0 ? (dc == 0 ? 0 : 1) : (dc == 0 ? 2 : 3);
-        const int rate = job.mvjcost[joint] + job.mvcost[0][min(max((int)dr, SUBPEL_MV_LOW), SUBPEL_MV_UPP)] +
-            job.mvcost[1][min(max((int)dc, SUBPEL_MV_LOW), SUBPEL_MV_UPP)];
+        const int rate = job.mvjcost[joint] + job.mvcost[0][min(max((int)dr, MV_LOW), MV_UPP)] +
+            job.mvcost[1][min(max((int)dc, MV_LOW), MV_UPP)];
         return (int)(((int64_t)rate * d.error_per_bit + (1 << 13)) >> 14);  // RDDIV_BITS + AV1_PROB_COST_SHIFT - RD_EPB_SHIFT + 4
     }
     case 1: return (2 * l1) >> 3;  // SSE_LAMBDA_LOWRES
@@ -80,59 +57,24 @@ __device__ int mv_err_cost(SvtHipMv mv, const SvtHipSubpelDesc &d, const SvtHipS
     }
 }
 
-struct Block {          // what a candidate's error is computed from
-    const uint8_t *win; // LDS: the reference window, row 0 / column 0 = 4 above / left of the sample start_mv points at
-    uint8_t       *tmp; // LDS: the intermediate of the first pass, rows 1 .. h + 5 of [h + 7][w]
-    int32_t       *red; // LDS: per-wave partial sums
-    const uint8_t *src; // global
-    int            src_stride, w, h, lw, win_stride, log2_area;
-    int            base_row, base_col;  // start_mv >> 3
-    int            table;               // row of SUBPEL_FILTERS
+struct Block : Window {  // what a candidate's error is computed from: the window from 4 above and 4 left of start_mv, and the source
+    const uint8_t *src;  // global
+    int            src_stride;
 };
 
 struct Error {
     uint32_t var, sse;
 };
 
-// vf(prediction at mv, src): the variance and the sum of squares.  against_128: vf(.., svt_aom_eb_av1_var_offs, 0, ..) instead.  Inlined
-// at each of the search's twenty-odd calls: as a function it costs a call frame in scratch and thirty more VGPRs.
-template <int NT> __device__ __forceinline__ Error candidate_error(const Block b, SvtHipMv mv, bool against_128) {
-    const int tid = threadIdx.x, w = b.w, h = b.h, lw = b.lw, ws = b.win_stride;
-    const int oy = (mv.row >> 3) - b.base_row + 1, ox = (mv.col >> 3) - b.base_col + 1;  // window row / column of tap 0 of sample (0, 0), less 3
-    const int sy = mv.row & 7, sx = mv.col & 7;
-    const int16_t *fx = SUBPEL_FILTERS[b.table][sx], *fy = SUBPEL_FILTERS[b.table][sy];
-    const int kx0 = sx ? SUBPEL_TAP_RANGE[b.table][0] : 3, kx1 = sx ? SUBPEL_TAP_RANGE[b.table][1] : 4;
-    const int ky0 = sy ? SUBPEL_TAP_RANGE[b.table][0] : 3, ky1 = sy ? SUBPEL_TAP_RANGE[b.table][1] : 4;
-    __syncthreads();  // the previous candidate's second pass has read tmp, its sums have been read from red
-    // horizontal pass over the rows the vertical taps reach: tmp row t is reference row t - 3 of the block
-    const int t0 = ky0, rows = h - 1 + ky1 - ky0;
-    for (int i = tid; i < (rows << lw); i += NT) {
-        const int      t = t0 + (i >> lw), c = i & (w - 1);
-        const uint8_t *p = b.win + (t + oy) * ws + c + ox;
-        int            s = 64;
-        for (int k = kx0; k < kx1; k++) s += fx[k] * p[k];
-        b.tmp[(t << lw) + c] = (uint8_t)clip_pixel(s >> 7);
-    }
-    __syncthreads();
+// vf(prediction at mv, src): the variance and the sum of squares.  against_128: vf(.., svt_aom_eb_av1_var_offs, 0, ..) instead.
+template <int NT> __device__ __forceinline__ Error candidate_error(const Block &b, SvtHipMv mv, bool against_128) {
     int      sum = 0;
     uint32_t sse = 0;
-    for (int i = tid; i < (h << lw); i += NT) {
-        const int      r = i >> lw, c = i & (w - 1);
-        const uint8_t *p = b.tmp + (r << lw) + c;
-        int            s = 64;
-        for (int k = ky0; k < ky1; k++) s += fy[k] * p[k << lw];
-        const int diff = clip_pixel(s >> 7) - (against_128 ? 128 : (int)b.src[r * b.src_stride + c]);
+    predict<NT>(b, mv, [&](int, int r, int c, int pre) {
+        const int diff = pre - (against_128 ? 128 : (int)b.src[r * b.src_stride + c]);
         sum += diff, sse += (uint32_t)(diff * diff);
-    }
-    sum = (int)wave_sum((uint32_t)sum), sse = wave_sum(sse);
-    if (NT > 64) {
-        if ((tid & 63) == 0)
-            b.red[2 * (tid >> 6)] = sum, b.red[2 * (tid >> 6) + 1] = (int32_t)sse;
-        __syncthreads();
-        sum = 0, sse = 0;
-#pragma unroll
-        for (int v = 0; v < NT / 64; v++) sum += b.red[2 * v], sse += (uint32_t)b.red[2 * v + 1];
-    }
+    });
+    block_sums<NT>(b.red, sum, sse);
     return {sse - (uint32_t)(((int64_t)sum * sum) >> b.log2_area), sse};
 }
 
@@ -146,11 +88,6 @@ struct Search {  // the running best of one search and what the checks need
 
     __device__ bool in_range(SvtHipMv mv) const {
         return mv.col >= d.col_min && mv.col <= d.col_max && mv.row >= d.row_min && mv.row <= d.row_max;
-    }
-    __device__ static SvtHipMv mv_of(int row, int col) {
-        SvtHipMv mv;
-        mv.row = (int16_t)row, mv.col = (int16_t)col;
-        return mv;
     }
     // the comparison both checks end in; returns whether mv won
     __device__ bool take_if_better(SvtHipMv mv, uint32_t cost, int thismse, uint32_t sse) {
@@ -195,10 +132,10 @@ template <int NT> __device__ void tree_rounds(Search &s, int round, int iters_pe
     for (int iter = 0; iter < round; iter++, hstep >>= 1) {
         const SvtHipMv c = s.best_mv;
         // svt_first_level_check
-        const uint32_t left = s.check<NT>(Search::mv_of(c.row, c.col - hstep)), right = s.check<NT>(Search::mv_of(c.row, c.col + hstep));
-        const uint32_t up = s.check<NT>(Search::mv_of(c.row - hstep, c.col)), down = s.check<NT>(Search::mv_of(c.row + hstep, c.col));
+        const uint32_t left = s.check<NT>(mv_of(c.row, c.col - hstep)), right = s.check<NT>(mv_of(c.row, c.col + hstep));
+        const uint32_t up = s.check<NT>(mv_of(c.row - hstep, c.col)), down = s.check<NT>(mv_of(c.row + hstep, c.col));
         int            step_row = up <= down ? -hstep : hstep, step_col = left <= right ? -hstep : hstep;
-        s.check<NT>(Search::mv_of(c.row + step_row, c.col + step_col));
+        s.check<NT>(mv_of(c.row + step_row, c.col + step_col));
         if ((c.row == s.best_mv.row && c.col == s.best_mv.col) || iters_per_step <= 1)
             continue;
         // svt_second_level_check_v2
@@ -208,36 +145,36 @@ template <int NT> __device__ void tree_rounds(Search &s, int round, int iters_pe
             step_col = -step_col;
         const SvtHipMv m = s.best_mv;
         bool           better = false;
-        s.check<NT>(Search::mv_of(m.row + step_row, m.col), &better);
-        s.check<NT>(Search::mv_of(m.row, m.col + step_col), &better);
+        s.check<NT>(mv_of(m.row + step_row, m.col), &better);
+        s.check<NT>(mv_of(m.row, m.col + step_col), &better);
         if (better)
-            s.check<NT>(Search::mv_of(m.row + step_row, m.col + step_col));
+            s.check<NT>(mv_of(m.row + step_row, m.col + step_col));
     }
 }
 
 // two_level_checks_fast (mcomp.c:378-607)
 template <int NT> __device__ void two_level_checks_fast(Search &s, SvtHipMv t, int hstep, uint32_t orgerr, int iters) {
-    const uint32_t left = s.check_fast<NT>(Search::mv_of(t.row, t.col - hstep)), right = s.check_fast<NT>(Search::mv_of(t.row, t.col + hstep));
-    const uint32_t up = s.check_fast<NT>(Search::mv_of(t.row - hstep, t.col)), down = s.check_fast<NT>(Search::mv_of(t.row + hstep, t.col));
+    const uint32_t left = s.check_fast<NT>(mv_of(t.row, t.col - hstep)), right = s.check_fast<NT>(mv_of(t.row, t.col + hstep));
+    const uint32_t up = s.check_fast<NT>(mv_of(t.row - hstep, t.col)), down = s.check_fast<NT>(mv_of(t.row + hstep, t.col));
     const int      step_row = up <= down ? -hstep : hstep, step_col = left <= right ? -hstep : hstep;
     if (s.besterr >= orgerr)
         return;
-    s.check_fast<NT>(Search::mv_of(t.row + step_row, t.col + step_col));
+    s.check_fast<NT>(mv_of(t.row + step_row, t.col + step_col));
     if (s.besterr >= orgerr || iters <= 1)
         return;
     // second_level_check_fast
     const int br = s.best_mv.row, bc = s.best_mv.col;
     if (t.row != br && t.col != bc) {
-        s.check_fast<NT>(Search::mv_of(br, bc + step_col));
-        s.check_fast<NT>(Search::mv_of(br + step_row, bc));
+        s.check_fast<NT>(mv_of(br, bc + step_col));
+        s.check_fast<NT>(mv_of(br + step_row, bc));
     } else if (t.row == br && t.col != bc) {
-        s.check_fast<NT>(Search::mv_of(br + hstep, bc + step_col));
-        s.check_fast<NT>(Search::mv_of(br - hstep, bc + step_col));
-        s.check_fast<NT>(Search::mv_of(br - step_row, bc));
+        s.check_fast<NT>(mv_of(br + hstep, bc + step_col));
+        s.check_fast<NT>(mv_of(br - hstep, bc + step_col));
+        s.check_fast<NT>(mv_of(br - step_row, bc));
     } else if (t.row != br && t.col == bc) {
-        s.check_fast<NT>(Search::mv_of(br + step_row, bc + hstep));
-        s.check_fast<NT>(Search::mv_of(br + step_row, bc - hstep));
-        s.check_fast<NT>(Search::mv_of(br, bc - step_col));
+        s.check_fast<NT>(mv_of(br + step_row, bc + hstep));
+        s.check_fast<NT>(mv_of(br + step_row, bc - hstep));
+        s.check_fast<NT>(mv_of(br, bc - step_col));
     }
 }
 
@@ -305,7 +242,7 @@ __global__ __launch_bounds__(NT) void subpel_kernel(const SvtHipSubpelJob job, c
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         const SvtHipSubpelDesc d = d_desc[i];
         const int              status = subpel_status(d, job);
-        const bool             large = status != SVT_HIP_SUBPEL_BAD_SIZE && (int)d.w * d.h > SUBPEL_SMALL_AREA;
+        const bool             large = status != SVT_HIP_SUBPEL_BAD_SIZE && (int)d.w * d.h > SMALL_AREA;
         if (large != LARGE)
             continue;
         SvtHipSubpelResult r = {};
@@ -318,7 +255,7 @@ __global__ __launch_bounds__(NT) void subpel_kernel(const SvtHipSubpelJob job, c
         Block b;
         b.win = win, b.tmp = tmp, b.red = red, b.src = d.src, b.src_stride = (int)d.src_stride, b.w = d.w, b.h = d.h;
         b.lw = log2_pow2(d.w), b.win_stride = d.w + 8, b.log2_area = b.lw + log2_pow2(d.h);
-        b.base_row = d.start_mv.row >> 3, b.base_col = d.start_mv.col >> 3;
+        b.base_row = d.start_mv.row >> 3, b.base_col = d.start_mv.col >> 3, b.margin = 4;
         b.table = d.method == SVT_HIP_SUBPEL_TREE_PRUNED ? 0 : d.subpel_search_type - SVT_HIP_SUBPEL_USE_2_TAPS;
         __syncthreads();  // the previous block's last candidate has read win
         const uint8_t *ref = d.ref + ((int64_t)b.base_row - 4) * (int64_t)d.ref_stride + (b.base_col - 4);
@@ -368,7 +305,7 @@ extern "C" int32_t svt_hip_subpel_mv_limits(int32_t mi_row, int32_t mi_col, int3
     int col_min = -(((mi_col + mi_width) * 4) + 4), col_max = (mi_cols - mi_col) * 4 + 4;
     int row_min = -(((mi_row + mi_height) * 4) + 4), row_max = (mi_rows - mi_row) * 4 + 4;
     // svt_av1_set_mv_search_range (av1me.c:205-226)
-    const int mv_low = SUBPEL_MV_LOW, mv_upp = SUBPEL_MV_UPP, max_fp = SUBPEL_MAX_FULL_PEL_VAL;
+    const int mv_low = MV_LOW, mv_upp = MV_UPP, max_fp = MAX_FULL_PEL_VAL;
     col_min = std::max(col_min, std::max((ref_mv->col >> 3) - max_fp + !!(ref_mv->col & 7), (mv_low >> 3) + 1));
     row_min = std::max(row_min, std::max((ref_mv->row >> 3) - max_fp + !!(ref_mv->row & 7), (mv_low >> 3) + 1));
     col_max = std::min(col_max, std::min((ref_mv->col >> 3) + max_fp, (mv_upp >> 3) - 1));

@@ -554,6 +554,41 @@ SUBPEL_DESC_DTYPE = record_dtype(SubpelDesc)       # numpy views of arrays of th
 SUBPEL_RESULT_DTYPE = record_dtype(SubpelResult)
 
 
+OBMC_MAX_NEIGHBOURS = 4                                                          # SVT_HIP_OBMC_* (include/svt_hip_inter.h)
+(OBMC_OK, OBMC_BAD_SIZE, OBMC_BAD_POINTER, OBMC_BAD_SEGMENT, OBMC_BAD_RANGE, OBMC_BAD_START_MV, OBMC_BAD_LIMITS, OBMC_BAD_FILTER,
+ OBMC_BAD_COST) = range(9)
+
+
+class ObmcNeighbour(C.Structure):        # SvtHipObmcNeighbour
+    _fields_ = [("rel_mi", C.c_uint8), ("mi_len", C.c_uint8)]
+
+
+class ObmcTargetDesc(C.Structure):       # SvtHipObmcTargetDesc
+    _fields_ = [("src", C.c_void_p), ("above", C.c_void_p), ("left", C.c_void_p), ("wsrc", C.c_void_p), ("mask", C.c_void_p),
+                ("src_stride", C.c_uint32), ("above_stride", C.c_uint32), ("left_stride", C.c_uint32), ("w", C.c_uint16), ("h", C.c_uint16),
+                ("up_available", C.c_uint8), ("left_available", C.c_uint8), ("n_above", C.c_uint8), ("n_left", C.c_uint8),
+                ("above_nb", ObmcNeighbour * OBMC_MAX_NEIGHBOURS), ("left_nb", ObmcNeighbour * OBMC_MAX_NEIGHBOURS), ("pad_", C.c_uint32)]
+
+
+class ObmcSearchDesc(C.Structure):       # SvtHipObmcSearchDesc
+    _fields_ = [("wsrc", C.c_void_p), ("mask", C.c_void_p), ("ref", C.c_void_p), ("ref_stride", C.c_uint32), ("w", C.c_uint16),
+                ("h", C.c_uint16), ("start_mv", Mv), ("ref_mv", Mv), ("raw_limits", C.c_int32 * 4), ("fp_limits", C.c_int32 * 4),
+                ("sad_per_bit", C.c_int32), ("error_per_bit", C.c_int32), ("iters_per_step", C.c_int32), ("do_full_refine", C.c_uint8),
+                ("do_frac_refine", C.c_uint8), ("fpel_search_range", C.c_uint8), ("fpel_search_diag", C.c_uint8),
+                ("approx_inter_rate", C.c_uint8), ("allow_hp", C.c_uint8), ("subpel_search_type", C.c_uint8), ("forced_stop", C.c_uint8),
+                ("pad_", C.c_uint32)]
+
+
+class ObmcSearchResult(C.Structure):     # SvtHipObmcSearchResult
+    _fields_ = [("best_mv", Mv), ("fullpel_mv", Mv), ("besterr", C.c_int32), ("distortion", C.c_int32), ("sse", C.c_uint32),
+                ("rate_mv", C.c_int32), ("fullpel_rounds", C.c_uint8), ("status", C.c_uint8), ("pad_", C.c_uint8 * 2)]
+
+
+OBMC_TARGET_DESC_DTYPE = record_dtype(ObmcTargetDesc)
+OBMC_SEARCH_DESC_DTYPE = record_dtype(ObmcSearchDesc)
+OBMC_SEARCH_RESULT_DTYPE = record_dtype(ObmcSearchResult)
+
+
 class TxfmParam(C.Structure):            # SvtHipTxfmParam == TxfmParam (definitions.h:1051-1063)
     _fields_ = [("tx_type", C.c_uint8), ("tx_size", C.c_uint8), ("lossless", C.c_int32), ("bd", C.c_int32), ("is_hbd", C.c_int32),
                 ("tx_set_type", C.c_uint8), ("eob", C.c_int32)]

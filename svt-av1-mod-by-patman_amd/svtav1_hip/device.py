@@ -39,10 +39,11 @@ class DeviceBuffer:
         assert arr.nbytes <= self.nbytes
         _call(self.lib, "svt_hip_upload", self.ptr, arr.ctypes.data, arr.nbytes, stream=stream, sync=True)
 
-    def download(self, dtype, shape, stream=None):
+    def download(self, dtype, shape, stream=None, offset=0):
+        """The array of `shape` that starts `offset` bytes into the buffer"""
         out = np.empty(shape, dtype=dtype)
-        assert out.nbytes <= self.nbytes
-        _call(self.lib, "svt_hip_download", out.ctypes.data, self.ptr, out.nbytes, stream=stream, sync=True)
+        assert offset + out.nbytes <= self.nbytes
+        _call(self.lib, "svt_hip_download", out.ctypes.data, self.ptr + offset, out.nbytes, stream=stream, sync=True)
         return out
 
     def fill(self, value, stream=None):
@@ -191,6 +192,13 @@ def upload_descriptors(lib, descs, stream=None):
     return buf
 
 
+def convolve_batch(lib, descs, stream=None, sync=True):
+    """svt_hip_convolve_batch over a list of abi.ConvolveDesc (one launch)."""
+    d_desc = upload_descriptors(lib, descs, stream)
+    _call(lib, "svt_hip_convolve_batch", d_desc.ptr, len(descs), stream=stream, sync=sync)
+    return d_desc
+
+
 def blend_batch(lib, descs, stream=None, sync=True):
     """svt_hip_blend_batch over a list of abi.BlendDesc (one launch)."""
     d_desc = upload_descriptors(lib, descs, stream)
@@ -217,6 +225,27 @@ def subpel_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
     d_out = Guarded(lib, C.sizeof(abi.SubpelResult) * n, guard, fill, stream)
     _call(lib, "svt_hip_subpel_search_batch", C.byref(job), d_desc.ptr, d_out.ptr, n, stream=stream)
     return d_out.read(abi.SUBPEL_RESULT_DTYPE)
+
+
+def obmc_target_batch(lib, descs, stream=None, guard=64, fill=0xA5):
+    """svt_hip_obmc_target_batch over a record array of abi.OBMC_TARGET_DESC_DTYPE (or a list of abi.ObmcTargetDesc), one call.  Returns
+    (the status words, the `guard` bytes before and after them: still `fill` if untouched); wsrc and mask land where the descriptors say."""
+    n = len(descs)
+    d_desc = upload_descriptors(lib, descs, stream)
+    d_out = Guarded(lib, 4 * n, guard, fill, stream)
+    _call(lib, "svt_hip_obmc_target_batch", d_desc.ptr, d_out.ptr, n, stream=stream)
+    return d_out.read(np.uint32)
+
+
+def obmc_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
+    """svt_hip_obmc_search_batch over a record array of abi.OBMC_SEARCH_DESC_DTYPE (or a list of abi.ObmcSearchDesc) under the abi.SubpelJob
+    `job` (one call).  Returns (results as a record array of abi.OBMC_SEARCH_RESULT_DTYPE, the `guard` bytes before and after them: still
+    `fill` if untouched)."""
+    n = len(descs)
+    d_desc = upload_descriptors(lib, descs, stream)
+    d_out = Guarded(lib, C.sizeof(abi.ObmcSearchResult) * n, guard, fill, stream)
+    _call(lib, "svt_hip_obmc_search_batch", C.byref(job), d_desc.ptr, d_out.ptr, n, stream=stream)
+    return d_out.read(abi.OBMC_SEARCH_RESULT_DTYPE)
 
 
 def txb_cost_batch(lib, d_base, descs, tables, w, h, d_txfm_result=None, d_distortion=None, stream=None, tables_in_lds=None, guard=64, fill=0xA5):
