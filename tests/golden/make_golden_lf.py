@@ -16,8 +16,8 @@ import pyorc  # noqa: E402
 
 ref = pyorc.ref()
 store = {}
-for key, lw, lh, bd, is16, fmt, sub, seed in L.GOLDEN_CDEF:
-    filt, strengths, damping, fbs, planes = L.golden_cdef_inputs(lw, lh, bd, is16, fmt, sub, seed)
+for key, lw, lh, bd, is16, fmt, sub, seed, content in L.GOLDEN_CDEF:
+    filt, strengths, damping, fbs, planes = L.golden_cdef_inputs(lw, lh, bd, is16, fmt, sub, seed, content)
     n_fb = ((lw + 63) // 64) * ((lh + 63) // 64)
     ldir, lvar = np.zeros((n_fb, 64), np.uint8), np.zeros((n_fb, 64), np.int32)
     for pli, xdec, ydec, w, h, recon, source in planes:

@@ -36,6 +36,74 @@ def smooth_plane(rng, w, h, bd):
     return np.clip(np.rint(img), 0, (1 << bd) - 1)
 
 
+# ---- harsh whole-picture CDEF content.  smooth_plane only ever yields directions 0 and 7 and filter-block distortions below
+# 2^17; these fill all eight directions (every row of the tap table, odd offsets included) and drive the distortion sums to
+# 2^25 .. 2^28.  Each generator returns (recon, source) as integer arrays clipped to the bit depth.
+CONTENTS = ("oriented", "noise", "ends", "checker", "saturated", "stripes")
+STRENGTHS16 = [0, 1, 2, 3, 4, 9, 18, 27, 35, 44, 52, 63, -1, 60, 15, 7]   # both classes; five zero-primary entries (> one group)
+
+
+def content_plane(kind, rng, w, h, bd):
+    top, sc = (1 << bd) - 1, 1 << (bd - 8)
+    y, x = np.mgrid[0:h, 0:w]
+
+    def noise():
+        return rng.integers(0, top + 1, size=(h, w))
+
+    if kind == "oriented":
+        # every 16x16 tile: a sinusoidal edge pattern at its own angle k * pi / 8, a small jitter, a little noise
+        tx, ty = x // 16, y // 16
+        nty, ntx = (h + 15) // 16, (w + 15) // 16
+        ang = ((tx + 3 * ty) % 8) * np.pi / 8 + rng.uniform(-0.04, 0.04, size=(nty, ntx))[ty, tx]
+        phase = rng.uniform(0, 2 * np.pi, size=(nty, ntx))[ty, tx]
+        u = (x % 16) * np.cos(ang) + (y % 16) * np.sin(ang)
+        recon = np.rint(top * (0.5 + 0.35 * np.sin(2 * np.pi * u / 7.0 + phase))) + rng.integers(-3 * sc, 3 * sc + 1, size=(h, w))
+        source = recon + rng.integers(-40 * sc, 40 * sc + 1, size=(h, w))
+    elif kind == "noise":
+        recon, source = noise(), noise()
+    elif kind == "ends":
+        recon, source = rng.choice(np.array([0, 1, top - 1, top]), size=(h, w)), noise()
+    elif kind == "checker":
+        recon = ((x + y) & 1) * top
+        source = top - recon
+    elif kind == "saturated":
+        recon, source = np.zeros((h, w), np.int64), np.full((h, w), top)
+    elif kind == "stripes":
+        recon, source = ((x // 3 + y // 5) & 1) * top, noise()
+    else:
+        raise ValueError(kind)
+    return np.clip(recon, 0, top).astype(np.int64), np.clip(source, 0, top).astype(np.int64)
+
+
+def content_planes(kind, lw, lh, bd, is16, fmt, seed):
+    """The three planes of one picture of `kind`, chroma from the same generator with another seed:
+    [(pli, xdec, ydec, w, h, recon, source)], rows 11 samples longer than the picture like the other CDEF cases."""
+    dt = np.uint16 if is16 else np.uint8
+    planes = []
+    for pli in range(3):
+        xdec, ydec = int(pli > 0 and fmt != 444), int(pli > 0 and fmt == 420)
+        w, h = lw >> xdec, lh >> ydec
+        recon, source = content_plane(kind, np.random.default_rng(seed + 1000 * pli), w + 11, h, bd)
+        planes.append((pli, xdec, ydec, w, h, recon.astype(dt), source.astype(dt)))
+    return planes
+
+
+def content_filt(lw, lh, kind, seed):
+    """filt8x8 of a picture: all ones, or the random 75 % map with one whole filter block cleared."""
+    w8, h8 = (lw + 7) // 8, (lh + 7) // 8
+    if kind == "ones":
+        return np.ones((h8, w8), np.uint8)
+    filt = (np.random.default_rng(seed + 77).random((h8, w8)) < 0.75).astype(np.uint8)
+    filt[0:8, 8:16] = 0
+    return filt
+
+
+def real_blocks(ldir, lw, lh):
+    """The direction (or variance) entries of the 8x8 blocks inside the picture, out of a [n_fb][64] array."""
+    w8, h8, nhfb = (lw + 7) // 8, (lh + 7) // 8, (lw + 63) // 64
+    return np.array([ldir[(r // 8) * nhfb + c // 8, (r % 8) * 8 + c % 8] for r in range(h8) for c in range(w8)])
+
+
 def cdef_plane(recon, source, pli, xdec, ydec, is16):
     return abi.CdefPlane(recon.ctypes.data, source.ctypes.data, recon.strides[0] // recon.itemsize,
                          source.strides[0] // source.itemsize, recon.shape[1] if False else 0, 0, is16, xdec, ydec, pli)
@@ -122,16 +190,20 @@ def ref_cdef_plane(ref, recon, source, w, h, is16, xdec, ydec, pli, filt, streng
     return mse, applied
 
 
-GOLDEN_CDEF = [  # key, luma w, luma h, bd, is16, fmt, sub, seed
-    ("a_420_8", 200, 136, 8, 0, 420, 2, 5), ("b_420_10", 136, 72, 10, 1, 420, 1, 6), ("c_444_8in16", 72, 136, 8, 1, 444, 4, 7),
-    ("d_420_10_tall", 72, 200, 10, 1, 420, 4, 8)]
+GOLDEN_CDEF = [  # key, luma w, luma h, bd, is16, fmt, sub, seed, content (None: smooth_plane)
+    ("a_420_8", 200, 136, 8, 0, 420, 2, 5, None), ("b_420_10", 136, 72, 10, 1, 420, 1, 6, None),
+    ("c_444_8in16", 72, 136, 8, 1, 444, 4, 7, None), ("d_420_10_tall", 72, 200, 10, 1, 420, 4, 8, None),
+    ("e_oriented_420_8", 136, 72, 8, 0, 420, 1, 9, "oriented"), ("f_noise_420_10", 136, 72, 10, 1, 420, 1, 10, "noise")]
 
 
-def golden_cdef_inputs(lw, lh, bd, is16, fmt, sub, seed):
+def golden_cdef_inputs(lw, lh, bd, is16, fmt, sub, seed, content=None):
     """Seeded inputs of one golden picture: yields per plane (pli, xdec, ydec, w, h, recon, source) + shared parameters."""
     rng = np.random.default_rng(seed)
     w8, h8, nhfb, nvfb = lw // 8, lh // 8, (lw + 63) // 64, (lh + 63) // 64
     filt = (rng.random((h8, w8)) < 0.75).astype(np.uint8)
+    if content:     # harsh content: the 16-entry strength list over both classes, every strength kind among the applied ones
+        fbs = rng.permutation(np.array([2, 37, 63, 0, 1, 22], np.uint8))
+        return filt, STRENGTHS16, 3 + seed % 4, fbs, content_planes(content, lw, lh, bd, is16, fmt, seed)
     strengths = [0, 5, 18, 35, 63, -1, 12, 2]
     damping = 3 + seed % 4
     fbs = rng.choice(np.array([s for s in strengths if s >= 0], np.uint8), size=nhfb * nvfb).astype(np.uint8)

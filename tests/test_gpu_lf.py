@@ -175,6 +175,93 @@ def test_tier_b_picture(hip, orc, lw, lh, bd, is16, sub, fmt):
         assert np.array_equal(got[:, :w], exp[pli][:, :w]), ("frame", pli)
 
 
+def content_cases():
+    """(content, bd, is16, fmt, filt8x8 kind, sub-sampling factor) of test_tier_b_picture_content."""
+    out = []
+    for kind in L.CONTENTS:
+        rich = kind in ("oriented", "noise")
+        for bd, is16 in [(8, 0), (10, 1)] + ([(8, 1)] if rich else []):
+            out += [(kind, bd, is16, 420, "ones", 1), (kind, bd, is16, 420, "map", 1)]
+            if rich:
+                out += [(kind, bd, is16, 444, "map", 1)]
+            if kind == "oriented":   # luma rows 2 / 4 apart; 4:4:4 chroma takes the sub-sampled 8x8 path without the luma distortion
+                out += [(kind, bd, is16, 420, "ones", 2), (kind, bd, is16, 420, "map", 4), (kind, bd, is16, 444, "map", 2),
+                        (kind, bd, is16, 444, "ones", 4)]
+    return out
+
+
+@pytest.mark.parametrize("kind,bd,is16,fmt,filt_kind,sub", content_cases())
+def test_tier_b_picture_content(hip, orc, kind, bd, is16, fmt, filt_kind, sub):
+    """Whole-picture CDEF on content that reaches all eight directions (every row of the packed path's tap table, odd offsets
+    and the shifted tile included) and distortion sums of 2^25 .. 2^28 (lf_cases.content_plane; the conditions on these inputs
+    are asserted in test_lf_oracle.py).  136 x 72: interior, right-edge, bottom-edge and corner filter blocks."""
+    lw, lh, n_fb, cs, seed = 136, 72, 6, bd - 8, 40
+    damping = 3 + (bd + sub + fmt) % 4
+    strengths = L.STRENGTHS16
+    prm = L.search_params(strengths, damping, cs, sub)
+    filt = L.content_filt(lw, lh, filt_kind, seed)
+    # per filter block, luma and chroma apart: primary 0 with a secondary, the strongest pair, and no filtering at all are
+    # among them on blocks that the map leaves on (it clears filter block 1)
+    fbs_y, fbs_uv = np.array([2, 37, 63, 0, 1, 22], np.uint8), np.array([63, 5, 0, 3, 44, 2], np.uint8)
+    for f in (fbs_y, fbs_uv):
+        on = np.delete(f, 1)
+        assert ((on // 4 == 0) & (on % 4 != 0)).any() and (on == 63).any() and (on == 0).any()
+    ldir_o, lvar_o = np.zeros((n_fb, 64), np.uint8), np.zeros((n_fb, 64), np.int32)
+    ddir, dvar = device.DeviceBuffer(hip, n_fb * 64), device.DeviceBuffer(hip, n_fb * 64 * 4)
+    ddir.fill(0), dvar.fill(0)
+    planes = L.content_planes(kind, lw, lh, bd, is16, fmt, seed)
+    exp = []
+    for pli, xdec, ydec, w, h, recon, source in planes:
+        args = (recon, source, w, h, is16, xdec, ydec, pli, filt, prm, fbs_uv if pli else fbs_y, damping, cs)
+        m1, o1 = run_plane_orc(orc, *args, ldir_o, lvar_o, n_fb)
+        m2, o2 = run_plane_gpu(hip, *args, ddir, dvar, n_fb)
+        assert np.array_equal(m1, m2), (pli, np.argwhere(m1 != m2)[:5], m1[m1 != m2][:5], m2[m1 != m2][:5])
+        if pli == 0:
+            assert np.array_equal(ddir.download(np.uint8, (n_fb, 64)), ldir_o)
+            assert np.array_equal(dvar.download(np.int32, (n_fb, 64)), lvar_o)
+        assert np.array_equal(o1[:, :w], o2[:, :w]), (pli, np.argwhere(o1[:, :w] != o2[:, :w])[:5])
+        if kind in ("oriented", "noise"):       # not a comparison of two copies
+            assert not np.array_equal(o1[:, :w], recon[:, :w]), pli
+        exp.append(o1)
+    d_filt, d_fbs, d_fbs_uv = (device.DeviceBuffer(hip, a.nbytes) for a in (filt, fbs_y, fbs_uv))
+    d_filt.upload(filt), d_fbs.upload(fbs_y), d_fbs_uv.upload(fbs_uv)
+    arr, bufs = (abi.CdefPlane * 3)(), []
+    for pli, xdec, ydec, w, h, recon, source in planes:
+        d_in, d_out = device.DeviceBuffer(hip, recon.nbytes), device.DeviceBuffer(hip, recon.nbytes)
+        d_in.upload(recon), d_out.fill(0)
+        arr[pli] = abi.CdefPlane(d_in.ptr, d_out.ptr, recon.shape[1], recon.shape[1], w, h, is16, xdec, ydec, pli)
+        bufs.append((d_in, d_out))
+    st = (C.c_void_p * 3)(d_fbs.ptr, d_fbs_uv.ptr, d_fbs_uv.ptr)
+    device.check(hip, hip.svt_hip_cdef_apply_frame(arr, C.c_uint32(3), V(d_filt.ptr), st, damping, cs, V(ddir.ptr), V(dvar.ptr), None), "cdef_apply_frame")
+    device.check(hip, hip.svt_hip_stream_sync(None), "sync")
+    for pli, xdec, ydec, w, h, recon, source in planes:
+        got = bufs[pli][1].download(recon.dtype, recon.shape)
+        assert np.array_equal(got[:, :w], exp[pli][:, :w]), ("frame", pli)
+
+
+@pytest.mark.parametrize("strengths", [list(range(64)), [0, 1, 2, 3], [1, 2, 3, 0, 2, 1], list(range(4, 64, 4)), [37], [-1, 63, -1, -1, 0, -1]],
+                         ids=["all64", "one_zero_group", "zero_class_two_groups", "no_zero_class", "single", "holes"])
+def test_tier_b_strength_list_shapes(hip, orc, strengths):
+    """The search walks the list in groups of four per class (zero / non-zero primary strength): lists that fill several
+    groups of one class, hold one class only, one entry, or unused (-1) entries, which keep what the table held."""
+    lw, lh, n_fb, bd, is16, seed, damping = 136, 72, 6, 10, 1, 41, 5
+    cs = bd - 8
+    prm = L.search_params(strengths, damping, cs, 1)
+    filt = L.content_filt(lw, lh, "map", seed)
+    fbs = np.zeros(n_fb, np.uint8)
+    ldir_o, lvar_o = np.zeros((n_fb, 64), np.uint8), np.zeros((n_fb, 64), np.int32)
+    ddir, dvar = device.DeviceBuffer(hip, n_fb * 64), device.DeviceBuffer(hip, n_fb * 64 * 4)
+    ddir.fill(0), dvar.fill(0)
+    for pli, xdec, ydec, w, h, recon, source in L.content_planes("oriented", lw, lh, bd, is16, 420, seed)[:2]:
+        args = (recon, source, w, h, is16, xdec, ydec, pli, filt, prm, fbs, damping, cs)
+        m1, _ = run_plane_orc(orc, *args, ldir_o, lvar_o, n_fb)
+        m2, _ = run_plane_gpu(hip, *args, ddir, dvar, n_fb)
+        assert np.array_equal(m1, m2), (pli, np.argwhere(m1 != m2)[:5])
+        used, unused = ([i for i, s in enumerate(strengths) if (s >= 0) == k] for k in (True, False))
+        assert (m1[:, unused] == 0xABCD).all() and (m1[1] == 0xABCD).all()      # unused entries and the cleared filter block
+        assert (np.delete(m1, 1, 0)[:, used] != 0xABCD).all()
+
+
 def test_tier_b_golden(hip):
     """Fixture produced by the reference's own svt_cdef_filter_fb + svt_compute_cdef_dist (tests/golden/make_golden_lf.py)."""
     g = np.load(GOLD)

@@ -174,6 +174,63 @@ def test_cdef_search_and_apply_vs_filter_fb(orc, ref, is16, bd, pli):
     assert np.array_equal(out_apply[:, :w], want_apply[:, :w])
 
 
+def content_search(orc, kind, bd, is16, strengths, lw=136, lh=72, fmt=420, filt_kind="ones", seed=40):
+    """Oracle search of one harsh-content picture (lf_cases.content_planes): (planes, filt, [mse per plane], dir, var)."""
+    n_fb = ((lw + 63) // 64) * ((lh + 63) // 64)
+    planes, filt = L.content_planes(kind, lw, lh, bd, is16, fmt, seed), L.content_filt(lw, lh, filt_kind, seed)
+    prm = L.search_params(strengths, 5, bd - 8, 1)
+    ldir, lvar = np.zeros((n_fb, 64), np.uint8), np.zeros((n_fb, 64), np.int32)
+    out = []
+    for pli, xdec, ydec, w, h, recon, source in planes:
+        st = recon.shape[1]
+        mse = np.full((n_fb, len(strengths)), 0xABCD, np.uint64)
+        orc.orc_cdef_search_plane(C.byref(abi.CdefPlane(recon.ctypes.data, source.ctypes.data, st, st, w, h, is16, xdec, ydec, pli)),
+                                  P(filt), C.byref(prm), P(mse), P(ldir), P(lvar))
+        out.append(mse)
+    return planes, filt, out, ldir, lvar
+
+
+@pytest.mark.parametrize("bd,is16", [(8, 0), (10, 1)])
+def test_cdef_content_conditions(orc, bd, is16):
+    """Conditions on the INPUTS of the whole-picture content tests (test_gpu_lf.py), asserted on the oracle alone: `oriented`
+    spreads the real luma 8x8 blocks over all eight directions (at least 8 % each) and gives every luma filter block at least 32
+    distinct mse values over the 64 strengths; `noise` reaches every direction.  If a re-seeded generator misses these, change the
+    generator, not the bounds."""
+    lw, lh = 136, 72
+    _, _, mse, ldir, _ = content_search(orc, "oriented", bd, is16, list(range(64)))
+    d = L.real_blocks(ldir, lw, lh)
+    assert d.size == 17 * 9
+    hist = np.bincount(d, minlength=8)
+    assert (hist >= 0.08 * d.size).all(), hist
+    for fb in range(mse[0].shape[0]):
+        assert len(set(mse[0][fb].tolist())) >= 32, (fb, mse[0][fb])
+    _, _, _, ldir, _ = content_search(orc, "noise", bd, is16, [0])
+    assert (np.bincount(L.real_blocks(ldir, lw, lh), minlength=8) > 0).all()
+
+
+@pytest.mark.parametrize("bd,is16", [(8, 0), (10, 1)])
+@pytest.mark.parametrize("kind", L.CONTENTS)
+def test_cdef_content_vs_reference(orc, ref, kind, bd, is16):
+    """The oracle's search and apply on every harsh content against the reference's own per-filter-block functions
+    (lf_cases.ref_cdef_plane): pins the oracle for the inputs on which it judges the GPU kernels."""
+    lw, lh, damping, cs = 136, 72, 5, bd - 8
+    strengths = L.STRENGTHS16
+    planes, filt, mse, ldir, lvar = content_search(orc, kind, bd, is16, strengths, filt_kind="map")
+    n_fb = mse[0].shape[0]
+    fbs = np.array([2, 37, 63, 0, 1, 22], np.uint8)
+    rdir, rvar = np.zeros((n_fb, 64), np.uint8), np.zeros((n_fb, 64), np.int32)
+    for (pli, xdec, ydec, w, h, recon, source), m in zip(planes, mse):
+        want_mse, want = L.ref_cdef_plane(ref, recon, source, w, h, is16, xdec, ydec, pli, filt, strengths, fbs, damping, cs, 1, rdir, rvar)
+        st = recon.shape[1]
+        out = np.zeros_like(recon)
+        orc.orc_cdef_apply_plane(C.byref(abi.CdefPlane(recon.ctypes.data, out.ctypes.data, st, st, w, h, is16, xdec, ydec, pli)),
+                                 P(filt), P(fbs), damping, cs, P(ldir), P(lvar))
+        assert np.array_equal(m, want_mse), (pli, np.argwhere(m != want_mse)[:5])
+        assert np.array_equal(out[:, :w], want[:, :w]), pli
+        if pli == 0:
+            assert np.array_equal(ldir, rdir) and np.array_equal(lvar, rvar)
+
+
 def test_cdef_oracle_vs_golden(orc):
     """No reference needed: the committed fixture (made by the reference, tests/golden/make_golden_lf.py) pins the oracle."""
     import os
