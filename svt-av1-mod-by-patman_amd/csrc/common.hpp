@@ -13,6 +13,8 @@ namespace svthip {
 
 // Thread-local error text returned by svt_hip_last_error().
 void set_error(const char *fmt, ...);
+// Refusal of an argument: sets the text, returns SVT_HIP_ERR_BAD_PARAMETER.
+int32_t refuse(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 
 // Calling thread's pooled stream unless the caller passed its own.
 hipStream_t resolve_stream(void *stream);
@@ -63,14 +65,22 @@ struct ThreadState {
 };
 ThreadState &tls();
 
-// The host side of one Tier B entry point, on its stack, after the argument checks:
+// The host side of one Tier B entry point.  Every exported svt_hip_* function that enqueues work (a kernel, a copy, a memset, a
+// synchronisation) opens one on its stack, at the point where its checks ask for the device:
+//     if (!jobs || !n) return refuse("svt_hip_x: bad argument");  // argument checks: no device needed
 //     TierBCall c("svt_hip_x", stream);                       // ensure_init + resolve_stream
 //     const Job *d_jobs = (const Job *)c.stage(jobs, bytes);   // host array -> next ring slot -> device
 //     void *aux = c.take(tls().wiener_aux, bytes, 2 * bytes);  // event-guarded per-thread device buffer
 //     if (!c.ok()) return c.status();
+//     if (!c.check(hipMemsetAsync(out, 0, 8, c.stream()), "hipMemsetAsync")) return c.status();  // any other HIP call
 //     hipLaunchKernelGGL(..., c.stream(), d_jobs, aux);
 //     return c.finish();                                       // launch check, events recorded
-// The status is sticky: after a failed step stage() and take() return nullptr and do nothing.  Whatever the scope took is
+// A failure reads "svt_hip_x: <step>: <HIP's text>", whichever entry point it happens in.  Three kinds of function have no scope and
+// keep SVT_HIP_CHECK: the life-cycle calls that enqueue nothing (init, malloc / free, host_alloc / host_free, stream_create /
+// stream_destroy, the debug read-back, shard.cpp); the readiness helpers (txfm_ready(), tf_filter.hip's ready() and the table uploads
+// behind their call_once), which keep their own ensure_init() because Tier A leaves reach them through TierAStage's `ready`; and
+// launch helpers that a Tier A leaf shares (tf_noise.hip's launch()), which take the scope's stream from their Tier B caller.
+// The status is sticky: after a failed step stage(), take() and check() do nothing and return nullptr / false.  Whatever the scope took is
 // given back -- its event recorded on the stream -- by finish() or, on any earlier return, by the destructor, so no slot
 // can be reused while an upload from it or a kernel that reads it is still in flight.  A nested scope (tf_filter_picture
 // -> me_frames) claims the next ring slot and never touches the outer scope's.  No allocation happens on the launch path
@@ -86,6 +96,7 @@ public:
     hipStream_t stream() const { return st_; }
     void       *stage(const void *host, size_t bytes);                 // 64 KiB minimum, x2 when it grows
     void       *take(GuardedBuf &b, size_t bytes, size_t grow_to);     // grows to grow_to when bytes > b.cap
+    bool        check(hipError_t e, const char *what);                 // a HIP call made on the scope's behalf; false once the scope has failed
     int32_t     finish();
 
 private:

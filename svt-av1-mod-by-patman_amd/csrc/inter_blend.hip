@@ -251,28 +251,24 @@ __global__ __launch_bounds__(64) void mask_search_kernel(const SvtHipMaskSearchD
 }  // namespace
 
 extern "C" int32_t svt_hip_blend_batch(const SvtHipBlendDesc *d_desc, uint32_t n, void *stream) {
-    if (!d_desc || n == 0) {
-        set_error("svt_hip_blend_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(blend_kernel, dim3((n + BLEND_CHUNKS - 1) / BLEND_CHUNKS, BLEND_CHUNKS), dim3(64), 0, resolve_stream(stream), d_desc, n);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    if (!d_desc || n == 0)
+        return refuse("svt_hip_blend_batch: bad argument");
+    TierBCall c("svt_hip_blend_batch", stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(blend_kernel, dim3((n + BLEND_CHUNKS - 1) / BLEND_CHUNKS, BLEND_CHUNKS), dim3(64), 0, c.stream(), d_desc, n);
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_compound_mask_search_batch(const SvtHipMaskSearchDesc *d_desc, SvtHipMaskSearchResult *d_result, uint32_t n,
                                                       void *stream) {
-    if (!d_desc || !d_result || n == 0) {
-        set_error("svt_hip_compound_mask_search_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(mask_search_kernel, dim3(n), dim3(64), 0, resolve_stream(stream), d_desc, d_result);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    if (!d_desc || !d_result || n == 0)
+        return refuse("svt_hip_compound_mask_search_batch: bad argument");
+    TierBCall c("svt_hip_compound_mask_search_batch", stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(mask_search_kernel, dim3(n), dim3(64), 0, c.stream(), d_desc, d_result);
+    return c.finish();
 }
 
 SVT_HIP_MODULE_WARMUP(inter_blend)

@@ -79,15 +79,13 @@ extern "C" int32_t svt_hip_convolve_sr_batch(const SvtHipConvolveDesc *d_desc, u
     return svt_hip_convolve_batch(d_desc, n, stream);
 }
 extern "C" int32_t svt_hip_convolve_batch(const SvtHipConvolveDesc *d_desc, uint32_t n, void *stream) {
-    if (!d_desc || n == 0) {
-        set_error("svt_hip_convolve_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(convolve_sr_kernel, dim3(n, 4), dim3(256), 0, resolve_stream(stream), d_desc);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    if (!d_desc || n == 0)
+        return refuse("svt_hip_convolve_batch: bad argument");
+    TierBCall c("svt_hip_convolve_batch", stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(convolve_sr_kernel, dim3(n, 4), dim3(256), 0, c.stream(), d_desc);
+    return c.finish();
 }
 
 #define SVT_HIP_DEF_CONV(mode, UX, UY)                                                                                          \

@@ -373,10 +373,8 @@ __global__ __launch_bounds__(NT) void obmc_search_kernel(const SvtHipSubpelJob j
 }  // namespace
 
 extern "C" int32_t svt_hip_obmc_target_batch(const SvtHipObmcTargetDesc *d_desc, uint32_t *d_status, uint32_t n, void *stream) {
-    if (!d_desc || !d_status) {
-        set_error("svt_hip_obmc_target_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!d_desc || !d_status)
+        return refuse("svt_hip_obmc_target_batch: bad argument");
     if (n == 0)
         return SVT_HIP_OK;
     TierBCall c("svt_hip_obmc_target_batch", stream);
@@ -390,10 +388,8 @@ extern "C" int32_t svt_hip_obmc_target_batch(const SvtHipObmcTargetDesc *d_desc,
 
 extern "C" int32_t svt_hip_obmc_search_batch(const SvtHipSubpelJob *job, const SvtHipObmcSearchDesc *d_desc, SvtHipObmcSearchResult *d_result,
                                              uint32_t n, void *stream) {
-    if (!job || !d_desc || !d_result) {
-        set_error("svt_hip_obmc_search_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!job || !d_desc || !d_result)
+        return refuse("svt_hip_obmc_search_batch: bad argument");
     if (n == 0)
         return SVT_HIP_OK;
     TierBCall c("svt_hip_obmc_search_batch", stream);
@@ -409,10 +405,8 @@ extern "C" int32_t svt_hip_obmc_search_batch(const SvtHipSubpelJob *job, const S
 
 extern "C" int32_t svt_hip_obmc_mv_limits(int32_t mi_row, int32_t mi_col, int32_t mi_width, int32_t mi_height, int32_t mi_rows,
                                           int32_t mi_cols, const SvtHipMv *ref_mv, int32_t raw_limits[4], int32_t fp_limits[4]) {
-    if (!ref_mv || !raw_limits || !fp_limits) {
-        set_error("svt_hip_obmc_mv_limits: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!ref_mv || !raw_limits || !fp_limits)
+        return refuse("svt_hip_obmc_mv_limits: bad argument");
     // mode_decision.c:2459-2462 (MI_SIZE 4, AOM_INTERP_EXTEND 4)
     raw_limits[0] = -(((mi_col + mi_width) * 4) + 4), raw_limits[1] = (mi_cols - mi_col) * 4 + 4;
     raw_limits[2] = -(((mi_row + mi_height) * 4) + 4), raw_limits[3] = (mi_rows - mi_row) * 4 + 4;

@@ -279,10 +279,8 @@ __global__ __launch_bounds__(NT) void subpel_kernel(const SvtHipSubpelJob job, c
 
 extern "C" int32_t svt_hip_subpel_search_batch(const SvtHipSubpelJob *job, const SvtHipSubpelDesc *d_desc, SvtHipSubpelResult *d_result,
                                                uint32_t n, void *stream) {
-    if (!job || !d_desc || !d_result) {
-        set_error("svt_hip_subpel_search_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!job || !d_desc || !d_result)
+        return refuse("svt_hip_subpel_search_batch: bad argument");
     if (n == 0)
         return SVT_HIP_OK;
     TierBCall c("svt_hip_subpel_search_batch", stream);
@@ -297,10 +295,8 @@ extern "C" int32_t svt_hip_subpel_search_batch(const SvtHipSubpelJob *job, const
 
 extern "C" int32_t svt_hip_subpel_mv_limits(int32_t mi_row, int32_t mi_col, int32_t mi_width, int32_t mi_height, int32_t mi_rows,
                                             int32_t mi_cols, const SvtHipMv *ref_mv, int32_t limits[4]) {
-    if (!ref_mv || !limits) {
-        set_error("svt_hip_subpel_mv_limits: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!ref_mv || !limits)
+        return refuse("svt_hip_subpel_mv_limits: bad argument");
     // product_coding_loop.c:2532-2535 (MI_SIZE 4, AOM_INTERP_EXTEND 4)
     int col_min = -(((mi_col + mi_width) * 4) + 4), col_max = (mi_cols - mi_col) * 4 + 4;
     int row_min = -(((mi_row + mi_height) * 4) + 4), row_max = (mi_rows - mi_row) * 4 + 4;

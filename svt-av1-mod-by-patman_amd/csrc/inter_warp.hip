@@ -259,27 +259,23 @@ int32_t warp_error_once(const SvtHipWarpErrorJob &job, int32_t *mat, int wmtype,
     if (!c.ok())
         return c.status();
     launch_error(job, d_cand, d_result, 1, c.stream());
-    const hipStream_t st = c.stream();
-    const int32_t     rc = c.finish();
-    if (rc != SVT_HIP_OK)
-        return rc;
-    SVT_HIP_CHECK(hipMemcpyAsync(error, d_result, sizeof(int64_t), hipMemcpyDeviceToHost, st));  // the 8-byte read-back
-    SVT_HIP_CHECK(hipStreamSynchronize(st));
-    return SVT_HIP_OK;
+    if (c.finish() != SVT_HIP_OK)  // the staged candidate is given back before the host waits
+        return c.status();
+    if (c.check(hipMemcpyAsync(error, d_result, sizeof(int64_t), hipMemcpyDeviceToHost, c.stream()), "hipMemcpyAsync"))  // the 8-byte read-back
+        c.check(hipStreamSynchronize(c.stream()), "hipStreamSynchronize");
+    return c.status();
 }
 
 }  // namespace
 
 extern "C" int32_t svt_hip_warp_batch(const SvtHipWarpDesc *d_desc, uint32_t n, const int16_t *d_filter, void *stream) {
-    if (!d_desc || !d_filter || n == 0) {
-        set_error("svt_hip_warp_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(warp_kernel, dim3(n, WARP_CHUNKS), dim3(64 * WARP_WAVES), 0, resolve_stream(stream), d_desc, d_filter);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    if (!d_desc || !d_filter || n == 0)
+        return refuse("svt_hip_warp_batch: bad argument");
+    TierBCall c("svt_hip_warp_batch", stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(warp_kernel, dim3(n, WARP_CHUNKS), dim3(64 * WARP_WAVES), 0, c.stream(), d_desc, d_filter);
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_warp_shear_params(const int32_t mat[6], int16_t out[4]) {
@@ -307,25 +303,22 @@ extern "C" uint64_t svt_hip_warp_error_workspace_bytes(uint32_t width, uint32_t 
 
 extern "C" int32_t svt_hip_warp_error_batch(const SvtHipWarpErrorJob *job, const SvtHipWarpCandidate *d_cand, SvtHipWarpErrorResult *d_result,
                                             uint32_t n, void *stream) {
-    if (!d_cand || !d_result || !error_job_ok(job, n)) {
-        set_error("svt_hip_warp_error_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    launch_error(*job, d_cand, d_result, n, resolve_stream(stream));
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    if (!d_cand || !d_result || !error_job_ok(job, n))
+        return refuse("svt_hip_warp_error_batch: bad argument");
+    TierBCall c("svt_hip_warp_error_batch", stream);
+    if (!c.ok())
+        return c.status();
+    launch_error(*job, d_cand, d_result, n, c.stream());
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_gm_refine(const SvtHipWarpErrorJob *job, int32_t wmmat[8], int32_t *wmtype, int32_t n_refinements,
                                      int64_t best_frame_error, int64_t *error, void *stream) {
-    if (!wmmat || !wmtype || !error || *wmtype < IDENTITY || *wmtype > AFFINE || n_refinements < 0 || !error_job_ok(job, 1)) {
-        set_error("svt_hip_gm_refine: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    if (!wmmat || !wmtype || !error || *wmtype < IDENTITY || *wmtype > AFFINE || n_refinements < 0 || !error_job_ok(job, 1))
+        return refuse("svt_hip_gm_refine: bad argument");
+    TierBCall c("svt_hip_gm_refine", stream);  // every evaluation opens its own scope inside this one (warp_error_once)
+    if (!c.ok())
+        return c.status();
     const int type = *wmtype, n_params = 2 * type;  // max_trans_model_params
     int64_t   best_error, step_error;
 #define SVT_HIP_GM_EVAL(out, threshold)                                                                 \
@@ -367,7 +360,7 @@ extern "C" int32_t svt_hip_gm_refine(const SvtHipWarpErrorJob *job, int32_t wmma
     force_wmtype(wmmat, type);
     *wmtype = get_wmtype(wmmat);
     *error = best_error;
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 SVT_HIP_MODULE_WARMUP(inter_warp)

@@ -48,21 +48,19 @@ template <int WAVES> void launch_predict(const SvtHipIntraPredDesc *d_desc, uint
 }
 
 int32_t predict_batch(const char *fn, const SvtHipIntraPredDesc *d_desc, uint32_t n, uint32_t waves, void *stream) {
-    if (!d_desc || n == 0 || (waves != 1 && waves != 2 && waves != 4)) {
-        set_error("%s: bad argument", fn);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t st = resolve_stream(stream);
+    if (!d_desc || n == 0 || (waves != 1 && waves != 2 && waves != 4))
+        return refuse("%s: bad argument", fn);
+    TierBCall c(fn, stream);
+    if (!c.ok())
+        return c.status();
+    hipStream_t st = c.stream();
     if (waves == 4)
         launch_predict<4>(d_desc, n, st);
     else if (waves == 2)
         launch_predict<2>(d_desc, n, st);
     else
         launch_predict<1>(d_desc, n, st);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 }  // namespace
@@ -77,16 +75,14 @@ extern "C" int32_t svt_hip_intra_predict_batch_packed(const SvtHipIntraPredDesc 
 }
 
 extern "C" int32_t svt_hip_cfl_predict_batch(const SvtHipCflDesc *d_desc, uint32_t n, void *stream) {
-    if (!d_desc || n == 0) {
-        set_error("svt_hip_cfl_predict_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    if (!d_desc || n == 0)
+        return refuse("svt_hip_cfl_predict_batch: bad argument");
+    TierBCall c("svt_hip_cfl_predict_batch", stream);
+    if (!c.ok())
+        return c.status();
     hipLaunchKernelGGL(cfl_predict_kernel<PACKED_WAVES>, dim3((n + PACKED_WAVES - 1) / PACKED_WAVES), dim3(64 * PACKED_WAVES), 0,
-                       resolve_stream(stream), d_desc, n);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+                       c.stream(), d_desc, n);
+    return c.finish();
 }
 
 SVT_HIP_MODULE_WARMUP(intra_predict)

@@ -138,14 +138,9 @@ __global__ __launch_bounds__(64) void intra_search_kernel(const SvtHipIntraSearc
 }  // namespace
 
 extern "C" int32_t svt_hip_intra_search_frames(const SvtHipIntraSearchJob *jobs, uint32_t n, void *stream) {
-    auto bad = [](uint32_t i, const char *m) {
-        set_error("svt_hip_intra_search_frames: job %u: %s", i, m);
-        return (int32_t)SVT_HIP_ERR_BAD_PARAMETER;
-    };
-    if (!jobs || n == 0 || n > 65535) {
-        set_error("svt_hip_intra_search_frames: NULL jobs or job count not in 1 .. 65535");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    auto bad = [](uint32_t i, const char *m) { return refuse("svt_hip_intra_search_frames: job %u: %s", i, m); };
+    if (!jobs || n == 0 || n > 65535)
+        return refuse("svt_hip_intra_search_frames: NULL jobs or job count not in 1 .. 65535");
     uint32_t max_cells = 0;
     for (uint32_t i = 0; i < n; i++) {
         const SvtHipIntraSearchJob &jb = jobs[i];

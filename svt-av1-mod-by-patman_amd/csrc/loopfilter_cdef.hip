@@ -652,64 +652,56 @@ __global__ __launch_bounds__(256) void search_one_dual_kernel(const uint64_t *__
 extern "C" int32_t svt_hip_cdef_search_plane(const SvtHipCdefPlane *plane, const uint8_t *d_filt8x8, const SvtHipCdefSearchParams *prm,
                                              uint64_t *d_mse, uint8_t *d_dir, int32_t *d_var, void *stream) {
     if (!plane_ok(plane) || !d_filt8x8 || !prm || !d_mse || !d_dir || !d_var || prm->n_strengths < 1 ||
-        prm->n_strengths > SVT_HIP_CDEF_MAX_STRENGTHS || prm->subsampling_factor < 1) {
-        set_error("svt_hip_cdef_search_plane: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+        prm->n_strengths > SVT_HIP_CDEF_MAX_STRENGTHS || prm->subsampling_factor < 1)
+        return refuse("svt_hip_cdef_search_plane: bad argument");
+    TierBCall c("svt_hip_cdef_search_plane", stream);
+    if (!c.ok())
+        return c.status();
     const int lw = (int)plane->width << plane->xdec, lh = (int)plane->height << plane->ydec;
     const int nhfb = (lw + 63) / 64, nvfb = (lh + 63) / 64;
-    hipLaunchKernelGGL(cdef_search_kernel, dim3(nhfb * nvfb), dim3(256), 0, resolve_stream(stream), *plane, d_filt8x8, *prm, d_mse, d_dir,
+    hipLaunchKernelGGL(cdef_search_kernel, dim3(nhfb * nvfb), dim3(256), 0, c.stream(), *plane, d_filt8x8, *prm, d_mse, d_dir,
                        d_var, nhfb);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_cdef_apply_plane(const SvtHipCdefPlane *plane, const uint8_t *d_filt8x8, const uint8_t *d_fb_strength,
                                             int32_t damping, int32_t coeff_shift, const uint8_t *d_dir, const int32_t *d_var,
                                             void *stream) {
-    if (!plane_ok(plane) || !d_filt8x8 || !d_fb_strength || !d_dir || !d_var || plane->recon == plane->source) {
-        set_error("svt_hip_cdef_apply_plane: bad argument (input and output planes must differ)");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    if (!plane_ok(plane) || !d_filt8x8 || !d_fb_strength || !d_dir || !d_var || plane->recon == plane->source)
+        return refuse("svt_hip_cdef_apply_plane: bad argument (input and output planes must differ)");
+    TierBCall c("svt_hip_cdef_apply_plane", stream);
+    if (!c.ok())
+        return c.status();
     const int lw = (int)plane->width << plane->xdec, lh = (int)plane->height << plane->ydec;
     const int nhfb = (lw + 63) / 64, nvfb = (lh + 63) / 64;
-    hipLaunchKernelGGL(cdef_apply_kernel, dim3(nhfb * nvfb), dim3(256), 0, resolve_stream(stream), *plane, d_filt8x8, d_fb_strength,
+    hipLaunchKernelGGL(cdef_apply_kernel, dim3(nhfb * nvfb), dim3(256), 0, c.stream(), *plane, d_filt8x8, d_fb_strength,
                        damping, coeff_shift, d_dir, d_var, nhfb);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ Tier A
 extern "C" int32_t svt_hip_cdef_apply_frame(const SvtHipCdefPlane *planes, uint32_t n_planes, const uint8_t *d_filt8x8,
                                             const uint8_t *const *fb_strength_dptrs, int32_t damping, int32_t coeff_shift, const uint8_t *d_dir,
                                             const int32_t *d_var, void *stream) {
-    if (!planes || n_planes == 0 || n_planes > 3 || !d_filt8x8 || !fb_strength_dptrs || !d_dir || !d_var) {
-        set_error("svt_hip_cdef_apply_frame: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!planes || n_planes == 0 || n_planes > 3 || !d_filt8x8 || !fb_strength_dptrs || !d_dir || !d_var)
+        return refuse("svt_hip_cdef_apply_frame: bad argument");
     ApplyFrame f{};
     for (uint32_t p = 0; p < n_planes; p++) {
         const int lw = (int)planes[p].width << planes[p].xdec, lh = (int)planes[p].height << planes[p].ydec;
         const int lw0 = (int)planes[0].width << planes[0].xdec, lh0 = (int)planes[0].height << planes[0].ydec;
         if (!plane_ok(&planes[p]) || !fb_strength_dptrs[p] || planes[p].recon == planes[p].source || (lw + 63) / 64 != (lw0 + 63) / 64 ||
-            (lh + 63) / 64 != (lh0 + 63) / 64) {
-            set_error("svt_hip_cdef_apply_frame: plane %u: bad plane (input and output must differ; all planes must cover the same filter blocks)", p);
-            return SVT_HIP_ERR_BAD_PARAMETER;
-        }
+            (lh + 63) / 64 != (lh0 + 63) / 64)
+            return refuse("svt_hip_cdef_apply_frame: plane %u: bad plane (input and output must differ; all planes must cover the same filter blocks)", p);
         f.pl[p] = planes[p], f.strength[p] = fb_strength_dptrs[p];
     }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    TierBCall c("svt_hip_cdef_apply_frame", stream);
+    if (!c.ok())
+        return c.status();
     const int lw = (int)planes[0].width << planes[0].xdec, lh = (int)planes[0].height << planes[0].ydec;
     const int nhfb = (lw + 63) / 64, nvfb = (lh + 63) / 64;
-    hipLaunchKernelGGL(cdef_apply_frame_kernel, dim3(nhfb * nvfb, n_planes), dim3(256), 0, resolve_stream(stream), f, d_filt8x8, damping,
+    hipLaunchKernelGGL(cdef_apply_frame_kernel, dim3(nhfb * nvfb, n_planes), dim3(256), 0, c.stream(), f, d_filt8x8, damping,
                        coeff_shift, d_dir, d_var, nhfb);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 TIER_A_LEAF(void, svt_aom_cdef_find_dir_dual,

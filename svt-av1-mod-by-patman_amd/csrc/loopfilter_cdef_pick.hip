@@ -236,43 +236,32 @@ extern "C" uint64_t svt_hip_cdef_pick_workspace_bytes(uint32_t n_fb, int32_t n_s
 extern "C" int32_t svt_hip_cdef_pick_strengths(const SvtHipCdefPickParams *prm, const uint64_t *d_mse, const uint8_t *d_filt8x8,
                                                SvtHipCdefPickResult *d_result, uint8_t *d_fb_gi, uint8_t *d_fb_strength, void *d_workspace,
                                                uint64_t workspace_bytes, void *stream) {
-    if (!prm || !d_mse || !d_filt8x8 || !d_result || !d_fb_gi || !d_fb_strength || !d_workspace) {
-        set_error("svt_hip_cdef_pick_strengths: NULL argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!prm || !d_mse || !d_filt8x8 || !d_result || !d_fb_gi || !d_fb_strength || !d_workspace)
+        return refuse("svt_hip_cdef_pick_strengths: NULL argument");
     const int n = prm->n_strengths;
-    if (n < 1 || n > MAXN) {
-        set_error("svt_hip_cdef_pick_strengths: n_strengths %d outside 1..%d", n, MAXN);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (n < 1 || n > MAXN)
+        return refuse("svt_hip_cdef_pick_strengths: n_strengths %d outside 1..%d", n, MAXN);
     Lists lists{};
     for (int gi = 0; gi < n; gi++) {
-        if (prm->strengths[gi] < 0 || prm->strengths[gi] > 63 || prm->strengths_uv[gi] < -1 || prm->strengths_uv[gi] > 63) {
-            set_error("svt_hip_cdef_pick_strengths: strengths[%d] = %d (0..63) / strengths_uv[%d] = %d (-1..63) out of range", gi,
-                      prm->strengths[gi], gi, prm->strengths_uv[gi]);
-            return SVT_HIP_ERR_BAD_PARAMETER;
-        }
+        if (prm->strengths[gi] < 0 || prm->strengths[gi] > 63 || prm->strengths_uv[gi] < -1 || prm->strengths_uv[gi] > 63)
+            return refuse("svt_hip_cdef_pick_strengths: strengths[%d] = %d (0..63) / strengths_uv[%d] = %d (-1..63) out of range", gi,
+                                prm->strengths[gi], gi, prm->strengths_uv[gi]);
         lists.y[gi] = prm->strengths[gi], lists.uv[gi] = prm->strengths_uv[gi];
     }
     const uint64_t n_fb64 = (uint64_t)prm->fb_cols * prm->fb_rows;
-    if (n_fb64 == 0 || n_fb64 > (1u << 24)) {
-        set_error("svt_hip_cdef_pick_strengths: filter-block grid %u x %u is empty or too large", prm->fb_cols, prm->fb_rows);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (((uint64_t)prm->w8 + 7) / 8 < prm->fb_cols || ((uint64_t)prm->h8 + 7) / 8 < prm->fb_rows) {
-        set_error("svt_hip_cdef_pick_strengths: filt8x8 of %u x %u does not reach every one of the %u x %u filter blocks", prm->w8, prm->h8,
-                  prm->fb_cols, prm->fb_rows);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (n_fb64 == 0 || n_fb64 > (1u << 24))
+        return refuse("svt_hip_cdef_pick_strengths: filter-block grid %u x %u is empty or too large", prm->fb_cols, prm->fb_rows);
+    if (((uint64_t)prm->w8 + 7) / 8 < prm->fb_cols || ((uint64_t)prm->h8 + 7) / 8 < prm->fb_rows)
+        return refuse("svt_hip_cdef_pick_strengths: filt8x8 of %u x %u does not reach every one of the %u x %u filter blocks", prm->w8, prm->h8,
+                            prm->fb_cols, prm->fb_rows);
     const int n_fb = (int)n_fb64;
-    if (workspace_bytes < ws_bytes(n_fb, n) || ((uintptr_t)d_workspace & 7) || ((uintptr_t)d_result & 7)) {
-        set_error("svt_hip_cdef_pick_strengths: workspace of %llu bytes, %llu needed (workspace and result 8-byte aligned)",
-                  (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_fb, n));
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t     st = resolve_stream(stream);
+    if (workspace_bytes < ws_bytes(n_fb, n) || ((uintptr_t)d_workspace & 7) || ((uintptr_t)d_result & 7))
+        return refuse("svt_hip_cdef_pick_strengths: workspace of %llu bytes, %llu needed (workspace and result 8-byte aligned)",
+                            (unsigned long long)workspace_bytes, (unsigned long long)ws_bytes(n_fb, n));
+    TierBCall c("svt_hip_cdef_pick_strengths", stream);
+    if (!c.ok())
+        return c.status();
+    hipStream_t     st = c.stream();
     const Workspace ws = ws_carve(d_workspace, n_fb, n);
     // slices of filter blocks: enough workgroups to fill the device a few times over, no more atomics than that needs
     const int n_chunks = (n * n + 255) / 256, tiles = (n_fb + TILE - 1) / TILE;
@@ -289,8 +278,7 @@ extern "C" int32_t svt_hip_cdef_pick_strengths(const SvtHipCdefPickParams *prm, 
     }
     hipLaunchKernelGGL(pick_finish, dim3((n_fb + 255) / 256), dim3(256), 0, st, ws, lists, n, n_fb, (uint64_t)prm->lambda, d_result, d_fb_gi,
                        d_fb_strength);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 SVT_HIP_MODULE_WARMUP(loopfilter_cdef_pick)

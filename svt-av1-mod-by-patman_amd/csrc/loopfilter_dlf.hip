@@ -246,18 +246,15 @@ SVT_HIP_DEF_LPF(vertical, 14, 1)
 extern "C" int32_t svt_hip_loop_filter_frame(const SvtHipLfFrame *f, void *stream) {
     if (!f || !f->mi || !f->width || !f->height || f->plane_start > f->plane_end || f->plane_end > 3 || f->mi_stride < f->mi_cols ||
         (f->bit_depth != 8 && f->bit_depth != 10 && f->bit_depth != 12) || (f->bit_depth > 8 && !f->is_16bit) ||
-        f->width > f->mi_cols * 4 || f->height > f->mi_rows * 4 || (f->mi_cols & 1) || (f->mi_rows & 1) || f->sharpness_level > 7) {
-        set_error("svt_hip_loop_filter_frame: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+        f->width > f->mi_cols * 4 || f->height > f->mi_rows * 4 || (f->mi_cols & 1) || (f->mi_rows & 1) || f->sharpness_level > 7)
+        return refuse("svt_hip_loop_filter_frame: bad argument");
     for (int p = f->plane_start; p < f->plane_end; p++)
-        if (!f->plane[p] || !f->stride[p]) {
-            set_error("svt_hip_loop_filter_frame: missing plane");
-            return SVT_HIP_ERR_BAD_PARAMETER;
-        }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t st = resolve_stream(stream);
+        if (!f->plane[p] || !f->stride[p])
+            return refuse("svt_hip_loop_filter_frame: missing plane");
+    TierBCall c("svt_hip_loop_filter_frame", stream);
+    if (!c.ok())
+        return c.status();
+    hipStream_t st = c.stream();
     LfPassArgs  a{};
     uint32_t    np = 0, gx = 0, gy = 0;
     for (int p = f->plane_start; p < f->plane_end; p++) {
@@ -280,8 +277,7 @@ extern "C" int32_t svt_hip_loop_filter_frame(const SvtHipLfFrame *f, void *strea
         hipLaunchKernelGGL(dlf_pass_kernel<0>, dim3(gx, gy, np), dim3(256), 0, st, a);
         hipLaunchKernelGGL(dlf_pass_kernel<1>, dim3(gx, gy, np), dim3(256), 0, st, a);
     }
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 SVT_HIP_MODULE_WARMUP(loopfilter_dlf)

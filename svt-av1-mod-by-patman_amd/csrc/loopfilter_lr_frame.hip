@@ -113,10 +113,8 @@ __global__ __launch_bounds__(LR_NT) void lr_frame_kernel(LrFrame f) {
 }  // namespace
 
 extern "C" int32_t svt_hip_restoration_filter_frame(const SvtHipLrPlane *planes, uint32_t n_planes, void *stream) {
-    if (!planes || n_planes == 0 || n_planes > 3) {
-        set_error("svt_hip_restoration_filter_frame: 1..3 planes");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!planes || n_planes == 0 || n_planes > 3)
+        return refuse("svt_hip_restoration_filter_frame: 1..3 planes");
     LrFrame  f;
     uint32_t gx = 0, gy = 0;
     f.n_planes = n_planes;
@@ -126,20 +124,18 @@ extern "C" int32_t svt_hip_restoration_filter_frame(const SvtHipLrPlane *planes,
         if (!pl.src || !pl.dst || pl.src == pl.dst || !pl.units || !pl.width || !pl.height || pl.src_stride < pl.width || pl.dst_stride < pl.width ||
             pl.ss_x > 1 || pl.ss_y > 1 || !bd_ok || (pl.bit_depth > 8 && !pl.is_16bit) || pl.unit_size < 32 || pl.unit_size > 256 ||
             (pl.unit_size & (pl.unit_size - 1)) || !pl.horz_units || !pl.vert_units ||
-            (!pl.optimized_lr && (!pl.boundary_above || !pl.boundary_below || pl.boundary_stride < pl.width + 2 * SVT_HIP_LR_EXTRA_HORZ))) {
-            set_error("svt_hip_restoration_filter_frame: plane %u: bad argument", p);
-            return SVT_HIP_ERR_BAD_PARAMETER;
-        }
+            (!pl.optimized_lr && (!pl.boundary_above || !pl.boundary_below || pl.boundary_stride < pl.width + 2 * SVT_HIP_LR_EXTRA_HORZ)))
+            return refuse("svt_hip_restoration_filter_frame: plane %u: bad argument", p);
         f.pl[p] = pl;
         const uint32_t pw = 64u >> pl.ss_x, full = 64u >> pl.ss_y, off = 8u >> pl.ss_y;
         const uint32_t nx = (pl.width + pw - 1) / pw, ny = (pl.height + off + full - 1) / full;
         gx = nx > gx ? nx : gx, gy = ny > gy ? ny : gy;
     }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(lr_frame_kernel, dim3(gx, gy, n_planes), dim3(LR_NT), 0, resolve_stream(stream), f);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_restoration_filter_frame", stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(lr_frame_kernel, dim3(gx, gy, n_planes), dim3(LR_NT), 0, c.stream(), f);
+    return c.finish();
 }
 
 SVT_HIP_MODULE_WARMUP(loopfilter_lr_frame)

@@ -281,27 +281,24 @@ template <typename T> const T *decode_ptr(const uint8_t *p, int highbd) {
 // ------------------------------------------------------------------------------------------------ Tier B
 extern "C" int32_t svt_hip_sgr_filter_unit(const SvtHipSgrUnit *unit, int32_t ep, int32_t *d_flt0, int32_t *d_flt1, uint32_t flt_stride,
                                            void *stream) {
-    if (!unit_ok(unit, false) || ep < 0 || ep > 15 || !d_flt0 || !d_flt1 || flt_stride < unit->width) {
-        set_error("svt_hip_sgr_filter_unit: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    if (!unit_ok(unit, false) || ep < 0 || ep > 15 || !d_flt0 || !d_flt1 || flt_stride < unit->width)
+        return refuse("svt_hip_sgr_filter_unit: bad argument");
+    TierBCall c("svt_hip_sgr_filter_unit", stream);
+    if (!c.ok())
+        return c.status();
     const dim3 grid((unit->width + unit->pu_w - 1) / unit->pu_w, (unit->height + unit->pu_h - 1) / unit->pu_h);
-    hipLaunchKernelGGL(sgr_filter_kernel<0>, grid, dim3(SGR_NT), 0, resolve_stream(stream), geom_of(unit), ep, d_flt0, d_flt1, flt_stride,
+    hipLaunchKernelGGL(sgr_filter_kernel<0>, grid, dim3(SGR_NT), 0, c.stream(), geom_of(unit), ep, d_flt0, d_flt1, flt_stride,
                        (void *)nullptr, 0u, 0, 0);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_sgr_apply_unit(const SvtHipSgrUnit *unit, int32_t ep, const int32_t xqd[2], void *d_dst, uint32_t dst_stride,
                                           void *stream) {
-    if (!unit_ok(unit, false) || ep < 0 || ep > 15 || !xqd || !d_dst || dst_stride < unit->width || d_dst == unit->dat) {
-        set_error("svt_hip_sgr_apply_unit: bad argument (output must not alias the input)");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    if (!unit_ok(unit, false) || ep < 0 || ep > 15 || !xqd || !d_dst || dst_stride < unit->width || d_dst == unit->dat)
+        return refuse("svt_hip_sgr_apply_unit: bad argument (output must not alias the input)");
+    TierBCall c("svt_hip_sgr_apply_unit", stream);
+    if (!c.ok())
+        return c.status();
     int xq[2];  // svt_decode_xq (restoration.c:634-645)
     if (SGR_PRM_H[ep][0] == 0)
         xq[0] = 0, xq[1] = (1 << PRJ_BITS) - xqd[1];
@@ -310,10 +307,9 @@ extern "C" int32_t svt_hip_sgr_apply_unit(const SvtHipSgrUnit *unit, int32_t ep,
     else
         xq[0] = xqd[0], xq[1] = (1 << PRJ_BITS) - xq[0] - xqd[1];
     const dim3 grid((unit->width + unit->pu_w - 1) / unit->pu_w, (unit->height + unit->pu_h - 1) / unit->pu_h);
-    hipLaunchKernelGGL(sgr_filter_kernel<1>, grid, dim3(SGR_NT), 0, resolve_stream(stream), geom_of(unit), ep, (int32_t *)nullptr,
+    hipLaunchKernelGGL(sgr_filter_kernel<1>, grid, dim3(SGR_NT), 0, c.stream(), geom_of(unit), ep, (int32_t *)nullptr,
                        (int32_t *)nullptr, 0u, d_dst, dst_stride, xq[0], xq[1]);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 static uint32_t search_flt_stride(uint32_t width) { return ((width + 7) & ~7u) + 8; }  // restoration_pick.c:561
@@ -325,13 +321,12 @@ extern "C" size_t svt_hip_sgr_search_work_bytes(uint32_t width, uint32_t height,
 
 extern "C" int32_t svt_hip_sgr_search_unit(const SvtHipSgrUnit *unit, int32_t start_ep, int32_t end_ep, int32_t ep_inc, int32_t do_refine,
                                            void *d_work, int32_t out[3], int64_t *best_err, void *stream) {
-    if (!unit_ok(unit, true) || start_ep < 0 || end_ep > 16 || ep_inc < 1 || start_ep >= end_ep || !d_work || !out) {
-        set_error("svt_hip_sgr_search_unit: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t    st    = resolve_stream(stream);
+    if (!unit_ok(unit, true) || start_ep < 0 || end_ep > 16 || ep_inc < 1 || start_ep >= end_ep || !d_work || !out)
+        return refuse("svt_hip_sgr_search_unit: bad argument");
+    TierBCall c("svt_hip_sgr_search_unit", stream);
+    if (!c.ok())
+        return c.status();
+    hipStream_t    st    = c.stream();
     const int      n_ep  = (end_ep - start_ep + ep_inc - 1) / ep_inc;
     const uint32_t fs    = search_flt_stride(unit->width);
     const size_t   plane = (size_t)fs * unit->height;
@@ -344,14 +339,14 @@ extern "C" int32_t svt_hip_sgr_search_unit(const SvtHipSgrUnit *unit, int32_t st
     hipLaunchKernelGGL(sgr_search_ep_kernel, dim3(n_ep), dim3(1024), 0, st, *unit, (const int32_t *)work, fs, start_ep, ep_inc, do_refine,
                        res);
     hipLaunchKernelGGL(sgr_pick_kernel, dim3(1), dim3(64), 0, st, (const EpResult *)res, n_ep, res + n_ep);
-    SVT_HIP_CHECK(hipGetLastError());
     EpResult best;
-    SVT_HIP_CHECK(hipMemcpyAsync(&best, res + n_ep, sizeof(best), hipMemcpyDeviceToHost, st));
-    SVT_HIP_CHECK(hipStreamSynchronize(st));
+    if (!c.check(hipGetLastError(), "launch") || !c.check(hipMemcpyAsync(&best, res + n_ep, sizeof(best), hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
+        !c.check(hipStreamSynchronize(st), "hipStreamSynchronize"))
+        return c.status();
     out[0] = best.ep, out[1] = best.xqd[0], out[2] = best.xqd[1];
     if (best_err)
         *best_err = best.err;
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ Tier A

@@ -339,17 +339,13 @@ __global__ __launch_bounds__(256) void wiener_convolve_kernel(const void *__rest
 extern "C" int32_t svt_hip_wiener_stats(const SvtHipWienerUnit *units, uint32_t n_units, int32_t wiener_win, int32_t is_16bit, int32_t bit_depth,
                                         int64_t *d_M, int64_t *d_H, void *stream) {
     if (!units || n_units == 0 || n_units > 65535 || (wiener_win != 7 && wiener_win != 5) || !d_M || !d_H ||
-        (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) || (bit_depth > 8 && !is_16bit)) {
-        set_error("svt_hip_wiener_stats: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+        (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) || (bit_depth > 8 && !is_16bit))
+        return refuse("svt_hip_wiener_stats: bad argument");
     int max_w = 0, max_h = 0;
     for (uint32_t i = 0; i < n_units; i++) {
         const SvtHipWienerUnit &u = units[i];
-        if (!u.dgd || !u.src || u.h_end <= u.h_start || u.v_end <= u.v_start || u.h_end - u.h_start > 4096 || u.v_end - u.v_start > 4096) {
-            set_error("svt_hip_wiener_stats: unit %u: bad limits", i);
-            return SVT_HIP_ERR_BAD_PARAMETER;
-        }
+        if (!u.dgd || !u.src || u.h_end <= u.h_start || u.v_end <= u.v_start || u.h_end - u.h_start > 4096 || u.v_end - u.v_start > 4096)
+            return refuse("svt_hip_wiener_stats: unit %u: bad limits", i);
         max_w = u.h_end - u.h_start > max_w ? u.h_end - u.h_start : max_w;
         max_h = u.v_end - u.v_start > max_h ? u.v_end - u.v_start : max_h;
     }
@@ -390,22 +386,20 @@ extern "C" int32_t svt_hip_wiener_convolve(const void *d_src, uint32_t src_strid
                                            const int16_t filter_x[8], const int16_t filter_y[8], int32_t is_16bit, int32_t bit_depth,
                                            void *stream) {
     if (!d_src || !d_dst || d_src == d_dst || !w || !h || w > 16384 || h > 16384 || !filter_x || !filter_y ||
-        (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) || (bit_depth > 8 && !is_16bit) || filter_x[7] != 0 || filter_y[7] != 0) {
-        set_error("svt_hip_wiener_convolve: bad argument (7-tap kernels with a zero 8th coefficient, output must not alias input)");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+        (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) || (bit_depth > 8 && !is_16bit) || filter_x[7] != 0 || filter_y[7] != 0)
+        return refuse("svt_hip_wiener_convolve: bad argument (7-tap kernels with a zero 8th coefficient, output must not alias input)");
+    TierBCall c("svt_hip_wiener_convolve", stream);
+    if (!c.ok())
+        return c.status();
     Taps f;
     memcpy(f.x, filter_x, 16), memcpy(f.y, filter_y, 16);
     int r0 = 3, r1 = 11;  // get_conv_params_wiener (convolve.h:70-86)
     const int range = bit_depth + 7 - r0 + 2;
     if (range > 16)
         r0 += range - 16, r1 -= range - 16;
-    hipLaunchKernelGGL(wiener_convolve_kernel, dim3((w + 63) / 64, (h + 63) / 64), dim3(256), 0, resolve_stream(stream), d_src, src_stride, d_dst,
+    hipLaunchKernelGGL(wiener_convolve_kernel, dim3((w + 63) / 64, (h + 63) / 64), dim3(256), 0, c.stream(), d_src, src_stride, d_dst,
                        dst_stride, (int)w, (int)h, f, (int)is_16bit, (int)bit_depth, r0, r1);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ Tier A

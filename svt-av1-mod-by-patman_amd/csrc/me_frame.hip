@@ -1586,10 +1586,7 @@ extern "C" uint32_t svt_hip_me_b64_count(uint32_t width, uint32_t height) {
 
 static int32_t validate_job(const SvtHipMeFrameJob &j, uint32_t idx) {
     const SvtHipMeParams &p = j.prm;
-    auto bad = [&](const char *what) {
-        set_error("svt_hip_me_frames: job %u: %s", idx, what);
-        return (int32_t)SVT_HIP_ERR_BAD_PARAMETER;
-    };
+    auto bad = [&](const char *what) { return refuse("svt_hip_me_frames: job %u: %s", idx, what); };
     if (p.num_hme_sa_w != 2 || p.num_hme_sa_h != 2)
         return bad("num_hme_sa_w/h must be 2 (as in the reference, motion_estimation.c:1945)");
     if (p.num_of_list_to_search < 1 || p.num_of_list_to_search > 2)
@@ -1649,10 +1646,8 @@ static int32_t validate_job(const SvtHipMeFrameJob &j, uint32_t idx) {
 }
 
 extern "C" int32_t svt_hip_me_validate_jobs(const SvtHipMeFrameJob *jobs, uint32_t n_jobs, uint32_t *max_b64_out) {
-    if (!jobs || n_jobs == 0 || n_jobs > 65535) {
-        set_error("svt_hip_me_frames: bad job count");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!jobs || n_jobs == 0 || n_jobs > 65535)
+        return refuse("svt_hip_me_frames: bad job count");
     uint32_t max_b64 = 0;
     for (uint32_t i = 0; i < n_jobs; i++) {
         const int32_t rc = validate_job(jobs[i], i);
@@ -1674,15 +1669,13 @@ static void launch_me(const SvtHipMeFrameJob *d_jobs, uint32_t n_jobs, uint32_t 
 }
 
 extern "C" int32_t svt_hip_me_frames_dev(const SvtHipMeFrameJob *d_jobs, uint32_t n_jobs, uint32_t max_b64, void *stream) {
-    if (!d_jobs || n_jobs == 0 || n_jobs > 65535 || max_b64 == 0) {
-        set_error("svt_hip_me_frames_dev: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    launch_me(d_jobs, n_jobs, max_b64, resolve_stream(stream), false);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    if (!d_jobs || n_jobs == 0 || n_jobs > 65535 || max_b64 == 0)
+        return refuse("svt_hip_me_frames_dev: bad argument");
+    TierBCall c("svt_hip_me_frames_dev", stream);
+    if (!c.ok())
+        return c.status();
+    launch_me(d_jobs, n_jobs, max_b64, c.stream(), false);
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_me_frames(const SvtHipMeFrameJob *jobs, uint32_t n_jobs, void *stream) {
@@ -1702,10 +1695,8 @@ extern "C" int32_t svt_hip_me_frames(const SvtHipMeFrameJob *jobs, uint32_t n_jo
 }
 
 extern "C" int32_t svt_hip_install_rtcd_me(void **table, uint32_t n_slots) {
-    if (!table || n_slots < SVT_HIP_SLOT_ME_COUNT) {
-        set_error("svt_hip_install_rtcd_me: table too small");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!table || n_slots < SVT_HIP_SLOT_ME_COUNT)
+        return refuse("svt_hip_install_rtcd_me: table too small");
     if (!ensure_init())
         return SVT_HIP_ERR_NO_DEVICE;  // caller keeps its CPU pointers
     void *fn[SVT_HIP_SLOT_ME_COUNT] = {

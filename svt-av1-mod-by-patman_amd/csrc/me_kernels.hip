@@ -143,19 +143,17 @@ __global__ __launch_bounds__(WG_THREADS) void ext_all_sad_kernel(const uint8_t *
 // ------------------------------------------------------------------------------------------------
 extern "C" int32_t svt_hip_sad_loop_batch(const uint8_t *d_base, const SvtHipSadLoopDesc *d_desc,
                                           SvtHipSadLoopResult *d_result, uint32_t n_desc, void *stream) {
-    if (!d_base || !d_desc || !d_result) {
-        set_error("svt_hip_sad_loop_batch: NULL pointer");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    if (!d_base || !d_desc || !d_result)
+        return refuse("svt_hip_sad_loop_batch: NULL pointer");
+    TierBCall c("svt_hip_sad_loop_batch", stream);
+    if (!c.ok())
+        return c.status();
     if (n_desc == 0)
         return SVT_HIP_OK;
     const uint32_t grid = n_desc < 65535u * 16u ? n_desc : 65535u * 16u;
-    hipLaunchKernelGGL(sad_loop_batch_kernel, dim3(grid), dim3(WG_THREADS), 0, resolve_stream(stream), d_base, d_desc,
+    hipLaunchKernelGGL(sad_loop_batch_kernel, dim3(grid), dim3(WG_THREADS), 0, c.stream(), d_base, d_desc,
                        d_result, n_desc);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 // ------------------------------------------------------------------------------------------------

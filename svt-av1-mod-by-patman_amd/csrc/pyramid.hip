@@ -362,19 +362,16 @@ bool plane_ok(const SvtHipPlane8 *p) {
 
 extern "C" int32_t svt_hip_pyramid_frame(const SvtHipPlane8 *full, const SvtHipPlane8 *quarter,
                                          const SvtHipPlane8 *sixteenth, int32_t hme_level1_enabled, void *stream) {
-    if (!plane_ok(full) || !plane_ok(sixteenth) || (hme_level1_enabled && !plane_ok(quarter))) {
-        set_error("svt_hip_pyramid_frame: bad plane descriptor");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!plane_ok(full) || !plane_ok(sixteenth) || (hme_level1_enabled && !plane_ok(quarter)))
+        return refuse("svt_hip_pyramid_frame: bad plane descriptor");
     // The reference writes the decimated picture at org_x + org_x*stride (pic_analysis_process.c:1934,1953):
     // it only works for org_x == org_y, and so do we.
-    if (sixteenth->org_x != sixteenth->org_y || (hme_level1_enabled && quarter->org_x != quarter->org_y)) {
-        set_error("svt_hip_pyramid_frame: decimated planes need org_x == org_y (reference quirk)");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t    st   = resolve_stream(stream);
+    if (sixteenth->org_x != sixteenth->org_y || (hme_level1_enabled && quarter->org_x != quarter->org_y))
+        return refuse("svt_hip_pyramid_frame: decimated planes need org_x == org_y (reference quirk)");
+    TierBCall c("svt_hip_pyramid_frame", stream);
+    if (!c.ok())
+        return c.status();
+    hipStream_t    st   = c.stream();
     const uint8_t *fsrc = full->buf + full->org_x + (size_t)full->org_y * full->stride;
     auto launch = [&](const uint8_t *in, uint32_t in_stride, const SvtHipPlane8 *o, int step) {
         const uint32_t rows = o->height + 2u * o->org_y;
@@ -392,48 +389,41 @@ extern "C" int32_t svt_hip_pyramid_frame(const SvtHipPlane8 *full, const SvtHipP
     } else {
         launch(fsrc, full->stride, sixteenth, 4);
     }
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_pad_plane(const SvtHipPlane8 *plane, void *stream) {
-    if (!plane_ok(plane)) {
-        set_error("svt_hip_pad_plane: bad plane descriptor");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    if (!plane_ok(plane))
+        return refuse("svt_hip_pad_plane: bad plane descriptor");
+    TierBCall c("svt_hip_pad_plane", stream);
+    if (!c.ok())
+        return c.status();
     dim3 grid((plane->stride + 255) / 256, plane->height + 2u * plane->org_y);
-    hipLaunchKernelGGL(pad_plane_kernel, grid, dim3(256), 0, resolve_stream(stream), plane->buf, plane->stride,
+    hipLaunchKernelGGL(pad_plane_kernel, grid, dim3(256), 0, c.stream(), plane->buf, plane->stride,
                        (uint32_t)plane->width, (uint32_t)plane->height, (uint32_t)plane->org_x, (uint32_t)plane->org_y);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_variance_frame(const SvtHipPlane8 *full, uint16_t *d_variance, uint64_t *d_mean,
                                           int32_t full_precision, void *stream) {
-    if (!plane_ok(full) || !d_variance) {
-        set_error("svt_hip_variance_frame: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    if (!plane_ok(full) || !d_variance)
+        return refuse("svt_hip_variance_frame: bad argument");
+    TierBCall c("svt_hip_variance_frame", stream);
+    if (!c.ok())
+        return c.status();
     const uint32_t bw = (full->width + 63u) / 64u, bh = (full->height + 63u) / 64u, nb = bw * bh;
-    hipLaunchKernelGGL(variance_kernel, dim3((nb + 3) / 4), dim3(256), 0, resolve_stream(stream),
+    hipLaunchKernelGGL(variance_kernel, dim3((nb + 3) / 4), dim3(256), 0, c.stream(),
                        (const uint8_t *)(full->buf + full->org_x + (size_t)full->org_y * full->stride), full->stride, bw,
                        nb, d_variance, d_mean, (int)full_precision);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 // Batched picture analysis: pyramids + variances of n pictures in one fused launch (blockIdx.y = picture), or in the three
 // launches of the single-picture kernels' batch forms (blockIdx.z / .y = picture) when a descriptor has other sizes.
 extern "C" int32_t svt_hip_analysis_frames(const SvtHipAnalysisJob *jobs, uint32_t n_jobs, int32_t hme_level1_enabled,
                                            int32_t full_precision, void *stream) {
-    if (!jobs || n_jobs == 0 || n_jobs > 65535) {
-        set_error("svt_hip_analysis_frames: bad job count");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!jobs || n_jobs == 0 || n_jobs > 65535)
+        return refuse("svt_hip_analysis_frames: bad job count");
     // SVTAV1_HIP_ANALYSIS_FUSED=0: every batch through the three launches, for A/B runs
     static const bool fused_on = !(getenv("SVTAV1_HIP_ANALYSIS_FUSED") && atoi(getenv("SVTAV1_HIP_ANALYSIS_FUSED")) == 0);
     bool              fused    = fused_on;
@@ -441,10 +431,8 @@ extern "C" int32_t svt_hip_analysis_frames(const SvtHipAnalysisJob *jobs, uint32
     for (uint32_t i = 0; i < n_jobs; i++) {
         const SvtHipPyramid8 &y = jobs[i].pyr;
         if (!plane_ok(&y.full) || !plane_ok(&y.sixteenth) || (hme_level1_enabled && !plane_ok(&y.quarter)) || !jobs[i].variance ||
-            y.sixteenth.org_x != y.sixteenth.org_y || (hme_level1_enabled && y.quarter.org_x != y.quarter.org_y)) {
-            set_error("svt_hip_analysis_frames: job %u: bad plane descriptor / missing output", i);
-            return SVT_HIP_ERR_BAD_PARAMETER;
-        }
+            y.sixteenth.org_x != y.sixteenth.org_y || (hme_level1_enabled && y.quarter.org_x != y.quarter.org_y))
+            return refuse("svt_hip_analysis_frames: job %u: bad plane descriptor / missing output", i);
         max_q_stride = y.quarter.stride > max_q_stride ? y.quarter.stride : max_q_stride;
         max_q_rows   = y.quarter.height + 2u * y.quarter.org_y > max_q_rows ? y.quarter.height + 2u * y.quarter.org_y : max_q_rows;
         max_s_stride = y.sixteenth.stride > max_s_stride ? y.sixteenth.stride : max_s_stride;

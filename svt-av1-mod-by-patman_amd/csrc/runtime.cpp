@@ -45,6 +45,14 @@ void set_error(const char *fmt, ...) {
     vsnprintf(t.err, sizeof(t.err), fmt, ap);
     va_end(ap);
 }
+int32_t refuse(const char *fmt, ...) {
+    ThreadState &t = tls();
+    va_list      ap;
+    va_start(ap, fmt);
+    vsnprintf(t.err, sizeof(t.err), fmt, ap);
+    va_end(ap);
+    return SVT_HIP_ERR_BAD_PARAMETER;
+}
 
 bool ensure_init() {
     const int dev = g.device.load();
@@ -193,6 +201,11 @@ void TierBCall::release() {
         held_[i]->held = false;
     }
     n_held_ = 0;
+}
+bool TierBCall::check(hipError_t e, const char *what) {
+    if (e != hipSuccess)
+        fail(e, what);
+    return ok();
 }
 int32_t TierBCall::finish() {
     const hipError_t e = ok() ? hipGetLastError() : hipSuccess;
@@ -361,16 +374,12 @@ int32_t svt_hip_init(int32_t device_ordinal) {
         set_error("no HIP device visible");
         return SVT_HIP_ERR_NO_DEVICE;
     }
-    if (device_ordinal < 0 || device_ordinal >= n) {
-        set_error("device ordinal %d out of range (%d devices)", device_ordinal, n);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (g.sticky.load() >= 0 && g.sticky.load() != device_ordinal) {
-        // per-thread streams, scratch buffers and the once-uploaded constant tables stay on the first device: one process
-        // = one GPU (the multi-GPU layout is one process per GPU)
-        set_error("already bound to device %d: one process drives one GPU", g.sticky.load());
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (device_ordinal < 0 || device_ordinal >= n)
+        return refuse("device ordinal %d out of range (%d devices)", device_ordinal, n);
+    // per-thread streams, scratch buffers and the once-uploaded constant tables stay on the first device: one process
+    // = one GPU (the multi-GPU layout is one process per GPU)
+    if (g.sticky.load() >= 0 && g.sticky.load() != device_ordinal)
+        return refuse("already bound to device %d: one process drives one GPU", g.sticky.load());
     SVT_HIP_CHECK(hipSetDevice(device_ordinal));
     hipDeviceProp_t prop;
     SVT_HIP_CHECK(hipGetDeviceProperties(&prop, device_ordinal));
@@ -422,37 +431,42 @@ int32_t svt_hip_free(void *dptr) {
     return SVT_HIP_OK;
 }
 int32_t svt_hip_memset(void *dptr, int value, size_t bytes, void *stream) {
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    SVT_HIP_CHECK(hipMemsetAsync(dptr, value, bytes, resolve_stream(stream)));
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_memset", stream);
+    if (!c.ok())
+        return c.status();
+    c.check(hipMemsetAsync(dptr, value, bytes, c.stream()), "hipMemsetAsync");
+    return c.finish();
 }
 int32_t svt_hip_upload(void *dptr, const void *hptr, size_t bytes, void *stream) {
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    SVT_HIP_CHECK(hipMemcpyAsync(dptr, hptr, bytes, hipMemcpyHostToDevice, resolve_stream(stream)));
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_upload", stream);
+    if (!c.ok())
+        return c.status();
+    c.check(hipMemcpyAsync(dptr, hptr, bytes, hipMemcpyHostToDevice, c.stream()), "hipMemcpyAsync");
+    return c.finish();
 }
 int32_t svt_hip_download(void *hptr, const void *dptr, size_t bytes, void *stream) {
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    SVT_HIP_CHECK(hipMemcpyAsync(hptr, dptr, bytes, hipMemcpyDeviceToHost, resolve_stream(stream)));
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_download", stream);
+    if (!c.ok())
+        return c.status();
+    c.check(hipMemcpyAsync(hptr, dptr, bytes, hipMemcpyDeviceToHost, c.stream()), "hipMemcpyAsync");
+    return c.finish();
 }
 int32_t svt_hip_upload_2d(void *dptr, size_t dpitch, const void *hptr, size_t hpitch, size_t width_bytes,
                           size_t height, void *stream) {
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    SVT_HIP_CHECK(hipMemcpy2DAsync(dptr, dpitch, hptr, hpitch, width_bytes, height, hipMemcpyHostToDevice,
-                                   resolve_stream(stream)));
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_upload_2d", stream);
+    if (!c.ok())
+        return c.status();
+    c.check(hipMemcpy2DAsync(dptr, dpitch, hptr, hpitch, width_bytes, height, hipMemcpyHostToDevice,
+                                   c.stream()), "hipMemcpy2DAsync");
+    return c.finish();
 }
 int32_t svt_hip_download_2d(void *hptr, size_t hpitch, const void *dptr, size_t dpitch, size_t width_bytes, size_t height,
                             void *stream) {
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    SVT_HIP_CHECK(hipMemcpy2DAsync(hptr, hpitch, dptr, dpitch, width_bytes, height, hipMemcpyDeviceToHost, resolve_stream(stream)));
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_download_2d", stream);
+    if (!c.ok())
+        return c.status();
+    c.check(hipMemcpy2DAsync(hptr, hpitch, dptr, dpitch, width_bytes, height, hipMemcpyDeviceToHost, c.stream()), "hipMemcpy2DAsync");
+    return c.finish();
 }
 int32_t svt_hip_host_alloc(void **hptr, size_t bytes) {
     if (!hptr)
@@ -468,10 +482,11 @@ int32_t svt_hip_host_free(void *hptr) {
     return SVT_HIP_OK;
 }
 int32_t svt_hip_copy(void *d_dst, const void *d_src, size_t bytes, void *stream) {
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    SVT_HIP_CHECK(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, resolve_stream(stream)));
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_copy", stream);
+    if (!c.ok())
+        return c.status();
+    c.check(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, c.stream()), "hipMemcpyAsync");
+    return c.finish();
 }
 int32_t svt_hip_stream_create(void **stream) {
     if (!stream)
@@ -488,10 +503,11 @@ int32_t svt_hip_stream_destroy(void *stream) {
     return SVT_HIP_OK;
 }
 int32_t svt_hip_stream_sync(void *stream) {
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    SVT_HIP_CHECK(hipStreamSynchronize(resolve_stream(stream)));
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_stream_sync", stream);
+    if (!c.ok())
+        return c.status();
+    c.check(hipStreamSynchronize(c.stream()), "hipStreamSynchronize");
+    return c.finish();
 }
 
 }  // extern "C"
@@ -548,10 +564,8 @@ extern "C" int32_t svt_hip_debug_tier_a_broken(int32_t reset) {
 extern "C" int32_t svt_hip_install_rtcd(const SvtHipRtcdBinding *b, uint32_t n, uint32_t *n_installed) {
     if (n_installed)
         *n_installed = 0;
-    if (!b && n) {
-        svthip::set_error("svt_hip_install_rtcd: null binding table");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!b && n)
+        return svthip::refuse("svt_hip_install_rtcd: null binding table");
     if (!svthip::ensure_init())
         return SVT_HIP_ERR_NO_DEVICE;  // nothing installed: the caller keeps its CPU pointers
     if (svthip::tier_a_broken()) {

@@ -131,10 +131,8 @@ int32_t svt_hip_comm_get_unique_id(uint8_t id[SVT_HIP_COMM_ID_BYTES]) {
 }
 
 int32_t svt_hip_comm_create(const uint8_t id[SVT_HIP_COMM_ID_BYTES], int32_t world, int32_t rank, void **comm) {
-    if (!id || !comm || world < 1 || rank < 0 || rank >= world) {
-        set_error("svt_hip_comm_create: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!id || !comm || world < 1 || rank < 0 || rank >= world)
+        return refuse("svt_hip_comm_create: bad argument");
     if (!ensure_init())
         return SVT_HIP_ERR_NO_DEVICE;
     const Rccl *r = rccl();
@@ -160,10 +158,8 @@ int32_t svt_hip_comm_destroy(void *comm) {
 
 int32_t svt_hip_publish_reference(void *d_picture, size_t bytes, int32_t owner, void *comm, void *producer_stream, void *side_stream,
                                   void **done) {
-    if (!d_picture || !bytes || !comm || !side_stream || owner < 0) {
-        set_error("svt_hip_publish_reference: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!d_picture || !bytes || !comm || !side_stream || owner < 0)
+        return refuse("svt_hip_publish_reference: bad argument");
     if (!ensure_init())
         return SVT_HIP_ERR_NO_DEVICE;
     const Rccl *r = rccl();

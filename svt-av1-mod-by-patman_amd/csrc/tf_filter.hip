@@ -271,10 +271,8 @@ void           upload() {
     }
 }
 int32_t ready(const void *p, uint32_t n, const char *who) {
-    if (!p || n == 0) {
-        set_error("%s: bad argument", who);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!p || n == 0)
+        return refuse("%s: bad argument", who);
     if (!ensure_init())
         return SVT_HIP_ERR_NO_DEVICE;
     std::call_once(g_once, upload);
@@ -287,29 +285,33 @@ extern "C" int32_t svt_hip_tf_accumulate_batch(const SvtHipTfBlock *d_blocks, ui
     const int32_t rc = ready(d_blocks, n_blocks, "svt_hip_tf_accumulate_batch");
     if (rc != SVT_HIP_OK)
         return rc;
-    hipLaunchKernelGGL(tf_accumulate_kernel, dim3(n_blocks), dim3(256), 0, resolve_stream(stream), d_blocks);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_tf_accumulate_batch", stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(tf_accumulate_kernel, dim3(n_blocks), dim3(256), 0, c.stream(), d_blocks);
+    return c.finish();
 }
 extern "C" int32_t svt_hip_tf_central_batch(const SvtHipTfBlock *d_blocks, uint32_t n_blocks, void *stream) {
     const int32_t rc = ready(d_blocks, n_blocks, "svt_hip_tf_central_batch");
     if (rc != SVT_HIP_OK)
         return rc;
-    hipLaunchKernelGGL(tf_central_kernel, dim3(n_blocks), dim3(256), 0, resolve_stream(stream), d_blocks);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_tf_central_batch", stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(tf_central_kernel, dim3(n_blocks), dim3(256), 0, c.stream(), d_blocks);
+    return c.finish();
 }
 extern "C" int32_t svt_hip_tf_normalise_batch(const SvtHipTfBlock *d_blocks, const SvtHipTfOut *d_out, uint32_t n_blocks, void *stream) {
     const int32_t rc = ready(d_blocks, n_blocks, "svt_hip_tf_normalise_batch");
     if (rc != SVT_HIP_OK)
         return rc;
-    if (!d_out) {
-        set_error("svt_hip_tf_normalise_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    hipLaunchKernelGGL(tf_normalise_kernel, dim3(n_blocks), dim3(256), 0, resolve_stream(stream), d_blocks, d_out);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    if (!d_out)
+        return refuse("svt_hip_tf_normalise_batch: bad argument");
+    TierBCall c("svt_hip_tf_normalise_batch", stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(tf_normalise_kernel, dim3(n_blocks), dim3(256), 0, c.stream(), d_blocks, d_out);
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_tf_filter_blocks(const SvtHipTfBlock *const *d_ref_blocks, uint32_t n_refs, const SvtHipTfBlock *d_static_blocks,
@@ -317,25 +319,23 @@ extern "C" int32_t svt_hip_tf_filter_blocks(const SvtHipTfBlock *const *d_ref_bl
     const int32_t rc = ready(d_static_blocks, n_blocks, "svt_hip_tf_filter_blocks");
     if (rc != SVT_HIP_OK)
         return rc;
-    if (!d_out || n_refs > SVT_HIP_TF_MAX_REFS || (n_refs && !d_ref_blocks) || ss_x > 1 || ss_y > 1) {
-        set_error("svt_hip_tf_filter_blocks: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!d_out || n_refs > SVT_HIP_TF_MAX_REFS || (n_refs && !d_ref_blocks) || ss_x > 1 || ss_y > 1)
+        return refuse("svt_hip_tf_filter_blocks: bad argument");
     TfRefLists lists;
     memset(&lists, 0, sizeof(lists));
     for (uint32_t r = 0; r < n_refs; r++) {
-        if (!d_ref_blocks[r]) {
-            set_error("svt_hip_tf_filter_blocks: reference %u has no block list", r);
-            return SVT_HIP_ERR_BAD_PARAMETER;
-        }
+        if (!d_ref_blocks[r])
+            return refuse("svt_hip_tf_filter_blocks: reference %u has no block list", r);
         lists.p[r] = d_ref_blocks[r];
     }
+    TierBCall c("svt_hip_tf_filter_blocks", stream);
+    if (!c.ok())
+        return c.status();
     if (ss_x && ss_y)
-        hipLaunchKernelGGL(tf_filter_blocks_kernel<1>, dim3(n_blocks), dim3(256), 0, resolve_stream(stream), lists, n_refs, d_static_blocks, d_out, ss_x, ss_y);
+        hipLaunchKernelGGL(tf_filter_blocks_kernel<1>, dim3(n_blocks), dim3(256), 0, c.stream(), lists, n_refs, d_static_blocks, d_out, ss_x, ss_y);
     else
-        hipLaunchKernelGGL(tf_filter_blocks_kernel<4>, dim3(n_blocks), dim3(256), 0, resolve_stream(stream), lists, n_refs, d_static_blocks, d_out, ss_x, ss_y);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+        hipLaunchKernelGGL(tf_filter_blocks_kernel<4>, dim3(n_blocks), dim3(256), 0, c.stream(), lists, n_refs, d_static_blocks, d_out, ss_x, ss_y);
+    return c.finish();
 }
 
 SVT_HIP_MODULE_WARMUP(tf_filter)

@@ -108,13 +108,13 @@ int32_t tier_a(const void *src, int width, int height, int stride, int is16, int
 
 extern "C" int32_t svt_hip_tf_estimate_noise(const void *d_src, uint32_t width, uint32_t height, uint32_t stride, int32_t is_16bit,
                                              int32_t bit_depth, SvtHipTfNoise *d_out, void *stream) {
-    if (!d_src || !d_out || width == 0 || height == 0 || stride < width || (is_16bit && (bit_depth < 8 || bit_depth > 16))) {
-        set_error("svt_hip_tf_estimate_noise: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    return launch(d_src, width, height, stride, is_16bit, bit_depth, d_out, resolve_stream(stream));
+    if (!d_src || !d_out || width == 0 || height == 0 || stride < width || (is_16bit && (bit_depth < 8 || bit_depth > 16)))
+        return refuse("svt_hip_tf_estimate_noise: bad argument");
+    TierBCall c("svt_hip_tf_estimate_noise", stream);
+    if (!c.ok())
+        return c.status();
+    const int32_t rc = launch(d_src, width, height, stride, is_16bit, bit_depth, d_out, c.stream());  // shared with the Tier A leaves
+    return rc == SVT_HIP_OK ? c.finish() : rc;
 }
 
 TIER_A_LEAF(int32_t, svt_estimate_noise_fp16,

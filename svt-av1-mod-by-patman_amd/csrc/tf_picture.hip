@@ -849,10 +849,7 @@ extern "C" uint64_t svt_hip_tf_workspace_state_offset(uint32_t width, uint32_t h
 }
 
 extern "C" int32_t svt_hip_tf_filter_picture(const SvtHipTfPictureJob *job, void *stream) {
-    auto bad = [](const char *m) {
-        set_error("svt_hip_tf_filter_picture: %s", m);
-        return (int32_t)SVT_HIP_ERR_BAD_PARAMETER;
-    };
+    auto bad = [](const char *m) { return refuse("svt_hip_tf_filter_picture: %s", m); };
     if (!job)
         return bad("NULL job");
     const SvtHipPlane8 &f = job->centre.pyr.full;
@@ -957,13 +954,11 @@ extern "C" int32_t svt_hip_tf_filter_picture(const SvtHipTfPictureJob *job, void
         } else {
             hipLaunchKernelGGL((tf_refine_kernel<false, false>), grid, dim3(256), 0, st, a, d_refs, job->tot_blks);
         }
-        SVT_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(tf_predict_kernel, dim3(nb, job->n_refs), dim3(256), 0, st, d_refs);
         hipLaunchKernelGGL(tf_predict_small_kernel, dim3(nb * SMALL_SPLIT, job->n_refs), dim3(64), 0, st, d_refs);
         if (job->ctrls.enable_8x8_pred)
             hipLaunchKernelGGL(tf_predict8_kernel, dim3(nb, job->n_refs), dim3(256), 0, st, a, d_refs);
     }
-    SVT_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(tf_blocks_kernel, dim3(nb, job->n_refs + 1), dim3(256), 0, st, a, d_refs, job->n_refs, static_blocks, outs);
     if ((rc = c.finish()) != SVT_HIP_OK)
         return rc;

@@ -535,10 +535,7 @@ size_t flag_bytes(uint32_t width, uint32_t height) {
 }  // namespace
 
 extern "C" int32_t svt_hip_tpl_dispenser_frame(const SvtHipTplFrameJob *job, void *stream) {
-    auto bad = [](const char *m) {
-        set_error("svt_hip_tpl_dispenser_frame: %s", m);
-        return (int32_t)SVT_HIP_ERR_BAD_PARAMETER;
-    };
+    auto bad = [](const char *m) { return refuse("svt_hip_tpl_dispenser_frame: %s", m); };
     if (!job)
         return bad("NULL job");
     const SvtHipPlane8 &s = job->src, &r = job->recon;
@@ -581,16 +578,18 @@ extern "C" int32_t svt_hip_tpl_dispenser_frame(const SvtHipTplFrameJob *job, voi
             if (f.max_width > s.width || f.max_height > s.height)
                 return bad("reference picture: max_width / max_height beyond the picture (its planes must be padded by >= 32 samples around them)");
         }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t    st = resolve_stream(stream);
+    TierBCall c("svt_hip_tpl_dispenser_frame", stream);
+    if (!c.ok())
+        return c.status();
+    hipStream_t    st = c.stream();
     const uint32_t aw = (s.width + 7) & ~7u, ah = (s.height + 7) & ~7u, a16 = (aw + 15) >> 4, rows16 = (ah + 15) >> 4;
     // level 5: 32x32 blocks in the complete 64x64 blocks, 16x16 blocks in the incomplete ones (see tpl_kernel)
     const uint32_t nfc = aw >> 6, n16c = ((aw & 63) + 15) >> 4, nfr = ah >> 6;
     const size_t   blocks = b32 ? (size_t)nfr * (4 * nfc + 4 * n16c) + (size_t)(rows16 - 4 * nfr) * a16 : (size_t)a16 * rows16;
     uint8_t       *ws = (uint8_t *)job->workspace;
     const size_t   fb = flag_bytes(s.width, s.height);
-    SVT_HIP_CHECK(hipMemsetAsync(ws, 0, fb + 256, st));
+    if (!c.check(hipMemsetAsync(ws, 0, fb + 256, st), "hipMemsetAsync"))
+        return c.status();
     TplArgs a;
     a.j = *job;
     a.src0 = s.buf + (size_t)s.org_y * s.stride + s.org_x, a.rec0 = r.buf + (size_t)r.org_y * r.stride + r.org_x;
@@ -601,8 +600,7 @@ extern "C" int32_t svt_hip_tpl_dispenser_frame(const SvtHipTplFrameJob *job, voi
         hipLaunchKernelGGL((tpl_kernel<2>), dim3((uint32_t)blocks), dim3(64), 0, st, a);
     else
         hipLaunchKernelGGL((tpl_kernel<0>), dim3((uint32_t)blocks), dim3(64), 0, st, a);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 extern "C" uint64_t svt_hip_tpl_workspace_bytes(uint32_t width, uint32_t height) {

@@ -276,28 +276,24 @@ bool dispatch_txfm(uint32_t w, uint32_t h, uint8_t *base, const SvtHipTxfmDesc *
 // ------------------------------------------------------------------------------------------------ Tier B
 extern "C" int32_t svt_hip_txfm_quant_batch(uint8_t *d_base, const SvtHipTxfmDesc *d_desc, SvtHipTxfmResult *d_result,
                                             uint32_t n_blocks, uint32_t w, uint32_t h, void *stream) {
-    if (!d_base || !d_desc || !d_result) {
-        set_error("svt_hip_txfm_quant_batch: NULL pointer");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!d_base || !d_desc || !d_result)
+        return refuse("svt_hip_txfm_quant_batch: NULL pointer");
     const int32_t rc = txfm_ready();
     if (rc != SVT_HIP_OK)
         return rc;
     if (n_blocks == 0)
         return SVT_HIP_OK;
-    if (!dispatch_txfm(w, h, d_base, d_desc, d_result, n_blocks, resolve_stream(stream), true)) {
-        set_error("svt_hip_txfm_quant_batch: %ux%u is not an AV1 transform size", w, h);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_txfm_quant_batch", stream);
+    if (!c.ok())
+        return c.status();
+    if (!dispatch_txfm(w, h, d_base, d_desc, d_result, n_blocks, c.stream(), true))
+        return refuse("svt_hip_txfm_quant_batch: %ux%u is not an AV1 transform size", w, h);
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_debug_txfm_fallback_blocks(uint32_t *out) {
-    if (!out) {
-        set_error("svt_hip_debug_txfm_fallback_blocks: NULL pointer");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!out)
+        return refuse("svt_hip_debug_txfm_fallback_blocks: NULL pointer");
     *out = 0;
     ThreadState &ts = tls();
     if (!ts.txfm_fast_stream)  // the last batch went to the general kernel alone
@@ -309,18 +305,18 @@ extern "C" int32_t svt_hip_debug_txfm_fallback_blocks(uint32_t *out) {
 
 extern "C" int32_t svt_hip_quantize_batch(uint8_t *d_base, const SvtHipTxfmDesc *d_desc, SvtHipTxfmResult *d_result,
                                           uint32_t n_blocks, uint32_t n_coeffs, void *stream) {
-    if (!d_base || !d_desc || !d_result || n_coeffs == 0) {
-        set_error("svt_hip_quantize_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!d_base || !d_desc || !d_result || n_coeffs == 0)
+        return refuse("svt_hip_quantize_batch: bad argument");
     const int32_t rc = txfm_ready();
     if (rc != SVT_HIP_OK)
         return rc;
     if (n_blocks == 0)
         return SVT_HIP_OK;
-    hipLaunchKernelGGL(quantize_kernel, dim3(n_blocks), dim3(256), 0, resolve_stream(stream), d_base, d_desc, d_result, n_coeffs);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    TierBCall c("svt_hip_quantize_batch", stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(quantize_kernel, dim3(n_blocks), dim3(256), 0, c.stream(), d_base, d_desc, d_result, n_coeffs);
+    return c.finish();
 }
 
 // ------------------------------------------------------------------------------------------------ Tier A

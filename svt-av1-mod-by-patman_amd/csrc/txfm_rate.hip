@@ -201,27 +201,25 @@ extern "C" int32_t svt_hip_txb_cost_batch_placed(const uint8_t *d_base, const Sv
                                                  SvtHipTxbCost *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, uint32_t tables_in_lds,
                                                  void *stream) {
     const TxbGeometry g(w, h);
-    if (!g.valid || n_tables == 0 || (n_blocks > 0 && (!d_base || !d_desc || !d_tables || !d_out))) {
-        set_error("svt_hip_txb_cost_batch: bad argument (%u x %u, %u table sets, %u blocks)", w, h, n_tables, n_blocks);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!g.valid || n_tables == 0 || (n_blocks > 0 && (!d_base || !d_desc || !d_tables || !d_out)))
+        return refuse("svt_hip_txb_cost_batch: bad argument (%u x %u, %u table sets, %u blocks)", w, h, n_tables, n_blocks);
     if (n_blocks == 0)
         return SVT_HIP_OK;
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    TierBCall c("svt_hip_txb_cost_batch_placed", stream);
+    if (!c.ok())
+        return c.status();
     const TxbCostLaunch prm{g.orient, g.txs_ctx, g.sqr, g.sqr_up, (1 - g.tx_scale) * 2, g.pixels >> 6, n_tables, n_blocks};
     const dim3  grid(grid_blocks(n_blocks, 256 / group_lanes(g.retained), (uint32_t)cu_count() * 8));  // 8 workgroups fill a CU's wave slots
     const bool  launched = for_retained_shape(g.iw, g.ih, [&](auto W, auto H) {
         constexpr int IW = decltype(W)::value, IH = decltype(H)::value;
         const auto    kernel = tables_in_lds ? txb_cost_kernel<IW, IH, true> : txb_cost_kernel<IW, IH, false>;
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, resolve_stream(stream), d_base, d_desc, d_tables, d_txfm_result, d_distortion, d_out, prm);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.stream(), d_base, d_desc, d_tables, d_txfm_result, d_distortion, d_out, prm);
     });
     if (!launched) {
         set_error("svt_hip_txb_cost_batch: no kernel for the retained shape %u x %u", g.iw, g.ih);
         return SVT_HIP_ERR_RUNTIME;
     }
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_txb_cost_batch(const uint8_t *d_base, const SvtHipTxbCostDesc *d_desc, const SvtHipRateTables *d_tables,

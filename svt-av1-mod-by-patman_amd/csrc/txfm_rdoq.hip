@@ -528,14 +528,13 @@ extern "C" int32_t svt_hip_rdoq_batch_mapped(uint8_t *d_base, const SvtHipTxfmDe
                                              SvtHipRdoqResult *d_out, uint32_t n_blocks, uint32_t w, uint32_t h, uint32_t mapping, void *stream) {
     const TxbGeometry g(w, h);
     const bool        is_mapping = mapping <= 1 || (mapping == 2 && g.retained <= kLaneMax);
-    if (!g.valid || !is_mapping || n_tables == 0 || (n_blocks > 0 && (!d_base || !d_txfm_desc || !d_desc || !d_tables || !d_txfm_result || !d_out))) {
-        set_error("svt_hip_rdoq_batch: bad argument (%u x %u, %u table sets, %u blocks)", w, h, n_tables, n_blocks);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!g.valid || !is_mapping || n_tables == 0 || (n_blocks > 0 && (!d_base || !d_txfm_desc || !d_desc || !d_tables || !d_txfm_result || !d_out)))
+        return refuse("svt_hip_rdoq_batch: bad argument (%u x %u, %u table sets, %u blocks)", w, h, n_tables, n_blocks);
     if (n_blocks == 0)
         return SVT_HIP_OK;
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    TierBCall c("svt_hip_rdoq_batch_mapped", stream);
+    if (!c.ok())
+        return c.status();
     const RdoqLaunch prm{g.orient, g.txs_ctx, g.tx_scale, (int32_t)g.sqrt_retained, g.pixels, n_tables, n_blocks};
     const dim3  grid(grid_blocks(n_blocks, mapping == 2 ? 64 : 64 / group_lanes(g.retained), (uint32_t)cu_count() * 16));
     const bool  launched = for_retained_shape(g.iw, g.ih, [&](auto W, auto H) {
@@ -543,14 +542,13 @@ extern "C" int32_t svt_hip_rdoq_batch_mapped(uint8_t *d_base, const SvtHipTxfmDe
         auto          kernel = mapping == 1 ? rdoq_kernel<IW, IH, true, false> : rdoq_kernel<IW, IH, false, false>;
         if constexpr ((uint32_t)(IW * IH) <= kLaneMax)  // where the lane-per-block instance exists; is_mapping refused it elsewhere
             kernel = mapping == 2 ? rdoq_kernel<IW, IH, false, true> : kernel;
-        hipLaunchKernelGGL(kernel, grid, dim3(64), 0, resolve_stream(stream), d_base, d_txfm_desc, d_desc, d_tables, d_txfm_result, d_out, prm);
+        hipLaunchKernelGGL(kernel, grid, dim3(64), 0, c.stream(), d_base, d_txfm_desc, d_desc, d_tables, d_txfm_result, d_out, prm);
     });
     if (!launched) {
         set_error("svt_hip_rdoq_batch: no kernel for the retained shape %u x %u", g.iw, g.ih);
         return SVT_HIP_ERR_RUNTIME;
     }
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 extern "C" int32_t svt_hip_rdoq_batch(uint8_t *d_base, const SvtHipTxfmDesc *d_txfm_desc, const SvtHipRdoqDesc *d_desc,

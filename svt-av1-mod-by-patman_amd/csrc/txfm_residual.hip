@@ -173,14 +173,14 @@ TIER_A_LEAF(void, svt_residual_kernel16bit,
 // every trial of the deblocking level search): *d_out (device, 8 bytes) is zeroed by the call and holds the sum when the stream has run
 extern "C" int32_t svt_hip_plane_sse(const void *d_a, uint32_t a_stride, const void *d_b, uint32_t b_stride, uint32_t width, uint32_t height, int32_t is_16bit,
                                      uint64_t *d_out, void *stream) {
-    if (!d_a || !d_b || !d_out || !width || !height) {
-        set_error("svt_hip_plane_sse: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipStream_t st = resolve_stream(stream);
-    SVT_HIP_CHECK(hipMemsetAsync(d_out, 0, 8, st));
+    if (!d_a || !d_b || !d_out || !width || !height)
+        return refuse("svt_hip_plane_sse: bad argument");
+    TierBCall c("svt_hip_plane_sse", stream);
+    if (!c.ok())
+        return c.status();
+    hipStream_t st = c.stream();
+    if (!c.check(hipMemsetAsync(d_out, 0, 8, st), "hipMemsetAsync"))
+        return c.status();
     const size_t pix = (size_t)width * height;
     const int    blocks = (int)((pix + 255) / 256 < 1024 ? (pix + 255) / 256 : 1024);
     if (is_16bit)
@@ -189,8 +189,7 @@ extern "C" int32_t svt_hip_plane_sse(const void *d_a, uint32_t a_stride, const v
     else
         hipLaunchKernelGGL((spatial_sse_kernel<uint8_t>), dim3(blocks), dim3(256), 0, st, (const uint8_t *)d_a, (int)a_stride, (const uint8_t *)d_b, (int)b_stride, (int)width,
                            (int)height, (unsigned long long *)d_out);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 // svt_spatial_full_distortion_kernel (common_dsp_rtcd.h:171; picture_operators_c.c:62-78) and svt_full_distortion_kernel16_bits
@@ -253,18 +252,16 @@ TIER_A_LEAF(void, svt_full_distortion_kernel_cbf_zero32_bits,
 extern "C" int32_t svt_hip_txfm_distortion_batch(const uint8_t *d_base, const SvtHipTxfmDesc *d_desc, uint64_t (*d_result)[2],
                                                  uint32_t n_blocks, uint32_t w, uint32_t h, void *stream) {
     const bool ok_w = w == 4 || w == 8 || w == 16 || w == 32 || w == 64, ok_h = h == 4 || h == 8 || h == 16 || h == 32 || h == 64;
-    if (!d_base || !d_desc || !d_result || !ok_w || !ok_h) {
-        set_error("svt_hip_txfm_distortion_batch: bad argument");
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    if (!d_base || !d_desc || !d_result || !ok_w || !ok_h)
+        return refuse("svt_hip_txfm_distortion_batch: bad argument");
+    TierBCall c("svt_hip_txfm_distortion_batch", stream);
+    if (!c.ok())
+        return c.status();
     if (n_blocks == 0)
         return SVT_HIP_OK;
-    hipLaunchKernelGGL(distortion_batch_kernel, dim3((n_blocks + 3) / 4), dim3(256), 0, resolve_stream(stream), d_base, d_desc, d_result,
+    hipLaunchKernelGGL(distortion_batch_kernel, dim3((n_blocks + 3) / 4), dim3(256), 0, c.stream(), d_base, d_desc, d_result,
                        n_blocks, (int)(w < 32 ? w : 32), (int)(h < 32 ? h : 32));
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 SVT_HIP_MODULE_WARMUP(txfm_residual)

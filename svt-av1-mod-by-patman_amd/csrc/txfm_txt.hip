@@ -284,18 +284,16 @@ struct SearchScratch {
 extern "C" int32_t svt_hip_txfm_spatial_distortion_batch(const uint8_t *d_base, const SvtHipTxfmDesc *d_desc, const SvtHipSpatialSrc *d_src,
                                                          uint64_t (*d_distortion)[2], uint32_t n_blocks, uint32_t w, uint32_t h, void *stream) {
     const TxbGeometry g(w, h);
-    if (!g.valid || (n_blocks > 0 && (!d_base || !d_desc || !d_src || !d_distortion))) {
-        set_error("svt_hip_txfm_spatial_distortion_batch: bad argument (%u x %u, %u blocks)", w, h, n_blocks);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+    if (!g.valid || (n_blocks > 0 && (!d_base || !d_desc || !d_src || !d_distortion)))
+        return refuse("svt_hip_txfm_spatial_distortion_batch: bad argument (%u x %u, %u blocks)", w, h, n_blocks);
     if (n_blocks == 0)
         return SVT_HIP_OK;
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(spatial_distortion_kernel<false>, dim3((n_blocks + 3) / 4), dim3(256), 0, resolve_stream(stream), d_base, d_desc, d_src,
+    TierBCall c("svt_hip_txfm_spatial_distortion_batch", stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(spatial_distortion_kernel<false>, dim3((n_blocks + 3) / 4), dim3(256), 0, c.stream(), d_base, d_desc, d_src,
                        (const SvtHipTxtDesc *)nullptr, d_distortion, n_blocks, n_blocks, w, h);
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 
 namespace {
@@ -306,16 +304,15 @@ int32_t select_batch(uint8_t *d_base, const SvtHipTxtDesc *d_desc, const SvtHipT
                      uint32_t w, uint32_t h, uint32_t mapping, bool recon, void *stream) {
     const TxbGeometry g(w, h);
     if (!g.valid || mapping > 1 || n_tables == 0 ||
-        (n_blocks > 0 && (!d_base || !d_desc || !d_txfm_desc || !d_cost_desc || !d_tables || !d_txfm_result || !d_distortion || !d_cost || !d_out))) {
-        set_error("svt_hip_txt_select_batch: bad argument (%u x %u, %u table sets, %u blocks, mapping %u)", w, h, n_tables, n_blocks, mapping);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+        (n_blocks > 0 && (!d_base || !d_desc || !d_txfm_desc || !d_cost_desc || !d_tables || !d_txfm_result || !d_distortion || !d_cost || !d_out)))
+        return refuse("svt_hip_txt_select_batch: bad argument (%u x %u, %u table sets, %u blocks, mapping %u)", w, h, n_tables, n_blocks, mapping);
     if (n_blocks == 0)
         return SVT_HIP_OK;
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    TierBCall c("svt_hip_txt_select_batch", stream);
+    if (!c.ok())
+        return c.status();
     const TxtLaunch   prm{g.sqr, g.sqr_up, (1 - g.tx_scale) * 2, g.retained, w, h, n_tables, n_cand_total, n_blocks, recon ? 1u : 0u};
-    const hipStream_t st = resolve_stream(stream);
+    const hipStream_t st = c.stream();
     const uint32_t    cap = (uint32_t)cu_count() * 16;
     if (mapping == 0) {
         hipLaunchKernelGGL(select_gather_kernel, dim3(grid_blocks(n_blocks, 64, cap)), dim3(64), 0, st, d_base, d_desc, d_txfm_desc, d_cost_desc, d_tables,
@@ -326,8 +323,7 @@ int32_t select_batch(uint8_t *d_base, const SvtHipTxtDesc *d_desc, const SvtHipT
         hipLaunchKernelGGL(gather_kernel, dim3(grid_blocks(n_blocks, 4, cap)), dim3(256), 0, st, d_base, d_desc, d_txfm_desc,
                            (const SvtHipTxtResult *)d_out, prm);
     }
-    SVT_HIP_CHECK(hipGetLastError());
-    return SVT_HIP_OK;
+    return c.finish();
 }
 }  // namespace
 
@@ -361,21 +357,20 @@ extern "C" int32_t svt_hip_txt_search_batch(uint8_t *d_base, const SvtHipTxfmDes
     const TxbGeometry g(w, h);
     const SearchScratch s(n_cand);
     if (!g.valid || n_tables == 0 ||
-        (n_blocks > 0 && (!d_base || !d_txfm_desc || !d_cost_desc || !d_tables || !d_desc || !d_scratch || !d_out || scratch_bytes < s.bytes))) {
-        set_error("svt_hip_txt_search_batch: bad argument (%u x %u, %u table sets, %u candidates of %u blocks, %zu bytes of scratch where %zu are needed)",
-                  w, h, n_tables, n_cand, n_blocks, scratch_bytes, s.bytes);
-        return SVT_HIP_ERR_BAD_PARAMETER;
-    }
+        (n_blocks > 0 && (!d_base || !d_txfm_desc || !d_cost_desc || !d_tables || !d_desc || !d_scratch || !d_out || scratch_bytes < s.bytes)))
+        return refuse("svt_hip_txt_search_batch: bad argument (%u x %u, %u table sets, %u candidates of %u blocks, %zu bytes of scratch where %zu are needed)",
+                      w, h, n_tables, n_cand, n_blocks, scratch_bytes, s.bytes);
     if (n_blocks == 0)
         return SVT_HIP_OK;
-    if (!ensure_init())
-        return SVT_HIP_ERR_NO_DEVICE;
+    TierBCall c("svt_hip_txt_search_batch", stream);
+    if (!c.ok())
+        return c.status();
     uint8_t *const          scratch = (uint8_t *)d_scratch;
     SvtHipTxfmResult *const result_a = (SvtHipTxfmResult *)(scratch + s.result_a), *const result_b = (SvtHipTxfmResult *)(scratch + s.result_b);
     SvtHipRdoqResult *const rdoq = d_rdoq_desc ? (SvtHipRdoqResult *)(scratch + s.rdoq) : nullptr;
     uint64_t(*const dist)[2] = (uint64_t(*)[2])(scratch + s.dist);
     SvtHipTxbCost *const cost = (SvtHipTxbCost *)(scratch + s.cost);
-    const hipStream_t    st = resolve_stream(stream);
+    const hipStream_t    st = c.stream();
     int32_t              rc = SVT_HIP_OK;
     if (n_cand > 0) {
         if ((rc = svt_hip_txfm_quant_batch(d_base, d_txfm_desc, result_a, n_cand, w, h, st)) != SVT_HIP_OK)
@@ -389,7 +384,6 @@ extern "C" int32_t svt_hip_txt_search_batch(uint8_t *d_base, const SvtHipTxfmDes
                 set_error("svt_hip_txt_search_batch: no inverse kernel for %u x %u", w, h);
                 return SVT_HIP_ERR_RUNTIME;
             }
-            SVT_HIP_CHECK(hipGetLastError());
         }
         if ((rc = svt_hip_txfm_distortion_batch(d_base, d_txfm_desc, dist, n_cand, w, h, st)) != SVT_HIP_OK)
             return rc;
@@ -397,13 +391,13 @@ extern "C" int32_t svt_hip_txt_search_batch(uint8_t *d_base, const SvtHipTxfmDes
             const uint32_t items = n_blocks * SVT_HIP_TXT_MAX_CAND;
             hipLaunchKernelGGL(spatial_distortion_kernel<true>, dim3((items + 3) / 4), dim3(256), 0, st, (const uint8_t *)d_base, d_txfm_desc,
                                (const SvtHipSpatialSrc *)nullptr, d_desc, dist, items, n_cand, w, h);
-            SVT_HIP_CHECK(hipGetLastError());
         }
         if ((rc = svt_hip_txb_cost_batch(d_base, d_cost_desc, d_tables, n_tables, result_a, dist, cost, n_cand, w, h, st)) != SVT_HIP_OK)
             return rc;
     }
-    return select_batch(d_base, d_desc, d_txfm_desc, d_cost_desc, d_tables, n_tables, result_a, rdoq, dist, cost, d_out, n_cand, n_blocks, w, h,
-                        mapping_for(g.retained), (flags & SVT_HIP_TXT_SEARCH_INVERSE) != 0, st);
+    rc = select_batch(d_base, d_desc, d_txfm_desc, d_cost_desc, d_tables, n_tables, result_a, rdoq, dist, cost, d_out, n_cand, n_blocks, w, h,
+                      mapping_for(g.retained), (flags & SVT_HIP_TXT_SEARCH_INVERSE) != 0, st);
+    return rc == SVT_HIP_OK ? c.finish() : rc;
 }
 
 SVT_HIP_MODULE_WARMUP(txfm_txt)
