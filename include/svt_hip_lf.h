@@ -10,6 +10,8 @@
  *   Source/Lib/Codec/enc_cdef.c:284-610          svt_av1_cdef_frame         (Tier B: svt_hip_cdef_apply_plane)
  *   Source/Lib/Codec/enc_cdef.c:697-727, 728-926 joint_strength_search_dual, finish_cdef_search
  *                                                                           (Tier B: svt_hip_cdef_pick_strengths)
+ *   Source/Lib/Codec/restoration_pick.c:1296-1431, 1555-1625  search_wiener_seg, search_wiener_finish, rest_finish_search
+ *                                                                           (Tier B: svt_hip_wiener_pick_plane)
  */
 #ifndef SVT_HIP_LF_H
 #define SVT_HIP_LF_H
@@ -341,6 +343,75 @@ typedef struct SvtHipLrPlane {
     uint32_t    optimized_lr;
 } SvtHipLrPlane;
 SVT_HIP_API int32_t svt_hip_restoration_filter_frame(const SvtHipLrPlane *planes, uint32_t n_planes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The Wiener decision of one plane between svt_hip_wiener_stats (which leaves M and H in device memory) and
+ * svt_hip_restoration_filter_frame (which takes the units from device memory), for pictures whose loop restoration is
+ * Wiener only (presets M4-M8).  Reference, all in restoration_pick.c:
+ *   per unit    search_wiener_seg (:1296-1378): wiener_decompose_sep_sym (:906-936, int64, truncating division),
+ *               finalize_sym_filter (:977-1006), compute_score (:937-975; a score above 0 rejects the filter),
+ *               finer_tile_search_wiener_seg (:1042-1147); a trial is try_restoration_unit_seg (:129-165) with
+ *               use_boundaries_in_rest_search == 0: the separable filter over the unit from the picture's own samples,
+ *               edge-replicated outside the cropped plane (svt_extend_frame), then the SSE against the source
+ *   per plane   search_wiener_finish (:1380-1431) over the units in raster order (`ref` starts at set_default_wiener and
+ *               follows the last unit that chose Wiener), search_rest_type_finish (:1456-1465), rest_finish_search
+ *               (:1555-1625) for RESTORE_NONE against RESTORE_WIENER: Wiener wins only with a strictly smaller cost
+ * Not covered (the caller keeps such pictures on the host): any configuration with the self-guided filter enabled
+ * (RESTORE_SGRPROJ, search_switchable: presets M3 and slower), several tiles.
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct SvtHipWienerPickParams { /* read on the host */
+    int32_t  wiener_win;                /* 7 or 5 */
+    int32_t  is_16bit, bit_depth;       /* as svt_hip_wiener_stats: 8 / 10 / 12, above 8 only with 16-bit samples */
+    uint32_t plane_width, plane_height; /* cropped size of the plane: samples outside it replicate its edge */
+    int32_t  use_refinement, max_one_refinement_step; /* WnFilterCtrls */
+    int32_t  rdmult;                    /* x->rdmult */
+    int32_t  wiener_restore_cost[2];    /* x->wiener_restore_cost */
+} SvtHipWienerPickParams;
+
+#define SVT_HIP_WIENER_PICK_UNIT_BYTES 64
+typedef struct SvtHipWienerPickUnit { /* one per restoration unit, device memory */
+    int64_t sse[2];                   /* [RESTORE_NONE], [RESTORE_WIENER]; the latter INT64_MAX where the score rejects */
+    int16_t hfilter[8], vfilter[8];   /* after the finer search; zero where rejected */
+    int64_t bits;                     /* what the unit adds to the rate of frame type WIENER before the decision: bits_wiener
+                                       * = cost[1] + (count_wiener_bits << 9) against `ref`; cost[0] where rejected */
+    int32_t best_rtype;               /* best_rtype[RESTORE_WIENER - 1]: 1 where cost_wiener < cost_none, else 0 */
+    int32_t trials;                   /* try_restoration_unit_seg calls of the finer search; 0 where rejected */
+} SvtHipWienerPickUnit;
+
+typedef struct SvtHipWienerPickResult { /* ONE record in device memory */
+    int32_t frame_restoration_type;     /* 0 RESTORE_NONE, 1 RESTORE_WIENER */
+    int32_t n_wiener;                   /* units with best_rtype 1 */
+    int64_t sse[2], bits[2];            /* rsc->sse / rsc->bits after search_rest_type_finish of each type */
+    double  cost[2];                    /* RDCOST_DBL(rdmult, bits >> 4, sse) of each type */
+} SvtHipWienerPickResult;
+
+/* Bytes of d_workspace for n_units restoration units: layout arithmetic, no device; 0 for an empty plane. */
+SVT_HIP_API uint64_t svt_hip_wiener_pick_workspace_bytes(uint32_t n_units);
+/* prm and units are read on the host; everything else is device memory:
+ *   units          the array svt_hip_wiener_stats took, in raster order of the plane's restoration units, limits as
+ *                  svt_aom_foreach_rest_unit_in_frame gives them; dgd / src of every unit point at sample (0, 0) of the
+ *                  plane, and every limit lies inside plane_width x plane_height
+ *   d_M, d_H       as svt_hip_wiener_stats wrote them for wiener_win; not modified
+ *   d_prev_units   NULL, or SvtHipLrUnit [n_units] of the previous frame (use_prev_frame_coeffs): a unit whose record is
+ *                  RESTORE_WIENER takes those taps and skips the solver and the score (NULL on key / intra-only frames)
+ *                  A record whose coded taps lie outside their ranges (no decision leaves one; the number of launches is derived
+ *                  from the ranges) is not taken: that unit is solved like one without a record
+ *   d_unit_records SvtHipWienerPickUnit [n_units]
+ *   d_lr_units     SvtHipLrUnit [n_units] for svt_hip_restoration_filter_frame: RESTORE_WIENER with the taps where the
+ *                  unit chose Wiener and the plane's type is Wiener, RESTORE_NONE otherwise
+ * The call enqueues its launches on `stream` and returns SVT_HIP_OK or an SVT_HIP_ERR_* code; it neither synchronises nor reads
+ * anything back.  Refused with SVT_HIP_ERR_BAD_PARAMETER and a message, before anything is enqueued:
+ *   - a NULL prm, units, d_M, d_H, d_unit_records, d_result, d_lr_units or d_workspace (d_prev_units may be NULL);
+ *   - n_units == 0 or n_units > 65535 (the units are one dimension of the launch grid);
+ *   - a window other than 5 or 7; a bit depth other than 8 / 10 / 12, or above 8 with 8-bit samples;
+ *   - an empty plane, or one wider or taller than 65536 samples;
+ *   - a unit without dgd or src, with empty or negative limits, or reaching outside plane_width x plane_height;
+ *   - a unit wider or taller than 4096 samples (the limit of svt_hip_wiener_stats);
+ *   - workspace_bytes below svt_hip_wiener_pick_workspace_bytes(n_units); d_workspace, d_unit_records or d_result not 8-byte aligned. */
+SVT_HIP_API int svt_hip_wiener_pick_plane(const SvtHipWienerPickParams *prm, const SvtHipWienerUnit *units, uint32_t n_units,
+                                          const int64_t *d_M, const int64_t *d_H, const SvtHipLrUnit *d_prev_units,
+                                          SvtHipWienerPickUnit *d_unit_records, SvtHipWienerPickResult *d_result,
+                                          SvtHipLrUnit *d_lr_units, void *d_workspace, uint64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -150,9 +150,10 @@ __device__ __forceinline__ void sgr_tile_filter(const uint16_t *tile, int32_t *A
 // (0,0) at [3][3]; `tmp` = (th + 7) x 64 uint16 LDS scratch.  svt_av1_(highbd_)wiener_convolve_add_src (convolve.c:57-200).
 constexpr int WIENER_IP = 64 + 8, WIENER_IN_SLACK = 2;  // the horizontal pass reads one dword past the last sample of a row
 typedef short lr_i16x2 __attribute__((ext_vector_type(2)));
-template <int NT>
-__device__ __forceinline__ void wiener_tile_filter(const uint16_t *in, uint16_t *tmp, int tid, int tw, int th, int x0, int y0, const int16_t *fx,
-                                                   const int16_t *fy, int bd, int r0, int r1, int is16, void *__restrict__ dst, uint32_t dst_stride) {
+// The filtered sample of (r, c) goes to sink(r, c, v): a store, or whatever else the caller does with it.
+template <int NT, class Sink>
+__device__ __forceinline__ void wiener_tile_filter_to(const uint16_t *in, uint16_t *tmp, int tid, int tw, int th, const int16_t *fx, const int16_t *fy, int bd,
+                                                      int r0, int r1, Sink sink) {
     constexpr int IP = WIENER_IP;
     const int limit = (1 << (bd + 1 + 7 - r0)) - 1;
     // the seven horizontal taps (+ 128 on the centre one: the "add_src" term) as four packed pairs, the 8th coefficient is zero by
@@ -188,12 +189,20 @@ __device__ __forceinline__ void wiener_tile_filter(const uint16_t *in, uint16_t 
         for (int k = 0; k < 7; k++) sum += (int32_t)tmp[(r + k) * 64 + c] * fy[k];
         int32_t v = (sum + ((1 << r1) >> 1)) >> r1;
         v         = v < 0 ? 0 : (v > hi ? hi : v);
+        sink(r, c, v);
+    }
+}
+// ... stored at (y0 + r, x0 + c) of dst
+template <int NT>
+__device__ __forceinline__ void wiener_tile_filter(const uint16_t *in, uint16_t *tmp, int tid, int tw, int th, int x0, int y0, const int16_t *fx,
+                                                   const int16_t *fy, int bd, int r0, int r1, int is16, void *__restrict__ dst, uint32_t dst_stride) {
+    wiener_tile_filter_to<NT>(in, tmp, tid, tw, th, fx, fy, bd, r0, r1, [&](int r, int c, int32_t v) {
         const size_t o = (size_t)(y0 + r) * dst_stride + x0 + c;
         if (is16)
             ((uint16_t *)dst)[o] = (uint16_t)v;
         else
             ((uint8_t *)dst)[o] = (uint8_t)v;
-    }
+    });
 }
 
 }  // namespace lr

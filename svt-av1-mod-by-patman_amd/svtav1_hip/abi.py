@@ -367,6 +367,28 @@ class LrPlane(C.Structure):         # SvtHipLrPlane
                 ("boundary_stride", C.c_uint32), ("optimized_lr", C.c_uint32)]
 
 
+class WienerPickParams(C.Structure):   # SvtHipWienerPickParams
+    _fields_ = [("wiener_win", C.c_int32), ("is_16bit", C.c_int32), ("bit_depth", C.c_int32), ("plane_width", C.c_uint32),
+                ("plane_height", C.c_uint32), ("use_refinement", C.c_int32), ("max_one_refinement_step", C.c_int32), ("rdmult", C.c_int32),
+                ("wiener_restore_cost", C.c_int32 * 2)]
+
+
+WIENER_PICK_UNIT_BYTES = 64         # SVT_HIP_WIENER_PICK_UNIT_BYTES
+
+
+class WienerPickUnit(C.Structure):     # SvtHipWienerPickUnit
+    _fields_ = [("sse", C.c_int64 * 2), ("hfilter", C.c_int16 * 8), ("vfilter", C.c_int16 * 8), ("bits", C.c_int64),
+                ("best_rtype", C.c_int32), ("trials", C.c_int32)]
+
+
+class WienerPickResult(C.Structure):   # SvtHipWienerPickResult
+    _fields_ = [("frame_restoration_type", C.c_int32), ("n_wiener", C.c_int32), ("sse", C.c_int64 * 2), ("bits", C.c_int64 * 2),
+                ("cost", C.c_double * 2)]
+
+
+WIENER_PICK_UNIT_DTYPE, WIENER_PICK_RESULT_DTYPE = record_dtype(WienerPickUnit), record_dtype(WienerPickResult)
+
+
 class ConvolveParams(C.Structure):   # SvtHipConvolveParams == ConvolveParams (definitions.h:580-593)
     _fields_ = [("ref", C.c_int32), ("do_average", C.c_int32), ("dst", C.c_void_p), ("dst_stride", C.c_int32), ("round_0", C.c_int32),
                 ("round_1", C.c_int32), ("plane", C.c_int32), ("is_compound", C.c_int32), ("use_jnt_comp_avg", C.c_int32),

@@ -50,7 +50,7 @@ def main():
         dem = subprocess.run(["c++filt", name], stdout=subprocess.PIPE, text=True).stdout.strip()
         if pat not in dem:
             continue
-        dem = re.sub(r"^void (\(anonymous namespace\)::)?", "", dem).split("(")[0]
+        dem = re.sub(r"^(void )?(\(anonymous namespace\)::)?", "", dem).split("(")[0]   # a template kernel's name carries its return type
         try:
             regs = int(g("vgpr_count"))  # arch + accumulation registers of the unified file
             alloc = max(VGPR_BLOCK, (regs + VGPR_BLOCK - 1) // VGPR_BLOCK * VGPR_BLOCK)
