@@ -12,6 +12,8 @@
  *                                                                           (Tier B: svt_hip_cdef_pick_strengths)
  *   Source/Lib/Codec/restoration_pick.c:1296-1431, 1555-1625  search_wiener_seg, search_wiener_finish, rest_finish_search
  *                                                                           (Tier B: svt_hip_wiener_pick_plane)
+ *   Source/Lib/Codec/restoration_pick.c:1148-1293, 1380-1431, 1555-1625  search_sgrproj_seg, the finish visitors, rest_finish_search,
+ *                                                                           copy_unit_info (Tier B: svt_hip_rest_pick_plane)
  */
 #ifndef SVT_HIP_LF_H
 #define SVT_HIP_LF_H
@@ -356,8 +358,8 @@ SVT_HIP_API int32_t svt_hip_restoration_filter_frame(const SvtHipLrPlane *planes
  *   per plane   search_wiener_finish (:1380-1431) over the units in raster order (`ref` starts at set_default_wiener and
  *               follows the last unit that chose Wiener), search_rest_type_finish (:1456-1465), rest_finish_search
  *               (:1555-1625) for RESTORE_NONE against RESTORE_WIENER: Wiener wins only with a strictly smaller cost
- * Not covered (the caller keeps such pictures on the host): any configuration with the self-guided filter enabled
- * (RESTORE_SGRPROJ, search_switchable: presets M3 and slower), several tiles.
+ * Not covered: several tiles.  With the self-guided filter enabled (RESTORE_SGRPROJ, search_switchable: presets M3 and slower)
+ * svt_hip_rest_pick_plane below takes this call's unit records and decides the plane.
  * ------------------------------------------------------------------------------------------------------------------- */
 typedef struct SvtHipWienerPickParams { /* read on the host */
     int32_t  wiener_win;                /* 7 or 5 */
@@ -412,6 +414,85 @@ SVT_HIP_API int svt_hip_wiener_pick_plane(const SvtHipWienerPickParams *prm, con
                                           const int64_t *d_M, const int64_t *d_H, const SvtHipLrUnit *d_prev_units,
                                           SvtHipWienerPickUnit *d_unit_records, SvtHipWienerPickResult *d_result,
                                           SvtHipLrUnit *d_lr_units, void *d_workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The restoration decision of one plane with the self-guided filter enabled (presets M3 and slower), between
+ * svt_hip_wiener_stats / svt_hip_wiener_pick_plane and svt_hip_restoration_filter_frame.  Reference, all in restoration_pick.c:
+ *   per unit    search_norestore_seg (:1432), search_sgrproj_seg (:1220-1264) = search_selfguided_restoration (:550-652: apply_sgr
+ *               in processing units from the unit's top-left, svt_get_proj_subspace, encode_xq :508, finer_search_pixel_proj_error
+ *               :320-411; the first strictly smallest error in candidate order wins) and try_restoration_unit_seg (:129-165) with
+ *               use_boundaries_in_rest_search == 0: svt_apply_selfguided_restoration in the tiling of
+ *               svt_av1_loop_restoration_filter_unit (stripes of 64 >> ss_y rows offset by 8 >> ss_y, tiles of 64 >> ss_x columns)
+ *               from the picture's own samples, then the SSE against the source
+ *   per plane   search_wiener_finish (:1380), search_sgrproj_finish (:1267), search_switchable (:1148), each over the units in
+ *               raster order with its own `ref` (set_default_wiener / set_default_sgrproj, then the last unit of that pass that
+ *               chose the type); rest_finish_search (:1555-1625) with num_rtypes = n_units > 1 ? 4 : 3; copy_unit_info (:1202)
+ * With d_wiener_records == NULL the Wiener filter counts as disabled (force_restore_type_d == RESTORE_SGRPROJ): NONE and SGRPROJ
+ * alone are costed.  With records, a unit's best_rtype[RESTORE_WIENER - 1] is the record's, and search_switchable counts the Wiener
+ * taps with prm->wiener_win (the reference: 7 for luma, 5 for chroma, whatever window was searched).
+ * Not covered: several tiles, use_boundaries_in_rest_search != 0, the ref-based ep range (sg_filter_ctrls.step_range < 16, which
+ * the caller can resolve into the four sg_* fields).
+ * ------------------------------------------------------------------------------------------------------------------- */
+typedef struct SvtHipRestPickParams {   /* read on the host; 76 bytes */
+    int32_t  is_16bit, bit_depth;       /* 8 / 10 / 12, above 8 only with 16-bit samples */
+    uint32_t plane_width, plane_height; /* cropped; samples outside replicate the edge (svt_extend_frame) */
+    int32_t  ss_x, ss_y;                /* processing unit = 64 >> ss; stripe offset = 8 >> ss_y */
+    int32_t  wiener_win;                /* 7 / 5: read only when Wiener records are given */
+    int32_t  sg_start_ep, sg_end_ep, sg_ep_inc, sg_refine; /* the loop of search_selfguided_restoration :589, already resolved */
+    int32_t  rdmult;                    /* x->rdmult */
+    int32_t  wiener_restore_cost[2], sgrproj_restore_cost[2], switchable_restore_cost[3];
+} SvtHipRestPickParams;
+
+#define SVT_HIP_REST_PICK_UNIT_BYTES 64
+typedef struct SvtHipRestPickUnit { /* one per restoration unit, device memory; offsets in bytes */
+    int64_t sse[3];                 /*  0: [RESTORE_NONE], [RESTORE_WIENER] (the record's sse[1]; INT64_MAX without records),
+                                     *     [RESTORE_SGRPROJ] (the trial with the winner) */
+    int64_t search_err;             /* 24: the winning projection error of the search */
+    int32_t ep, xqd[2];             /* 32, 36: rusi->sgrproj */
+    int32_t best_rtype[3];          /* 44: best_rtype[RESTORE_WIENER - 1], [RESTORE_SGRPROJ - 1], [RESTORE_SWITCHABLE - 1]; 0 for a
+                                     *     pass that did not run */
+    int32_t trials;                 /* 56: get_pixel_proj_error calls of the winning ep */
+    int32_t pad_;                   /* 60: zero */
+} SvtHipRestPickUnit;
+
+#define SVT_HIP_REST_PICK_RESULT_BYTES 184
+typedef struct SvtHipRestPickResult { /* ONE record in device memory; offsets in bytes */
+    int32_t frame_restoration_type;   /*   0: 0 RESTORE_NONE, 1 RESTORE_WIENER, 2 RESTORE_SGRPROJ, 3 RESTORE_SWITCHABLE */
+    int32_t tested;                   /*   4: bit r set = rest_finish_search costed type r */
+    int64_t sse[4], bits[4];          /*   8, 40: rsc->sse / rsc->bits after search_rest_type_finish of each tested type, else 0 */
+    double  cost[4];                  /*  72: RDCOST_DBL(rdmult, bits >> 4, sse) of each tested type, else 0 */
+    int32_t n_units_of_type[3];       /* 104: units of d_lr_units that are NONE / WIENER / SGRPROJ */
+    int32_t pad_;                     /* 116: zero */
+    int32_t sg_frame_ep_cnt[16];      /* 120: how many units' search chose each ep (:1256; rest_process.c:634 derives the next
+                                       *      frame's sg_frame_ep from it) */
+} SvtHipRestPickResult;
+
+/* Bytes of d_workspace: layout arithmetic, no device; 0 for no units, an empty plane or n_ep < 1.  n_ep = the candidates of the
+ * loop, (sg_end_ep - sg_start_ep + sg_ep_inc - 1) / sg_ep_inc.  The workspace holds, each rounded up to 256 bytes: 64 bytes per
+ * (unit, candidate) (the five sums of svt_get_proj_subspace, then the candidate's error, xqd and trials), 16 bytes per unit (the
+ * two SSE sums), and the filtered planes as int32 [n_ep][2][plane_width * plane_height] (flt0, flt1 of every candidate; a unit's
+ * samples lie packed, pitch = its width, at the sum of the sizes of the units before it). */
+SVT_HIP_API uint64_t svt_hip_rest_pick_workspace_bytes(uint32_t n_units, uint32_t plane_width, uint32_t plane_height, int32_t n_ep);
+/* prm and units are read on the host; everything else is device memory:
+ *   units            the array the Wiener calls take: raster order, limits as svt_aom_foreach_rest_unit_in_frame gives them, dgd / src
+ *                    at sample (0, 0) of the plane; at most 384 x 384 samples each, and together no more than the plane holds
+ *   d_wiener_records NULL (Wiener not searched on this plane), or what svt_hip_wiener_pick_plane wrote earlier on the same stream;
+ *                    only sse[1], the taps and best_rtype are read
+ *   d_lr_units       per unit the type copy_unit_info assigns under the plane's type, the taps where it is WIENER, ep / xqd where it
+ *                    is SGRPROJ, every other field zero; a NONE plane gets all-NONE units
+ * The call enqueues a fixed number of launches (and one memset) on `stream` and returns that number of launches (>= 1); it neither
+ * synchronises nor reads anything back.  It returns an SVT_HIP_ERR_* code, sign-extended (negative), when it refuses or fails.
+ * Refused with SVT_HIP_ERR_BAD_PARAMETER and a message, before anything is enqueued:
+ *   - a NULL prm, units, d_unit_records, d_result, d_lr_units or d_workspace; any of the last four not 8-byte aligned;
+ *   - n_units == 0 or n_units > 65535; a bit depth other than 8 / 10 / 12, or above 8 with 8-bit samples;
+ *   - an empty plane, or one wider or taller than 65536 samples; ss_x / ss_y outside {0, 1};
+ *   - sg_start_ep < 0, sg_end_ep > 16, sg_start_ep >= sg_end_ep or sg_ep_inc < 1; wiener_win not 5 or 7 while records are given;
+ *   - a unit without dgd or src, with empty or negative limits, reaching outside the plane, or over 384 samples in either dimension;
+ *   - units that together hold more samples than the plane; workspace_bytes below svt_hip_rest_pick_workspace_bytes(). */
+SVT_HIP_API int64_t svt_hip_rest_pick_plane(const SvtHipRestPickParams *prm, const SvtHipWienerUnit *units, uint32_t n_units,
+                                            const SvtHipWienerPickUnit *d_wiener_records, SvtHipRestPickUnit *d_unit_records,
+                                            SvtHipRestPickResult *d_result, SvtHipLrUnit *d_lr_units, void *d_workspace,
+                                            uint64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

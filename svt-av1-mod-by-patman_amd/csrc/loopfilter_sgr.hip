@@ -55,115 +55,6 @@ __global__ __launch_bounds__(SGR_NT) void sgr_filter_kernel(SgrGeom g, int ep, i
     sgr_tile_filter<MODE, SGR_NT>(tile, Am, Bm, tid, w, h, i0, j0, ep, g.bit_depth, g.is16, flt0, flt1, flt_stride, dst, dst_stride, xq0, xq1);
 }
 
-// ---- block-wide int64 reductions -------------------------------------------------------------------------------
-__device__ __forceinline__ long long wave_sum64(long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-// sum over the block; result valid in every thread.  scratch: one long long per wave (+1)
-__device__ long long block_sum64(long long v, long long *scratch) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    v = wave_sum64(v);
-    __syncthreads();  // scratch free
-    if (lane == 0)
-        scratch[wv] = v;
-    __syncthreads();
-    long long t = 0;
-    for (int i = 0; i < nw; i++) t += scratch[i];
-    return t;
-}
-
-struct UnitData {
-    const void    *src, *dat;
-    const int32_t *flt0, *flt1;
-    uint32_t       src_stride, dat_stride, flt0_stride, flt1_stride, width, height;
-    int            is16, r0, r1;
-};
-
-// svt_av1_{lowbd,highbd}_pixel_proj_error_c over the unit (block-wide)
-__device__ long long unit_error(const UnitData &u, int xq0, int xq1, long long *scratch) {
-    long long      acc = 0;
-    const uint32_t n   = u.width * u.height;
-    for (uint32_t idx = threadIdx.x; idx < n; idx += blockDim.x) {
-        const uint32_t i = idx / u.width, j = idx - i * u.width;
-        const int32_t  d = ldpx(u.dat, (size_t)i * u.dat_stride + j, u.is16), s = ldpx(u.src, (size_t)i * u.src_stride + j, u.is16);
-        const int32_t  uu = d << RST_BITS;
-        int32_t        v  = 1 << (RST_BITS + PRJ_BITS - 1);
-        if (u.r0 > 0)
-            v += xq0 * (u.flt0[(size_t)i * u.flt0_stride + j] - uu);
-        if (u.r1 > 0)
-            v += xq1 * (u.flt1[(size_t)i * u.flt1_stride + j] - uu);
-        const int32_t e = (u.r0 > 0 || u.r1 > 0) ? (v >> (RST_BITS + PRJ_BITS)) + d - s : d - s;
-        acc += (long long)e * e;
-    }
-    return block_sum64(acc, scratch);
-}
-
-// the five sums of svt_get_proj_subspace_c (block-wide)
-__device__ void unit_sums(const UnitData &u, long long out[5], long long *scratch) {
-    long long      a[5] = {0, 0, 0, 0, 0};
-    const uint32_t n    = u.width * u.height;
-    for (uint32_t idx = threadIdx.x; idx < n; idx += blockDim.x) {
-        const uint32_t  i = idx / u.width, j = idx - i * u.width;
-        const long long uu = (long long)ldpx(u.dat, (size_t)i * u.dat_stride + j, u.is16) << RST_BITS;
-        const long long s  = ((long long)ldpx(u.src, (size_t)i * u.src_stride + j, u.is16) << RST_BITS) - uu;
-        const long long f1 = u.r0 > 0 ? u.flt0[(size_t)i * u.flt0_stride + j] - uu : 0;
-        const long long f2 = u.r1 > 0 ? u.flt1[(size_t)i * u.flt1_stride + j] - uu : 0;
-        a[0] += f1 * f1, a[1] += f2 * f2, a[2] += f1 * f2, a[3] += f1 * s, a[4] += f2 * s;
-    }
-    for (int k = 0; k < 5; k++) out[k] = block_sum64(a[k], scratch);
-}
-
-// closed-form part of svt_get_proj_subspace_c (restoration_pick.c:471-506), IEEE double without contraction
-__device__ void solve_subspace(const long long sums[5], int size, int r0, int r1, int xq[2]) {
-    double H00 = (double)sums[0], H11 = (double)sums[1], H01 = (double)sums[2], C0 = (double)sums[3], C1 = (double)sums[4];
-    xq[0] = xq[1] = 0;
-    H00 /= size, H01 /= size, H11 /= size, C0 /= size, C1 /= size;
-    const double H10 = H01;
-    if (r0 == 0) {
-        if (H11 < 1e-8)
-            return;
-        xq[1] = (int)rint(C1 / H11 * (1 << PRJ_BITS));
-    } else if (r1 == 0) {
-        if (H00 < 1e-8)
-            return;
-        xq[0] = (int)rint(C0 / H00 * (1 << PRJ_BITS));
-    } else {
-        const double det = H00 * H11 - H01 * H10;
-        if (det < 1e-8)
-            return;
-        const double x0 = (H11 * C0 - H01 * C1) / det, x1 = (H00 * C1 - H10 * C0) / det;
-        xq[0] = (int)rint(x0 * (1 << PRJ_BITS)), xq[1] = (int)rint(x1 * (1 << PRJ_BITS));
-    }
-}
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ void decode_xq(const int xqd[2], int xq[2], int r0, int r1) {
-    if (r0 == 0)
-        xq[0] = 0, xq[1] = (1 << PRJ_BITS) - xqd[1];
-    else if (r1 == 0)
-        xq[0] = xqd[0], xq[1] = 0;
-    else
-        xq[0] = xqd[0], xq[1] = (1 << PRJ_BITS) - xq[0] - xqd[1];
-}
-__device__ void encode_xq(const int xq[2], int xqd[2], int r0, int r1) {
-    if (r0 == 0) {
-        xqd[0] = 0;
-        xqd[1] = clampi((1 << PRJ_BITS) - xq[1], PRJ_MIN1, PRJ_MAX1);
-    } else if (r1 == 0) {
-        xqd[0] = clampi(xq[0], PRJ_MIN0, PRJ_MAX0);
-        xqd[1] = clampi((1 << PRJ_BITS) - xqd[0], PRJ_MIN1, PRJ_MAX1);
-    } else {
-        xqd[0] = clampi(xq[0], PRJ_MIN0, PRJ_MAX0);
-        xqd[1] = clampi((1 << PRJ_BITS) - xqd[0] - xq[1], PRJ_MIN1, PRJ_MAX1);
-    }
-}
-__device__ long long err_of(const UnitData &u, const int xqd[2], long long *scratch) {
-    int xq[2];
-    decode_xq(xqd, xq, u.r0, u.r1);
-    return unit_error(u, xq[0], xq[1], scratch);
-}
-
 struct EpResult {
     long long err;
     int32_t   ep, xqd[2], pad;
@@ -184,47 +75,8 @@ __global__ __launch_bounds__(1024) void sgr_search_ep_kernel(SvtHipSgrUnit un, c
     int exq[2], xqd[2];
     solve_subspace(sums, (int)(un.width * un.height), u.r0, u.r1, exq);
     encode_xq(exq, xqd, u.r0, u.r1);
-    long long err = err_of(u, xqd, scratch), err2;
-    if (do_refine) {
-        const int tap_min[2] = {PRJ_MIN0, PRJ_MIN1}, tap_max[2] = {PRJ_MAX0, PRJ_MAX1};
-        const int start_step = 2;
-        for (int s = start_step; s >= 1; s >>= 1)
-            for (int p = 0; p < 2; ++p) {
-                if ((u.r0 == 0 && p == 0) || (u.r1 == 0 && p == 1))
-                    continue;
-                int skip = 0;
-                do {
-                    if (xqd[p] - s >= tap_min[p]) {
-                        xqd[p] -= s;
-                        err2 = err_of(u, xqd, scratch);
-                        if (err2 > err)
-                            xqd[p] += s;
-                        else {
-                            err = err2, skip = 1;
-                            if (s == start_step)
-                                continue;
-                        }
-                    }
-                    break;
-                } while (1);
-                if (skip)
-                    break;
-                do {
-                    if (xqd[p] + s <= tap_max[p]) {
-                        xqd[p] += s;
-                        err2 = err_of(u, xqd, scratch);
-                        if (err2 > err)
-                            xqd[p] -= s;
-                        else {
-                            err = err2;
-                            if (s == start_step)
-                                continue;
-                        }
-                    }
-                    break;
-                } while (1);
-            }
-    }
+    int       trials;
+    long long err = finer_search(u, xqd, do_refine, scratch, trials);
     if (threadIdx.x == 0)
         res[blockIdx.x] = EpResult{err, ep, {xqd[0], xqd[1]}, 0};
 }

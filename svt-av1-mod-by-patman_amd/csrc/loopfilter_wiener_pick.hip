@@ -28,6 +28,8 @@ constexpr int       W2MAX = 49;
 constexpr long long SCALE = 65536;  // WIENER_TAP_SCALE_FACTOR
 constexpr int       RESTORE_NONE = 0, RESTORE_WIENER = 1;
 constexpr long long SSE_REJECTED = 0x7fffffffffffffffLL;  // INT64_MAX
+using lr::count_refsubexpfin;
+using lr::rdcost_dbl;
 
 struct State {  // the search of one unit between two launches: the workspace
     int16_t            h[8], v[8];  // the filter of the trial that runs next (the best one once phase is DONE)
@@ -339,37 +341,6 @@ int trial_bound(int plane_off, int use_refinement, int max_one_step) {
             t += 2 * (max_one_step ? 2 : 2 + range / 4 + 2 + 2);
         }
     return t;
-}
-
-// svt_aom_count_primitive_refsubexpfin (entropy_coding.c:2805-2951)
-__device__ int count_refsubexpfin(int n, int k, int ref, int v) {
-    auto recenter = [](int r, int v) { return v > (r << 1) ? v : (v >= r ? (v - r) << 1 : ((r - v) << 1) - 1); };
-    ref &= 0xffff, v &= 0xffff;
-    v = ((ref << 1) <= n ? recenter(ref, v) : recenter((n - 1 - ref) & 0xffff, (n - 1 - v) & 0xffff)) & 0xffff;
-    int count = 0, i = 0, mk = 0;
-    for (;;) {
-        const int b = i ? k + i - 1 : k, a = 1 << b;
-        if (n <= mk + 3 * a) {
-            const int nn = (n - mk) & 0xffff, vv = (v - mk) & 0xffff;  // svt_aom_count_primitive_quniform
-            if (nn > 1) {
-                const int l = 32 - __clz(nn - 1), m = (1 << l) - nn;
-                count += vv < m ? l - 1 : l;
-            }
-            break;
-        }
-        count++;
-        if (v >= mk + a)
-            i++, mk += a;
-        else {
-            count += b;
-            break;
-        }
-    }
-    return count;
-}
-
-__device__ __forceinline__ double rdcost_dbl(int rdmult, long long rate, long long dist) {  // RDCOST_DBL (restoration.h:346)
-    return (((double)rate * (double)rdmult) / 512.0) + ((double)dist * 128.0);
 }
 
 // One thread walks the units in raster order, so everything that does not depend on `ref` is done beside it: the records and the

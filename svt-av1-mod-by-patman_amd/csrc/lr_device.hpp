@@ -2,6 +2,8 @@
 // loopfilter_lr_frame.hip): the self-guided filter and the Wiener filter of ONE processing unit whose samples (with their
 // 3-sample border) already sit in LDS.  Who fills the tile decides what the filter sees: straight picture samples for the
 // per-unit entry points, the stripe-boundary rows of svt_aom_setup_processing_stripe_boundary for the frame-level pass.
+// Also here: what the restoration decisions share (loopfilter_sgr.hip, loopfilter_wiener_pick.hip, loopfilter_rest_pick.hip): the
+// projection sums, solver, error and finer search of the self-guided filter, the sub-exponential bit count and RDCOST_DBL.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -66,10 +68,11 @@ template <int R> __device__ __forceinline__ void ab_at(const uint16_t *tile, int
 // 66 x AP int32 scratch maps in LDS.  MODE 0: write flt0 / flt1 (at [i0 + i][j0 + j]).  MODE 1: fused
 // svt_apply_selfguided_restoration (projection with xq, clip, store samples to dst).  Called by all NT threads of the workgroup
 // after a barrier that made the tile visible; contains barriers.
-template <int MODE, int NT>
-__device__ __forceinline__ void sgr_tile_filter(const uint16_t *tile, int32_t *Am, int32_t *Bm, int tid, int w, int h, int i0, int j0, int ep, int bd,
-                                                int is16, int32_t *__restrict__ flt0, int32_t *__restrict__ flt1, uint32_t flt_stride,
-                                                void *__restrict__ dst, uint32_t dst_stride, int xq0, int xq1) {
+// MODE 2: nothing is stored; sink(i, j, sample, f0, f1) gets every sample of the unit with its two filtered values (0 where the radius is 0).
+template <int MODE, int NT, class Sink>
+__device__ __forceinline__ void sgr_tile_filter_to(const uint16_t *tile, int32_t *Am, int32_t *Bm, int tid, int w, int h, int i0, int j0, int ep, int bd,
+                                                   int is16, int32_t *__restrict__ flt0, int32_t *__restrict__ flt1, uint32_t flt_stride,
+                                                   void *__restrict__ dst, uint32_t dst_stride, int xq0, int xq1, Sink sink) {
     const int r0 = SGR_PRM[ep][0], r1 = SGR_PRM[ep][1];
     constexpr int PER = 64 * 64 / NT;  // samples per thread of a 64x64 unit
     int32_t       f0[PER];
@@ -143,7 +146,16 @@ __device__ __forceinline__ void sgr_tile_filter(const uint16_t *tile, int32_t *A
             else
                 ((uint8_t *)dst)[di] = (uint8_t)o;
         }
+        if (MODE == 2)
+            sink(i, j, (int32_t)tile[(i + 3) * TP + j + 3], f0[k], f1);
     }
+}
+template <int MODE, int NT>
+__device__ __forceinline__ void sgr_tile_filter(const uint16_t *tile, int32_t *Am, int32_t *Bm, int tid, int w, int h, int i0, int j0, int ep, int bd,
+                                                int is16, int32_t *__restrict__ flt0, int32_t *__restrict__ flt1, uint32_t flt_stride,
+                                                void *__restrict__ dst, uint32_t dst_stride, int xq0, int xq1) {
+    sgr_tile_filter_to<MODE, NT>(tile, Am, Bm, tid, w, h, i0, j0, ep, bd, is16, flt0, flt1, flt_stride, dst, dst_stride, xq0, xq1,
+                                 [](int, int, int32_t, int32_t, int32_t) {});
 }
 
 // Separable 7-tap Wiener filter of one tw x th (<= 64 x 64) unit: `in` = LDS tile of (th + 7) x (tw + 7) samples (4-byte aligned, WIENER_IN_SLACK readable elements behind it), pitch IP, sample
@@ -204,6 +216,195 @@ __device__ __forceinline__ void wiener_tile_filter(const uint16_t *in, uint16_t 
             ((uint8_t *)dst)[o] = (uint8_t)v;
     });
 }
+
+// ---- block-wide int64 reductions -------------------------------------------------------------------------------
+__device__ __forceinline__ long long wave_sum64(long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+// sum over the block; result valid in every thread.  scratch: one long long per wave (+1)
+__device__ inline long long block_sum64(long long v, long long *scratch) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    v = wave_sum64(v);
+    __syncthreads();  // scratch free
+    if (lane == 0)
+        scratch[wv] = v;
+    __syncthreads();
+    long long t = 0;
+    for (int i = 0; i < nw; i++) t += scratch[i];
+    return t;
+}
+
+struct UnitData {
+    const void    *src, *dat;
+    const int32_t *flt0, *flt1;
+    uint32_t       src_stride, dat_stride, flt0_stride, flt1_stride, width, height;
+    int            is16, r0, r1;
+};
+
+// svt_av1_{lowbd,highbd}_pixel_proj_error_c over the unit (block-wide)
+__device__ inline long long unit_error(const UnitData &u, int xq0, int xq1, long long *scratch) {
+    long long      acc = 0;
+    const uint32_t n   = u.width * u.height;
+    for (uint32_t idx = threadIdx.x; idx < n; idx += blockDim.x) {
+        const uint32_t i = idx / u.width, j = idx - i * u.width;
+        const int32_t  d = ldpx(u.dat, (size_t)i * u.dat_stride + j, u.is16), s = ldpx(u.src, (size_t)i * u.src_stride + j, u.is16);
+        const int32_t  uu = d << RST_BITS;
+        int32_t        v  = 1 << (RST_BITS + PRJ_BITS - 1);
+        if (u.r0 > 0)
+            v += xq0 * (u.flt0[(size_t)i * u.flt0_stride + j] - uu);
+        if (u.r1 > 0)
+            v += xq1 * (u.flt1[(size_t)i * u.flt1_stride + j] - uu);
+        const int32_t e = (u.r0 > 0 || u.r1 > 0) ? (v >> (RST_BITS + PRJ_BITS)) + d - s : d - s;
+        acc += (long long)e * e;
+    }
+    return block_sum64(acc, scratch);
+}
+
+// the five sums of svt_get_proj_subspace_c (block-wide)
+__device__ inline void unit_sums(const UnitData &u, long long out[5], long long *scratch) {
+    long long      a[5] = {0, 0, 0, 0, 0};
+    const uint32_t n    = u.width * u.height;
+    for (uint32_t idx = threadIdx.x; idx < n; idx += blockDim.x) {
+        const uint32_t  i = idx / u.width, j = idx - i * u.width;
+        const long long uu = (long long)ldpx(u.dat, (size_t)i * u.dat_stride + j, u.is16) << RST_BITS;
+        const long long s  = ((long long)ldpx(u.src, (size_t)i * u.src_stride + j, u.is16) << RST_BITS) - uu;
+        const long long f1 = u.r0 > 0 ? u.flt0[(size_t)i * u.flt0_stride + j] - uu : 0;
+        const long long f2 = u.r1 > 0 ? u.flt1[(size_t)i * u.flt1_stride + j] - uu : 0;
+        a[0] += f1 * f1, a[1] += f2 * f2, a[2] += f1 * f2, a[3] += f1 * s, a[4] += f2 * s;
+    }
+    for (int k = 0; k < 5; k++) out[k] = block_sum64(a[k], scratch);
+}
+
+// closed-form part of svt_get_proj_subspace_c (restoration_pick.c:471-506), IEEE double without contraction
+__device__ inline void solve_subspace(const long long sums[5], int size, int r0, int r1, int xq[2]) {
+    double H00 = (double)sums[0], H11 = (double)sums[1], H01 = (double)sums[2], C0 = (double)sums[3], C1 = (double)sums[4];
+    xq[0] = xq[1] = 0;
+    H00 /= size, H01 /= size, H11 /= size, C0 /= size, C1 /= size;
+    const double H10 = H01;
+    if (r0 == 0) {
+        if (H11 < 1e-8)
+            return;
+        xq[1] = (int)rint(C1 / H11 * (1 << PRJ_BITS));
+    } else if (r1 == 0) {
+        if (H00 < 1e-8)
+            return;
+        xq[0] = (int)rint(C0 / H00 * (1 << PRJ_BITS));
+    } else {
+        const double det = H00 * H11 - H01 * H10;
+        if (det < 1e-8)
+            return;
+        const double x0 = (H11 * C0 - H01 * C1) / det, x1 = (H00 * C1 - H10 * C0) / det;
+        xq[0] = (int)rint(x0 * (1 << PRJ_BITS)), xq[1] = (int)rint(x1 * (1 << PRJ_BITS));
+    }
+}
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ inline void decode_xq(const int xqd[2], int xq[2], int r0, int r1) {
+    if (r0 == 0)
+        xq[0] = 0, xq[1] = (1 << PRJ_BITS) - xqd[1];
+    else if (r1 == 0)
+        xq[0] = xqd[0], xq[1] = 0;
+    else
+        xq[0] = xqd[0], xq[1] = (1 << PRJ_BITS) - xq[0] - xqd[1];
+}
+__device__ inline void encode_xq(const int xq[2], int xqd[2], int r0, int r1) {
+    if (r0 == 0) {
+        xqd[0] = 0;
+        xqd[1] = clampi((1 << PRJ_BITS) - xq[1], PRJ_MIN1, PRJ_MAX1);
+    } else if (r1 == 0) {
+        xqd[0] = clampi(xq[0], PRJ_MIN0, PRJ_MAX0);
+        xqd[1] = clampi((1 << PRJ_BITS) - xqd[0], PRJ_MIN1, PRJ_MAX1);
+    } else {
+        xqd[0] = clampi(xq[0], PRJ_MIN0, PRJ_MAX0);
+        xqd[1] = clampi((1 << PRJ_BITS) - xqd[0] - xq[1], PRJ_MIN1, PRJ_MAX1);
+    }
+}
+__device__ inline long long err_of(const UnitData &u, const int xqd[2], long long *scratch) {
+    int xq[2];
+    decode_xq(xqd, xq, u.r0, u.r1);
+    return unit_error(u, xq[0], xq[1], scratch);
+}
+
+// finer_search_pixel_proj_error (restoration_pick.c:320-411) with start_step 2, block-wide: every thread runs the (uniform) control flow,
+// every err_of() is a block reduction whose result all threads see.  xqd is moved in place; trials = get_pixel_proj_error calls.
+__device__ inline long long finer_search(const UnitData &u, int xqd[2], int do_refine, long long *scratch, int &trials) {
+    long long err = err_of(u, xqd, scratch), err2;
+    trials        = 1;
+    if (!do_refine)
+        return err;
+    const int tap_min[2] = {PRJ_MIN0, PRJ_MIN1}, tap_max[2] = {PRJ_MAX0, PRJ_MAX1};
+    const int start_step = 2;
+    for (int s = start_step; s >= 1; s >>= 1)
+        for (int p = 0; p < 2; ++p) {
+            if ((u.r0 == 0 && p == 0) || (u.r1 == 0 && p == 1))
+                continue;
+            int skip = 0;
+            do {
+                if (xqd[p] - s >= tap_min[p]) {
+                    xqd[p] -= s;
+                    err2 = err_of(u, xqd, scratch), trials++;
+                    if (err2 > err)
+                        xqd[p] += s;
+                    else {
+                        err = err2, skip = 1;
+                        if (s == start_step)
+                            continue;
+                    }
+                }
+                break;
+            } while (1);
+            if (skip)
+                break;
+            do {
+                if (xqd[p] + s <= tap_max[p]) {
+                    xqd[p] += s;
+                    err2 = err_of(u, xqd, scratch), trials++;
+                    if (err2 > err)
+                        xqd[p] -= s;
+                    else {
+                        err = err2;
+                        if (s == start_step)
+                            continue;
+                    }
+                }
+                break;
+            } while (1);
+        }
+    return err;
+}
+
+// svt_aom_count_primitive_refsubexpfin (entropy_coding.c:2805-2951)
+__device__ inline int count_refsubexpfin(int n, int k, int ref, int v) {
+    auto recenter = [](int r, int v) { return v > (r << 1) ? v : (v >= r ? (v - r) << 1 : ((r - v) << 1) - 1); };
+    ref &= 0xffff, v &= 0xffff;
+    v = ((ref << 1) <= n ? recenter(ref, v) : recenter((n - 1 - ref) & 0xffff, (n - 1 - v) & 0xffff)) & 0xffff;
+    int count = 0, i = 0, mk = 0;
+    for (;;) {
+        const int b = i ? k + i - 1 : k, a = 1 << b;
+        if (n <= mk + 3 * a) {
+            const int nn = (n - mk) & 0xffff, vv = (v - mk) & 0xffff;  // svt_aom_count_primitive_quniform
+            if (nn > 1) {
+                const int l = 32 - __clz(nn - 1), m = (1 << l) - nn;
+                count += vv < m ? l - 1 : l;
+            }
+            break;
+        }
+        count++;
+        if (v >= mk + a)
+            i++, mk += a;
+        else {
+            count += b;
+            break;
+        }
+    }
+    return count;
+}
+
+__device__ __forceinline__ double rdcost_dbl(int rdmult, long long rate, long long dist) {  // RDCOST_DBL (restoration.h:346)
+    return (((double)rate * (double)rdmult) / 512.0) + ((double)dist * 128.0);
+}
+
 
 }  // namespace lr
 }  // namespace svthip

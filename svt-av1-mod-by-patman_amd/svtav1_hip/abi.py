@@ -389,6 +389,29 @@ class WienerPickResult(C.Structure):   # SvtHipWienerPickResult
 WIENER_PICK_UNIT_DTYPE, WIENER_PICK_RESULT_DTYPE = record_dtype(WienerPickUnit), record_dtype(WienerPickResult)
 
 
+class RestPickParams(C.Structure):     # SvtHipRestPickParams
+    _fields_ = [("is_16bit", C.c_int32), ("bit_depth", C.c_int32), ("plane_width", C.c_uint32), ("plane_height", C.c_uint32),
+                ("ss_x", C.c_int32), ("ss_y", C.c_int32), ("wiener_win", C.c_int32), ("sg_start_ep", C.c_int32), ("sg_end_ep", C.c_int32),
+                ("sg_ep_inc", C.c_int32), ("sg_refine", C.c_int32), ("rdmult", C.c_int32), ("wiener_restore_cost", C.c_int32 * 2),
+                ("sgrproj_restore_cost", C.c_int32 * 2), ("switchable_restore_cost", C.c_int32 * 3)]
+
+
+REST_PICK_UNIT_BYTES, REST_PICK_RESULT_BYTES = 64, 184      # SVT_HIP_REST_PICK_UNIT_BYTES, SVT_HIP_REST_PICK_RESULT_BYTES
+
+
+class RestPickUnit(C.Structure):       # SvtHipRestPickUnit
+    _fields_ = [("sse", C.c_int64 * 3), ("search_err", C.c_int64), ("ep", C.c_int32), ("xqd", C.c_int32 * 2), ("best_rtype", C.c_int32 * 3),
+                ("trials", C.c_int32), ("pad_", C.c_int32)]
+
+
+class RestPickResult(C.Structure):     # SvtHipRestPickResult
+    _fields_ = [("frame_restoration_type", C.c_int32), ("tested", C.c_int32), ("sse", C.c_int64 * 4), ("bits", C.c_int64 * 4),
+                ("cost", C.c_double * 4), ("n_units_of_type", C.c_int32 * 3), ("pad_", C.c_int32), ("sg_frame_ep_cnt", C.c_int32 * 16)]
+
+
+REST_PICK_UNIT_DTYPE, REST_PICK_RESULT_DTYPE = record_dtype(RestPickUnit), record_dtype(RestPickResult)
+
+
 class ConvolveParams(C.Structure):   # SvtHipConvolveParams == ConvolveParams (definitions.h:580-593)
     _fields_ = [("ref", C.c_int32), ("do_average", C.c_int32), ("dst", C.c_void_p), ("dst_stride", C.c_int32), ("round_0", C.c_int32),
                 ("round_1", C.c_int32), ("plane", C.c_int32), ("is_compound", C.c_int32), ("use_jnt_comp_avg", C.c_int32),

@@ -379,6 +379,32 @@ class DeviceWienerPick:
                 "lr_units": self.lr_units.download(abi.LR_UNIT_DTYPE, (self.n_units,), stream)}
 
 
+class DeviceRestPick:
+    """Unit records, result record, the units for svt_hip_restoration_filter_frame and the workspace of svt_hip_rest_pick_plane for a
+    plane of n_units restoration units and n_ep candidates, pre-filled with `fill`.  run() only enqueues and returns the call's
+    int64 (launches, or a negative status); download() waits for the stream."""
+
+    def __init__(self, lib, n_units, plane_width, plane_height, n_ep, fill=0xA5):
+        self.lib, self.n_units = lib, n_units
+        self.units = DeviceBuffer(lib, n_units * C.sizeof(abi.RestPickUnit))
+        self.result = DeviceBuffer(lib, C.sizeof(abi.RestPickResult))
+        self.lr_units = DeviceBuffer(lib, n_units * C.sizeof(abi.LrUnit))
+        self.workspace = DeviceBuffer(lib, lib.svt_hip_rest_pick_workspace_bytes(n_units, plane_width, plane_height, n_ep))
+        for b in (self.units, self.result, self.lr_units, self.workspace):
+            b.fill(fill)
+        _call(lib, "svt_hip_stream_sync")
+
+    def run(self, prm, units, d_wiener_records=None, stream=None):
+        """units: the host array of abi.WienerUnit that svt_hip_wiener_stats took"""
+        return self.lib.svt_hip_rest_pick_plane(C.byref(prm), units, self.n_units, d_wiener_records, self.units.ptr, self.result.ptr,
+                                                self.lr_units.ptr, self.workspace.ptr, self.workspace.nbytes, stream)
+
+    def download(self, stream=None):
+        return {"units": self.units.download(abi.REST_PICK_UNIT_DTYPE, (self.n_units,), stream),
+                "result": self.result.download(abi.REST_PICK_RESULT_DTYPE, (), stream),
+                "lr_units": self.lr_units.download(abi.LR_UNIT_DTYPE, (self.n_units,), stream)}
+
+
 def warp_batch(lib, descs, d_filter, stream=None, sync=True):
     """svt_hip_warp_batch over a list of abi.WarpDesc (one launch); d_filter: device address of the [193][8] int16 filter table."""
     d_desc = upload_descriptors(lib, descs, stream)
