@@ -67,12 +67,7 @@ __global__ __launch_bounds__(LR_NT) void lr_frame_kernel(LrFrame f) {
     if (u.restoration_type == 0) {  // RESTORE_NONE: svt_aom_copy_tile
         for (int idx = tid; idx < w * h; idx += LR_NT) {
             const int    r = idx / w, c = idx - r * w;
-            const size_t o = (size_t)(ys + r) * pl.dst_stride + x0 + c;
-            const int32_t v = ldpx(pl.src, (size_t)(ys + r) * pl.src_stride + x0 + c, is16);
-            if (is16)
-                ((uint16_t *)pl.dst)[o] = (uint16_t)v;
-            else
-                ((uint8_t *)pl.dst)[o] = (uint8_t)v;
+            stpx(pl.dst, (size_t)(ys + r) * pl.dst_stride + x0 + c, is16, ldpx(pl.src, (size_t)(ys + r) * pl.src_stride + x0 + c, is16));
         }
         return;
     }
@@ -85,14 +80,11 @@ __global__ __launch_bounds__(LR_NT) void lr_frame_kernel(LrFrame f) {
         }
         __syncthreads();
         const int ep = u.ep, r0 = SGR_PRM[ep][0], r1 = SGR_PRM[ep][1];
-        int       xq0, xq1;  // svt_decode_xq (restoration.c:634-645)
-        if (r0 == 0)
-            xq0 = 0, xq1 = (1 << PRJ_BITS) - u.xqd[1];
-        else if (r1 == 0)
-            xq0 = u.xqd[0], xq1 = 0;
-        else
-            xq0 = u.xqd[0], xq1 = (1 << PRJ_BITS) - xq0 - u.xqd[1];
-        sgr_tile_filter<1, LR_NT>(tile, Am, Bm, tid, w, h, ys, x0, ep, bd, is16, nullptr, nullptr, 0u, pl.dst, pl.dst_stride, xq0, xq1);
+        int       xq[2];
+        decode_xq(u.xqd, xq, r0, r1);
+        sgr_tile_filter_to<LR_NT>(tile, Am, Bm, tid, w, h, ep, bd, [&](int i, int j, int32_t x, int32_t f0, int32_t f1) {
+            stpx(pl.dst, (size_t)(ys + i) * pl.dst_stride + x0 + j, is16, sgr_project(x, f0, f1, xq, r0, r1, bd));
+        });
         return;
     }
     // RESTORE_WIENER: svt_aom_wiener_filter_stripe(_highbd); get_conv_params_wiener (restoration.c:49-73)

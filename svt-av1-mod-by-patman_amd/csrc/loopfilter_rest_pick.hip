@@ -19,18 +19,14 @@
 // Samples outside the cropped plane replicate its edge (svt_extend_frame): coordinates are clamped, nothing outside is read.
 #include <vector>
 
-#include "common.hpp"
-#include "lr_device.hpp"
-#include "../../include/svt_hip_lf.h"
+#include "lr_pick.hpp"
 
 using namespace svthip;
 using namespace svthip::lr;
 
 namespace {
 
-constexpr int       RESTORE_NONE = 0, RESTORE_WIENER = 1, RESTORE_SGRPROJ = 2, RESTORE_SWITCHABLE = 3;
-constexpr long long SSE_REJECTED = 0x7fffffffffffffffLL;  // INT64_MAX
-constexpr int       NT           = 512;                   // threads of the two filtering kernels: see SGR_NT in loopfilter_sgr.hip
+constexpr int NT = 512;  // threads of the two filtering kernels: see SGR_NT in loopfilter_sgr.hip
 // The longest finer search.  A trial is accepted on an equal error, so on a flat unit (every filtered value equals the sample, every
 // error equals the first) every move ties and the walk at step 2 only ends at the clamp.  Per tap at step 2: either moves down
 // (at most (PRJ_MAX - PRJ_MIN) / 2 = 63 accepted ones, after which `if (skip) break;` leaves the tap loop), or one refused move
@@ -55,17 +51,7 @@ struct PlanePrm {
     unsigned long long plane_px;
 };
 
-__device__ __forceinline__ void lds_add(long long *p, long long v) { atomicAdd((unsigned long long *)p, (unsigned long long)v); }
 __device__ __forceinline__ const void *px_at(const void *base, size_t idx, int is16) { return (const uint8_t *)base + (idx << (is16 ? 1 : 0)); }
-
-// The w x h samples at (y, x) of the plane with their 3-sample border into the LDS tile, replicated outside the cropped plane
-__device__ __forceinline__ void load_tile(uint16_t *tile, const SvtHipWienerUnit &u, const PlanePrm &p, int y, int x, int w, int h) {
-    for (int idx = threadIdx.x; idx < (h + 6) * (w + 6); idx += NT) {
-        const int r = idx / (w + 6), c = idx - r * (w + 6);
-        const int yy = min(max(y + r - 3, 0), p.plane_h - 1), xx = min(max(x + c - 3, 0), p.plane_w - 1);
-        tile[r * TP + c] = (uint16_t)ldpx(u.dgd, (size_t)yy * u.dgd_stride + xx, p.is16);
-    }
-}
 
 // grid (tiles of the largest unit, candidates, units)
 __global__ __launch_bounds__(NT) void rpick_filter(const PUnit *__restrict__ units, Cand *__restrict__ cands, int32_t *__restrict__ planes, PlanePrm p) {
@@ -80,12 +66,12 @@ __global__ __launch_bounds__(NT) void rpick_filter(const PUnit *__restrict__ uni
     const int i0 = ((int)blockIdx.x / gx) * p.pu_h, j0 = ((int)blockIdx.x % gx) * p.pu_w, w = min(p.pu_w, uw - j0), h = min(p.pu_h, uh - i0);
     if (tid < 5)
         s_sums[tid] = 0;
-    load_tile(tile, u, p, u.v_start + i0, u.h_start + j0, w, h);
+    load_tile_clamped(tile, TP, u.dgd, u.dgd_stride, p.is16, p.plane_w, p.plane_h, u.v_start + i0 - 3, u.h_start + j0 - 3, h + 6, w + 6, NT);  // with the 3-sample border
     __syncthreads();
     int32_t  *f0p = planes + (size_t)(2 * k) * p.plane_px + units[blockIdx.z].off, *f1p = f0p + p.plane_px;
     const int r0 = SGR_PRM[ep][0], r1 = SGR_PRM[ep][1], is16 = p.is16;
     long long a[5] = {0, 0, 0, 0, 0};
-    sgr_tile_filter_to<2, NT>(tile, Am, Bm, tid, w, h, i0, j0, ep, p.bd, is16, nullptr, nullptr, 0u, nullptr, 0u, 0, 0,
+    sgr_tile_filter_to<NT>(tile, Am, Bm, tid, w, h, ep, p.bd,
                               [&](int i, int j, int32_t x, int32_t f0, int32_t f1) {
                                   const size_t o = (size_t)(i0 + i) * uw + j0 + j;
                                   if (r0 > 0)
@@ -108,98 +94,7 @@ __global__ __launch_bounds__(NT) void rpick_filter(const PUnit *__restrict__ uni
         atomicAdd((unsigned long long *)&cands[(size_t)blockIdx.z * p.n_ep + k].sums[tid], (unsigned long long)s_sums[tid]);
 }
 
-// The projection errors of NB candidate xqd in ONE pass over the unit (the pass is bound by its reads: two filtered values, dat and src
-// per sample); every thread gets all NB sums.  scratch: NB long long per wave.
-constexpr int NB = 4;
-__device__ void unit_errors(const UnitData &u, const int (*xqd)[2], long long *out, long long *scratch) {
-    int xq[NB][2];
-#pragma unroll
-    for (int k = 0; k < NB; k++) decode_xq(xqd[k], xq[k], u.r0, u.r1);
-    long long      acc[NB] = {0, 0, 0, 0};
-    const uint32_t n = u.width * u.height;
-#pragma unroll 2
-    for (uint32_t idx = threadIdx.x; idx < n; idx += blockDim.x) {
-        const uint32_t i = idx / u.width, j = idx - i * u.width;
-        const int32_t  d = ldpx(u.dat, (size_t)i * u.dat_stride + j, u.is16), s = ldpx(u.src, (size_t)i * u.src_stride + j, u.is16);
-        const int32_t  uu = d << RST_BITS;
-        const int32_t  a0 = u.r0 > 0 ? u.flt0[(size_t)i * u.flt0_stride + j] - uu : 0, a1 = u.r1 > 0 ? u.flt1[(size_t)i * u.flt1_stride + j] - uu : 0;
-#pragma unroll
-        for (int k = 0; k < NB; k++) {  // svt_av1_{lowbd,highbd}_pixel_proj_error_c
-            const int32_t v = (1 << (RST_BITS + PRJ_BITS - 1)) + xq[k][0] * a0 + xq[k][1] * a1, e = (v >> (RST_BITS + PRJ_BITS)) + d - s;
-            acc[k] += (long long)e * e;
-        }
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NB; k++) acc[k] = wave_sum64(acc[k]);
-    __syncthreads();  // scratch free
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < NB; k++) scratch[wv * NB + k] = acc[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NB; k++) {
-        long long t = 0;
-        for (int w = 0; w < nw; w++) t += scratch[w * NB + k];
-        out[k] = t;
-    }
-}
-
-// finer_search_pixel_proj_error (:320-411) with start_step 2.  The accepted path and the count of trials are the reference's; what differs
-// is how many errors one pass over the unit yields: a walk at step 2 ("at the highest step size continue moving in the same direction")
-// has its next NB moves evaluated together, and the moves behind the first refused one are dropped unused (and not counted).
-__device__ long long finer_search_batched(const UnitData &u, int xqd[2], int do_refine, long long *scratch, int &trials) {
-    int       cq[NB][2];
-    long long e[NB];
-#pragma unroll
-    for (int k = 0; k < NB; k++) cq[k][0] = xqd[0], cq[k][1] = xqd[1];
-    unit_errors(u, cq, e, scratch);
-    long long err = e[0];
-    trials        = 1;
-    if (!do_refine)
-        return err;
-    for (int s = 2; s >= 1; s >>= 1)
-        for (int p = 0; p < 2; ++p) {
-            if ((u.r0 == 0 && p == 0) || (u.r1 == 0 && p == 1))
-                continue;
-            const int lo = p == 0 ? PRJ_MIN0 : PRJ_MIN1, hi = p == 0 ? PRJ_MAX0 : PRJ_MAX1;
-            int       skip = 0;
-            for (int dir = -1; dir <= 1; dir += 2) {  // the two do-while loops
-                for (bool walk = true; walk;) {
-                    const int cur = p == 0 ? xqd[0] : xqd[1], room = (dir < 0 ? cur - lo : hi - cur) / s, nb = min(room, s == 2 ? NB : 1);
-                    if (nb == 0)
-                        break;  // the move would leave the range: `break` without a trial
-#pragma unroll
-                    for (int k = 0; k < NB; k++) {
-                        const int v = cur + dir * s * (min(k, nb - 1) + 1);
-                        cq[k][0] = p == 0 ? v : xqd[0], cq[k][1] = p == 0 ? xqd[1] : v;
-                    }
-                    unit_errors(u, cq, e, scratch);
-                    walk = s == 2;
-#pragma unroll
-                    for (int k = 0; k < NB; k++) {
-                        if (k >= nb)
-                            break;
-                        trials++;
-                        if (e[k] > err) {  // refused: the move is undone, the walk ends
-                            walk = false;
-                            break;
-                        }
-                        err = e[k], skip |= dir < 0;
-                        if (p == 0)
-                            xqd[0] += dir * s;
-                        else
-                            xqd[1] += dir * s;
-                    }
-                }
-                if (skip)
-                    break;
-            }
-            if (skip)
-                break;  // `if (skip) break;` leaves the loop over p
-        }
-    return err;
-}
+constexpr int NB = 4;  // moves of a step-2 walk of the finer search (lr_device.hpp) that one pass over the unit evaluates
 
 // grid (candidates, units)
 __global__ __launch_bounds__(1024) void rpick_search(const PUnit *__restrict__ units, Cand *__restrict__ cands, const int32_t *__restrict__ planes, PlanePrm p) {
@@ -216,18 +111,9 @@ __global__ __launch_bounds__(1024) void rpick_search(const PUnit *__restrict__ u
     int exq[2], xqd[2], trials;
     solve_subspace(sums, (int)(uw * uh), u.r0, u.r1, exq);
     encode_xq(exq, xqd, u.r0, u.r1);
-    const long long err = finer_search_batched(u, xqd, p.refine, scratch, trials);
+    const long long err = finer_search<NB>(u, xqd, p.refine, scratch, trials);
     if (threadIdx.x == 0)
         c.err = err, c.xqd[0] = xqd[0], c.xqd[1] = xqd[1], c.trials = trials, c.pad_ = 0;
-}
-
-// first strict minimum in candidate order (restoration_pick.c:638-643)
-__device__ __forceinline__ int best_cand(const Cand *c, int n) {
-    int b = 0;
-    for (int i = 1; i < n; i++)
-        if (c[i].err < c[b].err)
-            b = i;
-    return b;
 }
 
 // Stripe `sr` of a unit: stripes end at the picture rows k * stripe_h - stripe_off (restoration.c:1100-1113)
@@ -251,25 +137,18 @@ __global__ __launch_bounds__(NT) void rpick_trial(const PUnit *__restrict__ unit
     const int y0 = sr == 0 ? u.v_start : e0 + (sr - 1) * p.stripe_h, y1 = min(u.v_end, sr == 0 ? e0 : y0 + p.stripe_h);
     const int w = min(p.pu_w, uw - j0), h = y1 - y0;
     const Cand *cu = cands + (size_t)blockIdx.y * p.n_ep;
-    const int   b = best_cand(cu, p.n_ep), ep = p.start_ep + b * p.ep_inc, r0 = SGR_PRM[ep][0], r1 = SGR_PRM[ep][1], is16 = p.is16, bd = p.bd;
+    const int   b = first_min(cu, p.n_ep), ep = p.start_ep + b * p.ep_inc, r0 = SGR_PRM[ep][0], r1 = SGR_PRM[ep][1], is16 = p.is16, bd = p.bd;
     int xqd[2] = {cu[b].xqd[0], cu[b].xqd[1]}, xq[2];
     decode_xq(xqd, xq, r0, r1);
     if (tid < 2)
         s_sum[tid] = 0;
-    load_tile(tile, u, p, y0, u.h_start + j0, w, h);
+    load_tile_clamped(tile, TP, u.dgd, u.dgd_stride, is16, p.plane_w, p.plane_h, y0 - 3, u.h_start + j0 - 3, h + 6, w + 6, NT);
     __syncthreads();
     long long acc = 0, accn = 0;
-    sgr_tile_filter_to<2, NT>(tile, Am, Bm, tid, w, h, 0, 0, ep, bd, is16, nullptr, nullptr, 0u, nullptr, 0u, 0, 0,
-                              [&](int i, int j, int32_t x, int32_t f0, int32_t f1) {  // svt_apply_selfguided_restoration (restoration.c:957-992)
-                                  const int32_t uu = x << RST_BITS;
-                                  int32_t       v  = uu << PRJ_BITS;
-                                  if (r0 > 0)
-                                      v += xq[0] * (f0 - uu);
-                                  if (r1 > 0)
-                                      v += xq[1] * (f1 - uu);
-                                  const int16_t wv = (int16_t)rnd(v, PRJ_BITS + RST_BITS);
-                                  const int32_t hi = (1 << bd) - 1, o = wv < 0 ? 0 : (wv > hi ? hi : wv);
-                                  const int32_t s  = ldpx(u.src, (size_t)(y0 + i) * u.src_stride + u.h_start + j0 + j, is16);
+    sgr_tile_filter_to<NT>(tile, Am, Bm, tid, w, h, ep, bd,
+                              [&](int i, int j, int32_t x, int32_t f0, int32_t f1) {
+                                  const int32_t o = sgr_project(x, f0, f1, xq, r0, r1, bd);
+                                  const int32_t s = ldpx(u.src, (size_t)(y0 + i) * u.src_stride + u.h_start + j0 + j, is16);
                                   acc += (long long)((o - s) * (o - s)), accn += (long long)((x - s) * (x - s));
                               });
     acc = wave_sum64(acc), accn = wave_sum64(accn);
@@ -283,26 +162,6 @@ __global__ __launch_bounds__(NT) void rpick_trial(const PUnit *__restrict__ unit
 struct DecidePrm {
     int n_units, n_ep, start_ep, ep_inc, win, rdmult, cost_w[2], cost_s[2], cost_sw[3];
 };
-
-// count_sgrproj_bits (:655-669)
-__device__ int count_sgrproj_bits(int ep, const int *xqd, const int *ref) {
-    int bits = 4;  // SGRPROJ_PARAMS_BITS
-    if (SGR_PRM[ep][0] > 0)
-        bits += count_refsubexpfin(PRJ_MAX0 - PRJ_MIN0 + 1, 4, ref[0] - PRJ_MIN0, xqd[0] - PRJ_MIN0);
-    if (SGR_PRM[ep][1] > 0)
-        bits += count_refsubexpfin(PRJ_MAX1 - PRJ_MIN1 + 1, 4, ref[1] - PRJ_MIN1, xqd[1] - PRJ_MIN1);
-    return bits;
-}
-// count_wiener_bits (:1008-1037): taps = vfilter[0..2], hfilter[0..2]
-__device__ int count_wiener_bits(int win, const int16_t *taps, const int *ref) {
-    int c = 0;
-    for (int t = 0; t < 6; t++) {
-        const int q = t % 3, lo = q == 0 ? -5 : (q == 1 ? -23 : -17);  // WIENER_FILT_TAPn_MINV
-        if (win == 7 || q != 0)
-            c += count_refsubexpfin(16 << q, q + 1, ref[t] - lo, taps[t] - lo);
-    }
-    return c;
-}
 
 // One thread walks the units in raster order; everything that does not depend on a `ref` is prepared beside it by 256 threads,
 // 256 units at a time, in LDS (as wpick_decide does: a dependent read of device memory per unit costs more than the chains).
@@ -320,15 +179,15 @@ __global__ __launch_bounds__(256) void rpick_decide(const Cand *__restrict__ can
     if (tid < 3)
         s_count[tid] = 0;
     // thread 0's alone: ref and totals of the passes WIENER, SGRPROJ, SWITCHABLE
-    int       ref_w[6] = {3, -7, 15, 3, -7, 15}, ref_s[2] = {(PRJ_MIN0 + PRJ_MAX0) / 2, (PRJ_MIN1 + PRJ_MAX1) / 2};  // set_default_wiener / _sgrproj
-    int       sw_w[6] = {3, -7, 15, 3, -7, 15}, sw_s[2] = {(PRJ_MIN0 + PRJ_MAX0) / 2, (PRJ_MIN1 + PRJ_MAX1) / 2};
+    int ref_w[6], ref_s[2], sw_w[6], sw_s[2];
+    set_default_wiener(ref_w), set_default_sgrproj(ref_s), set_default_wiener(sw_w), set_default_sgrproj(sw_s);
     long long sse[4] = {0, 0, 0, 0}, bits[4] = {0, 0, 0, 0};
     for (int base = 0; base < p.n_units; base += CH) {
         const int i = base + tid;
         __syncthreads();
         if (i < p.n_units) {
             const Cand *cu = cands + (size_t)i * p.n_ep;
-            const int   b  = best_cand(cu, p.n_ep), ep = p.start_ep + b * p.ep_inc;
+            const int   b  = first_min(cu, p.n_ep), ep = p.start_ep + b * p.ep_inc;
             SvtHipRestPickUnit &r = recs[i];
             const long long     sse1 = with_w ? wrecs[i].sse[1] : SSE_REJECTED;
             r.sse[0] = (long long)accs[i].none, r.sse[1] = sse1, r.sse[2] = (long long)accs[i].sgr, r.search_err = cu[b].err;
@@ -350,7 +209,7 @@ __global__ __launch_bounds__(256) void rpick_decide(const Cand *__restrict__ can
                     if (sse1 == SSE_REJECTED)
                         bits[RESTORE_WIENER] += p.cost_w[0], sse[RESTORE_WIENER] += sse0;
                     else {
-                        const long long bits_wiener = p.cost_w[1] + (count_wiener_bits(p.win, s_taps[k], ref_w) << 9);
+                        const long long bits_wiener = p.cost_w[1] + (count_wiener_bits(p.win, s_taps[k], ref_w, wiener_tap_bits) << 9);
                         bw = s_wbest[k] == RESTORE_WIENER ? RESTORE_WIENER : RESTORE_NONE;
                         sse[RESTORE_WIENER] += bw ? sse1 : sse0, bits[RESTORE_WIENER] += bw ? bits_wiener : (long long)p.cost_w[0];
                         if (bw)
@@ -374,7 +233,7 @@ __global__ __launch_bounds__(256) void rpick_decide(const Cand *__restrict__ can
                     for (int r = 0; r < 3; r++) {
                         if (r > RESTORE_NONE && (r == RESTORE_WIENER ? bw : bs) == RESTORE_NONE)
                             continue;
-                        const long long pcost = r == RESTORE_NONE ? 0 : (r == RESTORE_WIENER ? count_wiener_bits(p.win, s_taps[k], sw_w) : count_sgrproj_bits(s_ep[k], s_xqd[k], sw_s));
+                        const long long pcost = r == RESTORE_NONE ? 0 : (r == RESTORE_WIENER ? count_wiener_bits(p.win, s_taps[k], sw_w, wiener_tap_bits) : count_sgrproj_bits(s_ep[k], s_xqd[k], sw_s));
                         const long long b     = p.cost_sw[r] + (pcost << 9);
                         const double    cost  = rdcost_dbl(p.rdmult, b >> 4, s_sse[r][k]);
                         if (r == 0 || cost < best_cost)
@@ -448,10 +307,8 @@ extern "C" int64_t svt_hip_rest_pick_plane(const SvtHipRestPickParams *prm, cons
         return refuse("svt_hip_rest_pick_plane: NULL argument");
     if (n_units == 0 || n_units > 65535)
         return refuse("svt_hip_rest_pick_plane: %u units (1..65535)", n_units);
-    if ((prm->bit_depth != 8 && prm->bit_depth != 10 && prm->bit_depth != 12) || (prm->bit_depth > 8 && !prm->is_16bit))
-        return refuse("svt_hip_rest_pick_plane: bit depth %d with %s samples", prm->bit_depth, prm->is_16bit ? "16-bit" : "8-bit");
-    if (prm->plane_width == 0 || prm->plane_height == 0 || prm->plane_width > 65536 || prm->plane_height > 65536)
-        return refuse("svt_hip_rest_pick_plane: plane of %u x %u", prm->plane_width, prm->plane_height);
+    if (const int32_t rc = pick_plane_ok("svt_hip_rest_pick_plane", prm->bit_depth, prm->is_16bit, prm->plane_width, prm->plane_height); rc != SVT_HIP_OK)
+        return rc;
     if ((prm->ss_x | prm->ss_y) & ~1)
         return refuse("svt_hip_rest_pick_plane: subsampling %d, %d (0 or 1)", prm->ss_x, prm->ss_y);
     if (prm->sg_start_ep < 0 || prm->sg_end_ep > 16 || prm->sg_start_ep >= prm->sg_end_ep || prm->sg_ep_inc < 1)
@@ -464,21 +321,16 @@ extern "C" int64_t svt_hip_rest_pick_plane(const SvtHipRestPickParams *prm, cons
     staged.resize(n_units);
     unsigned long long off = 0;
     int                max_tiles = 0, max_stripe_tiles = 0;
-    for (uint32_t i = 0; i < n_units; i++) {
-        const SvtHipWienerUnit &u = units[i];
-        if (!u.dgd || !u.src || u.h_start < 0 || u.v_start < 0 || u.h_end <= u.h_start || u.v_end <= u.v_start ||
-            (uint32_t)u.h_end > prm->plane_width || (uint32_t)u.v_end > prm->plane_height)
-            return refuse("svt_hip_rest_pick_plane: unit %u: limits [%d, %d) x [%d, %d) outside the plane of %u x %u", i, u.h_start, u.h_end, u.v_start,
-                          u.v_end, prm->plane_width, prm->plane_height);
-        const int uw = u.h_end - u.h_start, uh = u.v_end - u.v_start;
-        if (uw > 384 || uh > 384)
-            return refuse("svt_hip_rest_pick_plane: unit %u: %d x %d samples, 384 at the most", i, uw, uh);
-        staged[i] = PUnit{u, off};
-        off += (unsigned long long)uw * uh;
-        const int gx = (uw + p.pu_w - 1) / p.pu_w;
-        max_tiles        = std::max(max_tiles, gx * ((uh + p.pu_h - 1) / p.pu_h));
-        max_stripe_tiles = std::max(max_stripe_tiles, gx * stripes_of(u.v_start, u.v_end, p.stripe_h, p.stripe_off));
-    }
+    if (const int32_t rc = pick_units_ok("svt_hip_rest_pick_plane", units, n_units, prm->plane_width, prm->plane_height, 384,
+                                         [&](uint32_t i, const SvtHipWienerUnit &u, int uw, int uh) {
+                                             staged[i] = PUnit{u, off};
+                                             off += (unsigned long long)uw * uh;
+                                             const int gx = (uw + p.pu_w - 1) / p.pu_w;
+                                             max_tiles        = std::max(max_tiles, gx * ((uh + p.pu_h - 1) / p.pu_h));
+                                             max_stripe_tiles = std::max(max_stripe_tiles, gx * stripes_of(u.v_start, u.v_end, p.stripe_h, p.stripe_off));
+                                         });
+        rc != SVT_HIP_OK)
+        return rc;
     if (off > p.plane_px)
         return refuse("svt_hip_rest_pick_plane: the units hold %llu samples, the plane %llu", off, p.plane_px);
     const uint64_t need = svt_hip_rest_pick_workspace_bytes(n_units, prm->plane_width, prm->plane_height, p.n_ep);

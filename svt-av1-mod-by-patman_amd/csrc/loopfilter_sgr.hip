@@ -26,16 +26,13 @@ using namespace svthip::lr;
 
 namespace {
 
-static const int32_t SGR_PRM_H[16][2] = {{2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1}, {2, 1},
-                                         {2, 1}, {2, 1}, {0, 1}, {0, 1}, {0, 1}, {0, 1}, {2, 0}, {2, 0}};
-
 struct SgrGeom {
     const void *dat;
     uint32_t    dat_stride, width, height;
     uint8_t     is16, bit_depth, pu_w, pu_h;
 };
 
-// MODE 0: write flt0 / flt1.  MODE 1: fused svt_apply_selfguided_restoration (projection with xq, clip, store samples).
+// MODE 0: write flt0 / flt1.  MODE 1: fused svt_apply_selfguided_restoration (sgr_project with xq, store samples).
 // SGR_NT threads share one 64x64 unit's 45 KB of LDS: three workgroups fit a CU, so the thread count sets the number of
 // waves that can cover each other's barrier phases
 constexpr int SGR_NT = 512;
@@ -52,7 +49,17 @@ __global__ __launch_bounds__(SGR_NT) void sgr_filter_kernel(SgrGeom g, int ep, i
         tile[r * TP + c] = (uint16_t)ldpx(g.dat, (size_t)((ptrdiff_t)(i0 + r - 3) * g.dat_stride + (j0 + c - 3)), g.is16);
     }
     __syncthreads();
-    sgr_tile_filter<MODE, SGR_NT>(tile, Am, Bm, tid, w, h, i0, j0, ep, g.bit_depth, g.is16, flt0, flt1, flt_stride, dst, dst_stride, xq0, xq1);
+    const int r0 = SGR_PRM[ep][0], r1 = SGR_PRM[ep][1], xq[2] = {xq0, xq1};
+    sgr_tile_filter_to<SGR_NT>(tile, Am, Bm, tid, w, h, ep, g.bit_depth, [&](int i, int j, int32_t x, int32_t f0, int32_t f1) {
+        if (MODE == 0) {
+            const size_t o = (size_t)(i0 + i) * flt_stride + j0 + j;
+            if (r0 > 0)
+                flt0[o] = f0;
+            if (r1 > 0)
+                flt1[o] = f1;
+        } else
+            stpx(dst, (size_t)(i0 + i) * dst_stride + j0 + j, g.is16, sgr_project(x, f0, f1, xq, r0, r1, g.bit_depth));
+    });
 }
 
 struct EpResult {
@@ -61,7 +68,7 @@ struct EpResult {
 };
 
 // One workgroup per epsilon candidate: get_proj_subspace + encode_xq + finer_search_pixel_proj_error.  All threads run
-// the (uniform) control flow; every err_of() is a block reduction whose result all threads see.
+// the (uniform) control flow; every error of the finer search (lr_device.hpp, one trial a pass) is a block reduction whose result all threads see.
 __global__ __launch_bounds__(1024) void sgr_search_ep_kernel(SvtHipSgrUnit un, const int32_t *__restrict__ work, uint32_t flt_stride,
                                                              int start_ep, int ep_inc, int do_refine, EpResult *__restrict__ res) {
     __shared__ long long scratch[17];
@@ -76,19 +83,13 @@ __global__ __launch_bounds__(1024) void sgr_search_ep_kernel(SvtHipSgrUnit un, c
     solve_subspace(sums, (int)(un.width * un.height), u.r0, u.r1, exq);
     encode_xq(exq, xqd, u.r0, u.r1);
     int       trials;
-    long long err = finer_search(u, xqd, do_refine, scratch, trials);
+    long long err = finer_search<1>(u, xqd, do_refine, scratch, trials);
     if (threadIdx.x == 0)
         res[blockIdx.x] = EpResult{err, ep, {xqd[0], xqd[1]}, 0};
 }
-// first strict minimum in candidate order (restoration_pick.c:638-643)
 __global__ void sgr_pick_kernel(const EpResult *res, int n, EpResult *best) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        EpResult b = res[0];
-        for (int i = 1; i < n; i++)
-            if (res[i].err < b.err)
-                b = res[i];
-        *best = b;
-    }
+    if (threadIdx.x == 0 && blockIdx.x == 0)
+        *best = res[first_min(res, n)];
 }
 
 // Tier A reductions over host-staged data: out[0..4] = subspace sums, out[5] = projection error for (xq0, xq1)
@@ -100,7 +101,9 @@ __global__ __launch_bounds__(1024) void sgr_stats_kernel(UnitData u, int xq0, in
         if (threadIdx.x == 0)
             for (int k = 0; k < 5; k++) out[k] = s[k];
     } else {
-        const long long e = unit_error(u, xq0, xq1, scratch);
+        const int xq[1][2] = {{xq0, xq1}};
+        long long e;
+        unit_errors<1>(u, xq, &e, scratch);
         if (threadIdx.x == 0)
             out[5] = e;
     }
@@ -151,13 +154,8 @@ extern "C" int32_t svt_hip_sgr_apply_unit(const SvtHipSgrUnit *unit, int32_t ep,
     TierBCall c("svt_hip_sgr_apply_unit", stream);
     if (!c.ok())
         return c.status();
-    int xq[2];  // svt_decode_xq (restoration.c:634-645)
-    if (SGR_PRM_H[ep][0] == 0)
-        xq[0] = 0, xq[1] = (1 << PRJ_BITS) - xqd[1];
-    else if (SGR_PRM_H[ep][1] == 0)
-        xq[0] = xqd[0], xq[1] = 0;
-    else
-        xq[0] = xqd[0], xq[1] = (1 << PRJ_BITS) - xq[0] - xqd[1];
+    int xq[2];
+    decode_xq(xqd, xq, SGR_PRM[ep][0], SGR_PRM[ep][1]);
     const dim3 grid((unit->width + unit->pu_w - 1) / unit->pu_w, (unit->height + unit->pu_h - 1) / unit->pu_h);
     hipLaunchKernelGGL(sgr_filter_kernel<1>, grid, dim3(SGR_NT), 0, c.stream(), geom_of(unit), ep, (int32_t *)nullptr,
                        (int32_t *)nullptr, 0u, d_dst, dst_stride, xq[0], xq[1]);
@@ -227,9 +225,9 @@ TIER_A_LEAF(void, svt_av1_selfguided_restoration,
     hipLaunchKernelGGL(sgr_filter_kernel<0>, grid, dim3(SGR_NT), 0, s.stream(), geom_of(&u), ep, s.dev<int32_t>(o_f0), s.dev<int32_t>(o_f1),
                        (uint32_t)width, (void *)nullptr, 0u, 0, 0);
     s.finish(o_f0, o_f1 + fl_bytes - o_f0);  // adjacent: one copy brings both back
-    if (SGR_PRM_H[ep][0] > 0)
+    if (SGR_PRM[ep][0] > 0)
         s.out_rows(flt0, (size_t)flt_stride * 4, o_f0, height, (size_t)width * 4);
-    if (SGR_PRM_H[ep][1] > 0)
+    if (SGR_PRM[ep][1] > 0)
         s.out_rows(flt1, (size_t)flt_stride * 4, o_f1, height, (size_t)width * 4);
 }
 

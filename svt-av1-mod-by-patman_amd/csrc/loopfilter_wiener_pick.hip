@@ -16,20 +16,15 @@
 //                  that chose Wiener), the two RDCOST_DBL of the plane, the units for svt_hip_restoration_filter_frame.
 // A trial is try_restoration_unit_seg (:129-165) with use_boundaries_in_rest_search == 0 (enc_handle.c:4127): the filter reads
 // the picture's own samples, replicated outside the cropped plane as svt_extend_frame leaves them.
-#include "common.hpp"
-#include "lr_device.hpp"
-#include "../../include/svt_hip_lf.h"
+#include "lr_pick.hpp"
 
 using namespace svthip;
+using namespace svthip::lr;
 
 namespace {
 
 constexpr int       W2MAX = 49;
 constexpr long long SCALE = 65536;  // WIENER_TAP_SCALE_FACTOR
-constexpr int       RESTORE_NONE = 0, RESTORE_WIENER = 1;
-constexpr long long SSE_REJECTED = 0x7fffffffffffffffLL;  // INT64_MAX
-using lr::count_refsubexpfin;
-using lr::rdcost_dbl;
 
 struct State {  // the search of one unit between two launches: the workspace
     int16_t            h[8], v[8];  // the filter of the trial that runs next (the best one once phase is DONE)
@@ -46,10 +41,7 @@ struct State {  // the search of one unit between two launches: the workspace
 static_assert(sizeof(State) == 112, "workspace record");
 constexpr int FIRST = 0, MOVE = 1, DONE = 2;
 
-__device__ __forceinline__ int tap_min(int p) { return p == 0 ? -5 : (p == 1 ? -23 : -17); }  // WIENER_FILT_TAPn_MINV
-__device__ __forceinline__ int tap_max(int p) { return p == 0 ? 10 : (p == 1 ? 8 : 46); }     // WIENER_FILT_TAPn_MAXV
 __device__ __forceinline__ int init_tap(int i) { return i == 3 ? 106 : (i == 0 || i == 6 ? 3 : (i == 1 || i == 5 ? -7 : 15)); }
-__device__ __forceinline__ void lds_add(long long *p, long long v) { atomicAdd((unsigned long long *)p, (unsigned long long)v); }
 
 // linsolve_wiener (:766-803), literally; A is the matrix (the caller's B), b the right-hand side (the caller's A)
 template <int N, int STRIDE> __device__ int linsolve(long long *A, long long *b, int32_t *x) {
@@ -268,8 +260,8 @@ __device__ void advance(State &st, const SearchPrm &prm, long long err2, long lo
 
 // grid (tiles of the largest unit, units)
 __global__ __launch_bounds__(256) void wpick_trial(const SvtHipWienerUnit *__restrict__ units, State *__restrict__ states, SearchPrm prm) {
-    constexpr int IP = lr::WIENER_IP, NT = 256;
-    __shared__ alignas(4) uint16_t in[(64 + 7) * IP + lr::WIENER_IN_SLACK];
+    constexpr int IP = WIENER_IP, NT = 256;
+    __shared__ alignas(4) uint16_t in[(64 + 7) * IP + WIENER_IN_SLACK];
     __shared__ uint16_t            tmp[(64 + 7) * 64];
     __shared__ long long           s_sum[2];
     const int tid = threadIdx.x;
@@ -288,16 +280,13 @@ __global__ __launch_bounds__(256) void wpick_trial(const SvtHipWienerUnit *__res
     for (int k = 0; k < 8; k++) fx[k] = st.h[k], fy[k] = st.v[k];
     if (tid < 2)
         s_sum[tid] = 0;
-    for (int idx = tid; idx < (th + 7) * (tw + 7); idx += NT) {  // the picture's own samples, replicated outside the cropped plane
-        const int r = idx / (tw + 7), c = idx - r * (tw + 7);
-        const int y = min(max(u.v_start + y0 + r - 3, 0), prm.plane_h - 1), x = min(max(u.h_start + x0 + c - 3, 0), prm.plane_w - 1);
-        in[r * IP + c] = (uint16_t)lr::ldpx(u.dgd, (size_t)y * u.dgd_stride + x, is16);
-    }
+    // the picture's own samples, replicated outside the cropped plane
+    load_tile_clamped(in, IP, u.dgd, u.dgd_stride, is16, prm.plane_w, prm.plane_h, u.v_start + y0 - 3, u.h_start + x0 - 3, th + 7, tw + 7, NT);
     __syncthreads();
     long long acc = 0, accn = 0;
-    auto source = [&](int r, int c) { return lr::ldpx(u.src, (size_t)(u.v_start + y0 + r) * u.src_stride + (u.h_start + x0 + c), is16); };
+    auto source = [&](int r, int c) { return ldpx(u.src, (size_t)(u.v_start + y0 + r) * u.src_stride + (u.h_start + x0 + c), is16); };
     if (filter) {  // the filter of lr_device.hpp, the store replaced by the squared differences against the source
-        lr::wiener_tile_filter_to<NT>(in, tmp, tid, tw, th, fx, fy, bd, r0, r1, [&](int r, int c, int32_t v) {
+        wiener_tile_filter_to<NT>(in, tmp, tid, tw, th, fx, fy, bd, r0, r1, [&](int r, int c, int32_t v) {
             const int32_t s = source(r, c);
             acc += (long long)((v - s) * (v - s));
             if (with_none) {
@@ -312,7 +301,7 @@ __global__ __launch_bounds__(256) void wpick_trial(const SvtHipWienerUnit *__res
             accn += (long long)(d * d);
         }
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off), accn += __shfl_down(accn, off);
+    acc = wave_sum64(acc), accn = wave_sum64(accn);
     if ((tid & 63) == 0)
         lds_add(&s_sum[0], acc), lds_add(&s_sum[1], accn);
     __syncthreads();  // every thread of this workgroup has read the state
@@ -361,9 +350,10 @@ __global__ __launch_bounds__(256) void wpick_decide(const State *__restrict__ st
     }
     auto count = [&](int p, int ref, int v) {  // taps outside their range (a previous frame's record can hold anything) are counted directly
         const int n = 16 << p, r = ref - tap_min(p), x = v - tap_min(p);
-        return (unsigned)r < (unsigned)n && (unsigned)x < (unsigned)n ? (int)s_count[(p == 0 ? 0 : (p == 1 ? T1 : T2)) + r * n + x] : count_refsubexpfin(n, p + 1, r, x);
+        return (unsigned)r < (unsigned)n && (unsigned)x < (unsigned)n ? (int)s_count[(p == 0 ? 0 : (p == 1 ? T1 : T2)) + r * n + x] : wiener_tap_bits(p, ref, v);
     };
-    int             ref[6] = {3, -7, 15, 3, -7, 15}, n_wiener = 0;  // set_default_wiener; thread 0's alone
+    int ref[6], n_wiener = 0;  // thread 0's alone
+    set_default_wiener(ref);
     long long       sse_n = 0, sse_w = 0, bits_w = 0;
     const long long bits_none = cost0;
     for (int base = 0; base < n_units; base += CH) {
@@ -389,11 +379,7 @@ __global__ __launch_bounds__(256) void wpick_decide(const State *__restrict__ st
                     s_bits[k] = bits_none, s_best[k] = RESTORE_NONE;
                     continue;
                 }
-                int c = 0;  // count_wiener_bits (:1008-1037): the vertical taps, then the horizontal ones
-                for (int t = 0; t < 6; t++)
-                    if (win == 7 || t % 3 != 0)
-                        c += count(t % 3, ref[t], s_taps[k][t]);
-                const long long bits_wiener = cost1 + (c << 9);
+                const long long bits_wiener = cost1 + (count_wiener_bits(win, s_taps[k], ref, count) << 9);
                 const double    cost_wiener = (((double)(bits_wiener >> 4) * (double)rdmult) / 512.0) + s_dist_w[k];  // RDCOST_DBL, the distortion term from above
                 const bool      wiener      = cost_wiener < s_cost_none[k];
                 s_bits[k] = bits_wiener, s_best[k] = wiener ? RESTORE_WIENER : RESTORE_NONE;
@@ -443,22 +429,13 @@ extern "C" int svt_hip_wiener_pick_plane(const SvtHipWienerPickParams *prm, cons
         return refuse("svt_hip_wiener_pick_plane: %u units (1..65535)", n_units);
     if (prm->wiener_win != 7 && prm->wiener_win != 5)
         return refuse("svt_hip_wiener_pick_plane: wiener_win %d is neither 7 nor 5", prm->wiener_win);
-    if ((prm->bit_depth != 8 && prm->bit_depth != 10 && prm->bit_depth != 12) || (prm->bit_depth > 8 && !prm->is_16bit))
-        return refuse("svt_hip_wiener_pick_plane: bit depth %d with %s samples", prm->bit_depth, prm->is_16bit ? "16-bit" : "8-bit");
-    if (prm->plane_width == 0 || prm->plane_height == 0 || prm->plane_width > 65536 || prm->plane_height > 65536)
-        return refuse("svt_hip_wiener_pick_plane: plane of %u x %u", prm->plane_width, prm->plane_height);
+    if (const int32_t rc = pick_plane_ok("svt_hip_wiener_pick_plane", prm->bit_depth, prm->is_16bit, prm->plane_width, prm->plane_height); rc != SVT_HIP_OK)
+        return rc;
     int max_tiles = 0;
-    for (uint32_t i = 0; i < n_units; i++) {
-        const SvtHipWienerUnit &u = units[i];
-        if (!u.dgd || !u.src || u.h_start < 0 || u.v_start < 0 || u.h_end <= u.h_start || u.v_end <= u.v_start ||
-            (uint32_t)u.h_end > prm->plane_width || (uint32_t)u.v_end > prm->plane_height)
-            return refuse("svt_hip_wiener_pick_plane: unit %u: limits [%d, %d) x [%d, %d) outside the plane of %u x %u", i, u.h_start, u.h_end, u.v_start,
-                          u.v_end, prm->plane_width, prm->plane_height);
-        if (u.h_end - u.h_start > 4096 || u.v_end - u.v_start > 4096)
-            return refuse("svt_hip_wiener_pick_plane: unit %u: %d x %d samples, 4096 at the most", i, u.h_end - u.h_start, u.v_end - u.v_start);
-        const int tiles = ((u.h_end - u.h_start + 63) >> 6) * ((u.v_end - u.v_start + 63) >> 6);
-        max_tiles       = tiles > max_tiles ? tiles : max_tiles;
-    }
+    if (const int32_t rc = pick_units_ok("svt_hip_wiener_pick_plane", units, n_units, prm->plane_width, prm->plane_height, 4096,
+                                         [&](uint32_t, const SvtHipWienerUnit &, int uw, int uh) { max_tiles = std::max(max_tiles, ((uw + 63) >> 6) * ((uh + 63) >> 6)); });
+        rc != SVT_HIP_OK)
+        return rc;
     if (workspace_bytes < svt_hip_wiener_pick_workspace_bytes(n_units) || ((uintptr_t)d_workspace & 7) || ((uintptr_t)d_result & 7) ||
         ((uintptr_t)d_unit_records & 7))
         return refuse("svt_hip_wiener_pick_plane: workspace of %llu bytes, %llu needed (workspace, records and result 8-byte aligned)",

@@ -2,8 +2,11 @@
 // loopfilter_lr_frame.hip): the self-guided filter and the Wiener filter of ONE processing unit whose samples (with their
 // 3-sample border) already sit in LDS.  Who fills the tile decides what the filter sees: straight picture samples for the
 // per-unit entry points, the stripe-boundary rows of svt_aom_setup_processing_stripe_boundary for the frame-level pass.
+// Both tile filters hand every result to a sink: a store, a sum, whatever the caller does with it.
 // Also here: what the restoration decisions share (loopfilter_sgr.hip, loopfilter_wiener_pick.hip, loopfilter_rest_pick.hip): the
-// projection sums, solver, error and finer search of the self-guided filter, the sub-exponential bit count and RDCOST_DBL.
+// projection of svt_apply_selfguided_restoration, the clamped tile load of the two picks, the projection sums, the solver, the batched
+// error and finer search of the self-guided filter (the batch size a template parameter), the first minimum over candidates, the
+// sub-exponential bit count and RDCOST_DBL.  lr_pick.hpp adds what only the two plane picks need.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,17 +20,34 @@ constexpr int TP = 72;   // LDS pitch of the sample tile (64 + 2*3 = 70 used)
 constexpr int AP = 67;   // LDS pitch of the A / B maps (66 used, odd)
 constexpr int PRJ_MIN0 = -96, PRJ_MAX0 = 31, PRJ_MIN1 = -32, PRJ_MAX1 = 95;  // restoration.h:101-104
 
-static __device__ const int32_t SGR_PRM[16][4] = {/* r0, r1, s0, s1: svt_aom_eb_sgr_params (restoration.c:85-103) */
+constexpr int32_t SGR_PRM[16][4] = {/* r0, r1, s0, s1: svt_aom_eb_sgr_params (restoration.c:85-103); host code reads the radii */
                                            {2, 1, 140, 3236}, {2, 1, 112, 2158}, {2, 1, 93, 1618}, {2, 1, 80, 1438},
-                                           {2, 1, 70, 1295},  {2, 1, 58, 1177},  {2, 1, 47, 1079}, {2, 1, 37, 996},
-                                           {2, 1, 30, 925},   {2, 1, 25, 863},   {0, 1, -1, 2589}, {0, 1, -1, 1618},
-                                           {0, 1, -1, 1177},  {0, 1, -1, 925},   {2, 0, 56, -1},   {2, 0, 22, -1}};
+                                      {2, 1, 70, 1295},  {2, 1, 58, 1177},  {2, 1, 47, 1079}, {2, 1, 37, 996},
+                                      {2, 1, 30, 925},   {2, 1, 25, 863},   {0, 1, -1, 2589}, {0, 1, -1, 1618},
+                                      {0, 1, -1, 1177},  {0, 1, -1, 925},   {2, 0, 56, -1},   {2, 0, 22, -1}};
 
 __device__ __forceinline__ int32_t rnd(int32_t v, int n) { return (v + ((1 << n) >> 1)) >> n; }
 __device__ __forceinline__ int32_t ldpx(const void *p, size_t idx, int is16) {
     return is16 ? ((const __attribute__((address_space(1))) uint16_t *)p)[idx] : ((const __attribute__((address_space(1))) uint8_t *)p)[idx];  // pictures are global memory: no flat loads
 }
+__device__ __forceinline__ void stpx(void *p, size_t idx, int is16, int32_t v) {
+    if (is16)
+        ((uint16_t *)p)[idx] = (uint16_t)v;
+    else
+        ((uint8_t *)p)[idx] = (uint8_t)v;
+}
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// rows x cols samples from (y, x) of a plane into an LDS tile of the given pitch, by the nt threads of the workgroup.  Coordinates are
+// clamped to the plane: outside the cropped plane the samples replicate its edge (svt_extend_frame), nothing outside is read.
+__device__ __forceinline__ void load_tile_clamped(uint16_t *tile, int pitch, const void *plane, uint32_t stride, int is16, int plane_w, int plane_h, int y, int x,
+                                                  int rows, int cols, int nt) {
+    for (int idx = threadIdx.x; idx < rows * cols; idx += nt) {
+        const int r = idx / cols, c = idx - r * cols;
+        const int yy = min(max(y + r, 0), plane_h - 1), xx = min(max(x + c, 0), plane_w - 1);
+        tile[r * pitch + c] = (uint16_t)ldpx(plane, (size_t)yy * stride + xx, is16);
+    }
+}
 
 // A / B of one map position from the LDS tile (restoration.c:709-770 / 842-903); (i, j) relative to the unit, r = 1 | 2
 template <int R> __device__ __forceinline__ void ab_at(const uint16_t *tile, int i, int j, uint32_t s, int bd, int32_t &A, int32_t &B) {
@@ -64,15 +84,23 @@ template <int R> __device__ __forceinline__ void ab_at(const uint16_t *tile, int
     B = (int32_t)(((uint32_t)(256 - A) * sum * one_by_n + (1u << (RECIP_BITS - 1))) >> RECIP_BITS);
 }
 
+// The projection of svt_apply_selfguided_restoration (restoration.c:957-992): sample x restored from its two filtered values
+__device__ __forceinline__ int32_t sgr_project(int32_t x, int32_t f0, int32_t f1, const int xq[2], int r0, int r1, int bd) {
+    const int32_t u = x << RST_BITS;
+    int32_t       v = u << PRJ_BITS;
+    if (r0 > 0)
+        v += xq[0] * (f0 - u);
+    if (r1 > 0)
+        v += xq[1] * (f1 - u);
+    const int16_t wv = (int16_t)rnd(v, PRJ_BITS + RST_BITS);
+    return clampi(wv, 0, (1 << bd) - 1);
+}
+
 // Filter of one processing unit of w x h samples (<= 64 x 64) from the LDS tile (pitch TP, sample (0,0) at [3][3]); Am / Bm are
-// 66 x AP int32 scratch maps in LDS.  MODE 0: write flt0 / flt1 (at [i0 + i][j0 + j]).  MODE 1: fused
-// svt_apply_selfguided_restoration (projection with xq, clip, store samples to dst).  Called by all NT threads of the workgroup
-// after a barrier that made the tile visible; contains barriers.
-// MODE 2: nothing is stored; sink(i, j, sample, f0, f1) gets every sample of the unit with its two filtered values (0 where the radius is 0).
-template <int MODE, int NT, class Sink>
-__device__ __forceinline__ void sgr_tile_filter_to(const uint16_t *tile, int32_t *Am, int32_t *Bm, int tid, int w, int h, int i0, int j0, int ep, int bd,
-                                                   int is16, int32_t *__restrict__ flt0, int32_t *__restrict__ flt1, uint32_t flt_stride,
-                                                   void *__restrict__ dst, uint32_t dst_stride, int xq0, int xq1, Sink sink) {
+// 66 x AP int32 scratch maps in LDS.  Nothing is stored: sink(i, j, sample, f0, f1) gets every sample of the unit with its two filtered
+// values (0 where the radius is 0).  Called by all NT threads of the workgroup after a barrier that made the tile visible; contains barriers.
+template <int NT, class Sink>
+__device__ __forceinline__ void sgr_tile_filter_to(const uint16_t *tile, int32_t *Am, int32_t *Bm, int tid, int w, int h, int ep, int bd, Sink sink) {
     const int r0 = SGR_PRM[ep][0], r1 = SGR_PRM[ep][1];
     constexpr int PER = 64 * 64 / NT;  // samples per thread of a 64x64 unit
     int32_t       f0[PER];
@@ -102,8 +130,6 @@ __device__ __forceinline__ void sgr_tile_filter_to(const uint16_t *tile, int32_t
                 }
                 const int32_t v = a * (int32_t)tile[(i + 3) * TP + j + 3] + b;
                 f0[k]           = rnd(v, SGR_BITS + nb - RST_BITS);
-                if (MODE == 0)
-                    flt0[(size_t)(i0 + i) * flt_stride + j0 + j] = f0[k];
             }
         }
         __syncthreads();
@@ -128,34 +154,9 @@ __device__ __forceinline__ void sgr_tile_filter_to(const uint16_t *tile, int32_t
             const int32_t a = (A[0] + A[-1] + A[1] + A[-AP] + A[AP]) * 4 + (A[-AP - 1] + A[AP - 1] + A[-AP + 1] + A[AP + 1]) * 3;
             const int32_t b = (B[0] + B[-1] + B[1] + B[-AP] + B[AP]) * 4 + (B[-AP - 1] + B[AP - 1] + B[-AP + 1] + B[AP + 1]) * 3;
             f1              = rnd(a * (int32_t)tile[(i + 3) * TP + j + 3] + b, SGR_BITS + 5 - RST_BITS);
-            if (MODE == 0)
-                flt1[(size_t)(i0 + i) * flt_stride + j0 + j] = f1;
         }
-        if (MODE == 1) {
-            const int32_t u = (int32_t)tile[(i + 3) * TP + j + 3] << RST_BITS;
-            int32_t       v = u << PRJ_BITS;
-            if (r0 > 0)
-                v += xq0 * (f0[k] - u);
-            if (r1 > 0)
-                v += xq1 * (f1 - u);
-            const int16_t wv = (int16_t)rnd(v, PRJ_BITS + RST_BITS);
-            const int32_t hi = (1 << bd) - 1, o = wv < 0 ? 0 : (wv > hi ? hi : wv);
-            const size_t  di = (size_t)(i0 + i) * dst_stride + j0 + j;
-            if (is16)
-                ((uint16_t *)dst)[di] = (uint16_t)o;
-            else
-                ((uint8_t *)dst)[di] = (uint8_t)o;
-        }
-        if (MODE == 2)
-            sink(i, j, (int32_t)tile[(i + 3) * TP + j + 3], f0[k], f1);
+        sink(i, j, (int32_t)tile[(i + 3) * TP + j + 3], f0[k], f1);
     }
-}
-template <int MODE, int NT>
-__device__ __forceinline__ void sgr_tile_filter(const uint16_t *tile, int32_t *Am, int32_t *Bm, int tid, int w, int h, int i0, int j0, int ep, int bd,
-                                                int is16, int32_t *__restrict__ flt0, int32_t *__restrict__ flt1, uint32_t flt_stride,
-                                                void *__restrict__ dst, uint32_t dst_stride, int xq0, int xq1) {
-    sgr_tile_filter_to<MODE, NT>(tile, Am, Bm, tid, w, h, i0, j0, ep, bd, is16, flt0, flt1, flt_stride, dst, dst_stride, xq0, xq1,
-                                 [](int, int, int32_t, int32_t, int32_t) {});
 }
 
 // Separable 7-tap Wiener filter of one tw x th (<= 64 x 64) unit: `in` = LDS tile of (th + 7) x (tw + 7) samples (4-byte aligned, WIENER_IN_SLACK readable elements behind it), pitch IP, sample
@@ -208,13 +209,8 @@ __device__ __forceinline__ void wiener_tile_filter_to(const uint16_t *in, uint16
 template <int NT>
 __device__ __forceinline__ void wiener_tile_filter(const uint16_t *in, uint16_t *tmp, int tid, int tw, int th, int x0, int y0, const int16_t *fx,
                                                    const int16_t *fy, int bd, int r0, int r1, int is16, void *__restrict__ dst, uint32_t dst_stride) {
-    wiener_tile_filter_to<NT>(in, tmp, tid, tw, th, fx, fy, bd, r0, r1, [&](int r, int c, int32_t v) {
-        const size_t o = (size_t)(y0 + r) * dst_stride + x0 + c;
-        if (is16)
-            ((uint16_t *)dst)[o] = (uint16_t)v;
-        else
-            ((uint8_t *)dst)[o] = (uint8_t)v;
-    });
+    wiener_tile_filter_to<NT>(in, tmp, tid, tw, th, fx, fy, bd, r0, r1,
+                              [&](int r, int c, int32_t v) { stpx(dst, (size_t)(y0 + r) * dst_stride + x0 + c, is16, v); });
 }
 
 // ---- block-wide int64 reductions -------------------------------------------------------------------------------
@@ -243,23 +239,39 @@ struct UnitData {
     int            is16, r0, r1;
 };
 
-// svt_av1_{lowbd,highbd}_pixel_proj_error_c over the unit (block-wide)
-__device__ inline long long unit_error(const UnitData &u, int xq0, int xq1, long long *scratch) {
-    long long      acc = 0;
-    const uint32_t n   = u.width * u.height;
+// svt_av1_{lowbd,highbd}_pixel_proj_error_c over the unit (block-wide) for NB decoded candidates xq in ONE pass (the pass is bound by its
+// reads: two filtered values, dat and src per sample); every thread gets all NB sums.  scratch: NB long long per wave.  A plane whose
+// radius is 0 is not read, so with both radii 0 the error is that of dat - src whatever xq holds: the Tier A projection leaves can pass
+// such parameters.
+template <int NB> __device__ inline void unit_errors(const UnitData &u, const int (*xq)[2], long long *out, long long *scratch) {
+    long long      acc[NB] = {};
+    const uint32_t n = u.width * u.height;
+#pragma unroll(NB > 1 ? 2 : 1)  // a batch has the work to fill two iterations in flight; one candidate per pass is the plain loop
     for (uint32_t idx = threadIdx.x; idx < n; idx += blockDim.x) {
         const uint32_t i = idx / u.width, j = idx - i * u.width;
         const int32_t  d = ldpx(u.dat, (size_t)i * u.dat_stride + j, u.is16), s = ldpx(u.src, (size_t)i * u.src_stride + j, u.is16);
         const int32_t  uu = d << RST_BITS;
-        int32_t        v  = 1 << (RST_BITS + PRJ_BITS - 1);
-        if (u.r0 > 0)
-            v += xq0 * (u.flt0[(size_t)i * u.flt0_stride + j] - uu);
-        if (u.r1 > 0)
-            v += xq1 * (u.flt1[(size_t)i * u.flt1_stride + j] - uu);
-        const int32_t e = (u.r0 > 0 || u.r1 > 0) ? (v >> (RST_BITS + PRJ_BITS)) + d - s : d - s;
-        acc += (long long)e * e;
+        const int32_t  a0 = u.r0 > 0 ? u.flt0[(size_t)i * u.flt0_stride + j] - uu : 0, a1 = u.r1 > 0 ? u.flt1[(size_t)i * u.flt1_stride + j] - uu : 0;
+#pragma unroll
+        for (int k = 0; k < NB; k++) {
+            const int32_t v = (1 << (RST_BITS + PRJ_BITS - 1)) + xq[k][0] * a0 + xq[k][1] * a1, e = (v >> (RST_BITS + PRJ_BITS)) + d - s;
+            acc[k] += (long long)e * e;
+        }
     }
-    return block_sum64(acc, scratch);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NB; k++) acc[k] = wave_sum64(acc[k]);
+    __syncthreads();  // scratch free
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < NB; k++) scratch[wv * NB + k] = acc[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+        long long t = 0;
+        for (int w = 0; w < nw; w++) t += scratch[w * NB + k];
+        out[k] = t;
+    }
 }
 
 // the five sums of svt_get_proj_subspace_c (block-wide)
@@ -299,8 +311,8 @@ __device__ inline void solve_subspace(const long long sums[5], int size, int r0,
         xq[0] = (int)rint(x0 * (1 << PRJ_BITS)), xq[1] = (int)rint(x1 * (1 << PRJ_BITS));
     }
 }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ inline void decode_xq(const int xqd[2], int xq[2], int r0, int r1) {
+// svt_decode_xq (restoration.c:634-645); the host decodes with it too
+__host__ __device__ inline void decode_xq(const int xqd[2], int xq[2], int r0, int r1) {
     if (r0 == 0)
         xq[0] = 0, xq[1] = (1 << PRJ_BITS) - xqd[1];
     else if (r1 == 0)
@@ -320,58 +332,78 @@ __device__ inline void encode_xq(const int xq[2], int xqd[2], int r0, int r1) {
         xqd[1] = clampi((1 << PRJ_BITS) - xqd[0] - xq[1], PRJ_MIN1, PRJ_MAX1);
     }
 }
-__device__ inline long long err_of(const UnitData &u, const int xqd[2], long long *scratch) {
-    int xq[2];
-    decode_xq(xqd, xq, u.r0, u.r1);
-    return unit_error(u, xq[0], xq[1], scratch);
-}
 
 // finer_search_pixel_proj_error (restoration_pick.c:320-411) with start_step 2, block-wide: every thread runs the (uniform) control flow,
-// every err_of() is a block reduction whose result all threads see.  xqd is moved in place; trials = get_pixel_proj_error calls.
-__device__ inline long long finer_search(const UnitData &u, int xqd[2], int do_refine, long long *scratch, int &trials) {
-    long long err = err_of(u, xqd, scratch), err2;
+// every pass over the unit is a block reduction whose result all threads see.  xqd is moved in place; trials = get_pixel_proj_error calls.
+// The accepted path and the count of trials are the reference's; what NB sets is how many errors one pass over the unit yields: a walk
+// at step 2 ("at the highest step size continue moving in the same direction") has its next NB moves evaluated together, and the moves
+// behind the first refused one are dropped unused (and not counted).  NB = 1 is the reference's loop trial by trial.  scratch: as unit_errors.
+template <int NB> __device__ inline long long finer_search(const UnitData &u, int xqd[2], int do_refine, long long *scratch, int &trials) {
+    int       cq[NB][2];
+    long long e[NB];
+    auto errors = [&]() {
+        int xq[NB][2];
+#pragma unroll
+        for (int k = 0; k < NB; k++) decode_xq(cq[k], xq[k], u.r0, u.r1);
+        unit_errors<NB>(u, xq, e, scratch);
+    };
+#pragma unroll
+    for (int k = 0; k < NB; k++) cq[k][0] = xqd[0], cq[k][1] = xqd[1];
+    errors();
+    long long err = e[0];
     trials        = 1;
     if (!do_refine)
         return err;
-    const int tap_min[2] = {PRJ_MIN0, PRJ_MIN1}, tap_max[2] = {PRJ_MAX0, PRJ_MAX1};
-    const int start_step = 2;
-    for (int s = start_step; s >= 1; s >>= 1)
+    for (int s = 2; s >= 1; s >>= 1)
         for (int p = 0; p < 2; ++p) {
             if ((u.r0 == 0 && p == 0) || (u.r1 == 0 && p == 1))
                 continue;
-            int skip = 0;
-            do {
-                if (xqd[p] - s >= tap_min[p]) {
-                    xqd[p] -= s;
-                    err2 = err_of(u, xqd, scratch), trials++;
-                    if (err2 > err)
-                        xqd[p] += s;
-                    else {
-                        err = err2, skip = 1;
-                        if (s == start_step)
-                            continue;
+            const int lo = p == 0 ? PRJ_MIN0 : PRJ_MIN1, hi = p == 0 ? PRJ_MAX0 : PRJ_MAX1;
+            int       skip = 0;
+            for (int dir = -1; dir <= 1; dir += 2) {  // the two do-while loops
+                for (bool walk = true; walk;) {
+                    const int cur = p == 0 ? xqd[0] : xqd[1], room = (dir < 0 ? cur - lo : hi - cur) / s, nb = min(room, s == 2 ? NB : 1);
+                    if (nb == 0)
+                        break;  // the move would leave the range: `break` without a trial
+#pragma unroll
+                    for (int k = 0; k < NB; k++) {
+                        const int v = cur + dir * s * (min(k, nb - 1) + 1);
+                        cq[k][0] = p == 0 ? v : xqd[0], cq[k][1] = p == 0 ? xqd[1] : v;
+                    }
+                    errors();
+                    walk = s == 2;
+#pragma unroll
+                    for (int k = 0; k < NB; k++) {
+                        if (k >= nb)
+                            break;
+                        trials++;
+                        if (e[k] > err) {  // refused: the move is undone, the walk ends
+                            walk = false;
+                            break;
+                        }
+                        err = e[k], skip |= dir < 0;
+                        if (p == 0)
+                            xqd[0] += dir * s;
+                        else
+                            xqd[1] += dir * s;
                     }
                 }
-                break;
-            } while (1);
+                if (skip)
+                    break;
+            }
             if (skip)
-                break;
-            do {
-                if (xqd[p] + s <= tap_max[p]) {
-                    xqd[p] += s;
-                    err2 = err_of(u, xqd, scratch), trials++;
-                    if (err2 > err)
-                        xqd[p] -= s;
-                    else {
-                        err = err2;
-                        if (s == start_step)
-                            continue;
-                    }
-                }
-                break;
-            } while (1);
+                break;  // `if (skip) break;` leaves the loop over p
         }
     return err;
+}
+
+// The first strictly smallest error in candidate order (restoration_pick.c:638-643); c[i].err is candidate i's
+template <class Cand> __device__ __forceinline__ int first_min(const Cand *c, int n) {
+    int b = 0;
+    for (int i = 1; i < n; i++)
+        if (c[i].err < c[b].err)
+            b = i;
+    return b;
 }
 
 // svt_aom_count_primitive_refsubexpfin (entropy_coding.c:2805-2951)
@@ -404,7 +436,6 @@ __device__ inline int count_refsubexpfin(int n, int k, int ref, int v) {
 __device__ __forceinline__ double rdcost_dbl(int rdmult, long long rate, long long dist) {  // RDCOST_DBL (restoration.h:346)
     return (((double)rate * (double)rdmult) / 512.0) + ((double)dist * 128.0);
 }
-
 
 }  // namespace lr
 }  // namespace svthip

@@ -20,6 +20,13 @@ def sgr_plane(rng, w, h, bd, is16, kind):
     return dat, src
 
 
+def sgr_tie_plane(rng, w, h):
+    """8-bit in bytes: a constant degraded picture (every filtered value equals the sample, so every trial of the finer search ties and
+    the step-2 walk only ends at the clamp) under a random original."""
+    dat = np.full((h + 2 * B, w + 2 * B), int(rng.integers(0, 256)), np.uint8)
+    return dat, rng.integers(0, 256, size=dat.shape).astype(np.uint8)
+
+
 def at(a):
     return a.ctypes.data + (B * a.shape[1] + B) * a.itemsize
 

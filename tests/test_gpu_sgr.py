@@ -76,18 +76,24 @@ def gpu_unit(hip, dat, src, w, h, bd, is16, pu):
     return abi.SgrUnit(d_dat.ptr + off, d_src.ptr + off, dat.shape[1], src.shape[1], w, h, is16, bd, pu, pu), (d_dat, d_src)
 
 
-@pytest.mark.parametrize("case", range(8))
+TIE_CASE = 8  # one full and one partial processing unit; every trial of the finer search ties
+
+
+@pytest.mark.parametrize("case", range(9))
 def test_tier_b_search_filter_apply(hip, orc, case):
     rng = np.random.default_rng(200 + case)
-    w, h = ((96, 80), (136, 72), (64, 64), (200, 120), (56, 40), (384, 96), (256, 256), (328, 200))[case]
-    bd, is16 = ((8, 0), (10, 1), (8, 1))[case % 3]
+    w, h = ((96, 80), (136, 72), (64, 64), (200, 120), (56, 40), (384, 96), (256, 256), (328, 200), (72, 40))[case]
+    bd, is16 = (8, 0) if case == TIE_CASE else ((8, 0), (10, 1), (8, 1))[case % 3]
     pu = 64 if case % 2 == 0 else 32
     start, end, inc, refine = ((0, 16, 1, 1), (0, 16, 2, 1), (10, 16, 1, 0), (0, 8, 3, 1), (14, 16, 1, 1), (0, 16, 4, 1), (0, 16, 1, 1),
-                               (3, 4, 1, 1))[case]
-    dat, src = G.sgr_plane(rng, w, h, bd, is16, (0, 0, 2)[case % 3])
+                               (3, 4, 1, 1), (0, 16, 1, 1))[case]
+    dat, src = G.sgr_tie_plane(rng, w, h) if case == TIE_CASE else G.sgr_plane(rng, w, h, bd, is16, (0, 0, 2)[case % 3])
     o1 = np.zeros(3, np.int32)
     orc.orc_sgr_search_unit.restype = I64
     e1 = orc.orc_sgr_search_unit(V(G.at(dat)), w, h, dat.shape[1], V(G.at(src)), src.shape[1], is16, bd, pu, pu, start, end, inc, refine, P(o1))
+    if case == TIE_CASE:  # the walk at step 2 ran to the clamp: each searched tap ends on its limit or one step (of the last pass) from it
+        for p, (lo, hi) in enumerate(((-96, 31), (-32, 95))):  # SGRPROJ_PRJ_MIN0 / _MAX0, _MIN1 / _MAX1 (restoration.h:101-104)
+            assert abi.SGR_PARAMS[int(o1[0])][p] == 0 or min(int(o1[1 + p]) - lo, hi - int(o1[1 + p])) <= 1, o1
     unit, keep = gpu_unit(hip, dat, src, w, h, bd, is16, pu)
     n_ep = (end - start + inc - 1) // inc
     work = device.DeviceBuffer(hip, hip.svt_hip_sgr_search_work_bytes(w, h, n_ep))
