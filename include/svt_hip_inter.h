@@ -1,7 +1,7 @@
 /*
  * svt_hip_inter.h — C-ABI for inter prediction: interpolation (the single-reference and the
  * compound ("jnt") families), the masked-compound and OBMC blends, the compound mask search, warped prediction (local warp
- * and global motion), the global-motion error / refinement, the sub-pel motion search of mode decision and OBMC's weighted
+ * and global motion), the global-motion error / refinement, the full-pel and the sub-pel motion search of mode decision and OBMC's weighted
  * target and motion refinement.
  *
  * Reference interfaces replaced (paths relative to /root/reference):
@@ -21,6 +21,8 @@
  *   Source/Lib/Codec/enc_warped_motion.c:22-98   svt_av1_warp_error
  *   Source/Lib/Codec/global_motion.c:86-251      add_param_offset, force_wmtype, svt_av1_refine_integerized_param
  *   Source/Lib/Codec/mcomp.c:609-775             svt_av1_find_best_sub_pixel_tree(_pruned) as md_subpel_search calls them
+ *   Source/Lib/Codec/product_coding_loop.c:1781-2046, 2075-2498, 3087-3108, 3263   md_full_pel_search under md_sq_motion_search,
+ *                                                md_nsq_motion_search and pme_search, and the MVP scoring
  *   Source/Lib/Codec/enc_inter_prediction.c:1592-1649, 1767-1827   calc_target_weighted_pred and its two visitors
  *   Source/Lib/Codec/mode_decision.c:2425-2533, av1me.c:709-1132   single_motion_search (OBMC_CAUSAL): svt_av1_obmc_full_pixel_search,
  *                                                svt_av1_find_best_obmc_sub_pixel_tree_up, svt_aom_obmc_sad* / svt_aom_obmc_variance*
@@ -376,6 +378,109 @@ SVT_HIP_API int32_t svt_hip_subpel_search_batch(const SvtHipSubpelJob *job, cons
  * limits: col_min, col_max, row_min, row_max.  Host only, no device.  SVT_HIP_ERR_BAD_PARAMETER for a NULL pointer. */
 SVT_HIP_API int32_t svt_hip_subpel_mv_limits(int32_t mi_row, int32_t mi_col, int32_t mi_width, int32_t mi_height, int32_t mi_rows,
                                              int32_t mi_cols, const SvtHipMv *ref_mv, int32_t limits[4]);
+
+/* ---- Full-pel motion search of mode decision (Tier B) ----------------------------------------------------------------------
+ * One descriptor = one luma block of one (list, reference): md_full_pel_search (product_coding_loop.c:1918-2046) with
+ * md_full_pel_search_large_lbd / svt_pme_sad_loop_kernel_c behind it, chained the way its callers chain it:
+ *   SVT_HIP_FPEL_MVP  the scoring of :3087-3108: vf (variance) at each of up to 4 vectors, no clip, no vector cost, strict < from
+ *                     (uint32_t)~0 in index order -> best_fp_mvp_idx / best_fp_mvp_dist;
+ *   SVT_HIP_FPEL_SQ   md_sq_motion_search (:2314-2498): the probe at the ME vector, the gate, sparse levels 0 -> 1 -> 2;
+ *   SVT_HIP_FPEL_NSQ  md_nsq_motion_search (:2141-2241) from the MVC list on: the rounded MVCs into one search centre, then
+ *                     steps 4, 2, 1, taken only if strictly below the centre's cost;
+ *   SVT_HIP_FPEL_PME  the one md_full_pel_search call of pme_search (:3263): step 1 around the best MVP.
+ * Restated with the reference's types: uint32_t cost + int vector cost wraps, vectors and their differences are int16_t, mv >> 3 is
+ * arithmetic on vectors that need not be full-pel, a clip may leave start > end (nothing is visited, the outputs keep their incoming
+ * values), the generic scan is column-major and the psad scan (dist_type SAD, enable_psad, end_x - start_x >= 7 after the clip)
+ * row-major over eight columns out of every 7 + step with its width raised to a multiple of 8.  The first position in scan order wins a tie.
+ * 8-bit only, as every caller (hbd_md = EB_8_BIT_MD).  Not covered: scaled references, the derivation of the MVCs and MVPs,
+ * svt_aom_choose_best_av1_mv_pred, the early / post checks of pme_search and its q_weight modulation of the window, the encoder hook.
+ *
+ * What is read: of src the w x h block.  Of ref, per stage, the blocks at the visited positions and nothing outside the rectangle
+ * they span: from (mv >> 3) + start (after the clip of :1933-1947) to the last visited column / row, plus w x h.  On the psad path
+ * the last column is start_x + W - 1 with W = end_x - start_x raised to a multiple of 8: up to 6 columns beyond the clipped end_x.  In
+ * MVP mode the blocks at mv[i] >> 3.  The caller's picture border must cover that.  Positions of a level-1 window that the level-0
+ * skip removes lie inside that rectangle and may be staged though they are not scored. */
+#define SVT_HIP_FPEL_MVP 0
+#define SVT_HIP_FPEL_SQ 1
+#define SVT_HIP_FPEL_NSQ 2
+#define SVT_HIP_FPEL_PME 3
+#define SVT_HIP_FPEL_SAD 0 /* DistortionType (definitions.h) */
+#define SVT_HIP_FPEL_VAR 1
+#define SVT_HIP_FPEL_SSD 2
+#define SVT_HIP_FPEL_MAX_MV 6      /* MAX_MD_NSQ_SARCH_MVC_CNT; MVP mode takes up to SVT_HIP_FPEL_MAX_MVP */
+#define SVT_HIP_FPEL_MAX_MVP 4     /* MAX_MVP_CANIDATES */
+#define SVT_HIP_FPEL_TILE 32       /* search positions per axis of one LDS tile of the reference window */
+#define SVT_HIP_FPEL_MAX_EXTENT 4095 /* largest end - start of a window, per axis, before the clip */
+/* SvtHipFpelResult.status */
+#define SVT_HIP_FPEL_OK 0
+#define SVT_HIP_FPEL_BAD_SIZE 1    /* w x h is none of the 22 block sizes */
+#define SVT_HIP_FPEL_BAD_POINTER 2 /* src or ref NULL */
+#define SVT_HIP_FPEL_BAD_MODE 3
+#define SVT_HIP_FPEL_BAD_DIST 4    /* dist_type above SVT_HIP_FPEL_SSD */
+#define SVT_HIP_FPEL_BAD_COST 5    /* mv_cost_type out of range, or MV_COST_ENTROPY without the job's tables (not in MVP mode) */
+#define SVT_HIP_FPEL_BAD_COUNT 6   /* n_mv 0 or above the mode's maximum */
+#define SVT_HIP_FPEL_BAD_STEP 7    /* an enabled level with step 0: the reference's loop would not end */
+#define SVT_HIP_FPEL_BAD_WINDOW 8  /* an enabled level with end - start above SVT_HIP_FPEL_MAX_EXTENT on an axis */
+/* the return value of svt_hip_fpel_search_batch: a SvtHipStatus in 16 bits */
+#define SVT_HIP_FPEL_STATUS(s) ((int16_t)((s) == 0 ? 0 : (0x8000 | ((s) & 0x7fff))))
+
+typedef struct SvtHipFpelLevel {  /* one md_full_pel_search call: the window before the clip, in full-pel offsets from the centre */
+    int16_t start_x, end_x, start_y, end_y;
+    uint8_t enabled;              /* SQ only; elsewhere ignored */
+    uint8_t step;                 /* SQ: sprs_levN_step; elsewhere ignored (NSQ 4, 2, 1; PME 1) */
+    uint8_t pad_[2];
+} SvtHipFpelLevel;
+
+typedef struct SvtHipFpelDesc {
+    const uint8_t *src, *ref;     /* the block's co-located first sample in the source and in the reference picture; any alignment */
+    uint32_t src_stride, ref_stride;
+    uint16_t w, h;                /* one of the 22 sizes of init_fn_ptr (av1me.c:31-170) */
+    uint16_t blk_org_x, blk_org_y; /* ctx->blk_org_x / _y */
+    uint16_t ref_org_x, ref_org_y, ref_max_width, ref_max_height; /* ref_pic->org_x, org_y, max_width, max_height: the clip */
+    SvtHipMv ref_mv;              /* ctx->ref_mv, the vector the cost is taken against */
+    int32_t  error_per_bit;       /* AOMMAX(rdmult >> RD_EPB_SHIFT, 1), rdmult as md_full_pel_search picks it for dist_type */
+    uint32_t gate_th;             /* SQ: md_sq_me_ctrls.pame_distortion_th * bwidth * bheight */
+    SvtHipMv mv[SVT_HIP_FPEL_MAX_MV]; /* MVP: mvp_array[0 .. n_mv); SQ: mv[0] = the ME vector; NSQ: the MVCs as :2079-2140 built them,
+                                   * not yet rounded; PME: mv[0] = the best MVP */
+    SvtHipFpelLevel level[3];     /* SQ: sparse levels 0 .. 2 (svt_hip_fpel_sq_windows); PME: level[0] = the window */
+    uint8_t  mode;                /* SVT_HIP_FPEL_MVP .. _PME */
+    uint8_t  dist_type;           /* SVT_HIP_FPEL_SAD .. _SSD; MVP mode always takes the variance */
+    uint8_t  enable_psad;         /* the mode's controls' enable_psad */
+    uint8_t  mv_cost_type;        /* MV_COST_TYPE, see SvtHipMvCostParam */
+    uint8_t  n_mv;                /* MVP: 1 .. 4; NSQ: 1 .. 6; SQ, PME: ignored */
+    uint8_t  gate_enabled;        /* SQ: blk_geom->sq_size <= 64 */
+    uint8_t  search_area_multiplier; /* SQ: what check_temporal_mv_size / check_spatial_mv_size give; used only if the gate opens */
+    uint8_t  nsq_search_width, nsq_search_height; /* NSQ: md_nsq_me_ctrls.full_pel_search_width / _height */
+    uint8_t  pad_[7];
+} SvtHipFpelDesc;
+
+typedef struct SvtHipFpelResult {
+    SvtHipMv best_mv;   /* MVP: mv[mvp_idx]; SQ, NSQ: *me_mv_x / _y as the function leaves them; PME: best_search_mv */
+    uint32_t best_cost; /* MVP: best_fp_mvp_dist; SQ, NSQ: best_search_cost ((uint32_t)~0 if no search ran); PME: pme_mv_cost */
+    uint32_t aux_cost;  /* SQ: pa_me_cost; NSQ: search_center_cost; otherwise 0 */
+    uint8_t  expanded;  /* SQ: the gate opened with a non-zero multiplier and the sparse levels ran */
+    uint8_t  mvp_idx;   /* MVP: best_fp_mvp_idx */
+    uint8_t  status;    /* SVT_HIP_FPEL_*; non-zero: every other field is 0 */
+    uint8_t  pad_;
+} SvtHipFpelResult;
+/* d_result[i] belongs to d_desc[i]; job: mvjcost and the two centred mvcost tables, read by descriptors with MV_COST_ENTROPY.  The stages
+ * of a descriptor run back to back in one workgroup; the descriptors run in parallel.  Returns SVT_HIP_FPEL_STATUS(status):
+ * SVT_HIP_ERR_BAD_PARAMETER for a NULL job, d_desc or d_result; n == 0 is 0 and launches nothing.  Asynchronous on `stream`.
+ * best_mv / best_cost / mvp_idx feed SvtHipSubpelDesc.start_mv / best_mvp / best_mvp_dist. */
+SVT_HIP_API int16_t svt_hip_fpel_search_batch(const SvtHipSubpelJob *job, const SvtHipFpelDesc *d_desc, SvtHipFpelResult *d_result,
+                                              uint32_t n, void *stream);
+
+typedef struct SvtHipFpelSqCtrls {  /* the fields of MdSqMotionSearchCtrls the windows are derived from; [2]: only enabled, step, w, h */
+    uint16_t w[3], h[3], max_w[3], max_h[3]; /* sprs_levN_w, _h, max_sprs_levN_w, _h */
+    int16_t  multiplier[3];                  /* sprs_levN_multiplier */
+    uint8_t  enabled[3], step[3];
+} SvtHipFpelSqCtrls;
+/* product_coding_loop.c:2379-2393, 2423-2446, 2480-2487: the three windows of md_sq_motion_search before the clip, from the controls,
+ * search_area_multiplier and dist = svt_aom_get_scaled_picture_distance(|picture_number - ref poc|): the uint16_t products, the / 100,
+ * the rounding to multiples of the step and the % 4 == 0 -> -+ 2 widening of level 1.  A level with step 0 gets the window
+ * (0, 0, 0, 0) and keeps its enabled flag and its step (enabled, the descriptor is SVT_HIP_FPEL_BAD_STEP).  Host only, no device; with a
+ * NULL pointer nothing is written. */
+SVT_HIP_API void svt_hip_fpel_sq_windows(const SvtHipFpelSqCtrls *ctrls, uint8_t search_area_multiplier, uint16_t dist, SvtHipFpelLevel level[3]);
 
 /* ---- OBMC motion refinement (Tier B) ------------------------------------------------------------------------------------------
  * What svt_aom_precompute_obmc_data and svt_aom_obmc_motion_refinement compute between the neighbour predictions

@@ -38,23 +38,9 @@ __device__ int subpel_status(const SvtHipSubpelDesc &d, const SvtHipSubpelJob &j
     return SVT_HIP_SUBPEL_OK;
 }
 
-// svt_mv_err_cost (mcomp.c:44-68)
-__device__ int mv_err_cost(SvtHipMv mv, const SvtHipSubpelDesc &d, const SvtHipSubpelJob &job) {
-    const int16_t dr = (int16_t)(mv.row - d.ref_mv.row), dc = (int16_t)(mv.col - d.ref_mv.col);  // MV fields: int16
-    const int     l1 = (int16_t)abs((int)dr) + (int16_t)abs((int)dc);
-    switch (d.mv_cost_type) {
-    case 0: {  // MV_COST_ENTROPY: svt_mv_cost (mcomp.h:136-139)
-        const int joint = dr == 0 ? (dc == 0 ? 0 : 1) : (dc == 0 ? 2 : 3);
-        const int rate = job.mvjcost[joint] + job.mvcost[0][min(max((int)dr, MV_LOW), MV_UPP)] +
-            job.mvcost[1][min(max((int)dc, MV_LOW), MV_UPP)];
-        return (int)(((int64_t)rate * d.error_per_bit + (1 << 13)) >> 14);  // RDDIV_BITS + AV1_PROB_COST_SHIFT - RD_EPB_SHIFT + 4
-    }
-    case 1: return (2 * l1) >> 3;  // SSE_LAMBDA_LOWRES
-    case 2: return 0;              // SSE_LAMBDA_MIDRES is 0
-    case 3: return l1 >> 3;        // SSE_LAMBDA_HDRES
-    case 4: return (int)(((int64_t)(l1 << 8) * d.error_per_bit + (1 << 13)) >> 14);  // MV_COST_OPT
-    default: return 0;             // MV_COST_NONE
-    }
+// svt_mv_err_cost_ (mcomp.c:70-78): mv_cost_device.hpp, shared with inter_fpel.hip
+__device__ __forceinline__ int mv_err_cost(SvtHipMv mv, const SvtHipSubpelDesc &d, const SvtHipSubpelJob &job) {
+    return subpel::mv_err_cost(mv, d.ref_mv, d.mv_cost_type, d.error_per_bit, job);
 }
 
 struct Block : Window {  // what a candidate's error is computed from: the window from 4 above and 4 left of start_mv, and the source

@@ -4,11 +4,11 @@
 #pragma once
 #include "../../include/svt_hip_inter.h"
 #include "blend_device.hpp"
+#include "mv_cost_device.hpp"
 
 namespace svthip {
 namespace subpel {
 
-constexpr int MV_LOW = -(1 << 14), MV_UPP = 1 << 14;  // cabac_context_model.h:523-525
 constexpr int MAX_FULL_PEL_VAL = (1 << 10) - 1;      // av1me.h:24-27
 constexpr int SMALL_AREA = 256;                      // the single-wave kernels take blocks up to this many samples
 

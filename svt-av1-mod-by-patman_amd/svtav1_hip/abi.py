@@ -599,6 +599,47 @@ SUBPEL_DESC_DTYPE = record_dtype(SubpelDesc)       # numpy views of arrays of th
 SUBPEL_RESULT_DTYPE = record_dtype(SubpelResult)
 
 
+FPEL_MVP, FPEL_SQ, FPEL_NSQ, FPEL_PME = range(4)                                  # SVT_HIP_FPEL_* (include/svt_hip_inter.h)
+FPEL_SAD, FPEL_VAR, FPEL_SSD = range(3)
+FPEL_MAX_MV, FPEL_MAX_MVP, FPEL_TILE, FPEL_MAX_EXTENT = 6, 4, 32, 4095
+(FPEL_OK, FPEL_BAD_SIZE, FPEL_BAD_POINTER, FPEL_BAD_MODE, FPEL_BAD_DIST, FPEL_BAD_COST, FPEL_BAD_COUNT, FPEL_BAD_STEP,
+ FPEL_BAD_WINDOW) = range(9)
+
+
+def fpel_status(status):
+    """SVT_HIP_FPEL_STATUS: a SvtHipStatus as the int16_t that svt_hip_fpel_search_batch returns"""
+    return 0 if status == 0 else ((0x8000 | (status & 0x7FFF)) ^ 0x8000) - 0x8000
+
+
+class FpelLevel(C.Structure):            # SvtHipFpelLevel
+    _fields_ = [("start_x", C.c_int16), ("end_x", C.c_int16), ("start_y", C.c_int16), ("end_y", C.c_int16), ("enabled", C.c_uint8),
+                ("step", C.c_uint8), ("pad_", C.c_uint8 * 2)]
+
+
+class FpelDesc(C.Structure):             # SvtHipFpelDesc
+    _fields_ = [("src", C.c_void_p), ("ref", C.c_void_p), ("src_stride", C.c_uint32), ("ref_stride", C.c_uint32), ("w", C.c_uint16),
+                ("h", C.c_uint16), ("blk_org_x", C.c_uint16), ("blk_org_y", C.c_uint16), ("ref_org_x", C.c_uint16), ("ref_org_y", C.c_uint16),
+                ("ref_max_width", C.c_uint16), ("ref_max_height", C.c_uint16), ("ref_mv", Mv), ("error_per_bit", C.c_int32),
+                ("gate_th", C.c_uint32), ("mv", Mv * FPEL_MAX_MV), ("level", FpelLevel * 3), ("mode", C.c_uint8), ("dist_type", C.c_uint8),
+                ("enable_psad", C.c_uint8), ("mv_cost_type", C.c_uint8), ("n_mv", C.c_uint8), ("gate_enabled", C.c_uint8),
+                ("search_area_multiplier", C.c_uint8), ("nsq_search_width", C.c_uint8), ("nsq_search_height", C.c_uint8),
+                ("pad_", C.c_uint8 * 7)]
+
+
+class FpelResult(C.Structure):           # SvtHipFpelResult
+    _fields_ = [("best_mv", Mv), ("best_cost", C.c_uint32), ("aux_cost", C.c_uint32), ("expanded", C.c_uint8), ("mvp_idx", C.c_uint8),
+                ("status", C.c_uint8), ("pad_", C.c_uint8)]
+
+
+class FpelSqCtrls(C.Structure):          # SvtHipFpelSqCtrls
+    _fields_ = [("w", C.c_uint16 * 3), ("h", C.c_uint16 * 3), ("max_w", C.c_uint16 * 3), ("max_h", C.c_uint16 * 3),
+                ("multiplier", C.c_int16 * 3), ("enabled", C.c_uint8 * 3), ("step", C.c_uint8 * 3)]
+
+
+FPEL_DESC_DTYPE = record_dtype(FpelDesc)
+FPEL_RESULT_DTYPE = record_dtype(FpelResult)
+
+
 OBMC_MAX_NEIGHBOURS = 4                                                          # SVT_HIP_OBMC_* (include/svt_hip_inter.h)
 (OBMC_OK, OBMC_BAD_SIZE, OBMC_BAD_POINTER, OBMC_BAD_SEGMENT, OBMC_BAD_RANGE, OBMC_BAD_START_MV, OBMC_BAD_LIMITS, OBMC_BAD_FILTER,
  OBMC_BAD_COST) = range(9)

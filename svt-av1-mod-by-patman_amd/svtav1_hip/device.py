@@ -227,6 +227,17 @@ def subpel_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
     return d_out.read(abi.SUBPEL_RESULT_DTYPE)
 
 
+def fpel_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
+    """svt_hip_fpel_search_batch over a record array of abi.FPEL_DESC_DTYPE (or a list of abi.FpelDesc) under the abi.SubpelJob `job`
+    (one call).  Returns (results as a record array of abi.FPEL_RESULT_DTYPE, the `guard` bytes before and after them: still `fill` if
+    untouched)."""
+    n = len(descs)
+    d_desc = upload_descriptors(lib, descs, stream)
+    d_out = Guarded(lib, C.sizeof(abi.FpelResult) * n, guard, fill, stream)
+    _call(lib, "svt_hip_fpel_search_batch", C.byref(job), d_desc.ptr, d_out.ptr, n, stream=stream)
+    return d_out.read(abi.FPEL_RESULT_DTYPE)
+
+
 def obmc_target_batch(lib, descs, stream=None, guard=64, fill=0xA5):
     """svt_hip_obmc_target_batch over a record array of abi.OBMC_TARGET_DESC_DTYPE (or a list of abi.ObmcTargetDesc), one call.  Returns
     (the status words, the `guard` bytes before and after them: still `fill` if untouched); wsrc and mask land where the descriptors say."""
