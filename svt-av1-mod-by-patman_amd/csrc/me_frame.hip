@@ -42,6 +42,16 @@ constexpr uint32_t fp_pitch_c(uint32_t tw) { return (((tw + 3) >> 2) + 17) | 1u;
 constexpr uint32_t FP_TILE_W = ME_WIN_DW / fp_pitch_c(64) >= 63 + 8 ? 64 : 32;
 static_assert(ME_WIN_DW / fp_pitch_c(FP_TILE_W) >= 63 + 8, "full-pel window buffer too small for one tile");
 
+// Direct full-pel search (fullpel_direct_all): all references of a b64 in one pass, windows read from the reference planes.
+#ifndef SVT_HIP_ME_FP_DIRECT
+#define SVT_HIP_ME_FP_DIRECT 1  // 0: diagnostic build, every b64 takes the staged loop over the references (fullpel_ref)
+#endif
+// Widest / tallest final window (positions) the direct search takes, and the most groups of 16 work items (eight positions of
+// one window row) all reference slots together can have: one thread sets one group up.  The windows of preset 8 are 1 x 1,
+// 8 x 3, 16 x 4 or 16 x 5 above 1080p (five references: at most 50 groups) and up to 24 x 9 at the smallest resolutions.
+constexpr uint32_t FPD_MAX_W = 24, FPD_MAX_ROWS = 9, FPD_MAX_GROUPS = NL * NR * ((FPD_MAX_W + 7) / 8) * FPD_MAX_ROWS;
+static_assert(FPD_MAX_GROUPS <= 256, "one thread per group of work items sets the direct search up");
+
 struct PreHme {
     uint64_t sad;
     uint16_t sa_w, sa_h;
@@ -84,7 +94,13 @@ struct MeLds {
     union {
         alignas(16) uint32_t win[ME_HME_WIN_DW];
         struct {
-            alignas(16) uint32_t fp_win_[ME_WIN_DW];
+            union {
+                alignas(16) uint32_t fp_win_[ME_WIN_DW];
+                struct {  // the direct full-pel search stages no window (fullpel_direct_all)
+                    uint64_t fpd_key[NL * NR][85];               // the 85 minima of every reference slot
+                    uint2    fpd_grp[FPD_MAX_GROUPS];      // one record per group of 16 work items
+                };
+            };
             alignas(16) uint32_t src_full[64 * 16];
             uint64_t bestkey[85];
             uint32_t me_dist[85];
@@ -94,6 +110,8 @@ struct MeLds {
     alignas(16) uint32_t src_s[16 * 4];
 };
 static_assert(sizeof(MeLds::win) >= (ME_WIN_DW + 64 * 16) * 4 + 85 * 12, "full-pel view must fit the HME window buffer");
+static_assert(sizeof(MeLds::fpd_key) + sizeof(MeLds::fpd_grp) <= sizeof(MeLds::fp_win_), "direct full-pel view must fit the window buffer");
+static_assert(SVT_HIP_ME_MAX_REF == NR && SVT_HIP_ME_MAX_LIST == NL, "reference slot = list * NR + index");
 
 typedef __attribute__((address_space(1))) uint32_t g_u32;  // the result arrays are global memory (the pointers come out of LDS)
 #define MINV(a, b) ((a) < (b) ? (a) : (b))
@@ -260,8 +278,9 @@ template <int CTRL> __device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
     return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
 }
 
+// (inlined at its three call sites: an out-of-line copy saves and restores registers through scratch memory around every call)
 template <class LDS>
-__device__ void fp_search(LDS &L, uint32_t pitch, uint32_t x0, uint32_t y0, uint32_t cw, uint32_t ch, uint32_t order0,
+__device__ __forceinline__ void fp_search(LDS &L, uint32_t pitch, uint32_t x0, uint32_t y0, uint32_t cw, uint32_t ch, uint32_t order0,
                           uint32_t order_pitch, bool sub) {
     const uint32_t tid = threadIdx.x;
     const uint32_t nq = (cw + 3) >> 2, nitems = nq * ch * 16, inv_nq = make_inv_small(nq);
@@ -1327,6 +1346,207 @@ __device__ void fullpel_ref(LDS &L, const Ctx &c, int li, int ri, bool store, bo
     __syncthreads();
 }
 
+#if SVT_HIP_ME_FP_DIRECT
+// ---- direct full-pel search: every reference of the b64 in one pass, windows read from the reference planes ----
+// With me_early_exit_th != 0 fullpel_prepare_all has fixed every reference's centre, probe SADs and final window before any
+// reference is searched, so the searches do not depend on one another; and the windows of the fast presets are small (preset 8:
+// 1 x 1, 8 x 3, 16 x 4 or 16 x 5 positions), so that a staged window is read about three times and paid for with a copy, three to
+// four barriers and a partly filled round of work items PER REFERENCE.  Here the work items of all references form one range,
+// each lane reads the 24 bytes a block row of its eight positions needs from the plane, and the 85 minima of every reference
+// slot live in LDS side by side: three barriers per b64.  An item is (eight positions of one window row, one 16x16 block of the
+// source): the search is limited by the vector memory pipeline, and eight positions per lane read 24 bytes per block row where
+// two items of four positions read 40 (measured on the 4K workload: 1.57 against 1.61 ms per launch, the staged loop 1.68).
+//
+// Reads: the item of positions 8o .. 8o + 7 of a window row y and 16x16 block (zx, zy) reads bytes
+// [ox + 8o + 16zx, ox + 8o + 16zx + 24) of the window's rows y + 16zy + r, r < 16 (every other r with sub-sampled SAD).  That is
+// at most 8 * ceil(sw / 8) + 64 bytes from the window's first column — fp_stage fetches fp_pitch(sw) >= ceil(sw / 4) + 17 dwords
+// from there, which is as much or more for every sw — and no more than 8 bytes past the last byte position sw - 1 compares (the
+// contract of include/svt_hip_me.h allows 15); the rows are rows y + 16zy + r <= sh + 62 of the sh + 63 that fp_stage fetches.
+// So no byte is read that the staged search would not read for the same window.
+
+// `nrows` block rows of 16 samples against the eight positions at gp, one window row (24 bytes) held at a time (as direct_walk32:
+// a second row in flight costs registers this kernel does not have, and was measured no faster); a[0] / a[1]: the packed SADs of
+// the left / right 8 columns at positions 0..3, a[2] / a[3]: at positions 4..7
+__device__ __forceinline__ void fpd_rows(const uint8_t *gp, uint32_t gstep, const uint32_t *__restrict__ s, uint32_t sstep, uint32_t nrows,
+                                         uint64_t a[4]) {
+#pragma unroll 1
+    for (uint32_t r = 0; r < nrows; r++) {
+        const u128v v  = load_u128_any(gp);
+        const u64v  w  = load_u64_any(gp + 16);
+        const uint4 sv = *(const uint4 *)s;
+        a[0] = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.x, v.y), sv.x, a[0]);
+        a[0] = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.y, v.z), sv.y, a[0]);
+        a[1] = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.z, v.w), sv.z, a[1]);
+        a[1] = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.w, w.x), sv.w, a[1]);
+        a[2] = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.y, v.z), sv.x, a[2]);
+        a[2] = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.z, v.w), sv.y, a[2]);
+        a[3] = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.w, w.x), sv.z, a[3]);
+        a[3] = __builtin_amdgcn_qsad_pk_u16_u8(pair64(w.x, w.y), sv.w, a[3]);
+        gp += gstep, s += sstep;
+    }
+}
+
+// The full-pel search of all references of the b64 (the loop of fullpel_ref over them, prepared mode), if every final window is
+// at most FPD_MAX_W x FPD_MAX_ROWS positions (which makes at most FPD_MAX_GROUPS groups of items); otherwise nothing is done and
+// false returned, at the cost of three LDS reads per lane.  The answer is uniform over the workgroup (LDS values behind
+// fullpel_prepare_all's last barrier).  All threads; ends with a barrier when it returns true.
+template <class LDS>
+__device__ __forceinline__ bool fullpel_direct_all(LDS &L, const Ctx &c) {
+    ME_CTX_LOCALS(c);
+    const uint32_t lane = tid & 63u, wv = tid >> 6;
+    // every wave looks at all reference slots (lane = slot): groups of 16 work items (eight positions of one window row) per slot
+    uint32_t ng = 0;
+    {
+        const Slot q   = slot_of(lane, p, nlists);
+        bool       bad = false;
+        if (q.searched && S.sr[q.li][q.ri].do_ref) {
+            const int sw = S.fp_sw[lane], sh_ = S.fp_sh[lane];
+            bad = sw > (int)FPD_MAX_W || sh_ > (int)FPD_MAX_ROWS;
+            if (sw > 0 && sh_ > 0)
+                ng = (((uint32_t)sw + 7) >> 3) * (uint32_t)sh_;
+        }
+        if (__ballot(bad))
+            return false;
+    }
+    // first group of each slot: running sum over lanes 0..7 (row_shr 1, 2, 4; lanes without a left neighbour add 0)
+    uint32_t incl = ng;
+    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xf, 0xf, true);
+    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xf, 0xf, true);
+    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xf, 0xf, true);
+    const uint32_t ngroups = (uint32_t)__builtin_amdgcn_readlane((int)incl, NL * NR - 1);
+    // thread = group: where its 16 items read (byte offset of row y, position 8o of the window in the plane), which slot's minima
+    // they update, how many of the eight positions lie inside the window and the raster order of the first
+    uint32_t end[NL * NR - 1];  // (scalars)
+#pragma unroll
+    for (int k = 0; k < NL * NR - 1; k++) end[k] = (uint32_t)__builtin_amdgcn_readlane((int)incl, k);
+    if (tid < ngroups) {
+        uint32_t g = 0, base = 0;
+#pragma unroll
+        for (int k = 0; k < NL * NR - 1; k++)
+            if (tid >= end[k])
+                g = (uint32_t)k + 1, base = end[k];
+        const SvtHipPlane8 &rp  = job.ref[g / NR][g % NR].full;
+        const uint32_t      gsw = (uint32_t)S.fp_sw[g], no = (gsw + 7) >> 3, loc = tid - base;
+        const uint32_t      y = fast_div(loc, make_inv_small(no)), o = loc - y * no;
+        const int           px = (int)rp.org_x + (int)(int16_t)org_x + S.fp_ox[g] + (int)(8 * o);
+        const int           py = (int)rp.org_y + (int)(int16_t)org_y + S.fp_oy[g] + (int)y;
+        const uint32_t      nv = gsw - 8 * o < 8 ? gsw - 8 * o : 8;
+        L.fpd_grp[tid]         = make_uint2((uint32_t)(py * (int)rp.stride + px), g | (nv << 3) | ((1 + y * gsw + 8 * o) << 8));
+    }
+    // the 85 minima of every searched slot start from the centre probe's SADs (position 0 of the scan order) or empty, as in
+    // fullpel_ref: wave = slot
+    for (uint32_t g = wv; g < (uint32_t)(NL * NR); g += blockDim.x >> 6) {
+        const uint32_t li = g / NR, ri = g % NR;
+        if (!((int)li < nlists && ri < p.num_of_ref_pic_to_search[li] && S.sr[li][ri].do_ref))  // uniform over the wave
+            continue;
+        uint64_t *const key = L.fpd_key[g];
+        if (S.fp_centre[g]) {
+            const uint32_t sh1 = me_sub ? 1u : 0u;
+            const uint32_t v   = ((const uint16_t *)L.src_q)[g * 64 + lane];
+            uint32_t       s16 = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
+            s16                = dpp_add<0x4E>(s16);  // quad_perm [2,3,0,1]: the 16x16 of this lane's quad
+            uint32_t s32       = dpp_add<0x124>(s16); // row_ror:4
+            s32                = dpp_add<0x128>(s32); // row_ror:8: the 32x32 of this lane's row of 16
+            const uint32_t s64 = wave_sum_all(v);
+            key[21 + lane] = (uint64_t)(v << sh1) << 32;
+            if ((lane & 3) == 0)
+                key[5 + (lane >> 2)] = (uint64_t)(s16 << sh1) << 32;
+            if ((lane & 15) == 0)
+                key[1 + (lane >> 4)] = (uint64_t)(s32 << sh1) << 32;
+            if (lane == 0)
+                key[0] = (uint64_t)(s64 << sh1) << 32;
+        } else {
+            for (uint32_t pu = lane; pu < 85; pu += 64) key[pu] = ((uint64_t)MAX_SAD_VALUE_ << 32) | 0xffffffffu;
+        }
+    }
+    __syncthreads();
+    // the search: item = (group, 16x16 block of the source in z-order), the arithmetic of fp_search
+    {
+        const uint32_t zo = tid & 15;
+        const uint32_t zy = 2 * (zo >> 3) + ((zo >> 1) & 1), zx = 2 * ((zo >> 2) & 1) + (zo & 1);
+        const uint32_t *s = &L.src_full[(16 * zy) * 16 + 4 * zx];
+        const uint32_t sh1 = me_sub ? 1u : 0u;  // sub-sampled rows: every other row, SAD x 2 (motion_estimation.c:520-530)
+        for (uint32_t item = tid; item < 16 * ngroups; item += blockDim.x) {
+            const uint2         rec = L.fpd_grp[item >> 4];
+            const uint32_t      g = rec.y & 7u, nv = (rec.y >> 3) & 15u, ord_row = rec.y >> 8;
+            const SvtHipPlane8 &rp = job.ref[g / NR][g % NR].full;
+            const uint32_t      stride = rp.stride;
+            const uint8_t      *w = rp.buf + rec.x + sad_mul_u24(16 * zy, stride) + 16 * zx;
+            uint64_t            at[4] = {0, 0, 0, 0}, ab[4] = {0, 0, 0, 0};  // rows 0..7 / 8..15 of the 16x16 block
+            fpd_rows(w, stride << sh1, s, 16u << sh1, 8u >> sh1, at);
+            fpd_rows(w + 8 * stride, stride << sh1, s + 8 * 16, 16u << sh1, 8u >> sh1, ab);
+            // minima over this lane's positions as packed (sad << 3 | position) keys, as in fp_search
+            uint32_t k8[4] = {~0u, ~0u, ~0u, ~0u}, k16 = ~0u, k32 = ~0u, k64 = ~0u;
+#pragma unroll
+            for (uint32_t pp = 0; pp < 8; pp++) {
+                const uint32_t qd = 2 * (pp >> 2), lo_hi_shift = 16 * (pp & 1);
+                const uint32_t c0 = (((pp & 2) ? (uint32_t)(at[qd] >> 32) : (uint32_t)at[qd]) >> lo_hi_shift) & 0xffff;
+                const uint32_t c1 = (((pp & 2) ? (uint32_t)(at[qd + 1] >> 32) : (uint32_t)at[qd + 1]) >> lo_hi_shift) & 0xffff;
+                const uint32_t c2 = (((pp & 2) ? (uint32_t)(ab[qd] >> 32) : (uint32_t)ab[qd]) >> lo_hi_shift) & 0xffff;
+                const uint32_t c3 = (((pp & 2) ? (uint32_t)(ab[qd + 1] >> 32) : (uint32_t)ab[qd + 1]) >> lo_hi_shift) & 0xffff;
+                const uint32_t s16 = c0 + c1 + c2 + c3;
+                uint32_t       s32 = dpp_add<0xB1>(s16);   // quad_perm [1,0,3,2]
+                s32                = dpp_add<0x4E>(s32);   // quad_perm [2,3,0,1]
+                uint32_t s64       = dpp_add<0x124>(s32);  // row_ror:4
+                s64                = dpp_add<0x128>(s64);  // row_ror:8
+                // a position outside the window gets bits above every SAD (a 64x64 SAD of 16 rows is below 2^20) instead of a branch
+                // around its seven keys: the first position is always inside, so such a key never wins, and the positions' chains
+                // of DPP sums stay in one basic block, where they cover each other's wait states
+                const uint32_t tag = pp < nv ? pp : (0xff800000u | pp);
+                k8[0] = min(k8[0], (c0 << 3) | tag), k8[1] = min(k8[1], (c1 << 3) | tag);
+                k8[2] = min(k8[2], (c2 << 3) | tag), k8[3] = min(k8[3], (c3 << 3) | tag);
+                k16 = min(k16, (s16 << 3) | tag), k32 = min(k32, (s32 << 3) | tag), k64 = min(k64, (s64 << 3) | tag);
+            }
+            uint64_t *const key = L.fpd_key[g];
+#define FP_KEY(k) (((unsigned long long)(((k) >> 3) << sh1) << 32) | (ord_row + ((k) & 7u)))
+#pragma unroll
+            for (uint32_t cq = 0; cq < 4; cq++) atomicMin((unsigned long long *)&key[21 + 4 * zo + cq], FP_KEY(k8[cq]));
+            atomicMin((unsigned long long *)&key[5 + zo], FP_KEY(k16));
+            if ((zo & 3) == 0)
+                atomicMin((unsigned long long *)&key[1 + (zo >> 2)], FP_KEY(k32));
+            if (zo == 0)
+                atomicMin((unsigned long long *)&key[0], FP_KEY(k64));
+#undef FP_KEY
+        }
+    }
+    __syncthreads();
+    // keys -> p_sb_best_sad / p_sb_best_mv, the sum of the 64 8x8 SADs and first_ref_sad64, as at the end of fullpel_ref: wave = slot
+    for (uint32_t g = wv; g < (uint32_t)(NL * NR); g += blockDim.x >> 6) {
+        const uint32_t li = g / NR, ri = g % NR;
+        if (!((int)li < nlists && ri < p.num_of_ref_pic_to_search[li] && S.sr[li][ri].do_ref))  // uniform over the wave
+            continue;
+        const int      ox = S.fp_ox[g], oy = S.fp_oy[g];
+        const uint32_t sw = (uint32_t)(S.fp_sw[g] > 0 ? S.fp_sw[g] : 0);
+        uint32_t       part = 0;
+        for (uint32_t pu = lane; pu < 85; pu += 64) {
+            const uint64_t key    = L.fpd_key[g][pu];
+            const uint32_t ord    = (uint32_t)key;
+            const uint32_t my_sad = (uint32_t)(key >> 32);
+            if (g == 0 && pu == 0)
+                S.first_ref_sad64 = my_sad;
+            if (pu >= 21)
+                part += my_sad;
+            gs[g * 85 + pu] = my_sad;
+            if (ord != 0xffffffffu) {
+                int16_t mx, my;
+                if (ord == 0) {
+                    mx = S.fp_xc[g], my = S.fp_yc[g];
+                } else {
+                    const uint32_t pos = ord - 1, row = fast_div(pos, S.fp_inv[g]);
+                    mx = (int16_t)((int)(pos - row * sw) + ox), my = (int16_t)((int)row + oy);
+                }
+                gm[g * 85 + pu] = ((uint32_t)(uint16_t)my << 16) | (uint16_t)mx;
+            }
+        }
+        part = wave_sum(part);
+        if (lane == 0 && part)
+            S.me_sad_sum[li][ri] += (uint64_t)part;
+    }
+    __syncthreads();
+    return true;
+}
+#endif  // SVT_HIP_ME_FP_DIRECT
+
 // me_prune_ref (motion_estimation.c:1592-1635); first wave, lane = reference slot
 template <class LDS>
 __device__ void me_prune_lane0(LDS &L, const Ctx &c) {
@@ -1531,10 +1751,16 @@ __global__ __launch_bounds__(WG_THREADS, SVT_HIP_ME_WGS) void me_b64_kernel(cons
         const bool prepared = p.me_early_exit_th != 0;  // uniform
         if (prepared)
             fullpel_prepare_all(L, c);
-        for (int li = 0; li < nlists; ++li)
-            for (int ri = 0; ri < p.num_of_ref_pic_to_search[li]; ++ri)
-                if (S.sr[li][ri].do_ref)  // uniform
-                    fullpel_ref(L, c, li, ri, true, prepared);
+        bool direct = false;  // uniform
+#if SVT_HIP_ME_FP_DIRECT
+        if (prepared)  // small windows (the fast presets): all references in one pass, no staged window
+            direct = fullpel_direct_all(L, c);
+#endif
+        if (!direct)
+            for (int li = 0; li < nlists; ++li)
+                for (int ri = 0; ri < p.num_of_ref_pic_to_search[li]; ++ri)
+                    if (S.sr[li][ri].do_ref)  // uniform
+                        fullpel_ref(L, c, li, ri, true, prepared);
     }
     ME_PHASE(7);
     ME_STOP(7);

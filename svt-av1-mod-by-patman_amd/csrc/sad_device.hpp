@@ -106,6 +106,12 @@ typedef uint32_t __attribute__((ext_vector_type(4))) u128v;
 __device__ __forceinline__ u128v load_u128_any(const uint8_t *g) {
     return *(const __attribute__((address_space(1))) u128_unaligned *)g;
 }
+// 8 bytes from any byte address: one global_load_dwordx2
+typedef uint32_t __attribute__((ext_vector_type(2), aligned(1))) u64_unaligned;
+typedef uint32_t __attribute__((ext_vector_type(2))) u64v;
+__device__ __forceinline__ u64v load_u64_any(const uint8_t *g) {
+    return *(const __attribute__((address_space(1))) u64_unaligned *)g;
+}
 
 // products of two values below 2^24 with a result below 2^32: one full-rate v_mul_u32_u24 instead of the quarter-rate v_mul_lo_u32
 // (declared as the LLVM intrinsic: `__umul24` is expanded to shifts and a generic multiply that the selector does not always narrow again)
