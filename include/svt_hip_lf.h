@@ -14,6 +14,8 @@
  *                                                                           (Tier B: svt_hip_wiener_pick_plane)
  *   Source/Lib/Codec/restoration_pick.c:1148-1293, 1380-1431, 1555-1625  search_sgrproj_seg, the finish visitors, rest_finish_search,
  *                                                                           copy_unit_info (Tier B: svt_hip_rest_pick_plane)
+ *   Source/Lib/Codec/deblocking_filter.c:841-991, 1129-1252  try_filter_frame, search_filter_level, svt_av1_pick_filter_level
+ *                                                                           (Tier B: svt_hip_dlf_pick_levels, svt_hip_dlf_apply_picked)
  */
 #ifndef SVT_HIP_LF_H
 #define SVT_HIP_LF_H
@@ -210,6 +212,90 @@ typedef struct SvtHipLfFrame {
  * svt_aom_loop_filter_sb's combine_vert_horz_lf schedule is equivalent to).  delta_lf is not supported —
  * the reference never enables it (resource_coordination_process.c:410-412). */
 SVT_HIP_API int32_t svt_hip_loop_filter_frame(const SvtHipLfFrame *frame, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * The deblocking levels of a picture, searched on the device: svt_av1_pick_filter_level (deblocking_filter.c:1129) for the
+ * searched methods (LPF_PICK_FROM_FULL_IMAGE; the reference ignores partial_frame) = search_filter_level (:886-991) once per
+ * plane, every trial of it try_filter_frame (:841-881) = svt_av1_loop_filter_frame of that plane at the trial level, the SSE
+ * against the source (picture_sse_calculations, :716-834), and the unfiltered plane put back.
+ *   svt_hip_dlf_pick_levels   the whole search of up to three planes; the levels and the measured errors stay in a device record
+ *   svt_hip_dlf_apply_picked  svt_av1_loop_filter_frame with the levels read from that record
+ * Both only enqueue on `stream` and return the 32 bits of an SvtHipStatus as uint32_t: 0 = SVT_HIP_OK, else (uint32_t)SVT_HIP_ERR_*,
+ * the value EbErrorType has.  Neither synchronises nor reads anything back, and the host never learns a level.
+ *
+ * The chain is fixed: max_rounds times {plan, trial}, then one plan step.  The plan step (one wave; a lane per plane) takes the
+ * sums of the trials before it, advances each plane's loop through every iteration that needs no new error and stops at the
+ * first one that does: its filt_low and filt_high are both known before either is tried (:943-970), so a round carries up to two
+ * trials per plane, six in all; the first round is the trial at filt_mid.  The trial kernel filters one tile of one trial in LDS
+ * (all vertical edges, then all horizontal ones) and adds the tile's squared error to the trial's sum; the filtered samples are
+ * never written to memory.  A plane whose search has ended makes its trials inactive, and the workgroups of an inactive trial
+ * return at once.  Every round that runs measures at least one new level, so 63 rounds always finish; a plane that runs out of
+ * rounds gets its `finished` bit clear and the caller falls back (to the host loop, or to the record's best level so far).
+ *
+ * Not covered: mode_ref_delta_enabled (the reference never sets it, resource_coordination_process.c:367), delta_lf, several
+ * tiles, superres / resize, formats other than 4:2:0, the LPF_PICK_FROM_Q family (scalar host work).
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define SVT_HIP_DLF_MAX_LEVEL 63            /* MAX_LOOP_FILTER */
+/* Recommended max_rounds: the largest `rounds` of tests/golden/dlf_pick.npz (12), plus 4.  A search CAN need more (a replay of the loop
+ * over synthetic error tables needed up to 20): after every call check that `finished` has the bit of every searched plane, and fall
+ * back where it has not, or ask for up to 63 rounds, which always finish. */
+#define SVT_HIP_DLF_PICK_DEFAULT_ROUNDS 16
+
+typedef struct SvtHipDlfPickParams { /* read on the host */
+    SvtHipLfFrame frame;         /* plane[]: the UNFILTERED reconstruction (pick: read only; apply: filtered in place); mi, geometry,
+                                  * sharpness_level, bit_depth, is_16bit, plane_start / plane_end as in svt_hip_loop_filter_frame;
+                                  * lvl[] is ignored; filter_level[2] / _u / _v: the levels of planes that are not searched */
+    const void   *src[3];        /* device: top-left sample of the source picture's planes (sample type of the reconstruction) */
+    uint32_t      src_stride[3]; /* in samples */
+    uint32_t      sse_width[3], sse_height[3]; /* measured area per plane, not empty, at most the mi-aligned plane ((mi_cols * 4) >> ss): the
+                                  * reference measures aligned_width x aligned_height in the 8-bit pipeline and input_pic->width x
+                                  * height ((w + ss) >> ss for chroma) in the 16-bit one */
+    uint32_t      plane_mask;    /* bit p: plane p is searched (the reference skips chroma under dlf_avg_uv && temporal layer > 0) */
+    uint8_t       start_level[3];/* where each plane's search starts (`lvl`, :901-912), 0..63.  Luma is searched with dir == 2, so
+                                  * without dlf_avg the reference starts it from last_frame_filter_level[2], the previous U level */
+    uint8_t       only_4x4;      /* tx_mode == ONLY_4X4: the bias is not halved (:940) */
+    int32_t       early_exit_convergence; /* dlf_ctrls.early_exit_convergence; 0 = never */
+    int32_t       max_rounds;    /* 1..63 rounds of {plan, trial} to enqueue; SVT_HIP_DLF_PICK_DEFAULT_ROUNDS */
+    uint8_t       segmentation_enabled;
+    uint8_t       seg_lf_enabled[8][4]; /* [segment][SEG_LVL_ALT_LF_Y_V, _Y_H, _U, _V]: a segment's level is clamp(level + data, 0, 63) */
+    uint8_t       pad_[3];
+    int16_t       seg_lf_data[8][4];    /* where the feature is active (deblocking_common.c:107-115) */
+} SvtHipDlfPickParams;
+
+#define SVT_HIP_DLF_PICK_RESULT_BYTES 1608
+typedef struct SvtHipDlfPickResult { /* ONE record in device memory, no implicit padding; a plane that is not searched keeps level 0,
+                                      * rounds 0, trials 0, best_err 0, ss_err -1 and a clear `finished` bit */
+    int32_t  level[3];      /*    0: filt_best; of a plane that ran out of rounds, the best of what was measured */
+    uint32_t finished;      /*   12: bit p: the search of plane p ran to its end */
+    int32_t  rounds[3];     /*   16: rounds in which the plane measured something */
+    int32_t  trials[3];     /*   28: try_filter_frame calls = measured entries of ss_err */
+    uint8_t  hdr_level[4];  /*   40: loop_filter_params.filter_level[0], [1] (both level[0], :1211), filter_level_u, _v: searched planes
+                             *       from level[], the others from frame.filter_level*: the 4 bytes the frame header needs */
+    int32_t  pad_;          /*   44: zero */
+    int64_t  best_err[3];   /*   48: ss_err[filt_best] (:986) */
+    int64_t  ss_err[3][64]; /*   72: the reference's ss_err array (:920-923): -1 where the level was never tried */
+} SvtHipDlfPickResult;
+
+/* Bytes of d_workspace for a picture of width x height luma samples: layout arithmetic, no device; 0 for an empty picture.  The
+ * workspace holds the state of the three loops and the six trial sums; nothing in it depends on the picture's size today. */
+SVT_HIP_API uint64_t svt_hip_dlf_pick_workspace_bytes(uint32_t width, uint32_t height, int32_t is_16bit);
+/* Reads frame.plane[] and src[] of the searched planes and the mode info; writes d_result and d_workspace, nothing else.  Of the
+ * planes it reads nothing left of column 0 or above row 0 and nothing more than 8 samples past the mi-aligned size.  A trial at
+ * level 0 is the unfiltered plane's error whatever the segment features say (the reference leaves the frame call before it
+ * builds the table).  Refused with SVT_HIP_ERR_BAD_PARAMETER and a message, before the library asks for a device:
+ *   - a NULL prm, d_result or d_workspace; either of the last two not 8-byte aligned;
+ *   - everything svt_hip_loop_filter_frame refuses of `frame`; a searched plane without plane, stride, src or src_stride;
+ *   - a start_level of a searched plane or a frame.filter_level* above 63; plane_mask 0 or above 7; max_rounds outside 1..63;
+ *   - an empty measured area of a searched plane, or one larger than the mi-aligned plane; workspace_bytes below svt_hip_dlf_pick_workspace_bytes(). */
+SVT_HIP_API uint32_t svt_hip_dlf_pick_levels(const SvtHipDlfPickParams *prm, SvtHipDlfPickResult *d_result, void *d_workspace,
+                                             uint64_t workspace_bytes, void *stream);
+/* Filters frame.plane[plane_start .. plane_end) in place as svt_hip_loop_filter_frame does, with the level table of
+ * svt_av1_loop_filter_frame_init (deblocking_common.c:76-138) derived on the device: a searched plane (plane_mask) takes
+ * d_result->level[], luma in both directions; any other plane takes frame.filter_level[2] / _u / _v.  Luma levels 0 and 0 with
+ * plane_start == 0 filter nothing at all, a chroma level of 0 skips that plane (:99-105, deblocking_filter.c:570-572).  src, the
+ * measured areas, the start levels and max_rounds are not read.  Refused like svt_hip_dlf_pick_levels: a NULL prm or d_result,
+ * a d_result not 8-byte aligned, what the frame call refuses, a frame.filter_level* above 63, plane_mask 0 or above 7. */
+SVT_HIP_API uint32_t svt_hip_dlf_apply_picked(const SvtHipDlfPickParams *prm, const SvtHipDlfPickResult *d_result, void *stream);
 
 /* =============================================================================================
  * Self-guided restoration

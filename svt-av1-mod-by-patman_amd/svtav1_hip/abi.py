@@ -323,6 +323,23 @@ class LfFrame(C.Structure):       # SvtHipLfFrame
 
 LF_MI_DTYPE = record_dtype(LfMi)   # numpy view of the mode-info grid
 
+DLF_MAX_LEVEL, DLF_PICK_DEFAULT_ROUNDS, DLF_PICK_RESULT_BYTES = 63, 16, 1608
+
+
+class DlfPickParams(C.Structure):   # SvtHipDlfPickParams
+    _fields_ = [("frame", LfFrame), ("src", C.c_void_p * 3), ("src_stride", C.c_uint32 * 3), ("sse_width", C.c_uint32 * 3),
+                ("sse_height", C.c_uint32 * 3), ("plane_mask", C.c_uint32), ("start_level", C.c_uint8 * 3), ("only_4x4", C.c_uint8),
+                ("early_exit_convergence", C.c_int32), ("max_rounds", C.c_int32), ("segmentation_enabled", C.c_uint8),
+                ("seg_lf_enabled", (C.c_uint8 * 4) * 8), ("pad_", C.c_uint8 * 3), ("seg_lf_data", (C.c_int16 * 4) * 8)]
+
+
+class DlfPickResult(C.Structure):   # SvtHipDlfPickResult
+    _fields_ = [("level", C.c_int32 * 3), ("finished", C.c_uint32), ("rounds", C.c_int32 * 3), ("trials", C.c_int32 * 3),
+                ("hdr_level", C.c_uint8 * 4), ("pad_", C.c_int32), ("best_err", C.c_int64 * 3), ("ss_err", (C.c_int64 * 64) * 3)]
+
+
+DLF_PICK_RESULT_DTYPE = record_dtype(DlfPickResult)   # numpy view of SvtHipDlfPickResult
+
 
 class SgrParams(C.Structure):     # SvtHipSgrParams == SgrParamsType
     _fields_ = [("r", C.c_int32 * 2), ("s", C.c_int32 * 2)]

@@ -365,6 +365,38 @@ class DeviceCdefPick:
                 "fb_strength": self.fb_strength.download(np.uint8, (2, self.n_fb), stream)}
 
 
+class DeviceDlfPick:
+    """Result record and workspace of svt_hip_dlf_pick_levels / svt_hip_dlf_apply_picked for a picture of width x height luma samples,
+    pre-filled with `fill`; pass `result` / `workspace` (device addresses) to use memory of the caller's instead.  run() and apply() only
+    enqueue; download() waits for the stream."""
+
+    def __init__(self, lib, width, height, is_16bit, fill=0xA5, result=None, workspace=None):
+        self.lib = lib
+        self.workspace_bytes = lib.svt_hip_dlf_pick_workspace_bytes(width, height, is_16bit)
+        self.bufs = []
+        if result is None:
+            self.bufs.append(DeviceBuffer(lib, C.sizeof(abi.DlfPickResult)))
+            result = self.bufs[-1].ptr
+        if workspace is None:
+            self.bufs.append(DeviceBuffer(lib, self.workspace_bytes))
+            workspace = self.bufs[-1].ptr
+        self.result, self.workspace = result, workspace
+        for b in self.bufs:
+            b.fill(fill)
+        _call(lib, "svt_hip_stream_sync")
+
+    def run(self, prm, stream=None):
+        return self.lib.svt_hip_dlf_pick_levels(C.byref(prm), self.result, self.workspace, self.workspace_bytes, stream)
+
+    def apply(self, prm, stream=None):
+        return self.lib.svt_hip_dlf_apply_picked(C.byref(prm), self.result, stream)
+
+    def download(self, stream=None):
+        out = np.empty((), abi.DLF_PICK_RESULT_DTYPE)
+        _call(self.lib, "svt_hip_download", out.ctypes.data, self.result, out.nbytes, stream=stream, sync=True)
+        return out
+
+
 class DeviceWienerPick:
     """Unit records, result record, the units for svt_hip_restoration_filter_frame and the workspace of svt_hip_wiener_pick_plane
     for a plane of n_units restoration units, pre-filled with `fill`.  run() only enqueues; download() waits for the stream."""
