@@ -1,8 +1,8 @@
 /*
  * svt_hip_inter.h — C-ABI for inter prediction: interpolation (the single-reference and the
  * compound ("jnt") families), the masked-compound and OBMC blends, the compound mask search, warped prediction (local warp
- * and global motion), the global-motion error / refinement, the full-pel and the sub-pel motion search of mode decision and OBMC's weighted
- * target and motion refinement.
+ * and global motion), the global-motion corner detection / matching and error / refinement, the full-pel and the sub-pel motion
+ * search of mode decision and OBMC's weighted target and motion refinement.
  *
  * Reference interfaces replaced (paths relative to /root/reference):
  *   Source/Lib/Codec/common_dsp_rtcd.h:185-221   svt_av1_convolve_{2d_sr,x_sr,y_sr,2d_copy_sr},
@@ -19,6 +19,8 @@
  *                                                arithmetic of svt_av1_highbd_warp_affine_c on plain uint16 samples)
  *   Source/Lib/Codec/warped_motion.c:357-363, 1045-1068   is_affine_shear_allowed, svt_get_shear_params
  *   Source/Lib/Codec/enc_warped_motion.c:22-98   svt_av1_warp_error
+ *   Source/Lib/Codec/corner_detect.c:19-30, third_party/fastfeat/{fast.c, fast_9.c, nonmax.c}   svt_av1_fast_corner_detect
+ *   Source/Lib/Codec/corner_match.c:87-218       svt_av1_determine_correspondence with improve_correspondence
  *   Source/Lib/Codec/global_motion.c:86-251      add_param_offset, force_wmtype, svt_av1_refine_integerized_param
  *   Source/Lib/Codec/mcomp.c:609-775             svt_av1_find_best_sub_pixel_tree(_pruned) as md_subpel_search calls them
  *   Source/Lib/Codec/product_coding_loop.c:1781-2046, 2075-2498, 3087-3108, 3263   md_full_pel_search under md_sq_motion_search,
@@ -27,7 +29,7 @@
  *   Source/Lib/Codec/mode_decision.c:2425-2533, av1me.c:709-1132   single_motion_search (OBMC_CAUSAL): svt_av1_obmc_full_pixel_search,
  *                                                svt_av1_find_best_obmc_sub_pixel_tree_up, svt_aom_obmc_sad* / svt_aom_obmc_variance*
  * The warp entry points are Tier B only: the RTCD pointers svt_av1_warp_affine / svt_av1_highbd_warp_affine have no leaf.
- * Scaled references are not covered; the corner matching / RANSAC front end of global motion and svt_find_projection stay on
+ * Scaled references are not covered; RANSAC over the correspondences of global motion and svt_find_projection stay on
  * the host.  The rate model of the mask search (model_rd_with_curvfit) stays on the host.  An OBMC candidate needs no host
  * arithmetic: its neighbour predictions are SvtHipConvolveDesc descriptors, then svt_hip_obmc_target_batch,
  * svt_hip_obmc_search_batch, the prediction at the vector found and the SVT_HIP_BLEND_VMASK / _HMASK blends; which neighbours
@@ -292,6 +294,70 @@ SVT_HIP_API int32_t svt_hip_warp_error_batch(const SvtHipWarpErrorJob *job, cons
  * 3 AFFINE.  job->workspace serves one candidate.  Synchronous. */
 SVT_HIP_API int32_t svt_hip_gm_refine(const SvtHipWarpErrorJob *job, int32_t wmmat[8], int32_t *wmtype, int32_t n_refinements,
                                       int64_t best_frame_error, int64_t *error, void *stream);
+
+/* ---- Global-motion front end: FAST-9 corners and correspondences (Tier B) ------------------------------------------------
+ * svt_av1_fast_corner_detect and svt_av1_determine_correspondence (with improve_correspondence) on device-resident 8-bit luma
+ * planes, bit-exact.  A picture's corners are detected once and serve whether the picture is the frame or a reference of a match;
+ * one match call takes one frame against several references.  What follows on the host is RANSAC over the at most 64 KB of a
+ * SvtHipGmMatches record, then svt_hip_gm_refine.
+ * The two status exports return SVT_HIP_GM_STATUS(status) as uint16_t: 0, or the low 16 bits of the SvtHipStatus. */
+#define SVT_HIP_GM_MAX_CORNERS 4096 /* MAX_CORNERS */
+#define SVT_HIP_GM_MAX_PLANES 8     /* planes per detect call, jobs per match call */
+#define SVT_HIP_GM_MAX_MATCH_SZ 13  /* the reference's match_sz_sq is a uint8_t and sumsq2 * match_sz_sq overflows int from 15 on */
+#define SVT_HIP_GM_STATUS(s) ((uint16_t)((s) & 0xffff))
+
+typedef struct SvtHipGmPlane { /* host memory */
+    const uint8_t *luma;       /* device memory, sample (0, 0) */
+    uint32_t       width, height, stride;
+    uint32_t       pad_;
+} SvtHipGmPlane;
+
+typedef struct SvtHipGmCorners { /* device memory, one per plane */
+    uint32_t count;              /* min(found, SVT_HIP_GM_MAX_CORNERS): what svt_av1_fast_corner_detect returns */
+    uint32_t found;              /* corners that survive the suppression, before the cap */
+    int32_t  xy[2 * SVT_HIP_GM_MAX_CORNERS]; /* x, y in raster order; entries from 2 * count on are not written */
+} SvtHipGmCorners;
+
+typedef struct SvtHipGmMatchJob { /* host memory */
+    SvtHipGmPlane          frm, ref; /* equal width and height, the strides may differ */
+    const SvtHipGmCorners *frm_corners, *ref_corners; /* device memory, 8-byte aligned; ref_corners in raster order (see the call) */
+    uint8_t                frm_quarters, ref_quarters; /* 1 .. 4: the job uses the first count * quarters / 4 corners (gm_ctrls.corners) */
+    uint8_t                match_sz;                   /* odd, 3 .. SVT_HIP_GM_MAX_MATCH_SZ */
+    uint8_t                pad_[5];
+} SvtHipGmMatchJob;
+
+typedef struct SvtHipGmMatches { /* device memory, one per job */
+    uint32_t count, pad_;        /* what svt_av1_determine_correspondence returns */
+    int32_t  pts[4 * SVT_HIP_GM_MAX_CORNERS]; /* x, y, rx, ry: the reference's Correspondence records in its order; the entries
+                                               * from 4 * count up to 4 * (frame corners used) are 0, the rest is not written */
+} SvtHipGmMatches;
+
+/* Layout only, needs no device: n_planes * (the byte score map, the survivor bit map and the row counts of one width x height plane,
+ * each rounded up to 256); 0 for an empty plane.  A call over planes of different sizes needs the sum over its planes of the value
+ * for (width, height, 1); the value for the largest width and height and the number of planes is enough. */
+SVT_HIP_API uint64_t svt_hip_gm_corners_workspace_bytes(uint32_t width, uint32_t height, uint32_t n_planes);
+/* d_out[i] belongs to planes[i].  FAST-9 at barrier 18 on every pixel with 3 <= x < width - 3 and 3 <= y < height - 3, the score of
+ * fast9_score, the suppression of nonmax.c (a corner goes when one of its eight neighbours is a corner with a score >= its own), the
+ * survivors in raster order.  The order comes from per-row counts, never from atomics: two calls give identical records.
+ * SVT_HIP_ERR_BAD_PARAMETER for a NULL pointer, n > SVT_HIP_GM_MAX_PLANES, an empty plane, a stride smaller than the width, a
+ * workspace that is too small, and two refusals of this library's own: a plane of more than 16384 samples a side (the reference's
+ * squared distances leave int beyond), and records or a workspace that are not 8-byte aligned.
+ * n == 0 is SVT_HIP_OK and launches nothing.  Asynchronous on `stream`, no host step. */
+SVT_HIP_API uint16_t svt_hip_gm_detect_corners(const SvtHipGmPlane *planes, uint32_t n, SvtHipGmCorners *d_out, void *workspace,
+                                               uint64_t workspace_bytes, void *stream);
+/* d_out[i] belongs to jobs[i]; jobs may share corner records, and the call may follow the detect call that writes them on the same
+ * stream with nothing in between.  Per frame corner whose match_sz window lies inside the picture: the reference corner with the
+ * largest svt_av1_compute_cross_correlation_c among those whose window lies inside and whose squared distance is at most
+ * (max(width, height) >> 4) squared, the first one on ties; kept when that exceeds template_norm * 0.75 * 0.75; then both passes of
+ * improve_correspondence.
+ * PRECONDITION, NOT CHECKED: the corners of a reference record are in raster order (y ascending, x ascending within a row), as
+ * svt_hip_gm_detect_corners writes them: the candidates of a frame corner are found by a binary search on y.  A caller that fills a
+ * record itself must keep that order; any other order gives wrong correspondences and no error.  The frame record may be in any order.
+ * SVT_HIP_ERR_BAD_PARAMETER for a NULL pointer, n > SVT_HIP_GM_MAX_PLANES, an empty plane, a stride smaller than the width, unequal
+ * frame and reference sizes, quarters outside 1 .. 4, a match_sz that is even, below 3 or above SVT_HIP_GM_MAX_MATCH_SZ, and two
+ * refusals of this library's own: a plane of more than 16384 samples a side, and corner or match records that are not 8-byte aligned.
+ * n == 0 is SVT_HIP_OK and launches nothing.  Asynchronous on `stream`, no host step. */
+SVT_HIP_API uint16_t svt_hip_gm_match_corners(const SvtHipGmMatchJob *jobs, uint32_t n, SvtHipGmMatches *d_out, void *stream);
 
 /* ---- Sub-pel motion search of mode decision (Tier B) ---------------------------------------------------------------------
  * One descriptor = one luma block of one (list, reference): md_subpel_search (product_coding_loop.c:2502-2614) behind its

@@ -508,6 +508,34 @@ class WarpErrorResult(C.Structure):      # SvtHipWarpErrorResult
 WARP_CANDIDATE_DTYPE, WARP_ERROR_RESULT_DTYPE = record_dtype(WarpCandidate), record_dtype(WarpErrorResult)
 
 
+GM_MAX_CORNERS, GM_MAX_PLANES, GM_MAX_MATCH_SZ = 4096, 8, 13     # SVT_HIP_GM_* (include/svt_hip_inter.h)
+
+
+def gm_status(status):
+    """SVT_HIP_GM_STATUS: a SvtHipStatus as the uint16_t that svt_hip_gm_detect_corners and svt_hip_gm_match_corners return"""
+    return status & 0xFFFF
+
+
+class GmPlane(C.Structure):              # SvtHipGmPlane
+    _fields_ = [("luma", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("stride", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class GmCorners(C.Structure):            # SvtHipGmCorners
+    _fields_ = [("count", C.c_uint32), ("found", C.c_uint32), ("xy", C.c_int32 * (2 * GM_MAX_CORNERS))]
+
+
+class GmMatchJob(C.Structure):           # SvtHipGmMatchJob
+    _fields_ = [("frm", GmPlane), ("ref", GmPlane), ("frm_corners", C.c_void_p), ("ref_corners", C.c_void_p), ("frm_quarters", C.c_uint8),
+                ("ref_quarters", C.c_uint8), ("match_sz", C.c_uint8), ("pad_", C.c_uint8 * 5)]
+
+
+class GmMatches(C.Structure):            # SvtHipGmMatches
+    _fields_ = [("count", C.c_uint32), ("pad_", C.c_uint32), ("pts", C.c_int32 * (4 * GM_MAX_CORNERS))]
+
+
+GM_CORNERS_DTYPE, GM_MATCHES_DTYPE = record_dtype(GmCorners), record_dtype(GmMatches)   # numpy views of the two device records
+
+
 class TfBlock(C.Structure):              # SvtHipTfBlock (include/svt_hip_tf.h)
     _fields_ = [("src", C.c_void_p * 3), ("pred", C.c_void_p * 3), ("accum", C.c_void_p * 3), ("count", C.c_void_p * 3),
                 ("src_stride", C.c_uint32 * 3), ("pred_stride", C.c_uint32 * 3), ("decay_factor_fp16", C.c_uint32 * 3),
