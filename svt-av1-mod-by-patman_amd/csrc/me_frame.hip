@@ -1733,7 +1733,21 @@ __global__ __launch_bounds__(WG_THREADS, SVT_HIP_ME_WGS) void me_b64_kernel(cons
                         wg_direct_search(L.sh, a.nd, (uint32_t)direct_rows, a.src, a.row_dw, a.bh);
                     else
 #endif
-                    wg_multi_search(L.sh, a.nd, a.src, a.row_dw, a.bw, a.bh, L.win, a.cap);
+                    {
+#if SVT_HIP_ME_S16_DIRECT
+                        // HME level 0 (and pre-HME, in builds with bit 1 of the switch) searches a 16-sample-wide block on the 1/16
+                        // plane: the small and the flat areas are read from the plane ahead of the staged passes, which then hold
+                        // the tall and the large ones only, and do not run when nothing is left for them (uniform)
+                        const int s16 = step < 4 && ((step < 2 ? 2 : 1) & SVT_HIP_ME_S16_DIRECT) != 0
+                            ? wg_s16_plan(L.sh, a.nd, a.src, a.row_dw, a.bw, a.bh) : -1;
+                        if (s16 >= 0)
+                            wg_s16_search(L.sh, a.src, a.row_dw, a.bh);
+                        if (s16 != 0)
+                            wg_multi_search(L.sh, a.nd, a.src, a.row_dw, a.bw, a.bh, L.win, a.cap, s16 > 0);
+#else
+                        wg_multi_search(L.sh, a.nd, a.src, a.row_dw, a.bw, a.bh, L.win, a.cap);
+#endif
+                    }
                 }
             }
         }

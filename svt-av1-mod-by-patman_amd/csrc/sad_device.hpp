@@ -287,10 +287,23 @@ __device__ __forceinline__ void oct_sad_fixed(const uint32_t *__restrict__ w, ui
     for (int i = 0; i < 8; i++) out[i] = a[i];
 }
 
-__device__ __forceinline__ void search_plan_desc(SearchDesc &d, uint32_t bw, uint32_t bh, uint32_t win_cap_dw) {
+// Widest / tallest search area (positions) of a 16-sample-wide block that is read straight from the reference plane
+// (wg_s16_search below): HME level 0 of the fast presets (16 x 8, 16 x 4) and the wide pre-HME region (96..384 x 3) qualify,
+// the tall pre-HME region (8 x 100..200) and the level-0 quadrants of distant references or slow presets (up to 48 x 48) do not.
+constexpr int32_t S16_MAX_W = 384, S16_MAX_ROWS = 8;
+
+// The shape test of the direct search of 16-sample-wide blocks, for one descriptor of a call whose block passed the test of
+// wg_s16_plan: block rows step by once or twice the raw stride, every row is searched, and the area is within the limits.
+__device__ __forceinline__ bool s16_direct_shape(const SearchDesc &d) {
+    return d.sa_w > 0 && d.sa_h > 0 && d.sa_w <= S16_MAX_W && d.sa_h <= S16_MAX_ROWS && d.skip == 0 && d.raw_stride != 0 &&
+        (d.ref_stride == d.raw_stride || d.ref_stride == 2 * d.raw_stride);
+}
+
+// `s16`: wg_s16_search has already searched the descriptors of direct shape, which leaves nothing to search for them here
+__device__ __forceinline__ void search_plan_desc(SearchDesc &d, uint32_t bw, uint32_t bh, uint32_t win_cap_dw, bool s16 = false) {
     d.fast = 0;
     d.k    = 0;
-    if (d.sa_w <= 0 || d.sa_h <= 0) {
+    if (d.sa_w <= 0 || d.sa_h <= 0 || (s16 && s16_direct_shape(d))) {
         d.n_srows = 0, d.nq = 0, d.no = 0;
         return;
     }
@@ -328,10 +341,12 @@ template <bool ITEMS, class SH> __device__ __forceinline__ uint32_t find_seg(con
 // (search areas are int16 in every caller; (row, column) orders like the raster index and decodes without a division).
 // Must be called by all WG_THREADS threads of the workgroup; contains barriers.  Descriptor i must have been
 // written by thread i (or be visible through an earlier barrier).
+// `s16`: the call comes behind wg_s16_plan / wg_s16_search, which have initialised sh.best[] and searched every descriptor of
+// direct shape: those are left alone here, the others are searched as usual.
 template <class SH>
 __device__ __forceinline__ void wg_multi_search(SH &sh, uint32_t n, const uint32_t *__restrict__ src,
                                        uint32_t src_row_dw, uint32_t bw, uint32_t bh, uint32_t *__restrict__ win,
-                                       uint32_t win_cap_dw) {
+                                       uint32_t win_cap_dw, bool s16 = false) {
     uint32_t tid = threadIdx.x;
     asm volatile("" : "+v"(tid));  // opaque: or the planner's lane masks are hoisted out of the caller's loop, and spilled there
     // b128 source reads need 16-byte aligned rows (LDS addresses are 32-bit offsets: test the low bits)
@@ -340,8 +355,9 @@ __device__ __forceinline__ void wg_multi_search(SH &sh, uint32_t n, const uint32
     unsigned long long ms_last = wall_clock64();
 #endif
     if (tid < n) {
-        search_plan_desc(sh.desc[tid], bw, bh, win_cap_dw);
-        sh.best[tid] = KEY_NONE;
+        search_plan_desc(sh.desc[tid], bw, bh, win_cap_dw, s16);
+        if (!s16)
+            sh.best[tid] = KEY_NONE;
     }
     if (tid == 0) {
         sh.next_d = 0, sh.next_j = 0;
@@ -748,6 +764,174 @@ __device__ __forceinline__ void wg_direct_search(SH &sh, uint32_t n, uint32_t ma
                 kmin             = k < kmin ? k : kmin;
             }
             atomicMin((unsigned long long *)&sh.best[d], ((unsigned long long)(kmin >> 3) << 32) | ((j << 16) | (kmin & 7u)));
+        }
+    }
+    __syncthreads();
+}
+
+// ---- direct search of 16-sample-wide blocks: HME level 0 and the wide pre-HME region ----
+// A level-0 quadrant of the fast presets (16 x 8 positions) and the wide, flat pre-HME region (96..384 x 3) reuse a staged
+// dword about 3.9 times, as little as the windows above, and the wide region's windows are a third of what a pre-HME call
+// stages: such descriptors are read from the plane, each by its own shape (s16_direct_shape), beside descriptors of the same
+// call that stay staged (the tall pre-HME region, larger level-0 quadrants, `skip`).
+// SVT_HIP_ME_S16_DIRECT: bit 0 = HME level 0, bit 1 = pre-HME; 0 is the diagnostic build in which every such search is staged.
+// Level 0 is on: its calls become all-direct at the fast presets (1.577 -> 1.529 ms per launch of the 4K workload).  Pre-HME is
+// off: its call keeps the planner and the passes for the tall region, and reading the wide region's 288 items from the plane
+// costs what staging its 3689 dwords did (1.577 -> 1.581 ms alone, 1.529 -> 1.525 ms on top of level 0: inside the noise;
+// profiles/me_s16_direct_4k.json).
+#ifndef SVT_HIP_ME_S16_DIRECT
+#define SVT_HIP_ME_S16_DIRECT 1
+#endif
+#ifdef SVT_HIP_NO_QSAD  // the v_sad_u8 diagnostic build has no direct walk
+#undef SVT_HIP_ME_S16_DIRECT
+#define SVT_HIP_ME_S16_DIRECT 0
+#endif
+#ifndef SVT_HIP_ME_S16_LG
+#define SVT_HIP_ME_S16_LG 0  // log2 of the lanes that share an item's block rows: G = 1 / 2 / 4 measured 1.520 / 1.543 / 1.655 ms
+#endif
+
+// `nrows` block rows of 16 samples against the 8 positions at gp, added to sad[0..7]: per row 16 + 8 bytes from the plane (window
+// dwords 0..5) and the v_qsad_pk_u16_u8 sequence of oct_sad_fixed<16> (keep the two in step).  At most 16 rows: 16 * 16 * 255 =
+// 65280 is the most a 16-bit lane of the packed accumulators holds (wg_s16_plan rejects taller blocks).  One window row is held
+// at a time, as in direct_walk32.
+__device__ __forceinline__ void direct_walk16(const uint8_t *gp, uint32_t rstep, const uint32_t *__restrict__ sr, uint32_t src_row_dw,
+                                              uint32_t nrows, bool no_loads, bool no_sad, uint32_t sad[8]) {
+    uint64_t acc_a = 0, acc_b = 0;
+#pragma unroll 1
+    for (uint32_t r = 0; r < nrows; r++) {
+        u128v v = {0u, 0u, 0u, 0u};
+        u64v  w = {0u, 0u};
+        if (!no_loads)
+            v = load_u128_any(gp), w = load_u64_any(gp + 16);
+        if (no_sad) {
+            asm volatile("" ::"v"(v), "v"(w));  // (ABLATE builds) the loads stay
+        } else {
+            const uint4 sv = *(const uint4 *)sr;
+            acc_a = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.x, v.y), sv.x, acc_a);
+            acc_b = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.y, v.z), sv.x, acc_b);
+            acc_a = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.y, v.z), sv.y, acc_a);
+            acc_b = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.z, v.w), sv.y, acc_b);
+            acc_a = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.z, v.w), sv.z, acc_a);
+            acc_b = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.w, w.x), sv.z, acc_b);
+            acc_a = __builtin_amdgcn_qsad_pk_u16_u8(pair64(v.w, w.x), sv.w, acc_a);
+            acc_b = __builtin_amdgcn_qsad_pk_u16_u8(pair64(w.x, w.y), sv.w, acc_b);
+        }
+        gp += rstep, sr += src_row_dw;
+    }
+    sad[0] += (uint32_t)(acc_a & 0xffff), sad[1] += (uint32_t)((acc_a >> 16) & 0xffff);
+    sad[2] += (uint32_t)((acc_a >> 32) & 0xffff), sad[3] += (uint32_t)(acc_a >> 48);
+    sad[4] += (uint32_t)(acc_b & 0xffff), sad[5] += (uint32_t)((acc_b >> 16) & 0xffff);
+    sad[6] += (uint32_t)((acc_b >> 32) & 0xffff), sad[7] += (uint32_t)(acc_b >> 48);
+}
+
+// Which of the n descriptors (written by threads 0..n-1, not yet behind a barrier) does wg_s16_search take?  The answer is
+// uniform over the workgroup: -1 = the block does not qualify (nothing has been done: call wg_multi_search), otherwise sh.best[]
+// is initialised, one barrier is passed, the descriptors of direct shape are listed in sh.seg[0 .. sh.nseg) (`d`, `item_base`;
+// `nj` = items per searched row, `nstage` = its inverse for fast_div) with sh.nitems work items, and the answer is 1 when other
+// descriptors are left for wg_multi_search(.., s16 = true), 0 when there are none: then the planner, the passes and their
+// barriers do not run at all.  The block qualifies with at most 16 16-byte aligned source rows of 16 samples.
+template <class SH>
+__device__ __forceinline__ int wg_s16_plan(SH &sh, uint32_t n, const uint32_t *__restrict__ src, uint32_t src_row_dw, uint32_t bw,
+                                           uint32_t bh) {
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));  // (opaque, as in wg_direct_plan)
+    if (bw != 16 || bh > 16 || n > (uint32_t)SH::MAXS || n > 64u || (((uint32_t)(uintptr_t)src) & 15u) != 0 || (src_row_dw & 3u) != 0)
+        return -1;
+    if (tid < 64) {  // the first wave, lane = descriptor: every lane reads the descriptor it wrote itself
+        uint32_t items = 0, no = 0;
+        bool     direct = false, rest = false;
+        if (tid < n) {
+            const SearchDesc &ds = sh.desc[tid];
+            direct = s16_direct_shape(ds);
+            rest   = !direct && ds.sa_w > 0 && ds.sa_h > 0;
+            if (direct)
+                no = ((uint32_t)ds.sa_w + 7u) >> 3, items = no * (uint32_t)ds.sa_h;
+            sh.best[tid] = KEY_NONE;
+        }
+        uint32_t pi = items;  // inclusive prefix sum
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t a = __shfl_up(pi, off, 64);
+            if ((int)tid >= off)
+                pi += a;
+        }
+        const uint64_t dmask = __ballot(direct);
+        const uint32_t total = __shfl(pi, 63, 64);
+        const bool     any_rest = __ballot(rest) != 0;
+        if (direct) {
+            SearchSeg &sg = sh.seg[__popcll(dmask & ((1ull << tid) - 1ull))];
+            sg.d = tid, sg.item_base = pi - items, sg.nj = no, sg.nstage = make_inv_small(no);
+        }
+        if (tid == 0)
+            sh.nseg = (uint32_t)__popcll(dmask), sh.nitems = total, sh.nstage_dw = any_rest ? 1u : 0u;
+    }
+    __syncthreads();
+    return (int)sh.nstage_dw;
+}
+
+// Exhaustive search of the descriptors wg_s16_plan listed, results in sh.best[] as wg_multi_search leaves them.  A work item is
+// eight adjacent positions of one searched row of one descriptor; the items of all listed descriptors form one flat list.  The
+// bh <= 16 block rows of an item are split over G = 1 << SVT_HIP_ME_S16_LG adjacent lanes.  As built G is 1: eight sub-sampled
+// rows are too few to pay for the cross-lane sum, unlike level 1's sixteen rows of twice the width.  With G > 1, fewer lanes
+// share an item when G would leave less than two rows each (b64 at the bottom edge).  Each lane reads its window rows from the
+// plane — bytes [8o, 8o + 24) of the row for the o-th item, at most 8 bytes past the last byte the row's positions compare —
+// and its source rows from LDS; the partial SADs are summed across the G lanes and the first lane builds the key.  Must be
+// called by all WG_THREADS threads; ends with a barrier (none when there is no item).
+template <class SH>
+__device__ __forceinline__ void wg_s16_search(SH &sh, const uint32_t *__restrict__ src, uint32_t src_row_dw, uint32_t bh) {
+    uint32_t tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));  // (opaque, as in wg_direct_plan)
+    const uint32_t nseg = sh.nseg;
+#ifdef SVT_HIP_ME_ABLATE
+    const int      ms_skip = g_ms_skip;
+    const bool     no_loads = ms_skip & 1, no_sad = ms_skip & 2;
+    const uint32_t nitems = (ms_skip & 4) ? 0u : sh.nitems;
+#else
+    constexpr bool no_loads = false, no_sad = false;
+    const uint32_t nitems = sh.nitems;
+#endif
+    if (sh.nitems == 0)  // (uniform)
+        return;
+    constexpr uint32_t LG = SVT_HIP_ME_S16_LG;
+    static_assert(LG <= 2, "an item's lanes stay inside a group of four");
+    const uint32_t lg = bh < 4 ? 0u : (bh < 8 && LG > 1 ? 1u : LG);  // log2 G
+    const uint32_t rpl = (bh + (1u << lg) - 1u) >> lg, g = tid & ((1u << lg) - 1u);  // block rows per lane, lane within the item
+    const uint32_t rb = g * rpl, nrows = bh > rb ? (bh - rb < rpl ? bh - rb : rpl) : 0u;  // this lane's rows: [rb, rb + nrows)
+    uint32_t s = 0;  // items grow from one iteration to the next, and so does the segment that holds them
+    for (uint32_t item = tid >> lg; item < nitems; item += (uint32_t)WG_THREADS >> lg) {  // (the G lanes of an item leave together)
+        while (s + 1 < nseg && item >= sh.seg[s + 1].item_base) s++;
+        const SearchSeg   sg = sh.seg[s];
+        const SearchDesc &ds = sh.desc[sg.d];
+        const uint32_t    li = item - sg.item_base;
+        const uint32_t    j = fast_div(li, sg.nstage), x0 = 8u * (li - sad_mul_u24(j, sg.nj));  // searched row, first column
+        const uint32_t    rstep = ds.ref_stride;
+        const uint8_t    *gp = ds.ref + (size_t)(sad_mul_u24(j, ds.raw_stride) + sad_mul_u24(rb, rstep) + x0);
+        const uint32_t   *sr = src + rb * src_row_dw;
+        uint32_t          sad[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        direct_walk16(gp, rstep, sr, src_row_dw, nrows, no_loads, no_sad, sad);
+        // sum over the G lanes of the item: quad_perm [1,0,3,2], then [2,3,0,1]
+        if (lg >= 1) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) sad[i] += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sad[i], 0xB1, 0xf, 0xf, true);
+        }
+        if (LG >= 2 && lg >= 2) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) sad[i] += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sad[i], 0x4E, 0xf, 0xf, true);
+        }
+        if (no_sad) {  // (ABLATE builds)
+#pragma unroll
+            for (int i = 0; i < 8; i++) sad[i] = item + i;
+        }
+        if (g == 0) {
+            // as in wg_multi_search: positions in raster order, (sad << 3 | position) keeps the first minimum
+            const uint32_t nvalid = (uint32_t)ds.sa_w - x0;  // >= 1; fewer than 8 in a row's last item when the width is no multiple of 8
+            uint32_t       kmin = ~0u;
+#pragma unroll
+            for (uint32_t p = 0; p < 8; p++) {
+                const uint32_t k = p < nvalid ? ((sad[p] << 3) | p) : ~0u;
+                kmin             = k < kmin ? k : kmin;
+            }
+            atomicMin((unsigned long long *)&sh.best[sg.d], ((unsigned long long)(kmin >> 3) << 32) | ((j << 16) | (x0 + (kmin & 7u))));
         }
     }
     __syncthreads();
