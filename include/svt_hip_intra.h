@@ -37,7 +37,8 @@
  *                                     svt_cfl_predict_{lbd,hbd}_c as compute_cfl_ac_components (product_coding_loop.c:3615-3650)
  *                                     and the alpha search call them.
  * Neither is an RTCD leaf: a leaf would put a round trip over the bus behind every intra call of the encoder.
- * Not provided: palette prediction, intra block copy, the 4:4:4 and 4:2:2 CfL sub-sampling, the derivation of the availability
+ * (4) - (6), further down: the luma palette (search with its rate terms, prediction) and the screen-content decision.
+ * Not provided: intra block copy, chroma palettes, the 4:4:4 and 4:2:2 CfL sub-sampling, the derivation of the availability
  * counts (svt_aom_intra_has_top_right / _bottom_left, tile and frame edges: control logic of the caller), and the caller that keeps
  * mode decision's candidates on the device.
  */
@@ -138,6 +139,113 @@ typedef struct SvtHipCflDesc {
 } SvtHipCflDesc;
 /* Errors as svt_hip_intra_predict_batch. */
 SVT_HIP_API int32_t svt_hip_cfl_predict_batch(const SvtHipCflDesc *d_desc, uint32_t n, void *stream);
+
+/* ---- Luma palette: search, rate and prediction (Tier B), and the screen-content decision ---------------------------------
+ * (4) svt_hip_palette_search_batch: one descriptor = one luma block of 8x8 .. 64x64.
+ * Reference interface replaced:
+ *   Codec/palette.c:309-434           search_palette_luma with everything below it: svt_av1_count_colors[_highbd],
+ *                                     svt_get_palette_cache_y (palette.c:159-201), the dominant colours, svt_av1_k_means_dim1_c
+ *                                     (k_means_template.h), palette_rd_y with optimize_palette_colors, av1_remove_duplicates,
+ *                                     svt_av1_calc_indices_dim1 and extend_palette_color_map, and the rule that a candidate keeps
+ *                                     its slot only when more than 2 colours are left
+ *   Codec/rd_cost.c:691-704           the palette terms of av1_intra_fast_cost for every kept candidate: palette_ysize_fac_bits +
+ *                                     svt_aom_write_uniform_cost, svt_av1_palette_color_cost_y and svt_av1_cost_color_map
+ * (5) svt_hip_palette_predict_batch: the palette branch of svt_av1_predict_intra_block[_16bit]
+ *     (Codec/enc_intra_prediction.c:501-510, 647-656).
+ * (6) svt_hip_sc_classify: svt_aom_is_screen_content (Codec/pic_analysis_process.c:1848-1917).
+ * Not provided: chroma palettes (the reference never uses them), 12 bit, the palette_ymode_fac_bits term (its context comes from
+ * the neighbours' modes), svt_av1_tokenize_color_map and the CDF update, intra block copy, and the caller inside the encoder. */
+/* The three status exports of this part return SVT_HIP_PALETTE_STATUS(status) as uint64_t: 0, or the SvtHipStatus zero-extended
+ * (SVT_HIP_ERR_BAD_PARAMETER arrives as 0x80001005). */
+#define SVT_HIP_PALETTE_STATUS(s) ((uint64_t)(uint32_t)(s))
+#define SVT_HIP_PALETTE_MAX_SIZE  8  /* PALETTE_MAX_SIZE */
+#define SVT_HIP_PALETTE_MAX_CANDS 14 /* what search_palette_luma can keep for one block */
+#define SVT_HIP_PALETTE_DOMINANT  0  /* SvtHipPaletteCand.origin */
+#define SVT_HIP_PALETTE_KMEANS    1
+
+typedef struct SvtHipPaletteRates { /* of MdRateEstimationContext */
+    int32_t palette_ysize_fac_bits[7][7]; /* the 7 sizes of each row (the reference's rows have CDF_SIZE(7) = 8 entries) */
+    int32_t palette_ycolor_fac_bitss[7][5][8];
+} SvtHipPaletteRates;
+
+typedef struct SvtHipPaletteCtrls {
+    const SvtHipPaletteRates *d_rates; /* device memory, 4-byte aligned: the picture's table */
+    uint8_t dominant_color_step;       /* palette_ctrls.dominant_color_step: 1 or 2 */
+    uint8_t bit_depth;                 /* 8: uint8 samples; 10: 10-bit samples in uint16 */
+    uint8_t max_itr;                   /* 1 .. 50; the reference uses 50 */
+    uint8_t pad_[5];
+} SvtHipPaletteCtrls;
+
+typedef struct SvtHipPaletteCand {
+    uint8_t  origin;           /* SVT_HIP_PALETTE_DOMINANT / _KMEANS */
+    uint8_t  n;                /* the n of the loop the candidate came from */
+    uint8_t  palette_size;     /* 3 .. 8: after the cache snap and the removal of duplicates */
+    uint8_t  pad_;
+    uint16_t palette_colors[SVT_HIP_PALETTE_MAX_SIZE]; /* ascending; entries from palette_size on are 0 */
+    int32_t  size_bits;        /* palette_ysize_fac_bits[bsize_ctx][palette_size - 2] + svt_aom_write_uniform_cost(palette_size, map[0]) */
+    int32_t  color_bits;       /* svt_av1_palette_color_cost_y */
+    int32_t  map_bits;         /* svt_av1_cost_color_map */
+} SvtHipPaletteCand;
+
+typedef struct SvtHipPaletteRecord { /* every byte of it is written; pads and unused entries are 0 */
+    uint16_t          colors;  /* svt_av1_count_colors over rows x cols; 0 when a 10-bit sample is out of range, as in the reference */
+    uint8_t           n_cands; /* 0 unless 1 < colors <= 64 */
+    uint8_t           n_cache; /* entries of cache: svt_get_palette_cache_y */
+    uint16_t          cache[2 * SVT_HIP_PALETTE_MAX_SIZE];
+    uint8_t           pad_[12];
+    SvtHipPaletteCand cand[SVT_HIP_PALETTE_MAX_CANDS]; /* in the reference's order */
+} SvtHipPaletteRecord;
+
+typedef struct SvtHipPaletteDesc {
+    const void          *src;    /* the source luma PLANE (device): sample (org_y + r, org_x + c) is src[(org_y + r) * stride + org_x + c] */
+    SvtHipPaletteRecord *record; /* device, 8-byte aligned */
+    uint8_t             *maps;   /* device, 4-byte aligned, SVT_HIP_PALETTE_MAX_CANDS * width * height bytes: the colour index map of
+                                  * candidate i at i * width * height, width x height (extended); maps of slots from n_cands on are
+                                  * left as they are */
+    uint32_t stride;             /* in samples */
+    uint32_t org_x, org_y;       /* the block's origin in the plane */
+    uint8_t  width, height;      /* 8, 16, 32 or 64 each, at most 1:4: the 14 block sizes of 8x8 .. 64x64 (of the 16 that
+                                  * svt_aom_allow_palette admits, 4x16 and 16x4 are left out) */
+    uint8_t  rows, cols;         /* inside the picture (svt_aom_get_block_dimensions): 1 .. height, 1 .. width */
+    uint8_t  above_n, left_n;    /* 0 .. 8: palette_size of the neighbours; above_n = 0 on a superblock-row boundary */
+    uint8_t  pad_[6];
+    uint16_t above[SVT_HIP_PALETTE_MAX_SIZE], left[SVT_HIP_PALETTE_MAX_SIZE]; /* their palette_colors: ascending, below 1 << bit_depth */
+} SvtHipPaletteDesc;
+
+/* `ctrls` and `desc` are HOST memory (desc an array of n >= 1); everything they point to is device memory.  Every descriptor is
+ * validated before anything is launched: SVT_HIP_PALETTE_STATUS(SVT_HIP_ERR_BAD_PARAMETER), with svt_hip_last_error naming the function and the descriptor, for
+ * NULL arguments, a size other than 8 .. 64, rows / cols of 0 or beyond the block, a bit depth other than 8 or 10, a step other than
+ * 1 or 2, max_itr outside 1 .. 50, neighbour palettes longer than 8 or with a colour beyond the bit depth, a misaligned record, map
+ * storage or table, or an odd uint16 plane.  Asynchronous on `stream`; one workgroup per descriptor.  The same inputs give the same bytes. */
+SVT_HIP_API uint64_t svt_hip_palette_search_batch(const SvtHipPaletteCtrls *ctrls, const SvtHipPaletteDesc *desc, uint32_t n, void *stream);
+
+/* dst[r][c] = palette[map[(r + y) * map_width + c + x]] for r < h, c < w.  Descriptors live in DEVICE memory, as those of
+ * svt_hip_intra_predict_batch do: the kernel SKIPS a descriptor (dst keeps every byte) with a NULL pointer, w or h of 0, x + w > map_width,
+ * a bit depth other than 8 or 10 (8 unless is_16bit), or an odd uint16 dst.  A map entry is taken modulo 8. */
+typedef struct SvtHipPalettePredDesc {
+    const uint8_t  *map;       /* the block's colour index map, where the search left it */
+    const uint16_t *colors;    /* SvtHipPaletteCand.palette_colors of the chosen candidate */
+    void           *dst;
+    uint32_t        dst_stride; /* in samples */
+    uint16_t        map_width;  /* the block's width */
+    uint8_t         x, y, w, h; /* the transform block inside the map */
+    uint8_t         is_16bit;   /* 0: uint8 samples; 1: uint16, clamped to (1 << bit_depth) - 1 */
+    uint8_t         bit_depth;
+    uint8_t         pad_[4];
+} SvtHipPalettePredDesc;
+/* Errors as svt_hip_intra_predict_batch. */
+SVT_HIP_API uint64_t svt_hip_palette_predict_batch(const SvtHipPalettePredDesc *d_desc, uint32_t n, void *stream);
+
+typedef struct SvtHipScClass {
+    uint32_t counts_1;      /* whole 16x16 blocks with 2 .. 4 colours */
+    uint32_t counts_2;      /* those of them whose rounded per-pixel variance against 128 is > 0 */
+    uint32_t blocks;        /* whole 16x16 blocks of the plane */
+    uint8_t  sc_class[4];   /* sc_class0 .. sc_class3 */
+    uint32_t pad_[2];
+} SvtHipScClass;
+/* An 8-bit luma plane in device memory; d_out (device, 4-byte aligned) is written whole.  BAD_PARAMETER for NULL, an empty plane, a
+ * side beyond 16384, more than 2^31 / 50 pixels (the reference's int products) or stride < width. */
+SVT_HIP_API uint64_t svt_hip_sc_classify(const uint8_t *d_plane, uint32_t width, uint32_t height, uint32_t stride, SvtHipScClass *d_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -763,3 +763,51 @@ class CflDesc(C.Structure):              # SvtHipCflDesc
 
 # numpy views of arrays of SvtHipIntraPredDesc / SvtHipCflDesc (pointers as addresses)
 INTRA_PRED_DESC_DTYPE, CFL_DESC_DTYPE = record_dtype(IntraPredDesc), record_dtype(CflDesc)
+
+PALETTE_MAX_SIZE, PALETTE_MAX_CANDS, PALETTE_DOMINANT, PALETTE_KMEANS = 8, 14, 0, 1   # SVT_HIP_PALETTE_*
+
+
+def palette_status(status):
+    """SVT_HIP_PALETTE_STATUS: a SvtHipStatus as the uint64_t that svt_hip_palette_search_batch, svt_hip_palette_predict_batch and
+    svt_hip_sc_classify return"""
+    return status & 0xFFFFFFFF
+
+
+class PaletteRates(C.Structure):         # SvtHipPaletteRates
+    _fields_ = [("palette_ysize_fac_bits", C.c_int32 * 7 * 7), ("palette_ycolor_fac_bitss", C.c_int32 * 8 * 5 * 7)]
+
+
+class PaletteCtrls(C.Structure):         # SvtHipPaletteCtrls
+    _fields_ = [("d_rates", C.c_void_p), ("dominant_color_step", C.c_uint8), ("bit_depth", C.c_uint8), ("max_itr", C.c_uint8),
+                ("pad_", C.c_uint8 * 5)]
+
+
+class PaletteCand(C.Structure):          # SvtHipPaletteCand
+    _fields_ = [("origin", C.c_uint8), ("n", C.c_uint8), ("palette_size", C.c_uint8), ("pad_", C.c_uint8),
+                ("palette_colors", C.c_uint16 * PALETTE_MAX_SIZE), ("size_bits", C.c_int32), ("color_bits", C.c_int32), ("map_bits", C.c_int32)]
+
+
+class PaletteRecord(C.Structure):        # SvtHipPaletteRecord
+    _fields_ = [("colors", C.c_uint16), ("n_cands", C.c_uint8), ("n_cache", C.c_uint8), ("cache", C.c_uint16 * (2 * PALETTE_MAX_SIZE)),
+                ("pad_", C.c_uint8 * 12), ("cand", PaletteCand * PALETTE_MAX_CANDS)]
+
+
+class PaletteDesc(C.Structure):          # SvtHipPaletteDesc
+    _fields_ = [("src", C.c_void_p), ("record", C.c_void_p), ("maps", C.c_void_p), ("stride", C.c_uint32), ("org_x", C.c_uint32),
+                ("org_y", C.c_uint32), ("width", C.c_uint8), ("height", C.c_uint8), ("rows", C.c_uint8), ("cols", C.c_uint8),
+                ("above_n", C.c_uint8), ("left_n", C.c_uint8), ("pad_", C.c_uint8 * 6), ("above", C.c_uint16 * PALETTE_MAX_SIZE),
+                ("left", C.c_uint16 * PALETTE_MAX_SIZE)]
+
+
+class PalettePredDesc(C.Structure):      # SvtHipPalettePredDesc
+    _fields_ = [("map", C.c_void_p), ("colors", C.c_void_p), ("dst", C.c_void_p), ("dst_stride", C.c_uint32), ("map_width", C.c_uint16),
+                ("x", C.c_uint8), ("y", C.c_uint8), ("w", C.c_uint8), ("h", C.c_uint8), ("is_16bit", C.c_uint8), ("bit_depth", C.c_uint8),
+                ("pad_", C.c_uint8 * 4)]
+
+
+class ScClass(C.Structure):              # SvtHipScClass
+    _fields_ = [("counts_1", C.c_uint32), ("counts_2", C.c_uint32), ("blocks", C.c_uint32), ("sc_class", C.c_uint8 * 4), ("pad_", C.c_uint32 * 2)]
+
+
+# numpy views of the device records and of an array of SvtHipPalettePredDesc
+PALETTE_RECORD_DTYPE, PALETTE_PRED_DESC_DTYPE, SC_CLASS_DTYPE = record_dtype(PaletteRecord), record_dtype(PalettePredDesc), record_dtype(ScClass)
