@@ -74,7 +74,7 @@ struct B64State {
     uint32_t wg_sum;
     // integer search of the current reference
     int16_t  xc, yc, sw, sh, ox, oy;
-    int32_t  do_centre, need_zero_sad, need_hme_sad;
+    int32_t  do_centre, need_zero_sad;
     int16_t  stx, sty, stw, sth;  // block of positions whose window is currently staged (full-pel)
     int32_t  staged, restage;
     uint32_t zero_sad, hme_mv_sad;
@@ -277,6 +277,123 @@ __device__ void fp_stage(LDS &L, const uint8_t *win_org, uint32_t stride, uint32
 template <int CTRL> __device__ __forceinline__ uint32_t dpp_add(uint32_t v) {
     return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
 }
+// the sums of v over this lane's DPP quad (four lanes) and over its DPP row (16 lanes)
+__device__ __forceinline__ void dpp_quad_row_sums(uint32_t v, uint32_t &quad, uint32_t &row) {
+    quad = dpp_add<0x4E>(dpp_add<0xB1>(v));       // quad_perm [1,0,3,2], then [2,3,0,1]
+    row  = dpp_add<0x128>(dpp_add<0x124>(quad));  // row_ror:4, then row_ror:8
+}
+
+// The rules of integer_search_b64 (motion_estimation.c:1249-1586) that the staged loop over the references (fullpel_ref) and the
+// set-up of all references at once (fullpel_prepare_all, fullpel_direct_all) share.  All are inlined: this kernel has no register to
+// spare for a call (profiles/kernel_resources_me_fullpel.txt).
+
+// Search area of reference (li, ri) from the settings, the picture distance, the HME centre (xc, yc) and the reference's search-range
+// divisor (:1302 ff.); a reference whose zero-vector SAD is far below me_early_exit_th is searched at its centre alone.
+__device__ __forceinline__ void fp_search_area(const SvtHipMeParams &p, int li, int ri, int16_t xc, int16_t yc, uint32_t reduce_div,
+                                               uint32_t zz_sad, int16_t &sw, int16_t &sh_) {
+    uint16_t dist = pic_dist(p, li, ri);
+    if (!p.me_mctf)  // motion_estimation.c:1302
+        dist = scaled_dist(dist);
+    sw = (int16_t)p.me_sa_min.width, sh_ = (int16_t)p.me_sa_min.height;
+    sw  = (int16_t)MINV((sw * dist), p.me_sa_max.width);
+    sh_ = (int16_t)MINV((sh_ * dist), p.me_sa_max.height);
+    if (p.mv_sa_adj_enabled && (!p.mv_sa_adj_nearest_ref_only || ri == 0)) {
+        if (ABSV(xc) > p.mv_sa_adj_mv_size_th) sw = (int16_t)(sw * p.mv_sa_adj_sa_multiplier);
+        if (ABSV(yc) > p.mv_sa_adj_mv_size_th) sh_ = (int16_t)(sh_ * p.mv_sa_adj_sa_multiplier);
+    }
+    sw  = (int16_t)((MAXV(1u, div_small((uint32_t)sw, reduce_div)) + 7) & ~0x07u);
+    sh_ = (int16_t)MAXV(3u, div_small((uint32_t)sh_, reduce_div));
+    if (p.me_early_exit_th && zz_sad < (p.me_early_exit_th / 6))
+        sw = sh_ = 1;
+}
+
+// Window resize from the variance of the 64 8x8 SADs at the centre (:1393-1441)
+__device__ __forceinline__ void fp_resize_by_variance(const SvtHipMeParams &p, uint32_t var, int16_t &sw, int16_t &sh_) {
+    if (var > p.me_sr_mult2_th) {
+        sw  = (int16_t)((MAXV(1, sw * 3 / 2) + 7) & ~0x7);
+        sh_ = (int16_t)MAXV(1, sh_ * 3 / 2);
+    }
+    if (var < p.me_sr_div4_th) {
+        sw  = (int16_t)((MAXV(1, sw >> 2) + 7) & ~0x7);
+        sh_ = (int16_t)MAXV(1, sh_ >> 2);
+        sh_ = (int16_t)MAXV(3, sh_);
+    } else if (var < p.me_sr_div2_th) {
+        sw  = (int16_t)((MINV(sw, sw >> 1) + 7) & ~0x7);
+        sh_ = (int16_t)MINV(sh_, sh_ >> 1);
+        sh_ = (int16_t)MAXV(3, sh_);
+    }
+}
+
+// z-order index (Appendix A.1) of a 16x16 block of the b64 -> its column and row in units of 16 samples
+__device__ __forceinline__ void z16_block(uint32_t zo, uint32_t &zx, uint32_t &zy) {
+    zy = 2 * (zo >> 3) + ((zo >> 1) & 1), zx = 2 * ((zo >> 2) & 1) + (zo & 1);
+}
+
+// One wave gives the 85 (sad << 32 | raster order) minima of a reference their start: the SADs of the centre probe (position 0 of the
+// scan order, :1393-1441; `probe`: its 64 8x8 SADs in the order of p_best_sad_8x8, lane = entry) when the centre was probed, else empty.
+__device__ __forceinline__ void fp_seed_keys(uint64_t *key, const uint16_t *probe, bool centre, uint32_t sh1, uint32_t lane) {
+    if (centre) {  // uniform
+        const uint32_t v = probe[lane];
+        uint32_t       s16, s32;  // the 16x16 of this lane's quad, the 32x32 of this lane's row of 16
+        dpp_quad_row_sums(v, s16, s32);
+        const uint32_t s64 = wave_sum_all(v);
+        key[21 + lane] = (uint64_t)(v << sh1) << 32;
+        if ((lane & 3) == 0)
+            key[5 + (lane >> 2)] = (uint64_t)(s16 << sh1) << 32;
+        if ((lane & 15) == 0)
+            key[1 + (lane >> 4)] = (uint64_t)(s32 << sh1) << 32;
+        if (lane == 0)
+            key[0] = (uint64_t)(s64 << sh1) << 32;
+    } else {
+        for (uint32_t pu = lane; pu < 85; pu += 64) key[pu] = ((uint64_t)MAX_SAD_VALUE_ << 32) | 0xffffffffu;
+    }
+}
+
+// A lane of 16x16 block `zo` commits its packed (sad << POS_BITS | position) minima over the positions of one work item to the 85
+// keys: the first minimum in raster order wins, as in the reference.  ord_row: the raster order of the item's first position.
+template <uint32_t POS_BITS>
+__device__ __forceinline__ void fp_commit(uint64_t *key, uint32_t zo, const uint32_t (&k8)[4], uint32_t k16, uint32_t k32, uint32_t k64,
+                                          uint32_t ord_row, uint32_t sh1) {
+    const auto full = [&](uint32_t k) {
+        return ((unsigned long long)((k >> POS_BITS) << sh1) << 32) | (ord_row + (k & ((1u << POS_BITS) - 1u)));
+    };
+#pragma unroll
+    for (uint32_t c = 0; c < 4; c++) atomicMin((unsigned long long *)&key[21 + 4 * zo + c], full(k8[c]));
+    atomicMin((unsigned long long *)&key[5 + zo], full(k16));
+    if ((zo & 3) == 0)
+        atomicMin((unsigned long long *)&key[1 + (zo >> 2)], full(k32));
+    if (zo == 0)
+        atomicMin((unsigned long long *)&key[0], full(k64));
+}
+
+// Keys -> p_sb_best_sad / p_sb_best_mv of one reference (gs, gm: its 85 entries): lanes `lane`, `lane + nlanes`, .. take one key each.
+// Order 0 is the centre (xc, yc), order 1 + n the n-th position of the window of width sw at (ox, oy); `inv`: ceil(2^32 / sw) when
+// `use_inv`.  The 64x64 SAD also goes to *first_sad64 (the first reference's: p_sb_best_sad[0][0][0], read by later references,
+// :1359) unless that is null.  Returns, in the first lane of each wave, the wave's share of the sum of the 64 8x8 SADs (tab8x8 is a
+// permutation, :1608-1611).
+__device__ __forceinline__ uint32_t fp_store_results(const uint64_t *key, g_u32 *gs, g_u32 *gm, uint32_t *first_sad64, int xc, int yc, int ox,
+                                                     int oy, uint32_t sw, bool use_inv, uint32_t inv, uint32_t lane, uint32_t nlanes) {
+    uint32_t part = 0;
+    for (uint32_t pu = lane; pu < 85; pu += nlanes) {
+        const uint64_t k      = key[pu];
+        const uint32_t ord    = (uint32_t)k;
+        const uint32_t my_sad = (uint32_t)(k >> 32);
+        if (first_sad64 && pu == 0)
+            *first_sad64 = my_sad;
+        if (pu >= 21)
+            part += my_sad;
+        gs[pu] = my_sad;
+        if (ord != 0xffffffffu) {
+            int16_t mx = (int16_t)xc, my = (int16_t)yc;
+            if (ord != 0) {
+                const uint32_t pos = ord - 1, row = use_inv ? fast_div(pos, inv) : pos / sw;
+                mx = (int16_t)((int)(pos - row * sw) + ox), my = (int16_t)((int)row + oy);
+            }
+            gm[pu] = ((uint32_t)(uint16_t)my << 16) | (uint16_t)mx;
+        }
+    }
+    return wave_sum(part);
+}
 
 // (inlined at its three call sites: an out-of-line copy saves and restores registers through scratch memory around every call)
 template <class LDS>
@@ -287,7 +404,8 @@ __device__ __forceinline__ void fp_search(LDS &L, uint32_t pitch, uint32_t x0, u
     // lane (tid & 15) = z-order index of this lane's 16x16 block (Appendix A.1): the four 16x16 of a 32x32 are the four
     // lanes of a DPP quad, the four 32x32 are the four quads of a DPP row
     const uint32_t zo = tid & 15;
-    const uint32_t zy = 2 * (zo >> 3) + ((zo >> 1) & 1), zx = 2 * ((zo >> 2) & 1) + (zo & 1);
+    uint32_t       zx, zy;
+    z16_block(zo, zx, zy);
     const uint32_t *s = &L.src_full[(16 * zy) * 16 + 4 * zx];
     for (uint32_t base = 0; base < nitems; base += blockDim.x) {
         if (base + (tid & ~63u) >= nitems)
@@ -327,29 +445,16 @@ __device__ __forceinline__ void fp_search(LDS &L, uint32_t pitch, uint32_t x0, u
             const uint32_t c2 = ((pp < 2 ? (uint32_t)a10 : (uint32_t)(a10 >> 32)) >> lo_hi_shift) & 0xffff;
             const uint32_t c3 = ((pp < 2 ? (uint32_t)a11 : (uint32_t)(a11 >> 32)) >> lo_hi_shift) & 0xffff;
             const uint32_t s16 = c0 + c1 + c2 + c3;
-            uint32_t       s32 = dpp_add<0xB1>(s16);   // quad_perm [1,0,3,2]
-            s32                = dpp_add<0x4E>(s32);   // quad_perm [2,3,0,1]
-            uint32_t s64       = dpp_add<0x124>(s32);  // row_ror:4
-            s64                = dpp_add<0x128>(s64);  // row_ror:8
+            uint32_t       s32, s64;
+            dpp_quad_row_sums(s16, s32, s64);
             if (4 * q + pp < cw) {
                 k8[0] = min(k8[0], (c0 << 2) | pp), k8[1] = min(k8[1], (c1 << 2) | pp);
                 k8[2] = min(k8[2], (c2 << 2) | pp), k8[3] = min(k8[3], (c3 << 2) | pp);
                 k16 = min(k16, (s16 << 2) | pp), k32 = min(k32, (s32 << 2) | pp), k64 = min(k64, (s64 << 2) | pp);
             }
         }
-        if (on && k16 != ~0u) {
-            const uint32_t sh1 = sub ? 1 : 0;  // sub-sampled rows: SAD x 2 (motion_estimation.c:520-530)
-            const uint32_t ord_row = order0 + sad_mul_u24(y, order_pitch) + 4 * q;
-#define FP_KEY(k) (((unsigned long long)(((k) >> 2) << sh1) << 32) | (ord_row + ((k) & 3u)))
-#pragma unroll
-            for (uint32_t c = 0; c < 4; c++) atomicMin((unsigned long long *)&L.bestkey[21 + 4 * zo + c], FP_KEY(k8[c]));
-            atomicMin((unsigned long long *)&L.bestkey[5 + zo], FP_KEY(k16));
-            if ((zo & 3) == 0)
-                atomicMin((unsigned long long *)&L.bestkey[1 + (zo >> 2)], FP_KEY(k32));
-            if (zo == 0)
-                atomicMin((unsigned long long *)&L.bestkey[0], FP_KEY(k64));
-#undef FP_KEY
-        }
+        if (on && k16 != ~0u)  // sub-sampled rows: SAD x 2 (motion_estimation.c:520-530)
+            fp_commit<2>(L.bestkey, zo, k8, k16, k32, k64, order0 + sad_mul_u24(y, order_pitch) + 4 * q, sub ? 1 : 0);
     }
     __syncthreads();
 }
@@ -1044,23 +1149,10 @@ __device__ void fullpel_prepare_all(LDS &L, const Ctx &c) {
     const int16_t W = (int16_t)aw, H = (int16_t)ah, pad = 63;
     const int16_t ox_b = (int16_t)org_x, oy_b = (int16_t)org_y;
     if ((int)tid < nref) {
-        const int f = (int)tid, li = f < R0 ? 0 : 1, ri = f < R0 ? f : f - R0;
-        uint16_t  dist = pic_dist(p, li, ri);
-        int16_t   xc = S.sr[li][ri].hme_sc_x, yc = S.sr[li][ri].hme_sc_y;
-        int16_t   sw = (int16_t)p.me_sa_min.width, sh_ = (int16_t)p.me_sa_min.height;
-        if (!p.me_mctf)  // motion_estimation.c:1302
-            dist = scaled_dist(dist);
-        sw  = (int16_t)MINV((sw * dist), p.me_sa_max.width);
-        sh_ = (int16_t)MINV((sh_ * dist), p.me_sa_max.height);
-        if (p.mv_sa_adj_enabled && (!p.mv_sa_adj_nearest_ref_only || ri == 0)) {
-            if (ABSV(xc) > p.mv_sa_adj_mv_size_th) sw = (int16_t)(sw * p.mv_sa_adj_sa_multiplier);
-            if (ABSV(yc) > p.mv_sa_adj_mv_size_th) sh_ = (int16_t)(sh_ * p.mv_sa_adj_sa_multiplier);
-        }
-        sw  = (int16_t)((MAXV(1u, div_small((uint32_t)sw, S.reduce_div[li][ri])) + 7) & ~0x07u);
-        sh_ = (int16_t)MAXV(3u, div_small((uint32_t)sh_, S.reduce_div[li][ri]));
-        if (S.zz_sad[li][ri] < (p.me_early_exit_th / 6))
-            sw = sh_ = 1;
-        const int g = li * NR + ri;
+        const int     f = (int)tid, li = f < R0 ? 0 : 1, ri = f < R0 ? f : f - R0, g = li * NR + ri;
+        const int16_t xc = S.sr[li][ri].hme_sc_x, yc = S.sr[li][ri].hme_sc_y;
+        int16_t       sw, sh_;
+        fp_search_area(p, li, ri, xc, yc, S.reduce_div[li][ri], S.zz_sad[li][ri], sw, sh_);
         S.fp_xc[g] = xc, S.fp_yc[g] = yc, S.fp_sw[g] = sw, S.fp_sh[g] = sh_;
         S.fp_centre[g] = (uint8_t)(p.me_8x8_var_enabled && (sw * sh_ > 24));
     }
@@ -1073,8 +1165,9 @@ __device__ void fullpel_prepare_all(LDS &L, const Ctx &c) {
     uint32_t *const probe_v = L.src_s;              // [reference]
     {
         const uint32_t wv = tid >> 6, lane = tid & 63, sh1 = me_sub ? 1u : 0u;
-        const uint32_t zo = lane >> 2, cq = lane & 3;
-        const uint32_t zy = 2 * (zo >> 3) + ((zo >> 1) & 1), zx = 2 * ((zo >> 2) & 1) + (zo & 1);
+        const uint32_t cq = lane & 3;
+        uint32_t       zx, zy;
+        z16_block(lane >> 2, zx, zy);
         const uint32_t by = 2 * zy + (cq >> 1), bx = 2 * zx + (cq & 1);
         for (int f = (int)wv; f < nref; f += (int)(blockDim.x >> 6)) {
             const int li = f < R0 ? 0 : 1, ri = f < R0 ? f : f - R0, g = li * NR + ri;
@@ -1105,22 +1198,8 @@ __device__ void fullpel_prepare_all(LDS &L, const Ctx &c) {
     if ((int)tid < nref) {
         const int f = (int)tid, li = f < R0 ? 0 : 1, ri = f < R0 ? f : f - R0, g = li * NR + ri;
         int16_t   sw = S.fp_sw[g], sh_ = S.fp_sh[g], ox, oy;
-        if (S.sr[li][ri].do_ref && S.fp_centre[g]) {
-            const uint32_t var = probe_v[g];
-            if (var > p.me_sr_mult2_th) {
-                sw  = (int16_t)((MAXV(1, sw * 3 / 2) + 7) & ~0x7);
-                sh_ = (int16_t)MAXV(1, sh_ * 3 / 2);
-            }
-            if (var < p.me_sr_div4_th) {
-                sw  = (int16_t)((MAXV(1, sw >> 2) + 7) & ~0x7);
-                sh_ = (int16_t)MAXV(1, sh_ >> 2);
-                sh_ = (int16_t)MAXV(3, sh_);
-            } else if (var < p.me_sr_div2_th) {
-                sw  = (int16_t)((MINV(sw, sw >> 1) + 7) & ~0x7);
-                sh_ = (int16_t)MINV(sh_, sh_ >> 1);
-                sh_ = (int16_t)MAXV(3, sh_);
-            }
-        }
+        if (S.sr[li][ri].do_ref && S.fp_centre[g])
+            fp_resize_by_variance(p, probe_v[g], sw, sh_);
         clamp_me_window(S.fp_xc[g], S.fp_yc[g], ox_b, oy_b, W, H, pad, &sw, &sh_, &ox, &oy);
         S.fp_sw[g] = sw, S.fp_sh[g] = sh_, S.fp_ox[g] = ox, S.fp_oy[g] = oy;
         S.fp_inv[g] = make_inv_small((uint32_t)(sw > 0 ? sw : 0));
@@ -1128,69 +1207,35 @@ __device__ void fullpel_prepare_all(LDS &L, const Ctx &c) {
     __syncthreads();
 }
 
-// integer_search_b64 (motion_estimation.c:1249-1586) for one reference; all threads.  `store`: write the winners to the
-// output arrays and accumulate the 8x8 SAD sum (false when the reference is only evaluated for first_ref_sad64).  `prepared`:
-// parts 1 and 2 come from fullpel_prepare_all.
+// integer_search_b64 (motion_estimation.c:1249-1586) for one reference; all threads.  The winners go to the output arrays, the sum of
+// the 8x8 SADs to me_sad_sum.  `prepared`: parts 1 and 2 come from fullpel_prepare_all.
 template <class LDS>
-__device__ void fullpel_ref(LDS &L, const Ctx &c, int li, int ri, bool store, bool prepared) {
+__device__ void fullpel_ref(LDS &L, const Ctx &c, int li, int ri, bool prepared) {
     ME_CTX_LOCALS(c);
     const int16_t W = (int16_t)aw, H = (int16_t)ah, pad = 63;
     const int16_t ox_b = (int16_t)org_x, oy_b = (int16_t)org_y;
     const SvtHipPlane8 &rp = job.ref[li][ri].full;
+    const int g = li * NR + ri;
     if (prepared) {
-        // centre, final window and the centre probe's SADs come from fullpel_prepare_all: the 85 minima start from the probe's values
-        // (position 0 of the scan order, :1393-1441) or empty
-        const int g = li * NR + ri;
+        // centre, final window and the centre probe's SADs come from fullpel_prepare_all
         if (tid == 0) {
             S.xc = S.fp_xc[g], S.yc = S.fp_yc[g], S.sw = S.fp_sw[g], S.sh = S.fp_sh[g], S.ox = S.fp_ox[g], S.oy = S.fp_oy[g];
             S.restage = 1;
         }
-        if (S.fp_centre[g]) {  // uniform
-            if (tid < 64) {
-                const uint32_t sh1 = me_sub ? 1u : 0u;
-                const uint32_t v   = ((const uint16_t *)L.src_q)[g * 64 + (int)tid];
-                uint32_t       s16 = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
-                s16                = dpp_add<0x4E>(s16);  // quad_perm [2,3,0,1]: the 16x16 of this lane's quad
-                uint32_t s32       = dpp_add<0x124>(s16); // row_ror:4
-                s32                = dpp_add<0x128>(s32); // row_ror:8: the 32x32 of this lane's row of 16
-                const uint32_t s64 = wave_sum_all(v);
-                L.bestkey[21 + tid] = (uint64_t)(v << sh1) << 32;
-                if ((tid & 3) == 0)
-                    L.bestkey[5 + (tid >> 2)] = (uint64_t)(s16 << sh1) << 32;
-                if ((tid & 15) == 0)
-                    L.bestkey[1 + (tid >> 4)] = (uint64_t)(s32 << sh1) << 32;
-                if (tid == 0)
-                    L.bestkey[0] = (uint64_t)(s64 << sh1) << 32;
-            }
-        } else {
-            for (uint32_t pu = tid; pu < 85; pu += blockDim.x) L.bestkey[pu] = ((uint64_t)MAX_SAD_VALUE_ << 32) | 0xffffffffu;
-        }
+        if (tid < 64)
+            fp_seed_keys(L.bestkey, (const uint16_t *)L.src_q + g * 64, S.fp_centre[g], me_sub ? 1u : 0u, tid);
         __syncthreads();
     } else {
     // part 1: search area from settings + HME results
     if (tid == 0) {
-        uint16_t dist = pic_dist(p, li, ri);
-        int16_t  xc = S.sr[li][ri].hme_sc_x, yc = S.sr[li][ri].hme_sc_y;
-        int16_t  sw = (int16_t)p.me_sa_min.width, sh_ = (int16_t)p.me_sa_min.height;
-        if (!p.me_mctf)  // motion_estimation.c:1302
-            dist = scaled_dist(dist);
-        sw          = (int16_t)MINV((sw * dist), p.me_sa_max.width);
-        sh_         = (int16_t)MINV((sh_ * dist), p.me_sa_max.height);
-        if (p.mv_sa_adj_enabled && (!p.mv_sa_adj_nearest_ref_only || ri == 0)) {
-            if (ABSV(xc) > p.mv_sa_adj_mv_size_th) sw = (int16_t)(sw * p.mv_sa_adj_sa_multiplier);
-            if (ABSV(yc) > p.mv_sa_adj_mv_size_th) sh_ = (int16_t)(sh_ * p.mv_sa_adj_sa_multiplier);
-        }
-        sw  = (int16_t)((MAXV(1u, div_small((uint32_t)sw, S.reduce_div[li][ri])) + 7) & ~0x07u);
-        sh_ = (int16_t)MAXV(3u, div_small((uint32_t)sh_, S.reduce_div[li][ri]));
+        const int16_t xc = S.sr[li][ri].hme_sc_x, yc = S.sr[li][ri].hme_sc_y;
+        int16_t       sw, sh_;
+        fp_search_area(p, li, ri, xc, yc, S.reduce_div[li][ri], S.zz_sad[li][ri], sw, sh_);
         S.xc = xc, S.yc = yc, S.sw = sw, S.sh = sh_;
-        S.need_zero_sad = 0, S.need_hme_sad = 0;
-        if (p.me_early_exit_th) {
-            if (S.zz_sad[li][ri] < (p.me_early_exit_th / 6))
-                S.sw = S.sh = 1;
-        } else if ((xc != 0 || yc != 0) && p.is_ref) {
-            // check_00_center needs two 64x(h/2) SADs (:1139-1206)
-            S.need_zero_sad = 1;  // me_early_exit_th == 0 here, so zz_sad is not available
-            S.need_hme_sad  = 1;
+        S.need_zero_sad = 0;
+        if (!p.me_early_exit_th && (xc != 0 || yc != 0) && p.is_ref) {
+            // check_00_center needs two 64x(h/2) SADs (:1139-1206): me_early_exit_th == 0 here, so zz_sad is not available
+            S.need_zero_sad = 1;
             int16_t cx = xc, cy = yc;
             const int16_t RW = (int16_t)rp.width, RH = (int16_t)rp.height;
             cx = ((ox_b + cx) < -pad) ? (int16_t)(-pad - ox_b) : cx;
@@ -1256,7 +1301,8 @@ __device__ void fullpel_ref(LDS &L, const Ctx &c, int li, int ri, bool store, bo
             S.staged = 1;
         }
     }
-    for (uint32_t pu = tid; pu < 85; pu += blockDim.x) L.bestkey[pu] = ((uint64_t)MAX_SAD_VALUE_ << 32) | 0xffffffffu;
+    if (tid < 64)
+        fp_seed_keys(L.bestkey, nullptr, false, 0, tid);
     __syncthreads();
     if (S.do_centre) {
         fp_stage(L, plane_at(rp, ox_b + S.stx, oy_b + S.sty), rp.stride, (uint32_t)S.stw, (uint32_t)S.sth);
@@ -1267,21 +1313,8 @@ __device__ void fullpel_ref(LDS &L, const Ctx &c, int li, int ri, bool store, bo
             const int32_t  dv   = (int32_t)v - (int32_t)mean;
             const uint32_t ssq  = wave_sum((uint32_t)(dv * dv));
             if (tid == 0) {
-                int16_t        sw = S.sw, sh_ = S.sh;
-                const uint32_t var = ssq / 64;
-                if (var > p.me_sr_mult2_th) {
-                    sw  = (int16_t)((MAXV(1, sw * 3 / 2) + 7) & ~0x7);
-                    sh_ = (int16_t)MAXV(1, sh_ * 3 / 2);
-                }
-                if (var < p.me_sr_div4_th) {
-                    sw  = (int16_t)((MAXV(1, sw >> 2) + 7) & ~0x7);
-                    sh_ = (int16_t)MAXV(1, sh_ >> 2);
-                    sh_ = (int16_t)MAXV(3, sh_);
-                } else if (var < p.me_sr_div2_th) {
-                    sw  = (int16_t)((MINV(sw, sw >> 1) + 7) & ~0x7);
-                    sh_ = (int16_t)MINV(sh_, sh_ >> 1);
-                    sh_ = (int16_t)MAXV(3, sh_);
-                }
+                int16_t sw = S.sw, sh_ = S.sh;
+                fp_resize_by_variance(p, ssq / 64, sw, sh_);
                 S.sw = sw, S.sh = sh_;
             }
         }
@@ -1315,32 +1348,9 @@ __device__ void fullpel_ref(LDS &L, const Ctx &c, int li, int ri, bool store, bo
                     fp_search(L, fp_pitch(cw), 0, 0, cw, ch, 1 + ty * sw + tx, sw, me_sub);
                 }
         }
-        // keys -> p_sb_best_sad / p_sb_best_mv of this reference
-        uint32_t part = 0;  // this lane's share of the sum of the 64 8x8 SADs (tab8x8 is a permutation, :1608-1611)
-        for (uint32_t pu = tid; pu < 85; pu += blockDim.x) {
-            const uint64_t key    = L.bestkey[pu];
-            const uint32_t ord    = (uint32_t)key;
-            const uint32_t my_sad = (uint32_t)(key >> 32);
-            if (li == 0 && ri == 0 && pu == 0)
-                S.first_ref_sad64 = my_sad;
-            if (pu >= 21)
-                part += my_sad;
-            if (!store)
-                continue;
-            gs[(li * NR + ri) * 85 + pu] = my_sad;
-            if (ord != 0xffffffffu) {
-                int16_t mx, my;
-                if (ord == 0) {
-                    mx = S.xc, my = S.yc;
-                } else {
-                    const uint32_t pos = ord - 1, row = prepared ? fast_div(pos, S.fp_inv[li * NR + ri]) : pos / sw;
-                    mx = (int16_t)((int)(pos - row * sw) + ox), my = (int16_t)((int)row + oy);
-                }
-                gm[(li * NR + ri) * 85 + pu] = ((uint32_t)(uint16_t)my << 16) | (uint16_t)mx;
-            }
-        }
-        part = wave_sum(part);
-        if (store && (tid & 63) == 0 && part)
+        const uint32_t part = fp_store_results(L.bestkey, gs + g * 85, gm + g * 85, g == 0 ? &S.first_ref_sad64 : nullptr, S.xc, S.yc, ox, oy,
+                                               sw, prepared, prepared ? S.fp_inv[g] : 0u, tid, blockDim.x);
+        if ((tid & 63) == 0 && part)
             atomicAdd((unsigned long long *)&S.me_sad_sum[li][ri], (unsigned long long)part);
     }
     __syncthreads();
@@ -1433,37 +1443,19 @@ __device__ __forceinline__ bool fullpel_direct_all(LDS &L, const Ctx &c) {
         const uint32_t      nv = gsw - 8 * o < 8 ? gsw - 8 * o : 8;
         L.fpd_grp[tid]         = make_uint2((uint32_t)(py * (int)rp.stride + px), g | (nv << 3) | ((1 + y * gsw + 8 * o) << 8));
     }
-    // the 85 minima of every searched slot start from the centre probe's SADs (position 0 of the scan order) or empty, as in
-    // fullpel_ref: wave = slot
+    // the start of the 85 minima of every searched slot: wave = slot
     for (uint32_t g = wv; g < (uint32_t)(NL * NR); g += blockDim.x >> 6) {
         const uint32_t li = g / NR, ri = g % NR;
         if (!((int)li < nlists && ri < p.num_of_ref_pic_to_search[li] && S.sr[li][ri].do_ref))  // uniform over the wave
             continue;
-        uint64_t *const key = L.fpd_key[g];
-        if (S.fp_centre[g]) {
-            const uint32_t sh1 = me_sub ? 1u : 0u;
-            const uint32_t v   = ((const uint16_t *)L.src_q)[g * 64 + lane];
-            uint32_t       s16 = dpp_add<0xB1>(v);    // quad_perm [1,0,3,2]
-            s16                = dpp_add<0x4E>(s16);  // quad_perm [2,3,0,1]: the 16x16 of this lane's quad
-            uint32_t s32       = dpp_add<0x124>(s16); // row_ror:4
-            s32                = dpp_add<0x128>(s32); // row_ror:8: the 32x32 of this lane's row of 16
-            const uint32_t s64 = wave_sum_all(v);
-            key[21 + lane] = (uint64_t)(v << sh1) << 32;
-            if ((lane & 3) == 0)
-                key[5 + (lane >> 2)] = (uint64_t)(s16 << sh1) << 32;
-            if ((lane & 15) == 0)
-                key[1 + (lane >> 4)] = (uint64_t)(s32 << sh1) << 32;
-            if (lane == 0)
-                key[0] = (uint64_t)(s64 << sh1) << 32;
-        } else {
-            for (uint32_t pu = lane; pu < 85; pu += 64) key[pu] = ((uint64_t)MAX_SAD_VALUE_ << 32) | 0xffffffffu;
-        }
+        fp_seed_keys(L.fpd_key[g], (const uint16_t *)L.src_q + g * 64, S.fp_centre[g], me_sub ? 1u : 0u, lane);
     }
     __syncthreads();
     // the search: item = (group, 16x16 block of the source in z-order), the arithmetic of fp_search
     {
         const uint32_t zo = tid & 15;
-        const uint32_t zy = 2 * (zo >> 3) + ((zo >> 1) & 1), zx = 2 * ((zo >> 2) & 1) + (zo & 1);
+        uint32_t       zx, zy;
+        z16_block(zo, zx, zy);
         const uint32_t *s = &L.src_full[(16 * zy) * 16 + 4 * zx];
         const uint32_t sh1 = me_sub ? 1u : 0u;  // sub-sampled rows: every other row, SAD x 2 (motion_estimation.c:520-530)
         for (uint32_t item = tid; item < 16 * ngroups; item += blockDim.x) {
@@ -1485,10 +1477,8 @@ __device__ __forceinline__ bool fullpel_direct_all(LDS &L, const Ctx &c) {
                 const uint32_t c2 = (((pp & 2) ? (uint32_t)(ab[qd] >> 32) : (uint32_t)ab[qd]) >> lo_hi_shift) & 0xffff;
                 const uint32_t c3 = (((pp & 2) ? (uint32_t)(ab[qd + 1] >> 32) : (uint32_t)ab[qd + 1]) >> lo_hi_shift) & 0xffff;
                 const uint32_t s16 = c0 + c1 + c2 + c3;
-                uint32_t       s32 = dpp_add<0xB1>(s16);   // quad_perm [1,0,3,2]
-                s32                = dpp_add<0x4E>(s32);   // quad_perm [2,3,0,1]
-                uint32_t s64       = dpp_add<0x124>(s32);  // row_ror:4
-                s64                = dpp_add<0x128>(s64);  // row_ror:8
+                uint32_t       s32, s64;
+                dpp_quad_row_sums(s16, s32, s64);
                 // a position outside the window gets bits above every SAD (a 64x64 SAD of 16 rows is below 2^20) instead of a branch
                 // around its seven keys: the first position is always inside, so such a key never wins, and the positions' chains
                 // of DPP sums stay in one basic block, where they cover each other's wait states
@@ -1497,48 +1487,18 @@ __device__ __forceinline__ bool fullpel_direct_all(LDS &L, const Ctx &c) {
                 k8[2] = min(k8[2], (c2 << 3) | tag), k8[3] = min(k8[3], (c3 << 3) | tag);
                 k16 = min(k16, (s16 << 3) | tag), k32 = min(k32, (s32 << 3) | tag), k64 = min(k64, (s64 << 3) | tag);
             }
-            uint64_t *const key = L.fpd_key[g];
-#define FP_KEY(k) (((unsigned long long)(((k) >> 3) << sh1) << 32) | (ord_row + ((k) & 7u)))
-#pragma unroll
-            for (uint32_t cq = 0; cq < 4; cq++) atomicMin((unsigned long long *)&key[21 + 4 * zo + cq], FP_KEY(k8[cq]));
-            atomicMin((unsigned long long *)&key[5 + zo], FP_KEY(k16));
-            if ((zo & 3) == 0)
-                atomicMin((unsigned long long *)&key[1 + (zo >> 2)], FP_KEY(k32));
-            if (zo == 0)
-                atomicMin((unsigned long long *)&key[0], FP_KEY(k64));
-#undef FP_KEY
+            fp_commit<3>(L.fpd_key[g], zo, k8, k16, k32, k64, ord_row, sh1);
         }
     }
     __syncthreads();
-    // keys -> p_sb_best_sad / p_sb_best_mv, the sum of the 64 8x8 SADs and first_ref_sad64, as at the end of fullpel_ref: wave = slot
+    // keys -> p_sb_best_sad / p_sb_best_mv, the sum of the 64 8x8 SADs and first_ref_sad64: wave = slot
     for (uint32_t g = wv; g < (uint32_t)(NL * NR); g += blockDim.x >> 6) {
         const uint32_t li = g / NR, ri = g % NR;
         if (!((int)li < nlists && ri < p.num_of_ref_pic_to_search[li] && S.sr[li][ri].do_ref))  // uniform over the wave
             continue;
-        const int      ox = S.fp_ox[g], oy = S.fp_oy[g];
-        const uint32_t sw = (uint32_t)(S.fp_sw[g] > 0 ? S.fp_sw[g] : 0);
-        uint32_t       part = 0;
-        for (uint32_t pu = lane; pu < 85; pu += 64) {
-            const uint64_t key    = L.fpd_key[g][pu];
-            const uint32_t ord    = (uint32_t)key;
-            const uint32_t my_sad = (uint32_t)(key >> 32);
-            if (g == 0 && pu == 0)
-                S.first_ref_sad64 = my_sad;
-            if (pu >= 21)
-                part += my_sad;
-            gs[g * 85 + pu] = my_sad;
-            if (ord != 0xffffffffu) {
-                int16_t mx, my;
-                if (ord == 0) {
-                    mx = S.fp_xc[g], my = S.fp_yc[g];
-                } else {
-                    const uint32_t pos = ord - 1, row = fast_div(pos, S.fp_inv[g]);
-                    mx = (int16_t)((int)(pos - row * sw) + ox), my = (int16_t)((int)row + oy);
-                }
-                gm[g * 85 + pu] = ((uint32_t)(uint16_t)my << 16) | (uint16_t)mx;
-            }
-        }
-        part = wave_sum(part);
+        const uint32_t sw   = (uint32_t)(S.fp_sw[g] > 0 ? S.fp_sw[g] : 0);
+        const uint32_t part = fp_store_results(L.fpd_key[g], gs + g * 85, gm + g * 85, g == 0 ? &S.first_ref_sad64 : nullptr, S.fp_xc[g],
+                                               S.fp_yc[g], S.fp_ox[g], S.fp_oy[g], sw, true, S.fp_inv[g], lane, 64);
         if (lane == 0 && part)
             S.me_sad_sum[li][ri] += (uint64_t)part;
     }
@@ -1774,7 +1734,7 @@ __global__ __launch_bounds__(WG_THREADS, SVT_HIP_ME_WGS) void me_b64_kernel(cons
             for (int li = 0; li < nlists; ++li)
                 for (int ri = 0; ri < p.num_of_ref_pic_to_search[li]; ++ri)
                     if (S.sr[li][ri].do_ref)  // uniform
-                        fullpel_ref(L, c, li, ri, true, prepared);
+                        fullpel_ref(L, c, li, ri, prepared);
     }
     ME_PHASE(7);
     ME_STOP(7);

@@ -269,6 +269,47 @@ def test_me_frame(hip, orc, sc):
     me_cases.assert_same(want, got, str(sc))
 
 
+def mixed_fullpel_case(orc):
+    """(params, pyramids, oracle outputs) of a job in which the references of ONE b64 start and finish their full-pel search both
+    ways: reference 0 is noise (a 24 x 24 window, probed at its centre first, searched in two staged tiles), reference 1 lies
+    within -1 .. +2 of the current picture (zero-vector SAD below me_early_exit_th / 6: a 1 x 1 window, no centre probe, the winner
+    a window position), reference 2 is the `static` clip's own (probed, and the centre wins).  The plain `static` clip has no
+    1 x 1 window at this preset: its +-2 noise gives a zero-vector SAD of about 6500 against a bound of 32768 / 6 = 5461.  That
+    the clip does what it is for is checked here, from its pictures and the oracle's outputs alone."""
+    w, h, cur, l0 = 320, 192, 4, [3, 2, 1]
+    clip = me_cases.make_clip("static", w, h, 5, seed=12)
+    clip[3] = me_cases.make_clip("noise", w, h, 1, seed=13)[0]
+    near = clip[cur].astype(np.int16) + np.random.default_rng(14).integers(-1, 3, size=(h, w))
+    clip[2] = np.clip(near, 0, 255).astype(np.uint8)
+    pyrs = me_cases.build_pyramids(orc, clip)
+    prm = me_cases.scenario_params("m6_360p_tl0", cur, l0, [], 0, 1)
+    want = me_cases.run_cpu(orc.orc_me_frame_range, prm, pyrs, cur, l0, [], w, h)
+    nb = frames.b64_count(w, h)
+    do_ref = want["search_results"].reshape(nb, 2, 4, -1)[:, 0, :, 12]  # SvtHipMeSearchResult::do_ref
+    mv = want["best_mv"][:, 0]
+    mx = (mv & 0xffff).astype(np.uint16).view(np.int16).astype(np.int32)
+    my = (mv >> 16).astype(np.uint16).view(np.int16).astype(np.int32)
+    # init_zz_sad: twice the SAD of every other row (every b64 of this picture is a whole one)
+    zz = [2 * np.abs(clip[cur].astype(np.int32) - clip[poc])[0::2].reshape(h // 64, 32, w // 64, 64).sum(axis=(1, 3)).reshape(-1)
+          for poc in l0]
+    bound = prm.me_early_exit_th // 6
+    collapsed = (zz[1] < bound) & (do_ref[:, 1] == 1) & (np.ptp(mx[:, 1], axis=1) == 0) & (np.ptp(my[:, 1], axis=1) == 0)
+    probed = (zz[2] >= bound) & (do_ref[:, 2] == 1)
+    # a 24-wide tile of the staged search holds 20 rows of positions (ME_WIN_DW / fp_pitch(24) - 63), the direct search takes 9:
+    # winners 20 or more rows apart come from a window that was staged in two tiles
+    tiled = (do_ref[:, 0] == 1) & (np.ptp(my[:, 0], axis=1) >= 20)
+    assert (collapsed & tiled & probed).any(), (collapsed.tolist(), tiled.tolist(), probed.tolist())
+    return prm, pyrs, want, (cur, l0, [], w, h)
+
+
+def test_me_frame_mixed_fullpel(hip, orc):
+    """Both seeds of the 85 minima (centre probe / empty) and both decodes of a winner (order 0 / window position) among the
+    references of one b64, in the staged loop over prepared references."""
+    prm, pyrs, want, (cur, l0, l1, w, h) = mixed_fullpel_case(orc)
+    got = run_hip_me(hip, prm, pyrs, cur, l0, l1, w, h)[0]
+    me_cases.assert_same(want, got, "mixed full-pel")
+
+
 @pytest.mark.parametrize("sc", me_cases.MCTF_SCENARIOS, ids=lambda s: f"{s[0]}-{s[1]}x{s[2]}-th{s[6]}")
 def test_me_frame_mctf(hip, orc, sc):
     """ME_MCTF mode of the b64 kernel (the temporal filter's motion search) against the oracle and against
