@@ -59,6 +59,12 @@ struct PreHme {
     uint8_t  valid, pad_[7];
 };
 
+// What one HME level found for one reference: vector (full resolution units) and SAD of each of the 2 x 2 search quadrants
+struct Quads {
+    uint64_t s[2][2];
+    int16_t  x[2][2], y[2][2];
+};
+
 struct B64State {
     uint32_t org_x, org_y, b64_w, b64_h;
     SvtHipMeSearchResult sr[NL][NR];
@@ -66,9 +72,7 @@ struct B64State {
     uint32_t zz_sad[NL][NR];
     PreHme   ph[NL][NR][2];
     uint8_t  performed_phme[NL][NR][2];
-    int16_t  l0x[NL][NR][2][2], l0y[NL][NR][2][2], l1x[NL][NR][2][2], l1y[NL][NR][2][2], l2x[NL][NR][2][2],
-        l2y[NL][NR][2][2];
-    uint64_t l0s[NL][NR][2][2], l1s[NL][NR][2][2], l2s[NL][NR][2][2];
+    Quads    hme[3][NL][NR];  // [level]
     SvtHipSearchArea l0_min, l0_max;
     // scratch shared between lane 0 and the workgroup
     uint32_t wg_sum;
@@ -172,28 +176,29 @@ __device__ void wg_block_sad(LDS &L, const uint8_t *ref, uint32_t ref_stride, ui
     __syncthreads();
 }
 
-// The window clamp shared by hme_level_0/1/2 (motion_estimation.c:837-888, 940-990, 1041-1084).
-__device__ void hme_clamp(int16_t org_x, int16_t org_y, int16_t pad_w, int16_t pad_h, int16_t W, int16_t H, int16_t *pox,
-                          int16_t *poy, int16_t *pw, int16_t *ph) {
-    int16_t ox = *pox, oy = *poy, sa_w = *pw, sa_h = *ph;
-    if ((org_x + ox) < -pad_w) {
-        ox   = (int16_t)(-pad_w - org_x);
-        sa_w = (int16_t)(sa_w - (-pad_w - (org_x + ox)));
-    }
+// The search-window clamp that prehme_core (motion_estimation.c:1654-1699), hme_level_0/1/2 (:847-880, 940-990, 1041-1084) and
+// integer_search_b64 (:1479-1560) each write out: a window of sw x sh positions with its origin at (ox, oy) from the block at
+// (org_x, org_y) is clipped to the reference picture (W x H) and the pad_w / pad_h samples around it.  At the left and top edge the
+// levels move the origin in an `if` and then take (-pad - (org + origin)) off the size, the others use two conditional expressions
+// of which the second tests the origin the first has moved: with org + origin == -pad the one subtracts zero and the other's condition
+// is false, so neither changes the size there (no sum leaves the int16_t range: validate_job bounds the planes).  round8: all but
+// pre-HME round a clipped width of 8 or more down to a multiple of 8 (:864, 1504).
+__device__ __forceinline__ void clamp_window(int16_t org_x, int16_t org_y, int16_t pad_w, int16_t pad_h, int16_t W, int16_t H, bool round8,
+                                             int16_t &ox, int16_t &oy, int16_t &sw, int16_t &sh_) {
+    if ((org_x + ox) < -pad_w)
+        ox = (int16_t)(-pad_w - org_x);
     if ((org_x + ox) > W - 1)
         ox = (int16_t)(ox - ((org_x + ox) - (W - 1)));
-    if ((org_x + ox + sa_w) > W)
-        sa_w = (int16_t)MAXV(1, sa_w - ((org_x + ox + sa_w) - W));
-    sa_w = (sa_w < 8) ? sa_w : (int16_t)(sa_w & ~0x07);
-    if ((org_y + oy) < -pad_h) {
-        oy   = (int16_t)(-pad_h - org_y);
-        sa_h = (int16_t)(sa_h - (-pad_h - (org_y + oy)));
-    }
+    if ((org_x + ox + sw) > W)
+        sw = (int16_t)MAXV(1, sw - ((org_x + ox + sw) - W));
+    if (round8)
+        sw = (sw < 8) ? sw : (int16_t)(sw & ~0x07);
+    if ((org_y + oy) < -pad_h)
+        oy = (int16_t)(-pad_h - org_y);
     if ((org_y + oy) > H - 1)
         oy = (int16_t)(oy - ((org_y + oy) - (H - 1)));
-    if ((org_y + oy + sa_h) > H)
-        sa_h = (int16_t)MAXV(1, sa_h - ((org_y + oy + sa_h) - H));
-    *pox = ox, *poy = oy, *pw = sa_w, *ph = sa_h;
+    if ((org_y + oy + sh_) > H)
+        sh_ = (int16_t)MAXV(1, sh_ - ((org_y + oy + sh_) - H));
 }
 
 // Fill one search descriptor for an HME-style call (SUB_SAD/FULL_SAD argument rewrite of
@@ -223,34 +228,23 @@ __device__ void decode_result(const SH &sh, uint32_t i, bool sub, uint64_t *sad,
     *sad = s;
 }
 
-__device__ void set_quadrants(int16_t x[2][2], int16_t y[2][2], uint64_t s[2][2], int16_t vx, int16_t vy, uint64_t vs) {
-    for (int a = 0; a < 2; a++)
-        for (int b = 0; b < 2; b++) x[a][b] = vx, y[a][b] = vy, s[a][b] = vs;
+__device__ __forceinline__ void set_quadrant(Quads &q, uint32_t a, uint32_t b, int16_t vx, int16_t vy, uint64_t vs) {
+    q.x[a][b] = vx, q.y[a][b] = vy, q.s[a][b] = vs;
 }
 
-__device__ void best_quadrant(int16_t x[2][2], int16_t y[2][2], uint64_t s[2][2], int16_t *bx, int16_t *by, uint64_t *bs) {
-    *bx = x[0][0], *by = y[0][0], *bs = s[0][0];
-    if (s[1][0] < *bs) *bx = x[1][0], *by = y[1][0], *bs = s[1][0];
-    if (s[0][1] < *bs) *bx = x[0][1], *by = y[0][1], *bs = s[0][1];
-    if (s[1][1] < *bs) *bx = x[1][1], *by = y[1][1], *bs = s[1][1];
+__device__ void best_quadrant(const Quads &q, int16_t *bx, int16_t *by, uint64_t *bs) {
+    *bx = q.x[0][0], *by = q.y[0][0], *bs = q.s[0][0];
+    if (q.s[1][0] < *bs) *bx = q.x[1][0], *by = q.y[1][0], *bs = q.s[1][0];
+    if (q.s[0][1] < *bs) *bx = q.x[0][1], *by = q.y[0][1], *bs = q.s[0][1];
+    if (q.s[1][1] < *bs) *bx = q.x[1][1], *by = q.y[1][1], *bs = q.s[1][1];
 }
 
-// Final search-window clamp of integer_search_b64 (motion_estimation.c:1442-1561): window of sw x sh positions centred
-// on (xc, yc), clipped to the padded reference; returns its origin relative to the b64 and the clipped size.
-__device__ void clamp_me_window(int16_t xc, int16_t yc, int16_t ox_b, int16_t oy_b, int16_t W, int16_t H, int16_t pad, int16_t *psw,
-                                int16_t *psh, int16_t *pox, int16_t *poy) {
-    int16_t sw = *psw, sh_ = *psh;
-    int16_t ox = (int16_t)(xc - (sw >> 1)), oy = (int16_t)(yc - (sh_ >> 1));
-    ox  = ((ox_b + ox) < -pad) ? (int16_t)(-pad - ox_b) : ox;
-    sw  = ((ox_b + ox) < -pad) ? (int16_t)(sw - (-pad - (ox_b + ox))) : sw;
-    ox  = ((ox_b + ox) > W - 1) ? (int16_t)(ox - ((ox_b + ox) - (W - 1))) : ox;
-    sw  = ((ox_b + ox + sw) > W) ? (int16_t)MAXV(1, sw - ((ox_b + ox + sw) - W)) : sw;
-    sw  = (sw < 8) ? sw : (int16_t)(sw & ~0x07);
-    oy  = ((oy_b + oy) < -pad) ? (int16_t)(-pad - oy_b) : oy;
-    sh_ = ((oy_b + oy) < -pad) ? (int16_t)(sh_ - (-pad - (oy_b + oy))) : sh_;
-    oy  = ((oy_b + oy) > H - 1) ? (int16_t)(oy - ((oy_b + oy) - (H - 1))) : oy;
-    sh_ = ((oy_b + oy + sh_) > H) ? (int16_t)MAXV(1, sh_ - ((oy_b + oy + sh_) - H)) : sh_;
-    *psw = sw, *psh = sh_, *pox = ox, *poy = oy;
+// Final search window of integer_search_b64 (motion_estimation.c:1442-1561): sw x sh positions centred on (xc, yc), clipped to the
+// padded reference; returns its origin relative to the b64 and the clipped size.
+__device__ __forceinline__ void clamp_me_window(int16_t xc, int16_t yc, int16_t ox_b, int16_t oy_b, int16_t W, int16_t H, int16_t pad,
+                                                int16_t *psw, int16_t *psh, int16_t *pox, int16_t *poy) {
+    *pox = (int16_t)(xc - (*psw >> 1)), *poy = (int16_t)(yc - (*psh >> 1));
+    clamp_window(ox_b, oy_b, pad, pad, W, H, true, *pox, *poy, *psw, *psh);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -745,9 +739,7 @@ __device__ void init_state_lane0(LDS &L, const Ctx &c) {
             S.ph[i][j][k].valid = 0, S.ph[i][j][k].sad = 0, S.ph[i][j][k].col = S.ph[i][j][k].row = 0;
             S.performed_phme[i][j][k] = 0;
         }
-        set_quadrants(S.l0x[i][j], S.l0y[i][j], S.l0s[i][j], 0, 0, 0);
-        set_quadrants(S.l1x[i][j], S.l1y[i][j], S.l1s[i][j], 0, 0, 0);
-        set_quadrants(S.l2x[i][j], S.l2y[i][j], S.l2s[i][j], 0, 0, 0);
+        for (int lv = 0; lv < 3; lv++) S.hme[lv][i][j] = Quads{};
     }
 }
 
@@ -794,10 +786,10 @@ __device__ void zz_prune_lane0(LDS &L, const Ctx &c) {
     }
 }
 
-// The four searching stages (pre-HME, HME level 0 / 1 / 2) are written as a set-up part and a finish part around ONE shared
-// call of wg_multi_search in the kernel's step loop: a single inlined copy of the search (four copies do not fit the register
-// budget of 8 workgroups per CU, and an out-of-line copy saves and restores 16 registers per call through scratch memory —
-// measured 0.5 GB of extra traffic per launch).  `part` 0 = set-up (fills the descriptors and `a`), 1 = finish.
+// The four searching stages (pre-HME, HME level 0 / 1 / 2) are one round (hme_round), written as a set-up part and a finish part
+// around ONE shared call of wg_multi_search in the kernel's step loop: a single inlined copy of the search (four copies do not fit
+// the register budget of 8 workgroups per CU, and an out-of-line copy saves and restores 16 registers per call through scratch
+// memory — measured 0.5 GB of extra traffic per launch).  `part` 0 = set-up (fills the descriptors and `a`), 1 = finish.
 struct SearchArgs {
     bool            search;
     uint32_t        nd;
@@ -805,79 +797,198 @@ struct SearchArgs {
     uint32_t        row_dw, bw, bh, cap;
 };
 
-// prehme_b64 (motion_estimation.c:1792-1866) for references [f0, f1): one lane per (reference, region) sets its
-// descriptor up, ONE wg_multi_search call searches them all, the same lane decodes.  Ends with a barrier.
+// What a stage searches, apart from its rules (below): the plane that is 1 / (1 << shift) of the picture (vectors are kept in
+// full resolution units) against the source block of that scale, for 1 << lg_n descriptors per reference (the two regions of
+// pre-HME, the 2 x 2 quadrants of a level), with a window buffer of `cap` dwords: level 2 needs the full resolution source block,
+// which shares the buffer with the windows of the others (MeLds).
+enum { ST_PRE = 0, ST_L0, ST_L1, ST_L2 };
+struct StageGeom {
+    uint32_t shift, lg_n, cap;
+};
 template <class LDS>
-__device__ void prehme_round(LDS &L, const Ctx &c, int f0, int f1, bool searching, int part, SearchArgs &a) {
-    ME_CTX_LOCALS(c);
-    const int      f  = f0 + (int)(tid >> 1), si = (int)(tid & 1);
-    const int      li = f < R0 ? 0 : 1, ri = f < R0 ? f : f - R0;
-    const uint32_t nd = 2u * (uint32_t)(f1 - f0);
-    const bool     mine = tid < nd;
-    if (part == 0 && mine) {
-        PreHme     &d  = S.ph[li][ri][si];
-        SearchDesc &sd = L.sh.desc[tid];
-        sd.aux_go      = 0;
-        const SvtHipPlane8 &rp = job.ref[li][ri].sixteenth;
-        sd.sa_w = sd.sa_h = 0, sd.skip = 0, sd.ref = rp.buf, sd.ref_stride = sd.raw_stride = rp.stride;
-        if (tl > 0 || li == 0) {
-            const uint32_t factor = scaled_dist(pic_dist(p, li, ri));
-            const PreHme   o      = S.ph[0][ri][si];
-            // check_prehme_early_exit (:1763-1789)
-            if (p.me_early_exit_th && S.zz_sad[li][ri] < p.me_early_exit_th) {
-                d.col = d.row = 0, d.sad = 0, d.valid = 1;
-            } else if (p.prehme_l1_early_exit && li == 1 && o.valid &&
-                       ((o.sad < (32 * 32)) || ((ABSV(o.col) < 16) && (ABSV(o.row) < 16)))) {
-                d.col = (int16_t)-o.col, d.row = (int16_t)-o.row, d.sad = o.sad, d.valid = 1;
-            } else if (!S.sr[li][ri].do_ref) {
-                d.col = d.row = 0, d.sad = MAX_U32_;
-            } else {
-                d.sa_w = (uint16_t)MINV((uint32_t)(p.prehme_sa_min[si].width * factor), (uint32_t)p.prehme_sa_max[si].width);
-                d.sa_h = (uint16_t)MINV((uint32_t)(p.prehme_sa_min[si].height * factor), (uint32_t)p.prehme_sa_max[si].height);
-                // prehme_core (:1638-1736)
-                const int16_t ox16 = (int16_t)(((int16_t)org_x) >> 2), oy16 = (int16_t)(((int16_t)org_y) >> 2);
-                int16_t pad_w = (int16_t)rp.org_x - 1, pad_h = (int16_t)rp.org_y - 1;
-                int16_t sa_w = (int16_t)d.sa_w, sa_h = (int16_t)d.sa_h;
-                int16_t ox = -(int16_t)(sa_w >> 1), oy = -(int16_t)(sa_h >> 1);
-                const int16_t W = (int16_t)rp.width, H = (int16_t)rp.height;
-                ox   = ((ox16 + ox) < -pad_w) ? (int16_t)(-pad_w - ox16) : ox;
-                sa_w = ((ox16 + ox) < -pad_w) ? (int16_t)(sa_w - (-pad_w - (ox16 + ox))) : sa_w;
-                ox   = ((ox16 + ox) > W - 1) ? (int16_t)(ox - ((ox16 + ox) - (W - 1))) : ox;
-                sa_w = ((ox16 + ox + sa_w) > W) ? (int16_t)MAXV(1, sa_w - ((ox16 + ox + sa_w) - W)) : sa_w;
-                oy   = ((oy16 + oy) < -pad_h) ? (int16_t)(-pad_h - oy16) : oy;
-                sa_h = ((oy16 + oy) < -pad_h) ? (int16_t)(sa_h - (-pad_h - (oy16 + oy))) : sa_h;
-                oy   = ((oy16 + oy) > H - 1) ? (int16_t)(oy - ((oy16 + oy) - (H - 1))) : oy;
-                sa_h = ((oy16 + oy + sa_h) > H) ? (int16_t)MAXV(1, sa_h - ((oy16 + oy + sa_h) - H)) : sa_h;
-                const int16_t x_tl = (int16_t)(((int16_t)rp.org_x + ox16) + ox);
-                const int16_t y_tl = (int16_t)(((int16_t)rp.org_y + oy16) + oy);
-                const uint32_t bw = b64_w >> 2, bh = hme_sub ? (b64_h >> 2) >> 1 : (b64_h >> 2);
-                set_desc(sd, p, rp, x_tl, y_tl, sa_w, sa_h, p.prehme_skip_search_line && bw == 16 && bh <= 16);
-                sd.aux_x = ox, sd.aux_y = oy, sd.aux_go = 1;
-                S.performed_phme[li][ri][si] = 1;
-            }
-        } else {
-            d.col = (int16_t)-S.ph[0][ri][si].col;
-            d.row = (int16_t)-S.ph[0][ri][si].row;
-            d.sad = S.ph[0][ri][si].sad;
-        }
+__device__ __forceinline__ StageGeom stage_geom(int st) {
+    return StageGeom{st == ST_L2 ? 0u : st == ST_L1 ? 1u : 2u, st == ST_PRE ? 1u : 2u, st == ST_L2 ? LDS::WIN_DW : LDS::HME_WIN_DW};
+}
+__device__ __forceinline__ const SvtHipPlane8 &stage_plane(const SvtHipPyramid8 &y, uint32_t shift) {
+    return shift == 2 ? y.sixteenth : shift == 1 ? y.quarter : y.full;
+}
+
+// The rules of the stages for one descriptor of reference (li, ri).  Each either settles the descriptor's result without a search
+// and returns false, or gives the window to search — sa_w x sa_h positions at (ox, oy) from the block, before the clamp — and
+// returns true.
+
+// Region si of pre-HME (prehme_b64, motion_estimation.c:1792-1866): check_prehme_early_exit (:1763-1789), else the region's area
+// (:1821-1826, prehme_core :1648-1652); list 1 at temporal layer 0 mirrors list 0 (:1839-1848)
+__device__ __forceinline__ bool prehme_rules(const SvtHipMeParams &p, B64State &S, int tl, int li, int ri, uint32_t si, int16_t &sa_w,
+                                             int16_t &sa_h, int16_t &ox, int16_t &oy) {
+    PreHme      &d = S.ph[li][ri][si];
+    const PreHme o = S.ph[0][ri][si];
+    if (!(tl > 0 || li == 0)) {
+        d.col = (int16_t)-o.col, d.row = (int16_t)-o.row, d.sad = o.sad;
+    } else if (p.me_early_exit_th && S.zz_sad[li][ri] < p.me_early_exit_th) {
+        d.col = d.row = 0, d.sad = 0, d.valid = 1;
+    } else if (p.prehme_l1_early_exit && li == 1 && o.valid && ((o.sad < (32 * 32)) || ((ABSV(o.col) < 16) && (ABSV(o.row) < 16)))) {
+        d.col = (int16_t)-o.col, d.row = (int16_t)-o.row, d.sad = o.sad, d.valid = 1;
+    } else if (!S.sr[li][ri].do_ref) {
+        d.col = d.row = 0, d.sad = MAX_U32_;
+    } else {
+        const uint32_t factor = scaled_dist(pic_dist(p, li, ri));
+        d.sa_w = (uint16_t)MINV((uint32_t)(p.prehme_sa_min[si].width * factor), (uint32_t)p.prehme_sa_max[si].width);
+        d.sa_h = (uint16_t)MINV((uint32_t)(p.prehme_sa_min[si].height * factor), (uint32_t)p.prehme_sa_max[si].height);
+        sa_w = (int16_t)d.sa_w, sa_h = (int16_t)d.sa_h;
+        ox = -(int16_t)(sa_w >> 1), oy = -(int16_t)(sa_h >> 1);
+        S.performed_phme[li][ri][si] = 1;
+        return true;
     }
+    return false;
+}
+
+// get_hme_l0_search_area (:1870-1937): the area of one quadrant; hme_l0_sa is restored right after use (:2069-2073)
+__device__ __forceinline__ void hme_l0_search_area(const SvtHipMeParams &p, const B64State &S, int li, int ri, int16_t &w, int16_t &h) {
+    SvtHipSearchArea mn = S.l0_min, mx = S.l0_max;
+    if (p.enable_me_sr_adjustment && p.distance_based_hme_resizing) {
+        uint8_t is_hor = 1, is_ver = 1, is_still = 0;
+        if (p.reduce_hme_l0_sr_th_min && p.reduce_hme_l0_sr_th_max && (li || ri)) {
+            const int16_t mvx = S.hme[0][0][0].x[0][0], mvy = S.hme[0][0][0].y[0][0];
+            is_ver   = (ABSV(mvx) < p.reduce_hme_l0_sr_th_min) && (ABSV(mvy) > p.reduce_hme_l0_sr_th_max);
+            is_hor   = (ABSV(mvx) > p.reduce_hme_l0_sr_th_max) && (ABSV(mvy) < p.reduce_hme_l0_sr_th_min);
+            is_still = (ABSV(mvx) < (p.reduce_hme_l0_sr_th_min * 3)) && (ABSV(mvy) < (p.reduce_hme_l0_sr_th_min * 3));
+        }
+        uint8_t xo = 1, yo = 1;
+        if (!is_ver) yo = 2;
+        if (!is_hor) xo = 2;
+        if (p.enable_me_sr_adjustment == 2 && is_still) xo = yo = 4;
+        mn.width  = (uint16_t)(mn.width / (xo + ri));
+        mn.height = (uint16_t)(mn.height / (yo + ri));
+        mx.width  = (uint16_t)(mx.width / (xo + ri));
+        mx.height = (uint16_t)(mx.height / (yo + ri));
+    }
+    const int32_t factor = scaled_dist(pic_dist(p, li, ri));
+    w = (int16_t)div_small(mn.width, p.num_hme_sa_w);
+    w = (int16_t)MINV((((w * factor) + 15) & ~0x0F), (int32_t)((div_small(mx.width, p.num_hme_sa_w) + 15) & ~0x0Fu));
+    h = (int16_t)div_small(mn.height, p.num_hme_sa_h);
+    h = (int16_t)MINV((h * factor), (int32_t)div_small(mx.height, p.num_hme_sa_h));
+}
+
+// Quadrant (qx, qy) of HME level 0 (:1976-2106): its exits, else its share of the area (hme_level_0, :837-846)
+__device__ __forceinline__ bool hme_l0_rules(const SvtHipMeParams &p, B64State &S, int tl, int li, int ri, uint32_t qx, uint32_t qy,
+                                             int16_t &sa_w, int16_t &sa_h, int16_t &ox, int16_t &oy) {
+    Quads    &q   = S.hme[0][li][ri];
+    const int psi = S.ph[li][ri][0].sad <= S.ph[li][ri][1].sad ? 0 : 1;
+    if (p.me_early_exit_th && S.zz_sad[li][ri] < (p.me_early_exit_th >> 2)) {
+        set_quadrant(q, qx, qy, 0, 0, 0);
+    } else if (p.prev_me_stage_based_exit_th && S.performed_phme[li][ri][psi] &&
+               S.ph[li][ri][psi].sad < (p.prev_me_stage_based_exit_th >> 4)) {
+        set_quadrant(q, qx, qy, S.ph[li][ri][psi].col, S.ph[li][ri][psi].row, S.ph[li][ri][psi].sad);
+    } else if (!S.sr[li][ri].do_ref) {
+        set_quadrant(q, qx, qy, 0, 0, MAX_U32_);
+    } else if (tl > 0 || li == 0) {
+        int16_t w, h;
+        hme_l0_search_area(p, S, li, ri, w, h);
+        sa_w = (int16_t)((w + 7) & ~0x07), sa_h = h;
+        const int16_t xd = (int16_t)(sa_w * qx), yd = (int16_t)(sa_h * qy);
+        ox = (int16_t)(-(int16_t)((sa_w * p.num_hme_sa_w) >> 1) + xd);
+        oy = (int16_t)(-(int16_t)((sa_h * p.num_hme_sa_h) >> 1) + yd);
+        return true;
+    }
+    return false;
+}
+
+// The pre-HME vector replaces the worst quadrant of level 0 if it is better (:2086-2104)
+__device__ __forceinline__ void hme_l0_take_prehme(B64State &S, int li, int ri) {
+    Quads   &q   = S.hme[0][li][ri];
+    uint8_t  bw_ = 0, bh_ = 0;
+    uint64_t mx  = 0;
+    if (q.s[0][0] > mx) mx = q.s[0][0], bw_ = 0, bh_ = 0;
+    if (q.s[1][0] > mx) mx = q.s[1][0], bw_ = 1, bh_ = 0;
+    if (q.s[0][1] > mx) mx = q.s[0][1], bw_ = 0, bh_ = 1;
+    if (q.s[1][1] > mx) bw_ = 1, bh_ = 1;
+    const PreHme &d = S.ph[li][ri][S.ph[li][ri][0].sad <= S.ph[li][ri][1].sad ? 0 : 1];
+    if (d.sad < q.s[bw_][bh_])
+        set_quadrant(q, bw_, bh_, d.col, d.row, d.sad);
+}
+
+// Quadrant (qx, qy) of HME level 1 (:2111-2192) and level 2 (:2197-2247), lv = 1 | 2: the level's exits, else the level's area
+// centred on the vector the level before found for the quadrant (hme_level_1, :923-948; hme_level_2, :1025-1049)
+__device__ __forceinline__ bool hme_refine_rules(const SvtHipMeParams &p, B64State &S, uint32_t lv, int tl, int li, int ri, uint32_t qx,
+                                                 uint32_t qy, int16_t &sa_w, int16_t &sa_h, int16_t &ox, int16_t &oy) {
+    if (!(tl > 0 || li == 0))
+        return false;
+    Quads         &q  = S.hme[lv][li][ri];
+    const Quads   &pv = S.hme[lv - 1][li][ri];
+    const int16_t  px = pv.x[qx][qy], py = pv.y[qx][qy];
+    const uint64_t ps = pv.s[qx][qy];
+    if (lv == 1 && p.me_early_exit_th && S.zz_sad[li][ri] < (p.me_early_exit_th >> 2)) {
+        set_quadrant(q, qx, qy, 0, 0, 0);
+    } else if (lv == 1 && !S.sr[li][ri].do_ref) {
+        set_quadrant(q, qx, qy, 0, 0, MAX_U32_);
+    } else if (p.prev_me_stage_based_exit_th && ps < (p.prev_me_stage_based_exit_th >> (lv == 1 ? 5 : 2))) {
+        set_quadrant(q, qx, qy, px, py, ps);
+    } else {
+        const SvtHipSearchArea sa = lv == 1 ? p.hme_l1_sa : p.hme_l2_sa;
+        sa_w = (int16_t)(((int16_t)sa.width + 7) & ~0x07), sa_h = (int16_t)sa.height;
+        ox = (int16_t)(-(sa_w >> 1) + (int16_t)(px >> (2 - lv)));  // the plane's units
+        oy = (int16_t)(-(sa_h >> 1) + (int16_t)(py >> (2 - lv)));
+        return true;
+    }
+    return false;
+}
+
+// One searching stage `st` for references [f0, f1): one lane per descriptor (reference, region or quadrant) sets it up, ONE
+// wg_multi_search call searches them all, the same lane decodes.  Ends with a barrier.
+template <class LDS>
+__device__ void hme_round(LDS &L, const Ctx &c, int st, int f0, int f1, bool searching, int part, SearchArgs &a) {
+    ME_CTX_LOCALS(c);
+    const StageGeom g  = stage_geom<LDS>(st);
+    const uint32_t  nd = (uint32_t)(f1 - f0) << g.lg_n, sub = tid & ((1u << g.lg_n) - 1u), qx = sub & 1, qy = sub >> 1;
+    const bool      mine = tid < nd;
+    const int       f = f0 + (int)(tid >> g.lg_n), li = f < R0 ? 0 : 1, ri = f < R0 ? f : f - R0;
+    const uint32_t  hs = hme_sub ? 1u : 0u, bw = b64_w >> g.shift, bh = (b64_h >> g.shift) >> hs;
     if (part == 0) {
-        a = SearchArgs{searching, nd, L.src_s, hme_sub ? 8u : 4u, b64_w >> 2, hme_sub ? (b64_h >> 2) >> 1 : (b64_h >> 2), LDS::HME_WIN_DW};
+        if (mine) {
+            SearchDesc         &sd = L.sh.desc[tid];
+            const SvtHipPlane8 &rp = stage_plane(job.ref[li][ri], g.shift);
+            sd.aux_go              = 0;
+            sd.sa_w = sd.sa_h = 0, sd.skip = 0, sd.ref = rp.buf, sd.ref_stride = sd.raw_stride = rp.stride;
+            int16_t sa_w, sa_h, ox, oy;
+            // (the stage's answer is branched on where it is formed: kept in a variable, or returned by a function that picks
+            // the stage, it costs three more spilled registers)
+            if (st == ST_PRE ? prehme_rules(p, S, tl, li, ri, qx, sa_w, sa_h, ox, oy)
+                    : st == ST_L0 ? hme_l0_rules(p, S, tl, li, ri, qx, qy, sa_w, sa_h, ox, oy)
+                                  : hme_refine_rules(p, S, (uint32_t)(st - ST_L0), tl, li, ri, qx, qy, sa_w, sa_h, ox, oy)) {
+                // the block on the stage's plane; the padding the window may use: all of the down-scaled planes' but one sample
+                // (:838, 942, 1645), 63 samples of the full one (:1043)
+                const int16_t bx = (int16_t)(((int16_t)org_x) >> g.shift), by = (int16_t)(((int16_t)org_y) >> g.shift);
+                const int16_t pad_w = st == ST_L2 ? 63 : (int16_t)(rp.org_x - 1), pad_h = st == ST_L2 ? 63 : (int16_t)(rp.org_y - 1);
+                clamp_window(bx, by, pad_w, pad_h, (int16_t)rp.width, (int16_t)rp.height, st != ST_PRE, ox, oy, sa_w, sa_h);
+                const int16_t x_tl = (int16_t)(((int16_t)rp.org_x + bx) + ox);
+                const int16_t y_tl = (int16_t)(((int16_t)rp.org_y + by) + oy);
+                set_desc(sd, p, rp, x_tl, y_tl, sa_w, sa_h, st == ST_PRE && p.prehme_skip_search_line && bw == 16 && bh <= 16);
+                sd.aux_x = ox, sd.aux_y = oy, sd.aux_go = 1;
+            }
+        }
+        a = SearchArgs{searching, nd, g.shift == 2 ? L.src_s : g.shift == 1 ? L.src_q : L.src_full, (16u >> g.shift) << hs, bw, bh, g.cap};
         return;
     }
-    if (searching) {
-        if (mine && L.sh.desc[tid].aux_go) {
-            PreHme       &d    = S.ph[li][ri][si];
-            const int16_t q_ox = L.sh.desc[tid].aux_x, q_oy = L.sh.desc[tid].aux_y;
-            decode_result(L.sh, tid, hme_sub, &d.sad, &d.col, &d.row);
-            d.col = (int16_t)(d.col + q_ox);
-            d.col = (int16_t)(d.col * 4);
-            d.row = (int16_t)(d.row + q_oy);
-            d.row = (int16_t)(d.row * 4);
+    const bool go = mine && L.sh.desc[tid].aux_go;
+    if (go) {  // the winner: position in the window -> vector in full resolution units (:911-917, 1727-1734)
+        PreHme         &d  = S.ph[li][ri][qx];
+        Quads          &q  = S.hme[st == ST_PRE ? 0 : st - ST_L0][li][ri];
+        uint64_t *const rs = st == ST_PRE ? &d.sad : &q.s[qx][qy];
+        int16_t *const  rx = st == ST_PRE ? &d.col : &q.x[qx][qy], *const ry = st == ST_PRE ? &d.row : &q.y[qx][qy];
+        int16_t         mx = *rx, my = *ry;
+        decode_result(L.sh, tid, hme_sub, rs, &mx, &my);
+        *rx = (int16_t)((int16_t)(mx + L.sh.desc[tid].aux_x) * (1 << g.shift));
+        *ry = (int16_t)((int16_t)(my + L.sh.desc[tid].aux_y) * (1 << g.shift));
+        if (st == ST_PRE)
             d.valid = 1;
-        }
     }
     __syncthreads();
+    if (st == ST_L0) {  // one lane per reference
+        if (go && sub == 0 && p.prehme_enable)
+            hme_l0_take_prehme(S, li, ri);
+        __syncthreads();
+    }
 }
 
 // pre-HME based reference pruning (:1851-1865); first wave, lane = reference slot
@@ -894,201 +1005,6 @@ __device__ void phme_prune_lane0(LDS &L, const Ctx &c) {
     }
 }
 
-// HME level 0 (motion_estimation.c:1976-2106) for references [f0, f1); one lane per (reference, quadrant).  Ends with a barrier.
-template <class LDS>
-__device__ void hme_l0_round(LDS &L, const Ctx &c, int f0, int f1, int part, SearchArgs &a) {
-    ME_CTX_LOCALS(c);
-    const uint32_t nd   = (uint32_t)(f1 - f0) * 4u;
-    const bool     mine = tid < nd;
-    const int      f    = f0 + (int)(tid >> 2);
-    const uint32_t qi = tid & 3, sw_ = qi & 1, sh_ = qi >> 1;
-    const int      li = f < R0 ? 0 : 1, ri = f < R0 ? f : f - R0;
-    if (part == 0 && mine) {
-        SearchDesc         &sd = L.sh.desc[tid];
-        sd.aux_go              = 0;
-        const SvtHipPlane8 &rp = job.ref[li][ri].sixteenth;
-        sd.sa_w = sd.sa_h = 0, sd.skip = 0, sd.ref = rp.buf, sd.ref_stride = sd.raw_stride = rp.stride;
-        const int psi = S.ph[li][ri][0].sad <= S.ph[li][ri][1].sad ? 0 : 1;
-        if (p.me_early_exit_th && S.zz_sad[li][ri] < (p.me_early_exit_th >> 2)) {
-            S.l0x[li][ri][sw_][sh_] = 0, S.l0y[li][ri][sw_][sh_] = 0, S.l0s[li][ri][sw_][sh_] = 0;
-        } else if (p.prev_me_stage_based_exit_th && S.performed_phme[li][ri][psi] &&
-                   S.ph[li][ri][psi].sad < (p.prev_me_stage_based_exit_th >> 4)) {
-            S.l0x[li][ri][sw_][sh_] = S.ph[li][ri][psi].col, S.l0y[li][ri][sw_][sh_] = S.ph[li][ri][psi].row;
-            S.l0s[li][ri][sw_][sh_] = S.ph[li][ri][psi].sad;
-        } else if (!S.sr[li][ri].do_ref) {
-            S.l0x[li][ri][sw_][sh_] = 0, S.l0y[li][ri][sw_][sh_] = 0, S.l0s[li][ri][sw_][sh_] = MAX_U32_;
-        } else if (tl > 0 || li == 0) {
-            // get_hme_l0_search_area (:1870-1937); hme_l0_sa is restored right after use (:2069-2073)
-            SvtHipSearchArea mn = S.l0_min, mx = S.l0_max;
-            if (p.enable_me_sr_adjustment && p.distance_based_hme_resizing) {
-                uint8_t is_hor = 1, is_ver = 1, is_still = 0;
-                if (p.reduce_hme_l0_sr_th_min && p.reduce_hme_l0_sr_th_max && (li || ri)) {
-                    const int16_t mvx = S.l0x[0][0][0][0], mvy = S.l0y[0][0][0][0];
-                    is_ver   = (ABSV(mvx) < p.reduce_hme_l0_sr_th_min) && (ABSV(mvy) > p.reduce_hme_l0_sr_th_max);
-                    is_hor   = (ABSV(mvx) > p.reduce_hme_l0_sr_th_max) && (ABSV(mvy) < p.reduce_hme_l0_sr_th_min);
-                    is_still = (ABSV(mvx) < (p.reduce_hme_l0_sr_th_min * 3)) && (ABSV(mvy) < (p.reduce_hme_l0_sr_th_min * 3));
-                }
-                uint8_t xo = 1, yo = 1;
-                if (!is_ver) yo = 2;
-                if (!is_hor) xo = 2;
-                if (p.enable_me_sr_adjustment == 2 && is_still) xo = yo = 4;
-                mn.width  = (uint16_t)(mn.width / (xo + ri));
-                mn.height = (uint16_t)(mn.height / (yo + ri));
-                mx.width  = (uint16_t)(mx.width / (xo + ri));
-                mx.height = (uint16_t)(mx.height / (yo + ri));
-            }
-            const int32_t factor = scaled_dist(pic_dist(p, li, ri));
-            int16_t       w      = (int16_t)div_small(mn.width, p.num_hme_sa_w);
-            w = (int16_t)MINV((((w * factor) + 15) & ~0x0F), (int32_t)((div_small(mx.width, p.num_hme_sa_w) + 15) & ~0x0Fu));
-            int16_t h = (int16_t)div_small(mn.height, p.num_hme_sa_h);
-            h         = (int16_t)MINV((h * factor), (int32_t)div_small(mx.height, p.num_hme_sa_h));
-            const int16_t ox16 = (int16_t)(((int16_t)org_x) >> 2), oy16 = (int16_t)(((int16_t)org_y) >> 2);
-            // hme_level_0 (:820-920)
-            int16_t       sa_w = (int16_t)((w + 7) & ~0x07), sa_h = h;
-            const int16_t xd = (int16_t)(sa_w * sw_), yd = (int16_t)(sa_h * sh_);
-            int16_t       ox = (int16_t)(-(int16_t)((sa_w * p.num_hme_sa_w) >> 1) + xd);
-            int16_t       oy = (int16_t)(-(int16_t)((sa_h * p.num_hme_sa_h) >> 1) + yd);
-            hme_clamp(ox16, oy16, (int16_t)(rp.org_x - 1), (int16_t)(rp.org_y - 1), (int16_t)rp.width, (int16_t)rp.height, &ox,
-                      &oy, &sa_w, &sa_h);
-            const int16_t x_tl = (int16_t)(((int16_t)rp.org_x + ox16) + ox);
-            const int16_t y_tl = (int16_t)(((int16_t)rp.org_y + oy16) + oy);
-            set_desc(sd, p, rp, x_tl, y_tl, sa_w, sa_h, 0);
-            sd.aux_x = ox, sd.aux_y = oy, sd.aux_go = 1;
-        }
-    }
-    if (part == 0) {
-        a = SearchArgs{true, nd, L.src_s, hme_sub ? 8u : 4u, b64_w >> 2, hme_sub ? (b64_h >> 2) >> 1 : (b64_h >> 2), LDS::HME_WIN_DW};
-        return;
-    }
-    const bool go = mine && L.sh.desc[tid].aux_go;
-    const int16_t q_ox = L.sh.desc[tid & 31].aux_x, q_oy = L.sh.desc[tid & 31].aux_y;
-    if (go) {
-        int16_t mx = S.l0x[li][ri][sw_][sh_], my = S.l0y[li][ri][sw_][sh_];
-        decode_result(L.sh, tid, hme_sub, &S.l0s[li][ri][sw_][sh_], &mx, &my);
-        mx = (int16_t)(mx + q_ox), mx = (int16_t)(mx * 4);
-        my = (int16_t)(my + q_oy), my = (int16_t)(my * 4);
-        S.l0x[li][ri][sw_][sh_] = mx, S.l0y[li][ri][sw_][sh_] = my;
-    }
-    __syncthreads();
-    // the pre-HME vector replaces the worst quadrant if it is better (:2086-2104): one lane per reference
-    if (go && qi == 0 && p.prehme_enable) {
-        uint8_t  bw_ = 0, bh_ = 0;
-        uint64_t mx = 0;
-        if (S.l0s[li][ri][0][0] > mx) mx = S.l0s[li][ri][0][0], bw_ = 0, bh_ = 0;
-        if (S.l0s[li][ri][1][0] > mx) mx = S.l0s[li][ri][1][0], bw_ = 1, bh_ = 0;
-        if (S.l0s[li][ri][0][1] > mx) mx = S.l0s[li][ri][0][1], bw_ = 0, bh_ = 1;
-        if (S.l0s[li][ri][1][1] > mx) bw_ = 1, bh_ = 1;
-        const int si = S.ph[li][ri][0].sad <= S.ph[li][ri][1].sad ? 0 : 1;
-        if (S.ph[li][ri][si].sad < S.l0s[li][ri][bw_][bh_]) {
-            S.l0s[li][ri][bw_][bh_] = S.ph[li][ri][si].sad;
-            S.l0x[li][ri][bw_][bh_] = S.ph[li][ri][si].col;
-            S.l0y[li][ri][bw_][bh_] = S.ph[li][ri][si].row;
-        }
-    }
-    __syncthreads();
-}
-
-// HME level 1 (motion_estimation.c:2111-2192) for references [f0, f1).  Ends with a barrier.
-template <class LDS>
-__device__ void hme_l1_round(LDS &L, const Ctx &c, int f0, int f1, int part, SearchArgs &a) {
-    ME_CTX_LOCALS(c);
-    const uint32_t nd   = (uint32_t)(f1 - f0) * 4u;
-    const bool     mine = tid < nd;
-    const int      f    = f0 + (int)(tid >> 2);
-    const uint32_t qi = tid & 3, sw_ = qi & 1, sh_ = qi >> 1;
-    const int      li = f < R0 ? 0 : 1, ri = f < R0 ? f : f - R0;
-    if (part == 0 && mine) {
-        SearchDesc         &sd = L.sh.desc[tid];
-        sd.aux_go              = 0;
-        const SvtHipPlane8 &rp = job.ref[li][ri].quarter;
-        sd.sa_w = sd.sa_h = 0, sd.skip = 0, sd.ref = rp.buf, sd.ref_stride = sd.raw_stride = rp.stride;
-        if (tl > 0 || li == 0) {
-            if (p.me_early_exit_th && S.zz_sad[li][ri] < (p.me_early_exit_th >> 2)) {
-                S.l1x[li][ri][sw_][sh_] = 0, S.l1y[li][ri][sw_][sh_] = 0, S.l1s[li][ri][sw_][sh_] = 0;
-            } else if (!S.sr[li][ri].do_ref) {
-                S.l1x[li][ri][sw_][sh_] = 0, S.l1y[li][ri][sw_][sh_] = 0, S.l1s[li][ri][sw_][sh_] = MAX_U32_;
-            } else if (p.prev_me_stage_based_exit_th && S.l0s[li][ri][sw_][sh_] < (p.prev_me_stage_based_exit_th >> 5)) {
-                S.l1x[li][ri][sw_][sh_] = S.l0x[li][ri][sw_][sh_];
-                S.l1y[li][ri][sw_][sh_] = S.l0y[li][ri][sw_][sh_];
-                S.l1s[li][ri][sw_][sh_] = S.l0s[li][ri][sw_][sh_];
-            } else {
-                // hme_level_1 (:923-1022)
-                const int16_t ox4 = (int16_t)(((int16_t)org_x) >> 1), oy4 = (int16_t)(((int16_t)org_y) >> 1);
-                int16_t sa_w = (int16_t)(((int16_t)p.hme_l1_sa.width + 7) & ~0x07), sa_h = (int16_t)p.hme_l1_sa.height;
-                int16_t ox = (int16_t)(-(sa_w >> 1) + (int16_t)(S.l0x[li][ri][sw_][sh_] >> 1));
-                int16_t oy = (int16_t)(-(sa_h >> 1) + (int16_t)(S.l0y[li][ri][sw_][sh_] >> 1));
-                hme_clamp(ox4, oy4, (int16_t)(rp.org_x - 1), (int16_t)(rp.org_y - 1), (int16_t)rp.width, (int16_t)rp.height, &ox,
-                          &oy, &sa_w, &sa_h);
-                const int16_t x_tl = (int16_t)(((int16_t)rp.org_x + ox4) + ox);
-                const int16_t y_tl = (int16_t)(((int16_t)rp.org_y + oy4) + oy);
-                set_desc(sd, p, rp, x_tl, y_tl, sa_w, sa_h, 0);
-                sd.aux_x = ox, sd.aux_y = oy, sd.aux_go = 1;
-            }
-        }
-    }
-    if (part == 0) {
-        a = SearchArgs{true, nd, L.src_q, hme_sub ? 16u : 8u, b64_w >> 1, hme_sub ? (b64_h >> 1) >> 1 : (b64_h >> 1), LDS::HME_WIN_DW};
-        return;
-    }
-    const bool go = mine && L.sh.desc[tid].aux_go;
-    const int16_t q_ox = L.sh.desc[tid & 31].aux_x, q_oy = L.sh.desc[tid & 31].aux_y;
-    if (go) {
-        int16_t mx = S.l1x[li][ri][sw_][sh_], my = S.l1y[li][ri][sw_][sh_];
-        decode_result(L.sh, tid, hme_sub, &S.l1s[li][ri][sw_][sh_], &mx, &my);
-        mx = (int16_t)(mx + q_ox), mx = (int16_t)(mx * 2);
-        my = (int16_t)(my + q_oy), my = (int16_t)(my * 2);
-        S.l1x[li][ri][sw_][sh_] = mx, S.l1y[li][ri][sw_][sh_] = my;
-    }
-    __syncthreads();
-}
-
-// HME level 2 (motion_estimation.c:2197-2247) for references [f0, f1).  Ends with a barrier.
-template <class LDS>
-__device__ void hme_l2_round(LDS &L, const Ctx &c, int f0, int f1, int part, SearchArgs &a) {
-    ME_CTX_LOCALS(c);
-    const uint32_t nd   = (uint32_t)(f1 - f0) * 4u;
-    const bool     mine = tid < nd;
-    const int      f    = f0 + (int)(tid >> 2);
-    const uint32_t qi = tid & 3, sw_ = qi & 1, sh_ = qi >> 1;
-    const int      li = f < R0 ? 0 : 1, ri = f < R0 ? f : f - R0;
-    if (part == 0 && mine) {
-        SearchDesc         &sd = L.sh.desc[tid];
-        sd.aux_go              = 0;
-        const SvtHipPlane8 &rp = job.ref[li][ri].full;
-        sd.sa_w = sd.sa_h = 0, sd.skip = 0, sd.ref = rp.buf, sd.ref_stride = sd.raw_stride = rp.stride;
-        if (tl > 0 || li == 0) {
-            if (p.prev_me_stage_based_exit_th && S.l1s[li][ri][sw_][sh_] < (p.prev_me_stage_based_exit_th >> 2)) {
-                S.l2x[li][ri][sw_][sh_] = S.l1x[li][ri][sw_][sh_];
-                S.l2y[li][ri][sw_][sh_] = S.l1y[li][ri][sw_][sh_];
-                S.l2s[li][ri][sw_][sh_] = S.l1s[li][ri][sw_][sh_];
-            } else {
-                // hme_level_2 (:1025-1113)
-                int16_t sa_w = (int16_t)(((int16_t)p.hme_l2_sa.width + 7) & ~0x07), sa_h = (int16_t)p.hme_l2_sa.height;
-                int16_t ox = (int16_t)(-(sa_w >> 1) + S.l1x[li][ri][sw_][sh_]);
-                int16_t oy = (int16_t)(-(sa_h >> 1) + S.l1y[li][ri][sw_][sh_]);
-                hme_clamp((int16_t)org_x, (int16_t)org_y, 63, 63, (int16_t)rp.width, (int16_t)rp.height, &ox, &oy, &sa_w, &sa_h);
-                const int16_t x_tl = (int16_t)(((int16_t)rp.org_x + (int16_t)org_x) + ox);
-                const int16_t y_tl = (int16_t)(((int16_t)rp.org_y + (int16_t)org_y) + oy);
-                set_desc(sd, p, rp, x_tl, y_tl, sa_w, sa_h, 0);
-                sd.aux_x = ox, sd.aux_y = oy, sd.aux_go = 1;
-            }
-        }
-    }
-    if (part == 0) {
-        a = SearchArgs{true, nd, L.src_full, hme_sub ? 32u : 16u, b64_w, hme_sub ? b64_h >> 1 : b64_h, LDS::WIN_DW};
-        return;
-    }
-    const bool go = mine && L.sh.desc[tid].aux_go;
-    const int16_t q_ox = L.sh.desc[tid & 31].aux_x, q_oy = L.sh.desc[tid & 31].aux_y;
-    if (go) {
-        int16_t mx = S.l2x[li][ri][sw_][sh_], my = S.l2y[li][ri][sw_][sh_];
-        decode_result(L.sh, tid, hme_sub, &S.l2s[li][ri][sw_][sh_], &mx, &my);
-        S.l2x[li][ri][sw_][sh_] = (int16_t)(mx + q_ox);
-        S.l2y[li][ri][sw_][sh_] = (int16_t)(my + q_oy);
-    }
-    __syncthreads();
-}
-
 // set_final_seach_centre_sb (:2252-2450) + hme_prune_ref_and_adjust_sr (:2547-2588); first wave, lane = reference slot
 template <class LDS>
 __device__ void centre_prune_lane0(LDS &L, const Ctx &c) {
@@ -1103,14 +1019,8 @@ __device__ void centre_prune_lane0(LDS &L, const Ctx &c) {
         const bool taken   = p.enable_hme_flag && (from_l0 || from_l1 || from_l2);
         int16_t    hx = 0, hy = 0;
         uint64_t   hsad = 0;
-        if (taken && q.searched && (tl > 0 || q.li == 0)) {
-            if (from_l2)
-                best_quadrant(S.l2x[q.li][q.ri], S.l2y[q.li][q.ri], S.l2s[q.li][q.ri], &hx, &hy, &hsad);
-            else if (from_l1)
-                best_quadrant(S.l1x[q.li][q.ri], S.l1y[q.li][q.ri], S.l1s[q.li][q.ri], &hx, &hy, &hsad);
-            else
-                best_quadrant(S.l0x[q.li][q.ri], S.l0y[q.li][q.ri], S.l0s[q.li][q.ri], &hx, &hy, &hsad);
-        }
+        if (taken && q.searched && (tl > 0 || q.li == 0))
+            best_quadrant(S.hme[from_l2 ? 2 : from_l1 ? 1 : 0][q.li][q.ri], &hx, &hy, &hsad);
         const uint64_t last_l0 = __shfl((unsigned long long)hsad, R0 > 0 ? R0 - 1 : 0, 64);  // slot (0, R0 - 1)
         if (q.searched && !(tl > 0 || q.li == 0))
             hx = hy = 0, hsad = (taken && R0 > 0) ? last_l0 : 0;
@@ -1639,7 +1549,7 @@ __global__ __launch_bounds__(WG_THREADS, SVT_HIP_ME_WGS) void me_b64_kernel(cons
     ME_PHASE(1);
     ME_STOP(1);
     {
-        // List 1 reads list 0's pre-HME results for the l1 early exit (:1771-1781) and for the tl == 0 mirror (:1853-1860):
+        // List 1 reads list 0's pre-HME results for the l1 early exit (:1771-1781) and for the tl == 0 mirror (:1839-1848):
         // only then does it need a round of its own.  With distance-based resizing, references other than the first read
         // the first one's quadrant-(0,0) level-0 vector (get_hme_l0_search_area, :1881-1890): the first reference then
         // gets a round of its own.
@@ -1648,47 +1558,52 @@ __global__ __launch_bounds__(WG_THREADS, SVT_HIP_ME_WGS) void me_b64_kernel(cons
         const bool l2 = p.enable_hme_flag && p.enable_hme_level2_flag;
         const bool dep = p.enable_me_sr_adjustment && p.distance_based_hme_resizing && p.reduce_hme_l0_sr_th_min &&
             p.reduce_hme_l0_sr_th_max && nref > 1;
-        for (int step = 0; step < 6; step++) {
-            if (step == 2) {  // after pre-HME
-                if (pre) {
-                    phme_prune_lane0(L, c);
-                    __syncthreads();
-                }
-                ME_PHASE(2);
-                ME_STOP(2);
-            } else if (step == 4) {
-                ME_PHASE(3);
-                ME_STOP(3);
-            } else if (step == 5) {
-                ME_PHASE(4);
-                ME_STOP(4);
-                // the down-scaled stages' windows may have overwritten the full resolution source block: stage it again
-                // (the barrier that ends the last search orders the window reads before these writes)
-                if (pre || l0 || l1) {
-                    stage_sources(L, c, 1);
-                    __syncthreads();
-                }
+        // The schedule: the stage of each step, whether it runs, its references [f0, f1), and what runs before it whether it
+        // runs or not: the pre-HME pruning, a profiling / ablation mark (0: none), the full resolution source block staged again —
+        // the down-scaled stages' windows may have overwritten it (the barrier that ends the last search orders the window reads
+        // before these writes).  Step 1 searches nothing at temporal layer 0: list 1 mirrors list 0 there.
+        struct Step {
+            int  stage;
+            bool active;
+            int  f0, f1;
+            bool searching, prune;
+            int  mark;
+            bool restage;
+        };
+        const auto step_of = [&](int step) {  // (a function of the step, not an array: indexed by the loop, that would live in scratch)
+            switch (step) {  //    stage   active        f0  f1                 searching prune mark restage
+            case 0: return Step{ST_PRE, pre,          0,  split ? R0 : nref, true,     false, 0,  false};
+            case 1: return Step{ST_PRE, pre && split, R0, nref,              tl > 0,   false, 0,  false};
+            case 2: return Step{ST_L0,  l0,           0,  dep ? 1 : nref,    true,     pre,   2,  false};
+            case 3: return Step{ST_L0,  l0 && dep,    1,  nref,              true,     false, 0,  false};
+            case 4: return Step{ST_L1,  l1,           0,  nref,              true,     false, 3,  false};
+            default: return Step{ST_L2, l2,           0,  nref,              true,     false, 4,  pre || l0 || l1};
             }
-            const bool active = step == 0 ? pre : step == 1 ? (pre && split) : step == 2 ? l0 : step == 3 ? (l0 && dep) : step == 4 ? l1 : l2;
-            if (!active)
+        };
+        for (int step = 0; step < 6; step++) {
+            const Step s = step_of(step);
+            if (s.prune) {
+                phme_prune_lane0(L, c);
+                __syncthreads();
+            }
+            if (s.mark) {
+                ME_PHASE(s.mark);
+                ME_STOP(s.mark);
+            }
+            if (s.restage) {
+                stage_sources(L, c, 1);
+                __syncthreads();
+            }
+            if (!s.active)
                 continue;
-            const int f0 = step == 1 ? R0 : (step == 3 ? 1 : 0);
-            const int f1 = step == 0 ? (split ? R0 : nref) : (step == 2 ? (dep ? 1 : nref) : nref);
             SearchArgs a;
             for (int part = 0; part < 2; part++) {
-                if (step < 2)
-                    prehme_round(L, c, f0, f1, step == 0 || tl > 0, part, a);
-                else if (step < 4)
-                    hme_l0_round(L, c, f0, f1, part, a);
-                else if (step == 4)
-                    hme_l1_round(L, c, f0, f1, part, a);
-                else
-                    hme_l2_round(L, c, f0, f1, part, a);
+                hme_round(L, c, s.stage, s.f0, s.f1, s.searching, part, a);
                 if (part == 0 && a.search) {
-                    ME_SITE(step < 2 ? 0 : (step < 4 ? 1 : step - 2));
+                    ME_SITE(s.stage);
 #if SVT_HIP_ME_L1_DIRECT
                     // HME level 1 searches 8 x 3 positions per quadrant: too little reuse for a staged window (uniform choice)
-                    const int direct_rows = step == 4 ? wg_direct_plan(L.sh, a.nd, a.src, a.row_dw, a.bw, a.bh) : -1;
+                    const int direct_rows = s.stage == ST_L1 ? wg_direct_plan(L.sh, a.nd, a.src, a.row_dw, a.bw, a.bh) : -1;
                     if (direct_rows >= 0)
                         wg_direct_search(L.sh, a.nd, (uint32_t)direct_rows, a.src, a.row_dw, a.bh);
                     else
@@ -1698,7 +1613,7 @@ __global__ __launch_bounds__(WG_THREADS, SVT_HIP_ME_WGS) void me_b64_kernel(cons
                         // HME level 0 (and pre-HME, in builds with bit 1 of the switch) searches a 16-sample-wide block on the 1/16
                         // plane: the small and the flat areas are read from the plane ahead of the staged passes, which then hold
                         // the tall and the large ones only, and do not run when nothing is left for them (uniform)
-                        const int s16 = step < 4 && ((step < 2 ? 2 : 1) & SVT_HIP_ME_S16_DIRECT) != 0
+                        const int s16 = s.stage <= ST_L0 && ((s.stage == ST_PRE ? 2 : 1) & SVT_HIP_ME_S16_DIRECT) != 0
                             ? wg_s16_plan(L.sh, a.nd, a.src, a.row_dw, a.bw, a.bh) : -1;
                         if (s16 >= 0)
                             wg_s16_search(L.sh, a.src, a.row_dw, a.bh);

@@ -2,6 +2,7 @@
 import ctypes as C
 import json
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -143,6 +144,70 @@ def call_sad_loop(fn, prm, src, refw):
        C.c_uint32(prm["bh"]), C.c_uint32(prm["bw"]), C.byref(best), C.byref(x), C.byref(y), C.c_uint32(prm["stride"]),
        C.c_uint8(prm["skip"]), C.c_int16(prm["sw"]), C.c_int16(prm["sh"]))
     return int(best.value), int(x.value), int(y.value)
+
+
+# Parameter variants of the b64 kernel: each sets a few parameters (`over`) on top of a parameter set and is there for one rule of the
+# kernel.  tests/test_gpu_me.py compares every variant bit-exactly with the oracle; tests/test_me_variants_reach.py shows, on the
+# oracle alone, that the variant reaches its rule: the outputs differ from those with `over` undone (`base` holds what both runs set).
+VARIANT_CLIP = ("blocks", 384, 256, 77, "m6_360p_tl2")  # (kind, width, height, seed, parameter key)
+VARIANT_REFS = (2, [1, 0], [3, 4])                       # (current picture, list 0, list 1); temporal layer 2, a reference picture
+# 7 x 4 b64, the right and bottom ones partial; the pan gives the first reference's level-0 vector a length the thresholds can split
+FASTPAN_CLIP = ("fastpan", 392, 232, 65, "m2_360p_tl2")
+FASTPAN_M6_CLIP = FASTPAN_CLIP[:4] + ("m6_360p_tl2",)
+
+
+class Variant(NamedTuple):
+    over: dict
+    base: dict = {}
+    clip: tuple = VARIANT_CLIP
+    refs: tuple = VARIANT_REFS
+
+
+PARAM_VARIANTS = [
+    Variant(dict(hme_search_method=1, me_search_method=1)),
+    Variant(dict(prehme_l1_early_exit=1, prehme_skip_search_line=1)),
+    Variant(dict(enable_me_sr_adjustment=2, me_early_exit_th=0)),
+    # (on the `blocks` clip no HME centre is long enough for the adjustment to change a window)
+    Variant(dict(mv_sa_adj_enabled=1, mv_sa_adj_mv_size_th=3, mv_sa_adj_sa_multiplier=2), dict(me_early_exit_th=0), FASTPAN_M6_CLIP),
+    Variant(dict(prev_me_stage_based_exit_th=64 * 64 * 4)),
+    # the level-0 area rule from the first reference's vector (is_hor / is_ver / is_still) and the round of its own that the
+    # first reference gets for it (on the `blocks` clip with m6_360p_tl2 the round-up of the 16 x 16 minimum areas absorbs the divisor)
+    Variant(dict(reduce_hme_l0_sr_th_min=8, reduce_hme_l0_sr_th_max=100),
+            dict(enable_me_sr_adjustment=1, distance_based_hme_resizing=1), FASTPAN_CLIP),
+    Variant(dict(enable_me_sr_adjustment=2), dict(enable_me_sr_adjustment=1, distance_based_hme_resizing=1,
+                                                  reduce_hme_l0_sr_th_min=8, reduce_hme_l0_sr_th_max=100), FASTPAN_CLIP),
+    Variant(dict(only_l_bwd=1, prune_me_candidates_th=0)),
+    Variant(dict(me_safe_limit_zz_th=200000, similar_brightness_refs=1, hierarchical_levels=2)),
+    Variant(dict(enable_hme_level1_flag=0, prehme_enable=0)),
+    Variant(dict(enable_hme_flag=0, enable_hme_level0_flag=0, enable_hme_level1_flag=0, prehme_enable=0)),
+    # (on the `blocks` clip the variance of the centre probe resizes no window that holds a winner)
+    Variant(dict(me_8x8_var_enabled=0), {}, FASTPAN_M6_CLIP),
+    Variant(dict(enable_me_8x8=0)),
+    # the search centre from level 1, from level 0; pre-HME off alone
+    Variant(dict(enable_hme_level2_flag=0)),
+    Variant(dict(enable_hme_level2_flag=0, enable_hme_level1_flag=0)),
+    Variant(dict(prehme_enable=0)),
+    # other reference lists: one reference, one per list
+    Variant({}, {}, VARIANT_CLIP[:4] + ("m8_360p_tl2",), (2, [1], [])),
+    Variant(dict(use_best_unipred_cand_only=1), {}, VARIANT_CLIP[:4] + ("m8_360p_tl2",), (2, [1], [3])),
+]
+
+
+def variant_clip(orc, v, _cache={}):
+    """(pyramids, width, height) of the variant's clip; built once per clip"""
+    kind, w, h, seed, _ = v.clip
+    if v.clip[:4] not in _cache:
+        _cache[v.clip[:4]] = build_pyramids(orc, make_clip(kind, w, h, 5, seed=seed))
+    return _cache[v.clip[:4]], w, h
+
+
+def variant_params(v, undo=False, **more):
+    cur, l0, l1 = v.refs
+    prm = scenario_params(v.clip[4], cur, l0, l1, 2, 1)
+    for k, val in {**v.base, **({} if undo else v.over), **more}.items():
+        assert hasattr(prm, k), k
+        setattr(prm, k, val)
+    return prm
 
 
 # ME_MCTF mode (the temporal filter's call of svt_aom_motion_estimation_b64, temporal_filtering.c:3075): one list, one

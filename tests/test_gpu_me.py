@@ -341,37 +341,14 @@ def test_me_frame_golden(hip, orc):
 
 
 def test_me_frame_param_variants(hip, orc):
-    w, h, cur, l0, l1 = 384, 256, 2, [1, 0], [3, 4]
-    clip = me_cases.make_clip("blocks", w, h, 5, seed=77)
-    pyrs = me_cases.build_pyramids(orc, clip)
-    variants = [
-        dict(hme_search_method=1, me_search_method=1),
-        dict(prehme_l1_early_exit=1, prehme_skip_search_line=1),
-        dict(enable_me_sr_adjustment=2, me_early_exit_th=0),
-        dict(me_early_exit_th=0, mv_sa_adj_enabled=1, mv_sa_adj_mv_size_th=3, mv_sa_adj_sa_multiplier=2),
-        dict(prev_me_stage_based_exit_th=64 * 64 * 4),
-        dict(reduce_hme_l0_sr_th_min=8, reduce_hme_l0_sr_th_max=100),
-        dict(only_l_bwd=1, prune_me_candidates_th=0),
-        dict(me_safe_limit_zz_th=200000, similar_brightness_refs=1, hierarchical_levels=2),
-        dict(enable_hme_level1_flag=0, prehme_enable=0),
-        dict(enable_hme_flag=0, enable_hme_level0_flag=0, enable_hme_level1_flag=0, prehme_enable=0),
-        dict(me_8x8_var_enabled=0),
-        dict(enable_me_8x8=0),
-    ]
-    for v in variants:
-        prm = me_cases.scenario_params("m6_360p_tl2", cur, l0, l1, 2, 1)
-        for k, val in v.items():
-            setattr(prm, k, val)
+    """Every variant of me_cases.PARAM_VARIANTS bit-exact against the oracle (that each reaches its rule: test_me_variants_reach.py)."""
+    for v in me_cases.PARAM_VARIANTS:
+        pyrs, w, h = me_cases.variant_clip(orc, v)
+        cur, l0, l1 = v.refs
+        prm = me_cases.variant_params(v)
         want = me_cases.run_cpu(orc.orc_me_frame_range, prm, pyrs, cur, l0, l1, w, h)
         got = run_hip_me(hip, prm, pyrs, cur, l0, l1, w, h)[0]
         me_cases.assert_same(want, got, str(v))
-    for (ll0, ll1, extra) in (([1], [], {}), ([1], [3], dict(use_best_unipred_cand_only=1))):
-        prm = me_cases.scenario_params("m8_360p_tl2", cur, ll0, ll1, 2, 1)
-        for k, val in extra.items():
-            setattr(prm, k, val)
-        want = me_cases.run_cpu(orc.orc_me_frame_range, prm, pyrs, cur, ll0, ll1, w, h)
-        got = run_hip_me(hip, prm, pyrs, cur, ll0, ll1, w, h)[0]
-        me_cases.assert_same(want, got, str((ll0, ll1, extra)))
 
 
 def test_me_frames_batch_is_deterministic(hip, orc):

@@ -18,7 +18,7 @@ CASES = {
     "right_edge": ("noise", 200, 128, 5, "m8_360p_tl2", 2, [1, 0], [3, 4], 2, {}),
     # every SAD ties: the first minimum in raster order has to survive the lane split and the cross-lane sum
     "ties": ("flat", 128, 128, 5, "m8_360p_tl2", 2, [1, 0], [3, 4], 2, {}),
-    # hme_clamp clips windows at all four borders: fewer than 8 columns / 3 rows, negative origins
+    # clamp_window clips windows at all four borders: fewer than 8 columns / 3 rows, negative origins
     "clipped": ("fastpan", 256, 192, 5, "m8_360p_tl2", 2, [1, 0], [3, 4], 2, {}),
     # full SAD: block rows step by the raw stride and there are 32 of them (16-bit accumulators: 8 rows at most)
     "full_sad": ("fastpan", 256, 192, 5, "m8_360p_tl2", 2, [1, 0], [3, 4], 2, dict(hme_search_method=1, me_search_method=1)),

@@ -1,7 +1,7 @@
 """GPU parity of the direct search of 16-sample-wide blocks (wg_s16_search: HME level 0 and the wide pre-HME region read from the
 1/16 reference plane, descriptor by descriptor, beside descriptors of the same call that stay staged) against the oracle,
-bit-exact: small pictures chosen for the paths of that search.  `descriptor_shapes` restates the geometry of prehme_round /
-hme_l0_round, their zero-MV-SAD exits and the kernel's shape test on the host, so that test_cases_reach_their_paths can say
+bit-exact: small pictures chosen for the paths of that search.  `descriptor_shapes` restates the geometry of hme_round for pre-HME
+and level 0 (prehme_rules, hme_l0_rules), their zero-MV-SAD exits and the kernel's shape test on the host, so that test_cases_reach_their_paths can say
 without a GPU how many descriptors of every case are searched and by which path.  The library as built sends level 0 there
 (SVT_HIP_ME_S16_DIRECT = 1); the wide pre-HME region takes the same path in builds with bit 1 of that switch, which these cases
 cover as well: a build is tested by naming it in SVTAV1_HIP_LIB."""
@@ -75,7 +75,7 @@ def scaled_dist(d):
 
 
 def clamp_axis(org, o, sa, pad, size, round8):
-    """One axis of prehme_core / hme_clamp: (origin offset, area) of a search area clipped by the padded plane."""
+    """One axis of clamp_window: (origin offset, area) of a search area clipped by the padded plane."""
     if org + o < -pad:  # (the origin moves; the area keeps its size, as in the reference)
         o = -pad - org
     if org + o > size - 1:
@@ -98,7 +98,7 @@ def descriptor_shapes(prm, width, height, l0, l1, clip):
     """Every descriptor the pre-HME and level-0 rounds set up, with the exits that follow from the zero-MV SADs of the clip:
     (stage, b64 column, b64 row, list, reference, block width, block rows, sa_w, sa_h, x origin offset, skip, direct, searched).
     `direct` is the kernel's shape test on the area the descriptor gets when it is searched; `searched` is false when the
-    zz-SAD early exit of its stage (check_prehme_early_exit, the head of hme_l0_round) or the zz-SAD pruning of the reference
+    zz-SAD early exit of its stage (check_prehme_early_exit, the head of hme_l0_rules) or the zz-SAD pruning of the reference
     (zz_prune_lane0) takes the search away.  The pruning behind pre-HME (phme_prune_lane0) depends on search results and is not
     restated: it can take further level-0 searches of references other than the first away, never add one."""
     th, searching = prm.me_early_exit_th, lambda li: prm.temporal_layer_index > 0 or li == 0  # noqa: E731
