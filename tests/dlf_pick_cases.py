@@ -9,7 +9,7 @@ from collections import namedtuple
 import numpy as np
 
 import lf_cases as L
-from lf_cases import P
+from lf_cases import BH, BW, INTER_MODES_WITH_DELTA, TX, P, flat_mode_info, max_depth_of, split_tx  # noqa: F401
 from svtav1_hip import abi
 
 MAX_LEVEL = abi.DLF_MAX_LEVEL
@@ -32,45 +32,6 @@ CASES = [
     Case("tiles_8bit_harsh", 200, 136, 8, 0, 64, 2, 24, 0, 0, 1, 0, 7, (15, 40, 16), "aligned", 9),
 ]
 CASE = {c.name: c for c in CASES}
-
-BW = {v: k[0] for k, v in L.BSIZE.items()}
-BH = {v: k[1] for k, v in L.BSIZE.items()}
-TX = {(4, 4): 0, (8, 8): 1, (16, 16): 2, (32, 32): 3, (64, 64): 4, (4, 8): 5, (8, 4): 6, (8, 16): 7, (16, 8): 8, (16, 32): 9, (32, 16): 10,
-      (32, 64): 11, (64, 32): 12, (4, 16): 13, (16, 4): 14, (8, 32): 15, (32, 8): 16, (16, 64): 17, (64, 16): 18}   # TxSize by (w, h)
-INTER_MODES_WITH_DELTA = (13, 14, 16, 17, 18, 19, 20, 21, 22, 24)     # mode_lf_lut == 1: every inter mode but the two GLOBAL ones
-
-
-def split_tx(w, h):
-    """One step of the transform split of the AV1 specification: a square halves, 2:1 becomes the square of its short side, 4:1 halves
-    its long side."""
-    if w == h:
-        return max(w // 2, 4), max(h // 2, 4)
-    if w > h:
-        return (w // 2, h) if w == 4 * h else (h, h)
-    return (w, h // 2) if h == 4 * w else (w, w)
-
-
-def max_depth_of(bsize):
-    """The depths a block can have: none above 64 samples or for the 4x8 / 8x4 / 4x4 blocks, one for 8x8, two otherwise."""
-    w, h = BW[bsize], BH[bsize]
-    return 0 if max(w, h) > 64 or w * h <= 32 else 1 if (w, h) == (8, 8) else 2
-
-
-def flat_mode_info(minfo, mi_rows, mi_stride):
-    """The SvtHipLfMi grid of a partition (what INTEGRATION's gather loop builds), tx_depth limited to what the block can have in
-    `minfo` itself.  test_dlf_pick_abi.py checks the grid against the reference's gather (ref_lf_gather)."""
-    flat = np.zeros((mi_rows, mi_stride), abi.LF_MI_DTYPE)
-    for r in range(mi_rows):
-        for c in range(mi_stride):
-            b = int(minfo["bsize"][r, c])
-            minfo["tx_depth"][r, c] = min(int(minfo["tx_depth"][r, c]), max_depth_of(b))
-            skip_inter = bool(minfo["skip"][r, c]) and minfo["ref_frame0"][r, c] > 0
-            w, h = min(BW[b], 64), min(BH[b], 64)
-            for _ in range(0 if skip_inter else int(minfo["tx_depth"][r, c])):
-                w, h = split_tx(w, h)
-            flat[r, c] = (b, TX[(w, h)], TX[(min(max(BW[b] // 2, 4), 32), min(max(BH[b] // 2, 4), 32))], skip_inter,
-                          minfo["segment_id"][r, c], minfo["ref_frame0"][r, c], int(minfo["mode"][r, c]) in INTER_MODES_WITH_DELTA, 0)
-    return flat
 
 
 class Inputs:

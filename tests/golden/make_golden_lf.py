@@ -34,8 +34,8 @@ print("cdef.npz:", len(store), "arrays", os.path.getsize(os.path.join(HERE, "cde
 
 # ---- deblocking: the REAL svt_av1_loop_filter_frame on seeded pictures / partitions (lf_cases.golden_dlf_inputs)
 store = {}
-for key, w, h, bd, is16, variant, sb, seed in L.GOLDEN_DLF:
-    mi_cols, mi_rows, mi_stride, minfo, hdr, planes = L.golden_dlf_inputs(w, h, bd, is16, variant, sb, seed)
+for key, w, h, bd, is16, variant, sb, seed, content in L.GOLDEN_DLF:
+    mi_cols, mi_rows, mi_stride, minfo, hdr, planes = L.golden_dlf_inputs(w, h, bd, is16, variant, sb, seed, content)
     out = [p.copy() for p in planes]
     flat, lvl = L.ref_deblock(ref, out, w, h, minfo, mi_stride, mi_rows, mi_cols, hdr, bd, is16, sb)
     store[key + "_mi"], store[key + "_lvl"] = flat.view(np.uint8).reshape(mi_rows, mi_stride, 8), lvl

@@ -16,8 +16,8 @@ import pyorc  # noqa: E402
 
 ref = pyorc.ref()
 out = {}
-for name in R.CASES:
-    case = R.make_case(name)
+for name in list(R.CASES) + list(R.GOLDEN_CONTENT):
+    case = R.make_case(name) if name in R.CASES else R.make_content_case(*R.GOLDEN_CONTENT[name])
     arr, outs = R.lr_planes(case)
     assert ref.ref_restoration_filter_frame(arr, C.c_uint32(len(case))) == 0
     for p, (o, c) in enumerate(zip(outs, case)):

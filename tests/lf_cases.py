@@ -293,6 +293,126 @@ def random_mode_info(rng, mi_rows, mi_cols, mi_stride, sb=64, p_skip=0.45, p_int
     return f
 
 
+BW = {v: k[0] for k, v in BSIZE.items()}
+BH = {v: k[1] for k, v in BSIZE.items()}
+TX = {(4, 4): 0, (8, 8): 1, (16, 16): 2, (32, 32): 3, (64, 64): 4, (4, 8): 5, (8, 4): 6, (8, 16): 7, (16, 8): 8, (16, 32): 9, (32, 16): 10,
+      (32, 64): 11, (64, 32): 12, (4, 16): 13, (16, 4): 14, (8, 32): 15, (32, 8): 16, (16, 64): 17, (64, 16): 18}   # TxSize by (w, h)
+TXW = {v: k[0] for k, v in TX.items()}
+TXH = {v: k[1] for k, v in TX.items()}
+TX_UV = sorted({TX[(min(max(w // 2, 4), 32), min(max(h // 2, 4), 32))] for w, h in BSIZE})    # the 14 chroma sizes of 4:2:0
+INTER_MODES_WITH_DELTA = (13, 14, 16, 17, 18, 19, 20, 21, 22, 24)     # mode_lf_lut == 1: every inter mode but the two GLOBAL ones
+
+
+def split_tx(w, h):
+    """One step of the transform split of the AV1 specification: a square halves, 2:1 becomes the square of its short side, 4:1 halves
+    its long side."""
+    if w == h:
+        return max(w // 2, 4), max(h // 2, 4)
+    if w > h:
+        return (w // 2, h) if w == 4 * h else (h, h)
+    return (w, h // 2) if h == 4 * w else (w, w)
+
+
+def max_depth_of(bsize):
+    """The depths a block can have: none above 64 samples or for the 4x8 / 8x4 / 4x4 blocks, one for 8x8, two otherwise."""
+    w, h = BW[bsize], BH[bsize]
+    return 0 if max(w, h) > 64 or w * h <= 32 else 1 if (w, h) == (8, 8) else 2
+
+
+def flat_mode_info(minfo, mi_rows, mi_stride):
+    """The SvtHipLfMi grid of a partition (what INTEGRATION's gather loop builds), tx_depth limited to what the block can have in
+    `minfo` itself.  test_dlf_pick_abi.py checks the grid against the reference's gather (ref_lf_gather)."""
+    flat = np.zeros((mi_rows, mi_stride), abi.LF_MI_DTYPE)
+    for r in range(mi_rows):
+        for c in range(mi_stride):
+            b = int(minfo["bsize"][r, c])
+            minfo["tx_depth"][r, c] = min(int(minfo["tx_depth"][r, c]), max_depth_of(b))
+            skip_inter = bool(minfo["skip"][r, c]) and minfo["ref_frame0"][r, c] > 0
+            w, h = min(BW[b], 64), min(BH[b], 64)
+            for _ in range(0 if skip_inter else int(minfo["tx_depth"][r, c])):
+                w, h = split_tx(w, h)
+            flat[r, c] = (b, TX[(w, h)], TX[(min(max(BW[b] // 2, 4), 32), min(max(BH[b] // 2, 4), 32))], skip_inter,
+                          minfo["segment_id"][r, c], minfo["ref_frame0"][r, c], int(minfo["mode"][r, c]) in INTER_MODES_WITH_DELTA, 0)
+    return flat
+
+
+# ---- the catalogue partition.  A layout is a nested tuple: a partition type of the AV1 specification followed by the transform
+# depths of its blocks in coding order (0 where left out), or "split" followed by the layouts of the four quarters.  A 64x64
+# region takes its layout by its place in the picture, LAYOUTS64[(row * whole regions per row + column) % 12].  Together the
+# twelve hold every block size up to 64x64 with every depth it can have.  On a picture four regions wide the first two rows
+# alone hold every size at depth 0 (transform = block) at a place with a left and at one with an upper neighbour: the
+# regions that a block fills from side to side (5, 1, 2) or from top to bottom (5, 4, 6) lie off the left or upper border, the
+# smaller ones in the right or lower quarters.  No region is like the one beside or below it.
+_Q16 = ("split", ("horz", 0, 1), ("vert", 0, 1), ("horz4", 0, 1, 2, 0), ("vert4", 0, 1, 2, 0))   # 16x8, 8x16, 16x4, 4x16
+_Q8 = ("split", ("horz_a", 0, 1, 2), ("vert_a", 0, 1, 2), ("split", ("none", 1), ("horz",), ("vert",), ("split",) + (("none",),) * 4),
+       ("none", 0))                                                                               # 8x8 .. 4x4, 16x8 / 8x16 depth 2, 16x16
+LAYOUTS64 = [
+    ("split", ("horz_b", 2, 1, 2), ("vert_b", 2, 1, 2), ("horz4", 1, 2, 0, 1), ("none", 0)),
+    ("horz", 1, 0), ("horz4", 0, 1, 2, 0), ("split", ("vert4", 1, 2, 0, 1), ("none", 1), _Q16, _Q8),
+    ("vert", 1, 0), ("none", 0), ("vert4", 0, 1, 2, 0), ("split", ("horz", 0, 1), ("vert", 0, 1), ("horz4", 0, 1, 2, 0), ("vert4", 0, 1, 2, 0)),
+    ("none", 1), ("horz_a", 1, 2, 2), ("none", 2), ("vert_a", 0, 2, 2)]
+LAYOUTS128 = [("split",), ("split",), ("vert",), ("none",), ("horz",), ("split",)]      # per superblock, in raster order
+
+
+def _leaves(layout, x, y, s):
+    """The (x, y, w, h, depth) blocks of one layout of a square of `s` samples at (x, y), in coding order."""
+    k, hs, qs = layout[0], s // 2, s // 4
+    if k == "split":
+        return [b for i, sub in enumerate(layout[1:]) for b in _leaves(sub, x + (i & 1) * hs, y + (i >> 1) * hs, hs)]
+    blocks = {"none": [(x, y, s, s)], "horz": [(x, y, s, hs), (x, y + hs, s, hs)], "vert": [(x, y, hs, s), (x + hs, y, hs, s)],
+              "horz4": [(x, y + i * qs, s, qs) for i in range(4)], "vert4": [(x + i * qs, y, qs, s) for i in range(4)],
+              "horz_a": [(x, y, hs, hs), (x + hs, y, hs, hs), (x, y + hs, s, hs)],
+              "horz_b": [(x, y, s, hs), (x, y + hs, hs, hs), (x + hs, y + hs, hs, hs)],
+              "vert_a": [(x, y, hs, hs), (x, y + hs, hs, hs), (x + hs, y, hs, s)],
+              "vert_b": [(x, y, hs, s), (x + hs, y, hs, hs), (x + hs, y + hs, hs, hs)]}[k]
+    return [b + (d,) for b, d in zip(blocks, layout[1:] + (0,) * len(blocks))]
+
+
+def catalogue_mode_info(mi_rows, mi_cols, mi_stride, sb, seed, p_skip=0.45, p_intra=0.3):
+    """A deterministic partition: every 64x64 region has the layout and the transform depths that LAYOUTS64 gives its place,
+    and with sb == 128 the superblocks walk LAYOUTS128 in raster order, "split" standing for four such regions.  The first
+    block of each size above 64 samples is a skipped inter block (its 64-sample interior transform edges are the ones
+    set_lpf_parameters refuses); the other fields (skip, reference, mode, segment) are seeded random as in random_mode_info."""
+    rng = np.random.default_rng(seed)
+    f = {k: np.zeros((mi_rows, mi_stride), np.uint8) for k in ("bsize", "tx_depth", "skip", "ref_frame0", "mode", "segment_id")}
+    W, H = mi_cols * 4, mi_rows * 4
+    big = set()
+
+    def leaf(x, y, w, h, depth):
+        intra, skip = rng.random() < p_intra, int(rng.random() < p_skip)     # drawn for every block, inside the picture or not
+        ref0, mode_intra, mode_inter, seg = int(rng.integers(1, 8)), int(rng.integers(0, 13)), int(rng.integers(13, 25)), int(rng.integers(0, 8))
+        if x >= W or y >= H:
+            return
+        b = BSIZE[(w, h)]
+        if max(w, h) > 64 and b not in big:
+            big.add(b)
+            intra, skip = False, 1
+        vals = dict(bsize=b, tx_depth=min(depth, max_depth_of(b)), skip=skip, ref_frame0=0 if intra else ref0,
+                    mode=mode_intra if intra else mode_inter, segment_id=seg)
+        for k, v in vals.items():
+            f[k][y // 4:min((y + h) // 4, mi_rows), x // 4:min((x + w) // 4, mi_cols)] = v
+
+    def region(x, y):
+        for b in _leaves(LAYOUTS64[(y // 64 * max(W // 64, 1) + x // 64) % len(LAYOUTS64)], x, y, 64):
+            leaf(*b)
+
+    n_sb = 0
+    for y in range(0, H, sb):
+        for x in range(0, W, sb):
+            if sb == 64:
+                region(x, y)
+                continue
+            layout = LAYOUTS128[n_sb % len(LAYOUTS128)]
+            n_sb += 1
+            if layout[0] == "split":
+                for i in range(4):
+                    region(x + (i & 1) * 64, y + (i >> 1) * 64)
+            else:
+                for b in _leaves(layout, x, y, 128):
+                    leaf(*b)
+    return f
+
+
 def lf_header(rng, variant):
     """Frame-header loop-filter parameters; `variant` walks through the branches of svt_av1_loop_filter_frame_init."""
     h = RefLfHeader()
@@ -335,6 +455,34 @@ def lf_planes(rng, w, h, bd, is16):
     return out
 
 
+LF_CONTENTS = ("low", "high", "ends", "steps")
+
+
+def lf_content_planes(kind, rng, w, h, bd, is16):
+    """Three padded 4:2:0 planes whose samples sit at the ends of the range, where the signed clamps of filter4 act:
+    `low` lf_planes moved down until its lower part clips at 0, `high` its mirror at the top value, `ends` 16x16 areas drawn
+    from {0, 1, 2s} or from {top - 2s, top - 1, top}, `steps` steps of up to +-110 s per 8x8 block around mid-range with a
+    little noise (s = 1 << (bd - 8))."""
+    top, s = (1 << bd) - 1, 1 << (bd - 8)
+    if kind in ("low", "high"):
+        out = [np.clip(p.astype(np.int64) - 115 * s, 0, top) for p in lf_planes(rng, w, h, bd, is16)]
+        return [(top - p if kind == "high" else p).astype(np.uint16 if is16 else np.uint8) for p in out]
+    out = []
+    for pl in range(3):
+        pw, ph = (w >> (pl > 0)) + 2 * PAD, (h >> (pl > 0)) + 2 * PAD
+        if kind == "ends":
+            high = (rng.random((ph // 16 + 1, pw // 16 + 1)) < 0.5).repeat(16, 0).repeat(16, 1)[:ph, :pw]
+            pick = rng.integers(0, 3, size=(ph, pw))
+            img = np.where(high, np.array([top - 2 * s, top - 1, top])[pick], np.array([0, 1, 2 * s])[pick])
+        elif kind == "steps":
+            img = 128 * s + s * rng.integers(-110, 111, size=(ph // 8 + 1, pw // 8 + 1)).repeat(8, 0).repeat(8, 1)[:ph, :pw]
+            img = img + rng.integers(-1, 2, size=(ph, pw)) * s * (rng.random((ph, pw)) < 0.3)
+        else:
+            raise ValueError(kind)
+        out.append(np.clip(img, 0, top).astype(np.uint16 if is16 else np.uint8))
+    return out
+
+
 def lf_frame(planes, w, h, mi_ptr, mi_stride, mi_rows, mi_cols, hdr, bd, is16, plane_start=0, plane_end=3, lvl=None):
     f = abi.LfFrame()
     for i, p in enumerate(planes):
@@ -362,14 +510,70 @@ def ref_deblock(ref, planes, w, h, minfo, mi_stride, mi_rows, mi_cols, hdr, bd, 
     return flat, np.frombuffer(bytes(f.lvl), np.uint8).copy()
 
 
-GOLDEN_DLF = [  # key, w, h, bd, is16, header variant, sb, seed
-    ("a_8bit", 200, 136, 8, 0, 1, 64, 21), ("b_10bit_seg", 136, 72, 10, 1, 2, 64, 22), ("c_8in16_sb128", 264, 136, 8, 1, 0, 128, 23)]
+def random_levels(rng):
+    """A level table drawn at random, one entry in seven 0: any table is a valid input of the frame filter (the reference's
+    derivation of it from the frame header is control-plane code), and it needs no reference where there is none."""
+    lvl = rng.integers(0, 64, size=(3, 8, 2, 8, 2)).astype(np.uint8)
+    lvl[:, :, :, :, :] = np.where(rng.random(lvl.shape) < 0.15, 0, lvl)
+    return lvl.reshape(-1)
 
 
-def golden_dlf_inputs(w, h, bd, is16, variant, sb, seed):
+class CatalogueCase:
+    """One deblocking frame on the catalogue partition: the header of lf_header(variant) (variants 0..3: its four sharpness
+    values, no plane switched off), a random level table, and lf_planes or one of LF_CONTENTS."""
+
+    def __init__(self, w, h, bd, is16, sb, variant=0, content=None, seed=0):
+        self.w, self.h, self.bd, self.is16, self.sb = w, h, bd, is16, sb
+        rng = np.random.default_rng(7000 + seed)
+        self.mi_cols, self.mi_rows = (w + 7) // 8 * 2, (h + 7) // 8 * 2
+        self.mi_stride = self.mi_cols + 3
+        self.minfo = catalogue_mode_info(self.mi_rows, self.mi_cols, self.mi_stride, sb, 7000 + seed)
+        self.flat = flat_mode_info(self.minfo, self.mi_rows, self.mi_stride)
+        self.hdr = lf_header(rng, variant)
+        self.lvl = random_levels(rng)
+        wa, ha = self.mi_cols * 4, self.mi_rows * 4
+        self.planes = lf_planes(rng, wa, ha, bd, is16) if content is None else lf_content_planes(content, rng, wa, ha, bd, is16)
+
+    def frame(self, planes, mi_ptr, plane_start=0, plane_end=3, lvl=None):
+        return lf_frame(planes, self.w, self.h, mi_ptr, self.mi_stride, self.mi_rows, self.mi_cols, self.hdr, self.bd, self.is16,
+                        plane_start, plane_end, self.lvl if lvl is None else lvl)
+
+    def oracle(self, orc, plane_start=0, plane_end=3):
+        out = [p.copy() for p in self.planes]
+        orc.orc_loop_filter_frame(C.byref(self.frame(out, self.flat.ctypes.data, plane_start, plane_end)), self.sb)
+        return out
+
+
+DEPTHS = ((8, 0), (10, 1), (8, 1), (12, 1))
+CATALOGUE_PARAMS = [(bd, is16, sb, variant) for bd, is16 in DEPTHS for sb in (64, 128) for variant in range(4)]
+# kind, bit depth, is16, w, h, first plane; 130x258: the one size whose luma width is no multiple of 4
+LF_CONTENT_PARAMS = [(kind, bd, int(bd > 8), w, h, 0) for kind in LF_CONTENTS for bd in (8, 10, 12) for w, h in ((200, 136), (130, 258))]
+LF_CONTENT_PARAMS += [("steps", 10, 1, 200, 136, 1)]
+
+
+def catalogue_case(bd, is16, sb, variant):
+    """264 x 200.  The seeds are chosen: with them the level table of every case leaves each transform size a filtered edge
+    (test_lf_oracle.py::test_catalogue_conditions); about one table in eight has the zeros in the wrong place."""
+    return CatalogueCase(264, 200, bd, is16, sb, variant, None, 74000 + bd + is16 + sb + variant)
+
+
+def lf_content_case(kind, bd, is16, w, h):
+    """Superblock 128 on the tall picture, 64 on the wide one; the header variant (sharpness) follows the kind."""
+    return CatalogueCase(w, h, bd, is16, 128 if h > w else 64, LF_CONTENTS.index(kind), kind, 100 + bd + w)
+
+
+GOLDEN_DLF = [  # key, w, h, bd, is16, header variant, sb, seed, content (None: random partition and lf_planes; else catalogue partition)
+    ("a_8bit", 200, 136, 8, 0, 1, 64, 21, None), ("b_10bit_seg", 136, 72, 10, 1, 2, 64, 22, None),
+    ("c_8in16_sb128", 264, 136, 8, 1, 0, 128, 23, None), ("d_10bit_ends", 136, 72, 10, 1, 1, 64, 24, "ends")]
+
+
+def golden_dlf_inputs(w, h, bd, is16, variant, sb, seed, content=None):
     rng = np.random.default_rng(seed)
     mi_cols, mi_rows = (w + 7) // 8 * 2, (h + 7) // 8 * 2
     mi_stride = mi_cols + 1
+    if content:
+        minfo = catalogue_mode_info(mi_rows, mi_cols, mi_stride, sb, seed)
+        return mi_cols, mi_rows, mi_stride, minfo, lf_header(rng, variant), lf_content_planes(content, rng, mi_cols * 4, mi_rows * 4, bd, is16)
     minfo = random_mode_info(rng, mi_rows, mi_cols, mi_stride, sb=sb)
     hdr = lf_header(rng, variant)
     planes = lf_planes(rng, mi_cols * 4, mi_rows * 4, bd, is16)

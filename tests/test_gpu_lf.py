@@ -296,8 +296,8 @@ def test_tier_a_lpf(hip, orc, d, n):
     import test_lf_oracle as TL
     rng = np.random.default_rng(50 + n + (d == "vertical"))
     for trial in range(48):
-        bd = (8, 10, 8)[trial % 3]
-        is16 = int(trial % 3 != 0)
+        bd = (8, 10, 8, 12, 10)[trial % 5]      # 5 and the 4 kinds of lpf_block: every depth meets every kind
+        is16 = int(trial % 5 != 0)
         a = TL.lpf_block(rng, bd, trial)
         if d == "horizontal":
             a = a.T
@@ -335,9 +335,7 @@ class OrcLvl:
 
     @staticmethod
     def make(rng, hdr):
-        lvl = rng.integers(0, 64, size=(3, 8, 2, 8, 2)).astype(np.uint8)
-        lvl[:, :, :, :, :] = np.where(rng.random(lvl.shape) < 0.15, 0, lvl)
-        return lvl.reshape(-1)
+        return L.random_levels(rng)
 
 
 def deblock_inputs(variant):
@@ -390,6 +388,35 @@ def test_tier_b_deblock_frame(hip, orc, variant):
         assert np.array_equal(a, b), np.argwhere(a != b)[:5]
         changed += int((a != o).sum())
     assert (changed > 0) == (variant != 7)
+
+
+def check_deblock(hip, orc, c, ps=0):
+    """GPU == oracle on the three padded planes of a CatalogueCase, the padding and the planes before `ps` untouched."""
+    want = c.oracle(orc, ps, 3)
+    got = gpu_deblock(hip, c.planes, c.w, c.h, c.flat, c.mi_stride, c.mi_rows, c.mi_cols, c.hdr, c.bd, c.is16, c.lvl, ps, 3)
+    for i, (a, b, o) in enumerate(zip(want, got, c.planes)):
+        assert np.array_equal(a, b), (i, np.argwhere(a != b)[:5])
+        assert (a != o).any() == (i >= ps), i
+        inner = np.zeros(o.shape, bool)
+        inner[L.PAD:-L.PAD, L.PAD:-L.PAD] = True
+        assert np.array_equal(b[~inner], o[~inner]), i
+
+
+@pytest.mark.parametrize("bd,is16,sb,variant", L.CATALOGUE_PARAMS)
+def test_tier_b_deblock_catalogue(hip, orc, bd, is16, sb, variant):
+    """The catalogue partition (lf_cases.catalogue_mode_info) at 264 x 200: every block size with every transform depth, so every
+    row of TX_W_LOG2 / TX_H_LOG2 on either side of a filtered edge, 12 bit, the four sharpness values, a random level table.
+    What these inputs reach is asserted in test_lf_oracle.py::test_catalogue_conditions; the oracle is pinned to the reference
+    on them in test_loop_filter_frame_catalogue."""
+    check_deblock(hip, orc, L.catalogue_case(bd, is16, sb, variant))
+
+
+@pytest.mark.parametrize("kind,bd,is16,w,h,ps", L.LF_CONTENT_PARAMS)
+def test_tier_b_deblock_content(hip, orc, kind, bd, is16, w, h, ps):
+    """Content at the ends of the range (lf_cases.lf_content_planes), where the signed clamps of filter4 act, on the catalogue
+    partition; 130 x 258 is the size whose luma width is no multiple of 4; one case filters chroma only.  The conditions on
+    these inputs are in test_lf_oracle.py::test_deblock_content_conditions."""
+    check_deblock(hip, orc, L.lf_content_case(kind, bd, is16, w, h), ps)
 
 
 def test_tier_b_deblock_golden(hip):

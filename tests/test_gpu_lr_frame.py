@@ -51,6 +51,26 @@ def test_frame_golden(hip):
     for name in R.CASES:
         for p, a in enumerate(run_gpu(hip, R.make_case(name))):
             assert np.array_equal(a, g[f"{name}_p{p}"]), (name, p)
+    for name, (kind, dims) in R.GOLDEN_CONTENT.items():
+        for p, a in enumerate(run_gpu(hip, R.make_content_case(kind, dims))):
+            assert np.array_equal(a, g[f"{name}_p{p}"]), (name, p)
+
+
+@pytest.mark.parametrize("name", list(R.CONTENT_CASES))
+def test_frame_content(hip, orc, name):
+    """Content at the ends of the range with the fixed unit table of lr_cases.make_content_case: all 16 self-guided sets, xqd
+    and Wiener taps at the ends of their ranges, 12 bit, both optimized_lr values, a height of 64 k + 57.  What these inputs
+    reach is asserted in test_lr_frame_oracle.py::test_content_conditions; the oracle is pinned to the reference on them in
+    test_oracle_equals_reference_content."""
+    kind, dims = R.CONTENT_CASES[name]
+    case = R.make_content_case(kind, dims)
+    arr, outs = R.lr_planes(case)
+    orc.orc_restoration_filter_frame(arr, C.c_uint32(len(case)))
+    for p, (a, o, c) in enumerate(zip(run_gpu(hip, case), outs, case)):
+        want = o[:c["h"], :c["w"]]
+        assert np.array_equal(a, want), (name, p, np.argwhere(a != want)[:5])
+        if kind in ("noise", "ends"):       # not a comparison of two copies
+            assert not np.array_equal(want, c["src"]), (name, p)
 
 
 def test_frame_4k10(hip, orc):

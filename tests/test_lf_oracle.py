@@ -286,8 +286,8 @@ def test_lpf_leaves(orc, ref, d, n):
     f8 = L.rtcd(ref, f"svt_aom_lpf_{d}_{n}", None, V, C.c_int32, V, V, V)
     f16 = L.rtcd(ref, f"svt_aom_highbd_lpf_{d}_{n}", None, V, C.c_int32, V, V, V, C.c_int32)
     for trial in range(400):
-        bd = (8, 10, 8)[trial % 3]
-        is16 = int(trial % 3 != 0)
+        bd = (8, 10, 8, 12, 10)[trial % 5]      # 5 and the 4 kinds of lpf_block: every depth meets every kind
+        is16 = int(trial % 5 != 0)
         a = lpf_block(rng, bd, trial)
         if d == "horizontal":
             a = a.T
@@ -351,3 +351,231 @@ def test_loop_filter_oracle_vs_golden(orc):
             assert np.array_equal(a, b), key
         n += 1
     assert n == len(L.GOLDEN_DLF)
+
+
+# ---- the catalogue partition and the range-end contents (lf_cases.CatalogueCase): conditions on the inputs, then the pin
+_TXW_LOG2 = np.array([L.TXW[t].bit_length() - 1 for t in range(19)])
+_TXH_LOG2 = np.array([L.TXH[t].bit_length() - 1 for t in range(19)])
+_BW_LOG2 = np.array([L.BW[b].bit_length() - 1 for b in range(22)])
+_BH_LOG2 = np.array([L.BH[b].bit_length() - 1 for b in range(22)])
+
+
+def edge_census(c, plane, d, lvl=None):
+    """set_lpf_parameters (deblocking_filter.c:162-282) restated in numpy for every 4-sample unit of one plane and direction
+    (d 0: vertical edges) of a CatalogueCase: a dict of arrays [units down][units across] - `edge` the unit starts a transform
+    and is not at the picture's border, `filtered` / `refused` of those with a level (refused: both sides skipped inter blocks and
+    no block edge), `cur` / `prev` the transform sizes on both sides, `lc` / `lp` their levels, `len` and `level` of the filter."""
+    ss = int(plane > 0)
+    nx, ny = ((c.w >> ss) + 3) // 4, ((c.h >> ss) + 3) // 4
+    rows, cols = ss | (np.arange(ny) * 4 << ss >> 2), ss | (np.arange(nx) * 4 << ss >> 2)
+    mi = c.flat[np.ix_(rows, cols)]
+    pv = c.flat[np.ix_(rows - (d == 1) * (1 << ss), cols - (d == 0) * (1 << ss))]      # wraps at coordinate 0, where no edge is
+    coord = (np.arange(nx) * 4)[None, :] if d == 0 else (np.arange(ny) * 4)[:, None]
+    key = "tx_size_uv" if plane else "tx_size_y"
+    log2 = _TXW_LOG2 if d == 0 else _TXH_LOG2
+    ts, pv_ts = log2[mi[key]], log2[pv[key]]
+    table = (c.lvl if lvl is None else lvl).reshape(3, 8, 2, 8, 2)
+    lc = table[plane, mi["segment_id"], d, mi["ref_frame0"], mi["mode_lf"]].astype(int)
+    lp = table[plane, pv["segment_id"], d, pv["ref_frame0"], pv["mode_lf"]].astype(int)
+    bdim = (_BW_LOG2 if d == 0 else _BH_LOG2)[mi["bsize"]]
+    if ss:
+        bdim = np.maximum(bdim - 1, 2)
+    edge = ((coord & ((1 << ts) - 1)) == 0) & (coord > 0)
+    pu_edge = (coord & ((1 << bdim) - 1)) == 0
+    allowed = (pv["skip_inter"] == 0) | (mi["skip_inter"] == 0) | pu_edge
+    on = edge & ((lc != 0) | (lp != 0))
+    min_ts = np.minimum(ts, pv_ts)
+    length = np.where(min_ts <= 2, 4, np.where(plane > 0, 6, np.where(min_ts == 3, 8, 14)))
+    return dict(edge=edge, filtered=on & allowed, refused=on & ~allowed, cur=mi[key], prev=pv[key], lc=lc, lp=lp, len=length,
+                level=np.where(lc != 0, lc, lp))
+
+
+def branch_census(c, plane, d):
+    """The branch each of the four lines of every filtered edge takes on the UNFILTERED picture (filter_mask / hev_mask /
+    flat_mask of deblocking_common.c restated): the set of (length, branch), branch one of nomask, hev, nohev, flat, flat2."""
+    e = edge_census(c, plane, d)
+    uy, ux = np.nonzero(e["filtered"])
+    if not uy.size:
+        return set()
+    pic = c.planes[plane].astype(np.int64)
+    along, k = np.arange(4)[None, :, None], np.arange(-7, 7)[None, None, :]
+    y0, x0 = (L.PAD + uy * 4)[:, None, None], (L.PAD + ux * 4)[:, None, None]
+    s = pic[y0 + along, x0 + k] if d == 0 else pic[y0 + k, x0 + along]                 # [edge][line][p6 .. p0 q0 .. q6]
+    p, q = (lambda i: s[:, :, 6 - i]), (lambda i: s[:, :, 7 + i])
+    level, sharp, sh = e["level"][uy, ux], c.hdr.sharpness_level, c.bd - 8
+    inside = level >> (int(sharp > 0) + int(sharp > 4))                                 # svt_aom_update_sharpness
+    if sharp > 0:
+        inside = np.minimum(inside, 9 - sharp)
+    inside = np.maximum(inside, 1)
+    lim, blim, thr = ((v << sh)[:, None] for v in (inside, 2 * (level + 2) + inside, level >> 4))
+    one, n = 1 << sh, e["len"][uy, ux][:, None]
+    a = np.abs
+    mask = ~((a(p(1) - p(0)) > lim) | (a(q(1) - q(0)) > lim) | (a(p(0) - q(0)) * 2 + a(p(1) - q(1)) // 2 > blim))
+    mask &= (n < 6) | ~((a(p(2) - p(1)) > lim) | (a(q(2) - q(1)) > lim))
+    mask &= (n < 8) | ~((a(p(3) - p(2)) > lim) | (a(q(3) - q(2)) > lim))
+    flat = (n >= 6) & ~((a(p(1) - p(0)) > one) | (a(q(1) - q(0)) > one) | (a(p(2) - p(0)) > one) | (a(q(2) - q(0)) > one))
+    flat &= (n < 8) | ~((a(p(3) - p(0)) > one) | (a(q(3) - q(0)) > one))
+    flat2 = (n == 14) & ~np.any([(a(p(i) - p(0)) > one) | (a(q(i) - q(0)) > one) for i in (4, 5, 6)], axis=0)
+    hev = (a(p(1) - p(0)) > thr) | (a(q(1) - q(0)) > thr)
+    branch = np.where(mask & flat & flat2, 4, np.where(mask & flat, 3, np.where(~mask, 0, np.where(hev, 1, 2))))
+    names = ("nomask", "hev", "nohev", "flat", "flat2")
+    return {(int(ln), names[b]) for ln, b in set(zip(np.broadcast_to(n, branch.shape).ravel().tolist(), branch.ravel().tolist()))}
+
+
+BRANCHES = {4: ("nomask", "hev", "nohev"), 6: ("nomask", "hev", "nohev", "flat"), 8: ("nomask", "hev", "nohev", "flat"),
+            14: ("nomask", "hev", "nohev", "flat", "flat2")}
+_cases = {}
+
+
+def cached(make, *args):
+    """One CatalogueCase per argument list for the whole session, left unchanged by its users."""
+    if (make, args) not in _cases:
+        _cases[(make, args)] = make(*args)
+    return _cases[(make, args)]
+
+
+def blocks_of(minfo):
+    return set(zip(minfo["bsize"].ravel().tolist(), minfo["tx_depth"].ravel().tolist(),
+                   ((minfo["skip"] != 0) & (minfo["ref_frame0"] > 0)).ravel().tolist()))
+
+
+def tx_census(c):
+    """{(plane kind, direction, side): transform sizes seen on that side of a filtered edge}."""
+    out = {}
+    for plane in (0, 1, 2):
+        for d in (0, 1):
+            e = edge_census(c, plane, d)
+            for side in ("cur", "prev"):
+                out.setdefault((min(plane, 1), d, side), set()).update(e[side][e["filtered"]].tolist())
+    return out
+
+
+@pytest.mark.parametrize("sb", [64, 128])
+def test_catalogue_partition(sb):
+    """catalogue_mode_info holds every block size that fits the superblock with every depth it can have - at 264 x 200 for
+    superblock 64, on a 512 x 384 grid for 128, where 264 x 200 has room for eight whole 64x64 regions only - and, for 128 at
+    264 x 200, the three blocks above 64 samples as skipped inter blocks.  It is deterministic but for the seeded fields."""
+    w, h = (264, 200) if sb == 64 else (512, 384)
+    mi_cols, mi_rows = w // 4, h // 4
+    m = L.catalogue_mode_info(mi_rows, mi_cols, mi_cols + 3, sb, 1)
+    have = blocks_of({k: v[:, :mi_cols] for k, v in m.items()})
+    for (bw, bh), b in L.BSIZE.items():
+        if max(bw, bh) <= sb:
+            for depth in range(L.max_depth_of(b) + 1):
+                assert any(x[:2] == (b, depth) for x in have), (bw, bh, depth)
+    m2 = L.catalogue_mode_info(mi_rows, mi_cols, mi_cols + 3, sb, 2)
+    assert np.array_equal(m["bsize"], m2["bsize"]) and np.array_equal(m["tx_depth"], m2["tx_depth"])
+    assert not np.array_equal(m["segment_id"], m2["segment_id"])
+    if sb == 128:
+        small = L.catalogue_mode_info(50, 66, 69, 128, 1)
+        for size in ((128, 128), (128, 64), (64, 128)):
+            assert (L.BSIZE[size], 0, True) in blocks_of(small), size
+
+
+@pytest.mark.parametrize("bd,is16,sb,variant", L.CATALOGUE_PARAMS)
+def test_catalogue_conditions(bd, is16, sb, variant):
+    """Conditions on the INPUTS of every case of test_tier_b_deblock_catalogue (test_gpu_lf.py), from the mode info and the level
+    table alone: per direction each of the 19 luma and 14 chroma transform sizes is the current unit of a filtered edge and the
+    previous unit of one; superblock 128 has a luma transform edge refused because both sides are skipped inter blocks and it is
+    no block edge, inside a block above 64 samples; an edge with level 0 takes its neighbour's, another has none.  If a changed
+    catalogue or seed misses these, change that, not the conditions."""
+    c = cached(L.catalogue_case, bd, is16, sb, variant)
+    for (kind, d, side), seen in tx_census(c).items():
+        want = set(L.TX_UV) if kind else set(range(19))
+        assert seen == want, (kind, d, side, sorted(want - seen))
+    e = [edge_census(c, plane, d) for plane in range(3) for d in (0, 1)]
+    if sb == 128:
+        big = np.isin(c.flat["bsize"], [L.BSIZE[s] for s in ((128, 128), (128, 64), (64, 128))])[:, :c.mi_cols]
+        assert (c.flat["skip_inter"][:, :c.mi_cols][big] == 1).any() and (c.flat["tx_size_y"][:, :c.mi_cols][big] == L.TX[(64, 64)]).all()
+        ny, nx = e[0]["refused"].shape
+        assert sum(int((x["refused"] & big[:ny, :nx]).sum()) for x in e[:2]) > 0
+    assert any((x["edge"] & (x["lc"] == 0) & (x["lp"] != 0)).any() for x in e)
+    assert any((x["edge"] & (x["lc"] == 0) & (x["lp"] == 0)).any() for x in e)
+
+
+def test_catalogue_conditions_need_the_catalogue():
+    """The same census on random_mode_info partitions of the same picture misses transform sizes, whatever the seed: the
+    conditions above do guard the catalogue."""
+    c = L.catalogue_case(10, 1, 64, 1)
+    for seed in range(4):
+        c.minfo = L.random_mode_info(np.random.default_rng(seed), c.mi_rows, c.mi_cols, c.mi_stride, sb=64)
+        c.flat = L.flat_mode_info(c.minfo, c.mi_rows, c.mi_stride)
+        assert any(seen != (set(L.TX_UV) if kind else set(range(19))) for (kind, d, side), seen in tx_census(c).items()), seed
+
+
+def range_ends(before, after, top):
+    """Counts of samples the filter changed: that ended at 0, at the top value, that started at 0, at the top value."""
+    ch = before != after
+    return [int((ch & (after == 0)).sum()), int((ch & (after == top)).sum()), int((ch & (before == 0)).sum()), int((ch & (before == top)).sum())]
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_deblock_content_conditions(orc, bd):
+    """Conditions on the INPUTS of test_tier_b_deblock_content and _catalogue, per bit depth, from the inputs and the oracle's
+    outputs: over these cases together every (luma / chroma, direction, length, branch) occurs (the horizontal pass taken on
+    the unfiltered picture: a census of the inputs, not a check of outputs); `low` and `ends` have changed samples that end
+    at 0 and others that started there, `high` and `ends` the same at the top value, on both sizes; at 130 x 258 every case
+    has non-zero levels and changes samples in all three planes."""
+    top = (1 << bd) - 1
+    seen = {}
+    cases = [(kind, cached(L.lf_content_case, kind, b, is16, w, h)) for kind, b, is16, w, h, ps in L.LF_CONTENT_PARAMS if b == bd and ps == 0]
+    cases += [(None, cached(L.catalogue_case, b, is16, sb, v)) for b, is16, sb, v in L.CATALOGUE_PARAMS if b == bd and v == 1]
+    for kind, c in cases:
+        for plane in range(3):
+            for d in (0, 1):
+                seen.setdefault((min(plane, 1), d), set()).update(branch_census(c, plane, d))
+        if kind is None:
+            continue
+        out = c.oracle(orc)
+        ends = np.sum([range_ends(a, b, top) for a, b in zip(c.planes, out)], axis=0)
+        if kind in ("low", "ends"):
+            assert ends[0] > 0 and ends[2] > 0, (kind, c.w, ends)
+        if kind in ("high", "ends"):
+            assert ends[1] > 0 and ends[3] > 0, (kind, c.w, ends)
+        if c.w == 130:
+            assert c.w % 4 and c.lvl.any() and all((a != b).any() for a, b in zip(c.planes, out)), kind
+    for (kind, d), got in seen.items():
+        want = {(n, b) for n in ((4, 6) if kind else (4, 8, 14)) for b in BRANCHES[n]}
+        assert got == want, (kind, d, sorted(want - got))
+
+
+def test_deblock_content_conditions_need_the_content(orc):
+    """With lf_planes in place of the range-end contents no changed sample ends or starts at either end of the range."""
+    for bd, is16 in ((8, 0), (10, 1), (12, 1)):
+        c = L.CatalogueCase(200, 136, bd, is16, 64, 0, None, 100 + bd + 200)
+        assert not np.sum([range_ends(a, b, (1 << bd) - 1) for a, b in zip(c.planes, c.oracle(orc))]), bd
+
+
+@pytest.mark.parametrize("bd,is16,sb,variant", L.CATALOGUE_PARAMS)
+def test_loop_filter_frame_catalogue(orc, ref, bd, is16, sb, variant):
+    """The oracle against the REAL svt_av1_loop_filter_frame on every case of the catalogue partition, 12 bit through the same
+    frame call (the reference hands encoder_bit_depth to its highbd filters).  The mode info is the reference's own gather
+    (tx_depth_to_tx_size, av1_get_max_uv_txsize), and flat_mode_info must equal it.  The level table is the one the reference
+    derives from the case's header: the reference takes no table, so the random one of the GPU test is not pinned here."""
+    c = cached(L.catalogue_case, bd, is16, sb, variant)
+    p_ref = [p.copy() for p in c.planes]
+    flat, lvl = L.ref_deblock(ref, p_ref, c.w, c.h, c.minfo, c.mi_stride, c.mi_rows, c.mi_cols, c.hdr, bd, is16, sb)
+    assert flat.tobytes() == c.flat.tobytes()
+    p_orc = [p.copy() for p in c.planes]
+    orc.orc_loop_filter_frame(C.byref(c.frame(p_orc, flat.ctypes.data, lvl=lvl)), sb)
+    for a, b, o in zip(p_ref, p_orc, c.planes):
+        assert np.array_equal(a, b), np.argwhere(a != b)[:5]
+        assert (a != o).any()
+
+
+@pytest.mark.parametrize("kind,bd,is16,w,h,ps", L.LF_CONTENT_PARAMS)
+def test_loop_filter_frame_content(orc, ref, kind, bd, is16, w, h, ps):
+    """The same on the range-end contents, 130 x 258 and the chroma-only plane range included.  With the reference's level
+    table too the changed samples reach the end of the range they are named for, so the clamps are pinned where they act."""
+    c = cached(L.lf_content_case, kind, bd, is16, w, h)
+    p_ref = [p.copy() for p in c.planes]
+    flat, lvl = L.ref_deblock(ref, p_ref, w, h, c.minfo, c.mi_stride, c.mi_rows, c.mi_cols, c.hdr, bd, is16, c.sb, ps, 3)
+    assert flat.tobytes() == c.flat.tobytes()
+    p_orc = [p.copy() for p in c.planes]
+    orc.orc_loop_filter_frame(C.byref(c.frame(p_orc, flat.ctypes.data, ps, 3, lvl)), c.sb)
+    for i, (a, b, o) in enumerate(zip(p_ref, p_orc, c.planes)):
+        assert np.array_equal(a, b), np.argwhere(a != b)[:5]
+        assert (a != o).any() == (i >= ps)
+    ends = np.sum([range_ends(o, a, (1 << bd) - 1) for o, a in zip(c.planes, p_ref)], axis=0)
+    assert kind not in ("low", "ends") or (ends[0] > 0 and ends[2] > 0), ends
+    assert kind not in ("high", "ends") or (ends[1] > 0 and ends[3] > 0), ends
