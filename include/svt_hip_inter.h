@@ -29,8 +29,9 @@
  *   Source/Lib/Codec/mode_decision.c:2425-2533, av1me.c:709-1132   single_motion_search (OBMC_CAUSAL): svt_av1_obmc_full_pixel_search,
  *                                                svt_av1_find_best_obmc_sub_pixel_tree_up, svt_aom_obmc_sad* / svt_aom_obmc_variance*
  * The warp entry points are Tier B only: the RTCD pointers svt_av1_warp_affine / svt_av1_highbd_warp_affine have no leaf.
- * Scaled references are not covered; RANSAC over the correspondences of global motion and svt_find_projection stay on
- * the host.  The rate model of the mask search (model_rd_with_curvfit) stays on the host.  An OBMC candidate needs no host
+ * Prediction from a reference of another size (has_scale: svt_av1_convolve_2d_scale) is svt_hip_convolve_scale_batch of
+ * svt_hip_scale.h, whose compound intermediates are the ones of this header; the entry points here take references of the
+ * picture's size.  RANSAC over the correspondences of global motion and svt_find_projection stay on the host.  The rate model of the mask search (model_rd_with_curvfit) stays on the host.  An OBMC candidate needs no host
  * arithmetic: its neighbour predictions are SvtHipConvolveDesc descriptors, then svt_hip_obmc_target_batch,
  * svt_hip_obmc_search_batch, the prediction at the vector found and the SVT_HIP_BLEND_VMASK / _HMASK blends; which neighbours
  * overlap, and svt_aom_choose_best_av1_mv_pred behind the search, stay the caller's control logic.
@@ -366,7 +367,8 @@ SVT_HIP_API uint16_t svt_hip_gm_match_corners(const SvtHipGmMatchJob *jobs, uint
  * svt_aom_upsampled_pred_c (variance.c:204-254) + vf, two_level_checks_fast over the bilinear svf (variance.c:28-68, 308-318),
  * svt_mv_err_cost_ with all six MV_COST_TYPEs, and the reference's integer types (unsigned cost * weight wraps mod 2^32).
  * 8-bit only, as the reference (hbd_md = 0 there).  Not covered: the compound / masked / OBMC variants the reference leaves
- * commented out, scaled references, and the encoder hook.
+ * commented out, scaled references (the reference searches with is_scaled = 0 on a reference svt_hip_resize_planes of svt_hip_scale.h
+ * brought to the picture's size; only the final prediction is scaled, svt_hip_convolve_scale_batch), and the encoder hook.
  *
  * What is read: of src the w x h block; of ref the (w + 8) x (h + 8) window that starts 4 samples above and 4 to the left of the
  * sample start_mv points at, whatever the filter and the controls (with two iterations per step a candidate lies up to 14/8 pel
@@ -458,7 +460,8 @@ SVT_HIP_API int32_t svt_hip_subpel_mv_limits(int32_t mi_row, int32_t mi_col, int
  * arithmetic on vectors that need not be full-pel, a clip may leave start > end (nothing is visited, the outputs keep their incoming
  * values), the generic scan is column-major and the psad scan (dist_type SAD, enable_psad, end_x - start_x >= 7 after the clip)
  * row-major over eight columns out of every 7 + step with its width raised to a multiple of 8.  The first position in scan order wins a tie.
- * 8-bit only, as every caller (hbd_md = EB_8_BIT_MD).  Not covered: scaled references, the derivation of the MVCs and MVPs,
+ * 8-bit only, as every caller (hbd_md = EB_8_BIT_MD).  Not covered: scaled references (as for the sub-pel search: the caller searches
+ * the reference that svt_hip_resize_planes brought to the picture's size), the derivation of the MVCs and MVPs,
  * svt_aom_choose_best_av1_mv_pred, the early / post checks of pme_search and its q_weight modulation of the window, the encoder hook.
  *
  * What is read: of src the w x h block.  Of ref, per stage, the blocks at the visited positions and nothing outside the rectangle
@@ -553,7 +556,8 @@ SVT_HIP_API void svt_hip_fpel_sq_windows(const SvtHipFpelSqCtrls *ctrls, uint8_t
  * (SvtHipConvolveDesc) and the final blends (SVT_HIP_BLEND_VMASK / _HMASK): the weighted target, then single_motion_search
  * (mode_decision.c:2425-2533) for OBMC_CAUSAL.  8-bit only, as the reference (calc_target_weighted_pred sets is16bit = 0,
  * single_motion_search "supports 8bit path only").  Not covered: the bilinear osvf path (use_accurate_subpel_search == 0, which the
- * encoder never takes), scaled references, svt_aom_choose_best_av1_mv_pred and the validity check behind the search, and an
+ * encoder never takes), scaled references (neighbour predictions from one go through svt_hip_convolve_scale_batch of svt_hip_scale.h;
+ * the search itself is not scaled), svt_aom_choose_best_av1_mv_pred and the validity check behind the search, and an
  * encoder hook.  wsrc and mask are int32_t arrays and must be 4-byte aligned; every other pointer may have any alignment. */
 #define SVT_HIP_OBMC_MAX_NEIGHBOURS 4 /* max_neighbor_obmc[] never exceeds it */
 /* status of both entry points */

@@ -233,7 +233,8 @@ SVT_HIP_API int32_t svt_hip_loop_filter_frame(const SvtHipLfFrame *frame, void *
  * rounds gets its `finished` bit clear and the caller falls back (to the host loop, or to the record's best level so far).
  *
  * Not covered: mode_ref_delta_enabled (the reference never sets it, resource_coordination_process.c:367), delta_lf, several
- * tiles, superres / resize, formats other than 4:2:0, the LPF_PICK_FROM_Q family (scalar host work).
+ * tiles, superres / resize pictures (their scaling itself is svt_hip_scale.h: svt_hip_resize_planes, svt_hip_superres_upscale_planes),
+ * formats other than 4:2:0, the LPF_PICK_FROM_Q family (scalar host work).
  * ------------------------------------------------------------------------------------------------------------------- */
 #define SVT_HIP_DLF_MAX_LEVEL 63            /* MAX_LOOP_FILTER */
 /* Recommended max_rounds: the largest `rounds` of tests/golden/dlf_pick.npz (12), plus 4.  A search CAN need more (a replay of the loop

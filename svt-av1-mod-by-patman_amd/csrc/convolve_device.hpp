@@ -26,8 +26,9 @@ __device__ __forceinline__ void stpx(void *p, size_t idx, int is16, int32_t v, i
 }
 
 // compound epilogue (inter_prediction.c:531-543 and its siblings): store the offset intermediate, or average with the stored
-// one and write the pixel
-__device__ __forceinline__ void comp_out(const SvtHipConvolveDesc &d, int y, int x, int32_t res, int32_t round_offset, int round_bits) {
+// one and write the pixel.  Desc: SvtHipConvolveDesc, or SvtHipConvolveScaleDesc (inter_scale.hip), which has the same compound fields
+template <class Desc>
+__device__ __forceinline__ void comp_out(const Desc &d, int y, int x, int32_t res, int32_t round_offset, int round_bits) {
     uint16_t *cb = d.cbuf + (size_t)y * d.cbuf_stride + x;
     if (d.compound == 1) {
         *cb = (uint16_t)res;
@@ -56,6 +57,20 @@ __device__ __forceinline__ int32_t hsum8(const uint16_t *in, int e, const uint32
 #pragma unroll
     for (int k = 0; k < 4; k++)
         acc = __builtin_amdgcn_sdot2(__builtin_bit_cast(conv_i16x2, __builtin_amdgcn_alignbit(d[k + 1], d[k], sh)), __builtin_bit_cast(conv_i16x2, fp[k]), acc, false);
+    return acc;
+}
+
+// acc + sum of taps[k] * at(k), k < n <= 8, for a filter whose phase differs per lane (inter_scale.hip, loopfilter_resize.hip): taps is
+// one row of a table staged in LDS as [phase][8] int16, 16-byte aligned, so the row is one naturally aligned DS read; at(k) is not
+// called for k >= n.
+template <class At>
+__device__ __forceinline__ int32_t tap_sum(const int16_t *__restrict__ taps, int n, int32_t acc, At at) {
+    const uint4    q    = *(const uint4 *)taps;
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if (k < n)
+            acc += (int32_t)(int16_t)(w[k >> 1] >> (16 * (k & 1))) * at(k);
     return acc;
 }
 

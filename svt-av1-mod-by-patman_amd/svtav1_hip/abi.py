@@ -536,6 +536,43 @@ class GmMatches(C.Structure):            # SvtHipGmMatches
 GM_CORNERS_DTYPE, GM_MATCHES_DTYPE = record_dtype(GmCorners), record_dtype(GmMatches)   # numpy views of the two device records
 
 
+SCALE_MAX_PLANES, SCALE_MAX_TILE_COLS, SCALE_INVALID = 24, 64, -1     # SVT_HIP_SCALE_* (include/svt_hip_scale.h)
+
+
+class ResizePlane(C.Structure):          # SvtHipResizePlane
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride", C.c_uint32), ("dst_stride", C.c_uint32), ("src_width", C.c_uint32),
+                ("src_height", C.c_uint32), ("dst_width", C.c_uint32), ("dst_height", C.c_uint32), ("is_16bit", C.c_uint8),
+                ("bit_depth", C.c_uint8), ("pad_", C.c_uint8 * 6)]
+
+
+class SuperresPlane(C.Structure):        # SvtHipSuperresPlane
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride", C.c_uint32), ("dst_stride", C.c_uint32), ("rows", C.c_uint32),
+                ("frame_width", C.c_uint16), ("superres_upscaled_width", C.c_uint16), ("superres_denominator", C.c_uint8),
+                ("sub_x", C.c_uint8), ("is_16bit", C.c_uint8), ("bit_depth", C.c_uint8), ("tile_cols", C.c_uint16),
+                ("tile_col_start_mi", C.c_uint16 * (SCALE_MAX_TILE_COLS + 1))]
+
+
+class ConvolveScaleDesc(C.Structure):    # SvtHipConvolveScaleDesc
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride", C.c_uint32), ("dst_stride", C.c_uint32), ("w", C.c_uint16),
+                ("h", C.c_uint16), ("pad0_", C.c_uint32), ("filter_x", C.c_void_p), ("filter_y", C.c_void_p), ("subpel_x_qn", C.c_int32),
+                ("x_step_qn", C.c_int32), ("subpel_y_qn", C.c_int32), ("y_step_qn", C.c_int32), ("taps_x", C.c_uint8), ("taps_y", C.c_uint8),
+                ("round_0", C.c_uint8), ("round_1", C.c_uint8), ("bit_depth", C.c_uint8), ("is_16bit", C.c_uint8), ("compound", C.c_uint8),
+                ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8), ("pad_", C.c_uint8 * 7), ("cbuf", C.c_void_p),
+                ("cbuf_stride", C.c_uint32), ("pad2_", C.c_uint32)]
+
+
+class ScaleFactors(C.Structure):         # SvtHipScaleFactors
+    _fields_ = [("x_scale_fp", C.c_int32), ("y_scale_fp", C.c_int32), ("x_step_q4", C.c_int32), ("y_step_q4", C.c_int32)]
+
+
+class ScaledPosition(C.Structure):       # SvtHipScaledPosition
+    _fields_ = [("pos_x", C.c_int32), ("pos_y", C.c_int32), ("subpel_x", C.c_int32), ("subpel_y", C.c_int32), ("xs", C.c_int32),
+                ("ys", C.c_int32)]
+
+
+CONVOLVE_SCALE_DESC_DTYPE = record_dtype(ConvolveScaleDesc)   # numpy view of an array of descriptors
+
+
 class TfBlock(C.Structure):              # SvtHipTfBlock (include/svt_hip_tf.h)
     _fields_ = [("src", C.c_void_p * 3), ("pred", C.c_void_p * 3), ("accum", C.c_void_p * 3), ("count", C.c_void_p * 3),
                 ("src_stride", C.c_uint32 * 3), ("pred_stride", C.c_uint32 * 3), ("decay_factor_fp16", C.c_uint32 * 3),
