@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
+
 #include "../../include/svt_hip.h"
 #include "../../include/svt_hip_me.h"
 
@@ -109,6 +111,24 @@ private:
     GuardedBuf *held_[6];
     int         n_held_ = 0;
 };
+
+// The host side of a batch export whose descriptors two instantiations of one kernel share, each walking all n and skipping the other's:
+// refusal unless have_pointers, nothing for an empty batch, else one scope with `small` on min(n, small_per_cu per compute unit)
+// workgroups of small_threads and `large` likewise; a workgroup strides over the descriptors when there are more than its grid holds.
+template <class... Params, class... Args>
+int32_t launch_two_classes(const char *fn, bool have_pointers, uint32_t n, void *stream, void (*small)(Params...), uint32_t small_threads, uint32_t small_per_cu,
+                           void (*large)(Params...), uint32_t large_threads, uint32_t large_per_cu, const Args &...args) {
+    if (!have_pointers)
+        return refuse("%s: bad argument", fn);
+    if (n == 0)
+        return SVT_HIP_OK;
+    TierBCall c(fn, stream);
+    if (!c.ok())
+        return c.status();
+    hipLaunchKernelGGL(small, dim3(std::min(n, (uint32_t)cu_count() * small_per_cu)), dim3(small_threads), 0, c.stream(), args...);
+    hipLaunchKernelGGL(large, dim3(std::min(n, (uint32_t)cu_count() * large_per_cu)), dim3(large_threads), 0, c.stream(), args...);
+    return c.finish();
+}
 
 // The HIP runtime loads the code object of a translation unit when the first of its kernels is launched (hundreds of milliseconds for
 // the whole library, paid by whichever encoder threads come first: 23 ms per call of the first 35 calls inside the patched encoder).

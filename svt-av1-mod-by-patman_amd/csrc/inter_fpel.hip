@@ -27,8 +27,6 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int TILE = SVT_HIP_FPEL_TILE;
-constexpr int SMALL_SIDE = 32;  // the kernel with the small LDS footprint takes blocks whose sides are at most this
-typedef const __attribute__((address_space(1))) uint8_t g_u8;  // pictures are global memory (the pointers come out of LDS): no flat loads
 
 __device__ int fpel_status(const SvtHipFpelDesc &d, const SvtHipSubpelJob &job) {
     if (!is_block_size(d.w, d.h))
@@ -65,23 +63,6 @@ template <int SIDE> struct Shared {  // LDS of one workgroup whose blocks have s
     uint8_t            src[SIDE * SIDE];
     uint8_t            tile[((TILE - 1 + SIDE) * (TILE - 1 + SIDE) + 15) / 16 * 16];  // a SIDE x SIDE block over a full tile
 };
-
-// n bytes of a pitched rectangle of global memory into LDS, row_bytes to a row; four loads in flight per thread
-__device__ __forceinline__ void stage_rows(uint8_t *lds, const uint8_t *global, int64_t pitch, int row_bytes, int n) {
-    g_u8 *g = (g_u8 *)global;
-    for (int k0 = threadIdx.x; k0 < n; k0 += 4 * NT) {
-        uint8_t v[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int k = k0 + j * NT, y = k / row_bytes;
-            v[j] = k < n ? g[y * pitch + (k - y * row_bytes)] : 0;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            if (k0 + j * NT < n)
-                lds[k0 + j * NT] = v[j];
-    }
-}
 
 struct Best {  // *best_mvx, *best_mvy, *best_cost
     int16_t  mvx, mvy;
@@ -157,7 +138,7 @@ template <class Shared> __device__ __forceinline__ void full_pel_search(Shared &
                 const int      tw = lx - fx + w, th = ly - fy + h;
                 const uint8_t *ref = d.ref + ((int64_t)cy + sy + fy) * (int64_t)d.ref_stride + ((int64_t)cx + sx + fx);
                 __syncthreads();  // the previous tile has been scored
-                stage_rows(sh.tile, ref, d.ref_stride, tw, tw * th);
+                stage_rows<NT>(sh.tile, ref, d.ref_stride, tw, tw * th);
                 if (entropy && tid < 2 * TILE) {  // the table entries the tile's positions need, one global load each instead of two per position
                     const int  t = tid & (TILE - 1);
                     const bool is_row = tid < TILE;
@@ -202,7 +183,7 @@ template <class Shared> __device__ __forceinline__ void full_pel_search(Shared &
                     if (sub == 0) {
                         uint32_t cost = acc;  // SAD, or svt_spatial_full_distortion_kernel cast to uint32_t
                         if (s.dist_type == SVT_HIP_FPEL_VAR)
-                            cost = acc - (uint32_t)(((int64_t)sum * sum) >> log2_area);  // svt_aom_mefn_ptr[bsize].vf
+                            cost = variance_of(sum, acc, log2_area).var;  // svt_aom_mefn_ptr[bsize].vf
                         const SvtHipMv mv = mv_of(s.mvy + py * 8, s.mvx + px * 8);  // stored into int16_t
                         if (entropy) {
                             const int16_t dr = (int16_t)(mv.row - d.ref_mv.row), dc = (int16_t)(mv.col - d.ref_mv.col);
@@ -336,11 +317,14 @@ template <int SIDE> __global__ __launch_bounds__(NT) void fpel_kernel(const SvtH
         __syncthreads();
         SvtHipFpelResult r = {};
         r.status = (uint8_t)fpel_status(sh.d, job);
+        // takes() of subpel_device.hpp spelt out, with a side above SMALL_SIDE as the large class: through any function the expression
+        // compiles to a few other scalar instructions, and the kernel with them measured 0.7 to 1.4 % slower
+        // (profiles/md_search_refactor_ab.json)
         const bool large = r.status == SVT_HIP_FPEL_OK && (sh.d.w > SMALL_SIDE || sh.d.h > SMALL_SIDE);
         if (large != (SIDE > SMALL_SIDE))
             continue;
         if (r.status == SVT_HIP_FPEL_OK) {
-            stage_rows(sh.src, sh.d.src, sh.d.src_stride, sh.d.w, sh.d.w * sh.d.h);
+            stage_rows<NT>(sh.src, sh.d.src, sh.d.src_stride, sh.d.w, sh.d.w * sh.d.h);
             search_desc(sh, job, r);
         }
         if (tid == 0)
@@ -354,18 +338,8 @@ int16_t narrow(int32_t status) { return SVT_HIP_FPEL_STATUS(status); }
 
 extern "C" int16_t svt_hip_fpel_search_batch(const SvtHipSubpelJob *job, const SvtHipFpelDesc *d_desc, SvtHipFpelResult *d_result, uint32_t n,
                                              void *stream) {
-    if (!job || !d_desc || !d_result)
-        return narrow(refuse("svt_hip_fpel_search_batch: bad argument"));
-    if (n == 0)
-        return narrow(SVT_HIP_OK);
-    TierBCall c("svt_hip_fpel_search_batch", stream);
-    if (!c.ok())
-        return narrow(c.status());
-    // a workgroup strides over the descriptors when there are more than the grid holds
-    const uint32_t small_grid = std::min(n, (uint32_t)cu_count() * 8u), large_grid = std::min(n, (uint32_t)cu_count() * 3u);
-    hipLaunchKernelGGL(fpel_kernel<SMALL_SIDE>, dim3(small_grid), dim3(NT), 0, c.stream(), *job, d_desc, d_result, n);
-    hipLaunchKernelGGL(fpel_kernel<128>, dim3(large_grid), dim3(NT), 0, c.stream(), *job, d_desc, d_result, n);
-    return narrow(c.finish());
+    return narrow(launch_two_classes("svt_hip_fpel_search_batch", job && d_desc && d_result, n, stream, fpel_kernel<SMALL_SIDE>, NT, 8, fpel_kernel<128>, NT, 3,
+                                     job ? *job : SvtHipSubpelJob{}, d_desc, d_result, n));
 }
 
 extern "C" void svt_hip_fpel_sq_windows(const SvtHipFpelSqCtrls *ctrls, uint8_t search_area_multiplier, uint16_t dist, SvtHipFpelLevel level[3]) {

@@ -16,8 +16,6 @@
 #include "common.hpp"
 #include "subpel_device.hpp"
 
-#include <algorithm>
-
 using namespace svthip;
 using namespace svthip::subpel;
 
@@ -70,21 +68,14 @@ __device__ __forceinline__ bool in_segments(const SvtHipObmcNeighbour *nb, int n
 template <int NT, bool LARGE>
 __global__ __launch_bounds__(NT) void obmc_target_kernel(const SvtHipObmcTargetDesc *__restrict__ d_desc, uint32_t *__restrict__ d_status, uint32_t n) {
     const int tid = threadIdx.x;
-    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-        const SvtHipObmcTargetDesc d = d_desc[i];
-        const int                  status = target_status(d);
-        const bool                 large = status != SVT_HIP_OBMC_BAD_SIZE && (int)d.w * d.h > SMALL_AREA;
-        if (large != LARGE)
-            continue;
-        if (tid == 0)
-            d_status[i] = (uint32_t)status;
-        const int w = d.w, h = d.h;
-        if (status != SVT_HIP_OBMC_OK) {
-            if (is_block_size(w, h) && d.wsrc && d.mask && aligned4(d.wsrc) && aligned4(d.mask))
-                for (int k = tid; k < w * h; k += NT) d.wsrc[k] = 0, d.mask[k] = 0;
-            continue;
-        }
-        const int      lw = log2_pow2(w);
+    // a bad descriptor whose outputs can be addressed gets them zeroed
+    const auto zero_outputs = [&](const SvtHipObmcTargetDesc &d) {
+        if (is_block_size(d.w, d.h) && d.wsrc && d.mask && aligned4(d.wsrc) && aligned4(d.mask))
+            for (int k = tid; k < d.w * d.h; k += NT) d.wsrc[k] = 0, d.mask[k] = 0;
+    };
+    const auto status_of = [](const SvtHipObmcTargetDesc &d) { return target_status(d); };
+    for_each_descriptor<LARGE>(d_desc, d_status, n, status_of, ByArea(), [&](const SvtHipObmcTargetDesc &d, uint32_t &) {
+        const int      w = d.w, h = d.h, lw = log2_pow2(w);
         const int      n_above = d.up_available ? d.n_above : 0, n_left = d.left_available ? d.n_left : 0;
         const int      ov_above = min(h, 64) >> 1, ov_left = min(w, 64) >> 1;
         const uint8_t *ramp_above = OBMC_RAMPS + ov_above - 1, *ramp_left = OBMC_RAMPS + ov_left - 1;
@@ -102,7 +93,7 @@ __global__ __launch_bounds__(NT) void obmc_target_kernel(const SvtHipObmcTargetD
             }
             d.wsrc[k] = (int)d.src[(int64_t)r * d.src_stride + c] * 4096 - ws, d.mask[k] = m;
         }
-    }
+    }, zero_outputs);
 }
 
 // ---- the search ------------------------------------------------------------------------------------------------------------------
@@ -128,12 +119,6 @@ __device__ int search_status(const SvtHipObmcSearchDesc &d, const SvtHipSubpelJo
     return SVT_HIP_OBMC_OK;
 }
 
-// svt_mv_cost (mcomp.h:136-139) of a difference that has been stored in the int16 fields of an MV
-__device__ int mv_rate(int16_t dr, int16_t dc, const SvtHipSubpelJob &job) {
-    const int joint = dr == 0 ? (dc == 0 ? 0 : 1) : (dc == 0 ? 2 : 3);
-    return job.mvjcost[joint] + job.mvcost[0][min(max((int)dr, MV_LOW), MV_UPP)] + job.mvcost[1][min(max((int)dc, MV_LOW), MV_UPP)];
-}
-
 // mvsad_err_cost / mvsad_err_cost_light (av1me.c:237-261) of the full-pel vector (row, col) against ref_mv >> 3
 __device__ uint32_t mvsad_err_cost(int row, int col, const SvtHipObmcSearchDesc &d, const SvtHipSubpelJob &job) {
     const int dr = row - (d.ref_mv.row >> 3), dc = col - (d.ref_mv.col >> 3);
@@ -147,22 +132,20 @@ __device__ uint32_t mv_err_cost(int row, int col, const SvtHipObmcSearchDesc &d,
     const int dr = (int16_t)row - d.ref_mv.row, dc = (int16_t)col - d.ref_mv.col;
     if (d.approx_inter_rate)
         return 1296u + 50u * ((uint32_t)abs(dc) + (uint32_t)abs(dr));
-    return (uint32_t)(int)(((int64_t)mv_rate((int16_t)dr, (int16_t)dc, job) * d.error_per_bit + (1 << 13)) >> 14);
+    return (uint32_t)mv_entropy_cost(mv_rate((int16_t)dr, (int16_t)dc, job), d.error_per_bit);
 }
 
 struct Block : Window {
     const int32_t *wsrc, *mask;  // global, [h][w]
 };
 
-struct Error {
-    uint32_t var, sse;
-};
-
 // svt_aom_obmc_sad* of the (up to) 8 neighbours of the full-pel vector (row, col) at once, or with n_sites == 1 of the vector itself:
 // site j is (row, col) + SITES[j].  One pass over wsrc and mask.  red: 8 words per wave.
-template <int NT> __device__ __forceinline__ void weighted_sads(const Block &b, int row, int col, int n_sites, bool centre, uint32_t sad[8]) {
+template <int NT> __device__ __forceinline__ void weighted_sads(const Block &b, int row, int col, int n_sites, bool centre, uint32_t (&sad)[8]) {
     const int     tid = threadIdx.x, w = b.w, lw = b.lw, ws = b.win_stride;
     const int     oy = row - b.base_row + b.margin, ox = col - b.base_col + b.margin;
+    if (NT > 64)
+        __syncthreads();  // the previous pass's sums have been read from red
 #pragma unroll
     for (int j = 0; j < 8; j++) sad[j] = 0;
     for (int i = tid; i < (b.h << lw); i += NT) {
@@ -178,42 +161,22 @@ template <int NT> __device__ __forceinline__ void weighted_sads(const Block &b, 
                     sad[j] += (uint32_t)(abs(t - (int)p[SITE_ROW[j] * ws + SITE_COL[j]] * m) + 2048) >> 12;
         }
     }
-#pragma unroll
-    for (int j = 0; j < 8; j++) sad[j] = blend::wave_sum(sad[j]);
-    if (NT > 64) {
-        __syncthreads();  // the previous pass's sums have been read from red
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int j = 0; j < 8; j++) b.red[8 * (tid >> 6) + j] = (int32_t)sad[j];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            sad[j] = 0;
-#pragma unroll
-            for (int v = 0; v < NT / 64; v++) sad[j] += (uint32_t)b.red[8 * v + j];
-        }
-    }
+    block_sums<NT>(b.red, sad);
 }
 
 // upsampled_obmc_pref_error (av1me.c:901-938): svt_aom_upsampled_pred_c, then svt_aom_obmc_variance* (variance.c:347-373)
 template <int NT> __device__ __forceinline__ Error weighted_variance(const Block &b, int row, int col) {
-    int      sum = 0;
-    uint32_t sse = 0;
-    predict<NT>(b, mv_of(row, col), [&](int i, int, int, int pre) {
+    return predicted_error<NT>(b, mv_of(row, col), [&](int i, int, int, int pre) {
         const int v = b.wsrc[i] - pre * b.mask[i];
-        const int diff = v < 0 ? -((-v + 2048) >> 12) : (v + 2048) >> 12;  // ROUND_POWER_OF_TWO_SIGNED
-        sum += diff, sse += (uint32_t)(diff * diff);
+        return v < 0 ? -((-v + 2048) >> 12) : (v + 2048) >> 12;  // ROUND_POWER_OF_TWO_SIGNED
     });
-    block_sums<NT>(b.red, sum, sse);
-    return {sse - (uint32_t)(((int64_t)sum * sum) >> b.log2_area), sse};
 }
 
 struct Tree {  // svt_av1_find_best_obmc_sub_pixel_tree_up's running best
     const SvtHipObmcSearchDesc &d;
     const SvtHipSubpelJob      &job;
     const Block                &b;
-    int                         minc, maxc, minr, maxr;
+    int32_t                     lim[4];  // col_min, col_max, row_min, row_max
     int                         br, bc;
     uint32_t                    besterr, sse1;
     int                         distortion;
@@ -221,7 +184,7 @@ struct Tree {  // svt_av1_find_best_obmc_sub_pixel_tree_up's running best
     // the body of CHECK_BETTER1 and of the loop's own checks: the cost of (r, c), INT_MAX outside the limits; *won: it is the new best
     template <int NT> __device__ uint32_t check(int r, int c, bool *won) {
         *won = false;
-        if (!(c >= minc && c <= maxc && r >= minr && r <= maxr))
+        if (!(c >= lim[0] && c <= lim[1] && r >= lim[2] && r <= lim[3]))
             return 0x7FFFFFFFu;
         const Error    e = weighted_variance<NT>(b, r, c);
         const uint32_t cost = e.var + mv_err_cost(r, c, d, job);
@@ -289,11 +252,12 @@ __global__ __launch_bounds__(NT) void obmc_search_kernel(const SvtHipSubpelJob j
     __shared__ uint8_t tmp[TMP_BYTES];
     __shared__ int32_t red[8 * (NT / 64)];
     const int          tid = threadIdx.x;
+    // for_each_descriptor written out and, below, not stage_rows: with them the search measured 1 to 4 % slower
+    // (profiles/md_search_refactor_ab.json)
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         const SvtHipObmcSearchDesc d = d_desc[i];
         const int                  status = search_status(d, job);
-        const bool                 large = status != SVT_HIP_OBMC_BAD_SIZE && (int)d.w * d.h > SMALL_AREA;
-        if (large != LARGE)
+        if (!takes(LARGE, status, [&] { return ByArea()(d); }))
             continue;
         SvtHipObmcSearchResult r = {};
         r.status = (uint8_t)status;
@@ -350,10 +314,7 @@ __global__ __launch_bounds__(NT) void obmc_search_kernel(const SvtHipSubpelJob j
         int br = row * 8, bc = col * 8;
         if (d.do_frac_refine) {
             Tree s = {d, job, b};
-            // set_subpel_mv_search_range (av1me.c:778-790) on the limits from before the full-pel narrowing
-            const int max_mv = MAX_FULL_PEL_VAL * 8;
-            s.minc = max(MV_LOW + 1, max(d.raw_limits[0] * 8, d.ref_mv.col - max_mv)), s.maxc = min(MV_UPP - 1, min(d.raw_limits[1] * 8, d.ref_mv.col + max_mv));
-            s.minr = max(MV_LOW + 1, max(d.raw_limits[2] * 8, d.ref_mv.row - max_mv)), s.maxr = min(MV_UPP - 1, min(d.raw_limits[3] * 8, d.ref_mv.row + max_mv));
+            set_subpel_mv_search_range(s.lim, d.raw_limits, d.ref_mv);  // on the limits from before the full-pel narrowing
             s.br = br, s.bc = bc;
             tree_search<NT>(s);
             br = s.br, bc = s.bc;
@@ -373,34 +334,15 @@ __global__ __launch_bounds__(NT) void obmc_search_kernel(const SvtHipSubpelJob j
 }  // namespace
 
 extern "C" int32_t svt_hip_obmc_target_batch(const SvtHipObmcTargetDesc *d_desc, uint32_t *d_status, uint32_t n, void *stream) {
-    if (!d_desc || !d_status)
-        return refuse("svt_hip_obmc_target_batch: bad argument");
-    if (n == 0)
-        return SVT_HIP_OK;
-    TierBCall c("svt_hip_obmc_target_batch", stream);
-    if (!c.ok())
-        return c.status();
-    const uint32_t small_grid = std::min(n, (uint32_t)cu_count() * 32u), large_grid = std::min(n, (uint32_t)cu_count() * 8u);
-    hipLaunchKernelGGL((obmc_target_kernel<64, false>), dim3(small_grid), dim3(64), 0, c.stream(), d_desc, d_status, n);
-    hipLaunchKernelGGL((obmc_target_kernel<256, true>), dim3(large_grid), dim3(256), 0, c.stream(), d_desc, d_status, n);
-    return c.finish();
+    return launch_two_classes("svt_hip_obmc_target_batch", d_desc && d_status, n, stream, obmc_target_kernel<64, false>, 64, 32, obmc_target_kernel<256, true>,
+                              256, 8, d_desc, d_status, n);
 }
 
 extern "C" int32_t svt_hip_obmc_search_batch(const SvtHipSubpelJob *job, const SvtHipObmcSearchDesc *d_desc, SvtHipObmcSearchResult *d_result,
                                              uint32_t n, void *stream) {
-    if (!job || !d_desc || !d_result)
-        return refuse("svt_hip_obmc_search_batch: bad argument");
-    if (n == 0)
-        return SVT_HIP_OK;
-    TierBCall c("svt_hip_obmc_search_batch", stream);
-    if (!c.ok())
-        return c.status();
-    // a workgroup strides over the descriptors when there are more than the grid holds.  The windows: 16 x 16, 8 x 32 and 32 x 8 at
-    // R = 16 are the largest of the single-wave sizes (72 x 48 bytes), 128 x 128 of the others (168 x 168)
-    const uint32_t small_grid = std::min(n, (uint32_t)cu_count() * 32u), large_grid = std::min(n, (uint32_t)cu_count() * 8u);
-    hipLaunchKernelGGL((obmc_search_kernel<64, 72 * 48, 480, false>), dim3(small_grid), dim3(64), 0, c.stream(), *job, d_desc, d_result, n);
-    hipLaunchKernelGGL((obmc_search_kernel<256, 168 * 168, 135 * 128, true>), dim3(large_grid), dim3(256), 0, c.stream(), *job, d_desc, d_result, n);
-    return c.finish();
+    // The windows: 16 x 16, 8 x 32 and 32 x 8 at R = 16 are the largest of the single-wave sizes (72 x 48 bytes), 128 x 128 of the others (168 x 168)
+    return launch_two_classes("svt_hip_obmc_search_batch", job && d_desc && d_result, n, stream, obmc_search_kernel<64, 72 * 48, 480, false>, 64, 32,
+                              obmc_search_kernel<256, 168 * 168, 135 * 128, true>, 256, 8, job ? *job : SvtHipSubpelJob{}, d_desc, d_result, n);
 }
 
 extern "C" int32_t svt_hip_obmc_mv_limits(int32_t mi_row, int32_t mi_col, int32_t mi_width, int32_t mi_height, int32_t mi_rows,
@@ -410,12 +352,8 @@ extern "C" int32_t svt_hip_obmc_mv_limits(int32_t mi_row, int32_t mi_col, int32_
     // mode_decision.c:2459-2462 (MI_SIZE 4, AOM_INTERP_EXTEND 4)
     raw_limits[0] = -(((mi_col + mi_width) * 4) + 4), raw_limits[1] = (mi_cols - mi_col) * 4 + 4;
     raw_limits[2] = -(((mi_row + mi_height) * 4) + 4), raw_limits[3] = (mi_rows - mi_row) * 4 + 4;
-    // svt_av1_set_mv_search_range (av1me.c:205-226)
-    const int max_fp = MAX_FULL_PEL_VAL;
-    fp_limits[0] = std::max(raw_limits[0], std::max((ref_mv->col >> 3) - max_fp + !!(ref_mv->col & 7), (MV_LOW >> 3) + 1));
-    fp_limits[1] = std::min(raw_limits[1], std::min((ref_mv->col >> 3) + max_fp, (MV_UPP >> 3) - 1));
-    fp_limits[2] = std::max(raw_limits[2], std::max((ref_mv->row >> 3) - max_fp + !!(ref_mv->row & 7), (MV_LOW >> 3) + 1));
-    fp_limits[3] = std::min(raw_limits[3], std::min((ref_mv->row >> 3) + max_fp, (MV_UPP >> 3) - 1));
+    for (int k = 0; k < 4; k++) fp_limits[k] = raw_limits[k];
+    set_mv_search_range(fp_limits, *ref_mv);
     return SVT_HIP_OK;
 }
 

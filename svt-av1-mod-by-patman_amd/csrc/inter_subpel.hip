@@ -15,8 +15,6 @@
 #include "common.hpp"
 #include "subpel_device.hpp"
 
-#include <algorithm>
-
 using namespace svthip;
 using namespace svthip::subpel;
 
@@ -48,20 +46,9 @@ struct Block : Window {  // what a candidate's error is computed from: the windo
     int            src_stride;
 };
 
-struct Error {
-    uint32_t var, sse;
-};
-
 // vf(prediction at mv, src): the variance and the sum of squares.  against_128: vf(.., svt_aom_eb_av1_var_offs, 0, ..) instead.
 template <int NT> __device__ __forceinline__ Error candidate_error(const Block &b, SvtHipMv mv, bool against_128) {
-    int      sum = 0;
-    uint32_t sse = 0;
-    predict<NT>(b, mv, [&](int, int r, int c, int pre) {
-        const int diff = pre - (against_128 ? 128 : (int)b.src[r * b.src_stride + c]);
-        sum += diff, sse += (uint32_t)(diff * diff);
-    });
-    block_sums<NT>(b.red, sum, sse);
-    return {sse - (uint32_t)(((int64_t)sum * sum) >> b.log2_area), sse};
+    return predicted_error<NT>(b, mv, [&](int, int r, int c, int pre) { return pre - (against_128 ? 128 : (int)b.src[r * b.src_stride + c]); });
 }
 
 struct Search {  // the running best of one search and what the checks need
@@ -224,20 +211,8 @@ __global__ __launch_bounds__(NT) void subpel_kernel(const SvtHipSubpelJob job, c
     __shared__ uint8_t win[WIN_BYTES];
     __shared__ uint8_t tmp[TMP_BYTES];
     __shared__ int32_t red[2 * (NT / 64)];
-    const int          tid = threadIdx.x;
-    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-        const SvtHipSubpelDesc d = d_desc[i];
-        const int              status = subpel_status(d, job);
-        const bool             large = status != SVT_HIP_SUBPEL_BAD_SIZE && (int)d.w * d.h > SMALL_AREA;
-        if (large != LARGE)
-            continue;
-        SvtHipSubpelResult r = {};
-        r.status = (uint8_t)status;
-        if (status != SVT_HIP_SUBPEL_OK) {
-            if (tid == 0)
-                d_result[i] = r;
-            continue;
-        }
+    const auto         status_of = [&](const SvtHipSubpelDesc &d) { return subpel_status(d, job); };
+    for_each_descriptor<LARGE>(d_desc, d_result, n, status_of, ByArea(), [&](const SvtHipSubpelDesc &d, SvtHipSubpelResult &r) {
         Block b;
         b.win = win, b.tmp = tmp, b.red = red, b.src = d.src, b.src_stride = (int)d.src_stride, b.w = d.w, b.h = d.h;
         b.lw = log2_pow2(d.w), b.win_stride = d.w + 8, b.log2_area = b.lw + log2_pow2(d.h);
@@ -245,7 +220,8 @@ __global__ __launch_bounds__(NT) void subpel_kernel(const SvtHipSubpelJob job, c
         b.table = d.method == SVT_HIP_SUBPEL_TREE_PRUNED ? 0 : d.subpel_search_type - SVT_HIP_SUBPEL_USE_2_TAPS;
         __syncthreads();  // the previous block's last candidate has read win
         const uint8_t *ref = d.ref + ((int64_t)b.base_row - 4) * (int64_t)d.ref_stride + (b.base_col - 4);
-        for (int k = tid; k < (d.w + 8) * (d.h + 8); k += NT) {
+        // not stage_rows: with it the single-wave kernel comes out at 64 VGPRs instead of 65, another occupancy step than it was measured at
+        for (int k = threadIdx.x; k < (d.w + 8) * (d.h + 8); k += NT) {
             const int y = k / b.win_stride, x = k - y * b.win_stride;
             win[k] = ref[(int64_t)y * d.ref_stride + x];
         }
@@ -256,27 +232,15 @@ __global__ __launch_bounds__(NT) void subpel_kernel(const SvtHipSubpelJob job, c
         r.fullpel_err = s.besterr;
         r.exit = (uint8_t)search_block<NT>(s);
         r.best_mv = s.best_mv, r.besterr = (int32_t)s.besterr, r.distortion = s.distortion, r.sse = s.sse1;
-        if (tid == 0)
-            d_result[i] = r;
-    }
+    });
 }
 
 }  // namespace
 
 extern "C" int32_t svt_hip_subpel_search_batch(const SvtHipSubpelJob *job, const SvtHipSubpelDesc *d_desc, SvtHipSubpelResult *d_result,
                                                uint32_t n, void *stream) {
-    if (!job || !d_desc || !d_result)
-        return refuse("svt_hip_subpel_search_batch: bad argument");
-    if (n == 0)
-        return SVT_HIP_OK;
-    TierBCall c("svt_hip_subpel_search_batch", stream);
-    if (!c.ok())
-        return c.status();
-    // a workgroup strides over the descriptors when there are more than the grid holds
-    const uint32_t small_grid = std::min(n, (uint32_t)cu_count() * 32u), large_grid = std::min(n, (uint32_t)cu_count() * 8u);
-    hipLaunchKernelGGL((subpel_kernel<64, 640, 480, false>), dim3(small_grid), dim3(64), 0, c.stream(), *job, d_desc, d_result, n);
-    hipLaunchKernelGGL((subpel_kernel<256, 136 * 136, 135 * 128, true>), dim3(large_grid), dim3(256), 0, c.stream(), *job, d_desc, d_result, n);
-    return c.finish();
+    return launch_two_classes("svt_hip_subpel_search_batch", job && d_desc && d_result, n, stream, subpel_kernel<64, 640, 480, false>, 64, 32,
+                              subpel_kernel<256, 136 * 136, 135 * 128, true>, 256, 8, job ? *job : SvtHipSubpelJob{}, d_desc, d_result, n);
 }
 
 extern "C" int32_t svt_hip_subpel_mv_limits(int32_t mi_row, int32_t mi_col, int32_t mi_width, int32_t mi_height, int32_t mi_rows,
@@ -284,20 +248,9 @@ extern "C" int32_t svt_hip_subpel_mv_limits(int32_t mi_row, int32_t mi_col, int3
     if (!ref_mv || !limits)
         return refuse("svt_hip_subpel_mv_limits: bad argument");
     // product_coding_loop.c:2532-2535 (MI_SIZE 4, AOM_INTERP_EXTEND 4)
-    int col_min = -(((mi_col + mi_width) * 4) + 4), col_max = (mi_cols - mi_col) * 4 + 4;
-    int row_min = -(((mi_row + mi_height) * 4) + 4), row_max = (mi_rows - mi_row) * 4 + 4;
-    // svt_av1_set_mv_search_range (av1me.c:205-226)
-    const int mv_low = MV_LOW, mv_upp = MV_UPP, max_fp = MAX_FULL_PEL_VAL;
-    col_min = std::max(col_min, std::max((ref_mv->col >> 3) - max_fp + !!(ref_mv->col & 7), (mv_low >> 3) + 1));
-    row_min = std::max(row_min, std::max((ref_mv->row >> 3) - max_fp + !!(ref_mv->row & 7), (mv_low >> 3) + 1));
-    col_max = std::min(col_max, std::min((ref_mv->col >> 3) + max_fp, (mv_upp >> 3) - 1));
-    row_max = std::min(row_max, std::min((ref_mv->row >> 3) + max_fp, (mv_upp >> 3) - 1));
-    // svt_av1_set_subpel_mv_search_range (mcomp.h:113-125)
-    const int max_mv = max_fp * 8;
-    limits[0] = std::max(mv_low + 1, std::max(col_min * 8, ref_mv->col - max_mv));
-    limits[1] = std::min(mv_upp - 1, std::min(col_max * 8, ref_mv->col + max_mv));
-    limits[2] = std::max(mv_low + 1, std::max(row_min * 8, ref_mv->row - max_mv));
-    limits[3] = std::min(mv_upp - 1, std::min(row_max * 8, ref_mv->row + max_mv));
+    int32_t fp[4] = {-(((mi_col + mi_width) * 4) + 4), (mi_cols - mi_col) * 4 + 4, -(((mi_row + mi_height) * 4) + 4), (mi_rows - mi_row) * 4 + 4};
+    set_mv_search_range(fp, *ref_mv);
+    set_subpel_mv_search_range(limits, fp, *ref_mv);
     return SVT_HIP_OK;
 }
 

@@ -216,26 +216,28 @@ def compound_mask_search_batch(lib, descs, stream=None, fill=0xA5):
     return d_res.download(np.dtype(abi.MASK_SEARCH_RESULT_DTYPE), (len(descs),), stream)
 
 
+def _search_batch(lib, export, result_ctype, result_dtype, job, descs, stream, guard, fill):
+    """One call of a motion-search export under the abi.SubpelJob `job`: (results as a record array of result_dtype, the `guard` bytes before
+    and after them)"""
+    n = len(descs)
+    d_desc = upload_descriptors(lib, descs, stream)
+    d_out = Guarded(lib, C.sizeof(result_ctype) * n, guard, fill, stream)
+    _call(lib, export, C.byref(job), d_desc.ptr, d_out.ptr, n, stream=stream)
+    return d_out.read(result_dtype)
+
+
 def subpel_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
     """svt_hip_subpel_search_batch over a record array of abi.SUBPEL_DESC_DTYPE (or a list of abi.SubpelDesc) under the abi.SubpelJob `job`
     (one call).  Returns (results as a record array of abi.SUBPEL_RESULT_DTYPE, the `guard` bytes before and after them: still `fill` if
     untouched)."""
-    n = len(descs)
-    d_desc = upload_descriptors(lib, descs, stream)
-    d_out = Guarded(lib, C.sizeof(abi.SubpelResult) * n, guard, fill, stream)
-    _call(lib, "svt_hip_subpel_search_batch", C.byref(job), d_desc.ptr, d_out.ptr, n, stream=stream)
-    return d_out.read(abi.SUBPEL_RESULT_DTYPE)
+    return _search_batch(lib, "svt_hip_subpel_search_batch", abi.SubpelResult, abi.SUBPEL_RESULT_DTYPE, job, descs, stream, guard, fill)
 
 
 def fpel_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
     """svt_hip_fpel_search_batch over a record array of abi.FPEL_DESC_DTYPE (or a list of abi.FpelDesc) under the abi.SubpelJob `job`
     (one call).  Returns (results as a record array of abi.FPEL_RESULT_DTYPE, the `guard` bytes before and after them: still `fill` if
     untouched)."""
-    n = len(descs)
-    d_desc = upload_descriptors(lib, descs, stream)
-    d_out = Guarded(lib, C.sizeof(abi.FpelResult) * n, guard, fill, stream)
-    _call(lib, "svt_hip_fpel_search_batch", C.byref(job), d_desc.ptr, d_out.ptr, n, stream=stream)
-    return d_out.read(abi.FPEL_RESULT_DTYPE)
+    return _search_batch(lib, "svt_hip_fpel_search_batch", abi.FpelResult, abi.FPEL_RESULT_DTYPE, job, descs, stream, guard, fill)
 
 
 def obmc_target_batch(lib, descs, stream=None, guard=64, fill=0xA5):
@@ -252,11 +254,7 @@ def obmc_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
     """svt_hip_obmc_search_batch over a record array of abi.OBMC_SEARCH_DESC_DTYPE (or a list of abi.ObmcSearchDesc) under the abi.SubpelJob
     `job` (one call).  Returns (results as a record array of abi.OBMC_SEARCH_RESULT_DTYPE, the `guard` bytes before and after them: still
     `fill` if untouched)."""
-    n = len(descs)
-    d_desc = upload_descriptors(lib, descs, stream)
-    d_out = Guarded(lib, C.sizeof(abi.ObmcSearchResult) * n, guard, fill, stream)
-    _call(lib, "svt_hip_obmc_search_batch", C.byref(job), d_desc.ptr, d_out.ptr, n, stream=stream)
-    return d_out.read(abi.OBMC_SEARCH_RESULT_DTYPE)
+    return _search_batch(lib, "svt_hip_obmc_search_batch", abi.ObmcSearchResult, abi.OBMC_SEARCH_RESULT_DTYPE, job, descs, stream, guard, fill)
 
 
 def txb_cost_batch(lib, d_base, descs, tables, w, h, d_txfm_result=None, d_distortion=None, stream=None, tables_in_lds=None, guard=64, fill=0xA5):

@@ -14,7 +14,8 @@ import os
 import numpy as np
 
 import arena
-from subpel_cases import MV_LOW, MV_UPP, SIZES, i16, mv_cost_tables
+import md_search_cases
+from md_search_cases import MV_LOW, MV_UPP, SIZES, i16, mv_cost_tables
 from svtav1_hip import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -613,36 +614,18 @@ def pin_pictures(c):
 
 
 # ---- descriptors for the device -------------------------------------------------------------------------------------------------
-class Arena:
-    """The pictures of a list of cases in one host buffer, each plane at its own byte offset with its own stride, and the cost tables
-    behind them.  layout(i) -> (offset shift in bytes, extra stride) lets a test ask for unaligned pointers and odd strides: then the
-    restatement is run on the widened planes (the psad overshoot reads the stride padding)."""
+class Arena(md_search_cases.Arena):
+    """The pictures of a list of cases and the cost tables in one host buffer.  `views`: the planes as widened by the layout, on which the
+    restatement is then run (the psad overshoot reads the stride padding)."""
 
     def __init__(self, cases, layout=lambda i: (0, 0)):
-        self.cases, self.planes, self.views, ab = cases, [], [], arena.Arena(fill=arena.GUARD, tail=64)
+        super().__init__(cases, layout)
+        self.planes, self.views = [], []
         for i, c in enumerate(cases):
-            shift, extra = layout(i)
-            entry, view = [], []
-            for name, plane in zip(("src", "ref"), pictures(c)):
-                stride = plane.shape[1] + extra
-                buf = np.full((plane.shape[0], stride), 0x5A, np.uint8)
-                buf[:, :plane.shape[1]] = plane
-                mem = memory(buf)
-                at = ab.add(f"{name} of case {i}", mem, align=64, gap=0, skew=shift)
-                entry.append((at + (c.geo.org_y + c.geo.blk_y) * stride + c.geo.org_x + c.geo.blk_x, stride))
-                view.append(buf)
-            self.planes.append(entry)
-            self.views.append(view)
-        self.mvj, row, col = mv_cost_tables()
-        self.table_at = [ab.add(name, t, align=64, gap=0) - 4 * MV_LOW for name, t in (("mvcost row", row), ("mvcost col", col))]     # the centres
-        self.regions = ab.regions
-        self.host = ab.build()
-
-    def job(self, base):
-        j = abi.SubpelJob()
-        j.mvjcost[:] = [int(v) for v in self.mvj]
-        j.mvcost[0], j.mvcost[1] = base + self.table_at[0], base + self.table_at[1]
-        return j
+            placed = [self.place(i, name, plane, memory) for name, plane in zip(("src", "ref"), pictures(c))]
+            self.planes.append([(at + (c.geo.org_y + c.geo.blk_y) * stride + c.geo.org_x + c.geo.blk_x, stride) for at, stride, _ in placed])
+            self.views.append([buf for _, _, buf in placed])
+        self.finish()
 
     def descs(self, base):
         d = np.zeros(len(self.cases), abi.FPEL_DESC_DTYPE)

@@ -14,8 +14,9 @@ import os
 
 import numpy as np
 
-import arena
-from subpel_cases import FILTERS, MAX_FULL_PEL_VAL, MV_LOW, MV_UPP, SIZES, i16, mv_cost_tables
+import md_search_cases
+from md_search_cases import MAX_FULL_PEL_VAL, MV_LOW, MV_UPP, SIZES, i16, mv_cost_tables  # noqa: F401  (the tests read them from here)
+from subpel_cases import FILTERS
 from svtav1_hip import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -133,11 +134,8 @@ def target(c, src, above, left, segs=None):
 
 def mv_limits(mi_row, mi_col, mi_w, mi_h, mi_rows, mi_cols, ref_mv):
     """mode_decision.c:2459-2462 and svt_av1_set_mv_search_range -> (raw, fp): (col_min, col_max, row_min, row_max) each, full-pel"""
-    raw = (-(((mi_col + mi_w) * 4) + 4), (mi_cols - mi_col) * 4 + 4, -(((mi_row + mi_h) * 4) + 4), (mi_rows - mi_row) * 4 + 4)
-    r, c = ref_mv
-    fp = (max(raw[0], (c >> 3) - MAX_FULL_PEL_VAL + int(c & 7 != 0), (MV_LOW >> 3) + 1), min(raw[1], (c >> 3) + MAX_FULL_PEL_VAL, (MV_UPP >> 3) - 1),
-          max(raw[2], (r >> 3) - MAX_FULL_PEL_VAL + int(r & 7 != 0), (MV_LOW >> 3) + 1), min(raw[3], (r >> 3) + MAX_FULL_PEL_VAL, (MV_UPP >> 3) - 1))
-    return raw, fp
+    raw = md_search_cases.block_mv_limits(mi_row, mi_col, mi_w, mi_h, mi_rows, mi_cols)
+    return raw, md_search_cases.set_mv_search_range(raw, ref_mv)
 
 
 def case_limits(c):
@@ -253,9 +251,7 @@ class Search:
     def tree(self, br, bc):
         """svt_av1_find_best_obmc_sub_pixel_tree_up (av1me.c:963-1132), accurate path -> (br, bc)"""
         c = self.c
-        m = MAX_FULL_PEL_VAL * 8      # set_subpel_mv_search_range (av1me.c:778-790) on the limits before the full-pel narrowing
-        self.sub = (max(MV_LOW + 1, max(self.raw[0] * 8, c.ref_mv[1] - m)), min(MV_UPP - 1, min(self.raw[1] * 8, c.ref_mv[1] + m)),
-                    max(MV_LOW + 1, max(self.raw[2] * 8, c.ref_mv[0] - m)), min(MV_UPP - 1, min(self.raw[3] * 8, c.ref_mv[0] + m)))
+        self.sub = md_search_cases.set_subpel_mv_search_range(self.raw, c.ref_mv)      # on the limits before the full-pel narrowing
         rounds = 3 - c.stop
         if not c.hp and rounds == 3:
             rounds = 2
@@ -529,39 +525,27 @@ class Pin:
 
 
 # ---- descriptors for the device -------------------------------------------------------------------------------------------------
-class Arena:
-    """The samples of a list of cases in one host buffer, each plane at its own byte offset with its own stride, room for every case's wsrc
-    and mask, and the cost tables behind them.  layout(i) -> (offset shift in bytes, extra stride) lets a test ask for unaligned pointers and
-    odd strides of the uint8 planes; wsrc and mask stay 4-byte aligned."""
+class Arena(md_search_cases.Arena):
+    """The samples of a list of cases, room for every case's wsrc and mask, and the cost tables in one host buffer.  The layout moves the
+    uint8 planes; wsrc and mask stay 4-byte aligned."""
 
     def __init__(self, cases, layout=lambda i: (0, 0), restated=None):
-        self.cases, self.planes, self.outputs, ab = cases, [], [], arena.Arena(fill=arena.GUARD, tail=64)
+        super().__init__(cases, layout)
+        self.planes, self.outputs = [], []
         self.restated = restated or [Restated(c) for c in cases]
         for i, (c, r) in enumerate(zip(cases, self.restated)):
-            shift, extra = layout(i)
             entry = {}
             for name, plane in (("ref", r.ref), ("src", r.src), ("above", r.above), ("left", r.left)):
-                stride = plane.shape[1] + extra
-                buf = np.full((plane.shape[0], stride), 0x5A, np.uint8)
-                buf[:, :plane.shape[1]] = plane
-                at = ab.add(f"{name} of case {i}", buf, align=64, gap=0, skew=shift)
+                at, stride, _ = self.place(i, name, plane)
                 entry[name] = (at + (BORDER * stride + BORDER if name == "ref" else 0), stride)
             self.planes.append(entry)
-            self.outputs.append(tuple(ab.add(f"{name} of case {i}", nbytes=4 * c.w * c.h, align=64, gap=64) for name in ("wsrc", "mask")))
-        self.mvj, row, col = mv_cost_tables()
-        self.table_at = [ab.add(name, t, align=64, gap=0) - 4 * MV_LOW for name, t in (("mvcost row", row), ("mvcost col", col))]     # the centres
-        self.regions, self.host = ab.regions, ab.build()
+            self.outputs.append(tuple(self.ab.add(f"{name} of case {i}", nbytes=4 * c.w * c.h, align=64, gap=64) for name in ("wsrc", "mask")))
+        self.finish()
 
     def declared(self, picks=None):
         """(offset, bytes) of the wsrc and mask arrays of the cases `picks` (all by default)"""
         picks = range(len(self.cases)) if picks is None else picks
         return [(at, 4 * self.cases[i].w * self.cases[i].h) for i in picks for at in self.outputs[i]]
-
-    def job(self, base):
-        j = abi.SubpelJob()
-        j.mvjcost[:] = [int(v) for v in self.mvj]
-        j.mvcost[0], j.mvcost[1] = base + self.table_at[0], base + self.table_at[1]
-        return j
 
     def target_descs(self, base):
         d = np.zeros(len(self.cases), abi.OBMC_TARGET_DESC_DTYPE)
@@ -582,6 +566,8 @@ class Arena:
             (ref, ref_stride), (wsrc, mask) = self.planes[i]["ref"], self.outputs[i]
             d[i] = fill_search_desc(c, base + wsrc, base + mask, base + ref, ref_stride)
         return d
+
+    descs = search_descs
 
 
 def fill_search_desc(c, wsrc, mask, ref, ref_stride):

@@ -12,18 +12,15 @@ import os
 
 import numpy as np
 
-import arena
+import md_search_cases
+from md_search_cases import MAX_FULL_PEL_VAL, MV_LOW, MV_UPP, SIZES, i16, mv_cost_tables  # noqa: F401  (re-exported)
 from svtav1_hip import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "subpel.npz")
 
-# init_fn_ptr (av1me.c:31-170)
-SIZES = ((4, 4), (4, 8), (8, 4), (8, 8), (8, 16), (16, 8), (16, 16), (16, 32), (32, 16), (32, 32), (32, 64), (64, 32), (64, 64),
-         (64, 128), (128, 64), (128, 128), (4, 16), (16, 4), (8, 32), (32, 8), (16, 64), (64, 16))
 TREE, PRUNED = abi.SUBPEL_TREE, abi.SUBPEL_TREE_PRUNED
 ENTROPY, L1_LOWRES, L1_MIDRES, L1_HDRES, OPT, NONE = range(6)     # MV_COST_TYPE (mcomp.h:29-36)
-MV_LOW, MV_UPP, MAX_FULL_PEL_VAL = -(1 << 14), 1 << 14, 1023
 INT_MAX = 2 ** 31 - 1
 BORDER = 24                                                        # samples around the block in a generated picture
 RESULT_FIELDS = ("best_row", "best_col", "besterr", "distortion", "sse", "fullpel_err", "exit")
@@ -43,18 +40,6 @@ LimitCase = collections.namedtuple("LimitCase", "mi_row mi_col mi_w mi_h mi_rows
 
 
 # ---- generated inputs -----------------------------------------------------------------------------------------------------------
-def mv_cost_tables():
-    """(mvjcost[4], the row and the column table over MV_LOW .. MV_UPP): made up, shaped like the reference's (a cost per magnitude
-    class plus a little for the fractional bits), different for rows and columns."""
-    v = np.abs(np.arange(MV_LOW, MV_UPP + 1, dtype=np.int64))
-    bits = np.zeros_like(v)
-    for k in range(15):
-        bits += (v >> k) > 0
-    row = 300 + 410 * bits + 35 * (v & 7) + 17 * ((v >> 3) & 3)
-    col = 260 + 450 * bits + 29 * (v & 7) + 11 * ((v >> 3) & 5)
-    return np.array([130, 640, 580, 910], np.int32), row.astype(np.int32), col.astype(np.int32)
-
-
 def pictures(c):
     """(src, ref): two uint8 planes of (h + 2 BORDER) x (w + 2 BORDER) with the block at (BORDER, BORDER).  A coarse random grid is
     interpolated, in integers, to eight times the picture's resolution; ref samples it at the sample positions, src at the positions
@@ -91,10 +76,6 @@ def pictures(c):
 
 
 # ---- restatement ----------------------------------------------------------------------------------------------------------------
-def i16(v):
-    return ((int(v) + 0x8000) & 0xFFFF) - 0x8000
-
-
 def c_div(a, b):
     """C's integer division (towards zero)"""
     q = abs(a) // abs(b)
@@ -104,16 +85,9 @@ def c_div(a, b):
 def mv_limits(lc):
     """product_coding_loop.c:2527-2537: MvLimits, svt_av1_set_mv_search_range, svt_av1_set_subpel_mv_search_range -> (col_min, col_max,
     row_min, row_max)"""
-    col_min, col_max = -(((lc.mi_col + lc.mi_w) * 4) + 4), (lc.mi_cols - lc.mi_col) * 4 + 4
-    row_min, row_max = -(((lc.mi_row + lc.mi_h) * 4) + 4), (lc.mi_rows - lc.mi_row) * 4 + 4
-    r, c = lc.ref_row, lc.ref_col
-    col_min = max(col_min, max((c >> 3) - MAX_FULL_PEL_VAL + int(c & 7 != 0), (MV_LOW >> 3) + 1))
-    row_min = max(row_min, max((r >> 3) - MAX_FULL_PEL_VAL + int(r & 7 != 0), (MV_LOW >> 3) + 1))
-    col_max = min(col_max, min((c >> 3) + MAX_FULL_PEL_VAL, (MV_UPP >> 3) - 1))
-    row_max = min(row_max, min((r >> 3) + MAX_FULL_PEL_VAL, (MV_UPP >> 3) - 1))
-    m = MAX_FULL_PEL_VAL * 8
-    return (max(MV_LOW + 1, max(col_min * 8, c - m)), min(MV_UPP - 1, min(col_max * 8, c + m)),
-            max(MV_LOW + 1, max(row_min * 8, r - m)), min(MV_UPP - 1, min(row_max * 8, r + m)))
+    ref_mv = (lc.ref_row, lc.ref_col)
+    fp = md_search_cases.set_mv_search_range(md_search_cases.block_mv_limits(*lc[:6]), ref_mv)
+    return md_search_cases.set_subpel_mv_search_range(fp, ref_mv)
 
 
 def case_limits(c):
@@ -475,31 +449,16 @@ class Pin:
 
 
 # ---- descriptors for the device -------------------------------------------------------------------------------------------------
-class Arena:
-    """The pictures of a list of cases in one host buffer, each plane at its own byte offset with its own stride, and the cost tables
-    behind them.  layout(i) -> (offset shift in bytes, extra stride) lets a test ask for unaligned pointers and odd strides."""
+class Arena(md_search_cases.Arena):
+    """The pictures of a list of cases and the cost tables in one host buffer"""
 
     def __init__(self, cases, layout=lambda i: (0, 0)):
-        self.cases, self.planes, ab = cases, [], arena.Arena(tail=64)
+        super().__init__(cases, layout, fill=0)
+        self.planes = []
         for i, c in enumerate(cases):
-            shift, extra = layout(i)
-            entry = []
-            for name, plane in zip(("src", "ref"), pictures(c)):
-                stride = plane.shape[1] + extra
-                buf = np.full((plane.shape[0], stride), 0x5A, np.uint8)
-                buf[:, :plane.shape[1]] = plane
-                at = ab.add(f"{name} of case {i}", buf, align=64, gap=0, skew=shift)
-                entry.append((at + BORDER * stride + BORDER, stride))
-            self.planes.append(entry)
-        self.mvj, row, col = mv_cost_tables()
-        self.table_at = [ab.add(name, t, align=64, gap=0) - 4 * MV_LOW for name, t in (("mvcost row", row), ("mvcost col", col))]     # the centres
-        self.host = ab.build()
-
-    def job(self, base):
-        j = abi.SubpelJob()
-        j.mvjcost[:] = [int(v) for v in self.mvj]
-        j.mvcost[0], j.mvcost[1] = base + self.table_at[0], base + self.table_at[1]
-        return j
+            placed = [self.place(i, name, plane) for name, plane in zip(("src", "ref"), pictures(c))]
+            self.planes.append([(at + BORDER * stride + BORDER, stride) for at, stride, _ in placed])
+        self.finish()
 
     def descs(self, base):
         d = np.zeros(len(self.cases), abi.SUBPEL_DESC_DTYPE)

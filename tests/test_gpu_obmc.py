@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import md_search_cases as M
 import obmc_cases as O
 from arena import GUARD, check_containment
 from svtav1_hip import abi, device
@@ -19,32 +20,23 @@ def restated():
     return [O.Restated(c) for c in O.CASES]
 
 
-class Loaded:
+class Loaded(M.Loaded):
     """The samples and cost tables of a list of cases on the device, with room for every case's wsrc and mask"""
 
     def __init__(self, lib, cases, restated, layout=lambda i: (0, 0)):
-        self.lib, self.arena = lib, O.Arena(cases, layout, restated)
-        self.buf = device.DeviceBuffer(lib, self.arena.host.nbytes)
-        self.buf.upload(self.arena.host)
-        self.job = self.arena.job(self.buf.ptr)
-        self.target_descs, self.search_descs = self.arena.target_descs(self.buf.ptr), self.arena.search_descs(self.buf.ptr)
+        super().__init__(lib, O.Arena(cases, layout, restated), device.obmc_search_batch)
+        self.target_descs, self.search_descs = self.arena.target_descs(self.buf.ptr), self.descs
 
     def target(self, descs):
         """(status words, whether the guard bytes around them kept their fill)"""
-        out, guards = device.obmc_target_batch(self.lib, descs, fill=GUARD)
-        return out, bool((guards == GUARD).all())
+        return M.guarded(device.obmc_target_batch(self.lib, descs, fill=GUARD))
 
-    def search(self, descs, job=None):
-        out, guards = device.obmc_search_batch(self.lib, job or self.job, descs, fill=GUARD)
-        return out, bool((guards == GUARD).all())
+    search = M.Loaded.run
 
     def outputs(self, i):
         """(wsrc, mask) of case i as they are on the device now, int32 [h][w]"""
         c = self.arena.cases[i]
         return [self.buf.download(np.int32, (c.h, c.w), offset=at) for at in self.arena.outputs[i]]
-
-    def image(self):
-        return self.buf.download(np.uint8, (self.arena.host.nbytes,))
 
 
 @pytest.fixture(scope="module")
@@ -57,18 +49,14 @@ def loaded(hip, restated):
     return Loaded(hip, O.CASES, restated)
 
 
-@pytest.fixture(scope="module")
-def one_by_one(loaded):
-    """Every case in calls of its own, the target first and the search on what it left: (digests, records), computed once"""
-    digests, records = [], np.zeros(len(O.CASES), abi.OBMC_SEARCH_RESULT_DTYPE)
-    for i in range(len(O.CASES)):
-        status, clean = loaded.target(loaded.target_descs[i:i + 1])
-        assert clean and status[0] == abi.OBMC_OK, (i, status)
-        digests.append(tuple(O.digest(a) for a in loaded.outputs(i)))
-        rec, clean = loaded.search(loaded.search_descs[i:i + 1])
-        assert clean, i
-        records[i] = rec[0]
-    return digests, records
+def target_of_one(loaded, i):
+    """The target of case i in a call of its own: the digests of what it left, which the case's search then reads"""
+    status, clean = loaded.target(loaded.target_descs[i:i + 1])
+    assert clean and status[0] == abi.OBMC_OK, (i, status)
+    return tuple(O.digest(a) for a in loaded.outputs(i))
+
+
+one_by_one = M.one_by_one_fixture(before=target_of_one)      # (digests, records)
 
 
 def test_every_case_equals_the_fixture(one_by_one, gold):
@@ -82,7 +70,8 @@ def test_every_case_equals_the_fixture(one_by_one, gold):
 def test_all_cases_in_one_call(hip, restated, one_by_one):
     """The whole list shuffled in one call of each entry point on a fresh copy of the inputs, then every descriptor 27 times over: 8262
     descriptors, more than the 32 workgroups per compute unit that a 256-unit device's grid holds, so workgroups take a second descriptor.
-    Results as one by one; nothing outside the wsrc and mask arrays and the results is written."""
+    Then the 4 x 4 and 8 x 8 targets alone, more often than that grid holds workgroups, so that one workgroup of the single-wave target
+    kernel computes two.  Results as one by one; nothing outside the wsrc and mask arrays and the results is written."""
     digests, records = one_by_one
     ld = Loaded(hip, O.CASES, restated)
     order = np.random.RandomState(7).permutation(len(O.CASES))
@@ -100,6 +89,16 @@ def test_all_cases_in_one_call(hip, restated, one_by_one):
     assert clean and not status.any()
     out, clean = ld.search(ld.search_descs[many])
     assert clean and out.tobytes() == records[many].tobytes()
+    assert (ld.image() == after).all()
+    # the small blocks alone, so that a workgroup of the single-wave target kernel computes a second target: its grid holds 32 x 256
+    small = [i for i, c in enumerate(O.CASES) if (c.w, c.h) in ((4, 4), (8, 8))]
+    many = np.tile(small, 32 * 256 // len(small) + 1)
+    assert small and len(many) > 32 * 256
+    for at, nbytes in ld.arena.declared(small):      # poisoned, so that the pass has to write them again
+        device.check(hip, hip.svt_hip_memset(ld.buf.ptr + at, GUARD, nbytes, None), "svt_hip_memset")
+    assert not (ld.image() == after).all()
+    status, clean = ld.target(ld.target_descs[many])      # (the status words start as GUARD too: each is written by the workgroup that took it)
+    assert clean and not status.any()
     assert (ld.image() == after).all()
 
 
@@ -218,22 +217,9 @@ def test_bad_search_descriptors_among_good_ones(loaded, one_by_one):
 
 def test_call_level_errors(hip, loaded):
     """NULL job, descriptors, status words or results: SVT_HIP_ERR_BAD_PARAMETER; an empty batch is fine and writes nothing"""
-    res = device.DeviceBuffer(hip, 256)
-    res.fill(GUARD)
     d_search, d_target = device.upload_descriptors(hip, loaded.search_descs[:1]), device.upload_descriptors(hip, loaded.target_descs[:1])
-    f, g, job, r = hip.svt_hip_obmc_search_batch, hip.svt_hip_obmc_target_batch, C.byref(loaded.job), C.c_void_p(res.ptr)
-    p, q = C.c_void_p(d_search.ptr), C.c_void_p(d_target.ptr)
-    assert f(None, p, r, 1, None) == abi.SVT_HIP_ERR_BAD_PARAMETER and b"svt_hip_obmc_search_batch" in hip.svt_hip_last_error()
-    assert f(job, None, r, 1, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
-    assert f(job, p, None, 1, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
-    assert f(None, None, None, 0, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
-    assert f(job, p, r, 0, None) == abi.SVT_HIP_OK
-    assert g(None, r, 1, None) == abi.SVT_HIP_ERR_BAD_PARAMETER and b"svt_hip_obmc_target_batch" in hip.svt_hip_last_error()
-    assert g(q, None, 1, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
-    assert g(None, None, 0, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
-    assert g(q, r, 0, None) == abi.SVT_HIP_OK
-    device.check(hip, hip.svt_hip_stream_sync(None), "svt_hip_stream_sync")
-    assert (res.download(np.uint8, (256,)) == GUARD).all()
+    M.assert_call_level_errors(hip, "svt_hip_obmc_search_batch", abi.SVT_HIP_ERR_BAD_PARAMETER, [C.byref(loaded.job), C.c_void_p(d_search.ptr)])
+    M.assert_call_level_errors(hip, "svt_hip_obmc_target_batch", abi.SVT_HIP_ERR_BAD_PARAMETER, [C.c_void_p(d_target.ptr)])
 
 
 # ---- one OBMC candidate from neighbour vectors to final prediction ----------------------------------------------------------------

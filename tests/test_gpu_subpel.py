@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import md_search_cases as M
 import subpel_cases as S
 from arena import GUARD
 from svtav1_hip import abi, device
@@ -12,19 +13,9 @@ from svtav1_hip import abi, device
 pytestmark = pytest.mark.gpu
 
 
-class Loaded:
+def Loaded(lib, cases, layout=lambda i: (0, 0)):
     """The pictures and cost tables of a list of cases on the device"""
-
-    def __init__(self, lib, cases, layout=lambda i: (0, 0)):
-        self.lib, self.arena = lib, S.Arena(cases, layout)
-        self.buf = device.DeviceBuffer(lib, self.arena.host.nbytes)
-        self.buf.upload(self.arena.host)
-        self.job, self.descs = self.arena.job(self.buf.ptr), self.arena.descs(self.buf.ptr)
-
-    def run(self, descs):
-        """(records, whether the guard bytes around them kept their fill)"""
-        out, guards = device.subpel_search_batch(self.lib, self.job, descs, fill=GUARD)
-        return out, bool((guards == GUARD).all())
+    return M.Loaded(lib, S.Arena(cases, layout), device.subpel_search_batch)
 
 
 @pytest.fixture(scope="module")
@@ -37,15 +28,7 @@ def loaded(hip):
     return Loaded(hip, S.CASES)
 
 
-@pytest.fixture(scope="module")
-def one_by_one(loaded):
-    """Every case in a call of its own: the records, computed once"""
-    out = np.zeros(len(S.CASES), abi.SUBPEL_RESULT_DTYPE)
-    for i in range(len(S.CASES)):
-        rec, clean = loaded.run(loaded.descs[i:i + 1])
-        assert clean, i
-        out[i] = rec[0]
-    return out
+one_by_one = M.one_by_one_fixture()
 
 
 def test_every_case_equals_the_fixture(one_by_one, gold):
@@ -128,14 +111,5 @@ def test_bad_descriptors_among_good_ones(loaded, one_by_one):
 
 def test_call_level_errors(hip, loaded):
     """NULL job, descriptors or results: SVT_HIP_ERR_BAD_PARAMETER; an empty batch is fine and writes nothing"""
-    res = device.DeviceBuffer(hip, 256)
-    res.fill(GUARD)
     d_desc = device.upload_descriptors(hip, loaded.descs[:1])
-    f, job, p, r = hip.svt_hip_subpel_search_batch, C.byref(loaded.job), C.c_void_p(d_desc.ptr), C.c_void_p(res.ptr)
-    assert f(None, p, r, 1, None) == abi.SVT_HIP_ERR_BAD_PARAMETER and b"svt_hip_subpel_search_batch" in hip.svt_hip_last_error()
-    assert f(job, None, r, 1, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
-    assert f(job, p, None, 1, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
-    assert f(None, None, None, 0, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
-    assert f(job, p, r, 0, None) == abi.SVT_HIP_OK
-    device.check(hip, hip.svt_hip_stream_sync(None), "svt_hip_stream_sync")
-    assert (res.download(np.uint8, (256,)) == GUARD).all()
+    M.assert_call_level_errors(hip, "svt_hip_subpel_search_batch", abi.SVT_HIP_ERR_BAD_PARAMETER, [C.byref(loaded.job), C.c_void_p(d_desc.ptr)])

@@ -82,6 +82,25 @@ def test_mv_limits_are_the_fixtures(gold):
     assert lib.svt_hip_obmc_mv_limits(0, 0, 4, 4, 10, 10, C.byref(mv), out, None) == abi.SVT_HIP_ERR_BAD_PARAMETER
 
 
+def test_both_mv_limit_exports_apply_one_range_rule():
+    """Over the LIMIT_CASES of both families: the fp_limits of svt_hip_obmc_mv_limits are the full-pel range that svt_hip_subpel_mv_limits
+    narrows from the same inputs, through the shared restatement of svt_av1_set_mv_search_range, and each export is its own restatement: the
+    library's one copy of the rule, pinned from both sides."""
+    import md_search_cases as M
+    import subpel_cases as S
+    lib = abi.load()
+    cases = sorted({tuple(lc) for lc in S.LIMIT_CASES} | set(O.LIMIT_CASES))
+    assert S.LIMIT_CASES and O.LIMIT_CASES
+    for lc in cases:
+        raw, fp, sub, ref_mv = (C.c_int32 * 4)(), (C.c_int32 * 4)(), (C.c_int32 * 4)(), (lc[6], lc[7])
+        mv = abi.Mv(*ref_mv)
+        assert lib.svt_hip_obmc_mv_limits(*lc[:6], C.byref(mv), raw, fp) == abi.SVT_HIP_OK
+        assert lib.svt_hip_subpel_mv_limits(*lc[:6], C.byref(mv), sub) == abi.SVT_HIP_OK
+        assert tuple(fp) == M.set_mv_search_range(M.block_mv_limits(*lc[:6]), ref_mv), lc
+        assert tuple(sub) == M.set_subpel_mv_search_range(tuple(fp), ref_mv), lc
+        assert (tuple(raw), tuple(fp)) == O.mv_limits(*lc[:6], ref_mv) and tuple(sub) == S.mv_limits(S.LimitCase(*lc)), lc
+
+
 def test_restatement_matches_golden(gold, restated):
     """Without the reference: what every GPU test compares with is what the fixture holds."""
     for i, r in enumerate(restated):
