@@ -657,6 +657,80 @@ SVT_HIP_API int32_t svt_hip_obmc_search_batch(const SvtHipSubpelJob *job, const 
 SVT_HIP_API int32_t svt_hip_obmc_mv_limits(int32_t mi_row, int32_t mi_col, int32_t mi_width, int32_t mi_height, int32_t mi_rows,
                                            int32_t mi_cols, const SvtHipMv *ref_mv, int32_t raw_limits[4], int32_t fp_limits[4]);
 
+/* ---- Interpolation filter search of mode decision (Tier B) ---------------------------------------------------------------
+ * interpolation_filter_search (enc_inter_prediction.c:2413-2543) for a batch of luma blocks, bit-exact: for every pair of
+ * filter_sets (:2402-2412, [0] the vertical and [1] the horizontal filter; only the three equal pairs without dual filter) the
+ * switchable rate (svt_av1_get_switchable_rate :2157), the luma prediction of svt_aom_inter_prediction on its un-scaled path
+ * (av1_get_convolve_filter_params: the 4-tap banks for a side <= 4, sharp mapping to 4-tap regular there; get_conv_params_no_round; the sr
+ * family for one reference, the jnt family twice for a compound), the SSE of model_rd_for_sb (:2277) for plane 0, model_rd_from_sse (:2255)
+ * with the Laplacian tables of model_rd_norm (:2178), RDCOST and the smooth bias (:2520-2525); strict <, the first minimum wins.
+ * One descriptor is one luma block of one candidate; a call takes the candidates of a picture or of any part of it.
+ * NOT covered, the caller's: masked (wedge / difference-weighted) compounds, OBMC and inter-intra candidates (the reference folds them
+ * into the searched prediction at 8 bit); the packed 8 + 2 bit reference form; scaled references and intra block copy;
+ * av1_is_interp_needed (:2388), the vector clamp of compute_subpel_params (:3166-3177) and the derivation of the two contexts;
+ * chroma (the reference searches luma only); the encoder-side hook. */
+#define SVT_HIP_IFS_COMBOS 9           /* DUAL_FILTER_SET_SIZE */
+#define SVT_HIP_IFS_FILTER_BANKS 5     /* EIGHTTAP_REGULAR, EIGHTTAP_SMOOTH, MULTITAP_SHARP, then the two banks of av1_interp_4tap */
+#define SVT_HIP_IFS_CONTEXTS 16        /* SWITCHABLE_FILTER_CONTEXTS */
+/* SvtHipIfsResult.status */
+#define SVT_HIP_IFS_OK 0
+#define SVT_HIP_IFS_BAD_SIZE 1     /* w x h is none of the 22 block sizes */
+#define SVT_HIP_IFS_BAD_POINTER 2  /* src or ref0 NULL, or ref1 NULL with compound != 0 */
+#define SVT_HIP_IFS_BAD_PHASE 3    /* a phase above 15 */
+#define SVT_HIP_IFS_BAD_CTX 4      /* a context >= SVT_HIP_IFS_CONTEXTS */
+#define SVT_HIP_IFS_BAD_COMPOUND 5 /* compound 1 or above 3 */
+#define SVT_HIP_IFS_BAD_WEIGHT 6   /* compound 3 with fwd_offset + bck_offset != 16 */
+/* the SvtHipStatus of the call as the size_t that svt_hip_ifs_search_batch returns: its 32 bits, zero-extended */
+#define SVT_HIP_IFS_STATUS(s) ((size_t)(uint32_t)(s))
+
+typedef struct SvtHipIfsJob { /* host memory; the pointers in it are device memory.  What a picture's blocks share */
+    const int32_t *d_switchable_rate; /* [SVT_HIP_IFS_CONTEXTS][3]: md_rate_est_ctx->switchable_interp_fac_bitss */
+    const int16_t *d_filters;         /* [SVT_HIP_IFS_FILTER_BANKS][16][8], caller data: the library generates no filter */
+    uint32_t       full_lambda;       /* already divided as :2429-2430 (>> 2 * (bit_depth - 8) at 10 bit) */
+    int16_t        quantizer;         /* y_dequant_qtx[base_q_idx][1] of the search's bit depth */
+    uint8_t        bit_depth;         /* 8: uint8 samples; 10: plain uint16 samples */
+    uint8_t        enable_dual_filter;
+    uint8_t        subsampled_distortion, skip_sse_rd_model; /* InterpolationSearchCtrls */
+    uint16_t       smooth_bias_pct;   /* 0: none, else ifs_smooth_bias[picture_qp] (:2522-2525) */
+    uint8_t        pad_[4];
+} SvtHipIfsJob;
+
+typedef struct SvtHipIfsDesc {
+    const void *src;         /* the block's first sample in the source picture */
+    const void *ref0, *ref1; /* the reference sample that the block's (0,0) maps to after the whole-sample part of the clamped vector:
+                              * the contract of SvtHipConvolveDesc.src with 8 taps, so 3 samples are read to the left / above and 4 to
+                              * the right / below in a direction whose phase is not 0, none otherwise.  ref1 is read only when compound */
+    void       *dst;         /* NULL, or where the w x h prediction of the winning pair goes: byte for byte what svt_hip_convolve_batch
+                              * writes for the same inputs; nothing but that rectangle is written */
+    uint32_t    src_stride, ref0_stride, ref1_stride, dst_stride; /* in samples */
+    uint16_t    w, h;        /* one of the 22 block sizes, 4 x 4 .. 128 x 128 */
+    uint8_t     subpel_x0, subpel_y0, subpel_x1, subpel_y1; /* q4 phases 0 .. 15 of ref0 and ref1 */
+    uint8_t     compound;    /* 0 single reference, 2 plain average, 3 distance-weighted average (SvtHipConvolveDesc.compound) */
+    uint8_t     fwd_offset, bck_offset; /* compound 3: weights of ref0's and ref1's prediction, sum 16 */
+    uint8_t     ctx[2];      /* svt_aom_get_pred_context_switchable_interp for dir 0 and dir 1 */
+    uint8_t     pad_[3];
+} SvtHipIfsDesc;
+
+typedef struct SvtHipIfsResult {
+    uint64_t rd;              /* the winner's cost */
+    uint64_t sse;             /* the winner's sse as the distortion function returned it (before the bit-depth rounding) */
+    uint32_t interp_filters;  /* av1_make_interp_filters(y, x): y | x << 16 */
+    int32_t  switchable_rate;
+    uint8_t  best;            /* index of the winner in filter_sets */
+    uint8_t  status;          /* SVT_HIP_IFS_*; non-zero: every other field is 0 */
+    uint8_t  pad_[6];
+} SvtHipIfsResult;
+
+typedef struct SvtHipIfsTrace { /* every pair's figures; a pair that was not tested (dual filter off) is all ones */
+    uint64_t sse[SVT_HIP_IFS_COMBOS], rd[SVT_HIP_IFS_COMBOS];
+} SvtHipIfsTrace;
+/* d_result[i] (and d_trace[i] unless d_trace is NULL) belongs to d_desc[i]; a bad descriptor gets its status and zeroes in d_result,
+ * zeroes in d_trace, and touches nothing else.  SVT_HIP_IFS_STATUS(SVT_HIP_ERR_BAD_PARAMETER), before any device is looked for, for a NULL job,
+ * d_desc or d_result, a NULL table in the job and a bit depth other than 8 / 10; n == 0 is SVT_HIP_OK and launches nothing.
+ * Asynchronous on `stream`. */
+SVT_HIP_API size_t svt_hip_ifs_search_batch(const SvtHipIfsJob *job, const SvtHipIfsDesc *d_desc, SvtHipIfsResult *d_result,
+                                            SvtHipIfsTrace *d_trace, uint32_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

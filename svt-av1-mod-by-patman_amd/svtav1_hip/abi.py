@@ -681,7 +681,43 @@ SUBPEL_DESC_DTYPE = record_dtype(SubpelDesc)       # numpy views of arrays of th
 SUBPEL_RESULT_DTYPE = record_dtype(SubpelResult)
 
 
-FPEL_MVP, FPEL_SQ, FPEL_NSQ, FPEL_PME = range(4)                                  # SVT_HIP_FPEL_* (include/svt_hip_inter.h)
+IFS_COMBOS, IFS_FILTER_BANKS, IFS_CONTEXTS = 9, 5, 16                            # SVT_HIP_IFS_* (include/svt_hip_inter.h)
+IFS_OK, IFS_BAD_SIZE, IFS_BAD_POINTER, IFS_BAD_PHASE, IFS_BAD_CTX, IFS_BAD_COMPOUND, IFS_BAD_WEIGHT = range(7)
+
+
+def ifs_status(status):
+    """SVT_HIP_IFS_STATUS: a SvtHipStatus as the size_t that svt_hip_ifs_search_batch returns"""
+    return status & 0xFFFFFFFF
+
+
+class IfsJob(C.Structure):               # SvtHipIfsJob
+    _fields_ = [("d_switchable_rate", C.c_void_p), ("d_filters", C.c_void_p), ("full_lambda", C.c_uint32), ("quantizer", C.c_int16),
+                ("bit_depth", C.c_uint8), ("enable_dual_filter", C.c_uint8), ("subsampled_distortion", C.c_uint8),
+                ("skip_sse_rd_model", C.c_uint8), ("smooth_bias_pct", C.c_uint16), ("pad_", C.c_uint8 * 4)]
+
+
+class IfsDesc(C.Structure):              # SvtHipIfsDesc
+    _fields_ = [("src", C.c_void_p), ("ref0", C.c_void_p), ("ref1", C.c_void_p), ("dst", C.c_void_p), ("src_stride", C.c_uint32),
+                ("ref0_stride", C.c_uint32), ("ref1_stride", C.c_uint32), ("dst_stride", C.c_uint32), ("w", C.c_uint16), ("h", C.c_uint16),
+                ("subpel_x0", C.c_uint8), ("subpel_y0", C.c_uint8), ("subpel_x1", C.c_uint8), ("subpel_y1", C.c_uint8),
+                ("compound", C.c_uint8), ("fwd_offset", C.c_uint8), ("bck_offset", C.c_uint8), ("ctx", C.c_uint8 * 2), ("pad_", C.c_uint8 * 3)]
+
+
+class IfsResult(C.Structure):            # SvtHipIfsResult
+    _fields_ = [("rd", C.c_uint64), ("sse", C.c_uint64), ("interp_filters", C.c_uint32), ("switchable_rate", C.c_int32), ("best", C.c_uint8),
+                ("status", C.c_uint8), ("pad_", C.c_uint8 * 6)]
+
+
+class IfsTrace(C.Structure):             # SvtHipIfsTrace
+    _fields_ = [("sse", C.c_uint64 * 9), ("rd", C.c_uint64 * 9)]
+
+
+IFS_DESC_DTYPE = record_dtype(IfsDesc)
+IFS_RESULT_DTYPE = record_dtype(IfsResult)
+IFS_TRACE_DTYPE = record_dtype(IfsTrace)
+
+
+FPEL_MVP, FPEL_SQ, FPEL_NSQ, FPEL_PME = range(4)                                 # SVT_HIP_FPEL_* (include/svt_hip_inter.h)
 FPEL_SAD, FPEL_VAR, FPEL_SSD = range(3)
 FPEL_MAX_MV, FPEL_MAX_MVP, FPEL_TILE, FPEL_MAX_EXTENT = 6, 4, 32, 4095
 (FPEL_OK, FPEL_BAD_SIZE, FPEL_BAD_POINTER, FPEL_BAD_MODE, FPEL_BAD_DIST, FPEL_BAD_COST, FPEL_BAD_COUNT, FPEL_BAD_STEP,

@@ -233,6 +233,22 @@ def subpel_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
     return _search_batch(lib, "svt_hip_subpel_search_batch", abi.SubpelResult, abi.SUBPEL_RESULT_DTYPE, job, descs, stream, guard, fill)
 
 
+def ifs_search_batch(lib, job, descs, trace=True, stream=None, guard=64, fill=0xA5):
+    """svt_hip_ifs_search_batch over a record array of abi.IFS_DESC_DTYPE (or a list of abi.IfsDesc) under the abi.IfsJob `job` (one call).
+    Returns (results as a record array of abi.IFS_RESULT_DTYPE, the trace as one of abi.IFS_TRACE_DTYPE or None, the `guard` bytes before
+    and after the results and the trace: still `fill` if untouched)."""
+    n = len(descs)
+    d_desc = upload_descriptors(lib, descs, stream)
+    d_out = Guarded(lib, C.sizeof(abi.IfsResult) * n, guard, fill, stream)
+    d_trace = Guarded(lib, C.sizeof(abi.IfsTrace) * n, guard, fill, stream) if trace else None
+    check(lib, lib.svt_hip_ifs_search_batch(C.byref(job), d_desc.ptr, d_out.ptr, d_trace.ptr if trace else None, n, stream), "svt_hip_ifs_search_batch")
+    out, guards = d_out.read(abi.IFS_RESULT_DTYPE)
+    if not trace:
+        return out, None, guards
+    tr, tr_guards = d_trace.read(abi.IFS_TRACE_DTYPE)
+    return out, tr, np.concatenate([guards, tr_guards])
+
+
 def fpel_search_batch(lib, job, descs, stream=None, guard=64, fill=0xA5):
     """svt_hip_fpel_search_batch over a record array of abi.FPEL_DESC_DTYPE (or a list of abi.FpelDesc) under the abi.SubpelJob `job`
     (one call).  Returns (results as a record array of abi.FPEL_RESULT_DTYPE, the `guard` bytes before and after them: still `fill` if
